@@ -47,6 +47,61 @@ WORKLOADS = {
     'c1': ('transport mpLP of the reference tutorial (2 variables, 2 parameters); full tree', lambda pg: pg.transport_mplp_data(), None),
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs: array bytes in all (with the .npy headers the files stay under 64 MB)
+
+
+def dump_outputs(sol, out_dir):
+    """--dump-outputs: the Solution one timed step returned, as float64 .npy files under out_dir, so that two builds can be
+    compared output for output.  Regions are sorted by active set (the order in which the device appends them is not fixed);
+    per region the law x = A theta + b, the multipliers lambda = C theta + d, the region E theta <= f and its index sets, padded
+    to the largest region (-1 in index files, 0 in C / d).  E / f of all regions are stacked, E_rows holds the row offsets.
+    Beyond DUMP_BUDGET_BYTES a fixed, seeded sample of the sorted regions is written; region_index holds its positions."""
+    sol.materialize()
+    regs = sorted(sol.critical_regions, key=lambda r: (len(r.active_set), tuple(int(v) for v in r.active_set)))
+    n_t = sol.theta_dim()
+    # per region: A, b, C, d, E, f and the four padded index rows (upper bound of the padding: the largest region's widths)
+    mats = [(numpy.asarray(r.A, float).reshape(-1, n_t), numpy.asarray(r.b, float).ravel(), numpy.asarray(r.C, float).reshape(-1, n_t),
+             numpy.asarray(r.d, float).ravel(), numpy.asarray(r.E, float).reshape(-1, n_t), numpy.asarray(r.f, float).ravel()) for r in regs]
+    sets = [(list(r.active_set), list(r.omega_set), list(r.lambda_set), list(r.regular_set[1]) if r.regular_set else []) for r in regs]
+    wide = [max([len(s[i]) for s in sets], default=0) for i in range(4)]
+    n_x, k_c = max([m[0].shape[0] for m in mats], default=0), max([m[2].shape[0] for m in mats], default=0)
+    fixed = 8 * (n_x * (n_t + 1) + k_c * (n_t + 1) + sum(wide) + 2)
+    sizes = numpy.array([fixed + 8 * m[4].shape[0] * (n_t + 1) for m in mats], dtype=numpy.int64)
+    pick = numpy.arange(len(regs))
+    if sizes.sum() > DUMP_BUDGET_BYTES:
+        n = int(len(regs) * DUMP_BUDGET_BYTES / sizes.sum())
+        while True:
+            pick = numpy.sort(numpy.random.default_rng(0).choice(len(regs), size=n, replace=False))
+            if sizes[pick].sum() <= DUMP_BUDGET_BYTES:
+                break
+            n = int(n * 0.95)
+    R = len(pick)
+
+    def padded(i, fill):
+        a = numpy.full((R, wide[i]), fill, dtype=numpy.float64)
+        for row, j in enumerate(pick):
+            a[row, :len(sets[j][i])] = sets[j][i]
+        return a
+
+    C, d = numpy.zeros((R, k_c, n_t)), numpy.zeros((R, k_c))
+    for row, j in enumerate(pick):
+        C[row, :mats[j][2].shape[0]], d[row, :mats[j][3].shape[0]] = mats[j][2], mats[j][3]
+    n_e = numpy.array([mats[j][4].shape[0] for j in pick], dtype=numpy.int64)
+    arrays = {
+        'region_index': pick.astype(numpy.float64),
+        'active_set': padded(0, -1), 'omega_set': padded(1, -1), 'lambda_set': padded(2, -1), 'regular_set': padded(3, -1),
+        'A': numpy.array([mats[j][0] for j in pick], dtype=numpy.float64).reshape(R, n_x, n_t),
+        'b': numpy.array([mats[j][1] for j in pick], dtype=numpy.float64).reshape(R, n_x),
+        'C': C, 'd': d,
+        'E': numpy.concatenate([mats[j][4] for j in pick]) if R else numpy.zeros((0, n_t)),
+        'f': numpy.concatenate([mats[j][5] for j in pick]) if R else numpy.zeros(0),
+        'E_rows': numpy.concatenate([[0], numpy.cumsum(n_e)]).astype(numpy.float64),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        numpy.save(os.path.join(out_dir, name + '.npy'), a)
+    return {'dir': out_dir, 'regions': R, 'regions_in_solution': len(regs), 'bytes': int(sum(a.nbytes for a in arrays.values())),
+            'files': sorted(name + '.npy' for name in arrays)}
 
 
 def program_from_data(d, device=0):
@@ -165,7 +220,10 @@ def main():
     ap.add_argument('--dist-single', action='store_true', help='run the multi-GPU driver with a process group of one rank (self-test)')
     ap.add_argument('--sweep', action='store_true', help='shape sweep over the target class (n_x <= 20, n_theta <= 10): one JSON line with a row per shape (tools/shape_sweep.py); not the headline')
     ap.add_argument('--deep', type=int, default=0, help='also time the six-level variant of c4 on one GPU (the scaling workload the multi-GPU runs report under extra)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the solution of the last timed step as DIR/<name>.npy (float64, under 64 MB in all; see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     if args.sweep:
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
         import shape_sweep
@@ -271,11 +329,16 @@ def main():
         return el, profs, ms_list, last
 
     elapsed_nogc = None
+    dumped = None
     if args.events_in_value:
         elapsed, profiles, step_ms, sol = timed_region(True)
         elapsed_events = elapsed
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(sol, args.dump_outputs)
     else:
         elapsed, _, step_ms, sol = timed_region(False)
+        if args.dump_outputs and rank == 0:
+            dumped = dump_outputs(sol, args.dump_outputs)     # the last step of the region `value` comes from, written after its timing
         del sol
         step(None)      # (hand-over: the region objects of the last untimed-events step are released outside the next region)
         elapsed_events, profiles, _, sol = timed_region(True)
@@ -490,6 +553,8 @@ def main():
         if hasattr(cr, 'materialize'):
             cr.materialize()
     out['materialize_all_regions_ms'] = 1e3 * (time.perf_counter() - t_mat)
+    if dumped is not None:
+        out['dumped_outputs'] = dumped
     # regions/s both ways: `regions_per_s` counts the lazy CriticalRegion views the solve returns; the materialised figure adds the
     # time to cut every field of every region out of the level arrays to each step
     out['regions_per_s_lazy'] = out['regions_per_s']

@@ -370,8 +370,9 @@ def _solve_distributed_guarded(engine, program, group, profile, collect_regions,
         # the abandoned solve left work in flight: host copies into pooled page-locked arrays, all-gathers on RCCL's stream.  Everything
         # is waited for before its buffers can be handed out again, the repeat runs with the region stage behind the (x,theta) stage, and
         # the faster form is restored afterwards
-        if torch.cuda.is_available() and getattr(engine, 'device', None) is not None:
-            torch.cuda.synchronize(engine.device)
+        device = getattr(engine, 'device', None)
+        if device is not None and torch.device(device).type == 'cuda':      # (an engine on CPU tensors has nothing in flight)
+            torch.cuda.synchronize(device)
         if hasattr(engine, 'set_region_overlap'):
             engine.set_region_overlap(False)
         if profile is not None:

@@ -1,7 +1,8 @@
 import sys, time, warnings, cProfile, pstats
-sys.path.insert(0, '/root/repo')
 import os
-os.chdir(os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+os.chdir(ROOT)
 sys.path.insert(0, '.')
 from ppopt_amd import MPMIQP_Program
 from ppopt_amd.problem_generator import generate_mpmiqp_data
