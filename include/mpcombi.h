@@ -436,6 +436,27 @@ int mpc_lp_solve_batch(int32_t device, int64_t n_lp, int32_t m, int32_t n, const
 int mpc_qp_solve_batch(mpc_handle *h, int64_t m, const double *theta_host, int32_t *status, double *x, double *lambda,
                        uint8_t *active, int32_t *iters);
 
+/* ---- the mixed-integer QP at fixed parameter points, batched: one wavefront per (point, binary fixation) pair -------------- */
+/* MPMIQP_Program.solve_theta / solve_theta_batch (reference: mpmiqp_program.py:55-69 -> Solver.solve_miqp) for a positive definite
+ * continuous Hessian Q_c.  With the binaries y fixed to leaf l and z = [1; theta; y] (n_z = 1 + n_t + n_b), the continuous QP is
+ * the LCP  s = UV z + W lambda  of mpc_qp_solve_batch with the same W = A_c Q_c^-1 A_c' for every pair; its minimiser is
+ * x_c = X0 z - Gt' lambda and its objective, constants included, 1/2 x_c' Q_c x_c + (G z)' x_c + 1/2 z' K z.
+ *   W n_c x n_c, UV n_c x n_z, X0 n_x_c x n_z, Gt n_c x n_x_c, Q_c n_x_c x n_x_c, G n_x_c x n_z, K n_z x n_z (n_x_c = n_x - n_b);
+ *   the first n_eq of the n_c LCP rows are equalities; lcp_row[n_c]: the program row (of n_rows) each LCP row is.
+ *   check n_check x n_z, check_eq[n_check]: rows decided on z alone -- a pair with  check z < -MPC_MIQP_CHECK_TOL  on an inequality
+ *   or  |check z| > MPC_MIQP_CHECK_TOL  on an equality row is infeasible without a pivot.
+ *   binary_index[n_b]: positions of the binaries among the n_x variables; Y n_leaves x n_b: the fixations; theta m x n_t.
+ * Per point the lowest objective among the optimal pairs wins, the lowest leaf on ties.  Outputs (host): status[m] (0 optimal,
+ * 1 infeasible at that point, 3 some pair hit the iteration limit), leaf[m] (-1 unless optimal), obj[m] (NaN unless optimal);
+ * x (m x n_x: x_c with y spliced in, NaN unless optimal), lambda (m x n_rows, 0 on rows outside the LCP) and active (m x n_rows
+ * bytes, tight LCP rows) may be NULL.  Device memory: 12 bytes per (point, leaf) pair; the caller bounds m. */
+#define MPC_MIQP_CHECK_TOL 1e-9
+int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, int32_t n_x, int32_t n_t, int32_t n_b, const double *W,
+                         const double *UV, const double *X0, const double *Gt, const double *Q_c, const double *G, const double *K,
+                         int32_t n_check, const double *check, const uint8_t *check_eq, const int32_t *binary_index, int32_t n_rows,
+                         const int32_t *lcp_row, int64_t n_leaves, const double *Y, int64_t m, const double *theta, int32_t *status,
+                         int32_t *leaf, double *obj, double *x, double *lambda, uint8_t *active);
+
 /* ---- Chebyshev centre and radius of every facet of a batch of polytopes, one wavefront per facet ------------------------- */
 /* Replaces get_facet_centers (mp_solvers/solver_utils.py:204-250; one chebyshev_ball LP per facet, utils/chebyshev_ball.py:10-63)
  * of the geometric algorithm.  ef_rows: stacked rows [f | E] (n_t + 1 doubles each) of all polytopes, row_off[n_regions + 1];

@@ -201,6 +201,9 @@ def load():
         'mpc_lp_solve_batch': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _dp,
                                               ctypes.c_int32, _dp, ctypes.c_int32, _dp, ctypes.c_int32, _u8p, _ip, _dp,
                                               _dp, _ip]),
+        'mpc_miqp_solve_batch': (ctypes.c_int, [ctypes.c_int32] + [ctypes.c_int32] * 5 + [_dp] * 7 + [ctypes.c_int32, _dp, _u8p, _ip,
+                                                ctypes.c_int32, _ip, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _ip, _ip, _dp, _dp,
+                                                _dp, _u8p]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -218,7 +221,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_frontier_get', 'mpc_pruned_clear', 'mpc_pruned_add', 'mpc_pruned_add_device',
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
-                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch']
+                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -913,6 +916,34 @@ def lp_solve_batch(A, b, c, eq_flags, device: int = 0, want_x: bool = True):
     if rc != MPC_OK:
         raise MpcError(f'mpc_lp_solve_batch failed ({rc}): {L.mpc_last_global_error().decode()}')
     return status, x, obj, it
+
+
+def miqp_solve_batch(blocks: dict, Y: numpy.ndarray, theta: numpy.ndarray, device: int = 0, want_x: bool = True):
+    """The mixed-integer QP at every row of theta (include/mpcombi.h, mpc_miqp_solve_batch): the LCP of every (point, leaf) pair,
+    the best leaf per point (lowest objective, lowest leaf on ties), the winners' outputs.  ``blocks``: the arrays of
+    MPMIQP_Program.theta_blocks; Y [n_leaves, n_b] the fixations.  Device memory is 12 bytes per (point, leaf): the caller bounds
+    len(theta).  Returns (status [m], leaf [m], obj [m], x [m, n_x] or None, lambda [m, n_rows] or None, active [m, n_rows] or None)."""
+    L = load()
+    B = blocks
+    n_c, n_eq, n_x, n_t, n_b, n_rows = (int(B[k]) for k in ('n_c', 'n_eq', 'n_x', 'n_t', 'n_b', 'n_rows'))
+    arr = {k: _f64(B[k]) for k in ('W', 'UV', 'X0', 'Gt', 'Q_c', 'G', 'K', 'check')}
+    check_eq = numpy.ascontiguousarray(B['check_eq'], dtype=numpy.uint8)
+    bins = numpy.ascontiguousarray(B['binary_index'], dtype=numpy.int32)
+    lcp_row = numpy.ascontiguousarray(B['lcp_row'], dtype=numpy.int32)
+    Y = _f64(numpy.asarray(Y, dtype=numpy.float64).reshape(-1, n_b))
+    th = _f64(numpy.asarray(theta, dtype=numpy.float64).reshape(-1, n_t))
+    m, n_leaves = len(th), len(Y)
+    status, leaf, obj = numpy.zeros(m, dtype=numpy.int32), numpy.zeros(m, dtype=numpy.int32), numpy.zeros(m)
+    x = numpy.zeros((m, n_x)) if want_x else None
+    lam = numpy.zeros((m, n_rows)) if want_x else None
+    act = numpy.zeros((m, n_rows), dtype=numpy.uint8) if want_x else None
+    p = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+    rc = L.mpc_miqp_solve_batch(int(device), n_c, n_eq, n_x, n_t, n_b, *(p(arr[k]) for k in ('W', 'UV', 'X0', 'Gt', 'Q_c', 'G', 'K')),
+                                int(arr['check'].shape[0]), p(arr['check']), p(check_eq, _u8p), p(bins, _ip), n_rows, p(lcp_row, _ip),
+                                n_leaves, p(Y), m, p(th), p(status, _ip), p(leaf, _ip), p(obj), p(x), p(lam), p(act, _u8p))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_miqp_solve_batch failed ({rc}): {L.mpc_last_global_error().decode()}')
+    return status, leaf, obj, x, lam, act
 
 
 def facet_centres(ef_rows: numpy.ndarray, row_off: numpy.ndarray, device: int = 0):

@@ -4723,6 +4723,123 @@ extern "C" int mpc_qp_solve_batch(mpc_handle *h, int64_t m, const double *theta,
     return rc;
 }
 
+// ---- the MIQP at fixed parameter points: every (point, fixation) pair, pick, winners (qp.hpp) ------------------------------------
+extern "C" int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, int32_t n_x, int32_t n_t, int32_t n_b, const double *W,
+                                    const double *UV, const double *X0, const double *Gt, const double *Q_c, const double *G, const double *K,
+                                    int32_t n_check, const double *check, const uint8_t *check_eq, const int32_t *binary_index, int32_t n_rows,
+                                    const int32_t *lcp_row, int64_t n_leaves, const double *Y, int64_t m, const double *theta, int32_t *status,
+                                    int32_t *leaf, double *obj, double *x, double *lambda, uint8_t *active) {
+    const int nxc = n_x - n_b, nz = 1 + n_t + n_b;
+    if (n_c < 0 || n_eq < 0 || n_eq > n_c || n_t < 0 || n_b < 0 || nxc < 1 || n_check < 0 || n_rows < n_c || n_leaves < 0 || m < 0)
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad sizes");
+    if ((n_c && (!W || !UV || !Gt || !lcp_row)) || !X0 || !Q_c || !G || !K || (n_check && (!check || !check_eq)) || (n_b && !binary_index) ||
+        (n_leaves && n_b && !Y) || (m && (!status || !leaf || !obj)) || (m && n_t && !theta))
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: missing array");
+    // every index the kernels write through is checked here
+    std::vector<int32_t> cont;
+    {
+        std::vector<char> is_bin((size_t)n_x, 0);
+        for (int k = 0; k < n_b; ++k) {
+            if (binary_index[k] < 0 || binary_index[k] >= n_x || is_bin[binary_index[k]]) return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad binary_index");
+            is_bin[binary_index[k]] = 1;
+        }
+        for (int a = 0; a < n_x; ++a) if (!is_bin[a]) cont.push_back(a);
+        for (int i = 0; i < n_c; ++i) if (lcp_row[i] < 0 || lcp_row[i] >= n_rows) return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad lcp_row");
+    }
+    if (m == 0) return MPC_OK;
+    if (n_leaves == 0) {
+        for (long long p = 0; p < m; ++p) { status[p] = QP_INFEASIBLE; leaf[p] = -1; obj[p] = NAN; }
+        if (x) std::fill(x, x + (size_t)m * n_x, NAN);
+        if (lambda) std::fill(lambda, lambda + (size_t)m * n_rows, 0.0);
+        if (active) std::fill(active, active + (size_t)m * n_rows, (uint8_t)0);
+        return MPC_OK;
+    }
+    int ndev = 0;
+    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const int ld = odd_at_least(n_c + 3);
+    // the k_qp_batch tableau and multipliers, then z and x
+    const size_t lds = ((size_t)(n_c + 1) * ld + n_c + nz + nxc) * sizeof(double) + (size_t)(ld + 1 + 2 * (n_c + 2) + 2) * sizeof(int32_t) + 16;
+    if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "the QP tableau (n_c x n_c) does not fit the 160 KiB LDS of one CU");
+    for (const void *k : {reinterpret_cast<const void *>(k_miqp_pairs), reinterpret_cast<const void *>(k_miqp_winners)})
+        if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // constant blocks in one allocation: W UV X0 Gt Qc G K CK Y theta | ck_eq | cont bin lcp_row
+    const size_t nW = (size_t)n_c * n_c, nUV = (size_t)n_c * nz, nX0 = (size_t)nxc * nz, nGt = (size_t)n_c * nxc, nQ = (size_t)nxc * nxc;
+    const size_t nG = (size_t)nxc * nz, nK = (size_t)nz * nz, nCK = (size_t)n_check * nz, nY = (size_t)n_leaves * n_b, nTh = (size_t)m * n_t;
+    const size_t nd = nW + nUV + nX0 + nGt + nQ + nG + nK + nCK + nY + nTh, ni = (size_t)nxc + n_b + n_c;
+    std::vector<double> hd(std::max<size_t>(nd, 1));
+    std::vector<int32_t> hi(std::max<size_t>(ni, 1));
+    size_t o = 0;
+    auto put = [&](const double *src, size_t n) { const size_t at = o; if (n) std::copy(src, src + n, hd.begin() + at); o += n; return at; };
+    const size_t oW = put(W, nW), oUV = put(UV, nUV), oX0 = put(X0, nX0), oGt = put(Gt, nGt), oQ = put(Q_c, nQ), oG = put(G, nG), oK = put(K, nK);
+    const size_t oCK = put(check, nCK), oY = put(Y, nY), oTh = put(theta, nTh);
+    std::copy(cont.begin(), cont.end(), hi.begin());
+    if (n_b) std::copy(binary_index, binary_index + n_b, hi.begin() + nxc);
+    if (n_c) std::copy(lcp_row, lcp_row + n_c, hi.begin() + nxc + n_b);
+    const long long n_pairs = m * n_leaves;
+    DevBuf d_d, d_i, d_ck, d_ps, d_po, d_st, d_leaf, d_best, d_obj, d_x, d_l, d_a, d_w;
+    int rc = MPC_OK;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
+    chk(d_d.ensure(hd.size() * 8, nullptr)); chk(d_i.ensure(hi.size() * 4, nullptr)); chk(d_ck.ensure(std::max(n_check, 1), nullptr));
+    chk(d_ps.ensure((size_t)n_pairs * 4, nullptr)); chk(d_po.ensure((size_t)n_pairs * 8, nullptr));
+    chk(d_st.ensure((size_t)m * 4, nullptr)); chk(d_leaf.ensure((size_t)m * 4, nullptr)); chk(d_best.ensure((size_t)m * 8, nullptr));
+    chk(d_obj.ensure((size_t)m * 8, nullptr)); chk(d_w.ensure(16, nullptr));
+    if (x) chk(d_x.ensure((size_t)m * n_x * 8, nullptr));
+    if (lambda) chk(d_l.ensure((size_t)m * n_rows * 8, nullptr));
+    if (active) chk(d_a.ensure((size_t)m * n_rows, nullptr));
+    hipStream_t st = nullptr;
+    chk(pooled_stream(&st));
+    if (e == hipSuccess) {
+        chk(hipMemcpyAsync(d_d.p, hd.data(), hd.size() * 8, hipMemcpyHostToDevice, st));
+        chk(hipMemcpyAsync(d_i.p, hi.data(), hi.size() * 4, hipMemcpyHostToDevice, st));
+        if (n_check) chk(hipMemcpyAsync(d_ck.p, check_eq, (size_t)n_check, hipMemcpyHostToDevice, st));
+        chk(hipMemsetAsync(d_w.p, 0, 16, st));
+        if (x) chk(hipMemsetAsync(d_x.p, 0xff, (size_t)m * n_x * 8, st));   // all-ones bytes: a NaN where no pair is optimal
+        if (lambda) chk(hipMemsetAsync(d_l.p, 0, (size_t)m * n_rows * 8, st));
+        if (active) chk(hipMemsetAsync(d_a.p, 0, (size_t)m * n_rows, st));
+    }
+    if (e == hipSuccess) {
+        const double *dd = d_d.as<double>();
+        const int32_t *di = d_i.as<int32_t>();
+        MiqpBlocks B{n_c, n_eq, nxc, n_t, n_b, nz, n_check, n_x, n_rows, dd + oW, dd + oUV, dd + oX0, dd + oGt, dd + oQ, dd + oG, dd + oK,
+                     dd + oCK, dd + oY, dd + oTh, d_ck.as<uint8_t>(), di, di + nxc, di + nxc + n_b};
+        const int n_cu = std::max(cu_count(device), 1), per_cu = waves_per_cu((int)lds);
+        unsigned int *work = d_w.as<unsigned int>();
+        hipLaunchKernelGGL(k_miqp_pairs, dim3((unsigned)std::min<long long>(n_pairs, (long long)n_cu * per_cu)), dim3(64), lds, st, B, (long long)m,
+                           (long long)n_leaves, ld, d_ps.as<int32_t>(), d_po.as<double>(), work);
+        chk(hipGetLastError());
+        hipLaunchKernelGGL(k_miqp_pick, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (long long)m, (long long)n_leaves, d_ps.as<int32_t>(),
+                           d_po.as<double>(), d_st.as<int32_t>(), d_leaf.as<int32_t>(), d_best.as<double>());
+        chk(hipGetLastError());
+        hipLaunchKernelGGL(k_miqp_winners, dim3((unsigned)std::min<long long>(m, (long long)n_cu * per_cu)), dim3(64), lds, st, B, (long long)m, ld,
+                           d_leaf.as<int32_t>(), d_obj.as<double>(), x ? d_x.as<double>() : (double *)nullptr, lambda ? d_l.as<double>() : (double *)nullptr,
+                           active ? d_a.as<uint8_t>() : (uint8_t *)nullptr, work + 2);
+        chk(hipGetLastError());
+        chk(hipMemcpyAsync(status, d_st.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(leaf, d_leaf.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        chk(hipMemcpyAsync(obj, d_best.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+        if (x) chk(hipMemcpyAsync(x, d_x.p, (size_t)m * n_x * 8, hipMemcpyDeviceToHost, st));
+        if (lambda) chk(hipMemcpyAsync(lambda, d_l.p, (size_t)m * n_rows * 8, hipMemcpyDeviceToHost, st));
+        if (active) chk(hipMemcpyAsync(active, d_a.p, (size_t)m * n_rows, hipMemcpyDeviceToHost, st));
+    }
+    if (st) { hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess && es != hipSuccess) e = es; }
+    std::vector<double> again;
+    if (e == hipSuccess) {
+        // the winner pass repeats the arithmetic of pass 1: its objective must be the one that won, bit for bit
+        again.resize((size_t)m);
+        e = hipMemcpy(again.data(), d_obj.p, (size_t)m * 8, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) { rc = fail(nullptr, MPC_ERR_HIP, std::string("mpc_miqp_solve_batch: ") + hipGetErrorString(e)); (void)hipDeviceSynchronize(); }
+    else
+        for (long long p = 0; p < m; ++p)
+            if (leaf[p] >= 0 && std::memcmp(&again[(size_t)p], &obj[p], 8) != 0) { rc = fail(nullptr, MPC_ERR_STATE, "mpc_miqp_solve_batch: the winner pass disagrees with pass 1"); break; }
+    if (st) return_stream(st);
+    for (DevBuf *q : {&d_d, &d_i, &d_ck, &d_ps, &d_po, &d_st, &d_leaf, &d_best, &d_obj, &d_x, &d_l, &d_a, &d_w}) q->release();
+    return rc;
+}
+
 struct mpc_locator {
     int device = 0, n_x = 0, n_t = 0;
     long long n_regions = 0, n_rows = 0;

@@ -16,6 +16,7 @@
 // of the two.  Ratio ties are broken in favour of z0's row, then by the lowest variable id.
 #pragma once
 #include "lp_engine.hpp"
+#include "../../include/mpcombi.h"
 
 namespace mpc {
 
@@ -27,6 +28,103 @@ __device__ __forceinline__ int wave_max_i(int v) {
     return v;
 }
 
+// ---- the LCP of one point: dictionary, complementary pivoting, multipliers (shared by k_qp_batch and the MIQP kernels) ----
+// Dictionary: s_i = q_i - sum_j (-W_ij) lambda_j - (-1) z0 with q_i = qf(i); the cost row (index nc) is unused.
+template <class QF>
+__device__ inline void qp_lcp_dict(Lp &lp, int nc, int n_eq, const double *__restrict__ W, QF qf) {
+    const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc;
+    double *T = lp.T;
+    lp.m = nc; lp.n = 0; lp.na = nc + 1; lp.iters = 0; lp.max_iter = 50 * nc + 100; lp.growth = 0.0;
+    wave_sync();
+    for (int i = lane; i <= nc; i += 64) {
+        double *Ti = T + (size_t)i * ld;
+        double q = 0.0;
+        if (i < nc) q = qf(i);
+        Ti[0] = q;
+        for (int j = 0; j < nc; ++j) Ti[1 + j] = i < nc ? -W[(size_t)i * nc + j] : 0.0;
+        Ti[nc + 1] = (i >= n_eq && i < nc) ? -1.0 : 0.0;
+        if (i < nc) { lp.rowvar[i] = nc + i; lp.rowkind[i] = i < n_eq ? RK_EQ : RK_INEQ; }
+    }
+    for (int j = lane; j <= nc + 1; j += 64) lp.colvar[j] = j == 0 ? -1 : (j <= nc ? j - 1 : ID_Z0);
+    wave_sync();
+}
+
+// Lemke's method on the dictionary of qp_lcp_dict: QP_OPTIMAL, QP_INFEASIBLE or QP_ITERLIMIT (wave-uniform)
+__device__ inline int qp_lemke(Lp &lp, int nc, int n_eq) {
+    const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc;
+    double *T = lp.T;
+    int st = QP_OPTIMAL;
+    // equality rows: lambda_e enters on its own row (largest remaining diagonal first would be safer; W_ee > 0 for
+    // independent equality rows), the slack s_e is fixed at zero and its column deleted
+    for (int e = 0; e < n_eq && st == QP_OPTIMAL; ++e) {
+        int q = -1;
+        for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == e) q = j;
+        q = wave_max_i(q);
+        if (q < 0 || !(fabs(T[(size_t)e * ld + q]) > 1e-12)) { st = QP_INFEASIBLE; break; }   // dependent equality rows
+        lp_pivot(lp, e, q);
+        lp_drop_col(lp, q);
+        if (lane == 0) lp.rowkind[e] = RK_FREE;
+        wave_sync();
+    }
+    if (st == QP_OPTIMAL) {
+        // most negative value among the inequality rows
+        double vmin = 0.0; int key = 0, r = -1;
+        for (int i = lane; i < nc; i += 64)
+            if (lp.rowkind[i] == RK_INEQ) { const double v = T[(size_t)i * ld]; if (r < 0 || v < vmin) { vmin = v; r = i; } }
+        reduce_min_first(vmin, key, r);
+        if (r >= 0 && vmin < -1e-12) {
+            int qz = -1;
+            for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == ID_Z0) qz = j;
+            qz = wave_max_i(qz);
+            int left = lp.rowvar[r];
+            lp_pivot(lp, r, qz);
+            for (;;) {
+                if (lp.iters > lp.max_iter) { st = QP_ITERLIMIT; break; }
+                const int enter = left < nc ? left + nc : left - nc;   // the complement of the variable that left
+                int q = -1;
+                for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == enter) q = j;
+                q = wave_max_i(q);
+                if (q < 0) { st = QP_INFEASIBLE; break; }           // its column was deleted: cannot happen for inequality rows
+                // ratio test over the sign-restricted rows (the free multipliers of the equality rows never leave)
+                double best = INFINITY; int bz = 0, bvar = 0, br = -1;
+                for (int i = lane; i < nc; i += 64) {
+                    if (lp.rowkind[i] != RK_INEQ) continue;
+                    const double a = T[(size_t)i * ld + q];
+                    if (!(a > TOL_PIV)) continue;
+                    const double ratio = fmax(T[(size_t)i * ld], 0.0) / a;
+                    const int isz = lp.rowvar[i] == ID_Z0 ? 1 : 0, var = lp.rowvar[i];
+                    if (bland_better(ratio, isz, var, best, bz, bvar, br)) { best = ratio; bz = isz; bvar = var; br = i; }
+                }
+                double piv = 0.0;
+                reduce_ratio(best, piv, bz, bvar, br, true);
+                if (br < 0) { st = QP_INFEASIBLE; break; }          // ray termination
+                left = lp.rowvar[br];
+                lp_pivot(lp, br, q);
+                if (left == ID_Z0) break;                             // z0 left the basis: complementary solution
+            }
+        }
+    }
+    return st;
+}
+
+// the multipliers of the final dictionary into lamv[nc] (zero unless optimal)
+__device__ inline void qp_multipliers(const Lp &lp, int nc, int st, double *lamv) {
+    const int lane = lane_id();
+    for (int i = lane; i < nc; i += 64) lamv[i] = 0.0;
+    wave_sync();
+    if (st == QP_OPTIMAL)
+        for (int i = lane; i < nc; i += 64) { const int v = lp.rowvar[i]; if (v < nc) lamv[v] = lp.T[(size_t)i * lp.ld]; }
+    wave_sync();
+}
+
+// LDS view of the k_qp_batch tableau: (nc + 1) x ld doubles, the index block, then nc multipliers
+__device__ inline double *qp_lds_layout(Lp &lp, double *smem, int nc, int ld) {
+    int *ib = reinterpret_cast<int *>(smem + (size_t)(nc + 1) * ld);
+    lp.T = smem; lp.ld = ld; lp.colvar = ib; lp.rowvar = ib + ld + 1; lp.rowkind = ib + ld + 1 + nc + 2;
+    // (ld + 1) + 2 (nc + 2) ints precede it and ld is odd: the int block has an even length, lamv is 8-byte aligned as it stands
+    return reinterpret_cast<double *>(lp.rowkind + nc + 2);
+}
+
 __global__ void __launch_bounds__(64) k_qp_batch(long long n_qp, int nc, int n_eq, int nt, int nx, int ld, const double *__restrict__ W,
                                                  const double *__restrict__ UV, const double *__restrict__ X0H, const double *__restrict__ Gt,
                                                  const double *__restrict__ theta, int32_t *__restrict__ status, double *__restrict__ x,
@@ -34,90 +132,22 @@ __global__ void __launch_bounds__(64) k_qp_batch(long long n_qp, int nc, int n_e
                                                  unsigned int *work) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int lane = lane_id(), nr = nt + 1;
-    double *T = smem;
-    int *ib = reinterpret_cast<int *>(smem + (size_t)(nc + 1) * ld);
     Lp lp;
-    lp.T = T; lp.ld = ld; lp.colvar = ib; lp.rowvar = ib + ld + 1; lp.rowkind = ib + ld + 1 + nc + 2;
-    // (ld + 1) + 2 (nc + 2) ints precede it and ld is odd: the int block has an even length, lamv is 8-byte aligned as it stands
-    double *lamv = reinterpret_cast<double *>(lp.rowkind + nc + 2);   // multipliers of the solved point
-    const int ID_Z0 = 2 * nc;
+    double *lamv = qp_lds_layout(lp, smem, nc, ld);   // multipliers of the solved point
     for (;;) {
         unsigned int w = 0;
         if (lane == 0) w = atomicAdd(work, 1u);
         w = (unsigned)__builtin_amdgcn_readfirstlane((int)w);
         if (w >= n_qp) break;
         const double *th = theta + (size_t)w * nt;
-        lp.m = nc; lp.n = 0; lp.na = nc + 1; lp.iters = 0; lp.max_iter = 50 * nc + 100; lp.growth = 0.0;
-        wave_sync();
-        // dictionary: s_i = q_i - sum_j (-W_ij) lambda_j - (-1) z0 ; the cost row (index nc) is unused
-        for (int i = lane; i <= nc; i += 64) {
-            double *Ti = T + (size_t)i * ld;
-            double q = 0.0;
-            if (i < nc) { q = UV[(size_t)i * nr]; for (int t = 0; t < nt; ++t) q = fma(UV[(size_t)i * nr + 1 + t], th[t], q); }
-            Ti[0] = q;
-            for (int j = 0; j < nc; ++j) Ti[1 + j] = i < nc ? -W[(size_t)i * nc + j] : 0.0;
-            Ti[nc + 1] = (i >= n_eq && i < nc) ? -1.0 : 0.0;
-            if (i < nc) { lp.rowvar[i] = nc + i; lp.rowkind[i] = i < n_eq ? RK_EQ : RK_INEQ; }
-        }
-        for (int j = lane; j <= nc + 1; j += 64) lp.colvar[j] = j == 0 ? -1 : (j <= nc ? j - 1 : ID_Z0);
-        wave_sync();
-        int st = QP_OPTIMAL;
-        // equality rows: lambda_e enters on its own row (largest remaining diagonal first would be safer; W_ee > 0 for
-        // independent equality rows), the slack s_e is fixed at zero and its column deleted
-        for (int e = 0; e < n_eq && st == QP_OPTIMAL; ++e) {
-            int q = -1;
-            for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == e) q = j;
-            q = wave_max_i(q);
-            if (q < 0 || !(fabs(T[(size_t)e * ld + q]) > 1e-12)) { st = QP_INFEASIBLE; break; }   // dependent equality rows
-            lp_pivot(lp, e, q);
-            lp_drop_col(lp, q);
-            if (lane == 0) lp.rowkind[e] = RK_FREE;
-            wave_sync();
-        }
-        if (st == QP_OPTIMAL) {
-            // most negative value among the inequality rows
-            double vmin = 0.0; int key = 0, r = -1;
-            for (int i = lane; i < nc; i += 64)
-                if (lp.rowkind[i] == RK_INEQ) { const double v = T[(size_t)i * ld]; if (r < 0 || v < vmin) { vmin = v; r = i; } }
-            reduce_min_first(vmin, key, r);
-            if (r >= 0 && vmin < -1e-12) {
-                int qz = -1;
-                for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == ID_Z0) qz = j;
-                qz = wave_max_i(qz);
-                int left = lp.rowvar[r];
-                lp_pivot(lp, r, qz);
-                for (;;) {
-                    if (lp.iters > lp.max_iter) { st = QP_ITERLIMIT; break; }
-                    const int enter = left < nc ? left + nc : left - nc;   // the complement of the variable that left
-                    int q = -1;
-                    for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == enter) q = j;
-                    q = wave_max_i(q);
-                    if (q < 0) { st = QP_INFEASIBLE; break; }           // its column was deleted: cannot happen for inequality rows
-                    // ratio test over the sign-restricted rows (the free multipliers of the equality rows never leave)
-                    double best = INFINITY; int bz = 0, bvar = 0, br = -1;
-                    for (int i = lane; i < nc; i += 64) {
-                        if (lp.rowkind[i] != RK_INEQ) continue;
-                        const double a = T[(size_t)i * ld + q];
-                        if (!(a > TOL_PIV)) continue;
-                        const double ratio = fmax(T[(size_t)i * ld], 0.0) / a;
-                        const int isz = lp.rowvar[i] == ID_Z0 ? 1 : 0, var = lp.rowvar[i];
-                        if (bland_better(ratio, isz, var, best, bz, bvar, br)) { best = ratio; bz = isz; bvar = var; br = i; }
-                    }
-                    double piv = 0.0;
-                    reduce_ratio(best, piv, bz, bvar, br, true);
-                    if (br < 0) { st = QP_INFEASIBLE; break; }          // ray termination
-                    left = lp.rowvar[br];
-                    lp_pivot(lp, br, q);
-                    if (left == ID_Z0) break;                             // z0 left the basis: complementary solution
-                }
-            }
-        }
+        qp_lcp_dict(lp, nc, n_eq, W, [&](int i) {
+            double q = UV[(size_t)i * nr];
+            for (int t = 0; t < nt; ++t) q = fma(UV[(size_t)i * nr + 1 + t], th[t], q);
+            return q;
+        });
+        const int st = qp_lemke(lp, nc, n_eq);
         // outputs
-        for (int i = lane; i < nc; i += 64) lamv[i] = 0.0;
-        wave_sync();
-        if (st == QP_OPTIMAL)
-            for (int i = lane; i < nc; i += 64) { const int v = lp.rowvar[i]; if (v < nc) lamv[v] = T[(size_t)i * ld]; }
-        wave_sync();
+        qp_multipliers(lp, nc, st, lamv);
         if (lam) for (int i = lane; i < nc; i += 64) lam[(size_t)w * nc + i] = lamv[i];
         if (active) {
             // a constraint is active when its slack is nonbasic (zero) in the final dictionary
@@ -135,6 +165,147 @@ __global__ void __launch_bounds__(64) k_qp_batch(long long n_qp, int nc, int n_e
             }
         }
         if (lane == 0) { status[w] = st; if (iters) iters[w] = lp.iters; }
+        wave_sync();
+    }
+}
+
+// ---- the MIQP at fixed parameter points: one LCP per (point, binary fixation) pair ------------------------------------------
+// With the binaries y fixed, the continuous QP of an MIQP keeps its Hessian Q_c and its constraint rows A_c; only the right-hand
+// side and the linear term move, both affine in z = [1; theta; y].  So every pair shares W = A_c Q_c^-1 A_c' and only
+// q = UV z changes (the host assembly: MPMIQP_Program.theta_blocks).  Rows without continuous content but with theta content
+// are check rows: s = CK z decides them alone (s >= -MIQP_CHECK_TOL, or |s| <= MIQP_CHECK_TOL on equality rows).
+constexpr double MIQP_CHECK_TOL = MPC_MIQP_CHECK_TOL;   // include/mpcombi.h
+
+struct MiqpBlocks {
+    int nc, n_eq, nxc, nt, nb, nz, n_ck, n_x, n_rows;
+    const double *W, *UV, *X0, *Gt, *Qc, *G, *K, *CK, *Y, *theta;
+    const uint8_t *ck_eq;
+    const int32_t *cont_idx, *bin_idx, *lcp_row;
+};
+
+// LDS: the k_qp_batch tableau and multipliers, then z (nz) and x (nxc)
+__device__ inline int miqp_pair(const MiqpBlocks &B, Lp &lp, double *lamv, long long p, long long leaf, double &obj) {
+    const int lane = lane_id(), nz = B.nz, nc = B.nc, nxc = B.nxc;
+    double *zv = lamv + nc, *xv = zv + nz;
+    for (int k = lane; k < nz; k += 64)
+        zv[k] = k == 0 ? 1.0 : (k <= B.nt ? B.theta[(size_t)p * B.nt + k - 1] : B.Y[(size_t)leaf * B.nb + k - 1 - B.nt]);
+    wave_sync();
+    int bad = 0;
+    for (int k = lane; k < B.n_ck; k += 64) {
+        const double *ck = B.CK + (size_t)k * nz;
+        double s = ck[0];
+        for (int j = 1; j < nz; ++j) s = fma(ck[j], zv[j], s);
+        if (B.ck_eq[k] ? !(fabs(s) <= MIQP_CHECK_TOL) : !(s >= -MIQP_CHECK_TOL)) bad = 1;
+    }
+    obj = __longlong_as_double(0x7ff8000000000000ll);
+    if (wave_max_i(bad)) return QP_INFEASIBLE;                     // a violated check row: no pivot
+    qp_lcp_dict(lp, nc, B.n_eq, B.W, [&](int i) {
+        const double *u = B.UV + (size_t)i * nz;
+        double q = u[0];
+        for (int j = 1; j < nz; ++j) q = fma(u[j], zv[j], q);
+        return q;
+    });
+    const int st = qp_lemke(lp, nc, B.n_eq);
+    qp_multipliers(lp, nc, st, lamv);
+    if (st != QP_OPTIMAL) return st;
+    // x = X0 z - Gt' lambda
+    for (int a = lane; a < nxc; a += 64) {
+        double v = B.X0[(size_t)a * nz];
+        for (int j = 1; j < nz; ++j) v = fma(B.X0[(size_t)a * nz + j], zv[j], v);
+        for (int i = 0; i < nc; ++i) v = fma(-lamv[i], B.Gt[(size_t)i * nxc + a], v);
+        xv[a] = v;
+    }
+    wave_sync();
+    // objective 1/2 x'Q_c x + (G z)'x + 1/2 z'K z: a term per lane, one butterfly sum, lane 0's total for every lane
+    double part = 0.0;
+    for (int a = lane; a < nxc; a += 64) {
+        double qx = 0.0, gz = B.G[(size_t)a * nz];
+        for (int b = 0; b < nxc; ++b) qx = fma(B.Qc[(size_t)a * nxc + b], xv[b], qx);
+        for (int j = 1; j < nz; ++j) gz = fma(B.G[(size_t)a * nz + j], zv[j], gz);
+        part += xv[a] * (0.5 * qx + gz);
+    }
+    for (int k = lane; k < nz; k += 64) {
+        double kz = 0.0;
+        for (int j = 0; j < nz; ++j) kz = fma(B.K[(size_t)k * nz + j], zv[j], kz);
+        part += 0.5 * zv[k] * kz;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
+    obj = __shfl(part, 0);
+    return st;
+}
+
+// pass 1: (status, objective) of every (point, leaf) pair, [points x leaves]
+__global__ void __launch_bounds__(64) k_miqp_pairs(MiqpBlocks B, long long m, long long n_leaves, int ld, int32_t *__restrict__ status,
+                                                   double *__restrict__ obj, unsigned int *work) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    Lp lp;
+    double *lamv = qp_lds_layout(lp, smem, B.nc, ld);
+    const long long n_pairs = m * n_leaves;
+    for (;;) {
+        unsigned long long w = 0;
+        if (lane_id() == 0) w = atomicAdd(reinterpret_cast<unsigned long long *>(work), 1ull);
+        w = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)w);
+        if (w >= (unsigned long long)n_pairs) break;
+        double f;
+        const int st = miqp_pair(B, lp, lamv, (long long)(w / n_leaves), (long long)(w % n_leaves), f);
+        if (lane_id() == 0) { status[w] = st; obj[w] = f; }
+        wave_sync();
+    }
+}
+
+// pick pass, one thread per point: the lowest objective among the optimal pairs, the lowest leaf on ties (Solver.solve_milp).
+// A point with an iteration-limited pair is reported as such (its minimum is not certain); with no optimal pair it is infeasible.
+__global__ void k_miqp_pick(long long m, long long n_leaves, const int32_t *__restrict__ status, const double *__restrict__ obj,
+                            int32_t *__restrict__ pst, int32_t *__restrict__ leaf, double *__restrict__ best) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    long long bl = -1;
+    double bo = 0.0;
+    bool lim = false;
+    for (long long l = 0; l < n_leaves; ++l) {
+        const int s = status[p * n_leaves + l];
+        if (s == QP_ITERLIMIT) lim = true;
+        if (s != QP_OPTIMAL) continue;
+        const double o = obj[p * n_leaves + l];
+        if (bl < 0 || o < bo) { bl = l; bo = o; }
+    }
+    pst[p] = lim ? QP_ITERLIMIT : (bl >= 0 ? QP_OPTIMAL : QP_INFEASIBLE);
+    leaf[p] = lim ? -1 : (int32_t)bl;
+    best[p] = bl >= 0 && !lim ? bo : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// winner pass: each point's winning pair once more (the same arithmetic as pass 1), writing x (y spliced in), the multipliers
+// over all program rows and the active flags of the LCP rows
+__global__ void __launch_bounds__(64) k_miqp_winners(MiqpBlocks B, long long m, int ld, const int32_t *__restrict__ leaf,
+                                                     double *__restrict__ obj, double *__restrict__ x, double *__restrict__ lam,
+                                                     uint8_t *__restrict__ active, unsigned int *work) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    Lp lp;
+    double *lamv = qp_lds_layout(lp, smem, B.nc, ld);
+    const int lane = lane_id(), nc = B.nc;
+    const double *xv = lamv + nc + B.nz;
+    for (;;) {
+        unsigned int w = 0;
+        if (lane == 0) w = atomicAdd(work, 1u);
+        w = (unsigned)__builtin_amdgcn_readfirstlane((int)w);
+        if (w >= m) break;
+        const long long l = leaf[w];
+        if (l < 0) continue;
+        double f;
+        const int st = miqp_pair(B, lp, lamv, w, l, f);
+        if (lane == 0) obj[w] = st == QP_OPTIMAL ? f : __longlong_as_double(0x7ff8000000000000ll);
+        if (x) {
+            for (int a = lane; a < B.nxc; a += 64) x[(size_t)w * B.n_x + B.cont_idx[a]] = xv[a];
+            for (int k = lane; k < B.nb; k += 64) x[(size_t)w * B.n_x + B.bin_idx[k]] = B.Y[(size_t)l * B.nb + k];
+        }
+        if (lam) for (int i = lane; i < nc; i += 64) lam[(size_t)w * B.n_rows + B.lcp_row[i]] = lamv[i];
+        if (active) {
+            // as in k_qp_batch: a row is active when its slack is nonbasic in the final dictionary
+            for (int i = lane; i < nc; i += 64) active[(size_t)w * B.n_rows + B.lcp_row[i]] = st == QP_OPTIMAL ? 1 : 0;
+            wave_sync();
+            for (int i = lane; i < nc; i += 64) { const int v = lp.rowvar[i]; if (v >= nc && v < 2 * nc) active[(size_t)w * B.n_rows + B.lcp_row[v - nc]] = 0; }
+        }
         wave_sync();
     }
 }

@@ -164,3 +164,26 @@ class MPMILP_Program(MPLP_Program):
             const = self.c_c + self.c_t.T @ theta_point + 0.5 * theta_point.T @ self.Q_t @ theta_point
             soln.obj += float(const[0, 0])
         return soln
+
+    def solve_theta_batch(self, theta_points: numpy.ndarray) -> List[Optional[SolverOutput]]:
+        """``solve_theta`` for many parameter points (theta_points [m, n_theta]): the LPs of every (point, feasible fixation)
+        pair and the tie rule of Solver.solve_milp (the best objective, the first fixation on ties), as bounded batches on the
+        device LP kernel, the winners' minimisers in one more batch.  The fixations are those of ``feasible_combinations()``: for
+        theta in the parameter set that is every fixation solve_theta can choose.  Like solve_theta, theta is not checked
+        against A_t theta <= b_t."""
+        th = numpy.ascontiguousarray(theta_points, dtype=numpy.float64).reshape(-1, self.num_t())
+        out: List[Optional[SolverOutput]] = [None] * len(th)
+        if len(th) == 0 or self.A.shape[0] == 0:
+            return out
+        # per point exactly the arrays solve_theta hands to Solver.solve_milp
+        tcols = [th[p].reshape(-1, 1) for p in range(len(th))]
+        b = numpy.stack([(self.b + self.F @ t).reshape(-1) for t in tcols])
+        c = numpy.stack([(self.c + self.H @ t).reshape(-1) for t in tcols])
+        leaves = numpy.flatnonzero(self.leaf_feasibility())
+        ok, obj, sol = self.solver.solve_milp_points(c, self.A, b, self.equality_indices, self.binary_indices, leaves)
+        for p in numpy.flatnonzero(ok):
+            t = tcols[p]
+            slack = b[p] - self.A @ sol[p]
+            const = self.c_c + self.c_t.T @ t + 0.5 * t.T @ self.Q_t @ t
+            out[p] = SolverOutput(float(obj[p]) + float(const[0, 0]), sol[p].copy(), slack, numpy.nonzero(numpy.abs(slack) <= 1e-10)[0], None)
+        return out

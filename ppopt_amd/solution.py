@@ -200,15 +200,23 @@ class Solution:
         KKT conditions, which are sufficient for the convex programs of this package and need no QP solver.  A point
         in no region verifies when the program is infeasible there (one LP on the device)."""
         region = self.get_region(theta_point)
+        P = self.program
+        th = numpy.asarray(theta_point, dtype=float).reshape(-1, 1)
+        if self.is_mixed_integer_sol():
+            # the reference's rule by objective (solution.py:149-174): no region exactly where the deterministic solve has no
+            # solution, else the region's objective is the optimum
+            if region is None:
+                return True if not P.valid_parameter_realization(th) else P.solve_theta(th) is None
+            det = P.solve_theta(th)
+            if det is None:
+                return False
+            here = P.evaluate_objective(region.evaluate(th), th)
+            return abs(here - det.obj) <= tol * (1.0 + abs(det.obj))
         if region is None:
-            P = self.program
-            th = numpy.asarray(theta_point, dtype=float).reshape(-1, 1)
             if not P.valid_parameter_realization(th):
                 return True
             feasible = P.solver.solve_lp(None, P.A, P.b + P.F @ th, P.equality_indices) is not None
             return not feasible
-        if region.y_fixation is not None:
-            raise NotImplementedError('verify_theta covers continuous programs')
         return max(self.kkt_residuals(region, theta_point).values()) <= tol
 
     def chebyshev_centres(self, device: int = 0):
@@ -243,6 +251,8 @@ class Solution:
         if numpy.any(~numpy.isfinite(radii)):
             return False
         located = self.get_region_batch(centres, device)
+        if self.is_mixed_integer_sol():
+            return self._verify_mixed_integer(centres, located, tol)
         # the reference's own test where the program offers it: the deterministic solve at the centre (one device batch of QPs
         # / LPs, MPQP_Program.solve_theta_batch) must give the region's x* -- solution.py:128-145
         det = None
@@ -268,6 +278,22 @@ class Solution:
                 there = self.program.evaluate_objective(self.critical_regions[int(located[i])].evaluate(th), th)
                 if abs(here - there) > tol * (1.0 + abs(here)):
                     return False
+        return True
+
+    def _verify_mixed_integer(self, centres: numpy.ndarray, located: numpy.ndarray, tol: float) -> bool:
+        """verify_solution of a mixed-integer solution, by objective: the deterministic optimum at every Chebyshev centre (one
+        solve_theta_batch) is the objective of the region located there, and no region's own objective lies below it."""
+        P = self.program
+        det = P.solve_theta_batch(centres)
+        for i, region in enumerate(self.critical_regions):
+            if det[i] is None or located[i] < 0:
+                return False
+            th = centres[i].reshape(-1, 1)
+            opt = det[i].obj
+            there = P.evaluate_objective(self.critical_regions[int(located[i])].evaluate(th), th)
+            own = P.evaluate_objective(region.evaluate(th), th)
+            if abs(there - opt) > tol * (1.0 + abs(opt)) or own < opt - tol * (1.0 + abs(opt)):
+                return False
         return True
 
     def materialize(self) -> 'Solution':

@@ -267,6 +267,57 @@ class Solver:
             x[:, :, bins] = fix[None]
         return status.reshape(n_sets, n_fix), x, obj.reshape(n_sets, n_fix)
 
+    def solve_milp_points(self, c, A, b, equality_constraints: Optional[Sequence[int]], bin_vars: Sequence[int],
+                          leaves: numpy.ndarray):
+        """``solve_milp`` for many right-hand sides and objectives at once (c [P, n] or None, b [P, m]), over the given fixations
+        ``leaves`` (indices into ``binary_fixations``, ascending) instead of those feasible for each b: the LP of every (instance,
+        leaf) pair in bounded batches, the best objective per instance with the first leaf on ties, then the winners' minimisers
+        in one more batch.  Returns (ok [P], obj [P], sol [P, n] with the binaries spliced in)."""
+        A_aug, _, m, n, bins = self._milp_blocks(A, numpy.zeros(A.shape[0]), bin_vars)
+        nb = len(bins)
+        bb = numpy.ascontiguousarray(b, dtype=numpy.float64).reshape(-1, m)
+        P, L = len(bb), len(leaves)
+        b_aug = numpy.hstack([bb, numpy.ones((P, nb)), numpy.zeros((P, nb))])
+        cc = None if c is None else numpy.ascontiguousarray(c, dtype=numpy.float64).reshape(P, n)
+        shifts = numpy.arange(nb - 1, -1, -1, dtype=numpy.int64)[None, :]
+        fix = ((numpy.asarray(leaves, dtype=numpy.int64)[:, None] >> shifts) & 1).astype(numpy.int8)
+        eq_flags = self._set_flags([list(equality_constraints or [])], m)[0]
+        ok, best_obj, sol = numpy.zeros(P, dtype=bool), numpy.full(P, numpy.nan), numpy.full((P, n), numpy.nan)
+        if P == 0 or L == 0:
+            return ok, best_obj, sol
+        per_pair = 9 * (m + 2 * nb) + 8 * n + 16
+        step = max(1, int(self.MILP_BATCH_BYTES // (per_pair * L)))      # instances per batch (all their leaves)
+        best = numpy.full(P, -1, dtype=numpy.int64)
+        for lo in range(0, P, step):
+            hi = min(P, lo + step)
+            k = hi - lo
+            flags = numpy.zeros((k * L, m + 2 * nb), dtype=numpy.uint8)
+            flags[:, :m] = eq_flags
+            flags[:, m:m + nb] = numpy.tile(fix == 1, (k, 1))
+            flags[:, m + nb:] = numpy.tile(fix == 0, (k, 1))
+            st, _, ob, _ = _lib.lp_solve_batch(A_aug, numpy.repeat(b_aug[lo:hi], L, axis=0),
+                                               None if cc is None else numpy.repeat(cc[lo:hi], L, axis=0), flags, device=self.device, want_x=False)
+            good = (st == _lib.LP_OPTIMAL).reshape(k, L)
+            vals = numpy.where(good, ob.reshape(k, L), numpy.inf)
+            arg = numpy.argmin(vals, axis=1)                      # first leaf on ties
+            has = good.any(axis=1)
+            best[lo:hi] = numpy.where(has, arg, -1)
+            best_obj[lo:hi] = numpy.where(has, vals[numpy.arange(k), arg], numpy.nan)
+        win = numpy.flatnonzero(best >= 0)
+        if len(win):
+            step_w = max(1, int(self.MILP_BATCH_BYTES // per_pair))
+            for lo in range(0, len(win), step_w):
+                w = win[lo:lo + step_w]
+                flags = numpy.zeros((len(w), m + 2 * nb), dtype=numpy.uint8)
+                flags[:, :m] = eq_flags
+                flags[:, m:m + nb] = fix[best[w]] == 1
+                flags[:, m + nb:] = fix[best[w]] == 0
+                _, x, _, _ = _lib.lp_solve_batch(A_aug, b_aug[w], None if cc is None else cc[w], flags, device=self.device)
+                x[:, bins] = fix[best[w]]
+                sol[w] = x
+            ok[win] = True
+        return ok, best_obj, sol
+
     def solve_milp(self, c: Optional[numpy.ndarray], A: Optional[numpy.ndarray], b: Optional[numpy.ndarray],
                    equality_constraints: Optional[Sequence[int]] = None, bin_vars: Optional[Sequence[int]] = None,
                    verbose: bool = False, get_duals: bool = True) -> Optional[SolverOutput]:
