@@ -13,7 +13,13 @@
 // equality rows enter first and their slacks are deleted (a principal block pivot), the covering variable z0 enters on the
 // most negative q_i, then the complement of whatever left enters until z0 leaves (solved) or no row limits the entering
 // variable (ray termination: the QP is infeasible at this theta).  W is positive semidefinite, so Lemke terminates in one
-// of the two.  Ratio ties are broken in favour of z0's row, then by the lowest variable id.
+// of the two.  Ratio ties (to QP_TOL_TIE) go to z0's row, then lexicographically (qp_lex_row), then to the lowest variable id.
+// The LCP is solved in the symmetric diagonal scaling s' = D s, lambda = D lambda', D = diag(W_ii)^-1/2 (1 on a zero row):
+// D W D keeps W's semidefiniteness and complementarity and has a unit diagonal, so the absolute pivot tolerances (TOL_PIV,
+// the equality pivot, the start test) are relative to the rows' own scale.  Without it a Q of 1e10 I with unit rows left
+// every entry of W below TOL_PIV and feasible points ended in ray termination.  The multipliers are mapped back at the end.
+// An equality row that depends on the equality rows before it (its pivot entry vanishes) is dropped when it is consistent at
+// this theta (lambda_e = 0) and makes the point infeasible when it is not.
 #pragma once
 #include "lp_engine.hpp"
 #include "../../include/mpcombi.h"
@@ -21,6 +27,8 @@
 namespace mpc {
 
 enum : int { QP_OPTIMAL = 0, QP_INFEASIBLE = 1, QP_ITERLIMIT = 3 };
+constexpr double QP_TOL_DEP = 1e-10;   // scaled pivot entry below which an equality row counts as dependent on the earlier ones
+constexpr double QP_TOL_TIE = 1e-12;   // ratio-test rows whose scaled right-hand sides differ by less tie (qp_lex_row)
 
 __device__ __forceinline__ int wave_max_i(int v) {
 #pragma unroll
@@ -29,19 +37,23 @@ __device__ __forceinline__ int wave_max_i(int v) {
 }
 
 // ---- the LCP of one point: dictionary, complementary pivoting, multipliers (shared by k_qp_batch and the MIQP kernels) ----
-// Dictionary: s_i = q_i - sum_j (-W_ij) lambda_j - (-1) z0 with q_i = qf(i); the cost row (index nc) is unused.
+// Dictionary of the scaled LCP: s'_i = d_i q_i - sum_j (-d_i W_ij d_j) lambda'_j - (-1) z0 with q_i = qf(i), d_i = W_ii^-1/2;
+// the cost row (index nc) is unused.  d is left in dv[nc] (LDS) for qp_multipliers.
 template <class QF>
-__device__ inline void qp_lcp_dict(Lp &lp, int nc, int n_eq, const double *__restrict__ W, QF qf) {
+__device__ inline void qp_lcp_dict(Lp &lp, int nc, int n_eq, const double *__restrict__ W, double *dv, QF qf) {
     const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc;
     double *T = lp.T;
     lp.m = nc; lp.n = 0; lp.na = nc + 1; lp.iters = 0; lp.max_iter = 50 * nc + 100; lp.growth = 0.0;
     wave_sync();
+    for (int i = lane; i < nc; i += 64) { const double w = W[(size_t)i * nc + i]; dv[i] = w > 0.0 ? 1.0 / sqrt(w) : 1.0; }
+    wave_sync();
     for (int i = lane; i <= nc; i += 64) {
         double *Ti = T + (size_t)i * ld;
         double q = 0.0;
-        if (i < nc) q = qf(i);
+        const double di = i < nc ? dv[i] : 0.0;
+        if (i < nc) q = di * qf(i);
         Ti[0] = q;
-        for (int j = 0; j < nc; ++j) Ti[1 + j] = i < nc ? -W[(size_t)i * nc + j] : 0.0;
+        for (int j = 0; j < nc; ++j) Ti[1 + j] = i < nc ? -(W[(size_t)i * nc + j] * (di * dv[j])) : 0.0;
         Ti[nc + 1] = (i >= n_eq && i < nc) ? -1.0 : 0.0;
         if (i < nc) { lp.rowvar[i] = nc + i; lp.rowkind[i] = i < n_eq ? RK_EQ : RK_INEQ; }
     }
@@ -49,18 +61,97 @@ __device__ inline void qp_lcp_dict(Lp &lp, int nc, int n_eq, const double *__res
     wave_sync();
 }
 
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// The leaving row of a degenerate step, lexicographically.  The rows whose ratio is within QP_TOL_TIE (in the units of the
+// scaled right-hand side) of the minimum rmin all tie; z0's row wins among them, otherwise the rows are ranked by the rows of
+// B^-1 divided by their pivot entries, taken in the order of the initial basic variables s_k (column k of B^-1 is the
+// dictionary column of s_k while s_k is nonbasic, the unit vector of its row while it is basic), until one row is left; then
+// the lowest variable id.  Without it a run of degenerate pivots can reach an almost-complementary basis whose entering column
+// is zero (a secondary ray): a feasible point reported infeasible.  br (the plain rule's row) is returned when nothing ties.
+// Equality slacks (k < n_eq) were deleted with their columns and take no part.  Rows per lane: i = lane + 64 s, s < 32.
+__device__ inline int qp_lex_row(const Lp &lp, int nc, int n_eq, int q, double rmin, int br) {
+    const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc;
+    const double *T = lp.T;
+    unsigned tie = 0;
+    int ntie = 0, z0 = -1;
+    for (int i = lane, b = 0; i < nc; i += 64, ++b) {
+        if (lp.rowkind[i] != RK_INEQ) continue;
+        const double a = T[(size_t)i * ld + q];
+        if (!(a > TOL_PIV) || !(fmax(T[(size_t)i * ld], 0.0) <= rmin * a + QP_TOL_TIE)) continue;
+        tie |= 1u << b;
+        ++ntie;
+        if (lp.rowvar[i] == ID_Z0) z0 = i;
+    }
+    z0 = wave_max_i(z0);
+    if (z0 >= 0) return z0;
+    ntie = wave_sum_i(ntie);
+    if (ntie <= 1) return br;
+    for (int k = n_eq; k < nc && ntie > 1; ++k) {
+        int jc = -1, rb = -1;
+        for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == nc + k) jc = j;
+        jc = wave_max_i(jc);
+        if (jc < 0) {
+            for (int i = lane; i < nc; i += 64) if (lp.rowvar[i] == nc + k) rb = i;
+            rb = wave_max_i(rb);
+        }
+        double vmin = INFINITY;
+        for (int i = lane, b = 0; i < nc; i += 64, ++b)
+            if (tie >> b & 1u) {
+                const double v = jc >= 0 ? T[(size_t)i * ld + jc] : (i == rb ? 1.0 : 0.0);
+                vmin = fmin(vmin, v / T[(size_t)i * ld + q]);
+            }
+        vmin = wave_min(vmin);
+        ntie = 0;
+        for (int i = lane, b = 0; i < nc; i += 64, ++b)
+            if (tie >> b & 1u) {
+                const double v = jc >= 0 ? T[(size_t)i * ld + jc] : (i == rb ? 1.0 : 0.0);
+                if (v <= vmin * T[(size_t)i * ld + q] + QP_TOL_TIE) ++ntie;
+                else tie &= ~(1u << b);
+            }
+        ntie = wave_sum_i(ntie);
+    }
+    // the lowest variable id among the rows left
+    int bv = 0x7fffffff, bi = -1;
+    for (int i = lane, b = 0; i < nc; i += 64, ++b)
+        if ((tie >> b & 1u) && lp.rowvar[i] < bv) { bv = lp.rowvar[i]; bi = i; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int ov = __shfl_xor(bv, off), oi = __shfl_xor(bi, off);
+        if (ov < bv) { bv = ov; bi = oi; }
+    }
+    return bi >= 0 ? bi : br;
+}
+
 // Lemke's method on the dictionary of qp_lcp_dict: QP_OPTIMAL, QP_INFEASIBLE or QP_ITERLIMIT (wave-uniform)
 __device__ inline int qp_lemke(Lp &lp, int nc, int n_eq) {
-    const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc;
+    const int lane = lane_id(), ld = lp.ld, ID_Z0 = 2 * nc, ID_RETIRED = 2 * nc + 1;   // a retired row is neither slack nor multiplier
     double *T = lp.T;
     int st = QP_OPTIMAL;
-    // equality rows: lambda_e enters on its own row (largest remaining diagonal first would be safer; W_ee > 0 for
-    // independent equality rows), the slack s_e is fixed at zero and its column deleted
+    // equality rows: lambda_e enters on its own row (largest remaining diagonal first would be safer; the scaled W_ee is 1
+    // for independent equality rows), the slack s_e is fixed at zero and its column deleted
     for (int e = 0; e < n_eq && st == QP_OPTIMAL; ++e) {
         int q = -1;
         for (int j = 1 + lane; j <= lp.na; j += 64) if (lp.colvar[j] == e) q = j;
         q = wave_max_i(q);
-        if (q < 0 || !(fabs(T[(size_t)e * ld + q]) > 1e-12)) { st = QP_INFEASIBLE; break; }   // dependent equality rows
+        if (q < 0) { st = QP_INFEASIBLE; break; }
+        const double *Te = T + (size_t)e * ld;
+        if (!(fabs(Te[q]) > QP_TOL_DEP)) {
+            // row e is a combination of the equality rows pivoted before it: its multiplier entries vanish with T_ee and T_e0 is the
+            // residual of the dependence at this theta.  Consistent: lambda_e = 0 and the row is retired; otherwise infeasible.
+            double big = 0.0;
+            for (int j = 1 + lane; j <= lp.na; j += 64) big = fmax(big, fabs(Te[j]));
+            big = wave_max(big);
+            if (big > QP_TOL_DEP || !(fabs(Te[0]) <= QP_TOL_DEP)) { st = QP_INFEASIBLE; break; }
+            lp_drop_col(lp, q);
+            if (lane == 0) { lp.rowkind[e] = RK_DEAD; lp.rowvar[e] = ID_RETIRED; }
+            wave_sync();
+            continue;
+        }
         lp_pivot(lp, e, q);
         lp_drop_col(lp, q);
         if (lane == 0) lp.rowkind[e] = RK_FREE;
@@ -98,6 +189,7 @@ __device__ inline int qp_lemke(Lp &lp, int nc, int n_eq) {
                 double piv = 0.0;
                 reduce_ratio(best, piv, bz, bvar, br, true);
                 if (br < 0) { st = QP_INFEASIBLE; break; }          // ray termination
+                br = qp_lex_row(lp, nc, n_eq, q, best, br);
                 left = lp.rowvar[br];
                 lp_pivot(lp, br, q);
                 if (left == ID_Z0) break;                             // z0 left the basis: complementary solution
@@ -107,9 +199,13 @@ __device__ inline int qp_lemke(Lp &lp, int nc, int n_eq) {
     return st;
 }
 
-// the multipliers of the final dictionary into lamv[nc] (zero unless optimal)
+// the multipliers of the final dictionary into lamv[nc] (zero unless optimal); lamv holds the scaling d of qp_lcp_dict on entry:
+// lambda_v = d_v lambda'_v is formed in column 0 of the final tableau (not read again) before lamv is overwritten
 __device__ inline void qp_multipliers(const Lp &lp, int nc, int st, double *lamv) {
     const int lane = lane_id();
+    if (st == QP_OPTIMAL)
+        for (int i = lane; i < nc; i += 64) { const int v = lp.rowvar[i]; if (v < nc) lp.T[(size_t)i * lp.ld] *= lamv[v]; }
+    wave_sync();
     for (int i = lane; i < nc; i += 64) lamv[i] = 0.0;
     wave_sync();
     if (st == QP_OPTIMAL)
@@ -140,7 +236,7 @@ __global__ void __launch_bounds__(64) k_qp_batch(long long n_qp, int nc, int n_e
         w = (unsigned)__builtin_amdgcn_readfirstlane((int)w);
         if (w >= n_qp) break;
         const double *th = theta + (size_t)w * nt;
-        qp_lcp_dict(lp, nc, n_eq, W, [&](int i) {
+        qp_lcp_dict(lp, nc, n_eq, W, lamv, [&](int i) {
             double q = UV[(size_t)i * nr];
             for (int t = 0; t < nt; ++t) q = fma(UV[(size_t)i * nr + 1 + t], th[t], q);
             return q;
@@ -199,7 +295,7 @@ __device__ inline int miqp_pair(const MiqpBlocks &B, Lp &lp, double *lamv, long 
     }
     obj = __longlong_as_double(0x7ff8000000000000ll);
     if (wave_max_i(bad)) return QP_INFEASIBLE;                     // a violated check row: no pivot
-    qp_lcp_dict(lp, nc, B.n_eq, B.W, [&](int i) {
+    qp_lcp_dict(lp, nc, B.n_eq, B.W, lamv, [&](int i) {
         const double *u = B.UV + (size_t)i * nz;
         double q = u[0];
         for (int j = 1; j < nz; ++j) q = fma(u[j], zv[j], q);

@@ -137,7 +137,8 @@ class MPMIQP_Program(MPMILP_Program):
     def solve_theta_batch(self, theta_points: numpy.ndarray, leaves: Optional[List[List[int]]] = None) -> List[Optional[SolverOutput]]:
         """``solve_theta`` for many parameter points (theta_points [m, n_theta]): every (point, feasible fixation) pair as one LCP
         on the device, one call per chunk of points whose 12 bytes per pair stay within Solver.MILP_BATCH_BYTES.  ``leaves``:
-        the fixations to consider (default: feasible_combinations())."""
+        the fixations to consider (default: feasible_combinations()).  Raises MpcError when a point's minimum is uncertain (a pair at
+        the iteration limit) instead of reporting it as None."""
         from . import _lib
         th = numpy.ascontiguousarray(theta_points, dtype=numpy.float64).reshape(-1, self.num_t())
         B = self.theta_blocks()
@@ -149,6 +150,9 @@ class MPMIQP_Program(MPMILP_Program):
         for lo in range(0, len(th), step):
             hi = min(len(th), lo + step)
             status, _, obj, x, lam, _ = _lib.miqp_solve_batch(B, Y, th[lo:hi], device=self.solver.device)
+            if numpy.any(status == 3):
+                raise _lib.MpcError(f'the MIQP at {int(numpy.sum(status == 3))} parameter points has a fixation whose QP stopped at the '
+                                    f'iteration limit (first: point {lo + int(numpy.flatnonzero(status == 3)[0])}): its minimum is unknown')
             for j in numpy.flatnonzero(status == 0):
                 tp, xp = th[lo + j].reshape(-1, 1), x[j].reshape(-1, 1)
                 slack = (self.b + self.F @ tp - self.A @ xp).ravel()

@@ -60,9 +60,14 @@ class MPQP_Program(MPLP_Program):
     def solve_theta_batch(self, theta_points: numpy.ndarray) -> List[Optional[SolverOutput]]:
         """``solve_theta`` for many parameter points in one device launch (theta_points [m, n_theta]): the KKT conditions as a
         linear complementarity problem in the multipliers, Lemke's method, one wavefront per point (csrc/qp.hpp).  Needs a
-        positive definite Q.  Points outside A_t theta <= b_t are solved like any other (the single-point form filters them)."""
+        positive definite Q.  Points outside A_t theta <= b_t are solved like any other (the single-point form filters them).
+        Raises MpcError when Lemke's method stops at its iteration limit at any point: that point's answer is unknown, not None."""
+        from . import _lib
         th = numpy.ascontiguousarray(theta_points, dtype=numpy.float64).reshape(-1, self.num_t())
         status, x, lam, act = self.engine().qp_solve_batch(th)
+        if numpy.any(status == 3):
+            bad = numpy.flatnonzero(status == 3)
+            raise _lib.MpcError(f'the QP at {len(bad)} of {len(th)} parameter points stopped at the iteration limit (first: point {bad[0]})')
         out: List[Optional[SolverOutput]] = []
         for p in range(len(th)):
             if status[p] != 0:
