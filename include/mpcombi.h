@@ -464,6 +464,19 @@ int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, int32_t n_x,
 int mpc_facet_centres(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *centre,
                       double *radius, int32_t *status);
 
+/* ---- hit-and-run sampling of a batch of polytopes -------------------------------------------------------------------- */
+/* Hit-and-run chains in a batch of polytopes {x : A_p x <= b_p}; see DESIGN for the exact chain and its random stream.
+ * ab_rows: stacked rows [b | A] (n + 1 doubles each) of all polytopes, row_off[n_poly + 1] (<= 256 rows per polytope, n <= 64);
+ * start: one point per polytope; chain g = p * chains + k.  Emits a sample after every n_steps steps (samples * n_steps < 2^32).
+ * status per chain: MPC_HR_OK, MPC_HR_OUTSIDE (the start violates a row), MPC_HR_UNBOUNDED (a chord without an end); a chain
+ * whose status is not MPC_HR_OK has NaN samples.  ms: device time of the kernel (may be NULL). */
+#define MPC_HR_OK 0
+#define MPC_HR_OUTSIDE 1
+#define MPC_HR_UNBOUNDED 2
+int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const int64_t *row_off, const double *ab_rows,
+                    const double *start /* n_poly x n */, int64_t chains, int64_t samples, int64_t n_steps, uint64_t seed,
+                    double *out /* n_poly x chains x samples x n, host */, int32_t *status /* n_poly x chains */, float *ms);
+
 /* ---- consumer of the path: point location over a solution's critical regions, batched ---------------------------- */
 /* Replaces the loop of Solution.get_region / Solution.evaluate (solution.py:45-112, CriticalRegion.is_inside
  * critical_region.py:83-86) for many parameter points at once.

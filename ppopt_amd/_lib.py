@@ -18,6 +18,8 @@ MPC_LOCATE_OVERLAPPING, MPC_LOCATE_INCLUSIVE, MPC_LOCATE_WALK = 1, 2, 4   # flag
 MPC_SOLVE_MANY_BASE = 128   # flag of mpc_solve_many_start
 MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, MPC_LEVEL_ONLY_BASE = 1, 4, 8, 16, 32   # flags of mpc_level_start / mpc_level_run_ex
 MPC_SOLVE_FETCH = 64   # flag of mpc_solve_start
+MPC_HR_OK, MPC_HR_OUTSIDE, MPC_HR_UNBOUNDED = range(3)   # chain statuses of mpc_hit_and_run
+HR_MAX_DIM, HR_MAX_ROWS = 64, 256   # limits of mpc_hit_and_run
 INFEASIBLE, FEASIBLE, OPTIMAL_NO_REGION, REGION, SINGULAR_KKT, LP_LIMIT = range(6)
 LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITERLIMIT = range(4)
 MASK_WORDS = 2
@@ -204,6 +206,8 @@ def load():
         'mpc_miqp_solve_batch': (ctypes.c_int, [ctypes.c_int32] + [ctypes.c_int32] * 5 + [_dp] * 7 + [ctypes.c_int32, _dp, _u8p, _ip,
                                                 ctypes.c_int32, _ip, ctypes.c_int64, _dp, ctypes.c_int64, _dp, _ip, _ip, _dp, _dp,
                                                 _dp, _u8p]),
+        'mpc_hit_and_run': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_int64, ctypes.c_uint64, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -221,7 +225,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_frontier_get', 'mpc_pruned_clear', 'mpc_pruned_add', 'mpc_pruned_add_device',
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
-                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch']
+                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -944,6 +948,42 @@ def miqp_solve_batch(blocks: dict, Y: numpy.ndarray, theta: numpy.ndarray, devic
     if rc != MPC_OK:
         raise MpcError(f'mpc_miqp_solve_batch failed ({rc}): {L.mpc_last_global_error().decode()}')
     return status, leaf, obj, x, lam, act
+
+
+def hit_and_run(row_off, ab_rows, start, chains: int, samples: int, n_steps: int, seed: int, device: int = 0):
+    """Hit-and-run chains in a batch of polytopes {x : A_p x <= b_p} (include/mpcombi.h, mpc_hit_and_run; the chain is specified in
+    DESIGN §3.11).  ab_rows [total_rows, n+1] = [b | A] stacked, row_off [n_poly+1], start [n_poly, n].  Returns
+    (samples [n_poly, chains, samples, n], status [n_poly, chains]) with status MPC_HR_*; a chain whose status is not MPC_HR_OK
+    has NaN samples.  The time of the kernel is left in ``hit_and_run.last_ms``.  Bad sizes raise MpcError before any launch."""
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ab = _f64(numpy.asarray(ab_rows, dtype=numpy.float64))
+    n_poly = len(off) - 1
+    st = _f64(numpy.asarray(start, dtype=numpy.float64))
+    chains, samples, n_steps, seed = int(chains), int(samples), int(n_steps), int(seed)
+    if n_poly < 0 or ab.ndim != 2 or st.ndim != 2 or st.shape[0] != n_poly:
+        raise MpcError('hit_and_run: row_off [n_poly+1], ab_rows [rows, n+1] and start [n_poly, n] do not fit together')
+    n = st.shape[1]
+    if ab.shape[1] != n + 1 or ab.shape[0] != (int(off[-1]) if n_poly >= 0 else 0):
+        raise MpcError(f'hit_and_run: ab_rows has shape {ab.shape}, expected ({int(off[-1])}, {n + 1})')
+    if not 1 <= n <= HR_MAX_DIM:
+        raise MpcError(f'hit_and_run: dimension {n} outside 1..{HR_MAX_DIM}')
+    if off[0] != 0 or numpy.any(numpy.diff(off) < 0) or numpy.any(numpy.diff(off) > HR_MAX_ROWS):
+        raise MpcError(f'hit_and_run: row_off must start at 0 and give 0..{HR_MAX_ROWS} rows per polytope')
+    if chains < 0 or samples < 1 or n_steps < 1 or samples * n_steps >= 1 << 32 or not 0 <= seed < 1 << 64:
+        raise MpcError('hit_and_run: need chains >= 0, samples >= 1, n_steps >= 1, samples * n_steps < 2^32 and a 64-bit seed')
+    L = load()
+    out = numpy.empty((n_poly, chains, samples, n))
+    status = numpy.zeros((n_poly, chains), dtype=numpy.int32)
+    ms = ctypes.c_float(0.0)
+    rc = L.mpc_hit_and_run(int(device), n, n_poly, off.ctypes.data_as(_lp), ab.ctypes.data_as(_dp), st.ctypes.data_as(_dp), chains, samples,
+                           n_steps, seed, out.ctypes.data_as(_dp), status.ctypes.data_as(_ip), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_hit_and_run failed ({rc}): {L.mpc_last_global_error().decode()}')
+    hit_and_run.last_ms = float(ms.value)
+    return out, status
+
+
+hit_and_run.last_ms = 0.0
 
 
 def facet_centres(ef_rows: numpy.ndarray, row_off: numpy.ndarray, device: int = 0):

@@ -310,4 +310,135 @@ __global__ void __launch_bounds__(256) k_evaluate(long long m, int nt, int nx, c
     x[idx] = v;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// k_hit_and_run: hit-and-run Markov chains in a batch of polytopes {x : A_p x <= b_p}, rows stacked as [b | A] (the [f | E] rows of
+// the locator) with row_off[n_poly + 1].  Reference: find_extents / hit_and_run (geometry/polytope_operations.py), one numpy chain.
+//
+// Mapping: one LANE per chain, the 64 lanes of a wavefront are 64 chains of the SAME polytope, so the row index is wave-uniform and
+// every row is fetched with scalar loads and applied to 64 chains at once.  Four wavefronts per workgroup.  The chain
+// and its random stream are specified exactly in DESIGN §3.11; a numpy replay of it is tests/hit_and_run_reference.py.
+//   theta, d: VGPRs for NT <= 32; for NT = 64 theta lives in LDS ([t][256 lanes], dynamic) and d in VGPRs -- 128 doubles of state
+//   per lane do not fit the 256 architectural VGPRs.
+// Every loop is bounded by validated inputs: n <= 64, <= 256 rows per polytope, samples * n_steps < 2^32 (mpc_hit_and_run).
+
+// Philox4x32-10 with the Random123 constants; c is the counter on entry and the output on return
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t c1 = c[1], c3 = c[3];
+        c[0] = hi1 ^ c1 ^ k0; c[1] = lo1; c[2] = hi0 ^ c3 ^ k1; c[3] = lo0;
+    }
+}
+
+// a uniform double in [0, 1) from 53 bits of two words
+__device__ __forceinline__ double hr_u53(uint32_t a, uint32_t b) { return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * 0x1p-53; }
+
+constexpr int HR_BLOCK = 256;
+template <int NT, bool THETA_LDS>
+__global__ void __launch_bounds__(HR_BLOCK) k_hit_and_run(int n, long long n_poly, long long chains, long long waves_per_poly,
+                                                          const long long *__restrict__ row_off, const double *__restrict__ ab,
+                                                          const double *__restrict__ start, uint32_t samples, uint32_t n_steps,
+                                                          uint32_t key0, uint32_t key1, double *__restrict__ out, int32_t *__restrict__ status) {
+    extern __shared__ double hr_theta_lds[];   // THETA_LDS: [NT][HR_BLOCK]
+    // the wave index is made wave-uniform explicitly, so that everything derived from it (polytope, rows) lives in SGPRs
+    const long long wave = (long long)blockIdx.x * (HR_BLOCK / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave >= n_poly * waves_per_poly) return;
+    const long long p = wave / waves_per_poly;
+    const long long k = (wave - p * waves_per_poly) * 64 + (threadIdx.x & 63);
+    const long long g = p * chains + k;
+    const int nr = n + 1, npairs = (n + 1) / 2;
+    const long long r0 = row_off[p];
+    const int m = (int)(row_off[p + 1] - r0);
+    const double *__restrict__ rows = ab + r0 * nr;
+    double th_reg[THETA_LDS ? 1 : NT], d[NT];
+    auto TH = [&](int t) -> double & {
+        if constexpr (THETA_LDS) return hr_theta_lds[t * HR_BLOCK + threadIdx.x];
+        else return th_reg[t];
+    };
+    int st = k < chains ? 0 : -1;   // -1: a lane past the last chain
+#pragma unroll
+    for (int t = 0; t < NT; ++t) if (t < n) TH(t) = st == 0 ? start[p * n + t] : 0.0;
+    const uint32_t g_lo = (uint32_t)g, g_hi = (uint32_t)((unsigned long long)g >> 32);
+    const uint32_t total = samples * n_steps;
+    uint32_t until_sample = n_steps, q = 0;
+    for (uint32_t s = 0; s < total; ++s) {
+        if (!__any(st == 0)) break;
+        if (st == 0) {
+            // direction: Box-Muller pairs from calls j = 0 .. npairs-1, normalised
+#pragma unroll
+            for (int jp = 0; jp < (NT + 1) / 2; ++jp) {
+                if (jp < npairs) {
+                    uint32_t c[4] = {g_lo, g_hi, s, (uint32_t)jp};
+                    philox4x32_10(c, key0, key1);
+                    const double u1 = 1.0 - hr_u53(c[0], c[1]), u2 = hr_u53(c[2], c[3]);
+                    const double rad = sqrt(-2.0 * log(u1));
+                    double sn, cs;
+                    sincospi(2.0 * u2, &sn, &cs);
+                    d[2 * jp] = rad * cs;
+                    if (2 * jp + 1 < NT) d[2 * jp + 1] = 2 * jp + 1 < n ? rad * sn : 0.0;
+                }
+            }
+            double nn = 0.0;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) if (t < n) nn += d[t] * d[t];
+            const double nrm = sqrt(nn);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) if (t < n) d[t] = d[t] / nrm;
+            // one pass over the rows: slack s_i = b_i - a_i theta and rate g_i = a_i d give the chord [t_lo, t_hi]
+            double t_hi = INFINITY, t_lo = -INFINITY, smin = INFINITY;
+            for (int i = 0; i < m; ++i) {
+                const double *a = rows + (long long)i * nr;
+                double sv = a[0], gv = 0.0;
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (t < n) { sv = fma(-a[1 + t], TH(t), sv); gv = fma(a[1 + t], d[t], gv); }
+                smin = fmin(smin, sv);
+                const double ratio = sv / gv;
+                if (gv > 0.0) t_hi = fmin(t_hi, ratio);
+                else if (gv < 0.0) t_lo = fmax(t_lo, ratio);
+            }
+            if (s == 0 && smin < 0.0) st = MPC_HR_OUTSIDE;
+            else if (t_hi == INFINITY || t_lo == -INFINITY) st = MPC_HR_UNBOUNDED;
+            else {
+                uint32_t c[4] = {g_lo, g_hi, s, (uint32_t)npairs};
+                philox4x32_10(c, key0, key1);
+                const double t_step = t_lo + hr_u53(c[0], c[1]) * (t_hi - t_lo);
+                // acceptance: min_i (s_i - t g_i) >= 0, from the same s_i, g_i (recomputed bit for bit: same operations, same order)
+                double worst = INFINITY;
+                for (int i = 0; i < m; ++i) {
+                    const double *a = rows + (long long)i * nr;
+                    double sv = a[0], gv = 0.0;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        if (t < n) { sv = fma(-a[1 + t], TH(t), sv); gv = fma(a[1 + t], d[t], gv); }
+                    worst = fmin(worst, sv - t_step * gv);
+                }
+                if (worst >= 0.0) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) if (t < n) TH(t) = TH(t) + t_step * d[t];
+                }
+            }
+        }
+        if (--until_sample == 0) {
+            until_sample = n_steps;
+            if (st == 0) {
+                double *o = out + ((size_t)g * samples + q) * n;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) if (t < n) o[t] = TH(t);
+            }
+            ++q;
+        }
+    }
+    if (st < 0) return;
+    if (st > 0) {
+        double *o = out + (size_t)g * samples * n;
+        for (long long i = 0; i < (long long)samples * n; ++i) o[i] = __longlong_as_double(0x7ff8000000000000ll);
+    }
+    status[g] = st;
+}
+
 }  // namespace mpc

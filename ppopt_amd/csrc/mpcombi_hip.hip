@@ -4615,6 +4615,80 @@ extern "C" int mpc_facet_centres(int32_t device, int32_t n_t, int64_t n_regions,
     return MPC_OK;
 }
 
+// ---- hit-and-run chains in a batch of polytopes (k_hit_and_run, locate.hpp) -----------------------------------------------
+template <int NT, bool L>
+static void hr_launch(dim3 g, size_t lds, int n, long long n_poly, long long chains, long long wpp, const DevBuf &off, const DevBuf &ab,
+                      const DevBuf &st0, uint32_t samples, uint32_t n_steps, uint32_t k0, uint32_t k1, DevBuf &out, DevBuf &status) {
+    hipLaunchKernelGGL((k_hit_and_run<NT, L>), g, dim3(HR_BLOCK), lds, nullptr, n, n_poly, chains, wpp, off.as<long long>(), ab.as<double>(),
+                       st0.as<double>(), samples, n_steps, k0, k1, out.as<double>(), status.as<int32_t>());
+}
+
+extern "C" int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const int64_t *row_off, const double *ab_rows, const double *start,
+                               int64_t chains, int64_t samples, int64_t n_steps, uint64_t seed, double *out, int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (n < 1 || n > 64) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: n must lie in 1..64");
+    if (n_poly < 0 || chains < 0 || samples < 1 || n_steps < 1) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: bad sizes");
+    if (samples >= (1ll << 32) || n_steps >= (1ll << 32) || (unsigned long long)samples * (unsigned long long)n_steps >= (1ull << 32))
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: samples * n_steps must stay below 2^32");
+    if (!row_off) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing row_off");
+    if (row_off[0] != 0) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: row_off[0] must be 0");
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int64_t r = row_off[p + 1] - row_off[p];
+        if (r < 0 || r > 256) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: a polytope has more than 256 rows (or row_off decreases)");
+    }
+    if (n_poly == 0 || chains == 0) return MPC_OK;
+    const long long rows = row_off[n_poly];
+    if ((rows && !ab_rows) || !start || !out || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing array");
+    const long long wpp = (chains + 63) / 64;
+    if (n_poly > (1ll << 40) / wpp) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains");
+    const long long n_blocks = (n_poly * wpp + HR_BLOCK / 64 - 1) / (HR_BLOCK / 64);
+    if (n_blocks > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains for one launch");
+    int ndev = 0;
+    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const size_t n_chain = (size_t)n_poly * chains, n_out = n_chain * samples * n;
+    const int nt = n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+    const size_t lds = nt == 64 ? (size_t)64 * HR_BLOCK * sizeof(double) : 0;
+    if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_hit_and_run<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DevBuf d_off, d_ab, d_st0, d_out, d_status;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
+    chk(d_off.ensure((size_t)(n_poly + 1) * 8, nullptr)); chk(d_ab.ensure(std::max<size_t>(8, (size_t)rows * (n + 1) * 8), nullptr));
+    chk(d_st0.ensure((size_t)n_poly * n * 8, nullptr)); chk(d_out.ensure(n_out * 8, nullptr)); chk(d_status.ensure(n_chain * 4, nullptr));
+    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
+    if (e == hipSuccess) {
+        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_poly + 1) * 8, hipMemcpyHostToDevice));
+        if (rows) chk(hipMemcpy(d_ab.p, ab_rows, (size_t)rows * (n + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_st0.p, start, (size_t)n_poly * n * 8, hipMemcpyHostToDevice));
+    }
+    if (e == hipSuccess) {
+        const dim3 g((unsigned)n_blocks);
+        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), sm = (uint32_t)samples, ns = (uint32_t)n_steps;
+        chk(hipEventRecord(e0, nullptr));
+        switch (nt) {
+            case 2: hr_launch<2, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 4: hr_launch<4, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 8: hr_launch<8, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 16: hr_launch<16, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 32: hr_launch<32, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            default: hr_launch<64, true>(g, lds, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+        }
+        chk(hipGetLastError());
+        chk(hipEventRecord(e1, nullptr));
+        chk(hipMemcpy(out, d_out.p, n_out * 8, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(status, d_status.p, n_chain * 4, hipMemcpyDeviceToHost));
+        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
+    }
+    (void)hipDeviceSynchronize();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    for (DevBuf *bf : {&d_off, &d_ab, &d_st0, &d_out, &d_status}) bf->release();
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string("mpc_hit_and_run: ") + hipGetErrorString(e));
+    return MPC_OK;
+}
+
 // ---- batched LPs ------------------------------------------------------------------------------------------------
 static int lp_batch_impl(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b,
                          int32_t shared_b, const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x,

@@ -1,0 +1,18 @@
+"""Polytope: the pair {x : A x <= b} (reference: geometry/polytope.py)."""
+import numpy
+
+
+class Polytope:
+    """A convex polytope {x : A x <= b} in n dimensions."""
+
+    def __init__(self, A: numpy.ndarray, b: numpy.ndarray):
+        self.A = A
+        self.b = b
+
+    def rows(self):
+        """([b | A] as one [m, n+1] float64 array) -- the stacking of mpc_hit_and_run and of the locator's [f | E] rows."""
+        b = numpy.asarray(self.b, dtype=numpy.float64).reshape(-1, 1)
+        A = numpy.asarray(self.A, dtype=numpy.float64)
+        if A.ndim != 2 or A.shape[0] != b.shape[0]:
+            raise ValueError(f'Polytope: A has shape {A.shape} but b has {b.shape[0]} rows')
+        return numpy.hstack([b, A])

@@ -1,9 +1,35 @@
 """Solution: the program plus the list of critical regions (reference: solution.py:15-199)."""
+import time
+from dataclasses import dataclass, field
 from typing import List, Optional
 
 import numpy
 
 from .critical_region import CriticalRegion
+
+
+@dataclass
+class SampleCheck:
+    """Report of Solution.sample_check.  Global part: points drawn uniformly from the parameter set; per-region part: points drawn
+    uniformly inside every full-dimensional region."""
+    n_samples: int                  # points of the parameter set
+    n_feasible: int                 # ... where the program is feasible
+    n_uncovered: int                # feasible, but no region located
+    n_wrong: int                    # located, but the located law is not optimal (objective gap or a violated row)
+    n_spurious: int                 # located where the program is infeasible
+    n_spurious_bad: int             # ... and the law violates a program row by more than tol
+    covered_fraction: float         # located share of the feasible points
+    max_obj_gap: float              # largest |obj(x_r) - obj*| / (1 + |obj*|) over located feasible points
+    max_x_err: Optional[float]      # QPs: largest |x_r - x*|
+    uncovered_points: numpy.ndarray = field(repr=False)    # [<= 1000, n_theta]
+    n_regions_sampled: int = 0
+    n_regions_not_sampled: int = 0  # radius <= 1e-8, more than 256 rows, or no Chebyshev centre
+    failing_regions: List[int] = field(default_factory=list)
+    seconds: float = 0.0
+
+    @property
+    def ok(self) -> bool:
+        return self.n_uncovered == 0 and self.n_wrong == 0 and self.n_spurious_bad == 0 and not self.failing_regions
 
 
 class Solution:
@@ -295,6 +321,113 @@ class Solution:
             if abs(there - opt) > tol * (1.0 + abs(opt)) or own < opt - tol * (1.0 + abs(opt)):
                 return False
         return True
+
+    # ---- coverage and optimality away from the centres: uniform samples of the parameter set and of every region ------------
+    def _objective_rows(self, X: numpy.ndarray, T: numpy.ndarray) -> numpy.ndarray:
+        """program.evaluate_objective for every row of X [m, n_x] at T [m, n_theta]."""
+        P = self.program
+        v = X @ numpy.asarray(P.c, dtype=float).ravel() + numpy.einsum('ij,ij->i', T @ numpy.asarray(P.H, dtype=float).T, X)
+        v = v + float(numpy.asarray(P.c_c).ravel()[0]) + T @ numpy.asarray(P.c_t, dtype=float).ravel()
+        v = v + 0.5 * numpy.einsum('ij,ij->i', T @ numpy.asarray(P.Q_t, dtype=float), T)
+        if hasattr(P, 'Q'):
+            v = v + 0.5 * numpy.einsum('ij,ij->i', X @ numpy.asarray(P.Q, dtype=float), X)
+        return v
+
+    def _row_violation(self, X: numpy.ndarray, T: numpy.ndarray) -> numpy.ndarray:
+        """Largest violation of a program row A x <= b + F theta (equalities in both directions) by every row of X."""
+        P = self.program
+        r = X @ P.A.T - (P.b.reshape(1, -1) + T @ P.F.T)
+        eq = list(P.equality_indices)
+        if eq:
+            r[:, eq] = numpy.abs(r[:, eq])
+        return numpy.max(r, axis=1, initial=0.0)
+
+    def sample_check(self, num_samples: int = 100_000, per_region: int = 8, seed: int = 0, tol: float = 1e-6, device: int = 0,
+                     n_steps: Optional[int] = None) -> SampleCheck:
+        """Does the solution cover the feasible parameter set, and is every region's law optimal away from its centre?
+        Global part: ``num_samples`` points drawn uniformly from {A_t theta <= b_t} (geometry.sample_program_theta_space), the
+        program solved at all of them (one solve_theta_batch) and the points located (one get_region_batch); a feasible point in
+        no region is uncovered, a located point whose law is worse than the optimum (objective gap above tol (1 + |obj*|) or a row
+        violated by more than tol) is wrong.  Per-region part: ``per_region`` hit-and-run samples in every full-dimensional region
+        (one mpc_hit_and_run over all regions, from the Chebyshev centres), the same test on the region's own law; for
+        mixed-integer solutions the rule of _verify_mixed_integer (own objective not below the optimum, located winner equal to it).
+        MpcError for an unbounded parameter set and wherever solve_theta_batch raises."""
+        from . import _lib
+        from .geometry import polytope_operations as po
+        t0 = time.perf_counter()
+        P = self.program
+        steps = po.DEFAULT_N_STEPS if n_steps is None else int(n_steps)
+        mi = self.is_mixed_integer_sol()
+        is_qp = hasattr(P, 'Q') and not mi
+        scale = lambda o: tol * (1.0 + numpy.abs(o))
+
+        # global part: coverage of the parameter set
+        th = po.sample_program_theta_space(P, num_samples, n_steps=steps, seed=seed, device=device)
+        det = P.solve_theta_batch(th)
+        feas = numpy.array([d is not None for d in det], dtype=bool)
+        if self.critical_regions:
+            x_r, loc = self.evaluate_batch(th, device)
+        else:
+            x_r, loc = numpy.full((len(th), 0), numpy.nan), numpy.full(len(th), -1, dtype=numpy.int64)
+        located = loc >= 0
+        uncovered = feas & ~located
+        max_gap, max_x, n_wrong, n_spur_bad = 0.0, (0.0 if is_qp else None), 0, 0
+        idx = numpy.flatnonzero(located & feas)
+        if len(idx):
+            opt = numpy.array([det[i].obj for i in idx])
+            obj_r = self._objective_rows(x_r[idx], th[idx])
+            viol = self._row_violation(x_r[idx], th[idx])
+            gap = numpy.abs(obj_r - opt)
+            max_gap = float(numpy.max(gap / (1.0 + numpy.abs(opt))))
+            n_wrong = int(numpy.count_nonzero((gap > scale(opt)) | (viol > tol)))
+            if is_qp:
+                max_x = float(numpy.max(numpy.abs(x_r[idx] - numpy.vstack([det[i].sol.ravel() for i in idx]))))
+        spur = numpy.flatnonzero(located & ~feas)
+        if len(spur):
+            n_spur_bad = int(numpy.count_nonzero(self._row_violation(x_r[spur], th[spur]) > tol))
+
+        # per-region part: each region's own law at uniform points inside it
+        failing, n_sampled, n_not = set(), 0, len(self.critical_regions)
+        if self.critical_regions and per_region > 0:
+            loc_obj = self.locator(device)
+            row_off, ef, xlaw = loc_obj.row_off, loc_obj.ef, loc_obj.xlaw
+            centres, radii = self.chebyshev_centres(device)
+            counts = numpy.diff(row_off)
+            ok_r = numpy.flatnonzero(numpy.isfinite(radii) & (radii > po.FULL_DIM_RADIUS) & (counts <= _lib.HR_MAX_ROWS) & (counts > 0))
+            if len(ok_r):
+                sub_off = numpy.concatenate([[0], numpy.cumsum(counts[ok_r])]).astype(numpy.int64)
+                sub_rows = numpy.repeat(row_off[ok_r] - sub_off[:-1], counts[ok_r]) + numpy.arange(int(sub_off[-1]))
+                pts, status = _lib.hit_and_run(sub_off, ef[sub_rows], centres[ok_r], per_region, 1, steps, seed, device)
+                good = status == _lib.MPC_HR_OK                                   # [R_s, per_region]
+                n_sampled = int(numpy.count_nonzero(good.all(axis=1)))
+                owner = numpy.repeat(ok_r, per_region)[good.ravel()]
+                T = pts[:, :, 0, :].reshape(-1, pts.shape[-1])[good.ravel()]
+                det_r = P.solve_theta_batch(T)
+                feas_r = numpy.array([d is not None for d in det_r], dtype=bool)
+                for r in owner[~feas_r]:
+                    failing.add(int(r))          # a region's interior lies in the feasible set
+                fi = numpy.flatnonzero(feas_r)
+                if len(fi):
+                    opt = numpy.array([det_r[i].obj for i in fi])
+                    Tf = T[fi]
+                    own_law = xlaw[owner[fi]]                                    # [k, n_x, n_t + 1]
+                    X_own = own_law[:, :, 0] + numpy.einsum('kij,kj->ki', own_law[:, :, 1:], Tf)
+                    own = self._objective_rows(X_own, Tf)
+                    if mi:
+                        x_w, loc_w = self.evaluate_batch(Tf, device)
+                        there = numpy.where(loc_w >= 0, self._objective_rows(numpy.nan_to_num(x_w), Tf), numpy.nan)
+                        bad = (own < opt - scale(opt)) | (loc_w < 0) | ~(numpy.abs(there - opt) <= scale(opt))
+                    else:
+                        bad = (numpy.abs(own - opt) > scale(opt)) | (self._row_violation(X_own, Tf) > tol)
+                    failing.update(int(r) for r in owner[fi][bad])
+            n_not = len(self.critical_regions) - n_sampled
+        n_feas = int(numpy.count_nonzero(feas))
+        return SampleCheck(n_samples=len(th), n_feasible=n_feas, n_uncovered=int(numpy.count_nonzero(uncovered)), n_wrong=n_wrong,
+                           n_spurious=len(spur), n_spurious_bad=n_spur_bad,
+                           covered_fraction=float(numpy.count_nonzero(located & feas) / n_feas) if n_feas else 1.0,
+                           max_obj_gap=max_gap, max_x_err=max_x, uncovered_points=th[uncovered][:1000].copy(),
+                           n_regions_sampled=n_sampled, n_regions_not_sampled=n_not, failing_regions=sorted(failing),
+                           seconds=time.perf_counter() - t0)
 
     def materialize(self) -> 'Solution':
         """Cuts every field of every region out of the per-level arrays the device returned (the regions a solve hands back are lazy
