@@ -78,10 +78,6 @@ struct LevelCounters {
     unsigned long long r2_not_t0, r2_t1;  // k_region2: ~(wall clock of the first wavefront's start), wall clock of the last one's end
     unsigned long long xq_pivots;   // k_xq / k_xq_grouped: product-form iterations executed (each reads one column and one row of the parent's record)
     unsigned int xq_thread, pad_xq;  // candidates of the last level's quick test decided by k_xq_thread (round 5); pad_xq: ... of which from another parent's record
-    // Round 6: the queue between the theta stage and the region stage of a large last level.  k_theta2 appends every candidate it finds
-    // optimal (q_tail; the entries live in the level's opt_list, -1 until written), region wavefronts claim positions (work_r2 is the
-    // head); q_closed is raised by a one-thread launch behind the theta kernel: the tail is final.
-    unsigned int q_tail, q_closed, q_fault, q_early;   // q_fault: a claimed entry never arrived (never observed); q_early: regions built by the early launch
     unsigned int x_second, pad_x2;   // k_x2 (round 6): doubtful cached runs repeated from D0 inside the kernel (DictCache::second_max)
 };
 
@@ -683,16 +679,16 @@ __device__ __forceinline__ int block_exclusive_scan_1024(int v, int *total_out) 
     __syncthreads();
     return incl - v + wsum[w];
 }
-// The same scan of 1024 items by 1024 / IT threads, IT consecutive items per thread (IT = 4: four-wavefront workgroups, which find room
-// on a compute unit that a persistent kernel's wavefronts occupy; a 16-wavefront workgroup waits there until a whole unit drains).
-template <int IT>
-__device__ __forceinline__ void block_exclusive_scan_it(const int (&v)[IT], int (&ex)[IT], int *total_out) {
-    constexpr int NW = 16 / IT;
+// The same scan of 1024 items by 1024 / SCAN_IT threads, SCAN_IT consecutive items per thread: four-wavefront workgroups, which find room
+// on a compute unit that a persistent kernel's wavefronts occupy (a 16-wavefront workgroup waits there until a whole unit drains).
+constexpr int SCAN_IT = 4;
+__device__ __forceinline__ void block_exclusive_scan_it(const int (&v)[SCAN_IT], int (&ex)[SCAN_IT], int *total_out) {
+    constexpr int NW = 16 / SCAN_IT;
     __shared__ int wsum_it[NW];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int s = 0;
 #pragma unroll
-    for (int k = 0; k < IT; ++k) s += v[k];
+    for (int k = 0; k < SCAN_IT; ++k) s += v[k];
     int incl = s;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); if (lane >= off) incl += o; }
@@ -704,48 +700,45 @@ __device__ __forceinline__ void block_exclusive_scan_it(const int (&v)[IT], int 
     if (total_out && threadIdx.x == 64 * NW - 1) *total_out = base + incl;
     int run = base + incl - s;
 #pragma unroll
-    for (int k = 0; k < IT; ++k) { ex[k] = run; run += v[k]; }
+    for (int k = 0; k < SCAN_IT; ++k) { ex[k] = run; run += v[k]; }
     __syncthreads();
 }
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_scan_block_sums(const int32_t *__restrict__ in, long long n, int32_t *__restrict__ sums) {
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_scan_block_sums(const int32_t *__restrict__ in, long long n, int32_t *__restrict__ sums) {
     __shared__ int tot;
-    const long long i0 = blockIdx.x * (long long)SCAN_BLOCK + (long long)threadIdx.x * IT;
-    int v[IT], ex[IT];
+    const long long i0 = blockIdx.x * (long long)SCAN_BLOCK + (long long)threadIdx.x * SCAN_IT;
+    int v[SCAN_IT], ex[SCAN_IT];
 #pragma unroll
-    for (int k = 0; k < IT; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-    block_exclusive_scan_it<IT>(v, ex, &tot);
+    for (int k = 0; k < SCAN_IT; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
+    block_exclusive_scan_it(v, ex, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 // one block: exclusive scan of up to nb block sums in place (chunked), total -> *total
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_scan_sums(int32_t *__restrict__ sums, int nb, int32_t *__restrict__ total) {
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_scan_sums(int32_t *__restrict__ sums, int nb, int32_t *__restrict__ total) {
     __shared__ int tot;
     int carry = 0;
     for (int base = 0; base < nb; base += SCAN_BLOCK) {
-        const int i0 = base + (int)threadIdx.x * IT;
-        int v[IT], ex[IT];
+        const int i0 = base + (int)threadIdx.x * SCAN_IT;
+        int v[SCAN_IT], ex[SCAN_IT];
 #pragma unroll
-        for (int k = 0; k < IT; ++k) v[k] = i0 + k < nb ? sums[i0 + k] : 0;
-        block_exclusive_scan_it<IT>(v, ex, &tot);
+        for (int k = 0; k < SCAN_IT; ++k) v[k] = i0 + k < nb ? sums[i0 + k] : 0;
+        block_exclusive_scan_it(v, ex, &tot);
 #pragma unroll
-        for (int k = 0; k < IT; ++k) if (i0 + k < nb) sums[i0 + k] = ex[k] + carry;
+        for (int k = 0; k < SCAN_IT; ++k) if (i0 + k < nb) sums[i0 + k] = ex[k] + carry;
         carry += tot;
         __syncthreads();
     }
     if (threadIdx.x == 0) *total = carry;
 }
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_scan_apply(const int32_t *__restrict__ in, int32_t *__restrict__ out, long long n,
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_scan_apply(const int32_t *__restrict__ in, int32_t *__restrict__ out, long long n,
                                                     const int32_t *__restrict__ sums) {
-    const long long i0 = blockIdx.x * (long long)SCAN_BLOCK + (long long)threadIdx.x * IT;
-    int v[IT], ex[IT];
+    const long long i0 = blockIdx.x * (long long)SCAN_BLOCK + (long long)threadIdx.x * SCAN_IT;
+    int v[SCAN_IT], ex[SCAN_IT];
 #pragma unroll
-    for (int k = 0; k < IT; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-    block_exclusive_scan_it<IT>(v, ex, nullptr);
+    for (int k = 0; k < SCAN_IT; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
+    block_exclusive_scan_it(v, ex, nullptr);
     const int add = sums[blockIdx.x];
 #pragma unroll
-    for (int k = 0; k < IT; ++k) if (i0 + k < n) out[i0 + k] = ex[k] + add;
+    for (int k = 0; k < SCAN_IT; ++k) if (i0 + k < n) out[i0 + k] = ex[k] + add;
 }
 
 // ---- deterministic multi-class partition by status -----------------------------------------------------------------------
@@ -753,15 +746,14 @@ MPC_GLOBAL void MPC_LB(1024 / IT) k_scan_apply(const int32_t *__restrict__ in, i
 // frontier order (lists + c*n) and their lengths, instead of one flag/scan/scatter round per class.
 constexpr int PART_CLASSES = 4;
 __device__ __forceinline__ int part_class(unsigned long long spec, int st) { return (int)((spec >> (4 * (st & 15))) & 15ull); }
-// 1024 statuses per workgroup of 1024 / IT threads: sub-chunk j of the workgroup is the 1024 / IT statuses from j * (1024 / IT)
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_part_count(const uint8_t *__restrict__ status, long long n, unsigned long long spec,
+// 1024 statuses per workgroup of 1024 / SCAN_IT threads: sub-chunk j of the workgroup is the 1024 / SCAN_IT statuses from j * (1024 / SCAN_IT)
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_part_count(const uint8_t *__restrict__ status, long long n, unsigned long long spec,
                                                      int32_t *__restrict__ blockcounts, int nb) {
-    constexpr int BT = 1024 / IT, NW = BT / 64;
+    constexpr int BT = 1024 / SCAN_IT, NW = BT / 64;
     __shared__ int wc[16][PART_CLASSES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-    for (int j = 0; j < IT; ++j) {
+    for (int j = 0; j < SCAN_IT; ++j) {
         const long long i = blockIdx.x * 1024LL + j * BT + threadIdx.x;
         const int cls = i < n ? part_class(spec, status[i]) : 15;
 #pragma unroll
@@ -778,33 +770,31 @@ MPC_GLOBAL void MPC_LB(1024 / IT) k_part_count(const uint8_t *__restrict__ statu
     }
 }
 // grid = PART_CLASSES blocks: exclusive scan of each class's block counts in place, totals[c] = list length
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_part_sums(int32_t *__restrict__ blockcounts, int nb, int32_t *__restrict__ totals) {
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_part_sums(int32_t *__restrict__ blockcounts, int nb, int32_t *__restrict__ totals) {
     __shared__ int tot;
     int32_t *sums = blockcounts + (size_t)blockIdx.x * nb;
     int carry = 0;
     for (int base = 0; base < nb; base += SCAN_BLOCK) {
-        const int i0 = base + (int)threadIdx.x * IT;
-        int v[IT], ex[IT];
+        const int i0 = base + (int)threadIdx.x * SCAN_IT;
+        int v[SCAN_IT], ex[SCAN_IT];
 #pragma unroll
-        for (int k = 0; k < IT; ++k) v[k] = i0 + k < nb ? sums[i0 + k] : 0;
-        block_exclusive_scan_it<IT>(v, ex, &tot);
+        for (int k = 0; k < SCAN_IT; ++k) v[k] = i0 + k < nb ? sums[i0 + k] : 0;
+        block_exclusive_scan_it(v, ex, &tot);
 #pragma unroll
-        for (int k = 0; k < IT; ++k) if (i0 + k < nb) sums[i0 + k] = ex[k] + carry;
+        for (int k = 0; k < SCAN_IT; ++k) if (i0 + k < nb) sums[i0 + k] = ex[k] + carry;
         carry += tot;
         __syncthreads();
     }
     if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
-template <int IT>
-MPC_GLOBAL void MPC_LB(1024 / IT) k_part_scatter(const uint8_t *__restrict__ status, long long n, unsigned long long spec,
+MPC_GLOBAL void MPC_LB(1024 / SCAN_IT) k_part_scatter(const uint8_t *__restrict__ status, long long n, unsigned long long spec,
                                                        const int32_t *__restrict__ blockbase, int nb, int32_t *__restrict__ lists) {
-    constexpr int BT = 1024 / IT, NW = BT / 64;
+    constexpr int BT = 1024 / SCAN_IT, NW = BT / 64;
     __shared__ int wc[16][PART_CLASSES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int cls[IT], within[IT];
+    int cls[SCAN_IT], within[SCAN_IT];
 #pragma unroll
-    for (int j = 0; j < IT; ++j) {
+    for (int j = 0; j < SCAN_IT; ++j) {
         const long long i = blockIdx.x * 1024LL + j * BT + threadIdx.x;
         cls[j] = i < n ? part_class(spec, status[i]) : 15;
         within[j] = 0;
@@ -817,7 +807,7 @@ MPC_GLOBAL void MPC_LB(1024 / IT) k_part_scatter(const uint8_t *__restrict__ sta
     }
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < IT; ++j) {
+    for (int j = 0; j < SCAN_IT; ++j) {
         if (cls[j] < PART_CLASSES) {
             const long long i = blockIdx.x * 1024LL + j * BT + threadIdx.x;
             int before = 0;
@@ -914,10 +904,6 @@ MPC_GLOBAL void MPC_LB(256) k_fetch_many(const FetchEntry *__restrict__ tab) {
 MPC_GLOBAL void k_publish_words(const unsigned int *__restrict__ src, unsigned int *__restrict__ dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
-MPC_GLOBAL void MPC_LB(256) k_fill_i32(int32_t *__restrict__ dst, long long n, int32_t v) {
-    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256ll) dst[i] = v;
-}
-MPC_GLOBAL void k_set_u32(unsigned int *__restrict__ dst, unsigned int v) { if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_store(dst, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
 // two sources, one after the other in dst (a level's counters and its list lengths: one launch)
 MPC_GLOBAL void k_publish_words2(const unsigned int *__restrict__ src1, int n1, const unsigned int *__restrict__ src2, int n2, unsigned int *__restrict__ dst) {
     for (int i = threadIdx.x; i < n1 + n2; i += blockDim.x) dst[i] = i < n1 ? src1[i] : src2[i - n1];

@@ -275,49 +275,38 @@ struct mpc_handle {
     hipStream_t stream2 = nullptr;   // side stream: retry kernels of few long-running wavefronts overlap the main pipeline
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_xfork = nullptr, ev_xjoin = nullptr;
     hipStream_t stream3 = nullptr;   // region stage of a level, launched under its (x,theta) stage
-    hipStream_t stream4 = nullptr;   // round 6: the drain launch of the queue form of the region stage (beside the early launch on stream3)
-    hipEvent_t ev_rjoin2 = nullptr, ev_nth = nullptr;   // its completion; "the theta list's length has been published"
+    hipStream_t stream4 = nullptr;   // round 6: k_x1's stream (see ev_x1go)
     // Round 6: the streamed one-step dictionaries of a storing level (k_x1) run on stream4 BESIDE the end of their level (children, pruned
     // masks, counters) and the next level's KKT kernel -- nothing of those reads a dictionary; the first kernel of the next level that
     // does waits for ev_x1done (x1_join).  MPC_X1_DEFER=0: in line, as round 5.  Not when a profile asks for per-kernel event times.
     hipEvent_t ev_x1go = nullptr, ev_x1done = nullptr;
     bool x1_pending = false;
-    std::function<int()> x1_stash;   // x1_defer >= 2: the deferred k_x1 launch, issued by x1_flush behind the level's last kernels
-    int x1_defer = 1;           // 1: k_x1 on its own stream from the plan pass on; 2: issued behind the level's last kernels (measured: the children stage gets its 0.26 ms back, the next level's KKT kernel loses 0.40 beside k_x1 -- its W gathers live in the L2 that k_x1 streams through: config 4 3.89 -> 3.95 ms, config 3 4.17 -> 4.27); 0: in line
-    int x1_lds_cap = 0;
+    int x1_defer = 1;           // 1: k_x1 on its own stream from the plan pass on; 0: in line
     int xq_skip_below = 100000;  // the last level's product-form quick test leaves a list shorter than this to k_x2 when a tableau row is one lane's (MPC_XQ_SKIP_BELOW; 0: never).  Measured: config 3 (62 k left over) 4.26 -> 4.18 ms, config 4 (2.7 k) unchanged -- its last level ends with the region kernel
     int x_second_max = 1024;     // k_x2: a level's budget of doubtful cached runs repeated from D0 in the kernel (MPC_X_SECOND_MAX; 0: all go to the LDS engine)
     double x_fresh_limit = 1e6;   // k_x2: growth up to which a run from D0 decides (DictCache::fresh_limit; MPC_X_FRESH_LIMIT=0: GROWTH_SAFE)
     int kkt_spread_threads = 1 << 19;   // classic path: the spread form while candidates x KKT_SPREAD stays below this (MPC_KKT_SPREAD_THREADS)
     int kkt_spread = 1;         // small levels: k_kkt_thread with KKT_SPREAD lanes per candidate (MPC_KKT_SPREAD=0: one lane)
-    int helper_it = 4;          // scan / partition helpers: 4 = four-wavefront workgroups of 4 items per thread, 1 = 1024-thread workgroups (MPC_HELPER_IT)
     // Round 6: the pruned list bucketed by smallest non-equality member (kernels.hpp, k_children_count_b), rebuilt at the start of every level
     // whose children stage is large enough to pay for it (MPC_PRUNED_BUCKET_MIN: parents x pruned sets; 0 = never)
     DevBuf pruned_b, pruned_head;
     double pruned_bucket_min = 2.0e7;
     long long pruned_bucket_np = 1024;   // MPC_PRUNED_BUCKET_NP: ... and at least this many pruned sets (tests: 1)
-    int r2_early = 0;                // MPC_R2_EARLY=1: the queue form of a large last level's region stage (measured slower, DESIGN 6h: off; tests switch it on)
-    long long r2_early_min = 65536;  // MPC_R2_EARLY_MIN: smallest level that takes the queue form
-    int r2_early_wpc = 0, r2_early_spin = 200000, r2_early_thw = 1, r2_early_prio = 3;   // ... MPC_R2_EARLY_THW: theta wavefronts per SIMD beside the early launch; MPC_R2_EARLY_PRIO: their issue priority   // MPC_R2_EARLY_WPC: wavefronts per CU of the early launch; MPC_R2_EARLY_SPIN: looks at an empty queue before a wavefront leaves
-    long long n_r2_early = 0;        // regions the early launch built in the last level run (statistics)
-    hipEvent_t ev_rfork = nullptr, ev_rjoin = nullptr, ev_rgo = nullptr;
+    hipEvent_t ev_rjoin = nullptr, ev_rgo = nullptr;
     bool no_roverlap = false;        // MPC_NO_ROVERLAP=1 / mpc_set_region_overlap(h, 0): region stage after the (x,theta) stage (no overlap)
     bool r3_dirty = false;           // a region kernel launched on stream3 has not been joined by a completed level yet
     int test_spare = 0;              // MPC_TEST_SPARE=N (tests): N fewer spare region slots than the overlapped launch would reserve
     int rsplit_max = 4;              // MPC_RSPLIT_MAX: most wavefronts that share one optimal candidate in k_region2 (power of two, <= 16; measured:
                                      // 8 and 16 shorten no level of config 4 or 2 -- every wavefront repeats the row build and the Chebyshev LP, 40 % of
                                      // a region at 4 -- and move the facet list of one sliver region)
-    bool no_lean = false;            // MPC_NO_LEAN=1: large levels read every list length back (round-2 behaviour); default: only the lengths the
-                                     // host needs to size the region stage are read back, the other stages take theirs from device memory
     bool theta_open = false;         // the parameter set is open in some direction (or the program has equality rows only): the reference's
                                      // optimality LP can be unbounded -> k_recession behind every verdict stage, no overlapped region launch,
-                                     // no level without host round trips, no shared launches (MPC_NO_RECESSION=1: round-3 behaviour, A/B)
+                                     // no level without host round trips, no shared launches
     int xqg_per_cu = XQG_WAVES;      // MPC_XQG_PER_CU: workgroups (of four wavefronts) per CU of the persistent k_xq_grouped launch
     int x2_wpc = 12, x2_div = 16, xq_wpc = 20;    // MPC_X2_WPC (most) / MPC_X2_DIV (items per wavefront) / MPC_XQ_WPC: wavefronts per CU of the persistent
                                      // k_x2 / k_xq launches (round 3: 16 and 32 whatever the size of the level)
     std::vector<std::pair<void *, size_t>> parked_blocks;   // device blocks the level buffers have outgrown (DevBuf::parked), given back by graveyard_flush
     bool region_side_stream = false; // this level's k_region2 launch ran on the side stream, under the (x,theta) stage (mpc_level_stats)
-    bool r3_fork_event = false;      // MPC_R3_FORK=1: the region stream starts behind an event of the main stream (round-3 form; A/B)
     int r2_cap_pct = 100;            // MPC_R2_CAP: share (per cent) of k_region2's wave slots an overlapped one-wave-per-candidate launch may take
     bool no_fetch_kernel = false;    // MPC_NO_FETCH_KERNEL=1: the solve loop fetches the records of a level that did not stream with copy commands and waits (A/B)
     bool no_spec_tail = false;       // MPC_NO_SPEC_TAIL=1: a large level waits for the second partition and for the region kernel's give-up count before
@@ -333,10 +322,6 @@ struct mpc_handle {
                                      // (9,880 candidates) 0.72 -> 0.67 ms; level 4 (181 k) 1.51 -> 1.58: there the stage fills the GPU before the region kernel's long wavefronts are placed
                                      // (region kernel 0.48 -> 0.60 ms, the stage itself 0.93 -> 1.03) -- large levels keep the region launch first
     hipEvent_t ev_part = nullptr;
-    bool no_batch_plans = true;      // MPC_BATCH_PLANS=1 switches the one-step plans on in the shared launches (tests).  Measured on the bench enumeration (64 sub-programs, 16-column
-                                     // records of 3.5 KB) and on 128 small programs: SLOWER with them (121 against 108 ms; 20.9 against 19.6 ms, device 10.1 against 8.6) -- the register
-                                     // simplex on so small a record costs less than the plan pass's batch of dependent look-ups; off by default
-    long long batch_plan_min = 64;   // MPC_BATCH_PLAN_MIN: smallest member level (candidates) that plans
     bool no_kkt_lists = false;       // MPC_NO_KKT_LISTS=1: the work lists behind k_kkt_thread by compaction of the status array (round 4; A/B, tests)
     bool no_small_rx = false;        // MPC_NO_SMALL_RX=1: region kernel and (x,theta) kernel of a small level as two launches (A/B, tests)
     bool no_small_fuse = false;      // MPC_NO_SMALL_FUSE=1: the small path with its round-4 launches (doubtful candidates re-solved in place; A/B, tests)
@@ -358,7 +343,6 @@ struct mpc_handle {
     DevProblem Pv{}, Pr{};    // verdict / region kernel views (same blocks, different LDS layouts)
     int lds_v = 0, lds_r = 0; // dynamic LDS bytes per wavefront
     int debug_cycles = 0;     // MPC_DEBUG_CYCLES=1: per-level cycle breakdown on stderr
-    int force_xqgroup = 0;    // MPC_FORCE_XQGROUP=1: k_xq_grouped whatever the number of siblings (tests)
     long long last_level_n = 0;   // candidates of the previous level (= the parents of this one)
     int no_xqgroup = 0;       // MPC_NO_XQGROUP=1: the last level's quick test reads the parent records from HBM per candidate (A/B)
     int no_rbox = 0;          // MPC_NO_RBOX=1: no bounding-box screen of the region rows in k_region2 (A/B)
@@ -369,11 +353,9 @@ struct mpc_handle {
     int x1_wpc = 16;          // MPC_X1_WPC: wavefronts per CU of k_x1 (config 4, level 4, beside the region kernel: x stage 1.13 / 0.95 / 1.02 ms with 8 / 16 / 32)
     long long n_x1 = 0;       // dictionaries of the last level run that k_x1 wrote
     float ms_x1 = 0;
-    int xq_retry = 0;         // MPC_XQ_RETRY=1: a doubtful pivot met by the quick test is flagged by the quick test itself and re-solved at once on the second stream (round 5; off: on config 3 half of the doubtful candidates only show in k_x2, beyond the quick test's sixteen iterations, so the level pays the LDS engine twice -- 3.55 ms against 3.28)
     int no_xq_early = 0;      // MPC_NO_XQ_EARLY=1: the thread pass of the quick test always behind the theta stage, -1: always beside it (A/B)
     long long prev_regions = 0, xq_early_regions = 0;   // MPC_XQ_EARLY_REGIONS = r > 0: the pass runs beside the theta stage only when the level before found fewer than r regions (0: always)
     int xqt_wpc = 16;         // MPC_XQT_WPC: wavefronts per CU of k_xq_thread (it is bound by the cache's request rate: config 4's level 0.45 ms alone with 8 per CU, 0.49 with 24; beside the region kernel 0.92 / 0.70 / 0.78 / 0.75 with 4 / 8 / 12 / 16)
-    int xqg_overlap = 0;      // MPC_XQG_OVERLAP=1: the region stage runs under the (x,theta) stage also when the quick test is the grouped one (experiment)
     int xq_thread = -1;       // MPC_XQ_THREAD: 0 = the quick test without its one-thread-per-candidate first pass k_xq_thread (round 5); 1 = the pass against the generating parent only; n >= 2 = ... and up to n - 1 other parents; default: every other parent
     long long n_xq_thread = 0; float ms_xq_thread = 0;   // the last level run: candidates that pass decided, its time
     bool fetch_nowait = false; // mpc_level_regions_slots_nowait: even the integer heads are only queued
@@ -387,7 +369,7 @@ struct mpc_handle {
     long long n_needx = 0;
     DevProblem Pf{};          // view for k_verdict2 (small LDS layout: no tableau)
     int lds_f = 0, grid_f = 0;
-    DevBuf retry_list, theta_list, vretry_list, status_tmp, part_counts, part_lists, kept_g, done_g, pf_dev, pr2_dev, headd, headi, epool, facet_flags, kkt_code, kkt_L, theta_blocks, xq_groups, xq_list, x1_buf, xretry_list;
+    DevBuf retry_list, theta_list, vretry_list, status_tmp, part_counts, part_lists, kept_g, done_g, pf_dev, pr2_dev, headd, headi, epool, facet_flags, kkt_code, kkt_L, theta_blocks, xq_groups, xq_list, x1_buf;
     ThetaArgs targs{};
     // (x,theta) dictionary cache: [0]/[1] ping-pong between the level being read (parents) and the level being written
     DevBuf dict_d[2], dict_i[2], dict_stored[2], parent_slot, parent_slot_next;
@@ -490,38 +472,6 @@ int fail(mpc_handle *h, int code, const std::string &msg) {
             return fail(h, MPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));               \
     } while (0)
 
-// dense host helpers (one-off program setup; fp64)
-bool cholesky(std::vector<double> &M, int n) {
-    double dmax = 0;
-    for (int i = 0; i < n; ++i) dmax = std::max(dmax, std::fabs(M[(size_t)i * n + i]));
-    for (int j = 0; j < n; ++j) {
-        double d = M[(size_t)j * n + j];
-        for (int l = 0; l < j; ++l) d -= M[(size_t)j * n + l] * M[(size_t)j * n + l];
-        if (!(d > 1e-10 * dmax)) return false;
-        const double s = std::sqrt(d);
-        M[(size_t)j * n + j] = s;
-        for (int i = j + 1; i < n; ++i) {
-            double v = M[(size_t)i * n + j];
-            for (int l = 0; l < j; ++l) v -= M[(size_t)i * n + l] * M[(size_t)j * n + l];
-            M[(size_t)i * n + j] = v / s;
-        }
-    }
-    return true;
-}
-// x := Q^-1 x given the lower Cholesky factor
-void chol_apply(const std::vector<double> &L, int n, double *x) {
-    for (int i = 0; i < n; ++i) {
-        double v = x[i];
-        for (int l = 0; l < i; ++l) v -= L[(size_t)i * n + l] * x[l];
-        x[i] = v / L[(size_t)i * n + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double v = x[i];
-        for (int l = i + 1; l < n; ++l) v -= L[(size_t)l * n + i] * x[l];
-        x[i] = v / L[(size_t)i * n + i];
-    }
-}
-
 struct Layout { int off_T, off_K, off_L, off_E, off_X, n_doubles, off_as, off_inact, off_colvar, off_rowvar, off_rowkind, off_kept, off_pri, off_stored, n_ints, bytes; };
 
 Layout make_layout(int size_T, int size_K, int size_L, int size_E, int size_X, int kmax, int n_c, int ld_max, int rows_max, int rows_t) {
@@ -547,6 +497,7 @@ void apply_layout(DevProblem &P, const Layout &l) {
 
 int waves_per_cu(int lds_bytes) { return std::max(1, std::min(16, (160 * 1024) / std::max(lds_bytes, 1))); }
 
+// dense host helpers (one-off program setup; fp64)
 // LU with partial pivoting of the n x n matrix M (row major, overwritten); perm receives the row order.
 bool lu_factor(std::vector<double> &M, int n, std::vector<int> &perm) {
     perm.resize(n);
@@ -577,7 +528,7 @@ void lu_solve_host(const std::vector<double> &LU, const std::vector<int> &perm, 
 // graveyard_flush, which the level paths call behind their closing synchronisation (all streams of the handle have been joined by then)
 static std::vector<DevBuf *> level_buffers(mpc_handle *h) {
     return {&h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list, &h->childmask, &h->count, &h->offset, &h->recd, &h->reci,
-            &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->xretry_list, &h->theta_list, &h->vretry_list,
+            &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list,
             &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
             &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next};
 }
@@ -651,27 +602,16 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     HIP_TRY(nullptr, pooled_event(&h->ev_xjoin, false));
     HIP_TRY(nullptr, pooled_stream(&h->stream3));
     HIP_TRY(nullptr, pooled_stream(&h->stream4));
-    HIP_TRY(nullptr, pooled_event(&h->ev_rjoin2, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_nth, false));
     HIP_TRY(nullptr, pooled_event(&h->ev_x1go, false));
     HIP_TRY(nullptr, pooled_event(&h->ev_x1done, false));
     { const char *ev = std::getenv("MPC_X1_DEFER"); if (ev) h->x1_defer = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_X1_LDS_CAP"); if (ev) h->x1_lds_cap = std::max(0, std::atoi(ev)); }
     { const char *ev = std::getenv("MPC_KKT_SPREAD"); if (ev) h->kkt_spread = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_KKT_SPREAD_THREADS"); if (ev) h->kkt_spread_threads = std::max(0, std::atoi(ev)); }
     { const char *ev = std::getenv("MPC_X_FRESH_LIMIT"); if (ev) h->x_fresh_limit = std::atof(ev); }
     { const char *ev = std::getenv("MPC_X_SECOND_MAX"); if (ev) h->x_second_max = std::max(0, std::atoi(ev)); }
     { const char *ev = std::getenv("MPC_XQ_SKIP_BELOW"); if (ev) h->xq_skip_below = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_HELPER_IT"); if (ev) h->helper_it = std::atoi(ev) == 1 ? 1 : 4; }
     { const char *ev = std::getenv("MPC_PRUNED_BUCKET_MIN"); if (ev) h->pruned_bucket_min = std::atof(ev); }
     { const char *ev = std::getenv("MPC_PRUNED_BUCKET_NP"); if (ev) h->pruned_bucket_np = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_R2_EARLY"); if (ev) h->r2_early = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_R2_EARLY_MIN"); if (ev) h->r2_early_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_R2_EARLY_WPC"); if (ev) h->r2_early_wpc = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_R2_EARLY_SPIN"); if (ev) h->r2_early_spin = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_R2_EARLY_THW"); if (ev) h->r2_early_thw = std::max(1, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_R2_EARLY_PRIO"); if (ev) h->r2_early_prio = std::max(0, std::min(3, std::atoi(ev))); }
-    HIP_TRY(nullptr, pooled_event(&h->ev_rfork, false));
     HIP_TRY(nullptr, pooled_event(&h->ev_rjoin, false));
     HIP_TRY(nullptr, pooled_event(&h->ev_rgo, false));
     h->n_x = nx; h->n_t = nt; h->n_c = nc; h->n_eq = ne; h->n_tc = ntc; h->is_qp = p->Q != nullptr;
@@ -681,13 +621,10 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     { const char *ev = std::getenv("MPC_NO_RSPLIT"); h->no_rsplit = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_RBOX"); h->no_rbox = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_XQGROUP"); h->no_xqgroup = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_FORCE_XQGROUP"); h->force_xqgroup = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_XQUICK"); h->no_xquick = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_XQ_THREAD"); h->xq_thread = ev ? std::atoi(ev) : -1; }
-    { const char *ev = std::getenv("MPC_XQG_OVERLAP"); h->xqg_overlap = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_XQT_WPC"); if (ev && std::atoi(ev) > 0) h->xqt_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_X1"); h->x1 = ev ? std::atoi(ev) : 2; }
-    { const char *ev = std::getenv("MPC_XQ_RETRY"); h->xq_retry = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_X1_WPC"); if (ev && std::atoi(ev) > 0) h->x1_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQT_MIN"); if (ev) h->xqt_min = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_X1_MIN"); if (ev) h->x1_min = std::atoll(ev); }
@@ -701,20 +638,16 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     { const char *ev = std::getenv("MPC_NO_X_FIRST"); h->x_first = !(ev && ev[0] == '1'); }
     { const char *ev = std::getenv("MPC_X_FIRST_MIN"); if (ev) h->x_first_min = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_X_FIRST_MAX"); if (ev) h->x_first_max = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_BATCH_PLANS"); h->no_batch_plans = !(ev && ev[0] == '1'); }
-    { const char *ev = std::getenv("MPC_BATCH_PLAN_MIN"); if (ev) h->batch_plan_min = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_NO_KKT_LISTS"); h->no_kkt_lists = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALL_RX"); h->no_small_rx = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALL_FUSE"); h->no_small_fuse = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALLPATH"); h->no_smallpath = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_LEAN"); h->no_lean = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SPEC_TAIL"); h->no_spec_tail = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_FETCH_KERNEL"); h->no_fetch_kernel = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_X2_WPC"); if (ev && std::atoi(ev) > 0) h->x2_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQ_WPC"); if (ev && std::atoi(ev) > 0) h->xq_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQG_PER_CU"); if (ev && std::atoi(ev) > 0) h->xqg_per_cu = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_X2_DIV"); if (ev && std::atoi(ev) > 0) h->x2_div = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_R3_FORK"); h->r3_fork_event = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_R2_CAP"); if (ev && std::atoi(ev) > 0) h->r2_cap_pct = std::min(100, std::atoi(ev)); }
     { const char *ev = std::getenv("MPC_TEST_SMALL_FALLBACK"); h->test_small_fallback = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_RSPLIT_MAX"); if (ev) { int v = std::atoi(ev); h->rsplit_max = v >= 16 ? 16 : (v >= 8 ? 8 : (v >= 4 ? 4 : (v >= 2 ? 2 : 1))); } }
@@ -724,40 +657,6 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     { const char *ev = std::getenv("MPC_DICT_BUDGET_GB"); if (ev) h->dict_budget_gb = std::atof(ev); }
 
     const int nr = nt + 1;
-    // ---- host-side one-off blocks ----------------------------------------------------------------------
-    // W = A Q^-1 A', UV, G', X0H and A A' are formed on the DEVICE by the MFMA set-up kernel (setup_mfma.hip) once the raw
-    // matrices are in HBM (below).  MPC_HOST_SETUP=1 keeps the scalar host computation instead (A/B comparisons, tests).
-    const bool host_setup = [] { const char *ev = std::getenv("MPC_HOST_SETUP"); return ev && ev[0] == '1'; }();
-    std::vector<double> W, UV, Gt, X0H;
-    int mode = 1;
-    if (p->Q && host_setup) {
-        std::vector<double> L(p->Q, p->Q + (size_t)nx * nx);
-        for (int i = 0; i < nx; ++i) for (int j = 0; j < i; ++j) { const double s = 0.5 * (L[(size_t)i * nx + j] + L[(size_t)j * nx + i]); L[(size_t)i * nx + j] = s; L[(size_t)j * nx + i] = s; }
-        if (cholesky(L, nx)) {
-            mode = 0;
-            Gt.assign((size_t)nc * nx, 0.0);
-            for (int i = 0; i < nc; ++i) { std::copy(p->A + (size_t)i * nx, p->A + (size_t)(i + 1) * nx, Gt.begin() + (size_t)i * nx); chol_apply(L, nx, &Gt[(size_t)i * nx]); }
-            W.assign((size_t)nc * nc, 0.0);
-            for (int i = 0; i < nc; ++i) for (int j = 0; j <= i; ++j) {
-                double s = 0; for (int l = 0; l < nx; ++l) s += p->A[(size_t)i * nx + l] * Gt[(size_t)j * nx + l];
-                W[(size_t)i * nc + j] = s; W[(size_t)j * nc + i] = s;
-            }
-            // columns of [c | H] through Q^-1
-            std::vector<double> QiCH((size_t)nx * nr), col(nx);
-            for (int t = 0; t < nr; ++t) {
-                for (int i = 0; i < nx; ++i) col[i] = t == 0 ? p->c[i] : p->H[(size_t)i * nt + t - 1];
-                chol_apply(L, nx, col.data());
-                for (int i = 0; i < nx; ++i) QiCH[(size_t)i * nr + t] = col[i];
-            }
-            X0H.assign((size_t)nx * nr, 0.0);
-            for (size_t i = 0; i < X0H.size(); ++i) X0H[i] = -QiCH[i];
-            UV.assign((size_t)nc * nr, 0.0);
-            for (int i = 0; i < nc; ++i) for (int t = 0; t < nr; ++t) {
-                double s = 0; for (int l = 0; l < nx; ++l) s += p->A[(size_t)i * nx + l] * QiCH[(size_t)l * nr + t];
-                UV[(size_t)i * nr + t] = s + (t == 0 ? p->b[i] : p->F[(size_t)i * nt + t - 1]);
-            }
-        }
-    }
     const int cols = 1 + nx + nt, rows_x = nc + ntc;
     std::vector<double> base((size_t)rows_x * cols, 0.0);
     for (int i = 0; i < nc; ++i) {
@@ -892,31 +791,20 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     const size_t oA = put(p->A, (size_t)nc * nx), ob = put(p->b, nc), oF = put(p->F, (size_t)nc * nt), oc = put(p->c, nx), oH = put(p->H, (size_t)nx * nt);
     const size_t oQ = put(p->Q ? p->Q : zeros.data(), (size_t)nx * nx);
     const size_t oAt = put(ntc ? p->A_t : zeros.data(), (size_t)std::max(ntc * nt, 1)), obt = put(ntc ? p->b_t : zeros.data(), std::max(ntc, 1));
-    // the blocks the set-up kernel fills are reserved at full size (zero until then); with MPC_HOST_SETUP=1 they are filled here
-    auto put_or_reserve = [&](const std::vector<double> &v, size_t cnt) { std::vector<double> z; if (v.empty()) z.assign(std::max<size_t>(cnt, 1), 0.0); return put(v.empty() ? z.data() : v.data(), std::max<size_t>(cnt, 1)); };
-    const bool dev_schur = p->Q && !host_setup;
-    const size_t oW = put_or_reserve(W, (mode == 0 || dev_schur) ? (size_t)nc * nc : 1), oUV = put_or_reserve(UV, (mode == 0 || dev_schur) ? (size_t)nc * nr : 1);
-    const size_t oGt = put_or_reserve(Gt, (mode == 0 || dev_schur) ? (size_t)nc * nx : 1), oX0H = put_or_reserve(X0H, (mode == 0 || dev_schur) ? (size_t)nx * nr : 1);
-    std::vector<double> AAT;
-    if (host_setup) {
-        AAT.assign((size_t)nc * nc, 0.0);
-        for (int i = 0; i < nc; ++i) for (int j = 0; j <= i; ++j) {
-            double sdot = 0; for (int l = 0; l < nx; ++l) sdot += p->A[(size_t)i * nx + l] * p->A[(size_t)j * nx + l];
-            AAT[(size_t)i * nc + j] = sdot; AAT[(size_t)j * nc + i] = sdot;
-        }
-    }
-    const size_t oAAT = put_or_reserve(AAT, (size_t)nc * nc);
+    // the blocks the set-up kernel fills are reserved at full size (zero until then)
+    auto reserve = [&](size_t cnt) { const std::vector<double> z(std::max<size_t>(cnt, 1), 0.0); return put(z.data(), z.size()); };
+    const bool dev_schur = p->Q != nullptr;
+    const size_t oW = reserve(dev_schur ? (size_t)nc * nc : 1), oUV = reserve(dev_schur ? (size_t)nc * nr : 1);
+    const size_t oGt = reserve(dev_schur ? (size_t)nc * nx : 1), oX0H = reserve(dev_schur ? (size_t)nx * nr : 1);
+    const size_t oAAT = reserve((size_t)nc * nc);
     std::vector<double> ATr((size_t)std::max(nx * nc, 1), 0.0);      // A transposed (k_region2's row build reads a column of A per step)
     for (int i = 0; i < nc; ++i) for (int l = 0; l < nx; ++l) ATr[(size_t)l * nc + i] = p->A[(size_t)i * nx + l];
     const size_t oATr = put(ATr.data(), ATr.size());
     // equality rows eliminated from the Schur blocks (setup_mfma.hpp): lets k_kkt_thread take active sets of ne + (1..8) rows
     const bool want_elim = ne > 0 && dev_schur && ![] { const char *ev = std::getenv("MPC_NO_EQ_ELIM"); return ev && ev[0] == '1'; }();
-    const std::vector<double> none;
-    const size_t oWr = put_or_reserve(none, want_elim ? (size_t)nc * nc : 1), oUVr = put_or_reserve(none, want_elim ? (size_t)nc * nr : 1);
-    const size_t oAATr = put_or_reserve(none, want_elim ? (size_t)nc * nc : 1), oMe = put_or_reserve(none, want_elim ? (size_t)ne * nr : 1);
-    const size_t oNe = put_or_reserve(none, want_elim ? (size_t)ne * nc : 1), ogE = put_or_reserve(none, want_elim ? (size_t)2 * ne : 1);
-    std::vector<double> UVr;
-    bool elim_ok = false;
+    const size_t oWr = reserve(want_elim ? (size_t)nc * nc : 1), oUVr = reserve(want_elim ? (size_t)nc * nr : 1);
+    const size_t oAATr = reserve(want_elim ? (size_t)nc * nc : 1), oMe = reserve(want_elim ? (size_t)ne * nr : 1);
+    const size_t oNe = reserve(want_elim ? (size_t)ne * nc : 1), ogE = reserve(want_elim ? (size_t)2 * ne : 1);
     const size_t obase = put(base.data(), base.size());
     const size_t od0 = put(d0.empty() ? zeros.data() : d0.data(), d0.empty() ? 1 : d0.size());
     const size_t od0T = put(d0T.empty() ? zeros.data() : d0T.data(), d0T.empty() ? 1 : d0T.size());
@@ -925,8 +813,11 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     const size_t otvr = put(tv_rows.empty() ? zeros.data() : tv_rows.data(), tv_rows.empty() ? 1 : tv_rows.size());
     HIP_TRY(nullptr, h->blocks.ensure(host.size() * sizeof(double), h->stream));
     HIP_TRY(nullptr, hipMemcpyAsync(h->blocks.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    if (!host_setup) {
-        // ---- the dense Hessian factor and the one-off Schur blocks on the matrix cores (setup_mfma.hip) ----------------------
+    // ---- the dense Hessian factor and the one-off Schur blocks W = A Q^-1 A', UV, G', X0H, A A' on the matrix cores (setup_mfma.hip) ----
+    std::vector<double> UV, UVr;
+    int mode = 1;
+    bool elim_ok = false;
+    {
         double *db = h->blocks.as<double>();
         SetupJob job{};
         job.nx = nx; job.nt = nt; job.nc = nc; job.NP = setup_pad16(nx); job.MP = setup_pad16(nc); job.RP = setup_pad16(nr);
@@ -1101,23 +992,20 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     }
     // ---- is the parameter set open in some direction?  (then the reference's optimality LP can be unbounded: k_recession) -------------
     {
-        const char *ev = std::getenv("MPC_NO_RECESSION");
         bool open = false;
-        if (!(ev && ev[0] == '1')) {
-            if (nc == ne) open = true;                                     // no multiplier / slack row at all bounds t (the base set)
-            else if (nt > 0 && (ntc == 0 || tv_theta.empty())) open = true;   // no row, or no vertex: the set contains a line (or the search failed: the test is always safe)
-            else if (nt > 0) {
-                if (!box_done) {   // a vertex, but maybe an open cone: the bounding box (2 n_t LPs on the device, as for the register-resident kernels)
-                    std::vector<double> cc((size_t)2 * nt * nt, 0.0), obj(2 * nt, 0.0);
-                    for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
-                    std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
-                    std::vector<int32_t> stt(2 * nt, -1);
-                    const int rcb = lp_batch_impl(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
-                    HIP_TRY(nullptr, hipSetDevice(device));
-                    for (int t = 0; t < 2 * nt; ++t) box_open = box_open || rcb != MPC_OK || stt[t] != LP_OPTIMAL;
-                }
-                open = box_open;
+        if (nc == ne) open = true;                                     // no multiplier / slack row at all bounds t (the base set)
+        else if (nt > 0 && (ntc == 0 || tv_theta.empty())) open = true;   // no row, or no vertex: the set contains a line (or the search failed: the test is always safe)
+        else if (nt > 0) {
+            if (!box_done) {   // a vertex, but maybe an open cone: the bounding box (2 n_t LPs on the device, as for the register-resident kernels)
+                std::vector<double> cc((size_t)2 * nt * nt, 0.0), obj(2 * nt, 0.0);
+                for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
+                std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
+                std::vector<int32_t> stt(2 * nt, -1);
+                const int rcb = lp_batch_impl(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
+                HIP_TRY(nullptr, hipSetDevice(device));
+                for (int t = 0; t < 2 * nt; ++t) box_open = box_open || rcb != MPC_OK || stt[t] != LP_OPTIMAL;
             }
+            open = box_open;
         }
         h->theta_open = open;
         if (std::getenv("MPC_DEBUG_CREATE")) std::fprintf(stderr, "[mpc] create: parameter set %s\n", open ? "OPEN in some direction (k_recession behind the verdict stages)" : "bounded");
@@ -1154,7 +1042,7 @@ int mpc_destroy(mpc_handle *h) {
     if (h->stream4) (void)hipStreamSynchronize(h->stream4);
     graveyard_flush(h);
     for (DevBuf *b : {&h->blocks, &h->iblocks, &h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list,
-                      &h->childmask, &h->count, &h->offset, &h->recd, &h->reci, &h->ctr, &h->pruned_b, &h->pruned_head, &h->scratch, &h->sums, &h->retry_list, &h->pf_dev, &h->pr2_dev, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->theta_blocks, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->xretry_list, &h->theta_list, &h->vretry_list, &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
+                      &h->childmask, &h->count, &h->offset, &h->recd, &h->reci, &h->ctr, &h->pruned_b, &h->pruned_head, &h->scratch, &h->sums, &h->retry_list, &h->pf_dev, &h->pr2_dev, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->theta_blocks, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list, &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
                       &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next, &h->dcnt}) b->release();
     if (h->tot_host) { (void)host_pool_give(h->tot_host); h->tot_host = h->tot_dev = nullptr; }
     for (HostBuf *b : {&h->st_list, &h->st_status, &h->st_hd, &h->st_hi, &h->st_pool, &h->st_fxd, &h->st_fxi, &h->st_rlist, &h->st_flags}) b->release();
@@ -1170,14 +1058,11 @@ int mpc_destroy(mpc_handle *h) {
     return_event(h->ev_xfork, false);
     return_event(h->ev_part, false);
     return_event(h->ev_xjoin, false);
-    return_event(h->ev_rfork, false);
     return_event(h->ev_rjoin, false);
     return_event(h->ev_rgo, false);
     return_stream(h->stream2);
     return_stream(h->stream3);
     return_stream(h->stream4);
-    return_event(h->ev_rjoin2, false);
-    return_event(h->ev_nth, false);
     return_event(h->ev_x1go, false);
     return_event(h->ev_x1done, false);
     if (h->own_stream) return_stream(h->stream);
@@ -1196,11 +1081,11 @@ int mpc_trim(mpc_handle *h) {
     if (h->stream2) HIP_TRY(h, hipStreamSynchronize(h->stream2));
     if (h->stream3) HIP_TRY(h, hipStreamSynchronize(h->stream3));
     if (h->stream4) HIP_TRY(h, hipStreamSynchronize(h->stream4));
-    h->x1_pending = false; h->x1_stash = nullptr;
+    h->x1_pending = false;
     graveyard_flush(h);
     stream_release(h);
     for (DevBuf *b : {&h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list, &h->childmask, &h->count, &h->offset, &h->recd, &h->reci,
-                      &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->xretry_list, &h->theta_list, &h->vretry_list,
+                      &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list,
                       &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
                       &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next}) b->release();
     for (HostBuf *b : {&h->st_list, &h->st_status, &h->st_hd, &h->st_hi, &h->st_pool, &h->st_fxd, &h->st_fxi, &h->st_rlist, &h->st_flags}) b->release();
@@ -1379,15 +1264,10 @@ static int launch_scan(mpc_handle *h, const int32_t *in, int32_t *out, long long
     }
     const int nb = (int)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
     HIP_TRY(h, h->sums.ensure((size_t)std::max(nb, 1) * sizeof(int32_t), h->stream));
-    if (h->helper_it == 4) {   // four-wavefront workgroups (see block_exclusive_scan_it)
-        hipLaunchKernelGGL(k_scan_block_sums<4>, dim3(nb), dim3(SCAN_BLOCK / 4), 0, h->stream, in, n, h->sums.as<int32_t>());
-        hipLaunchKernelGGL(k_scan_sums<4>, dim3(1), dim3(SCAN_BLOCK / 4), 0, h->stream, h->sums.as<int32_t>(), nb, total_dev);
-        hipLaunchKernelGGL(k_scan_apply<4>, dim3(nb), dim3(SCAN_BLOCK / 4), 0, h->stream, in, out, n, h->sums.as<int32_t>());
-    } else {
-        hipLaunchKernelGGL(k_scan_block_sums<1>, dim3(nb), dim3(SCAN_BLOCK), 0, h->stream, in, n, h->sums.as<int32_t>());
-        hipLaunchKernelGGL(k_scan_sums<1>, dim3(1), dim3(SCAN_BLOCK), 0, h->stream, h->sums.as<int32_t>(), nb, total_dev);
-        hipLaunchKernelGGL(k_scan_apply<1>, dim3(nb), dim3(SCAN_BLOCK), 0, h->stream, in, out, n, h->sums.as<int32_t>());
-    }
+    // four-wavefront workgroups (see block_exclusive_scan_it)
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(nb), dim3(SCAN_BLOCK / SCAN_IT), 0, h->stream, in, n, h->sums.as<int32_t>());
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(SCAN_BLOCK / SCAN_IT), 0, h->stream, h->sums.as<int32_t>(), nb, total_dev);
+    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(SCAN_BLOCK / SCAN_IT), 0, h->stream, in, out, n, h->sums.as<int32_t>());
     HIP_TRY(h, hipGetLastError());
     return MPC_OK;
 }
@@ -1471,17 +1351,7 @@ static void stream_release(mpc_handle *h) {   // blocks of a streamed level nobo
 constexpr int KKT_THREAD_MAX = 10;
 constexpr int KKT_SPREAD = BATCH_KKT_SPREAD, KKT_SPREAD_KMAX = BATCH_KKT_SPREAD_KMAX;   // small levels: lanes per candidate of k_kkt_thread, up to this many inequality rows
 // every stream of the handle that may read or write dictionary records waits for the deferred k_x1 of the previous level (stream waits: the host does not block)
-// issues a stashed k_x1 launch (MPC_X1_DEFER=2: behind the level's children stage, so that it runs beside the NEXT level's KKT kernel -- issue
-// bound, no traffic -- instead of beside the children stage, which like k_x1 is bound by the memory system: config 4's k_children_count_b
-// took 0.34 ms beside it, 0.08 alone)
-static int x1_flush(mpc_handle *h) {
-    if (!h->x1_stash) return MPC_OK;
-    std::function<int()> f;
-    f.swap(h->x1_stash);
-    return f();
-}
 static int x1_join(mpc_handle *h) {
-    { int rcf = x1_flush(h); if (rcf) return rcf; }
     if (!h->x1_pending) return MPC_OK;
     for (hipStream_t sx : {h->stream, h->stream2, h->stream3}) if (sx) HIP_TRY(h, hipStreamWaitEvent(sx, h->ev_x1done, 0));
     h->x1_pending = false;
@@ -1944,20 +1814,6 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
     }
     dc.chunk = 1;
     m.dc = dc;
-    // one-step plans (round 5): a storing level whose candidates have parents' records; the look-up of other parents needs the previous
-    // frontier, which sits in the children buffer -- only while that buffer is not about to be re-allocated for this level's children
-    m.plan = 0; m.x1_buf = nullptr; m.alt = XqAlt{}; m.plan_blocks = m.x1_blocks = 0;
-    if (h->storing && dc.parent_slot && h->x1 > 0 && !h->no_batch_plans && n >= h->batch_plan_min && n <= 0x7fffffffLL / 8) {
-        HIP_TRY(h, h->x1_buf.ensure((6 * nn + 16) * sizeof(int32_t), st));
-        m.x1_buf = h->x1_buf.as<int32_t>();
-        m.plan = 1;
-        const size_t child_bytes = gen_children ? nn * (size_t)std::max(h->n_c - k, 1) * (k + 1) * sizeof(int32_t) : 0;
-        if (h->x1 >= 2 && h->n_prev > 0 && h->n_prev <= 0x7fffffffLL && k >= 2 && h->children.cap >= child_bytes &&
-            h->children.cap >= (size_t)h->n_prev * (k - 1) * sizeof(int32_t) && h->dict_stored[1 - h->dict_cur].cap >= (size_t)h->n_prev) {
-            m.alt.prev_frontier = h->children.as<int32_t>(); m.alt.prev_stored = h->dict_stored[1 - h->dict_cur].as<uint8_t>();
-            m.alt.n_prev = (int)h->n_prev; m.alt.tries = MPC_MAX_NC;
-        }
-    }
     m.storing = h->storing ? 1 : 0;
     m.dict_stored_cur = h->storing ? h->dict_stored[h->dict_cur].as<uint8_t>() : nullptr;
     m.quick_test = (!h->storing && dc.parent_slot && !h->no_xquick) ? 1 : 0;
@@ -2177,7 +2033,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
     HIP_TRY(h, hipSetDevice(h->device));
     stream_release(h);
     // (a deferred k_x1 of the previous level: joined at once unless this is a large level whose first kernel, k_kkt_thread, reads no dictionary)
-    const bool x1_late_join = h->x1_pending && h->fast && !h->force_v1 && h->kkt_mode == 0 && h->no_kkt_thread != 1 && !h->no_lean &&
+    const bool x1_late_join = h->x1_pending && h->fast && !h->force_v1 && h->kkt_mode == 0 && h->no_kkt_thread != 1 &&
                               (h->skip_small || !small_path_ok(h, h->n, h->k, flags, gen_children)) && h->k - h->targs.ne >= 1 && h->k - h->targs.ne <= KKT_THREAD_MAX;
     if (!x1_late_join) { int rcj = x1_join(h); if (rcj) return rcj; }
     if (!h->skip_small && small_path_ok(h, h->n, h->k, flags, gen_children)) {
@@ -2233,7 +2089,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         // read-back after the theta stage) and the final statistics; the theta LP, the (x,theta) stage after the quick test and the
         // child generation take theirs from device memory (dcnt: [0] theta list, [8] open after the quick test, [20] children) and are
         // launched for the bound the host does know.
-        const bool lean = !h->no_lean;
         HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
         {   // counters and list lengths cleared by one launch (a hipMemsetAsync costs the host ~16 us, a launch ~3 us)
             ZeroBufs z{};
@@ -2260,12 +2115,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             HIP_TRY(h, hipGetLastError());
             pruned_bucketed = true;
         }
-        // (round 6) a large last level: the theta kernel will list its optimal candidates itself (the queue form below); entries -1 = not written
-        const bool r2_queue_ready = lean && h->r2_early > 0 && !gen_children && n >= h->r2_early_min && n <= 0x7fffffffLL && h->fast && h->fast_r >= 0 && !h->force_v1 && !(flags & MPC_LEVEL_GRAPH);
-        if (r2_queue_ready) {
-            hipLaunchKernelGGL(k_fill_i32, dim3((unsigned)std::min<long long>(1024, (n + 255) / 256)), dim3(256), 0, st, h->opt_list.as<int32_t>(), n, -1);
-            HIP_TRY(h, hipGetLastError());
-        }
         int32_t *dcnt = h->dcnt.as<int32_t>();
         bool theta_lean = false, xq_lean = false, children_lean = false;
         // deterministic partition of the candidates into up to four lists by status (spec: status -> class nibble, 15 = none);
@@ -2281,17 +2130,10 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             if (small) {
                 hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, spec, h->part_lists.as<int32_t>(), (long long)n, tot);
             } else {
-                if (h->helper_it == 4) {
-                    hipLaunchKernelGGL(k_part_count<4>, dim3(nb1024), dim3(256), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024);
-                    hipLaunchKernelGGL(k_part_sums<4>, dim3(PART_CLASSES), dim3(256), 0, st, h->part_counts.as<int32_t>(), nb1024, tot);
-                    hipLaunchKernelGGL(k_part_scatter<4>, dim3(nb1024), dim3(256), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024,
-                                       h->part_lists.as<int32_t>());
-                } else {
-                    hipLaunchKernelGGL(k_part_count<1>, dim3(nb1024), dim3(1024), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024);
-                    hipLaunchKernelGGL(k_part_sums<1>, dim3(PART_CLASSES), dim3(1024), 0, st, h->part_counts.as<int32_t>(), nb1024, tot);
-                    hipLaunchKernelGGL(k_part_scatter<1>, dim3(nb1024), dim3(1024), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024,
-                                       h->part_lists.as<int32_t>());
-                }
+                hipLaunchKernelGGL(k_part_count, dim3(nb1024), dim3(1024 / SCAN_IT), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024);
+                hipLaunchKernelGGL(k_part_sums, dim3(PART_CLASSES), dim3(1024 / SCAN_IT), 0, st, h->part_counts.as<int32_t>(), nb1024, tot);
+                hipLaunchKernelGGL(k_part_scatter, dim3(nb1024), dim3(1024 / SCAN_IT), 0, st, h->status.as<uint8_t>(), n, spec, h->part_counts.as<int32_t>(), nb1024,
+                                   h->part_lists.as<int32_t>());
             }
             HIP_TRY(h, hipGetLastError());
             if (deferred) return MPC_OK;
@@ -2331,17 +2173,14 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
         h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
         int32_t *region_out_hi = nullptr;   // head_i of the level's slots as the device sees it (device buffer or mapped host block)
-        // Round 6, the queue form (`early`): the launch runs BESIDE the theta kernel and takes the optimal candidates from the queue that kernel
-        // fills (n_opt is then the BOUND that sizes the buffers: the length of the theta list); region2_drain below is its second launch.
-        struct R2Saved { double *hd = nullptr, *er = nullptr; int32_t *hi = nullptr; RegionStream rs{}; int ldk = 0; bool valid = false; } r2s;
-        auto region2_launch = [&](int32_t n_opt, int32_t extra, hipStream_t rst, bool one_wave, bool early = false) -> int {
+        auto region2_launch = [&](int32_t n_opt, int32_t extra, hipStream_t rst, bool one_wave) -> int {
             const int rows_t_ = h->n_c - h->n_eq + h->n_tc;
             const size_t n_tot = (size_t)n_opt + (size_t)extra;   // slots: the launch's candidates + spare ones for late optimal candidates
             HIP_TRY(h, h->headd.ensure(n_tot * h->fd * sizeof(double), st));
             HIP_TRY(h, h->headi.ensure(n_tot * h->fi * sizeof(int32_t), st));
             HIP_TRY(h, h->epool.ensure(n_tot * rows_t_ * (h->n_t + 1) * sizeof(double), st));
             // few optimal candidates: several wavefronts per candidate (the facet tests are split among them)
-            int W = (h->no_rsplit || one_wave || early) ? 1 : h->rsplit_max;
+            int W = (h->no_rsplit || one_wave) ? 1 : h->rsplit_max;
             while (W > 1 && (long long)n_opt * W > h->grid_r2) W >>= 1;
             const int ldk = (rows_t_ + 1 + 63) & ~63;
             if (W > 1) {
@@ -2351,8 +2190,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             }
             // an overlapped launch may take only a share of the wave slots (r2_cap_pct): its 256-register wavefronts otherwise fill the
             // register file of every SIMD they sit on and the (x,theta) kernel beside them gets no slot there until they leave
-            const long long grid_cap = early ? std::min<long long>(h->grid_r2, (long long)h->n_cu * h->r2_early_wpc)
-                                       : ((rst != st && one_wave) ? std::max<long long>(h->n_cu, (long long)h->grid_r2 * h->r2_cap_pct / 100) : h->grid_r2);
+            const long long grid_cap = (rst != st && one_wave) ? std::max<long long>(h->n_cu, (long long)h->grid_r2 * h->r2_cap_pct / 100) : h->grid_r2;
             const dim3 g((unsigned)std::min<long long>((long long)n_opt * W, grid_cap)), b(64);
             const DevProblem *pr = h->pr2_dev.as<DevProblem>();
             // where the records go: device buffers (fetched / gathered later), or -- streaming -- page-locked host blocks the
@@ -2391,27 +2229,14 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                                                    W, h->kept_g.as<uint8_t>(), ldk, h->done_g.as<unsigned int>(), \
                                                    h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)NT_ * NT_ + NT_, rs)
             region_out_hi = out_hi;
-            if (early) {
-                // every slot is marked empty first: which of them the queue will reach is not known yet (the host's region objects are cut
-                // from whole chunks of slots)
-                rprep.head_i = out_hi; rprep.fi = h->fi; rprep.first = 0; rprep.extra = (int)n_tot; rprep_any = true;
-                rs.early = 1; rs.spin_max = h->r2_early_spin; rs.q_cap = (int)std::min<size_t>(nn, 0x7fffffff);
-                r2s.hd = out_hd; r2s.hi = out_hi; r2s.er = out_er; r2s.rs = rs; r2s.ldk = ldk; r2s.valid = true;
-            } else if (extra > 0) { rprep.head_i = out_hi; rprep.fi = h->fi; rprep.first = n_opt; rprep.extra = extra; rprep_any = true; }
-            if (early) {
-                // (everything this launch reads was queued on the main stream in front of the event the host has just waited for)
-                { int rcs = prep_flush_on(rprep, rprep_any, rst); if (rcs) return rcs; }
-            } else if (rst != st) {
+            if (extra > 0) { rprep.head_i = out_hi; rprep.fi = h->fi; rprep.first = n_opt; rprep.extra = extra; rprep_any = true; }
+            if (rst != st) {
                 // The side stream does NOT wait for the main stream: every caller has synchronised the main stream (the partition whose
                 // counts sized this launch) and has queued nothing since that the region kernel reads, so the region stage's own
                 // preparation and the kernel go straight to the side stream -- one cross-stream hop (~25 us) less per large level than the
                 // fork through an event.  The main stream continues only when the side stream has reached the region kernel, so that
                 // the region wavefronts (the long chains) are placed first and the (x,theta) kernels fill in around them -- without this
                 // the two dispatches race and the persistent (x,theta) kernel often takes the whole GPU first.
-                if (h->r3_fork_event) {   // MPC_R3_FORK=1: round-3 form, the side stream starts behind an event of the main stream
-                    HIP_TRY(h, hipEventRecord(h->ev_rfork, st));
-                    HIP_TRY(h, hipStreamWaitEvent(rst, h->ev_rfork, 0));
-                }
                 { int rcs = prep_flush_on(rprep, rprep_any, rst); if (rcs) return rcs; }
                 HIP_TRY(h, hipEventRecord(h->ev_rgo, rst));
                 HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rgo, 0));
@@ -2420,8 +2245,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 { int rcs = prep_flush_on(rprep, rprep_any, st); if (rcs) return rcs; }
             }
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[4], rst));
-            if (early && h->r2_early_wpc <= 0) { /* MPC_R2_EARLY_WPC=0: no wavefronts beside the theta kernel, the drain launch alone (it still starts without a partition and its read-back) */ }
-            else
             switch (h->fast_r) {
                 case 0: MPC_LAUNCH_R2(4, 1); break;
                 case 1: MPC_LAUNCH_R2(4, 2); break;
@@ -2436,37 +2259,9 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             kernel_timed[2] = true;
             HIP_TRY(h, hipGetLastError());
             h->used_region2 = true;
-            if (!early) stream_ready(h);   // the caller of mpc_level_stream_info may start consuming chunks (queue form: once the queue's length is known)
+            stream_ready(h);   // the caller of mpc_level_stream_info may start consuming chunks
             return MPC_OK;
         };
-        // the drain launch of the queue form: behind the theta kernel (the queue is closed), on its own stream beside the early launch
-        auto region2_drain = [&](int32_t n_opt) -> int {
-            const dim3 g((unsigned)std::max<long long>(1, std::min<long long>(n_opt, h->grid_r2))), b(64);
-            const DevProblem *pr = h->pr2_dev.as<DevProblem>();
-            RegionStream rs = r2s.rs;
-            rs.early = 2;
-            double *out_hd = r2s.hd, *out_er = r2s.er; int32_t *out_hi = r2s.hi;
-            const int ldk = r2s.ldk, W = 1;
-            hipStream_t rst = h->stream4;
-#define MPC_LAUNCH_R2(NT_, SL_) hipLaunchKernelGGL((k_region2<NT_, SL_>), g, b, h->lds_r2, rst, pr, h->frontier.as<int32_t>(), k, h->opt_ptr, n_opt, \
-                                                   h->status.as<uint8_t>(), out_hd, out_hi, h->fd, h->fi, out_er, ctr, kkc, kkl, \
-                                                   W, h->kept_g.as<uint8_t>(), ldk, h->done_g.as<unsigned int>(), \
-                                                   h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)NT_ * NT_ + NT_, rs)
-            switch (h->fast_r) {
-                case 0: MPC_LAUNCH_R2(4, 1); break;
-                case 1: MPC_LAUNCH_R2(4, 2); break;
-                case 2: MPC_LAUNCH_R2(8, 1); break;
-                case 3: MPC_LAUNCH_R2(8, 2); break;
-                case 4: MPC_LAUNCH_R2(10, 1); break;
-                default: MPC_LAUNCH_R2(10, 2); break;
-            }
-#undef MPC_LAUNCH_R2
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipEventRecord(h->ev_rjoin2, rst));
-            return MPC_OK;
-        };
-        bool r2_early = false, r2_drained = false, r2_early_A = false;   // r2_early: the theta kernel lists its optimal candidates; _A: an early region launch runs beside it
-        long long r2_early_ntot = 0;   // slots of the queue form's buffers (the bound + spare ones)
         bool region_launched = false;
         int32_t n_late = 0;   // optimal candidates found after an overlapped region launch (spare slots)
         int32_t n_opt_fast = -1;   // >= 0: the fast path has already built h->opt_list
@@ -2495,7 +2290,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                                         h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
                 // lean: children and their parent slots are sized by the bound n (n_c - k) and written without waiting for the count
                 const double child_bound_bytes = (double)nn * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
-                children_lean = lean && child_bound_bytes <= 1.5e9;
+                children_lean = child_bound_bytes <= 1.5e9;
                 { int rcs = launch_scan(h, h->count.as<int32_t>(), h->offset.as<int32_t>(), n, children_lean ? dcnt + 20 : total); if (rcs) return rcs; }
                 HIP_TRY(h, hipGetLastError());
                 int32_t n_children = 0;
@@ -2518,7 +2313,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             hipLaunchKernelGGL(k_publish_words2, dim3(1), dim3(128), 0, st, reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4),
                                reinterpret_cast<const unsigned int *>(dcnt), 32, reinterpret_cast<unsigned int *>(h->tot_dev + 16));
             HIP_TRY(h, hipGetLastError());
-            { int rcf = x1_flush(h); if (rcf) return rcf; }      // (MPC_X1_DEFER=2: k_x1 starts behind the level's last kernels)
             return MPC_OK;
         };
         // open parameter set: the candidates the verdict stage calls optimal are asked whether the reference's max-t LP is bounded (k_recession)
@@ -2548,9 +2342,9 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 const bool spread = h->kkt_spread > 0 && kd <= KKT_SPREAD_KMAX && n * KKT_SPREAD <= (long long)h->kkt_spread_threads;
                 const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256)), b(256);
                 ThetaArgs ta = h->targs;
-                // (round 5) a lean level lets the kernel list its own output: the theta stage's work list and the candidates its box
-                // screen sends to the (x,theta) question -- two compactions of five launches each saved on the level's critical path
-                const bool kkt_lists = lean && !h->no_kkt_lists && n <= 0x7fffffffLL;
+                // (round 5) the kernel lists its own output: the theta stage's work list and the candidates its box screen sends to
+                // the (x,theta) question -- two compactions of five launches each saved on the level's critical path
+                const bool kkt_lists = !h->no_kkt_lists && n <= 0x7fffffffLL;
                 if (kkt_lists) {
                     HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
                     HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
@@ -2570,15 +2364,14 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[7], st));
                 kernel_timed[3] = true;
                 HIP_TRY(h, hipGetLastError());
-                int32_t n_todo = 0;
-                if (kkt_lists) { theta_lean = true; n_todo = (int32_t)n; kkt_listed = true; }
+                if (kkt_lists) kkt_listed = true;
                 else {
-                    if (lean) { int rcs = compact(ST_TODO, ST_TODO, nullptr, dcnt + 0); if (rcs) return rcs; theta_lean = true; n_todo = (int32_t)n; }
-                    else { int rcs = compact(ST_TODO, ST_TODO, &n_todo); if (rcs) return rcs; }
+                    { int rcs = compact(ST_TODO, ST_TODO, nullptr, dcnt + 0); if (rcs) return rcs; }
                     HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
                     std::swap(h->theta_list, h->retry_list);   // compact() filled retry_list; keep it as the theta list
                 }
-                n_theta = n_todo;   // lean: the bound
+                theta_lean = true;
+                n_theta = (int32_t)n;   // the bound
                 theta_list = h->theta_list.as<int32_t>();
             }
             // The quick test's thread pass BESIDE the theta stage (round 5).  On a level that keeps no dictionaries, k_kkt_thread's box
@@ -2589,8 +2382,8 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // (the previous level's deferred k_x1 is joined by whoever reads dictionary records first: the thread pass on the second stream
             //  below -- the theta kernel reads none and goes ahead --, else the (x,theta) stage behind the theta stage)
             bool early_xq = false;
-            if (kkc && lean && h->no_xq_early <= 0 && h->xq_thread != 0 && !h->no_xquick && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
-                n >= h->xqt_min && !h->force_xqgroup && (h->no_xq_early < 0 || h->prev_regions < h->xq_early_regions || h->xq_early_regions <= 0)) {
+            if (kkc && h->no_xq_early <= 0 && h->xq_thread != 0 && !h->no_xquick && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
+                n >= h->xqt_min && (h->no_xq_early < 0 || h->prev_regions < h->xq_early_regions || h->xq_early_regions <= 0)) {
                 // (The pass then overlaps the theta stage AND the region stage: the partition behind the theta stage lists only the doubtful
                 //  and the optimal candidates -- classes the pass never touches --, the region kernel starts on its stream, and the open
                 //  candidates are listed when the pass has ended.  Config 4's last level: 1.86 ms with the pass behind the theta stage,
@@ -2628,31 +2421,8 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                     early_xq = true; xq_early_ran = true;
                 }
             }
-            // Round 6: region wavefronts BESIDE the theta stage of a large last level (the queue form).  The theta
-            // kernel appends every candidate it finds optimal to a queue (the level's opt_list) the moment it has decided it; a first
-            // region launch of a few wavefronts per CU is already running on the side stream and builds regions while the theta stage is
-            // still solving -- until now the region stage waited for the theta kernel's tail, a partition and a host read-back.  The
-            // record buffers are sized by the length of the theta list, which k_kkt_thread has counted: published here, read by the host
-            // while the theta kernel already runs.  A second launch behind the theta kernel drains the queue with the full width.
-            if (r2_queue_ready && early_xq && kkt_listed && n_theta > 0 && !h->theta_open && !h->no_roverlap && h->test_late <= 0 && h->test_spare <= 0) {
-                r2_early = true;
-                if (h->r2_early_wpc > 0) {   // (the early launch's buffers are sized by the theta list's length: read while the theta kernel runs)
-                    hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned int *>(dcnt + 0), reinterpret_cast<unsigned int *>(h->tot_dev + 9), 1);
-                    HIP_TRY(h, hipGetLastError());
-                    HIP_TRY(h, hipEventRecord(h->ev_nth, st));
-                }
-            }
             if (n_theta > 0) {   // two-stage theta LP
                 ThetaArgs ta = h->targs;
-                if (r2_early) {
-                    ta.optq = h->opt_list.as<int32_t>(); ta.q_tail = &ctr->q_tail;
-                    // one theta wavefront per SIMD (the kernel is a tail of few long LPs: 0.40 / 0.33 ms with one / two, round 5) leaves
-                    // every SIMD room for a region wavefront of the early launch; the theta wavefronts issue with priority (ThetaArgs::prio)
-                    if (h->r2_early_wpc > 0) {
-                        if (ta.wave_max > 0) ta.wave_max = std::min<int>(ta.wave_max, h->r2_early_thw * 4 * h->n_cu);
-                        ta.prio = h->r2_early_prio;
-                    }
-                }
                 ta.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_theta / ((long long)h->grid_f * 8)));
                 if (theta_lean) { ta.n_dev = dcnt + 0; ta.chunk = 0; }   // length and chunk rule on the device
                 // wave slots the theta kernel takes (ThetaArgs::wave_div / wave_max): with the length on the device the kernel applies the
@@ -2675,25 +2445,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 kernel_timed[0] = true;
                 n_theta_items = n_theta;
                 HIP_TRY(h, hipGetLastError());
-                if (r2_early) {
-                    // the queue closes behind the theta kernel; its length and the number of doubtful candidates are published for the host
-                    hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(64), 0, st, &ctr->q_closed, 1u);
-                    hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, &ctr->q_tail, reinterpret_cast<unsigned int *>(h->tot_dev + 10), 1);
-                    hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, &ctr->n_retry_theta, reinterpret_cast<unsigned int *>(h->tot_dev + 11), 1);
-                    HIP_TRY(h, hipGetLastError());
-                    HIP_TRY(h, hipEventRecord(h->ev_part, st));
-                    if (h->r2_early_wpc > 0) {
-                        // ... and while the theta kernel runs: the early region launch (MPC_R2_EARLY_WPC > 0; off by default)
-                        HIP_TRY(h, hipEventSynchronize(h->ev_nth));
-                        const int32_t n_theta_host = h->tot_host[9];
-                        const int32_t spare = (int32_t)std::min<long long>(std::max<long long>(2048, n_theta_host / 8), 1 << 20);
-                        h->opt_ptr = h->opt_list.as<int32_t>();
-                        int rcs = n_theta_host > 0 ? region2_launch(n_theta_host, spare, h->stream3, true, true) : MPC_OK;
-                        if (rcs) return rcs;
-                        r2_early_ntot = (long long)n_theta_host + spare;
-                        r2_early_A = n_theta_host > 0;
-                    }
-                }
             }
             // ---- (x,theta) stage with the dictionary cache -------------------------------------------------------------
             const int nxc = h->fast_x >= 2 ? 32 : 16;
@@ -2701,7 +2452,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
             DictCache dc{};
             dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
-    dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
             dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
             if (h->have_prev_dict && h->have_parent_slot) {
                 dc.parent_slot = h->parent_slot.as<int32_t>();
@@ -2760,32 +2510,14 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 // "dictionary stored" for k_children_write.  The end of this level (k_x2 for the unplanned rest, children, counters), the
                 // hand-over and the next level's KKT kernel run beside it.
                 const bool defer = h->x1_defer > 0 && !h->timing && h->stream4;
-                const bool late = defer && h->x1_defer >= 2;      // issued by x1_flush behind the level's last kernels
                 hipStream_t sx1 = defer ? h->stream4 : st;
-                if (defer && !late) { HIP_TRY(h, hipEventRecord(h->ev_x1go, st)); HIP_TRY(h, hipStreamWaitEvent(sx1, h->ev_x1go, 0)); }
+                if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1go, st)); HIP_TRY(h, hipStreamWaitEvent(sx1, h->ev_x1go, 0)); }
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[12], st));
                 LevelCounters *ctr_x1 = defer ? (LevelCounters *)nullptr : ctr;   // (its pivot count would land in the next level's counters)
-                // MPC_X1_LDS_CAP = c > 0: the deferred kernel asks for (144 KB / c) of LDS it never touches, which holds it to c wavefronts per compute unit
-                const unsigned lds_x1 = defer && h->x1_lds_cap > 0 ? (unsigned)((144 * 1024) / h->x1_lds_cap) & ~255u : 0u;
-                const int32_t *x1_n_ptr = pl.x1_n;
-                if (late) {
-                    // the list's length lives among the level's counters, which the next level clears: the late launch reads a copy
-                    int32_t *keep = xb + 6 * nn;
-                    hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned int *>(pl.x1_n), reinterpret_cast<unsigned int *>(keep), 1);
-                    x1_n_ptr = keep;
-                }
-                const bool two = (h->fast_x & 1) != 0;
-                const int32_t *x1_list_p = pl.x1_list, *plan_slot_p = pl.plan_slot, *plan_step_p = pl.plan_step;
-                auto launch_x1 = [h, two, g1, lds_x1, sx1, pfx, x1_list_p, x1_n_ptr, ctr_x1, dc, nxc, plan_slot_p, plan_step_p, late, defer]() -> int {
-                    if (late) { HIP_TRY(h, hipEventRecord(h->ev_x1go, h->stream)); HIP_TRY(h, hipStreamWaitEvent(sx1, h->ev_x1go, 0)); }
-                    if (two) hipLaunchKernelGGL((k_x1<2>), dim3(g1), dim3(64), lds_x1, sx1, pfx, x1_list_p, x1_n_ptr, ctr_x1, dc, nxc, plan_slot_p, plan_step_p);
-                    else hipLaunchKernelGGL((k_x1<1>), dim3(g1), dim3(64), lds_x1, sx1, pfx, x1_list_p, x1_n_ptr, ctr_x1, dc, nxc, plan_slot_p, plan_step_p);
-                    HIP_TRY(h, hipGetLastError());
-                    if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1done, sx1)); h->x1_pending = true; }
-                    return MPC_OK;
-                };
-                if (late) h->x1_stash = launch_x1;
-                else { int rcx = launch_x1(); if (rcx) return rcx; }
+                if (h->fast_x & 1) hipLaunchKernelGGL((k_x1<2>), dim3(g1), dim3(64), 0, sx1, pfx, pl.x1_list, pl.x1_n, ctr_x1, dc, nxc, pl.plan_slot, pl.plan_step);
+                else hipLaunchKernelGGL((k_x1<1>), dim3(g1), dim3(64), 0, sx1, pfx, pl.x1_list, pl.x1_n, ctr_x1, dc, nxc, pl.plan_slot, pl.plan_step);
+                HIP_TRY(h, hipGetLastError());
+                if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1done, sx1)); h->x1_pending = true; }
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[13], st));
                 // what is left: the register simplex, list lengths on the device
                 DictCache dr = dc;
@@ -2809,7 +2541,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // One partition after the theta stage: [0] numerically doubtful (status 7), [1] feasible and [2] optimal (decided
             // in theta space; they only need a dictionary for their children), [3] feasibility still open.
             int32_t cntA[PART_CLASSES] = {0, 0, 0, 0};
-            const bool x_first = lean && !early_xq && h->x_first && h->storing && dc.parent_slot && h->x1 > 0 && n >= std::max<long long>(h->x1_min, h->x_first_min) && n <= h->x_first_max &&
+            const bool x_first = !early_xq && h->x_first && h->storing && dc.parent_slot && h->x1 > 0 && n >= std::max<long long>(h->x1_min, h->x_first_min) && n <= h->x_first_max &&
                                  n <= 0x7fffffffLL && !(flags & MPC_LEVEL_GRAPH);
             if (x_first) {
                 { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA, true, dcnt + 28); if (rcs) return rcs; }
@@ -2828,15 +2560,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 // The thread pass is still rewriting the statuses of ITS candidates (NEEDX -> feasible / infeasible / singular) on the second
                 // stream: this partition asks only for the two classes it never touches -- doubtful and optimal candidates of the theta
                 // stage --, so that the region stage can start beside it; the open candidates are listed when the pass has ended (below).
-                if (r2_early) {
-                    // (queue form: the optimal candidates are the queue; region wavefronts are already rewriting their statuses.  The doubtful
-                    //  candidates are counted by the theta kernel itself: without one -- the usual case -- no partition is needed at all, and
-                    //  its 1024-thread workgroups would wait for room beside the region wavefronts: 0.75 ms on config 4's last level)
-                    HIP_TRY(h, hipEventSynchronize(h->ev_part));
-                    if (h->tot_host[11] > 0) { int rcs = partition({{ST_RETRY, 0}}, cntA); if (rcs) return rcs; }
-                    cntA[2] = h->tot_host[10];
-                    h->opt_ptr = h->opt_list.as<int32_t>();
-                } else { int rcs = partition({{ST_RETRY, 0}, {ST_OPT_PENDING, 2}}, cntA); if (rcs) return rcs; }
+                { int rcs = partition({{ST_RETRY, 0}, {ST_OPT_PENDING, 2}}, cntA); if (rcs) return rcs; }
                 cntA[3] = (int32_t)std::min<long long>(n, 0x7fffffffLL);     // a bound, for the decisions that follow; the count comes after the join
             } else { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA); if (rcs) return rcs; }
             // The doubtful candidates are re-solved by the LDS engine, which can refactorise its basis: a few hundred
@@ -2871,22 +2595,9 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // a CU halves that CU's share of it -- config 3's last level loses 0.1-0.25 ms with the region stage under it)
             const size_t lds_q = (size_t)h->dict_stride_d * sizeof(double) + (size_t)h->dict_stride_i * sizeof(int32_t);
             const bool quick_test = cntA[3] > 0 && !(flags & MPC_LEVEL_GRAPH) && !h->storing && dc.parent_slot && !h->no_xquick;
-            const bool use_grouped = quick_test && !h->no_xqgroup && ((h->last_level_n > 0 && (long long)cntA[3] >= 10 * h->last_level_n) || h->force_xqgroup) &&
+            const bool use_grouped = quick_test && !h->no_xqgroup && h->last_level_n > 0 && (long long)cntA[3] >= 10 * h->last_level_n &&
                                      cntA[3] >= 4096 && lds_q <= 64 * 1024 && !early_xq;   // (after the thread pass few candidates per parent are left)
-            if (r2_early_A) {
-                // queue form: the early launch is running; the queue is closed and holds cntA[2] candidates -- the drain launch takes what is
-                // left with the full width, and the host learns how many chunks of slots there are
-                h->n_opt = cntA[2];
-                region_extra = (int32_t)std::max<long long>(0, r2_early_ntot - cntA[2]);     // every slot behind the queue's is a spare one
-                if (h->so.active) {
-                    h->so.n_chunks = (int)(((long long)cntA[2] + (1ll << h->so.shift) - 1) >> h->so.shift);
-                    h->cw_chunks = h->so.n_chunks;
-                }
-                if (cntA[2] > 0) { int rcs = region2_drain(cntA[2]); if (rcs) return rcs; r2_drained = true; }
-                region_launched = true;
-                stream_ready(h);
-            } else
-            if (!h->no_roverlap && !h->theta_open && cntA[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH) && x_items >= h->roverlap_min && (!use_grouped || h->xqg_overlap)) {
+            if (!h->no_roverlap && !h->theta_open && cntA[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH) && x_items >= h->roverlap_min && !use_grouped) {
                 // Candidates that turn out optimal later -- re-solved doubtful ones: the n_early of the theta stage, rarely one of
                 // the (x,theta) stage -- get spare slots behind the launch's and take the LDS-engine route of the candidates
                 // k_region2 gives up on.  The spare slots cover every re-solved candidate of the theta stage plus up to 1,024 of the
@@ -2897,7 +2608,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 const int32_t hold = std::min<int32_t>(std::max(h->test_late, 0), cntA[2] - 1);
                 const int32_t n_launch = cntA[2] - hold;
                 region_extra = std::max(0, n_early + hold + std::min<int32_t>(cntA[3], 1024) - std::max(h->test_spare, 0));
-                if (!r2_early) { rprep.copy_dst = h->opt_list.as<int32_t>(); rprep.copy_src = part_list(2); rprep.copy_n = n_launch; rprep_any = true; }   // (queue form: the list IS the queue)
+                rprep.copy_dst = h->opt_list.as<int32_t>(); rprep.copy_src = part_list(2); rprep.copy_n = n_launch; rprep_any = true;
                 h->opt_ptr = h->opt_list.as<int32_t>();
                 h->n_opt = n_launch;
                 int rcs = region2_launch(n_launch, region_extra, h->stream3, x_items >= h->roverlap_long);
@@ -2949,7 +2660,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 HIP_TRY(h, hipGetLastError());
                 n_needx = 0;
             }
-            bool xretry_forked = false;
             if (quick_test) {
                 // last level: decisions only -- the quick test on three vectors of the parent's dictionary first
                 DictCache dq = dc;
@@ -2979,7 +2689,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                     if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[11], st));
                     HIP_TRY(h, hipGetLastError());
                     xq_thread_timed = true;
-                    if (lean && !use_grouped) { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 9); if (rcs) return rcs; xqt_lean = true; }   // (the grouped form sizes its group scan on the host)
+                    if (!use_grouped) { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 9); if (rcs) return rcs; xqt_lean = true; }   // (the grouped form sizes its group scan on the host)
                     else { int32_t n_left = 0; int rcs = compact(ST_NEEDX, ST_NEEDX_SING, &n_left); if (rcs) return rcs; xq_n = n_left; }
                     HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
                     std::swap(h->xq_list, h->retry_list);   // compact() filled retry_list; keep it as the wavefront kernel's list
@@ -2987,10 +2697,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 }
                 dq.chunk = (int)std::max<long long>(1, std::min<long long>(16, xq_n / (grid_q * 4)));
                 if (xqt_lean) { dq.n_list_dev = dcnt + 9; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
-                // doubtful pivots are flagged by the quick test itself and re-solved at once on the second stream (below), unless that stream
-                // is busy with the theta stage's own doubtful candidates (their statuses are still ST_RETRY in the status array)
-                const bool xq_flags_retry = h->xq_retry && n_early == 0 && lean;
-                dq.flag_retry = xq_flags_retry ? 1 : 0;
                 const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(xqt_lean ? (long long)xq_n : ((long long)xq_n + dq.chunk - 1) / dq.chunk, grid_q))), bb(64);
                 // Grouped by parent when a parent has many open children (config 3: 12.6 per parent, -0.5 ms; config 4: 7.1 per
                 // parent, where the per-candidate reads of k_xq are cheaper than one 16 KB copy per parent, +0.45 ms): threshold 10.
@@ -3016,26 +2722,8 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[9], st));
                 kernel_timed[4] = true;
                 HIP_TRY(h, hipGetLastError());
-                if (xq_flags_retry) {
-                    // The candidates the quick test flagged as doubtful (config 3's last level: 217) are re-solved by the LDS engine NOW, on the
-                    // second stream, beside k_x2 and the end of the level -- rounds 1-4 let k_x2 repeat their runs to flag them, and started
-                    // the re-solve (0.6 ms of a few hundred long wavefronts) behind everything else, then repeated the end of the level.
-                    { int rcs = compact(ST_RETRY, ST_RETRY, nullptr, dcnt + 11); if (rcs) return rcs; }
-                    HIP_TRY(h, h->xretry_list.ensure(nn * sizeof(int32_t), st));
-                    std::swap(h->xretry_list, h->retry_list);
-                    HIP_TRY(h, hipEventRecord(h->ev_xfork, st));
-                    HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_xfork, 0));
-                    HIP_TRY(h, hipMemsetAsync(&ctr->work_retry, 0, sizeof(unsigned int), h->stream2));
-                    hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>(xq_n, 4096), h->grid_v))), dim3(64), h->lds_v, h->stream2, h->Pv,
-                                       h->frontier.as<int32_t>(), (long long)xq_n, k, stp, ctr, h->xretry_list.as<int32_t>(), dcnt + 11);
-                    HIP_TRY(h, hipGetLastError());
-                    HIP_TRY(h, hipEventRecord(h->ev_xjoin, h->stream2));
-                    xretry_forked = true;
-                }
-                int32_t n_left = 0;
-                if (lean) { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 8); if (rcs) return rcs; xq_lean = true; n_left = n_needx; }
-                else { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, &n_left); if (rcs) return rcs; }
-                n_needx = n_left;   // lean: the bound (everything the quick test was given)
+                { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 8); if (rcs) return rcs; }
+                xq_lean = true;   // n_needx stays the bound (everything the quick test was given)
                 needx_list = h->retry_list.as<int32_t>();
             }
             if (x_done) n_x_items = n_needx + dc.n_pre1 + dc.n_pre2;      // (queued behind the partition, above)
@@ -3067,14 +2755,9 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             }
             // second partition: [0] doubtful candidates of the (x,theta) stage, [2] the optimal candidates for the region stage
             int32_t cntB[PART_CLASSES] = {0, 0, 0, 0};
-            if (xretry_forked) {   // the re-solved doubtful candidates of the quick test carry their final statuses now
-                HIP_TRY(h, hipStreamWaitEvent(st, h->ev_xjoin, 0));
-                HIP_TRY(h, hipMemsetAsync(&ctr->work_retry, 0, sizeof(unsigned int), st));
-            }
             if (region_launched) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rjoin, 0));   // the region kernel rewrites statuses
-            if (r2_drained) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rjoin2, 0));
             bool have_cntB = false;
-            if (region_launched && lean && !h->no_spec_tail) {
+            if (region_launched && !h->no_spec_tail) {
                 // The overlapped region stage has finished (the stream waits for it above), so in the usual case nothing is left to do but
                 // the end of the level: no doubtful candidate of the (x,theta) stage, no late optimal one, none that k_region2 gave up on.
                 // The three counts that say so used to cost three host round trips (this partition, the n_rretry read-back, the final one:
@@ -3116,7 +2799,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                                    h->frontier.as<int32_t>(), (long long)n_retry, k, h->status.as<uint8_t>(), ctr, part_list(0), (const int32_t *)nullptr);
                 HIP_TRY(h, hipGetLastError());
                 if (region_launched) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rjoin, 0));
-                if (r2_drained) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rjoin2, 0));
                 { int rcs = recession(); if (rcs) return rcs; }
                 { int rcs = partition({{ST_OPT_PENDING, 2}}, cntB); if (rcs) return rcs; }   // they may have turned out optimal
             }
@@ -3190,18 +2872,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         if (prep_any || rprep_any) return fail(h, MPC_ERR_STATE, "level_run: a queued preparation (clear / copy) was never issued");
         h->r3_dirty = false;   // the main stream waited for ev_rjoin before the second partition
         std::memcpy(&host_ctr, h->tot_host + 16, sizeof(LevelCounters));
-        h->n_r2_early = 0;
-        if (r2_early_A) {
-            if (host_ctr.q_fault) return fail(h, MPC_ERR_HIP, "region stage, queue form: a claimed queue entry never arrived");
-            h->n_r2_early = host_ctr.q_early;
-            // the last chunk of slots is a partial one the kernel could not recognise as complete (it never knew the queue's final length):
-            // every slot is complete now
-            if (h->so.active && h->st_flags.p) {
-                int32_t *fl = h->st_flags.as<int32_t>();
-                for (int j = 0; j < h->so.n_chunks; ++j) __atomic_store_n(fl + j, 1, __ATOMIC_RELEASE);
-            }
-            if (std::getenv("MPC_DEBUG_R2_EARLY")) std::fprintf(stderr, "[mpc] k=%d queue form of the region stage: %u of %lld regions' candidates built by the early launch\n", k, host_ctr.q_early, (long long)h->n_opt);
-        }
         {
             const int32_t *cnt_host = h->tot_host + 16 + (int)(sizeof(LevelCounters) / 4);
             if (children_lean) h->n_children = cnt_host[20];

@@ -398,34 +398,6 @@ def test_mfma_setup_reports_a_semidefinite_hessian():
     eng.close()
 
 
-@pytest.mark.parametrize('name', ['rand_6_3_12_s1', 'c2_dblint_n5', 'quadtank_n3', 'c4_rand_20_8_20_s0'])
-def test_device_setup_and_host_setup_give_the_same_solve(name, monkeypatch):
-    """A/B: the blocks formed by the MFMA kernel against the scalar host computation it replaced (MPC_HOST_SETUP=1): identical
-    verdicts on every level, identical region sets and index sets, coefficients within 1e-8 relative (the north-star tolerance; the sliver region of rand_6_3_12_s1, cond(KKT) 1e9, moves by 2e-9)."""
-    from test_gpu_parity import engine_from_golden, run_levels
-    g = load_golden(name)
-    nl = None if bool(g['complete']) else int(g['n_levels']) + 1
-    runs = []
-    for env in ({}, {'MPC_HOST_SETUP': '1'}):
-        with monkeypatch.context() as m:
-            for key, val in env.items():
-                m.setenv(key, val)
-            eng = engine_from_golden(g)
-            levels, regions = run_levels(eng, nl)
-            runs.append(([(c.copy(), s.copy()) for c, s, _ in levels], {tuple(r.active_set): r for r in regions}))
-            eng.close()
-    (la, ra), (lb, rb) = runs
-    assert len(la) == len(lb)
-    for (ca, sa), (cb, sb) in zip(la, lb):
-        assert numpy.array_equal(ca, cb) and numpy.array_equal(sa, sb)
-    assert set(ra) == set(rb)
-    for key, r1 in ra.items():
-        r2 = rb[key]
-        assert r1.omega_set == r2.omega_set and r1.lambda_set == r2.lambda_set and r1.regular_set == r2.regular_set, key
-        for fld in ('A', 'b', 'C', 'd', 'E', 'f'):
-            assert rel_err(getattr(r1, fld), getattr(r2, fld)) <= COEF_TOL, (key, fld, rel_err(getattr(r1, fld), getattr(r2, fld)))
-
-
 # ---- the quick test's first pass with one thread per candidate (k_xq_thread) ---------------------------------------------------------
 @pytest.mark.parametrize('name', ['c4_rand_20_8_20_s0', 'c3_quadtank_n10'])
 def test_thread_pass_of_the_quick_test_changes_no_verdict(name, monkeypatch):
@@ -526,7 +498,7 @@ def test_one_thread_pass_and_one_step_plans_forced_on_every_level(name, monkeypa
 @pytest.mark.parametrize('name', ['rand_6_3_12_s1', 'c2_dblint_n5', 'quadtank_n3', 'c4_rand_20_8_20_s0', 'mplp_rand_5_3_12_s2'])
 def test_levels_without_host_round_trips_equal_the_classic_path(name, monkeypatch):
     """Four ways through the same levels: default (small levels keep every list length on the device, large ones most of them),
-    MPC_NO_SMALLPATH=1 + MPC_NO_LEAN=1 (round-2 behaviour: a read-back after every stage), MPC_SMALLPATH_MAX=10^9 (every level on
+    MPC_NO_SMALLPATH=1 (every level on the classic path with its host read-backs), MPC_SMALLPATH_MAX=10^9 (every level on
     the no-round-trip path), MPC_TEST_SMALL_FALLBACK=1 (every small level runs that way, reports 'repeat', and is repeated on the
     classic path).  Same kernels, same lists: candidates, verdicts and region records must be IDENTICAL, bit for bit."""
     from test_gpu_parity import engine_from_golden, run_levels
@@ -534,7 +506,7 @@ def test_levels_without_host_round_trips_equal_the_classic_path(name, monkeypatc
     nl = None if bool(g['complete']) else int(g['n_levels']) + 1
     runs = []
     # (fifth, round 5: the small path with the region kernel and the (x,theta) kernel as two launches instead of one grid, and its end in five launches)
-    for env in ({}, {'MPC_NO_SMALLPATH': '1', 'MPC_NO_LEAN': '1'}, {'MPC_SMALLPATH_MAX': '1000000000'}, {'MPC_TEST_SMALL_FALLBACK': '1'},
+    for env in ({}, {'MPC_NO_SMALLPATH': '1'}, {'MPC_SMALLPATH_MAX': '1000000000'}, {'MPC_TEST_SMALL_FALLBACK': '1'},
                 {'MPC_NO_SMALL_RX': '1', 'MPC_NO_SMALL_FUSE': '1'}):
         with monkeypatch.context() as m:
             for key, val in env.items():
@@ -679,30 +651,6 @@ def kkt_cond_large(P, active_set):
     return kkt_condition(P, active_set) > 1e6
 
 
-def test_queue_form_of_the_last_level_region_stage_gives_the_same_regions(monkeypatch):
-    """Round 6, measured and left off: on a large last level the theta kernel lists its optimal candidates in a queue and region
-    wavefronts of an early launch (MPC_R2_EARLY_WPC per CU) take them while the theta stage is still solving; a drain launch behind the theta
-    kernel takes the rest.  Slot order then follows the queue (atomic), so the comparison is by active set: the regions of config 4's
-    fifth level are those of the default form, bit for bit, with the early launch and with the drain launch alone."""
-    from ppopt_amd.mp_solvers import mpqp_hip_combinatorial
-    import bench
-    prog = bench.build_program('c4')
-    ref = {tuple(r.active_set): r for r in mpqp_hip_combinatorial.solve(prog, max_levels=5).critical_regions}
-    prog.release_engine()
-    for wpc in ('4', '0'):
-        monkeypatch.setenv('MPC_R2_EARLY', '1')
-        monkeypatch.setenv('MPC_R2_EARLY_WPC', wpc)
-        prog2 = bench.build_program('c4')
-        got = {tuple(r.active_set): r for r in mpqp_hip_combinatorial.solve(prog2, max_levels=5).critical_regions}
-        prog2.release_engine()
-        assert got.keys() == ref.keys(), wpc
-        for key, r in got.items():
-            q = ref[key]
-            assert r.omega_set == q.omega_set and r.lambda_set == q.lambda_set and r.regular_set == q.regular_set, (wpc, key)
-            for fld in ('A', 'b', 'C', 'd', 'E', 'f'):
-                assert numpy.asarray(getattr(r, fld)).tobytes() == numpy.asarray(getattr(q, fld)).tobytes(), (wpc, key, fld)
-
-
 def test_one_thread_kkt_solves_of_nine_and_ten_rows_equal_the_wavefront_solves():
     """Round 6: k_kkt_thread covers active sets of up to ten inequality rows (eight until now; deeper levels solved their KKT systems
     inside k_theta2, wavefront-wide in LDS).  generate_mpqp_data(10, 2, 20, 7) runs to cardinality 10 (its parameter set is a pointed
@@ -801,16 +749,14 @@ def test_children_from_the_bucketed_pruned_list_equal_the_full_scan(monkeypatch)
 
 
 def test_small_level_kkt_lanes_and_helper_workgroups_change_nothing(monkeypatch):
-    """Round 6: (a) on a small level k_kkt_thread gives a candidate eight lanes -- each repeats the factorisation, the box screen's rows are
+    """Round 6: on a small level k_kkt_thread gives a candidate eight lanes -- each repeats the factorisation, the box screen's rows are
     dealt among them, the verdict is the OR (MPC_KKT_SPREAD=0: one lane) -- and lists its own output instead of a compaction launch
-    (MPC_NO_KKT_LISTS=1); (b) the scan / partition helpers of a large level are four-wavefront workgroups of four items per thread
-    (MPC_HELPER_IT=1: sixteen wavefronts of one).  Every level's statuses and children, and every region of configs 4 and 2, are the same
-    either way."""
+    (MPC_NO_KKT_LISTS=1).  Every level's statuses and children, and every region of configs 4 and 2, are the same either way."""
     import bench
     from ppopt_amd.mp_solvers import mpqp_hip_combinatorial
     from test_gpu_parity import engine_from_golden
-    new = {'MPC_KKT_SPREAD': '1', 'MPC_NO_KKT_LISTS': '0', 'MPC_HELPER_IT': '4', 'MPC_KKT_BOX_SELECT': '0'}
-    old = {'MPC_KKT_SPREAD': '0', 'MPC_NO_KKT_LISTS': '1', 'MPC_HELPER_IT': '1', 'MPC_KKT_BOX_SELECT': '1'}      # (the last: the screen's row test with selects instead of max(a blo, a bhi))
+    new = {'MPC_KKT_SPREAD': '1', 'MPC_NO_KKT_LISTS': '0', 'MPC_KKT_BOX_SELECT': '0'}
+    old = {'MPC_KKT_SPREAD': '0', 'MPC_NO_KKT_LISTS': '1', 'MPC_KKT_BOX_SELECT': '1'}      # (the last: the screen's row test with selects instead of max(a blo, a bhi))
     for name, n_levels in (('c4_rand_20_8_20_s0', 4), ('c2_dblint_n5', 5), ('quadtank_n3', 5), ('c3_quadtank_n10', 3)):
         g = load_golden(name)
         runs = []
