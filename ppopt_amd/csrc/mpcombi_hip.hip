@@ -142,8 +142,6 @@ size_t g_pool_free_bytes = 0;
 constexpr size_t POOL_MAX_FREE = size_t(16) << 30;
 
 hipError_t host_pool_take(size_t bytes, void **out, size_t *got, bool coherent = false) {
-    static const bool coarse_only = [] { const char *ev = std::getenv("MPC_HOST_COARSE"); return ev && ev[0] == '1'; }();   // A/B switch
-    if (coarse_only) coherent = false;
     const size_t gran = bytes >= (size_t(1) << 20) ? (size_t(1) << 20) : (size_t(64) << 10);
     const size_t need = std::max<size_t>((bytes + gran - 1) / gran * gran, gran);
     const int cls = coherent ? 1 : 0;
@@ -308,16 +306,11 @@ struct mpc_handle {
     std::vector<std::pair<void *, size_t>> parked_blocks;   // device blocks the level buffers have outgrown (DevBuf::parked), given back by graveyard_flush
     bool region_side_stream = false; // this level's k_region2 launch ran on the side stream, under the (x,theta) stage (mpc_level_stats)
     int r2_cap_pct = 100;            // MPC_R2_CAP: share (per cent) of k_region2's wave slots an overlapped one-wave-per-candidate launch may take
-    bool no_fetch_kernel = false;    // MPC_NO_FETCH_KERNEL=1: the solve loop fetches the records of a level that did not stream with copy commands and waits (A/B)
-    bool no_spec_tail = false;       // MPC_NO_SPEC_TAIL=1: a large level waits for the second partition and for the region kernel's give-up count before
-                                     // it queues its end (round-3 behaviour); default: the end is queued behind the partition, one synchronisation
     bool test_small_fallback = false; // MPC_TEST_SMALL_FALLBACK=1 (tests): every level run without host round trips reports "repeat on the classic path"
     bool timing = true;              // mpc_set_timing: HIP-event records around the stages and kernels of a level (off: their times in the stats are 0)
-    bool no_kev = false;             // MPC_NO_KEV=1: never
     bool no_smallpath = false;       // MPC_NO_SMALLPATH=1: levels of any size take the classic path with its host round trips (A/B)
     long long smallpath_max = 4096;  // MPC_SMALLPATH_MAX: largest level (candidates) that runs without host round trips (measured: config 4 is
                                      // fastest with 1,024-4,096 -- a level of 15,691 candidates prefers the classic path, which streams its records)
-    bool x_first = true;             // MPC_NO_X_FIRST=1: the (x,theta) stage of a storing level waits for the region stage's launch as in round 4 (A/B)
     long long x_first_min = 4096, x_first_max = 65536;   // MPC_X_FIRST_MIN / _MAX: levels (candidates) whose (x,theta) stage is queued before the read-back.  Measured, config 4: level 3
                                      // (9,880 candidates) 0.72 -> 0.67 ms; level 4 (181 k) 1.51 -> 1.58: there the stage fills the GPU before the region kernel's long wavefronts are placed
                                      // (region kernel 0.48 -> 0.60 ms, the stage itself 0.93 -> 1.03) -- large levels keep the region launch first
@@ -344,16 +337,13 @@ struct mpc_handle {
     int lds_v = 0, lds_r = 0; // dynamic LDS bytes per wavefront
     int debug_cycles = 0;     // MPC_DEBUG_CYCLES=1: per-level cycle breakdown on stderr
     long long last_level_n = 0;   // candidates of the previous level (= the parents of this one)
-    int no_xqgroup = 0;       // MPC_NO_XQGROUP=1: the last level's quick test reads the parent records from HBM per candidate (A/B)
     int no_rbox = 0;          // MPC_NO_RBOX=1: no bounding-box screen of the region rows in k_region2 (A/B)
     int no_rsplit = 0;        // MPC_NO_RSPLIT=1: one wavefront per candidate in k_region2 whatever the load (A/B)
-    int no_xquick = 0;        // MPC_NO_XQUICK=1: no quick (x,theta) test on the last level (A/B)
     int x1 = 1;               // MPC_X1=0: every dictionary of a storing level by the register simplex k_x2 (rounds 1-4); 1: one-step plans (k_xq_thread, plan mode) streamed by k_x1, from the generating parent only; 2 (default): ... and from the candidate's other parents
     long long xqt_min = 4096, x1_min = 2048;   // MPC_XQT_MIN / MPC_X1_MIN: smallest list the one-thread pass / the one-step plans take (tests set 1: every level of a small program goes through them)
     int x1_wpc = 16;          // MPC_X1_WPC: wavefronts per CU of k_x1 (config 4, level 4, beside the region kernel: x stage 1.13 / 0.95 / 1.02 ms with 8 / 16 / 32)
     long long n_x1 = 0;       // dictionaries of the last level run that k_x1 wrote
     float ms_x1 = 0;
-    int no_xq_early = 0;      // MPC_NO_XQ_EARLY=1: the thread pass of the quick test always behind the theta stage, -1: always beside it (A/B)
     long long prev_regions = 0, xq_early_regions = 0;   // MPC_XQ_EARLY_REGIONS = r > 0: the pass runs beside the theta stage only when the level before found fewer than r regions (0: always)
     int xqt_wpc = 16;         // MPC_XQT_WPC: wavefronts per CU of k_xq_thread (it is bound by the cache's request rate: config 4's level 0.45 ms alone with 8 per CU, 0.49 with 24; beside the region kernel 0.92 / 0.70 / 0.78 / 0.75 with 4 / 8 / 12 / 16)
     int xq_thread = -1;       // MPC_XQ_THREAD: 0 = the quick test without its one-thread-per-candidate first pass k_xq_thread (round 5); 1 = the pass against the generating parent only; n >= 2 = ... and up to n - 1 other parents; default: every other parent
@@ -620,30 +610,23 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
     { const char *ev = std::getenv("MPC_DEBUG_CYCLES"); h->debug_cycles = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_RSPLIT"); h->no_rsplit = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_RBOX"); h->no_rbox = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_XQGROUP"); h->no_xqgroup = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_XQUICK"); h->no_xquick = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_XQ_THREAD"); h->xq_thread = ev ? std::atoi(ev) : -1; }
     { const char *ev = std::getenv("MPC_XQT_WPC"); if (ev && std::atoi(ev) > 0) h->xqt_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_X1"); h->x1 = ev ? std::atoi(ev) : 2; }
     { const char *ev = std::getenv("MPC_X1_WPC"); if (ev && std::atoi(ev) > 0) h->x1_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQT_MIN"); if (ev) h->xqt_min = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_X1_MIN"); if (ev) h->x1_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_NO_XQ_EARLY"); h->no_xq_early = ev ? std::atoi(ev) : 0; }
     { const char *ev = std::getenv("MPC_XQ_EARLY_REGIONS"); if (ev) h->xq_early_regions = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_NO_KKT_THREAD"); h->no_kkt_thread = ev ? std::atoi(ev) : 0; }   // 2: only the small-level path
     { const char *ev = std::getenv("MPC_NO_ROVERLAP"); h->no_roverlap = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_TEST_LATE"); h->test_late = ev ? std::atoi(ev) : 0; }
     { const char *ev = std::getenv("MPC_TEST_SPARE"); h->test_spare = ev ? std::atoi(ev) : 0; }
-    { const char *ev = std::getenv("MPC_NO_KEV"); h->no_kev = ev && ev[0] == '1'; h->timing = !h->no_kev; }
-    { const char *ev = std::getenv("MPC_NO_X_FIRST"); h->x_first = !(ev && ev[0] == '1'); }
     { const char *ev = std::getenv("MPC_X_FIRST_MIN"); if (ev) h->x_first_min = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_X_FIRST_MAX"); if (ev) h->x_first_max = std::atoll(ev); }
     { const char *ev = std::getenv("MPC_NO_KKT_LISTS"); h->no_kkt_lists = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALL_RX"); h->no_small_rx = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALL_FUSE"); h->no_small_fuse = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_NO_SMALLPATH"); h->no_smallpath = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_SPEC_TAIL"); h->no_spec_tail = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_FETCH_KERNEL"); h->no_fetch_kernel = ev && ev[0] == '1'; }
     { const char *ev = std::getenv("MPC_X2_WPC"); if (ev && std::atoi(ev) > 0) h->x2_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQ_WPC"); if (ev && std::atoi(ev) > 0) h->xq_wpc = std::atoi(ev); }
     { const char *ev = std::getenv("MPC_XQG_PER_CU"); if (ev && std::atoi(ev) > 0) h->xqg_per_cu = std::atoi(ev); }
@@ -1130,7 +1113,7 @@ int mpc_program_block(mpc_handle *h, int32_t which, double *out, int64_t cap, in
     return MPC_OK;
 }
 int mpc_set_region_overlap(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->no_roverlap = !on; return MPC_OK; }
-int mpc_set_timing(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->timing = on && !h->no_kev; return MPC_OK; }
+int mpc_set_timing(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->timing = on; return MPC_OK; }
 int64_t mpc_region_doubles(const mpc_handle *h) { return h ? h->rec_d : 0; }
 int64_t mpc_region_ints(const mpc_handle *h) { return h ? h->rec_i : 0; }
 int32_t mpc_lds_bytes(const mpc_handle *h, int32_t which) { return !h ? 0 : (which == 0 ? h->lds_v : h->lds_r); }
@@ -1567,7 +1550,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     dc.chunk = 1;
     const int32_t *needx_list = part_list(3);
     const int32_t *needx_n = dcnt + 7;
-    const bool quick_test = !h->storing && dc.parent_slot && !h->no_xquick;
+    const bool quick_test = !h->storing && dc.parent_slot;
     bool merged_rx = false;
     if (fused && !quick_test && !h->no_small_rx) {
         // region kernel + (x,theta) kernel as ONE grid (batch_level.hpp, SmallRX): the two work on disjoint candidates
@@ -1816,7 +1799,7 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
     m.dc = dc;
     m.storing = h->storing ? 1 : 0;
     m.dict_stored_cur = h->storing ? h->dict_stored[h->dict_cur].as<uint8_t>() : nullptr;
-    m.quick_test = (!h->storing && dc.parent_slot && !h->no_xquick) ? 1 : 0;
+    m.quick_test = (!h->storing && dc.parent_slot) ? 1 : 0;
     // pruned masks + children
     m.keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
     m.theta_open = h->theta_open ? 1 : 0;
@@ -2382,12 +2365,12 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // (the previous level's deferred k_x1 is joined by whoever reads dictionary records first: the thread pass on the second stream
             //  below -- the theta kernel reads none and goes ahead --, else the (x,theta) stage behind the theta stage)
             bool early_xq = false;
-            if (kkc && h->no_xq_early <= 0 && h->xq_thread != 0 && !h->no_xquick && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
-                n >= h->xqt_min && (h->no_xq_early < 0 || h->prev_regions < h->xq_early_regions || h->xq_early_regions <= 0)) {
+            if (kkc && h->xq_thread != 0 && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
+                n >= h->xqt_min && (h->prev_regions < h->xq_early_regions || h->xq_early_regions <= 0)) {
                 // (The pass then overlaps the theta stage AND the region stage: the partition behind the theta stage lists only the doubtful
                 //  and the optimal candidates -- classes the pass never touches --, the region kernel starts on its stream, and the open
                 //  candidates are listed when the pass has ended.  Config 4's last level: 1.86 ms with the pass behind the theta stage,
-                //  1.72 beside it; config 3's: 3.45 / 3.25.  MPC_NO_XQ_EARLY=1: behind.)
+                //  1.72 beside it; config 3's: 3.45 / 3.25.)
                 const int nxc_e = h->fast_x >= 2 ? 32 : 16;
                 const long long sd_e = (long long)nxc_e * h->Pf.n_d0r, si_e = dict_ints(h->Pf.n_d0r, nxc_e, h->n_c);
                 const bool will_store = gen_children && (double)nn * (sd_e * 8.0 + si_e * 4.0) / 1e9 <= h->dict_budget_gb;
@@ -2541,7 +2524,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // One partition after the theta stage: [0] numerically doubtful (status 7), [1] feasible and [2] optimal (decided
             // in theta space; they only need a dictionary for their children), [3] feasibility still open.
             int32_t cntA[PART_CLASSES] = {0, 0, 0, 0};
-            const bool x_first = !early_xq && h->x_first && h->storing && dc.parent_slot && h->x1 > 0 && n >= std::max<long long>(h->x1_min, h->x_first_min) && n <= h->x_first_max &&
+            const bool x_first = !early_xq && h->storing && dc.parent_slot && h->x1 > 0 && n >= std::max<long long>(h->x1_min, h->x_first_min) && n <= h->x_first_max &&
                                  n <= 0x7fffffffLL && !(flags & MPC_LEVEL_GRAPH);
             if (x_first) {
                 { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA, true, dcnt + 28); if (rcs) return rcs; }
@@ -2594,8 +2577,8 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // (the grouped quick test keeps four 128-register wavefronts per SIMD busy through LDS latency: one region wavefront on
             // a CU halves that CU's share of it -- config 3's last level loses 0.1-0.25 ms with the region stage under it)
             const size_t lds_q = (size_t)h->dict_stride_d * sizeof(double) + (size_t)h->dict_stride_i * sizeof(int32_t);
-            const bool quick_test = cntA[3] > 0 && !(flags & MPC_LEVEL_GRAPH) && !h->storing && dc.parent_slot && !h->no_xquick;
-            const bool use_grouped = quick_test && !h->no_xqgroup && h->last_level_n > 0 && (long long)cntA[3] >= 10 * h->last_level_n &&
+            const bool quick_test = cntA[3] > 0 && !(flags & MPC_LEVEL_GRAPH) && !h->storing && dc.parent_slot;
+            const bool use_grouped = quick_test && h->last_level_n > 0 && (long long)cntA[3] >= 10 * h->last_level_n &&
                                      cntA[3] >= 4096 && lds_q <= 64 * 1024 && !early_xq;   // (after the thread pass few candidates per parent are left)
             if (!h->no_roverlap && !h->theta_open && cntA[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH) && x_items >= h->roverlap_min && !use_grouped) {
                 // Candidates that turn out optimal later -- re-solved doubtful ones: the n_early of the theta stage, rarely one of
@@ -2757,7 +2740,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             int32_t cntB[PART_CLASSES] = {0, 0, 0, 0};
             if (region_launched) HIP_TRY(h, hipStreamWaitEvent(st, h->ev_rjoin, 0));   // the region kernel rewrites statuses
             bool have_cntB = false;
-            if (region_launched && !h->no_spec_tail) {
+            if (region_launched) {
                 // The overlapped region stage has finished (the stream waits for it above), so in the usual case nothing is left to do but
                 // the end of the level: no doubtful candidate of the (x,theta) stage, no late optimal one, none that k_region2 gave up on.
                 // The three counts that say so used to cost three host round trips (this partition, the n_rretry read-back, the final one:
@@ -3011,7 +2994,7 @@ static int worker_solve(mpc_handle *h) {
                 mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
                 const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t),
                              b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
-                const bool all_slots = h->used_region2 && h->n_rretry == 0 && !h->no_fetch_kernel;   // every record is in slot form on the device
+                const bool all_slots = h->used_region2 && h->n_rretry == 0;   // every record is in slot form on the device
                 if (host_pool_take(b_hd, &lv.hd, nullptr, all_slots) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, all_slots) != hipSuccess ||
                     host_pool_take(b_er, &lv.er, nullptr, all_slots) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
                 if (rc == MPC_OK && all_slots) {
@@ -3554,9 +3537,6 @@ int mpc_fetch_wait(int32_t device) { return fetch_many_wait(device); }
 int mpc_level_batch_fetch(mpc_handle **hs, int32_t n_handles, double *const *head_d, int32_t *const *head_i, const int64_t *cap_slots,
                           double *const *erows, const int64_t *cap_rows, int64_t *n_slots, int64_t *n_rows) {
     if (!hs || n_handles < 0 || !head_d || !head_i || !cap_slots || !erows || !cap_rows || !n_slots || !n_rows) return MPC_ERR_INVALID;
-    static const bool no_many = [] { const char *ev = std::getenv("MPC_NO_FETCH_MANY"); return ev && ev[0] == '1'; }();   // A/B: three copy commands per member
-    static const bool no_merge = [] { const char *ev = std::getenv("MPC_NO_RRETRY_MERGE"); return ev && ev[0] == '1'; }();   // A/B, tests: re-solved candidates' records merged by the host (round 4)
-    auto no_merge_or = [&](bool plain) { return no_merge && !plain; };
     std::vector<FetchEntry> tab;
     mpc_handle *lead = nullptr;
     for (int i = 0; i < n_handles; ++i) {
@@ -3567,7 +3547,7 @@ int mpc_level_batch_fetch(mpc_handle **hs, int32_t n_handles, double *const *hea
         const long long rows_t = h->n_c - h->n_eq + h->n_tc;
         const bool merge = h->n_rretry > 0 && h->rretry_rows < 0;
         const long long rows_out = h->n_rretry > 0 ? h->n_erows + h->n_rretry * rows_t : h->n_erows;   // (bound: a re-solved region keeps at most rows_t rows)
-        const bool fast = !no_many && !no_merge_or(h->n_rretry == 0) && h->level_done && !h->so.active && h->n_regions > 0 && h->n_opt > 0 && h->used_region2 &&
+        const bool fast = h->level_done && !h->so.active && h->n_regions > 0 && h->n_opt > 0 && h->used_region2 &&
                           h->n_rretry <= RRETRY_MERGE_MAX && h->n_opt <= 0x7fffffffLL &&
                           (h->n_rretry == 0 || (h->recd.p && h->reci.p && h->retry_list.p && h->epool.cap >= (size_t)rows_out * (h->n_t + 1) * sizeof(double))) &&
                           cap_slots[i] >= h->n_opt && cap_rows[i] >= rows_out && head_d[i] && head_i[i] && (erows[i] || rows_out == 0) &&

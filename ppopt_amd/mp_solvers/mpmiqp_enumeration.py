@@ -26,7 +26,7 @@ from . import mpqp_hip_combinatorial
 from .solve_mpqp import _COMBINATORIAL, mpqp_algorithm, solve_mpqp
 
 BATCH_CHUNKS = int(os.environ.get('MPC_BATCH_CHUNKS', '2'))   # chunks of fixations solved together (see below)
-MAX_BATCH = int(os.environ.get('MPC_MAX_BATCH', '256'))       # most sub-programs alive at once (one host thread each while they are constructed)
+MAX_BATCH = int(os.environ.get('MPC_MAX_BATCH', '256'))       # most sub-programs alive at once
 
 
 def solve_mpmiqp_enumeration(program, num_cores: int = -1,
@@ -55,67 +55,28 @@ def solve_mpmiqp_enumeration(program, num_cores: int = -1,
             are shared by all fixations: only the right-hand side differs), the redundancy LPs of ALL sub-programs are posed as one device
             batch per shape (Solver.lp_feasible_many; statuses only), their results applied, and the set-ups (mpc_create: C, no interpreter
             lock) run on a few threads.  The two diagnostic LPs of the constructor, whose only outcome is a warning that this function
-            discards, are not posed.  (Round 3: one thread per fixation with the LP calls of all threads coalesced -- 65 ms for 64
-            sub-programs, of which half was interpreter-lock hand-over; MPC_MI_THREADS=1 keeps that form.)"""
-            import copy
-            from ..solver import LPCoalescer
-            if os.environ.get('MPC_MI_THREADS', '0') != '1' and hasattr(program.solver, 'lp_feasible_many'):
-                with warnings.catch_warnings():
-                    warnings.simplefilter('ignore')
-                    subs = [program.generate_substituted_problem(fix, deferred=True) for fix in fixes]
-                    requests = [sub._redundancy_request() for sub in subs]
-                    answers = program.solver.lp_feasible_many([(PA, Pb, [[*eq, i] for i in todo]) for PA, Pb, eq, todo in requests])
-                    for sub, req, ok in zip(subs, requests, answers):
-                        sub._redundancy_apply(req, ok.tolist())
-                    if len(subs) > 2 and num_cores != 1:
-                        with ThreadPoolExecutor(max_workers=min(8, len(subs))) as setup_pool:
-                            list(setup_pool.map(lambda sub: sub.engine(device, closed=True), subs))
-                    else:
-                        for sub in subs:
-                            sub.engine(device, closed=True)
-                return subs
-            if len(fixes) <= 1 or num_cores == 1 or os.environ.get('MPC_NO_LP_COALESCE', '0') == '1':
-                with warnings.catch_warnings():    # the substituted programs repeat the parent's construction warnings
-                    warnings.simplefilter('ignore')
+            discards, are not posed.  (Round 3 ran one thread per fixation with the LP calls of all threads coalesced -- 65 ms for 64
+            sub-programs, of which half was interpreter-lock hand-over; that form has been removed.)  A program built with another solver
+            plug (the constructor's ``solver=``) has no batched LPs: its sub-programs are constructed one after the other."""
+            with warnings.catch_warnings():        # the substituted programs repeat the parent's construction warnings
+                warnings.simplefilter('ignore')
+                if not hasattr(program.solver, 'lp_feasible_many'):
                     subs = [program.generate_substituted_problem(fix) for fix in fixes]
                     for sub in subs:
                         sub.engine(device, closed=True)     # set-up of the sub-program (MFMA set-up kernel)
                     return subs
-            co = LPCoalescer(program.solver, len(fixes))
-            parked = copy.copy(program)
-            parked.solver = co.solver()
-
-            def one(fix):
-                try:
-                    sub = parked.generate_substituted_problem(fix)
-                finally:
-                    co.worker_done()
-                sub.solver = program.solver
-                sub.engine(device, closed=True)
-                return sub
-            # exactly one thread per fixation, all alive until every construction is through: the coalescer counts on each of them
-            # reaching its next LP call (an executor may run two constructions on one thread, one after the other)
-            import threading
-            results, errors = [None] * len(fixes), []
-
-            def run(j):
-                try:
-                    results[j] = one(fixes[j])
-                except BaseException as ex:        # re-raised below, in the caller's thread
-                    errors.append(ex)
-            with warnings.catch_warnings():        # one filter around all threads (catch_warnings is not thread-safe)
-                warnings.simplefilter('ignore')
-                threads = [threading.Thread(target=run, args=(j,)) for j in range(len(fixes))]
-                for th in threads:
-                    th.start()
-                for th in threads:
-                    th.join()
-            if errors:
-                for sub in results:
-                    if sub is not None:
-                        sub.release_engine()
-                raise errors[0]
-            return results
+                subs = [program.generate_substituted_problem(fix, deferred=True) for fix in fixes]
+                requests = [sub._redundancy_request() for sub in subs]
+                answers = program.solver.lp_feasible_many([(PA, Pb, [[*eq, i] for i in todo]) for PA, Pb, eq, todo in requests])
+                for sub, req, ok in zip(subs, requests, answers):
+                    sub._redundancy_apply(req, ok.tolist())
+                if len(subs) > 2 and num_cores != 1:
+                    with ThreadPoolExecutor(max_workers=min(8, len(subs))) as setup_pool:
+                        list(setup_pool.map(lambda sub: sub.engine(device, closed=True), subs))
+                else:
+                    for sub in subs:
+                        sub.engine(device, closed=True)
+            return subs
 
         # MPC_BATCH_CHUNKS > 1: the fixations are solved in chunks -- while the device works on the levels of one chunk (the host waits
         # inside the C ABI, GIL released) a second thread substitutes, presolves and sets up the sub-programs of the next one.  Measured

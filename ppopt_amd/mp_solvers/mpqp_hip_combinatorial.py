@@ -72,7 +72,6 @@ REGION_STATUS = 3   # MPC_REGION
 # overlap gains there (sub-programs of the mixed-integer enumeration, the first levels of every solve)
 STREAM_MIN_CANDIDATES = int(os.environ.get('MPC_STREAM_MIN', '512'))
 BASE_ON_TWIN = os.environ.get('MPC_NO_TWIN', '0') != '1'   # the base-set check on a second handle, started with the first streamed level
-MANY_LOOP = os.environ.get('MPC_NO_MANY_LOOP', '0') != '1'     # solve_many: the level loop of all members inside the library (mpc_solve_many_start); '1' = from here (A/B, tests)
 SOLVE_LOOP = os.environ.get('MPC_NO_SOLVE_LOOP', '0') != '1'   # the level loop inside the library (mpc_solve_start); '1' = level by level from here (A/B)
 
 
@@ -353,9 +352,6 @@ def _solve_many(programs, device: int = 0, max_levels: Optional[int] = None, pru
         d = max(e.n_x, e.n_t) - e.n_eq
         depth_max.append(d if max_levels is None else min(d, max_levels))
         e.set_timing(profile is not None)
-        if not MANY_LOOP:      # (the library's loop does both itself)
-            e.pruned_clear()
-            e.frontier_root()
     # Device memory: a member's level holds buffers sized by its number of candidates (region records, children, two generations of
     # the dictionary cache: Engine.level_memory_gb).  Members whose next level does not fit the budget next to the others are PARKED
     # at their current level and resumed when the running ones have finished (and given their level buffers back: Engine.trim).
@@ -391,7 +387,7 @@ def _solve_many(programs, device: int = 0, max_levels: Optional[int] = None, pru
     first = [i for i in range(len(engs)) if depth_max[i] > 0]
     job = None
     try:
-        if MANY_LOOP and first:
+        if first:
             # The loop over the levels of ALL members runs on a thread of the library (mpc_solve_many_*): shared launches, the level's record
             # copy, the frontier hand-overs, the next level -- the device does not wait for this interpreter between levels; this thread
             # builds the region objects of a level while later levels run.  The loop stops when the members' next level would not fit the

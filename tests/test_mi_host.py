@@ -203,79 +203,6 @@ def test_milp_any_feasible_and_solve_milp_with_bounded_batches(monkeypatch):
         S.solve_milp_batch(None, A, b, [[]] * 64, bins)
 
 
-# ---- LP calls of several threads posed as shared device batches (solver.LPCoalescer; the presolve of the enumeration's sub-programs) ----
-def test_lp_coalescer_poses_the_calls_of_all_threads_together(monkeypatch):
-    from concurrent.futures import ThreadPoolExecutor
-    from ppopt_amd import solver as solver_mod
-    from ppopt_amd.solver import LPCoalescer
-    counter = {'lps': 0, 'max_flag_bytes': 0}
-    monkeypatch.setattr(solver_mod._lib, 'lp_solve_batch', _scipy_lp_batch(counter))
-    rng = numpy.random.default_rng(5)
-
-    def box_lp(n, shift):      # a box around `shift`, two extra cuts; feasible, bounded
-        A = numpy.vstack([numpy.eye(n), -numpy.eye(n), rng.standard_normal((2, n))])
-        b = numpy.concatenate([shift + 1.0, 1.0 - shift, [5.0, 5.0]])
-        return A, b, rng.standard_normal(n)
-    jobs = [box_lp(3 if j % 2 else 4, rng.standard_normal(3 if j % 2 else 4) * 0.1) for j in range(10)]
-
-    def work(solver, job, extra_round):
-        A, b, c = job
-        out = [solver.solve_lp(c, A, b, [])]                                           # stage 1: one LP
-        out.append(solver.solve_lp_batch(None, A, b, [[i] for i in range(A.shape[0])]))    # stage 2: one LP per row
-        if extra_round:
-            out.append(solver.solve_lp(-c, A, b, [0]))                                 # some workers make a third call
-        return out
-    plain = Solver()
-    want = [work(plain, job, j % 3 == 0) for j, job in enumerate(jobs)]
-    calls_plain = counter['calls']
-    counter['calls'] = 0
-    co = LPCoalescer(plain, len(jobs))
-    parked = co.solver()
-
-    def worker(args):
-        j, job = args
-        try:
-            return work(parked, job, j % 3 == 0)
-        finally:
-            co.worker_done()
-    with ThreadPoolExecutor(max_workers=len(jobs)) as pool:
-        got = list(pool.map(worker, enumerate(jobs)))
-    assert counter['calls'] <= 6 < calls_plain            # three stages x two shapes at most, against 24 separate calls
-    assert co.n_calls == calls_plain
-
-    def same(a, b):
-        if a is None or b is None:
-            return a is None and b is None
-        return a.obj == b.obj and numpy.array_equal(a.sol, b.sol) and numpy.array_equal(a.active_set, b.active_set)
-    for w, g in zip(want, got):
-        assert same(w[0], g[0]) and len(w[1]) == len(g[1]) and all(same(x, y) for x, y in zip(w[1], g[1]))
-        assert len(w) == len(g) and (len(w) == 2 or same(w[2], g[2]))
-
-
-def test_lp_coalescer_hands_a_failure_to_every_parked_caller(monkeypatch):
-    from concurrent.futures import ThreadPoolExecutor
-    from ppopt_amd import solver as solver_mod
-    from ppopt_amd.solver import LPCoalescer
-
-    def broken(*a, **k):
-        raise RuntimeError('device lost')
-    monkeypatch.setattr(solver_mod._lib, 'lp_solve_batch', broken)
-    co = LPCoalescer(Solver(), 4)
-    parked = co.solver()
-    A, b = numpy.vstack([numpy.eye(2), -numpy.eye(2)]), numpy.ones(4)
-
-    def worker(_):
-        try:
-            parked.solve_lp(None, A, b, [])
-            return 'no error'
-        except RuntimeError as ex:
-            return str(ex)
-        finally:
-            co.worker_done()
-    with ThreadPoolExecutor(max_workers=4) as pool:
-        assert list(pool.map(worker, range(4))) == ['device lost'] * 4
-
-
 def test_substituted_rows_are_cached_per_program_and_follow_row_changes():
     """MPMILP_Program._substituted_rows finds the rows with continuous / parametric content once per program; a program whose rows
     are replaced afterwards must not reuse the old selection."""

@@ -36,8 +36,8 @@ def run(env, args, want):
 if __name__ == '__main__':
     args = [int(v) for v in sys.argv[1:5]]
     want = [tuple(int(x) for x in s.split(',')) for s in sys.argv[5].split(';')]
-    for name, env in (('default', {}), ('round-4 paths', {'MPC_XQ_THREAD': '0', 'MPC_X1': '0', 'MPC_NO_KKT_LISTS': '1', 'MPC_NO_SMALL_FUSE': '1', 'MPC_NO_X_FIRST': '1'}),
-                      ('classic, no quick test', {'MPC_NO_SMALLPATH': '1', 'MPC_NO_XQUICK': '1', 'MPC_XQ_THREAD': '0', 'MPC_X1': '0'}), ('LDS engine only', {'MPC_FORCE_V1': '1'})):
+    for name, env in (('default', {}), ('round-4 paths', {'MPC_XQ_THREAD': '0', 'MPC_X1': '0', 'MPC_NO_KKT_LISTS': '1', 'MPC_NO_SMALL_FUSE': '1'}),
+                      ('classic path', {'MPC_NO_SMALLPATH': '1', 'MPC_XQ_THREAD': '0', 'MPC_X1': '0'}), ('LDS engine only', {'MPC_FORCE_V1': '1'})):
         print('%-24s' % name, run(env, args, want))
     sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + '/tests')
     import numpy, warnings
