@@ -477,6 +477,31 @@ int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const int64_t *ro
                     const double *start /* n_poly x n */, int64_t chains, int64_t samples, int64_t n_steps, uint64_t seed,
                     double *out /* n_poly x chains x samples x n, host */, int32_t *status /* n_poly x chains */, float *ms);
 
+/* ---- 2-D and 1-D slices of a batch of polytopes (plots, exact coverage in a plane) ------------------------------------- */
+/* The slice of every region {theta : E_r theta <= f_r} by the plane theta = theta0 + U z (U: n x 2 row-major, U[t][k]), clipped to the
+ * box lo_k <= z_k <= hi_k (box = {lo0, lo1, hi0, hi1}, finite, lo < hi), as a convex polygon; see DESIGN for the method.
+ * ef_rows: stacked rows [f | E] (n + 1 doubles each) of all regions, row_off[n_regions + 1] (<= 256 rows per region, 1 <= n <= 64).
+ * Region r owns the vertex slots row_off[r] + 4 r .. row_off[r + 1] + 4 r + 3 (its rows + 4): vert holds count[r] vertices (z_0, z_1)
+ * counter-clockwise from the vertex of smallest atan2 about their mean; edge_row[k] is the row whose edge starts at vertex k (the
+ * region's own row index, or -1 .. -4 for the box sides z_0 <= hi0, z_1 <= hi1, z_0 >= lo0, z_1 >= lo1); area[r] the polygon's
+ * area; slots past count[r] are not written.  status: MPC_SLICE_FULL, MPC_SLICE_EMPTY (count 0), MPC_SLICE_LOWDIM (a segment or a
+ * point: area <= eps D^2, D the box diameter; the vertices found are given), ORed with MPC_SLICE_CUT when a box side is an edge.
+ * eps (> 0, < 1) owns every tolerance: minimum edge length eps D, zero normal |E_i U| <= eps |E_i| max_k |U_k| (and parallel rows
+ * |sin| <= eps), lower-dimensional area eps D^2.  ms: device time of the kernel (may be NULL). */
+#define MPC_SLICE_FULL 0
+#define MPC_SLICE_EMPTY 1
+#define MPC_SLICE_LOWDIM 2
+#define MPC_SLICE_CUT 4
+int mpc_slice_polygons(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                       const double *U, const double *box, double eps, double *vert /* (row_off[n_regions] + 4 n_regions) x 2 */,
+                       int32_t *edge_row /* row_off[n_regions] + 4 n_regions */, int32_t *count, double *area, int32_t *status, float *ms);
+/* The slice of every region by the line theta = theta0 + u t within t_lo <= t <= t_hi (finite, t_lo < t_hi): interval[r] = [a, b]
+ * (NaN for MPC_SLICE_EMPTY), status as above with MPC_SLICE_LOWDIM for b - a <= eps (t_hi - t_lo) and MPC_SLICE_CUT when an end is
+ * t_lo or t_hi. */
+int mpc_slice_intervals(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                        const double *u, double t_lo, double t_hi, double eps, double *interval /* n_regions x 2 */, int32_t *status,
+                        float *ms);
+
 /* ---- consumer of the path: point location over a solution's critical regions, batched ---------------------------- */
 /* Replaces the loop of Solution.get_region / Solution.evaluate (solution.py:45-112, CriticalRegion.is_inside
  * critical_region.py:83-86) for many parameter points at once.

@@ -20,6 +20,8 @@ MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, M
 MPC_SOLVE_FETCH = 64   # flag of mpc_solve_start
 MPC_HR_OK, MPC_HR_OUTSIDE, MPC_HR_UNBOUNDED = range(3)   # chain statuses of mpc_hit_and_run
 HR_MAX_DIM, HR_MAX_ROWS = 64, 256   # limits of mpc_hit_and_run
+MPC_SLICE_FULL, MPC_SLICE_EMPTY, MPC_SLICE_LOWDIM, MPC_SLICE_CUT = 0, 1, 2, 4   # statuses of mpc_slice_polygons / _intervals (CUT: a flag)
+SLICE_EPS = 1e-9   # default of the one tolerance argument of the slice kernels
 INFEASIBLE, FEASIBLE, OPTIMAL_NO_REGION, REGION, SINGULAR_KKT, LP_LIMIT = range(6)
 LP_OPTIMAL, LP_INFEASIBLE, LP_UNBOUNDED, LP_ITERLIMIT = range(4)
 MASK_WORDS = 2
@@ -208,6 +210,10 @@ def load():
                                                 _dp, _u8p]),
         'mpc_hit_and_run': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_int64, ctypes.c_uint64, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_slice_polygons': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, ctypes.c_double,
+                                              _dp, _ip, _ip, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_slice_intervals': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_double, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -225,7 +231,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_frontier_get', 'mpc_pruned_clear', 'mpc_pruned_add', 'mpc_pruned_add_device',
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
-                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run']
+                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -984,6 +990,90 @@ def hit_and_run(row_off, ab_rows, start, chains: int, samples: int, n_steps: int
 
 
 hit_and_run.last_ms = 0.0
+
+
+def _slice_rows(who, row_off, ef_rows, n, eps):
+    """(row_off, ef_rows) checked against the limits of the slice kernels; MpcError before any launch."""
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ef = _f64(numpy.asarray(ef_rows, dtype=numpy.float64))
+    if len(off) < 1 or off[0] != 0 or numpy.any(numpy.diff(off) < 0):
+        raise MpcError(f'{who}: row_off must start at 0 and not decrease')
+    if not 1 <= n <= HR_MAX_DIM:
+        raise MpcError(f'{who}: dimension {n} outside 1..{HR_MAX_DIM}')
+    if ef.ndim != 2 or ef.shape != (int(off[-1]), n + 1):
+        raise MpcError(f'{who}: ef_rows has shape {ef.shape}, expected ({int(off[-1])}, {n + 1})')
+    if numpy.any(numpy.diff(off) > HR_MAX_ROWS):
+        raise MpcError(f'{who}: at most {HR_MAX_ROWS} rows per region, got {int(numpy.max(numpy.diff(off)))}')
+    if not 0.0 < float(eps) < 1.0:
+        raise MpcError(f'{who}: eps must lie in (0, 1)')
+    return off, ef
+
+
+def slice_polygons(row_off, ef_rows, theta_0, U, box, eps: float = SLICE_EPS, device: int = 0):
+    """The slice of every region {E theta <= f} by the plane theta = theta_0 + U z, clipped to box = (lo0, lo1, hi0, hi1), as a convex
+    polygon (include/mpcombi.h, mpc_slice_polygons).  ef_rows [rows, n+1] = [f | E] stacked, row_off [R+1], theta_0 [n],
+    U [n, 2].  Returns (vert [rows + 4R, 2], edge_row [rows + 4R], count [R], area [R], status [R]); region r's vertices are
+    vert[row_off[r] + 4r :][:count[r]].  The kernel time is left in ``slice_polygons.last_ms``.  Bad shapes, more than 256 rows in a
+    region, n outside 1..64 or a box that is not finite with lo < hi raise MpcError before any launch."""
+    th0 = _f64(numpy.asarray(theta_0, dtype=numpy.float64).reshape(-1))
+    n = len(th0)
+    Um = _f64(numpy.asarray(U, dtype=numpy.float64))
+    if Um.shape != (n, 2):
+        raise MpcError(f'slice_polygons: U has shape {Um.shape}, expected ({n}, 2)')
+    bx = _f64(numpy.asarray(box, dtype=numpy.float64).reshape(-1))
+    if bx.shape != (4,) or not numpy.all(numpy.isfinite(bx)) or not (bx[0] < bx[2] and bx[1] < bx[3]):
+        raise MpcError(f'slice_polygons: box must be (lo0, lo1, hi0, hi1), finite, with lo < hi; got {bx}')
+    if not numpy.all(numpy.isfinite(th0)) or not numpy.all(numpy.isfinite(Um)):
+        raise MpcError('slice_polygons: theta_0 and U must be finite')
+    off, ef = _slice_rows('slice_polygons', row_off, ef_rows, n, eps)
+    R = len(off) - 1
+    slots = int(off[-1]) + 4 * R
+    vert = numpy.zeros((slots, 2))
+    edge = numpy.zeros(slots, dtype=numpy.int32)
+    count = numpy.zeros(R, dtype=numpy.int32)
+    area = numpy.zeros(R)
+    status = numpy.zeros(R, dtype=numpy.int32)
+    ms = ctypes.c_float(0.0)
+    L = load()
+    rc = L.mpc_slice_polygons(int(device), n, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), th0.ctypes.data_as(_dp), Um.ctypes.data_as(_dp),
+                              bx.ctypes.data_as(_dp), float(eps), vert.ctypes.data_as(_dp), edge.ctypes.data_as(_ip), count.ctypes.data_as(_ip),
+                              area.ctypes.data_as(_dp), status.ctypes.data_as(_ip), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_slice_polygons failed ({rc}): {L.mpc_last_global_error().decode()}')
+    slice_polygons.last_ms = float(ms.value)
+    return vert, edge, count, area, status
+
+
+slice_polygons.last_ms = 0.0
+
+
+def slice_intervals(row_off, ef_rows, theta_0, u, t_range, eps: float = SLICE_EPS, device: int = 0):
+    """The slice of every region by the line theta = theta_0 + u t within t_range = (t_lo, t_hi) (mpc_slice_intervals): (interval [R, 2]
+    (NaN rows for MPC_SLICE_EMPTY), status [R]).  The kernel time is left in ``slice_intervals.last_ms``; MpcError before any launch
+    for bad inputs."""
+    th0 = _f64(numpy.asarray(theta_0, dtype=numpy.float64).reshape(-1))
+    n = len(th0)
+    uv = _f64(numpy.asarray(u, dtype=numpy.float64).reshape(-1))
+    if uv.shape != (n,) or not numpy.all(numpy.isfinite(uv)) or not numpy.all(numpy.isfinite(th0)):
+        raise MpcError(f'slice_intervals: theta_0 and u must be finite vectors of the same length, got {th0.shape} and {uv.shape}')
+    t_lo, t_hi = (float(v) for v in t_range)
+    if not (numpy.isfinite(t_lo) and numpy.isfinite(t_hi) and t_lo < t_hi):
+        raise MpcError(f'slice_intervals: t_range must be finite with t_lo < t_hi, got {(t_lo, t_hi)}')
+    off, ef = _slice_rows('slice_intervals', row_off, ef_rows, n, eps)
+    R = len(off) - 1
+    interval = numpy.zeros((R, 2))
+    status = numpy.zeros(R, dtype=numpy.int32)
+    ms = ctypes.c_float(0.0)
+    L = load()
+    rc = L.mpc_slice_intervals(int(device), n, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), th0.ctypes.data_as(_dp), uv.ctypes.data_as(_dp),
+                               t_lo, t_hi, float(eps), interval.ctypes.data_as(_dp), status.ctypes.data_as(_ip), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_slice_intervals failed ({rc}): {L.mpc_last_global_error().decode()}')
+    slice_intervals.last_ms = float(ms.value)
+    return interval, status
+
+
+slice_intervals.last_ms = 0.0
 
 
 def facet_centres(ef_rows: numpy.ndarray, row_off: numpy.ndarray, device: int = 0):

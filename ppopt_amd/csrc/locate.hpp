@@ -441,4 +441,240 @@ __global__ void __launch_bounds__(HR_BLOCK) k_hit_and_run(int n, long long n_pol
     status[g] = st;
 }
 
+
+// ------------------------------------------------------------------------------------------------------------------
+// k_slice_polygons: the slice of every region {theta : E theta <= f} by the plane theta = theta_c + U z (z in R^2), clipped to the box
+// |z_0| <= hx, |z_1| <= hy, as a convex polygon.  z is measured from the centre of the user's box (the host shifts theta_0 to
+// theta_c = theta_0 + U c), so that a small polygon far from the origin keeps its digits.  Rows are the stacked [f | E] rows of the
+// locator with row_off[n_regions + 1]; plane[t] = (theta_c[t], U[t][0], U[t][1]).
+//
+// Mapping: one WAVEFRONT per region, four per workgroup, so the region and the row loop bounds are wave-uniform.  Lane l
+// owns rows l, l + 64, ... of the region's m rows followed by the four box rows (m + 4 <= 260, so <= 5 per lane):
+//   1. reduce: a_i = E_i U, beta_i = f_i - E_i theta_c, normalised to |a_i| = 1 and staged in LDS.  |a_i| <= eps |E_i| |U| is a row
+//      constant on the plane: dropped if beta_i >= -eps (|f_i| + |E_i theta_c|), else the slice is empty.
+//   2. clip: the line a_i z = beta_i, z = beta_i a_i + t d_i with d_i = a_i turned +90 degrees (counter-clockwise walk for an outward
+//      normal), against every other row as a parametric interval [t_lo, t_hi].  A row parallel to row i (|a_j d_i| <= eps) empties
+//      the line if it is tighter by more than eps D (D the box diameter), and a same-direction one within eps D of it is a
+//      duplicate: the lower index keeps the edge.  Row i is an edge iff t_hi - t_lo > eps D.
+//   3. rank the edges by the angle of their outward normal (counts over LDS); edge k contributes its start point as vertex k.  The
+//      list is rotated to start at the vertex of smallest atan2 about the vertex mean; the area is the shoelace sum of every edge's
+//      own start and end about that mean (wave reductions, butterflies: every lane holds the same bits).
+// Every loop is bounded by validated inputs: n <= 64, <= 256 rows per region (mpc_slice_polygons).  No scratch (arrays of 5,
+// fully unrolled).
+constexpr int SP_BLOCK = 256, SP_WAVES = SP_BLOCK / 64, SP_MAX_ROWS = 256 + 4, SP_PER_LANE = (SP_MAX_ROWS + 63) / 64;
+
+__device__ __forceinline__ double sp_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ int sp_wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ void __launch_bounds__(SP_BLOCK) k_slice_polygons(int n, long long n_regions, const long long *__restrict__ row_off,
+                                                             const double *__restrict__ ef, const double *__restrict__ plane, double hx,
+                                                             double hy, double cx, double cy, double eps, double *__restrict__ vert,
+                                                             int32_t *__restrict__ edge_row, int32_t *__restrict__ count,
+                                                             double *__restrict__ area, int32_t *__restrict__ status) {
+    __shared__ double s_ax[SP_WAVES][SP_MAX_ROWS], s_ay[SP_WAVES][SP_MAX_ROWS], s_b[SP_WAVES][SP_MAX_ROWS], s_key[SP_WAVES][SP_MAX_ROWS];
+    __shared__ int s_flag[SP_WAVES][SP_MAX_ROWS];   // 1: active row (phase 1), then 1: edge (phase 2)
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * SP_WAVES + w;
+    const bool live = r < n_regions;   // wave-uniform; every wave reaches the barriers
+    const long long r0 = live ? row_off[r] : 0;
+    const int m = live ? (int)(row_off[r + 1] - r0) : 0, mt = live ? m + 4 : 0;
+    const double D = 2.0 * sqrt(hx * hx + hy * hy), lt = eps * D;
+    double unorm = 0.0;
+    {
+        double u0 = 0.0, u1 = 0.0;
+        for (int t = 0; t < n; ++t) { u0 += plane[3 * t + 1] * plane[3 * t + 1]; u1 += plane[3 * t + 2] * plane[3 * t + 2]; }
+        unorm = sqrt(fmax(u0, u1));
+    }
+    // 1. reduce every row to the plane
+    int violated = 0;
+#pragma unroll
+    for (int k = 0; k < SP_PER_LANE; ++k) {
+        const int i = lane + 64 * k;
+        if (i >= mt) continue;
+        double ax, ay, b;
+        int act = 1;
+        if (i < m) {
+            const double *row = ef + (r0 + i) * (long long)(n + 1);
+            const double f = row[0];
+            double dot = 0.0, ee = 0.0;
+            ax = 0.0; ay = 0.0;
+            for (int t = 0; t < n; ++t) {
+                const double e = row[1 + t];
+                ax += e * plane[3 * t + 1];
+                ay += e * plane[3 * t + 2];
+                dot += e * plane[3 * t];
+                ee += e * e;
+            }
+            b = f - dot;
+            const double nrm = sqrt(ax * ax + ay * ay);
+            if (nrm <= eps * sqrt(ee) * unorm) {
+                act = 0;
+                if (b < -eps * (fabs(f) + fabs(dot))) violated = 1;
+            } else {
+                ax /= nrm; ay /= nrm; b /= nrm;
+            }
+        } else {   // box rows -1 .. -4: z_0 <= hx, z_1 <= hy, -z_0 <= hx, -z_1 <= hy
+            const int s = i - m;
+            ax = s == 0 ? 1.0 : s == 2 ? -1.0 : 0.0;
+            ay = s == 1 ? 1.0 : s == 3 ? -1.0 : 0.0;
+            b = (s & 1) ? hy : hx;
+        }
+        s_ax[w][i] = ax; s_ay[w][i] = ay; s_b[w][i] = b; s_flag[w][i] = act;
+    }
+    __syncthreads();
+    // 2. clip the line of every active row against all others
+    double sx[SP_PER_LANE], sy[SP_PER_LANE], ex[SP_PER_LANE], ey[SP_PER_LANE];
+    int edge[SP_PER_LANE];
+    int nonempty = 0;
+#pragma unroll
+    for (int k = 0; k < SP_PER_LANE; ++k) {
+        const int i = lane + 64 * k;
+        edge[k] = 0; sx[k] = sy[k] = ex[k] = ey[k] = 0.0;
+        if (i >= mt || !s_flag[w][i]) continue;
+        const double ax = s_ax[w][i], ay = s_ay[w][i], bi = s_b[w][i];
+        const double px = bi * ax, py = bi * ay, dx = -ay, dy = ax;
+        double tlo = -INFINITY, thi = INFINITY;
+        bool dead = false;
+        for (int j = 0; j < mt; ++j) {
+            if (j == i || !s_flag[w][j]) continue;
+            const double bx = s_ax[w][j], by = s_ay[w][j];
+            const double den = bx * dx + by * dy;
+            const double num = s_b[w][j] - (bx * px + by * py);
+            if (fabs(den) <= eps) {
+                if (num < -lt) dead = true;                                                 // a tighter parallel row
+                else if (num <= lt && bx * ax + by * ay > 0.0 && j < i) dead = true;        // a duplicate with a lower index
+            } else if (den > 0.0) thi = fmin(thi, num / den);
+            else tlo = fmax(tlo, num / den);
+        }
+        if (!dead && thi - tlo >= -lt) nonempty = 1;
+        if (!dead && thi - tlo > lt) {
+            edge[k] = 1;
+            sx[k] = px + tlo * dx; sy[k] = py + tlo * dy;
+            ex[k] = px + thi * dx; ey[k] = py + thi * dy;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SP_PER_LANE; ++k) {
+        const int i = lane + 64 * k;
+        if (i >= mt) continue;
+        s_flag[w][i] = edge[k];
+        s_key[w][i] = atan2(s_ay[w][i], s_ax[w][i]);
+    }
+    __syncthreads();
+    if (!live) return;   // no barrier below
+    // 3. order, mean, area, start
+    int mine = 0;
+    double mx = 0.0, my = 0.0;
+#pragma unroll
+    for (int k = 0; k < SP_PER_LANE; ++k) if (edge[k]) { ++mine; mx += sx[k]; my += sy[k]; }
+    const int nv = sp_wave_sum(mine);
+    violated = sp_wave_sum(violated);
+    nonempty = sp_wave_sum(nonempty);
+    mx = sp_wave_sum(mx); my = sp_wave_sum(my);
+    int st;
+    if (violated || (nv == 0 && !nonempty)) st = MPC_SLICE_EMPTY;
+    else {
+        mx /= nv > 0 ? nv : 1; my /= nv > 0 ? nv : 1;
+        int rank[SP_PER_LANE];
+        double ang_min = INFINITY, a2 = 0.0;
+        int rank_min = 0, cut = 0;
+#pragma unroll
+        for (int k = 0; k < SP_PER_LANE; ++k) {
+            const int i = lane + 64 * k;
+            rank[k] = 0;
+            if (!edge[k]) continue;
+            const double key = s_key[w][i];
+            int rk = 0;
+            for (int j = 0; j < mt; ++j) rk += s_flag[w][j] && (s_key[w][j] < key || (s_key[w][j] == key && j < i));
+            rank[k] = rk;
+            const double ang = atan2(sy[k] - my, sx[k] - mx);
+            if (ang < ang_min || (ang == ang_min && rk < rank_min)) { ang_min = ang; rank_min = rk; }
+            a2 += (sx[k] - mx) * (ey[k] - my) - (sy[k] - my) * (ex[k] - mx);
+            if (i >= m) cut = 1;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double oa = __shfl_xor(ang_min, off);
+            const int orank = __shfl_xor(rank_min, off);
+            if (oa < ang_min || (oa == ang_min && orank < rank_min)) { ang_min = oa; rank_min = orank; }
+        }
+        const double ar = 0.5 * sp_wave_sum(a2);
+        cut = sp_wave_sum(cut);
+        st = (nv < 3 || ar <= eps * D * D) ? MPC_SLICE_LOWDIM : MPC_SLICE_FULL;
+        if (cut) st |= MPC_SLICE_CUT;
+        const long long vo = r0 + 4 * r;
+#pragma unroll
+        for (int k = 0; k < SP_PER_LANE; ++k) {
+            const int i = lane + 64 * k;
+            if (!edge[k]) continue;
+            const long long q = vo + (rank[k] - rank_min + nv) % nv;
+            vert[2 * q] = sx[k] + cx;
+            vert[2 * q + 1] = sy[k] + cy;
+            edge_row[q] = i < m ? i : -(i - m + 1);
+        }
+        if (lane == 0) { count[r] = nv; area[r] = ar; }
+    }
+    if (lane == 0) {
+        status[r] = st;
+        if (st == MPC_SLICE_EMPTY) { count[r] = 0; area[r] = 0.0; }
+    }
+}
+
+// k_slice_intervals: the slice of every region by the line theta = theta_0 + u t, clipped to [t_lo, t_hi]; one wavefront per region,
+// lanes over its rows, min / max by wave butterflies.  |E_i u| <= eps |E_i| |u| is a row constant on the line (as in k_slice_polygons).
+__global__ void __launch_bounds__(SP_BLOCK) k_slice_intervals(int n, long long n_regions, const long long *__restrict__ row_off,
+                                                              const double *__restrict__ ef, const double *__restrict__ line, double t_lo,
+                                                              double t_hi, double eps, double *__restrict__ interval,
+                                                              int32_t *__restrict__ status) {
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const long long r = (long long)blockIdx.x * SP_WAVES + w;
+    if (r >= n_regions) return;
+    const long long r0 = row_off[r];
+    const int m = (int)(row_off[r + 1] - r0);
+    double uu = 0.0;
+    for (int t = 0; t < n; ++t) uu += line[2 * t + 1] * line[2 * t + 1];
+    const double unorm = sqrt(uu);
+    double lo = -INFINITY, hi = INFINITY;
+    int violated = 0;
+    for (int i = lane; i < m; i += 64) {
+        const double *row = ef + (r0 + i) * (long long)(n + 1);
+        const double f = row[0];
+        double a = 0.0, dot = 0.0, ee = 0.0;
+        for (int t = 0; t < n; ++t) {
+            const double e = row[1 + t];
+            a += e * line[2 * t + 1];
+            dot += e * line[2 * t];
+            ee += e * e;
+        }
+        const double b = f - dot;
+        if (fabs(a) <= eps * sqrt(ee) * unorm) { if (b < -eps * (fabs(f) + fabs(dot))) violated = 1; }
+        else if (a > 0.0) hi = fmin(hi, b / a);
+        else lo = fmax(lo, b / a);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = fmax(lo, __shfl_xor(lo, off));
+        hi = fmin(hi, __shfl_xor(hi, off));
+        violated |= __shfl_xor(violated, off);
+    }
+    if (lane) return;
+    const double L = t_hi - t_lo, a = fmax(lo, t_lo), b = fmin(hi, t_hi);
+    int st;
+    if (violated || b - a < -eps * L) st = MPC_SLICE_EMPTY;
+    else st = (b - a <= eps * L ? MPC_SLICE_LOWDIM : MPC_SLICE_FULL) | (lo <= t_lo || hi >= t_hi ? MPC_SLICE_CUT : 0);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    interval[2 * r] = st == MPC_SLICE_EMPTY ? nan : a;
+    interval[2 * r + 1] = st == MPC_SLICE_EMPTY ? nan : fmax(a, b);
+    status[r] = st;
+}
+
 }  // namespace mpc

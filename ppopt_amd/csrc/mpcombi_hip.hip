@@ -4339,6 +4339,108 @@ extern "C" int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const 
     return MPC_OK;
 }
 
+// ---- slices of a batch of polytopes by a plane or a line (k_slice_polygons / k_slice_intervals, locate.hpp) ---------------------
+static int slice_check(const char *who, int32_t n, int64_t n_regions, const int64_t *row_off, double eps) {
+    char msg[160];
+    if (n < 1 || n > 64) { snprintf(msg, sizeof msg, "%s: n must lie in 1..64", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    if (n_regions < 0 || !row_off || row_off[0] != 0) { snprintf(msg, sizeof msg, "%s: bad n_regions or row_off", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    if (!(eps > 0.0 && eps < 1.0)) { snprintf(msg, sizeof msg, "%s: eps must lie in (0, 1)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    for (int64_t r = 0; r < n_regions; ++r) {
+        const int64_t k = row_off[r + 1] - row_off[r];
+        if (k < 0 || k > 256) { snprintf(msg, sizeof msg, "%s: a region has more than 256 rows (or row_off decreases)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    }
+    if (n_regions > 4ll * 0x7fffffffll) { snprintf(msg, sizeof msg, "%s: too many regions for one launch", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    return MPC_OK;
+}
+
+// one launch of a slice kernel with its inputs copied in and its outputs copied out; launch(d_in...) enqueues the kernel
+template <class Launch>
+static int slice_run(const char *who, int32_t device, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int32_t n,
+                     const std::vector<double> &param, std::initializer_list<std::pair<void *, size_t>> outs, float *ms, Launch launch) {
+    int ndev = 0;
+    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const long long rows = row_off[n_regions];
+    DevBuf d_off, d_ef, d_param, d_out[5];
+    const size_t n_out = outs.size();
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
+    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure(std::max<size_t>(8, (size_t)rows * (n + 1) * 8), nullptr));
+    chk(d_param.ensure(param.size() * 8, nullptr));
+    { size_t q = 0; for (auto &o : outs) chk(d_out[q++].ensure(std::max<size_t>(8, o.second), nullptr)); }
+    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
+    if (e == hipSuccess) {
+        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
+        if (rows) chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_param.p, param.data(), param.size() * 8, hipMemcpyHostToDevice));
+    }
+    if (e == hipSuccess) {
+        chk(hipEventRecord(e0, nullptr));
+        launch(dim3((unsigned)((n_regions + SP_WAVES - 1) / SP_WAVES)), d_off.as<long long>(), d_ef.as<double>(), d_param.as<double>(), d_out);
+        chk(hipGetLastError());
+        chk(hipEventRecord(e1, nullptr));
+        size_t q = 0;
+        for (auto &o : outs) { if (o.second) chk(hipMemcpy(o.first, d_out[q].p, o.second, hipMemcpyDeviceToHost)); ++q; }
+        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
+    }
+    (void)hipDeviceSynchronize();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    d_off.release(); d_ef.release(); d_param.release();
+    for (size_t q = 0; q < n_out; ++q) d_out[q].release();
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return MPC_OK;
+}
+
+extern "C" int mpc_slice_polygons(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                                  const double *U, const double *box, double eps, double *vert, int32_t *edge_row, int32_t *count, double *area,
+                                  int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (int rc = slice_check("mpc_slice_polygons", n, n_regions, row_off, eps)) return rc;
+    if (!theta0 || !U || !box) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing theta0, U or box");
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(box[k]) || !std::isfinite(box[k + 2]) || !(box[k] < box[k + 2]))
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: the box must be finite with lo < hi");
+    if (n_regions == 0) return MPC_OK;
+    const long long rows = row_off[n_regions], slots = rows + 4 * n_regions;
+    if ((rows && !ef_rows) || !vert || !edge_row || !count || !area || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing array");
+    // z is measured from the box centre c: plane[t] = (theta0 + U c, U[t][0], U[t][1])
+    const double cx = 0.5 * (box[0] + box[2]), cy = 0.5 * (box[1] + box[3]), hx = 0.5 * (box[2] - box[0]), hy = 0.5 * (box[3] - box[1]);
+    std::vector<double> plane(3 * (size_t)n);
+    for (int t = 0; t < n; ++t) {
+        plane[3 * t] = theta0[t] + U[2 * t] * cx + U[2 * t + 1] * cy;
+        plane[3 * t + 1] = U[2 * t];
+        plane[3 * t + 2] = U[2 * t + 1];
+    }
+    return slice_run("mpc_slice_polygons", device, n_regions, row_off, ef_rows, n, plane,
+                     {{vert, (size_t)slots * 16}, {edge_row, (size_t)slots * 4}, {count, (size_t)n_regions * 4}, {area, (size_t)n_regions * 8},
+                      {status, (size_t)n_regions * 4}}, ms,
+                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *o) {
+                         hipLaunchKernelGGL(k_slice_polygons, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, hx, hy, cx, cy, eps,
+                                            o[0].as<double>(), o[1].as<int32_t>(), o[2].as<int32_t>(), o[3].as<double>(), o[4].as<int32_t>());
+                     });
+}
+
+extern "C" int mpc_slice_intervals(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                                   const double *u, double t_lo, double t_hi, double eps, double *interval, int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (int rc = slice_check("mpc_slice_intervals", n, n_regions, row_off, eps)) return rc;
+    if (!theta0 || !u) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing theta0 or u");
+    if (!std::isfinite(t_lo) || !std::isfinite(t_hi) || !(t_lo < t_hi)) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: the range must be finite with t_lo < t_hi");
+    if (n_regions == 0) return MPC_OK;
+    if ((row_off[n_regions] && !ef_rows) || !interval || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing array");
+    std::vector<double> line(2 * (size_t)n);
+    for (int t = 0; t < n; ++t) { line[2 * t] = theta0[t]; line[2 * t + 1] = u[t]; }
+    return slice_run("mpc_slice_intervals", device, n_regions, row_off, ef_rows, n, line,
+                     {{interval, (size_t)n_regions * 16}, {status, (size_t)n_regions * 4}}, ms,
+                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *o) {
+                         hipLaunchKernelGGL(k_slice_intervals, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, t_lo, t_hi, eps,
+                                            o[0].as<double>(), o[1].as<int32_t>());
+                     });
+}
+
 // ---- batched LPs ------------------------------------------------------------------------------------------------
 static int lp_batch_impl(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b,
                          int32_t shared_b, const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x,

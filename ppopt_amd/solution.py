@@ -429,6 +429,102 @@ class Solution:
                            n_regions_sampled=n_sampled, n_regions_not_sampled=n_not, failing_regions=sorted(failing),
                            seconds=time.perf_counter() - t0)
 
+    # ---- slices: the polygon of every region in a plane of parameter space, the interval on a line ----------------------------
+    def _plane(self, dims, fixed, plane):
+        """(theta_0 [n_t], U [n_t, 2], dims or None) of slice_2d's arguments; ValueError for arguments that do not fit."""
+        n_t = self.theta_dim()
+        if plane is not None:
+            theta_0 = numpy.asarray(plane[0], dtype=float).reshape(-1)
+            U = numpy.asarray(plane[1], dtype=float)
+            if theta_0.shape != (n_t,) or U.shape != (n_t, 2):
+                raise ValueError(f'plane must be (theta_0 [{n_t}], U [{n_t}, 2]), got {theta_0.shape} and {U.shape}')
+            if numpy.linalg.matrix_rank(U) < 2:
+                raise ValueError('the columns of U must be linearly independent')
+            return theta_0, U, None
+        dims = tuple(int(d) for d in dims)
+        if len(dims) != 2 or dims[0] == dims[1] or not all(0 <= d < n_t for d in dims):
+            raise ValueError(f'dims must be two different parameter indices in 0..{n_t - 1}, got {dims}')
+        theta_0 = numpy.zeros(n_t)
+        others = [t for t in range(n_t) if t not in dims]
+        if isinstance(fixed, dict):
+            if sorted(int(k) for k in fixed) != others:
+                raise ValueError(f'fixed must give the parameters {others} (the ones not in dims), got {sorted(fixed)}')
+            for k, v in fixed.items():
+                theta_0[int(k)] = float(v)
+        elif fixed is not None:
+            f = numpy.asarray(fixed, dtype=float).reshape(-1)
+            if f.shape != (n_t,):
+                raise ValueError(f'fixed must be a full parameter vector of length {n_t} or a dict {{index: value}}, got length {f.size}')
+            theta_0[others] = f[others]
+        elif others:
+            raise ValueError(f'the solution has {n_t} parameters: give fixed (values of {others}) or plane=(theta_0, U)')
+        U = numpy.zeros((n_t, 2))
+        U[dims[0], 0] = U[dims[1], 1] = 1.0
+        return theta_0, U, dims
+
+    def _plane_box(self, theta_0, U, device):
+        """Bounding box (lo0, lo1, hi0, hi1) of {z : A_t (theta_0 + U z) <= b_t}: four LPs in one device batch."""
+        from . import _lib
+        P = self.program
+        A = numpy.asarray(P.A_t, dtype=float) @ U
+        b = numpy.asarray(P.b_t, dtype=float).reshape(-1) - numpy.asarray(P.A_t, dtype=float) @ theta_0
+        k = U.shape[1]
+        # bounded iff the normals of the reduced rows leave no open half-plane (half-line) free: checked here, before any launch
+        nz = A[numpy.linalg.norm(A, axis=1) > 1e-12 * numpy.max(numpy.abs(A), initial=1e-300) * numpy.sqrt(k)]
+        if k == 1:
+            bounded = numpy.any(nz > 0) and numpy.any(nz < 0)
+        else:
+            ang = numpy.sort(numpy.arctan2(nz[:, 1], nz[:, 0]))
+            bounded = len(ang) > 2 and numpy.max(numpy.diff(numpy.concatenate([ang, [ang[0] + 2 * numpy.pi]]))) < numpy.pi
+        if not bounded:
+            raise ValueError('the slice of the parameter set A_t theta <= b_t is unbounded; give box')
+        c = numpy.vstack([numpy.eye(k), -numpy.eye(k)])
+        status, x, obj, _ = _lib.lp_solve_batch(A, b, c, numpy.zeros((2 * k, len(b)), dtype=numpy.uint8), device=device)
+        if numpy.any(status == _lib.LP_INFEASIBLE):
+            raise ValueError('the slice misses the parameter set A_t theta <= b_t; give box')
+        if numpy.any(status != _lib.LP_OPTIMAL):
+            raise ValueError('the slice of the parameter set A_t theta <= b_t is unbounded; give box')
+        return numpy.concatenate([obj[:k], -obj[k:]])
+
+    def slice_2d(self, dims=(0, 1), fixed=None, plane=None, box=None, eps: Optional[float] = None, device: int = 0):
+        """The polygon of every region in a plane of parameter space (geometry.SolutionSlice; one k_slice_polygons launch).
+        The plane holds the parameters ``dims`` free and the others at ``fixed`` (a full parameter vector, or {index: value}); for two
+        parameters nothing needs to be given.  ``plane=(theta_0, U)`` gives any plane theta = theta_0 + U z instead.  ``box`` =
+        (lo0, lo1, hi0, hi1) bounds z; by default the bounding box of the parameter set's slice (four LPs), and ValueError when that is
+        unbounded.  ``eps`` is the kernel's one tolerance (_lib.SLICE_EPS)."""
+        from . import _lib
+        from .geometry.slice import slice_rows
+        theta_0, U, dims = self._plane(dims, fixed, plane)
+        box = self._plane_box(theta_0, U, device) if box is None else numpy.asarray(box, dtype=float).reshape(-1)
+        if box.shape != (4,) or not numpy.all(numpy.isfinite(box)) or not (box[0] < box[2] and box[1] < box[3]):
+            raise ValueError(f'box must be (lo0, lo1, hi0, hi1), finite, with lo < hi; got {box}')
+        ef, row_off, _ = self._stacked()
+        return slice_rows(row_off, ef, theta_0, U, box, eps=_lib.SLICE_EPS if eps is None else eps, device=device, dims=dims)
+
+    def slice_1d(self, theta_0, direction, t_range=None, eps: Optional[float] = None, device: int = 0):
+        """The interval of every region on the line theta = theta_0 + direction t (geometry.LineSlice; one k_slice_intervals launch),
+        with the laws' values x*(theta) at both ends.  ``t_range`` = (t_lo, t_hi) defaults to the line's extent in the parameter set
+        (two LPs); ValueError when that is unbounded."""
+        from . import _lib
+        from .geometry.slice import LineSlice
+        n_t = self.theta_dim()
+        th0 = numpy.asarray(theta_0, dtype=float).reshape(-1)
+        u = numpy.asarray(direction, dtype=float).reshape(-1)
+        if th0.shape != (n_t,) or u.shape != (n_t,) or not numpy.any(u):
+            raise ValueError(f'theta_0 and direction must be vectors of length {n_t}, direction nonzero')
+        if t_range is None:
+            lo, hi = self._plane_box(th0, u.reshape(-1, 1), device)
+            t_range = (float(lo), float(hi))
+        t_range = tuple(float(v) for v in t_range)
+        if len(t_range) != 2 or not (numpy.isfinite(t_range).all() and t_range[0] < t_range[1]):
+            raise ValueError(f't_range must be finite with t_lo < t_hi, got {t_range}')
+        ef, row_off, xlaw = self._stacked()
+        iv, st = _lib.slice_intervals(row_off, ef, th0, u, t_range, _lib.SLICE_EPS if eps is None else eps, device)
+        ends = [th0 + iv[:, k:k + 1] * u for k in (0, 1)]        # [R, n_t], NaN rows for empty slices
+        x = [xlaw[:, :, 0] + numpy.einsum('rij,rj->ri', xlaw[:, :, 1:], e) for e in ends]
+        return LineSlice(regions=numpy.arange(len(st)), intervals=iv, status=st, theta_0=th0, direction=u, t_range=t_range,
+                         x_start=x[0], x_end=x[1])
+
     def materialize(self) -> 'Solution':
         """Cuts every field of every region out of the per-level arrays the device returned (the regions a solve hands back are lazy
         views, ppopt_amd/region_batch.py) -- batch-wise, a few array operations per level.  Returns self."""
