@@ -533,6 +533,45 @@ int mpc_locator_query(mpc_locator *loc, int64_t m, const double *theta, double t
                       double *x, float *ms_locate);
 int mpc_locator_destroy(mpc_locator *loc);
 
+/* ---- point-location search trees over a solution's hyperplanes ------------------------------------------------- */
+/* A binary tree over unit planes s(theta) = n.theta - o whose descent gives EXACTLY the scan's answer (the flags above, any query
+ * tol_q <= the build tol).  Region j is classified through its expanded polytope P^_j = {E_i theta <= f_i + tol max(1, |E_i|)}: "+" if
+ * min s over P^_j >= -band, "-" if max s <= band, in both children otherwise (also when both hold).  An internal node keeps
+ * tau- = max over its "+"-only regions of max(0, -min s), tau+ = max over its "-"-only regions of max(0, max s), each widened by
+ * 1e-9 (1 + |o| + |theta*|_1) (theta* the optimal point of the LP that gave it); a query visits the "+" child if s >= -tau- and the
+ * "-" child if s <= tau+, and applies the scan's rule to the union of the visited leaves' lists (ascending region indices).
+ *
+ * mpc_tree_build: builds on the locator's device-resident rows and attaches the tree to the locator.
+ *   planes      n_planes x (n_t + 1): unit [n | o] (|n| = 1 within 1e-6)
+ *   cand_off, cand_plane  (may both be NULL) the planes of every region, CSR over regions (n_regions + 1 offsets): the split
+ *               candidates of a node are the planes of its regions; NULL: every plane is a candidate
+ *   tol         build tolerance (>= 0); band >= 0 (unit-normal distance); leaf_size >= 1; 1 <= max_depth <= 64
+ *   budget      device bytes allowed for the classification bitsets (2 or 3 x n_regions x ceil(n_planes / 64) x 8); <= 0: 4 GiB
+ * Limits (MPC_ERR_INVALID with a message, before any launch): n_t <= 16, <= 256 rows per region, the bitsets within the budget.
+ * stats (may be NULL): shape, work and device milliseconds per stage. */
+#define MPC_LOCATE_TREE 8   /* mpc_locator_query: descend the attached tree (MPC_ERR_INVALID without one or with tol > its tol) */
+typedef struct mpc_tree_stats {
+    int64_t n_nodes, n_leaves, depth, max_leaf, leaf_items;
+    double mean_leaf;
+    int64_t pairs, box_pairs, lps, pivots, capped, tau_lps;   /* classification pairs, decided by the box, LPs (both modes), pivots,
+                                                                 LP runs stopped at the pivot cap (reported as unbounded), tau LPs */
+    int64_t bitset_bytes;
+    double ms_classify, ms_split, ms_tau, ms_total;            /* device time of k_tree_classify<0>, of the split / partition
+                                                                 kernels, of k_tree_classify<1>; wall time of the whole build */
+} mpc_tree_stats;
+int mpc_tree_build(mpc_locator *loc, int32_t n_planes, const double *planes, const int64_t *cand_off, const int32_t *cand_plane, double tol,
+                   double band, int32_t leaf_size, int32_t max_depth, int64_t budget, mpc_tree_stats *stats);
+/* The attached tree: n_nodes nodes (node 0 the root; children have larger indices), n_items leaf entries. */
+int mpc_locator_tree_size(mpc_locator *loc, int64_t *n_nodes, int64_t *n_items, int32_t *n_planes, double *tol);
+/* node_plane[k] (-1: leaf), node_child[2k] ("+") / [2k + 1] ("-"), node_tau[2k] (tau-) / [2k + 1] (tau+), node_off[n_nodes + 1]: node
+ * k's leaf list is items[node_off[k] .. node_off[k + 1]); planes n_planes x (n_t + 1) as built */
+int mpc_locator_get_tree(mpc_locator *loc, double *planes, int32_t *node_plane, int32_t *node_child, double *node_tau, int64_t *node_off,
+                         int32_t *items);
+/* attaches a tree given as the arrays above (a tree built earlier, or read back); validated: indices in range, children after their
+ * parent, tau >= 0, leaf lists ascending */
+int mpc_locator_set_tree(mpc_locator *loc, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
+                         const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol);
+
 #ifdef __cplusplus
 }
 #endif

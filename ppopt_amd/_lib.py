@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('MPC_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libmpcombi_hip.so')   # MPC_LIB_PATH: A/B builds
 
 MPC_OK, MPC_ERR_INVALID, MPC_ERR_HIP, MPC_ERR_CAPACITY, MPC_ERR_STATE = range(5)
-MPC_LOCATE_OVERLAPPING, MPC_LOCATE_INCLUSIVE, MPC_LOCATE_WALK = 1, 2, 4   # flags of mpc_locator_query
+MPC_LOCATE_OVERLAPPING, MPC_LOCATE_INCLUSIVE, MPC_LOCATE_WALK, MPC_LOCATE_TREE = 1, 2, 4, 8   # flags of mpc_locator_query
+TREE_MAX_DIM, TREE_MAX_ROWS, TREE_MAX_DEPTH = 16, 256, 64   # limits of mpc_tree_build
 MPC_SOLVE_MANY_BASE = 128   # flag of mpc_solve_many_start
 MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, MPC_LEVEL_ONLY_BASE = 1, 4, 8, 16, 32   # flags of mpc_level_start / mpc_level_run_ex
 MPC_SOLVE_FETCH = 64   # flag of mpc_solve_start
@@ -105,6 +106,16 @@ def _share_the_hip_runtime_with_torch():
             ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
     except Exception:       # no torch, or an unusual layout: the library's own runtime is used
         pass
+
+
+class TreeStats(ctypes.Structure):
+    """mpc_tree_stats (include/mpcombi.h)"""
+    _fields_ = [(n, ctypes.c_int64) for n in ('n_nodes', 'n_leaves', 'depth', 'max_leaf', 'leaf_items')] + [('mean_leaf', ctypes.c_double)] + \
+               [(n, ctypes.c_int64) for n in ('pairs', 'box_pairs', 'lps', 'pivots', 'capped', 'tau_lps', 'bitset_bytes')] + \
+               [(n, ctypes.c_double) for n in ('ms_classify', 'ms_split', 'ms_tau', 'ms_total')]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 def load():
@@ -214,6 +225,11 @@ def load():
                                               _dp, _ip, _ip, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
         'mpc_slice_intervals': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_double,
                                                ctypes.c_double, ctypes.c_double, _dp, _ip, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_tree_build': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _dp, _lp, _ip, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int64, ctypes.POINTER(TreeStats)]),
+        'mpc_locator_tree_size': (ctypes.c_int, [ctypes.c_void_p, _lp, _lp, _ip, _dp]),
+        'mpc_locator_get_tree': (ctypes.c_int, [ctypes.c_void_p, _dp, _ip, _ip, _dp, _lp, _ip]),
+        'mpc_locator_set_tree': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _dp, ctypes.c_int64, _ip, _ip, _dp, _lp, _ip, ctypes.c_double]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -231,7 +247,8 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_frontier_get', 'mpc_pruned_clear', 'mpc_pruned_add', 'mpc_pruned_add_device',
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
-                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals']
+                    'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
+                    'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1123,8 +1140,69 @@ class Locator:
         self.has_adjacency = rc == MPC_OK
         return self.has_adjacency
 
+    def build_tree(self, planes, cand_off, cand_plane, tol: float, band: float, leaf_size: int = 1, max_depth: int = 48,
+                   budget: int = 0) -> dict:
+        """Builds a search tree on this locator's rows and attaches it (mpc_tree_build); returns its stats.  planes [H, n_t+1] unit
+        [n | o]; cand_off [n_regions+1] / cand_plane: the planes of every region (or both None).  Bad shapes raise MpcError before
+        any launch; the library's own limits (rows per region, the bitset budget) raise MpcError with its message."""
+        pl = _f64(numpy.asarray(planes, dtype=numpy.float64)).reshape(-1, self.n_t + 1)
+        if self.n_t > TREE_MAX_DIM:
+            raise MpcError(f'build_tree: n_theta = {self.n_t} > {TREE_MAX_DIM}')
+        if not 1 <= int(max_depth) <= TREE_MAX_DEPTH or int(leaf_size) < 1:
+            raise MpcError(f'build_tree: max_depth must lie in 1..{TREE_MAX_DEPTH} and leaf_size >= 1')
+        if (cand_off is None) != (cand_plane is None):
+            raise MpcError('build_tree: cand_off and cand_plane go together')
+        co = cp = None
+        if cand_off is not None:
+            co = numpy.ascontiguousarray(cand_off, dtype=numpy.int64).reshape(-1)
+            cp = numpy.ascontiguousarray(cand_plane, dtype=numpy.int32).reshape(-1)
+            if len(co) != self.n_regions + 1 or co[0] != 0 or co[-1] != len(cp) or numpy.any(numpy.diff(co) < 0):
+                raise MpcError('build_tree: cand_off must hold n_regions + 1 non-decreasing offsets into cand_plane')
+            if len(cp) and (cp.min() < 0 or cp.max() >= len(pl)):
+                raise MpcError('build_tree: a candidate plane is out of range')
+        st = TreeStats()
+        rc = self._L.mpc_tree_build(self._h, len(pl), pl.ctypes.data_as(_dp), None if co is None else co.ctypes.data_as(_lp),
+                                    None if cp is None else cp.ctypes.data_as(_ip), float(tol), float(band), int(leaf_size), int(max_depth),
+                                    int(budget), ctypes.byref(st))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_tree_build failed ({rc}): {self._L.mpc_last_global_error().decode()}')
+        return st.as_dict()
+
+    def get_tree(self) -> dict:
+        """The attached tree's arrays (mpc_locator_get_tree)."""
+        n_nodes, n_items, n_planes, tol = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32(), ctypes.c_double()
+        rc = self._L.mpc_locator_tree_size(self._h, ctypes.byref(n_nodes), ctypes.byref(n_items), ctypes.byref(n_planes), ctypes.byref(tol))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_locator_tree_size failed ({rc}): {self._L.mpc_last_global_error().decode()}')
+        N, K, H = n_nodes.value, n_items.value, n_planes.value
+        t = {'planes': numpy.zeros((H, self.n_t + 1)), 'node_plane': numpy.zeros(N, dtype=numpy.int32),
+             'node_child': numpy.zeros((N, 2), dtype=numpy.int32), 'node_tau': numpy.zeros((N, 2)),
+             'node_off': numpy.zeros(N + 1, dtype=numpy.int64), 'items': numpy.zeros(K, dtype=numpy.int32), 'tol': tol.value}
+        rc = self._L.mpc_locator_get_tree(self._h, t['planes'].ctypes.data_as(_dp), t['node_plane'].ctypes.data_as(_ip),
+                                          t['node_child'].ctypes.data_as(_ip), t['node_tau'].ctypes.data_as(_dp),
+                                          t['node_off'].ctypes.data_as(_lp), t['items'].ctypes.data_as(_ip))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_locator_get_tree failed ({rc}): {self._L.mpc_last_global_error().decode()}')
+        return t
+
+    def set_tree(self, planes, node_plane, node_child, node_tau, node_off, items, tol: float) -> None:
+        """Attaches a tree given as arrays (mpc_locator_set_tree); shapes are checked here, contents by the library."""
+        pl = _f64(numpy.asarray(planes, dtype=numpy.float64)).reshape(-1, self.n_t + 1)
+        npl = numpy.ascontiguousarray(node_plane, dtype=numpy.int32).reshape(-1)
+        N = len(npl)
+        ch = numpy.ascontiguousarray(node_child, dtype=numpy.int32).reshape(-1)
+        tau = _f64(numpy.asarray(node_tau, dtype=numpy.float64)).reshape(-1)
+        off = numpy.ascontiguousarray(node_off, dtype=numpy.int64).reshape(-1)
+        it = numpy.ascontiguousarray(items, dtype=numpy.int32).reshape(-1)
+        if N < 1 or ch.shape != (2 * N,) or tau.shape != (2 * N,) or off.shape != (N + 1,) or off[-1] != len(it):
+            raise MpcError('set_tree: node arrays of inconsistent shapes')
+        rc = self._L.mpc_locator_set_tree(self._h, len(pl), pl.ctypes.data_as(_dp), N, npl.ctypes.data_as(_ip), ch.ctypes.data_as(_ip),
+                                          tau.ctypes.data_as(_dp), off.ctypes.data_as(_lp), it.ctypes.data_as(_ip), float(tol))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_locator_set_tree failed ({rc}): {self._L.mpc_last_global_error().decode()}')
+
     def query(self, theta: numpy.ndarray, tol: float = 1e-5, overlapping: bool = False, want_x: bool = True,
-              inclusive: bool = False, walk: bool = False):
+              inclusive: bool = False, walk: bool = False, tree: bool = False):
         """theta [m, n_t] -> (region index [m] (-1: none), x [m, n_x] or None).  ``inclusive``: membership is
         ``E theta <= f + tol`` (MPC_LOCATE_INCLUSIVE) instead of the strict ``E theta - f < tol``."""
         th = _f64(theta).reshape(-1, self.n_t)
@@ -1134,7 +1212,7 @@ class Locator:
         ms = ctypes.c_float(0.0)
         rc = self._L.mpc_locator_query(self._h, m, th.ctypes.data_as(_dp), float(tol),
                                        (MPC_LOCATE_OVERLAPPING if overlapping else 0) | (MPC_LOCATE_INCLUSIVE if inclusive else 0)
-                                       | (MPC_LOCATE_WALK if walk and self.has_adjacency else 0),
+                                       | (MPC_LOCATE_WALK if walk and self.has_adjacency else 0) | (MPC_LOCATE_TREE if tree else 0),
                                        region.ctypes.data_as(_lp), None if x is None else x.ctypes.data_as(_dp), ctypes.byref(ms))
         if rc != MPC_OK:
             raise MpcError(f'mpc_locator_query failed ({rc}): {self._L.mpc_last_global_error().decode()}')

@@ -13,6 +13,54 @@
 
 namespace mpc {
 
+// The scan's membership test of one row [f | E] and its objective of a region's law; shared with k_locate_tree (tree.hpp), so that both
+// locators form the same numbers with the same operations.
+//   inclusive: E theta <= f + tol with the product formed first and then compared, like `A @ theta <= b` of the reference's
+//   PointLocation (upop/point_location.py:46,59): a point exactly on a facet belongs to the region;  strict: E theta - f < tol.
+template <int NT>
+__device__ __forceinline__ bool loc_row_inside(const double *row, const double (&th)[NT], int nt, double tol, int inclusive) {
+    if (inclusive) {
+        double v = 0.0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) if (t < nt) v = fma(row[1 + t], th[t], v);
+        return v <= row[0] + tol;
+    }
+    double v = -row[0];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) if (t < nt) v = fma(row[1 + t], th[t], v);
+    return v < tol;
+}
+
+// objective 1/2 x'Qx + theta'H'x + c'x at x = A theta + b (terms without x are the same for every region); xl = [b | A] of the region
+template <int NT>
+__device__ __forceinline__ double loc_objective(const double *xl, int nx, int nt, const double (&th)[NT], const double *cvec, const double *H,
+                                                const double *Q) {
+    const int nr = nt + 1;
+    double obj = 0.0;
+    for (int a = 0; a < nx; ++a) {
+        double xa = xl[a * nr];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) if (t < nt) xa = fma(xl[a * nr + 1 + t], th[t], xa);
+        double g = cvec ? cvec[a] : 0.0;
+        if (H) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) if (t < nt) g = fma(H[a * nt + t], th[t], g);
+        }
+        if (Q) {
+            double qx = 0.0;
+            for (int j = 0; j < nx; ++j) {
+                double xj = xl[j * nr];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) if (t < nt) xj = fma(xl[j * nr + 1 + t], th[t], xj);
+                qx = fma(Q[a * nx + j], xj, qx);
+            }
+            g = fma(0.5, qx, g);
+        }
+        obj = fma(g, xa, obj);
+    }
+    return obj;
+}
+
 // Rows are staged through LDS in tiles of LOC_TILE rows, loaded cooperatively (coalesced) by the 256 points of a block;
 // with each row come the region it belongs to and the index of the first row of the next region, so that a wavefront
 // which has no lane left inside a region jumps over the rest of its rows.
@@ -40,30 +88,7 @@ __global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, lon
     auto commit = [&]() {
         if (cur < 0 || !inside) return;
         if (!overlapping) { found = cur; alive = false; return; }
-        // objective 1/2 x'Qx + theta'H'x + c'x at x = A theta + b (terms without x are the same for every region)
-        const double *xl = xlaw + (size_t)cur * nx * nr;
-        double obj = 0.0;
-        for (int a = 0; a < nx; ++a) {
-            double xa = xl[a * nr];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) if (t < nt) xa = fma(xl[a * nr + 1 + t], th[t], xa);
-            double g = cvec ? cvec[a] : 0.0;
-            if (H) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) if (t < nt) g = fma(H[a * nt + t], th[t], g);
-            }
-            if (Q) {
-                double qx = 0.0;
-                for (int j = 0; j < nx; ++j) {
-                    double xj = xl[j * nr];
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) if (t < nt) xj = fma(xl[j * nr + 1 + t], th[t], xj);
-                    qx = fma(Q[a * nx + j], xj, qx);
-                }
-                g = fma(0.5, qx, g);
-            }
-            obj = fma(g, xa, obj);
-        }
+        const double obj = loc_objective<NT>(xlaw + (size_t)cur * nx * nr, nx, nt, th, cvec, H, Q);
         if (obj <= best) { best = obj; found = cur; }
     };
     for (long long tile0 = 0; tile0 < n_rows; tile0 += LOC_TILE) {
@@ -88,19 +113,7 @@ __global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, lon
                 inside = overlapping ? (p < m) : alive;
                 if (!overlapping && !__any(alive)) { i = n_rows; break; }   // every lane has its region
             }
-            if (inclusive) {
-                // E theta <= f + tol with the product formed first and then compared, like `A @ theta <= b` of the reference's
-                // PointLocation (upop/point_location.py:46,59): a point exactly on a facet belongs to the region
-                double v = 0.0;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) v = fma(tile[li][1 + t], th[t], v);
-                inside = inside && (v <= tile[li][0] + tol);
-            } else {
-                double v = -tile[li][0];
-#pragma unroll
-                for (int t = 0; t < NT; ++t) v = fma(tile[li][1 + t], th[t], v);
-                inside = inside && (v < tol);
-            }
+            inside = inside && loc_row_inside<NT>(tile[li], th, NT, tol, inclusive);   // tile rows are zero past nt
             if (!__any(inside)) { i = tend[li]; continue; }   // nobody is left in this region: on to the next one
             ++i;
         }

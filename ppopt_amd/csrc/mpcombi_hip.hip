@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "kernels2.hpp"
 #include "locate.hpp"
+#include "tree.hpp"
 #include "graph.hpp"
 #include "qp.hpp"
 #include <memory>
@@ -4678,6 +4679,15 @@ struct mpc_locator {
     bool has_adj = false;
     long long last_unresolved = 0;   // points of the last walk query that went to the list scan
     bool hasQ = false, hasc = false, hasH = false;
+    std::vector<int64_t> h_row_off;  // host copy of row_off (limits of mpc_tree_build)
+    // search tree (mpc_tree_build / mpc_locator_set_tree): host arrays as attached, and their device copies
+    bool has_tree = false;
+    double tree_tol = 0.0;
+    int tree_planes = 0;
+    std::vector<double> h_planes, h_tau;
+    std::vector<int32_t> h_plane, h_child, h_items;
+    std::vector<int64_t> h_off;
+    DevBuf t_planes, t_plane, t_child, t_tau, t_off, t_items;
 };
 
 static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xlaw, const double *Q,
@@ -4705,6 +4715,8 @@ static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_of
     HIP_TRY(nullptr, hipEventCreate(&L->e1));
     const long long rows = n_regions ? row_off[n_regions] : 0;
     L->n_rows = rows;
+    L->h_row_off.assign(row_off, row_off + (n_regions ? n_regions + 1 : 0));
+    if (!n_regions) L->h_row_off.assign(1, 0);
     auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
         hipError_t e = b.ensure(std::max<size_t>(bytes, 8), L->stream);
         if (e != hipSuccess || !bytes) return e;
@@ -4767,6 +4779,9 @@ extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta,
                                  float *ms_locate) {
     if (!L || m < 0 || (m > 0 && (!theta || !region))) return MPC_ERR_INVALID;
     if (ms_locate) *ms_locate = 0.0f;
+    const bool tree = (flags & MPC_LOCATE_TREE) != 0;
+    if (tree && !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: MPC_LOCATE_TREE without an attached tree");
+    if (tree && !(tol <= L->tree_tol)) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: tol is larger than the tolerance the tree was built for");
     if (m == 0) return MPC_OK;
     HIP_TRY(nullptr, hipSetDevice(L->device));
     hipStream_t st = L->stream;
@@ -4782,7 +4797,37 @@ extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta,
                                            (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), OUT_)
 #define MPC_LOCATE_ANY(M_, TH_, OUT_) do { if (nt <= 4) MPC_LOCATE(4, M_, TH_, OUT_); else if (nt <= 8) MPC_LOCATE(8, M_, TH_, OUT_); else MPC_LOCATE(16, M_, TH_, OUT_); } while (0)
     const bool walk = (flags & MPC_LOCATE_WALK) && L->has_adj && !(flags & (MPC_LOCATE_OVERLAPPING | MPC_LOCATE_INCLUSIVE)) && L->n_regions > 0 && nt <= 16;
-    if (!walk) {
+    if (tree) {
+        // descent of the attached tree; points whose band stack overflowed (-2) go to the list scan
+#define MPC_TREE(NT_) hipLaunchKernelGGL((k_locate_tree<NT_>), g, b, 0, st, (long long)m, nt, nx, L->t_planes.as<double>(), L->t_plane.as<int32_t>(), \
+                                         L->t_child.as<int32_t>(), L->t_tau.as<double>(), L->t_off.as<long long>(), L->t_items.as<int32_t>(), \
+                                         L->row_off.as<long long>(), L->ef.as<double>(), L->xlaw.as<double>(), Q, c, H, L->theta.as<double>(), tol, \
+                                         (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), L->region.as<long long>())
+        if (nt <= 4) MPC_TREE(4); else if (nt <= 8) MPC_TREE(8); else MPC_TREE(16);
+#undef MPC_TREE
+        HIP_TRY(nullptr, hipGetLastError());
+        HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(nullptr, hipStreamSynchronize(st));
+        std::vector<long long> open;
+        for (long long p = 0; p < m; ++p) if (region[p] == -2) open.push_back(p);
+        if (!open.empty()) {
+            const long long mo = (long long)open.size();
+            std::vector<double> tho((size_t)mo * nt);
+            for (long long i = 0; i < mo; ++i) std::memcpy(&tho[(size_t)i * nt], theta + (size_t)open[(size_t)i] * nt, sizeof(double) * nt);
+            std::vector<long long> ro((size_t)mo);
+            HIP_TRY(nullptr, L->theta2.ensure((size_t)mo * nt * sizeof(double), st));
+            HIP_TRY(nullptr, L->region2.ensure((size_t)mo * sizeof(long long), st));
+            HIP_TRY(nullptr, hipMemcpyAsync(L->theta2.p, tho.data(), (size_t)mo * nt * sizeof(double), hipMemcpyHostToDevice, st));
+            MPC_LOCATE_ANY(mo, L->theta2.as<double>(), L->region2.as<long long>());
+            HIP_TRY(nullptr, hipGetLastError());
+            HIP_TRY(nullptr, hipMemcpyAsync(ro.data(), L->region2.p, (size_t)mo * sizeof(long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(nullptr, hipStreamSynchronize(st));
+            for (long long i = 0; i < mo; ++i) region[open[(size_t)i]] = ro[(size_t)i];
+            HIP_TRY(nullptr, hipMemcpyAsync(L->region.p, region, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, st));   // k_evaluate reads it
+        }
+        L->last_unresolved = (long long)open.size();
+        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
+    } else if (!walk) {
         MPC_LOCATE_ANY(m, L->theta.as<double>(), L->region.as<long long>());
         HIP_TRY(nullptr, hipGetLastError());
         HIP_TRY(nullptr, hipEventRecord(L->e1, st));
@@ -4843,12 +4888,323 @@ extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta,
     return MPC_OK;
 }
 
+// ---- search trees (tree.hpp) ------------------------------------------------------------------------------------
+constexpr long long TREE_DEFAULT_BUDGET = 4ll << 30, TREE_MAX_LEVEL_ITEMS = 1ll << 28;
+
+static int tree_attach(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane, const int32_t *node_child,
+                       const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
+    const int nr = L->n_t + 1;
+    const int64_t n_items = node_off[n_nodes];
+    L->has_tree = false;
+    L->h_planes.assign(planes, planes + (size_t)n_planes * nr);
+    L->h_plane.assign(node_plane, node_plane + n_nodes);
+    L->h_child.assign(node_child, node_child + 2 * n_nodes);
+    L->h_tau.assign(node_tau, node_tau + 2 * n_nodes);
+    L->h_off.assign(node_off, node_off + n_nodes + 1);
+    L->h_items.assign(items, items + n_items);
+    hipStream_t st = L->stream;
+    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), st);
+        if (e != hipSuccess || !bytes) return e;
+        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    HIP_TRY(nullptr, up(L->t_planes, L->h_planes.data(), L->h_planes.size() * 8));
+    HIP_TRY(nullptr, up(L->t_plane, L->h_plane.data(), L->h_plane.size() * 4));
+    HIP_TRY(nullptr, up(L->t_child, L->h_child.data(), L->h_child.size() * 4));
+    HIP_TRY(nullptr, up(L->t_tau, L->h_tau.data(), L->h_tau.size() * 8));
+    HIP_TRY(nullptr, up(L->t_off, L->h_off.data(), L->h_off.size() * 8));
+    HIP_TRY(nullptr, up(L->t_items, L->h_items.data(), L->h_items.size() * 4));
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    L->tree_planes = n_planes;
+    L->tree_tol = tol;
+    L->has_tree = true;
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_set_tree(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
+                                    const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
+    const char *who = "mpc_locator_set_tree";
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (!L) return bad("no locator");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
+    if (n_nodes < 1 || !node_plane || !node_child || !node_tau || !node_off) return bad("missing node arrays");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (node_off[0] != 0) return bad("node_off[0] must be 0");
+    const int nr = L->n_t + 1;
+    for (int64_t i = 0; i < (int64_t)n_planes * nr; ++i) if (!std::isfinite(planes[i])) return bad("planes must be finite");
+    for (int64_t k = 0; k < n_nodes; ++k) {
+        if (node_off[k + 1] < node_off[k]) return bad("node_off decreases");
+        const int32_t h = node_plane[k];
+        if (h < -1 || h >= n_planes) return bad("a node plane is out of range");
+        if (h >= 0) {
+            for (int q = 0; q < 2; ++q) {
+                const int32_t ch = node_child[2 * k + q];
+                if (ch <= k || ch >= n_nodes) return bad("a child index is not after its parent or out of range");
+                if (!(node_tau[2 * k + q] >= 0.0)) return bad("tau must be >= 0");
+            }
+        }
+    }
+    if (node_off[n_nodes] > 0 && !items) return bad("missing items");
+    for (int64_t k = 0; k < n_nodes; ++k)
+        for (int64_t i = node_off[k]; i < node_off[k + 1]; ++i) {
+            if (items[i] < 0 || items[i] >= L->n_regions) return bad("a leaf item is not a region index");
+            if (i > node_off[k] && items[i] < items[i - 1]) return bad("a leaf list is not ascending");
+        }
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    return tree_attach(L, n_planes, planes, n_nodes, node_plane, node_child, node_tau, node_off, items, tol);
+}
+
+extern "C" int mpc_locator_tree_size(mpc_locator *L, int64_t *n_nodes, int64_t *n_items, int32_t *n_planes, double *tol) {
+    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_tree_size: no tree attached");
+    if (n_nodes) *n_nodes = (int64_t)L->h_plane.size();
+    if (n_items) *n_items = (int64_t)L->h_items.size();
+    if (n_planes) *n_planes = L->tree_planes;
+    if (tol) *tol = L->tree_tol;
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_get_tree(mpc_locator *L, double *planes, int32_t *node_plane, int32_t *node_child, double *node_tau, int64_t *node_off,
+                                    int32_t *items) {
+    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_get_tree: no tree attached");
+    auto put = [](void *dst, const auto &v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    put(planes, L->h_planes); put(node_plane, L->h_plane); put(node_child, L->h_child); put(node_tau, L->h_tau); put(node_off, L->h_off);
+    put(items, L->h_items);
+    return MPC_OK;
+}
+
+extern "C" int mpc_tree_build(mpc_locator *L, int32_t n_planes, const double *planes, const int64_t *cand_off, const int32_t *cand_plane, double tol,
+                              double band, int32_t leaf_size, int32_t max_depth, int64_t budget, mpc_tree_stats *stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const char *who = "mpc_tree_build";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!L) return bad("no locator");
+    const int nt = L->n_t, nr = nt + 1;
+    const long long R = L->n_regions;
+    if (nt < 1 || nt > TR_MAX_NT) return bad("n_t must lie in 1..16");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (!std::isfinite(band) || band < 0.0) return bad("band must be finite and >= 0");
+    if (leaf_size < 1) return bad("leaf_size must be >= 1");
+    if (max_depth < 1 || max_depth > 64) return bad("max_depth must lie in 1..64");
+    if ((cand_off == nullptr) != (cand_plane == nullptr)) return bad("cand_off and cand_plane go together");
+    int m_max = 0;
+    for (long long r = 0; r < R; ++r) {
+        const long long k = L->h_row_off[(size_t)r + 1] - L->h_row_off[(size_t)r];
+        if (k > TR_MAX_ROWS) return bad("a region has more than 256 rows");
+        m_max = std::max<int>(m_max, (int)k);
+    }
+    for (int h = 0; h < n_planes; ++h) {
+        double nn = 0.0;
+        for (int t = 0; t < nt; ++t) nn += planes[(size_t)h * nr + t] * planes[(size_t)h * nr + t];
+        if (!std::isfinite(planes[(size_t)h * nr + nt]) || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("planes must be finite with unit normals");
+    }
+    if (cand_off) {
+        if (cand_off[0] != 0) return bad("cand_off[0] must be 0");
+        for (long long r = 0; r < R; ++r) if (cand_off[r + 1] < cand_off[r]) return bad("cand_off decreases");
+        for (long long i = 0; i < cand_off[R]; ++i) if (cand_plane[i] < 0 || cand_plane[i] >= n_planes) return bad("a candidate plane is out of range");
+    }
+    const int hw = (n_planes + 63) / 64;
+    const long long limit = budget > 0 ? budget : TREE_DEFAULT_BUDGET;
+    const long long bitset_bytes = (cand_off ? 3 : 2) * (long long)R * hw * 8;
+    if (bitset_bytes > limit) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "the classification bitsets need %lld bytes, over the budget of %lld bytes", bitset_bytes, limit);
+        return bad(msg);
+    }
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    hipStream_t st = L->stream;
+    DevBuf d_planes, d_plus, d_minus, d_owner, d_xs, d_empty, d_cnt, d_items, d_off, d_part, d_iplane, d_side, d_pairs, d_nplane, d_tau, d_er, d_ep;
+    DevBuf *all[] = {&d_planes, &d_plus, &d_minus, &d_owner, &d_xs, &d_empty, &d_cnt, &d_items, &d_off, &d_part, &d_iplane, &d_side, &d_pairs,
+                     &d_nplane, &d_tau, &d_er, &d_ep};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Cleanup {
+        hipStream_t st; DevBuf **b; size_t n; hipEvent_t *ev;
+        ~Cleanup() { (void)hipStreamSynchronize(st); for (size_t i = 0; i < n; ++i) b[i]->release(); for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
+    } cleanup{st, all, sizeof all / sizeof all[0], ev};
+    HIP_TRY(nullptr, hipEventCreate(&ev[0]));
+    HIP_TRY(nullptr, hipEventCreate(&ev[1]));
+    float ms_classify = 0.0f, ms_split = 0.0f, ms_tau = 0.0f;
+    auto timed = [&](float &acc, auto &&launch) -> hipError_t {
+        hipError_t e = hipEventRecord(ev[0], st);
+        if (e != hipSuccess) return e;
+        launch();
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
+        if ((e = hipEventSynchronize(ev[1])) != hipSuccess) return e;
+        float ms = 0.0f;
+        if ((e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess) return e;
+        acc += ms;
+        return hipSuccess;
+    };
+    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
+        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), st);
+        if (e != hipSuccess || !bytes) return e;
+        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
+    };
+    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(nullptr, up(d_cnt, cnt, sizeof cnt));
+    TreeClassifyArgs a{};
+    a.nt = nt; a.m_max = std::max(m_max, 1); a.n_planes = n_planes; a.hw = hw; a.n_regions = R;
+    a.row_off = L->row_off.as<long long>(); a.ef = L->ef.as<double>(); a.tol = tol; a.band = band;
+    a.counters = d_cnt.as<unsigned long long>();
+    const size_t lds = tr_lds_bytes(a.m_max, nt);
+    if (R > 0 && n_planes > 0) {
+        HIP_TRY(nullptr, up(d_planes, planes, (size_t)n_planes * nr * 8));
+        const size_t bits = (size_t)R * hw * 8;
+        HIP_TRY(nullptr, d_plus.ensure(bits, st)); HIP_TRY(nullptr, d_minus.ensure(bits, st));
+        HIP_TRY(nullptr, hipMemsetAsync(d_plus.p, 0, bits, st)); HIP_TRY(nullptr, hipMemsetAsync(d_minus.p, 0, bits, st));
+        HIP_TRY(nullptr, d_xs.ensure((size_t)R * nt * 8, st)); HIP_TRY(nullptr, d_empty.ensure((size_t)R * 4, st));
+        if (cand_off && cand_off[R] > 0) {
+            HIP_TRY(nullptr, d_owner.ensure(bits, st));
+            HIP_TRY(nullptr, hipMemsetAsync(d_owner.p, 0, bits, st));
+            std::vector<int32_t> er((size_t)cand_off[R]);
+            for (long long r = 0; r < R; ++r) for (long long i = cand_off[r]; i < cand_off[r + 1]; ++i) er[(size_t)i] = (int32_t)r;
+            HIP_TRY(nullptr, up(d_er, er.data(), er.size() * 4));
+            HIP_TRY(nullptr, up(d_ep, cand_plane, er.size() * 4));
+            const long long ne = cand_off[R];
+            hipLaunchKernelGGL(k_tree_owner, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, ne, hw, d_er.as<int32_t>(), d_ep.as<int32_t>(),
+                               d_owner.as<unsigned long long>());
+            HIP_TRY(nullptr, hipGetLastError());
+        }
+        a.planes = d_planes.as<double>(); a.plus = d_plus.as<unsigned long long>(); a.minus = d_minus.as<unsigned long long>();
+        a.xs = d_xs.as<double>(); a.empty = d_empty.as<int32_t>();
+        HIP_TRY(nullptr, timed(ms_classify, [&] { hipLaunchKernelGGL((k_tree_classify<0>), dim3((unsigned)R), dim3(64), lds, st, a); }));
+    }
+    const unsigned long long *owner = (cand_off && cand_off[R] > 0) ? d_owner.as<unsigned long long>() : nullptr;
+    // the level loop: host node records, device counts
+    struct Node { int32_t plane = -1, child[2] = {-1, -1}; double tau[2] = {0.0, 0.0}; int depth = 0; std::vector<int32_t> list; };
+    std::vector<Node> nodes(1);
+    nodes[0].list.resize((size_t)R);
+    for (long long r = 0; r < R; ++r) nodes[0].list[(size_t)r] = (int32_t)r;
+    std::vector<int> level{0};
+    long long tau_lps = 0;
+    while (!level.empty() && n_planes > 0) {
+        std::vector<int> work;
+        for (int k : level) if ((long long)nodes[k].list.size() > leaf_size && nodes[k].depth < max_depth) work.push_back(k);
+        if (work.empty()) break;
+        std::vector<long long> off(work.size() + 1, 0);
+        for (size_t w = 0; w < work.size(); ++w) off[w + 1] = off[w] + (long long)nodes[work[w]].list.size();
+        if (off.back() > TREE_MAX_LEVEL_ITEMS) return fail(nullptr, MPC_ERR_CAPACITY, "mpc_tree_build: a level holds more than 2^28 (node, region) entries");
+        std::vector<int32_t> items((size_t)off.back());
+        for (size_t w = 0; w < work.size(); ++w) std::copy(nodes[work[w]].list.begin(), nodes[work[w]].list.end(), items.begin() + off[w]);
+        HIP_TRY(nullptr, up(d_items, items.data(), items.size() * 4));
+        HIP_TRY(nullptr, up(d_off, off.data(), off.size() * 8));
+        const long long nw = (long long)work.size();
+        const long long target_chunks = std::max<long long>(1, 4096 / nw);
+        const int chunk_len = (int)std::max<long long>(TS_BLOCK, (((n_planes + target_chunks - 1) / target_chunks) + TS_BLOCK - 1) / TS_BLOCK * TS_BLOCK);
+        const int chunks = (n_planes + chunk_len - 1) / chunk_len;
+        HIP_TRY(nullptr, d_part.ensure((size_t)nw * chunks * sizeof(int4), st));
+        HIP_TRY(nullptr, timed(ms_split, [&] {
+            hipLaunchKernelGGL(k_tree_split, dim3((unsigned)nw, (unsigned)chunks), dim3(TS_BLOCK), 0, st, n_planes, hw, chunk_len, d_off.as<long long>(),
+                               d_items.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(), owner, d_part.as<int4>());
+        }));
+        std::vector<int4> part((size_t)nw * chunks);
+        HIP_TRY(nullptr, hipMemcpy(part.data(), d_part.p, part.size() * sizeof(int4), hipMemcpyDeviceToHost));
+        std::vector<int32_t> item_plane(items.size(), 0);
+        std::vector<int> inner;
+        for (long long w = 0; w < nw; ++w) {
+            int bmx = TS_NONE, bn0 = TS_NONE, bh = -1;
+            for (int c = 0; c < chunks; ++c) {
+                const int4 q = part[(size_t)(w * chunks + c)];
+                if (q.z < 0) continue;
+                if (bh < 0 || q.x < bmx || (q.x == bmx && (q.y < bn0 || (q.y == bn0 && q.z < bh)))) { bmx = q.x; bn0 = q.y; bh = q.z; }
+            }
+            Node &nd = nodes[work[(size_t)w]];
+            if (bh < 0 || bmx >= (int)nd.list.size()) continue;   // no plane makes progress: a leaf
+            nd.plane = bh;
+            inner.push_back((int)w);
+            std::fill(item_plane.begin() + off[w], item_plane.begin() + off[w + 1], bh);
+        }
+        if (inner.empty()) break;
+        HIP_TRY(nullptr, up(d_iplane, item_plane.data(), item_plane.size() * 4));
+        HIP_TRY(nullptr, d_side.ensure(items.size(), st));
+        HIP_TRY(nullptr, timed(ms_split, [&] {
+            hipLaunchKernelGGL(k_tree_partition, dim3((unsigned)((items.size() + 255) / 256)), dim3(256), 0, st, (long long)items.size(), hw,
+                               d_items.as<int32_t>(), d_iplane.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(),
+                               d_side.as<int8_t>());
+        }));
+        std::vector<int8_t> side(items.size());
+        HIP_TRY(nullptr, hipMemcpy(side.data(), d_side.p, side.size(), hipMemcpyDeviceToHost));
+        // children and the one-sided (node, region) pairs of tau
+        std::vector<int32_t> pairs, nplane;
+        std::vector<int> next;
+        for (size_t q = 0; q < inner.size(); ++q) {
+            const long long w = inner[q];
+            const int k = work[(size_t)w];
+            Node cp, cm;
+            cp.depth = cm.depth = nodes[k].depth + 1;
+            for (long long i = off[w]; i < off[w + 1]; ++i) {
+                const int32_t j = items[(size_t)i];
+                const int sd = side[(size_t)i];
+                if (sd != 2) cp.list.push_back(j);
+                if (sd != 1) cm.list.push_back(j);
+                if (sd) { pairs.push_back((int32_t)q); pairs.push_back(j); pairs.push_back(sd - 1); }
+            }
+            nplane.push_back(nodes[k].plane);
+            const int ip = (int)nodes.size();
+            nodes[k].child[0] = ip; nodes[k].child[1] = ip + 1;
+            nodes[k].list.clear(); nodes[k].list.shrink_to_fit();
+            nodes.push_back(std::move(cp)); nodes.push_back(std::move(cm));
+            next.push_back(ip); next.push_back(ip + 1);
+        }
+        const long long n_pairs = (long long)pairs.size() / 3;
+        std::vector<unsigned long long> tau(2 * inner.size(), 0ull);
+        if (n_pairs > 0) {
+            HIP_TRY(nullptr, up(d_pairs, pairs.data(), pairs.size() * 4));
+            HIP_TRY(nullptr, up(d_nplane, nplane.data(), nplane.size() * 4));
+            HIP_TRY(nullptr, up(d_tau, tau.data(), tau.size() * 8));
+            TreeClassifyArgs b = a;
+            b.n_pairs = n_pairs; b.pair = d_pairs.as<int32_t>(); b.node_plane = d_nplane.as<int32_t>(); b.tau = d_tau.as<unsigned long long>();
+            HIP_TRY(nullptr, timed(ms_tau, [&] { hipLaunchKernelGGL((k_tree_classify<1>), dim3((unsigned)n_pairs), dim3(64), lds, st, b); }));
+            HIP_TRY(nullptr, hipMemcpy(tau.data(), d_tau.p, tau.size() * 8, hipMemcpyDeviceToHost));
+            tau_lps += n_pairs;
+        }
+        for (size_t q = 0; q < inner.size(); ++q) {
+            Node &nd = nodes[work[(size_t)inner[q]]];
+            for (int sd = 0; sd < 2; ++sd) { double v; std::memcpy(&v, &tau[2 * q + sd], 8); nd.tau[sd] = v; }
+        }
+        level.swap(next);
+    }
+    HIP_TRY(nullptr, hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+    // flatten
+    const int64_t N = (int64_t)nodes.size();
+    std::vector<int32_t> plane_v((size_t)N), child_v((size_t)(2 * N)), items_v;
+    std::vector<double> tau_v((size_t)(2 * N));
+    std::vector<int64_t> off_v((size_t)N + 1, 0);
+    int64_t n_leaves = 0, max_leaf = 0, depth = 0;
+    for (int64_t k = 0; k < N; ++k) {
+        const Node &nd = nodes[(size_t)k];
+        plane_v[(size_t)k] = nd.plane;
+        for (int q = 0; q < 2; ++q) { child_v[(size_t)(2 * k + q)] = nd.child[q]; tau_v[(size_t)(2 * k + q)] = nd.tau[q]; }
+        if (nd.plane < 0) {
+            items_v.insert(items_v.end(), nd.list.begin(), nd.list.end());
+            ++n_leaves;
+            max_leaf = std::max<int64_t>(max_leaf, (int64_t)nd.list.size());
+        }
+        off_v[(size_t)k + 1] = (int64_t)items_v.size();
+        depth = std::max<int64_t>(depth, nd.depth);
+    }
+    if (int rc = tree_attach(L, n_planes, planes, N, plane_v.data(), child_v.data(), tau_v.data(), off_v.data(), items_v.data(), tol)) return rc;
+    if (stats) {
+        stats->n_nodes = N; stats->n_leaves = n_leaves; stats->depth = depth; stats->max_leaf = max_leaf;
+        stats->leaf_items = (int64_t)items_v.size();
+        stats->mean_leaf = n_leaves ? (double)items_v.size() / (double)n_leaves : 0.0;
+        stats->pairs = (int64_t)cnt[0]; stats->box_pairs = (int64_t)cnt[1]; stats->lps = (int64_t)cnt[2]; stats->pivots = (int64_t)cnt[3];
+        stats->capped = (int64_t)cnt[4]; stats->tau_lps = tau_lps; stats->bitset_bytes = bitset_bytes;
+        stats->ms_classify = ms_classify; stats->ms_split = ms_split; stats->ms_tau = ms_tau;
+        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return MPC_OK;
+}
+
 extern "C" int mpc_locator_destroy(mpc_locator *L) {
     if (!L) return MPC_OK;
     (void)hipSetDevice(L->device);
     if (L->stream) (void)hipStreamSynchronize(L->stream);
     for (DevBuf *b : {&L->row_off, &L->row_region, &L->row_end, &L->ef, &L->xlaw, &L->Q, &L->c, &L->H, &L->theta, &L->region, &L->x, &L->masks, &L->sorted_masks,
-                      &L->sorted_region, &L->row_info, &L->theta2, &L->region2}) b->release();
+                      &L->sorted_region, &L->row_info, &L->theta2, &L->region2, &L->t_planes, &L->t_plane, &L->t_child, &L->t_tau, &L->t_off,
+                      &L->t_items}) b->release();
     if (L->e0) (void)hipEventDestroy(L->e0);
     if (L->e1) (void)hipEventDestroy(L->e1);
     if (L->stream) (void)hipStreamDestroy(L->stream);

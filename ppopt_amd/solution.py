@@ -196,6 +196,21 @@ class Solution:
                                                inclusive=inclusive, walk=self.use_walk and self.is_complete)
         return x, region
 
+    def search_tree(self, **kw):
+        """A point-location search tree of this solution (upop.SearchTree.build(self, **kw)), built once per locator and
+        keyword set; get_region_batch / evaluate_batch keep scanning -- use the tree's locate_batch / evaluate_batch."""
+        from .upop.search_tree import SearchTree
+        device = int(kw.get('device', 0))
+        self.locator(device)
+        key = (self._locator_key, tuple(sorted(kw.items())))
+        cache = getattr(self, '_search_trees', None)
+        if cache is None or cache[0] != self._locator_key:
+            cache = (self._locator_key, {})
+            self._search_trees = cache
+        if key not in cache[1]:
+            cache[1][key] = SearchTree.build(self, **kw)
+        return cache[1][key]
+
     # ---- verification without a QP solver: the KKT conditions of the program at theta ----------------------------------------
     def kkt_residuals(self, region: CriticalRegion, theta_point: numpy.ndarray) -> dict:
         """Largest violation of each optimality condition of the program at ``theta_point`` by the region's laws

@@ -58,15 +58,12 @@ def _objective_in_theta(program, A: numpy.ndarray, b: numpy.ndarray):
     return 0.5 * (P + P.T), q.reshape(n_t), r
 
 
-def export_tables(solution: Solution) -> Dict:
-    """The numeric content of an export: unique hyperplanes, the (plane, side) lists of the regions, laws and objectives."""
-    regions = solution.critical_regions
-    n_t = solution.program.num_t()
+def plane_table(regions, n_t: int):
+    """(planes [H, n_t + 1] as unit [n | o], region_start [R + 1], region_plane, region_side): every hyperplane that bounds some
+    region once, with a region's rows as (plane, side) pairs (row = side * [n | o] up to its norm)."""
     planes: List[numpy.ndarray] = []
     index: Dict[tuple, int] = {}
     start, plane_of, side_of = [0], [], []
-    laws, objectives = [], []
-    n_x = 0
     for region in regions:
         E = numpy.asarray(region.E, dtype=numpy.float64).reshape(-1, n_t)
         f = numpy.asarray(region.f, dtype=numpy.float64).reshape(-1)
@@ -84,16 +81,26 @@ def export_tables(solution: Solution) -> Dict:
             plane_of.append(index[key])
             side_of.append(side)
         start.append(len(plane_of))
+    return (numpy.array(planes).reshape(len(planes), n_t + 1), numpy.array(start, dtype=numpy.int64), numpy.array(plane_of, dtype=numpy.int64),
+            numpy.array(side_of, dtype=numpy.int64))
+
+
+def export_tables(solution: Solution) -> Dict:
+    """The numeric content of an export: unique hyperplanes, the (plane, side) lists of the regions, laws and objectives."""
+    regions = solution.critical_regions
+    n_t = solution.program.num_t()
+    planes_arr, start, plane_of, side_of = plane_table(regions, n_t)
+    laws, objectives = [], []
+    n_x = 0
+    for region in regions:
         A, b = _full_law(region, n_t)
         n_x = A.shape[0]
         laws.append(numpy.hstack([A, b]))
         objectives.append(_objective_in_theta(solution.program, A, b))
-    planes_arr = numpy.array(planes).reshape(len(planes), n_t + 1)
     return {'n_theta': n_t, 'n_x': n_x, 'n_regions': len(regions), 'tol': float(solution.point_location_tolerance),
             'overlapping': bool(solution.is_overlapping),
             'plane_normal': planes_arr[:, :n_t], 'plane_offset': planes_arr[:, n_t],
-            'region_start': numpy.array(start, dtype=numpy.int64), 'region_plane': numpy.array(plane_of, dtype=numpy.int64),
-            'region_side': numpy.array(side_of, dtype=numpy.int64),
+            'region_start': start, 'region_plane': plane_of, 'region_side': side_of,
             'law': numpy.array(laws).reshape(len(regions), n_x, n_t + 1),
             'obj_P': numpy.array([o[0] for o in objectives]).reshape(len(regions), n_t, n_t),
             'obj_q': numpy.array([o[1] for o in objectives]).reshape(len(regions), n_t),
@@ -131,9 +138,73 @@ _LOCATE_BODY = '''
     return best;'''
 
 
-def generate_code_cpp(solution: Solution, float_type: str = 'float') -> str:
-    """A header-only C++ translation unit (namespace ``ppopt_solution``) with ``locate`` and ``evaluate``."""
+# locate() through a SearchTree: the descent visits the "+" child if s >= -tau-, the "-" child if s <= tau+ (both inside a band),
+# and applies the rule of _LOCATE_BODY to the regions of the visited leaves (ascending lists)
+_TREE_BODY = """
+{h_bool}region_inside({p_int}r, {ctheta}) {{
+    for ({int} e = region_start[r]; e < region_start[r + 1]; ++e) {{
+        {cint} p = region_plane[e];
+        {real} lhs = 0;
+        for ({int} t = 0; t < n_theta; ++t) lhs += plane_normal[p * n_theta + t] * theta[t];
+        if (!(region_side[e] * (lhs - plane_offset[p]) <= tol)) return false;
+    }}
+    return true;
+}}
+{h_real}region_value({p_int}r, {ctheta}) {{
+    {real} value = obj_r[r];
+    for ({int} i = 0; i < n_theta; ++i) {{
+        {real} row = 0;
+        for ({int} j = 0; j < n_theta; ++j) row += obj_P[(r * n_theta + i) * n_theta + j] * theta[j];
+        value += theta[i] * (obj_q[r * n_theta + i] + row / 2);
+    }}
+    return value;
+}}
+{h_void}tree_visit({p_k}k, {ctheta}, {state}) {{
+    while (tree_plane[k] >= 0) {{
+        {cint} p = tree_plane[k];
+        {real} s = 0;
+        for ({int} t = 0; t < n_theta; ++t) s += plane_normal[p * n_theta + t] * theta[t];
+        s -= plane_offset[p];
+        {cbool} go_plus = s >= -tree_tau[2 * k], go_minus = s <= tree_tau[2 * k + 1];
+        if (go_plus && go_minus) tree_visit(tree_child[2 * k + 1], theta, st);
+        k = go_plus ? tree_child[2 * k] : tree_child[2 * k + 1];
+    }}
+    for ({int} i = tree_off[k]; i < tree_off[k + 1]; ++i) {{
+        {cint} r = tree_items[i];
+        if (!overlapping && st{dot}best >= 0 && r >= st{dot}best) break;
+        if (!region_inside(r, theta)) continue;
+        if (!overlapping) {{ st{dot}best = r; break; }}
+        {real} value = region_value(r, theta);
+        if (st{dot}best < 0 || value < st{dot}value || (value == st{dot}value && r > st{dot}best)) {{ st{dot}best = r; st{dot}value = value; }}
+    }}
+}}
+"""
+
+
+def _tree_tables(tree, lang: str, real: str) -> str:
+    """The tree's node arrays as C++ or JS constants."""
+    def arr(name, vals, integer):
+        if lang == 'js':
+            return f'const {name} = [{_numbers(vals, integer)}];\n'
+        return f'static const {"int" if integer else real} {name}[] = {{{_numbers(vals, integer) or "0"}}};\n'
+    return (arr('tree_plane', tree.node_plane, True) + arr('tree_child', tree.node_child, True) + arr('tree_tau', tree.node_tau, False)
+            + arr('tree_off', tree.node_off, True) + arr('tree_items', tree.items, True))
+
+
+def _check_tree(solution, tree, t) -> None:
+    planes = numpy.hstack([t['plane_normal'], t['plane_offset'][:, None]])
+    if tree.planes.shape != planes.shape or not numpy.array_equal(tree.planes, planes):
+        raise ValueError('the tree was not built on this solution\'s plane table')
+    if tree.tol < t['tol']:
+        raise ValueError(f'the tree was built for tol {tree.tol} < the export tol {t["tol"]}')
+
+
+def generate_code_cpp(solution: Solution, float_type: str = 'float', tree=None) -> str:
+    """A header-only C++ translation unit (namespace ``ppopt_solution``) with ``locate`` and ``evaluate``.  With ``tree`` (a
+    ``SearchTree`` of this solution) ``locate`` descends the tree and tests only the regions of the leaves it reaches."""
     t = export_tables(solution)
+    if tree is not None:
+        _check_tree(solution, tree, t)
     real = float_type
     arr = lambda ctype, name, vals, integer=False: (f'static const {ctype} {name}[] = {{{_numbers(vals, integer) or "0"}}};\n')
     out = ['// explicit solution exported by ppopt_amd.upop.linear_code_gen.generate_code_cpp\n',
@@ -148,7 +219,12 @@ def generate_code_cpp(solution: Solution, float_type: str = 'float') -> str:
            arr('int', 'region_side', t['region_side'], True), arr('real', 'law', t['law']),
            arr('real', 'obj_P', t['obj_P']), arr('real', 'obj_q', t['obj_q']), arr('real', 'obj_r', t['obj_r']),
            '// index of the region that contains theta (-1: none)\n',
-           'inline int locate(const real *theta) {', _LOCATE_BODY.format(real='real'), '\n}\n',
+           *(('inline int locate(const real *theta) {', _LOCATE_BODY.format(real='real'), '\n}\n') if tree is None else
+             (_tree_tables(tree, 'cpp', 'real'), 'struct tree_state { int best; real value; };',
+              _TREE_BODY.format(h_bool='inline bool ', h_real='inline real ', h_void='inline void ', p_int='const int ', p_k='int ',
+                                cbool='const bool', cint='const int', int='int', real='real', ctheta='const real *theta',
+                                state='tree_state &st', dot='.'),
+              'inline int locate(const real *theta) {\n    tree_state st = {-1, 0};\n    tree_visit(0, theta, st);\n    return st.best;\n}\n')),
            '// x[0..n_x) = optimal decision at theta; false if theta lies in no region\n',
            'inline bool evaluate(const real *theta, real *x) {\n'
            '    const int r = locate(theta);\n'
@@ -165,9 +241,12 @@ def generate_code_cpp(solution: Solution, float_type: str = 'float') -> str:
     return ''.join(out)
 
 
-def generate_code_js(solution: Solution) -> str:
-    """A JavaScript module text: ``locate(theta)`` -> region index, ``evaluate(theta)`` -> array or null."""
+def generate_code_js(solution: Solution, tree=None) -> str:
+    """A JavaScript module text: ``locate(theta)`` -> region index, ``evaluate(theta)`` -> array or null.  With ``tree`` (a
+    ``SearchTree`` of this solution) ``locate`` descends the tree."""
     t = export_tables(solution)
+    if tree is not None:
+        _check_tree(solution, tree, t)
     arr = lambda name, vals, integer=False: f'const {name} = [{_numbers(vals, integer)}];\n'
     body = _LOCATE_BODY.format(real='let').replace('int best', 'let best').replace('for (int ', 'for (let ') \
         .replace('const int p', 'const p').replace('bool inside', 'let inside')
@@ -178,7 +257,11 @@ def generate_code_js(solution: Solution) -> str:
            arr('region_start', t['region_start'], True), arr('region_plane', t['region_plane'], True),
            arr('region_side', t['region_side'], True), arr('law', t['law']),
            arr('obj_P', t['obj_P']), arr('obj_q', t['obj_q']), arr('obj_r', t['obj_r']),
-           'function locate(theta) {', body, '\n}\n',
+           *(('function locate(theta) {', body, '\n}\n') if tree is None else
+             (_tree_tables(tree, 'js', 'let'),
+              _TREE_BODY.format(h_bool='function ', h_real='function ', h_void='function ', p_int='', p_k='', cbool='const', cint='const',
+                                int='let', real='let', ctheta='theta', state='st', dot='.'),
+              'function locate(theta) {\n    const st = {best: -1, value: 0};\n    tree_visit(0, theta, st);\n    return st.best;\n}\n')),
            'function evaluate(theta) {\n'
            '    const r = locate(theta);\n'
            '    if (r < 0) return null;\n'
