@@ -572,6 +572,30 @@ int mpc_locator_get_tree(mpc_locator *loc, double *planes, int32_t *node_plane, 
 int mpc_locator_set_tree(mpc_locator *loc, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
                          const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol);
 
+/* ---- merging regions with equal laws into convex unions (Solution.merge_regions) --------------------------------- */
+/* Regions are polytopes {theta : n.theta <= o} of unit rows: ef_rows [rows][n_t + 1] = [o | n] (|n| = 1 within 1e-6, finite), CSR over
+ * regions by row_off[n_regions + 1] (row_off[0] = 0).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16,
+ * 1..256 rows per region.
+ *
+ * mpc_merge_regions: a feasible point xs [n_regions][n_t] and the bounding box box [n_regions][2][n_t] (lower, upper; -inf / +inf
+ *   where unbounded) of every region, one wavefront each (k_merge_regions); status[j] = 1 for an empty region (its box is +inf / -inf).
+ *   stats (may be NULL): [0] LPs, [1] pivots, [2] LP runs stopped at the pivot cap.  ms (may be NULL): device milliseconds.
+ * mpc_merge_pairs: the convexity test of P u Q for every pair (P, Q) = (pair_a[k], pair_b[k]) (k_merge_pairs), from the xs and box of
+ *   mpc_merge_regions.  Row r of P is valid for Q iff max over Q of (n_r.theta - o_r) <= tol max(1, |o_r|) (bit r of
+ *   env_a[k][0 .. MPC_MERGE_WORDS)), and the same for Q's rows over P (env_b).  verdict[k] = 1 iff every LP
+ *   max t s.t. theta in the valid rows widened by tol max(1, |o|), n_i.theta - o_i >= t, n_j.theta - o_j >= t over the non-valid rows
+ *   i of P and j of Q has t* <= tol (the union is then the valid rows); t_max[k]: the largest t reached (-inf: no such LP).  An
+ *   unbounded or capped LP counts as "not valid" / "not convex".  Deterministic: atomics only in the counters.
+ *   stats (may be NULL): [0] pairs, [1] pairs whose valid rows needed no LP, [2] rows tested, [3] rows decided without an LP, [4] LPs,
+ *   [5] pivots, [6] capped runs. */
+#define MPC_MERGE_WORDS 4
+#define MPC_MERGE_MAX_ROWS 256
+int mpc_merge_regions(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *xs, double *box,
+                      int32_t *status, int64_t *stats, float *ms);
+int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
+                    const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
+                    uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

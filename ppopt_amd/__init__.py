@@ -9,6 +9,7 @@ from .mpqp_program import MPQP_Program
 from .mpmilp_program import MPMILP_Program
 from .mpmiqp_program import MPMIQP_Program
 from .solution import Solution
+from .region_merge import MergedRegion
 from .solver import Solver, SolverOutput
 
-__all__ = ['CriticalRegion', 'MPLP_Program', 'MPQP_Program', 'MPMILP_Program', 'MPMIQP_Program', 'Solution', 'Solver', 'SolverOutput']
+__all__ = ['CriticalRegion', 'MPLP_Program', 'MPQP_Program', 'MPMILP_Program', 'MPMIQP_Program', 'Solution', 'MergedRegion', 'Solver', 'SolverOutput']

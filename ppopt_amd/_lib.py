@@ -230,6 +230,10 @@ def load():
         'mpc_locator_tree_size': (ctypes.c_int, [ctypes.c_void_p, _lp, _lp, _ip, _dp]),
         'mpc_locator_get_tree': (ctypes.c_int, [ctypes.c_void_p, _dp, _ip, _ip, _dp, _lp, _ip]),
         'mpc_locator_set_tree': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _dp, ctypes.c_int64, _ip, _ip, _dp, _lp, _ip, ctypes.c_double]),
+        'mpc_merge_regions': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _ip, _lp,
+                                             ctypes.POINTER(ctypes.c_float)]),
+        'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
+                                           ctypes.c_double, _u64p, _u64p, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -248,7 +252,8 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
-                    'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree']
+                    'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
+                    'mpc_merge_pairs']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1106,6 +1111,58 @@ def facet_centres(ef_rows: numpy.ndarray, row_off: numpy.ndarray, device: int = 
     if rc != MPC_OK:
         raise MpcError(f'mpc_facet_centres failed ({rc}): {L.mpc_last_global_error().decode()}')
     return centre, radius, status
+
+
+MERGE_MAX_ROWS = 256   # rows per region of mpc_merge_regions / mpc_merge_pairs (include/mpcombi.h)
+MERGE_WORDS = 4        # 64-bit words of a row mask (MPC_MERGE_WORDS)
+
+
+def _merge_rows(who, row_off, ef_rows):
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ef = _f64(numpy.asarray(ef_rows, dtype=numpy.float64))
+    if ef.ndim != 2 or len(off) < 1 or off[0] != 0 or off[-1] != len(ef):
+        raise MpcError(f'{who}: row_off [n_regions + 1] must run from 0 to the number of rows of ef_rows [rows, n_t + 1]')
+    return off, ef
+
+
+def merge_regions(row_off, ef_rows, device: int = 0):
+    """(xs [R, n_t] a feasible point, box [R, 2, n_t] lower / upper bounds, status [R] (1: empty), stats) of every region of unit rows
+    ef_rows = [o | n] (include/mpcombi.h, mpc_merge_regions).  The limits are checked by the library before any launch (MpcError)."""
+    off, ef = _merge_rows('merge_regions', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    L = load()
+    xs, box, status = numpy.zeros((R, n_t)), numpy.zeros((R, 2, n_t)), numpy.zeros(R, dtype=numpy.int32)
+    st, ms = numpy.zeros(3, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_merge_regions(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), xs.ctypes.data_as(_dp), box.ctypes.data_as(_dp),
+                             status.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_merge_regions failed ({rc}): {L.mpc_last_global_error().decode()}')
+    return xs, box, status, {'lps': int(st[0]), 'pivots': int(st[1]), 'capped': int(st[2]), 'ms': float(ms.value)}
+
+
+def merge_pairs(row_off, ef_rows, xs, box, pair_a, pair_b, tol: float, device: int = 0):
+    """The convexity test of every pair of regions (include/mpcombi.h, mpc_merge_pairs): (env_a [n_pairs, MERGE_WORDS] uint64,
+    env_b, verdict [n_pairs] int32, t_max [n_pairs], stats)."""
+    off, ef = _merge_rows('merge_pairs', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    x = _f64(numpy.asarray(xs, dtype=numpy.float64)).reshape(R, n_t)
+    bx = _f64(numpy.asarray(box, dtype=numpy.float64)).reshape(R, 2, n_t)
+    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
+    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
+    if pa.shape != pb.shape:
+        raise MpcError('merge_pairs: pair_a and pair_b must have the same length')
+    n = len(pa)
+    L = load()
+    env_a, env_b = numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
+    verdict, t_max = numpy.zeros(n, dtype=numpy.int32), numpy.zeros(n)
+    st, ms = numpy.zeros(7, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_merge_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), x.ctypes.data_as(_dp), bx.ctypes.data_as(_dp), n,
+                           pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), float(tol), env_a.ctypes.data_as(_u64p), env_b.ctypes.data_as(_u64p),
+                           verdict.ctypes.data_as(_ip), t_max.ctypes.data_as(_dp), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_merge_pairs failed ({rc}): {L.mpc_last_global_error().decode()}')
+    names = ('pairs', 'box_pairs', 'rows', 'box_rows', 'lps', 'pivots', 'capped')
+    return env_a, env_b, verdict, t_max, dict({k: int(v) for k, v in zip(names, st)}, ms=float(ms.value))
 
 
 class Locator:

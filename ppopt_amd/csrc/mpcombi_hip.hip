@@ -28,6 +28,7 @@
 #include "kernels2.hpp"
 #include "locate.hpp"
 #include "tree.hpp"
+#include "merge.hpp"
 #include "graph.hpp"
 #include "qp.hpp"
 #include <memory>
@@ -5209,5 +5210,161 @@ extern "C" int mpc_locator_destroy(mpc_locator *L) {
     if (L->e1) (void)hipEventDestroy(L->e1);
     if (L->stream) (void)hipStreamDestroy(L->stream);
     delete L;
+    return MPC_OK;
+}
+
+// ---- merging regions with equal laws (merge.hpp) ---------------------------------------------------------------------
+static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (n_t < 1 || n_t > TR_MAX_NT) return bad("n_t must lie in 1..16");
+    if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad("bad region count or missing row_off");
+    if (n_regions > 0x7fffffffll) return bad("too many regions for one launch");
+    if (n_regions > 0 && row_off[0] != 0) return bad("row_off[0] must be 0");
+    *m_max = 1;
+    for (int64_t r = 0; r < n_regions; ++r) {
+        const int64_t k = row_off[r + 1] - row_off[r];
+        if (k < 1 || k > MG_MAX_ROWS) return bad("every region needs 1..256 rows");
+        *m_max = std::max<int>(*m_max, (int)k);
+    }
+    const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
+    if (rows > 0 && !ef_rows) return bad("missing ef_rows");
+    for (int64_t i = 0; i < rows; ++i) {
+        const double *row = ef_rows + i * (n_t + 1);
+        double nn = 0.0;
+        bool finite = std::isfinite(row[0]);
+        for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
+        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("rows must be finite with unit normals");
+    }
+    return MPC_OK;
+}
+
+extern "C" int mpc_merge_regions(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *xs,
+                                 double *box, int32_t *status, int64_t *stats, float *ms) {
+    const char *who = "mpc_merge_regions";
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (n_regions == 0) return MPC_OK;
+    if (!xs || !box || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_regions: missing output array");
+    int ndev = 0;
+    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const long long rows = row_off[n_regions];
+    const size_t lds = tr_lds_bytes(m_max, n_t);
+    DevBuf d_off, d_ef, d_xs, d_box, d_st, d_cnt;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
+    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure((size_t)rows * (n_t + 1) * 8, nullptr));
+    chk(d_xs.ensure((size_t)n_regions * n_t * 8, nullptr)); chk(d_box.ensure((size_t)n_regions * 2 * n_t * 8, nullptr));
+    chk(d_st.ensure((size_t)n_regions * 4, nullptr)); chk(d_cnt.ensure(3 * 8, nullptr));
+    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
+    if (e == hipSuccess) {
+        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n_t + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemset(d_cnt.p, 0, 3 * 8));
+    }
+    if (e == hipSuccess && lds > 48 * 1024)
+        chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_regions), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (e == hipSuccess) {
+        chk(hipEventRecord(e0, nullptr));
+        hipLaunchKernelGGL(k_merge_regions, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
+                           d_off.as<long long>(), d_ef.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_st.as<int32_t>(),
+                           d_cnt.as<unsigned long long>());
+        chk(hipGetLastError());
+        chk(hipEventRecord(e1, nullptr));
+        chk(hipMemcpy(xs, d_xs.p, (size_t)n_regions * n_t * 8, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(box, d_box.p, (size_t)n_regions * 2 * n_t * 8, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(status, d_st.p, (size_t)n_regions * 4, hipMemcpyDeviceToHost));
+        unsigned long long cnt[3] = {0, 0, 0};
+        chk(hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+        if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
+        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
+    }
+    (void)hipDeviceSynchronize();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    for (DevBuf *bf : {&d_off, &d_ef, &d_xs, &d_box, &d_st, &d_cnt}) bf->release();
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    return MPC_OK;
+}
+
+extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
+                               const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
+                               uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms) {
+    const char *who = "mpc_merge_pairs";
+    if (stats) for (int i = 0; i < 7; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: tol must be finite and >= 0");
+    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (n_pairs == 0) return MPC_OK;
+    if (!xs || !box || !pair_a || !pair_b || !env_a || !env_b || !verdict || !t_max)
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: missing array");
+    int pair_rows = 2;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t p = pair_a[k], q = pair_b[k];
+        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: a pair names a region out of range, or the same region twice");
+        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q] + 2));
+    }
+    for (int64_t i = 0; i < n_regions * n_t; ++i)
+        if (std::isnan(xs[i]) || std::isinf(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: xs must be finite");
+    int ndev = 0;
+    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    const long long rows = row_off[n_regions];
+    const int lds_rows = std::max(pair_rows, m_max);
+    const size_t lds = tr_lds_bytes(lds_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_env adds 64)
+    DevBuf d_off, d_ef, d_xs, d_box, d_pa, d_pb, d_ea, d_eb, d_v, d_t, d_cnt;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipSuccess;
+    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
+    const size_t np = (size_t)n_pairs, words = np * MG_WORDS * 8;
+    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure((size_t)rows * (n_t + 1) * 8, nullptr));
+    chk(d_xs.ensure((size_t)n_regions * n_t * 8, nullptr)); chk(d_box.ensure((size_t)n_regions * 2 * n_t * 8, nullptr));
+    chk(d_pa.ensure(np * 4, nullptr)); chk(d_pb.ensure(np * 4, nullptr)); chk(d_ea.ensure(words, nullptr)); chk(d_eb.ensure(words, nullptr));
+    chk(d_v.ensure(np * 4, nullptr)); chk(d_t.ensure(np * 8, nullptr)); chk(d_cnt.ensure(7 * 8, nullptr));
+    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
+    if (e == hipSuccess) {
+        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n_t + 1) * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_xs.p, xs, (size_t)n_regions * n_t * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_box.p, box, (size_t)n_regions * 2 * n_t * 8, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_pa.p, pair_a, np * 4, hipMemcpyHostToDevice));
+        chk(hipMemcpy(d_pb.p, pair_b, np * 4, hipMemcpyHostToDevice));
+        chk(hipMemset(d_cnt.p, 0, 7 * 8));
+    }
+    if (e == hipSuccess && lds > 48 * 1024)
+        chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (e == hipSuccess) {
+        MergePairArgs a{};
+        a.nt = n_t; a.m_max = lds_rows; a.n_pairs = n_pairs;
+        a.row_off = d_off.as<long long>(); a.ef = d_ef.as<double>(); a.xs = d_xs.as<double>(); a.box = d_box.as<double>();
+        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+        a.env_a = d_ea.as<unsigned long long>(); a.env_b = d_eb.as<unsigned long long>(); a.verdict = d_v.as<int32_t>(); a.t_max = d_t.as<double>();
+        a.counters = d_cnt.as<unsigned long long>();
+        chk(hipEventRecord(e0, nullptr));
+        hipLaunchKernelGGL(k_merge_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
+        chk(hipGetLastError());
+        chk(hipEventRecord(e1, nullptr));
+        chk(hipMemcpy(env_a, d_ea.p, words, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(env_b, d_eb.p, words, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(verdict, d_v.p, np * 4, hipMemcpyDeviceToHost));
+        chk(hipMemcpy(t_max, d_t.p, np * 8, hipMemcpyDeviceToHost));
+        unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+        chk(hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+        if (stats) for (int i = 0; i < 7; ++i) stats[i] = (int64_t)cnt[i];
+        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
+    }
+    (void)hipDeviceSynchronize();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    for (DevBuf *bf : {&d_off, &d_ef, &d_xs, &d_box, &d_pa, &d_pb, &d_ea, &d_eb, &d_v, &d_t, &d_cnt}) bf->release();
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     return MPC_OK;
 }

@@ -41,6 +41,8 @@ class Solution:
     # the regions cover the whole feasible parameter set (set by the solvers that run to completion): the walk is only used
     # then -- in a partial solution most walks end at a missing neighbour
     is_complete = False
+    # set on the result of merge_regions (region_merge.build_merged_solution): source, outputs, members, stats
+    merge_info = None
 
     def __init__(self, program, critical_regions: List[CriticalRegion], is_overlapping: bool = False,
                  point_location_tolerance: float = 1e-5):
@@ -73,7 +75,22 @@ class Solution:
         cr = self.get_region(theta_point)
         return None if cr is None else cr.evaluate(theta_point)
 
+    def _refuse_merged(self, what: str) -> None:
+        if self.merge_info is not None:
+            raise ValueError(f'{what} needs the full law and the multipliers, which a merged solution does not keep: verify the source '
+                             f'(merge_info["source"]) instead')
+
+    def merge_regions(self, outputs=None, tol: float = 1e-8, law_tol: float = 1e-8, device: int = 0) -> 'Solution':
+        """A new solution whose regions are convex unions of this one's regions with the same law on the rows ``outputs`` of x (None:
+        all rows); greedy pairwise merging in rounds on the device, deterministic and pairwise maximal (region_merge.py).
+        Every region of the result is a region_merge.MergedRegion with the law x[outputs] = A theta + b and the ascending source indices
+        ``members``.  ValueError before any launch for overlapping (mpLP) and mixed-integer sources, n_theta > 16, a region of more than
+        256 rows and outputs out of range."""
+        from .region_merge import merge_regions
+        return merge_regions(self, outputs=outputs, tol=tol, law_tol=law_tol, device=device)
+
     def evaluate_objective(self, theta_point) -> Optional[float]:
+        self._refuse_merged('evaluate_objective')
         x = self.evaluate(theta_point)
         return None if x is None else self.program.evaluate_objective(x, theta_point)
 
@@ -171,9 +188,11 @@ class Solution:
                 self._locator.close()
             ef, row_off, xlaw = self._stacked()
             P = self.program
-            self._locator = _lib.Locator(row_off, ef, xlaw, getattr(P, 'Q', None), getattr(P, 'c', None), getattr(P, 'H', None), device)
+            # a merged solution's laws hold only the rows of x it was merged for, and it is never overlapping: no objective, no walk
+            P_obj = None if self.merge_info is not None else P
+            self._locator = _lib.Locator(row_off, ef, xlaw, getattr(P_obj, 'Q', None), getattr(P_obj, 'c', None), getattr(P_obj, 'H', None), device)
             adj = getattr(self, '_adjacency', None)
-            if adj is not None and len(adj[1]) == int(row_off[-1]) and len(self.critical_regions) >= self.WALK_MIN_REGIONS:
+            if adj is not None and self.merge_info is None and len(adj[1]) == int(row_off[-1]) and len(self.critical_regions) >= self.WALK_MIN_REGIONS:
                 self._locator.set_adjacency(adj[0], adj[1], P.num_constraints())
             self._locator_key = key
         return self._locator
@@ -216,6 +235,7 @@ class Solution:
         """Largest violation of each optimality condition of the program at ``theta_point`` by the region's laws
         x* = A theta + b, lambda* = C theta + d: primal feasibility, multiplier sign, stationarity, complementarity
         (all scaled by 1 + the magnitude of the quantities involved)."""
+        self._refuse_merged('kkt_residuals')
         P = self.program
         th = numpy.asarray(theta_point, dtype=float).reshape(-1, 1)
         x = numpy.asarray(region.A) @ th + numpy.asarray(region.b).reshape(-1, 1)
@@ -240,6 +260,7 @@ class Solution:
         deterministic solve (solution.py:149-174); here the region's own x*(theta), lambda*(theta) are put through the
         KKT conditions, which are sufficient for the convex programs of this package and need no QP solver.  A point
         in no region verifies when the program is infeasible there (one LP on the device)."""
+        self._refuse_merged('verify_theta')
         region = self.get_region(theta_point)
         P = self.program
         th = numpy.asarray(theta_point, dtype=float).reshape(-1, 1)
@@ -286,6 +307,7 @@ class Solution:
     def verify_solution(self, tol: float = 1e-6, device: int = 0) -> bool:
         """Every region is optimal at its own Chebyshev centre and, without overlaps, is the region found there
         (solution.py:114-147 with the KKT conditions in place of the deterministic solve)."""
+        self._refuse_merged('verify_solution')
         if not self.critical_regions:
             return True
         centres, radii = self.chebyshev_centres(device)
@@ -367,6 +389,7 @@ class Solution:
         (one mpc_hit_and_run over all regions, from the Chebyshev centres), the same test on the region's own law; for
         mixed-integer solutions the rule of _verify_mixed_integer (own objective not below the optimum, located winner equal to it).
         MpcError for an unbounded parameter set and wherever solve_theta_batch raises."""
+        self._refuse_merged('sample_check')
         from . import _lib
         from .geometry import polytope_operations as po
         t0 = time.perf_counter()

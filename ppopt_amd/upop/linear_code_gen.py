@@ -92,11 +92,13 @@ def export_tables(solution: Solution) -> Dict:
     planes_arr, start, plane_of, side_of = plane_table(regions, n_t)
     laws, objectives = [], []
     n_x = 0
+    # a merged solution's laws hold only some rows of x and it is never overlapping: locate() does not read its (zero) objectives
+    merged = getattr(solution, 'merge_info', None) is not None
     for region in regions:
         A, b = _full_law(region, n_t)
         n_x = A.shape[0]
         laws.append(numpy.hstack([A, b]))
-        objectives.append(_objective_in_theta(solution.program, A, b))
+        objectives.append((numpy.zeros((n_t, n_t)), numpy.zeros(n_t), 0.0) if merged else _objective_in_theta(solution.program, A, b))
     return {'n_theta': n_t, 'n_x': n_x, 'n_regions': len(regions), 'tol': float(solution.point_location_tolerance),
             'overlapping': bool(solution.is_overlapping),
             'plane_normal': planes_arr[:, :n_t], 'plane_offset': planes_arr[:, n_t],

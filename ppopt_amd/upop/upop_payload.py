@@ -54,6 +54,9 @@ def find_unique_hyperplanes(overall: numpy.ndarray) -> Tuple[List[int], List[int
 
 def upop_tables(solution: Solution) -> Dict:
     """Everything the three exports are made of, as arrays and lists."""
+    if getattr(solution, 'merge_info', None) is not None:
+        raise ValueError('the payload exports carry the program and full laws, which a merged solution does not keep: use '
+                         'generate_code_cpp / generate_code_js / generate_code_matlab, or export the source (merge_info["source"])')
     regions = solution.critical_regions
     n_t = solution.program.num_t()
     E = numpy.vstack([numpy.asarray(r.E, dtype=numpy.float64).reshape(-1, n_t) for r in regions])
