@@ -572,6 +572,40 @@ int mpc_locator_get_tree(mpc_locator *loc, double *planes, int32_t *node_plane, 
 int mpc_locator_set_tree(mpc_locator *loc, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
                          const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol);
 
+/* ---- explicit controllers in closed loop (Solution.simulate) ------------------------------------------------------- */
+/* mpc_locator_simulate: n trajectories of `steps` steps of theta+ = A theta + B u + c + w under the law u = x*(theta)[inputs] of the
+ * locator's regions, in one launch (k_simulate, closed_loop.hpp).  Step k of trajectory p: a non-finite theta_k ends it (status 3);
+ * j_k = the region mpc_locator_query returns for theta_k with the same tol and flags, and -1 ends it (status 2); u_k = the rows `inputs`
+ * of j_k's law (x of mpc_locator_query, bit for bit); theta_{k+1,i} = c_i + sum_j A_ij theta_j + sum_l B_il u_l + w_i, each term rounded
+ * on its own in this order (no fma; 0.0 start without c, no w term without a disturbance); |theta_{k+1} - theta_k|_inf <= stop_tol
+ * (stop_tol >= 0) ends it after the step (status 1).  Status 0: all steps ran.  exit_step[p]: the index of the last state (steps for
+ * status 0, k + 1 for status 1, k for 2 and 3).
+ *   flags     MPC_LOCATE_OVERLAPPING / _INCLUSIVE as for mpc_locator_query; the locator: MPC_LOCATE_TREE (the attached tree, tol <= its
+ *             tol), MPC_LOCATE_WALK (the adjacency walk from the previous region; needs adjacency, not with the two flags above), neither:
+ *             the list scan; MPC_SIM_FINAL: record the final states only
+ *   theta0    n x n_t;  A n_t x n_t, B n_t x n_u, c n_t (may be NULL), inputs n_u indices into the law's n_x rows (1 <= n_u <= 16)
+ *   w         steps x n x n_t (step-major, may be NULL), or box_lo / box_hi (n_t each, may be NULL): w = lo + (hi - lo) U, U the 53-bit
+ *             uniform of Philox4x32-10 under the key (seed mod 2^32, (seed >> 32) ^ MPC_SIM_KEY_SALT) at the counter (p mod 2^32, p >> 32,
+ *             k, j): components 2j and 2j + 1 from words (0, 1) and (2, 3)
+ *   budget    device bytes allowed (<= 0: 4 GiB)
+ * Outputs, step-major: theta (steps + 1) x n x n_t (with MPC_SIM_FINAL: n x n_t, the state at exit_step), u steps x n x n_u, region
+ * steps x n; after a trajectory's end theta and u are NaN (all bits set) and region -1.  status, exit_step n.
+ * Limits (MPC_ERR_INVALID with a message, before any launch): n_t <= 16, 1 <= n_u <= 16, inputs in range, finite theta0, A, B, c, w
+ * and box (lo <= hi), the budget.  stats (may be NULL). */
+#define MPC_SIM_FINAL 16
+#define MPC_SIM_KEY_SALT 0x636c6f6f
+typedef struct mpc_sim_stats {
+    int64_t traj_steps;   /* steps taken, over all trajectories (a step that ends a trajectory with status 2 counts) */
+    int64_t crossings;    /* walk: regions crossed */
+    int64_t fallbacks;    /* walk / tree: points settled by the lane's own list scan */
+    int32_t mode;         /* the locator that ran: 0 the list scan, MPC_LOCATE_WALK, MPC_LOCATE_TREE */
+    float ms;             /* device milliseconds of k_simulate */
+} mpc_sim_stats;
+int mpc_locator_simulate(mpc_locator *loc, int64_t n, int32_t steps, const double *theta0, int32_t n_u, const int32_t *inputs, const double *A,
+                         const double *B, const double *c, const double *w, const double *box_lo, const double *box_hi, uint64_t seed,
+                         double tol, double stop_tol, int32_t flags, int64_t budget, double *theta, double *u, int32_t *region, int32_t *status,
+                         int32_t *exit_step, mpc_sim_stats *stats);
+
 /* ---- merging regions with equal laws into convex unions (Solution.merge_regions) --------------------------------- */
 /* Regions are polytopes {theta : n.theta <= o} of unit rows: ef_rows [rows][n_t + 1] = [o | n] (|n| = 1 within 1e-6, finite), CSR over
  * regions by row_off[n_regions + 1] (row_off[0] = 0).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16,

@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('MPC_LIB_PATH') or os.path.join(_HERE, 'csrc', 'libmpc
 
 MPC_OK, MPC_ERR_INVALID, MPC_ERR_HIP, MPC_ERR_CAPACITY, MPC_ERR_STATE = range(5)
 MPC_LOCATE_OVERLAPPING, MPC_LOCATE_INCLUSIVE, MPC_LOCATE_WALK, MPC_LOCATE_TREE = 1, 2, 4, 8   # flags of mpc_locator_query
+MPC_SIM_FINAL, MPC_SIM_KEY_SALT = 16, 0x636c6f6f   # flag of mpc_locator_simulate (record the final states only); its Philox key salt
+SIM_MAX_DIM, SIM_MAX_INPUTS, SIM_DEFAULT_BUDGET = 16, 16, 4 << 30   # limits of mpc_locator_simulate
 TREE_MAX_DIM, TREE_MAX_ROWS, TREE_MAX_DEPTH = 16, 256, 64   # limits of mpc_tree_build
 MPC_SOLVE_MANY_BASE = 128   # flag of mpc_solve_many_start
 MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, MPC_LEVEL_ONLY_BASE = 1, 4, 8, 16, 32   # flags of mpc_level_start / mpc_level_run_ex
@@ -116,6 +118,12 @@ class TreeStats(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SimStats(ctypes.Structure):
+    """mpc_sim_stats (include/mpcombi.h)"""
+    _fields_ = [('traj_steps', ctypes.c_int64), ('crossings', ctypes.c_int64), ('fallbacks', ctypes.c_int64), ('mode', ctypes.c_int32),
+                ('ms', ctypes.c_float)]
 
 
 def load():
@@ -230,6 +238,9 @@ def load():
         'mpc_locator_tree_size': (ctypes.c_int, [ctypes.c_void_p, _lp, _lp, _ip, _dp]),
         'mpc_locator_get_tree': (ctypes.c_int, [ctypes.c_void_p, _dp, _ip, _ip, _dp, _lp, _ip]),
         'mpc_locator_set_tree': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _dp, ctypes.c_int64, _ip, _ip, _dp, _lp, _ip, ctypes.c_double]),
+        'mpc_locator_simulate': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _dp, ctypes.c_int32, _ip, _dp, _dp, _dp, _dp, _dp,
+                                                 _dp, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, _dp, _dp,
+                                                 _ip, _ip, _ip, ctypes.POINTER(SimStats)]),
         'mpc_merge_regions': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _ip, _lp,
                                              ctypes.POINTER(ctypes.c_float)]),
         'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
@@ -253,7 +264,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
-                    'mpc_merge_pairs']
+                    'mpc_merge_pairs', 'mpc_locator_simulate']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1275,6 +1286,39 @@ class Locator:
             raise MpcError(f'mpc_locator_query failed ({rc}): {self._L.mpc_last_global_error().decode()}')
         self.last_ms = float(ms.value)
         return region, x
+
+    def simulate(self, theta0, steps: int, A, B, inputs, c=None, w=None, box=None, seed: int = 0, tol: float = 1e-5,
+                 stop_tol: Optional[float] = None, overlapping: bool = False, inclusive: bool = False, walk: bool = False, tree: bool = False,
+                 final_only: bool = False, budget: int = 0):
+        """mpc_locator_simulate.  theta0 [n, n_t]; w [steps, n, n_t] step-major or None; box (lo, hi) or None.  Returns the step-major
+        arrays (theta [steps+1, n, n_t] or [n, n_t] with final_only, u [steps, n, n_u], region [steps, n] int32 (None with final_only),
+        status [n], exit_step [n]) and the stats as a dict."""
+        th0 = _f64(theta0).reshape(-1, self.n_t)
+        n, steps = len(th0), int(steps)
+        A_, B_ = _f64(A).reshape(self.n_t, self.n_t), _f64(B).reshape(self.n_t, -1)
+        n_u = B_.shape[1]
+        inp = numpy.ascontiguousarray(inputs, dtype=numpy.int32).reshape(-1)
+        c_ = None if c is None else _f64(c).reshape(-1)
+        w_ = None if w is None else _f64(w).reshape(steps, n, self.n_t)
+        lo = hi = None
+        if box is not None:
+            lo, hi = _f64(box[0]).reshape(-1), _f64(box[1]).reshape(-1)
+        theta = numpy.empty((n, self.n_t) if final_only else (steps + 1, n, self.n_t))
+        u = None if final_only else numpy.empty((steps, n, n_u))
+        region = None if final_only else numpy.empty((steps, n), dtype=numpy.int32)
+        status, exit_step = numpy.empty(n, dtype=numpy.int32), numpy.empty(n, dtype=numpy.int32)
+        st = SimStats()
+        p = lambda a, t=_dp: None if a is None else a.ctypes.data_as(t)
+        flags = (MPC_LOCATE_OVERLAPPING if overlapping else 0) | (MPC_LOCATE_INCLUSIVE if inclusive else 0) | (MPC_LOCATE_WALK if walk else 0) \
+            | (MPC_LOCATE_TREE if tree else 0) | (MPC_SIM_FINAL if final_only else 0)
+        rc = self._L.mpc_locator_simulate(self._h, n, steps, p(th0), n_u, p(inp, _ip), p(A_), p(B_), p(c_), p(w_), p(lo), p(hi), int(seed),
+                                          float(tol), -1.0 if stop_tol is None else float(stop_tol), flags, int(budget), p(theta), p(u),
+                                          p(region, _ip), p(status, _ip), p(exit_step, _ip), ctypes.byref(st))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_locator_simulate failed ({rc}): {self._L.mpc_last_global_error().decode()}')
+        stats = {name: getattr(st, name) for name, _ in SimStats._fields_}
+        self.last_ms = float(st.ms)
+        return theta, u, region, status, exit_step, stats
 
     def close(self):
         if getattr(self, '_h', None):

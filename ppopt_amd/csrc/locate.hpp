@@ -65,23 +65,20 @@ __device__ __forceinline__ double loc_objective(const double *xl, int nx, int nt
 // with each row come the region it belongs to and the index of the first row of the next region, so that a wavefront
 // which has no lane left inside a region jumps over the rest of its rows.
 constexpr int LOC_TILE = 256;
+
+// The scan of one point per lane, shared by k_locate and k_simulate (closed_loop.hpp).  Every thread of the block calls it (it stages
+// the rows with barriers); `active` is false for a lane without a point, which only helps to stage.  tile / trid / tend: LDS of
+// LOC_TILE rows.  Returns the region (-1: none).
 template <int NT>
-__global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, long long n_regions, long long n_rows,
-                                                const int32_t *__restrict__ row_region, const int32_t *__restrict__ row_end,
-                                                const double *__restrict__ ef, const double *__restrict__ xlaw,
-                                                const double *__restrict__ Q, const double *__restrict__ cvec, const double *__restrict__ H,
-                                                const double *__restrict__ theta, double tol, int overlapping, int inclusive,
-                                                long long *__restrict__ region_out) {
-    __shared__ double tile[LOC_TILE][NT + 1];
-    __shared__ int trid[LOC_TILE], tend[LOC_TILE];
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ long long loc_scan_block(bool active, const double (&th)[NT], int nt, int nx, long long n_rows,
+                                                    const int32_t *__restrict__ row_region, const int32_t *__restrict__ row_end,
+                                                    const double *__restrict__ ef, const double *__restrict__ xlaw, const double *__restrict__ Q,
+                                                    const double *__restrict__ cvec, const double *__restrict__ H, double tol, int overlapping,
+                                                    int inclusive, double (*tile)[NT + 1], int *trid, int *tend) {
     const int nr = nt + 1;
-    double th[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) th[t] = (p < m && t < nt) ? theta[p * nt + t] : 0.0;
     long long found = -1;
     double best = INFINITY;
-    bool alive = p < m, inside = false;
+    bool alive = active, inside = false;
     int cur = -1;
     long long i = 0;   // next row of this wavefront (wave-uniform)
     // the point is inside every row of region `cur`: first match, or candidate for the lowest objective
@@ -110,7 +107,7 @@ __global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, lon
             if (rid != cur) {
                 commit();
                 cur = rid;
-                inside = overlapping ? (p < m) : alive;
+                inside = overlapping ? active : alive;
                 if (!overlapping && !__any(alive)) { i = n_rows; break; }   // every lane has its region
             }
             inside = inside && loc_row_inside<NT>(tile[li], th, NT, tol, inclusive);   // tile rows are zero past nt
@@ -119,7 +116,48 @@ __global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, lon
         }
     }
     commit();
+    return found;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, long long n_regions, long long n_rows,
+                                                const int32_t *__restrict__ row_region, const int32_t *__restrict__ row_end,
+                                                const double *__restrict__ ef, const double *__restrict__ xlaw,
+                                                const double *__restrict__ Q, const double *__restrict__ cvec, const double *__restrict__ H,
+                                                const double *__restrict__ theta, double tol, int overlapping, int inclusive,
+                                                long long *__restrict__ region_out) {
+    __shared__ double tile[LOC_TILE][NT + 1];
+    __shared__ int trid[LOC_TILE], tend[LOC_TILE];
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    double th[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) th[t] = (p < m && t < nt) ? theta[p * nt + t] : 0.0;
+    const long long found = loc_scan_block<NT>(p < m, th, nt, nx, n_rows, row_region, row_end, ef, xlaw, Q, cvec, H, tol, overlapping, inclusive,
+                                               tile, trid, tend);
     if (p < m) region_out[p] = found;
+}
+
+// The list scan of one lane on its own (no barriers, no LDS): the fallback of k_simulate for a point the walk or the tree left
+// unresolved.  The scan's row test and objective, regions in list order: the first containing region, or with `overlapping` the
+// containing region of lowest objective, ties to the later one -- the answer of loc_scan_block.
+template <int NT>
+__device__ __forceinline__ long long loc_scan_lane(const double (&th)[NT], int nt, int nx, long long n_regions, const long long *__restrict__ row_off,
+                                                   const double *__restrict__ ef, const double *__restrict__ xlaw, const double *__restrict__ Q,
+                                                   const double *__restrict__ cvec, const double *__restrict__ H, double tol, int overlapping,
+                                                   int inclusive) {
+    const int nr = nt + 1;
+    long long found = -1;
+    double best = INFINITY;
+    for (long long r = 0; r < n_regions; ++r) {
+        if (row_off[r + 1] <= row_off[r]) continue;   // the scan walks rows: a region without rows is never met
+        bool inside = true;
+        for (long long k = row_off[r]; k < row_off[r + 1] && inside; ++k) inside = loc_row_inside<NT>(ef + k * nr, th, nt, tol, inclusive);
+        if (!inside) continue;
+        if (!overlapping) return r;
+        const double obj = loc_objective<NT>(xlaw + (size_t)r * nx * nr, nx, nt, th, cvec, H, Q);
+        if (obj <= best) { best = obj; found = r; }
+    }
+    return found;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -138,20 +176,18 @@ __global__ void __launch_bounds__(256) k_locate(long long m, int nt, int nx, lon
 // To return the region the scan would return (the FIRST containing region of the list), a located point is also offered to
 // the neighbours across the rows it satisfies by less than 2*tol, if their index is smaller.
 // row_info[row] = kind << 16 | id:  kind 0 multiplier row of active constraint id, 1 inactive constraint id, 2 A_t row, 3 unknown.
+// The walk of one lane from start_region (shared by k_locate_walk and k_simulate): the region (-1 outside, -2 unresolved); `crossings`
+// counts the regions crossed.  certify_first (k_simulate, whose walks start anywhere): a located point with a row within 2 tol whose
+// neighbour is unknown is left unresolved, since an earlier region behind that row may contain it too.
 template <int NT, int MW>
-__global__ void __launch_bounds__(256) k_locate_walk(long long m, int nt, long long n_regions, const long long *__restrict__ row_off,
-                                                     const double *__restrict__ ef, const int32_t *__restrict__ row_info,
-                                                     const unsigned long long *__restrict__ masks,          // [n_regions][MW], region order
-                                                     const unsigned long long *__restrict__ sorted_masks,   // [n_regions][MW], ascending
-                                                     const int32_t *__restrict__ sorted_region,             // region of sorted_masks[i]
-                                                     const double *__restrict__ theta, double tol, int start_region, int max_steps,
-                                                     int n_c, long long *__restrict__ region_out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
+__device__ __forceinline__ long long loc_walk(const double (&th)[NT], int nt, long long n_regions, const long long *__restrict__ row_off,
+                                              const double *__restrict__ ef, const int32_t *__restrict__ row_info,
+                                              const unsigned long long *__restrict__ masks,          // [n_regions][MW], region order
+                                              const unsigned long long *__restrict__ sorted_masks,   // [n_regions][MW], ascending
+                                              const int32_t *__restrict__ sorted_region,             // region of sorted_masks[i]
+                                              double tol, long long start_region, int max_steps, int n_c, unsigned long long &crossings,
+                                              bool certify_first = false) {
     const int nr = nt + 1;
-    double th[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) th[t] = t < nt ? theta[p * nt + t] : 0.0;
     auto lookup = [&](const unsigned long long (&key)[MW]) -> long long {
         long long lo = 0, hi = n_regions;
         while (lo < hi) {
@@ -217,7 +253,7 @@ __global__ void __launch_bounds__(256) k_locate_walk(long long m, int nt, long l
             bound = worst;
         }
         if (!any_violated) { found = row_off[r + 1] > row_off[r] ? r : -2; break; }
-        if (next >= 0) { prev = r; r = next; continue; }
+        if (next >= 0) { prev = r; r = next; ++crossings; continue; }
         // Every violated row leads nowhere with one row added or removed.  Where the constraint gradients are dependent the
         // region behind a facet differs by TWO rows (one enters, one leaves): try, for the most violated rows, the neighbour's
         // active set with one further row exchanged, and take the first that exists and is violated less than this region.
@@ -257,7 +293,7 @@ __global__ void __launch_bounds__(256) k_locate_walk(long long m, int nt, long l
                 }
             }
         }
-        if (next >= 0) { prev = r; r = next; continue; }
+        if (next >= 0) { prev = r; r = next; ++crossings; continue; }
         found = met_omega ? -1 : -2;
         break;
     }
@@ -274,12 +310,33 @@ __global__ void __launch_bounds__(256) k_locate_walk(long long m, int nt, long l
                     double w; long long wr;
                     worst_row(q, w, wr);
                     if (wr >= 0 && w < tol) best = q;
+                } else if (certify_first && q == -2) {   // what lies behind this near row is unknown: the rule cannot be certified
+                    best = -2;
+                    break;
                 }
             }
         }
         found = best;
     }
-    region_out[p] = found;
+    return found;
+}
+
+template <int NT, int MW>
+__global__ void __launch_bounds__(256) k_locate_walk(long long m, int nt, long long n_regions, const long long *__restrict__ row_off,
+                                                     const double *__restrict__ ef, const int32_t *__restrict__ row_info,
+                                                     const unsigned long long *__restrict__ masks,          // [n_regions][MW], region order
+                                                     const unsigned long long *__restrict__ sorted_masks,   // [n_regions][MW], ascending
+                                                     const int32_t *__restrict__ sorted_region,             // region of sorted_masks[i]
+                                                     const double *__restrict__ theta, double tol, int start_region, int max_steps,
+                                                     int n_c, long long *__restrict__ region_out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    double th[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) th[t] = t < nt ? theta[p * nt + t] : 0.0;
+    unsigned long long crossings = 0;
+    region_out[p] = loc_walk<NT, MW>(th, nt, n_regions, row_off, ef, row_info, masks, sorted_masks, sorted_region, tol, start_region, max_steps,
+                                     n_c, crossings);
 }
 
 // The few points the walk left unresolved: one thread per (point, region), the first containing region by atomicMin.

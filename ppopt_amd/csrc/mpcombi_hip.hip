@@ -28,6 +28,7 @@
 #include "kernels2.hpp"
 #include "locate.hpp"
 #include "tree.hpp"
+#include "closed_loop.hpp"
 #include "merge.hpp"
 #include "graph.hpp"
 #include "qp.hpp"
@@ -5210,6 +5211,150 @@ extern "C" int mpc_locator_destroy(mpc_locator *L) {
     if (L->e1) (void)hipEventDestroy(L->e1);
     if (L->stream) (void)hipStreamDestroy(L->stream);
     delete L;
+    return MPC_OK;
+}
+
+// ---- closed-loop simulation (closed_loop.hpp) --------------------------------------------------------------------------
+constexpr long long SIM_DEFAULT_BUDGET = 4ll << 30;
+
+extern "C" int mpc_locator_simulate(mpc_locator *L, int64_t n, int32_t steps, const double *theta0, int32_t n_u, const int32_t *inputs,
+                                    const double *A, const double *B, const double *c, const double *w, const double *box_lo,
+                                    const double *box_hi, uint64_t seed, double tol, double stop_tol, int32_t flags, int64_t budget,
+                                    double *theta, double *u, int32_t *region, int32_t *status, int32_t *exit_step, mpc_sim_stats *stats) {
+    const char *who = "mpc_locator_simulate";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!L) return bad("no locator");
+    const int nt = L->n_t, nx = L->n_x;
+    const bool final_only = (flags & MPC_SIM_FINAL) != 0, tree = (flags & MPC_LOCATE_TREE) != 0, walk = (flags & MPC_LOCATE_WALK) != 0;
+    const bool overlapping = (flags & MPC_LOCATE_OVERLAPPING) != 0, inclusive = (flags & MPC_LOCATE_INCLUSIVE) != 0;
+    if (n < 0 || n > (1ll << 40) || steps < 1 || steps > (1 << 30)) return bad("n must lie in 0..2^40 and steps in 1..2^30");
+    if (nt < 1 || nt > 16) return bad("n_theta must lie in 1..16");
+    if (n_u < 1 || n_u > 16) return bad("n_u must lie in 1..16");
+    if (L->n_regions < 1) return bad("the locator holds no region");
+    if (n > 0 && (!theta0 || !theta || !status || !exit_step)) return bad("missing theta0, theta, status or exit_step");
+    if (n > 0 && !final_only && (!u || !region)) return bad("a full record needs u and region");
+    if (!inputs || !A || !B) return bad("missing inputs, A or B");
+    for (int i = 0; i < n_u; ++i)
+        if (inputs[i] < 0 || inputs[i] >= nx) return bad("input index " + std::to_string(inputs[i]) + " is out of range (0 <= inputs < n_x = " + std::to_string(nx) + ")");
+    auto finite = [](const double *v, long long k) { for (long long i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false; return true; };
+    if (!finite(A, (long long)nt * nt) || !finite(B, (long long)nt * n_u) || (c && !finite(c, nt))) return bad("A, B and c must be finite");
+    if (n > 0 && !finite(theta0, n * nt)) return bad("theta0 must be finite");
+    if (w && (box_lo || box_hi)) return bad("a disturbance array and a box exclude each other");
+    if ((box_lo == nullptr) != (box_hi == nullptr)) return bad("box_lo and box_hi go together");
+    if (box_lo)
+        for (int t = 0; t < nt; ++t)
+            if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] <= box_hi[t])) return bad("the box must be finite with lo <= hi");
+    if (w && n > 0 && !finite(w, n * (long long)steps * nt)) return bad("the disturbance must be finite");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (std::isnan(stop_tol)) return bad("stop_tol must not be NaN (< 0: off)");
+    if (tree && walk) return bad("MPC_LOCATE_TREE and MPC_LOCATE_WALK exclude each other");
+    if (tree && !L->has_tree) return bad("MPC_LOCATE_TREE without an attached tree");
+    if (tree && !(tol <= L->tree_tol)) return bad("tol is larger than the tolerance the tree was built for");
+    if (walk && (!L->has_adj || overlapping || inclusive)) return bad("MPC_LOCATE_WALK needs adjacency, and neither MPC_LOCATE_OVERLAPPING nor MPC_LOCATE_INCLUSIVE");
+    // device bytes of the record and the inputs (doubles: no overflow for any n, steps that pass above)
+    const double rec = final_only ? (double)n * nt * 8 : (double)n * ((double)(steps + 1) * nt * 8 + (double)steps * (n_u * 8 + 4));
+    const double bytes = rec + (double)n * nt * 8 + (w ? (double)n * steps * nt * 8 : 0.0);
+    const double cap = budget > 0 ? (double)budget : (double)SIM_DEFAULT_BUDGET;
+    if (bytes > cap)
+        return bad("the run needs " + std::to_string((long long)bytes) + " device bytes, more than the budget of " + std::to_string((long long)cap) +
+                   " (record the final states only, or run fewer trajectories at a time)");
+    if (n == 0) return MPC_OK;
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    hipStream_t st = L->stream;
+    const size_t n_th = (size_t)(final_only ? 1 : steps + 1) * n * nt, n_uu = final_only ? 0 : (size_t)steps * n * n_u, n_rg = final_only ? 0 : (size_t)steps * n;
+    // the plant in one block: A [nt][nt], B [nt][n_u], c [nt], lo [nt], hi [nt], then the inputs
+    std::vector<double> plant((size_t)nt * nt + (size_t)nt * n_u + 3 * (size_t)nt, 0.0);
+    std::memcpy(plant.data(), A, sizeof(double) * nt * nt);
+    std::memcpy(plant.data() + nt * nt, B, sizeof(double) * nt * n_u);
+    const size_t oc = (size_t)nt * nt + (size_t)nt * n_u, olo = oc + nt, ohi = olo + nt;
+    if (c) std::memcpy(plant.data() + oc, c, sizeof(double) * nt);
+    if (box_lo) { std::memcpy(plant.data() + olo, box_lo, sizeof(double) * nt); std::memcpy(plant.data() + ohi, box_hi, sizeof(double) * nt); }
+    DevBuf d_th0, d_th, d_u, d_rg, d_st, d_ex, d_w, d_plant, d_in, d_cnt;
+    unsigned long long cnt[3] = {0, 0, 0};
+    float ms = 0.0f;
+    auto run = [&]() -> hipError_t {
+        hipError_t e;
+#define SIM_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+        SIM_TRY(d_th0.ensure((size_t)n * nt * 8, st));
+        SIM_TRY(d_th.ensure(n_th * 8, st));
+        if (!final_only) { SIM_TRY(d_u.ensure(n_uu * 8, st)); SIM_TRY(d_rg.ensure(n_rg * 4, st)); }
+        SIM_TRY(d_st.ensure((size_t)n * 4, st));
+        SIM_TRY(d_ex.ensure((size_t)n * 4, st));
+        if (w) SIM_TRY(d_w.ensure((size_t)n * steps * nt * 8, st));
+        SIM_TRY(d_plant.ensure(plant.size() * 8, st));
+        SIM_TRY(d_in.ensure((size_t)n_u * 4, st));
+        SIM_TRY(d_cnt.ensure(3 * 8, st));
+        SIM_TRY(hipMemcpyAsync(d_th0.p, theta0, (size_t)n * nt * 8, hipMemcpyHostToDevice, st));
+        if (w) SIM_TRY(hipMemcpyAsync(d_w.p, w, (size_t)n * steps * nt * 8, hipMemcpyHostToDevice, st));
+        SIM_TRY(hipMemcpyAsync(d_plant.p, plant.data(), plant.size() * 8, hipMemcpyHostToDevice, st));
+        SIM_TRY(hipMemcpyAsync(d_in.p, inputs, (size_t)n_u * 4, hipMemcpyHostToDevice, st));
+        SIM_TRY(hipMemsetAsync(d_cnt.p, 0, 3 * 8, st));
+        if (!final_only) {   // what lies after a trajectory's end is never written: NaN (all bits set) and region -1
+            SIM_TRY(hipMemsetAsync(d_th.p, 0xff, n_th * 8, st));
+            SIM_TRY(hipMemsetAsync(d_u.p, 0xff, n_uu * 8, st));
+            SIM_TRY(hipMemsetAsync(d_rg.p, 0xff, n_rg * 4, st));
+        }
+        const double *pl = d_plant.as<double>();
+        SimArgs a{};
+        a.n = n; a.steps = steps; a.nt = nt; a.nx = nx; a.nu = n_u;
+        a.n_regions = L->n_regions; a.n_rows = L->n_rows;
+        a.row_off = L->row_off.as<long long>(); a.row_region = L->row_region.as<int32_t>(); a.row_end = L->row_end.as<int32_t>();
+        a.ef = L->ef.as<double>(); a.xlaw = L->xlaw.as<double>();
+        a.Q = L->hasQ ? L->Q.as<double>() : nullptr; a.cvec = L->hasc ? L->c.as<double>() : nullptr; a.H = L->hasH ? L->H.as<double>() : nullptr;
+        a.tol = tol; a.overlapping = overlapping; a.inclusive = inclusive;
+        if (walk) {
+            a.row_info = L->row_info.as<int32_t>(); a.sorted_region = L->sorted_region.as<int32_t>();
+            a.masks = L->masks.as<unsigned long long>(); a.sorted_masks = L->sorted_masks.as<unsigned long long>();
+            a.n_c = L->n_c; a.max_walk = 384;   // the step limit of mpc_locator_query's walk
+        }
+        if (tree) {
+            a.planes = L->t_planes.as<double>(); a.node_tau = L->t_tau.as<double>(); a.node_plane = L->t_plane.as<int32_t>();
+            a.node_child = L->t_child.as<int32_t>(); a.items = L->t_items.as<int32_t>(); a.node_off = L->t_off.as<long long>();
+        }
+        a.theta0 = d_th0.as<double>(); a.inputs = d_in.as<int32_t>();
+        a.A = pl; a.B = pl + nt * nt; a.c = c ? pl + oc : nullptr; a.w = w ? d_w.as<double>() : nullptr;
+        a.lo = box_lo ? pl + olo : nullptr; a.hi = box_lo ? pl + ohi : nullptr;
+        a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32) ^ MPC_SIM_KEY_SALT;
+        a.stop_tol = stop_tol; a.final_only = final_only;
+        a.theta = d_th.as<double>(); a.u = final_only ? nullptr : d_u.as<double>(); a.region = final_only ? nullptr : d_rg.as<int32_t>();
+        a.status = d_st.as<int32_t>(); a.exit_step = d_ex.as<int32_t>(); a.counters = d_cnt.as<unsigned long long>();
+        const dim3 g((unsigned)((n + SIM_BLOCK - 1) / SIM_BLOCK)), b(SIM_BLOCK);
+        SIM_TRY(hipEventRecord(L->e0, st));
+#define MPC_SIM(NT_, NU_, MODE_) hipLaunchKernelGGL((k_simulate<NT_, NU_, MODE_>), g, b, 0, st, a)
+#define MPC_SIM_NU(NT_, MODE_) do { if (n_u <= 4) MPC_SIM(NT_, 4, MODE_); else MPC_SIM(NT_, 16, MODE_); } while (0)
+#define MPC_SIM_NT(MODE_) do { if (nt <= 4) MPC_SIM_NU(4, MODE_); else if (nt <= 8) MPC_SIM_NU(8, MODE_); else MPC_SIM_NU(16, MODE_); } while (0)
+        if (tree) MPC_SIM_NT(SIM_TREE);
+        else if (walk && L->mask_words == 2) MPC_SIM_NT(SIM_WALK2);
+        else if (walk) MPC_SIM_NT(SIM_WALK4);
+        else MPC_SIM_NT(SIM_SCAN);
+#undef MPC_SIM_NT
+#undef MPC_SIM_NU
+#undef MPC_SIM
+        SIM_TRY(hipGetLastError());
+        SIM_TRY(hipEventRecord(L->e1, st));
+        SIM_TRY(hipMemcpyAsync(theta, d_th.p, n_th * 8, hipMemcpyDeviceToHost, st));
+        if (!final_only) {
+            SIM_TRY(hipMemcpyAsync(u, d_u.p, n_uu * 8, hipMemcpyDeviceToHost, st));
+            SIM_TRY(hipMemcpyAsync(region, d_rg.p, n_rg * 4, hipMemcpyDeviceToHost, st));
+        }
+        SIM_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        SIM_TRY(hipMemcpyAsync(exit_step, d_ex.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        SIM_TRY(hipMemcpyAsync(cnt, d_cnt.p, 3 * 8, hipMemcpyDeviceToHost, st));
+        SIM_TRY(hipStreamSynchronize(st));
+        SIM_TRY(hipEventElapsedTime(&ms, L->e0, L->e1));
+#undef SIM_TRY
+        return hipSuccess;
+    };
+    const hipError_t e = run();
+    if (e != hipSuccess) (void)hipStreamSynchronize(st);
+    for (DevBuf *q : {&d_th0, &d_th, &d_u, &d_rg, &d_st, &d_ex, &d_w, &d_plant, &d_in, &d_cnt}) q->release();
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    if (stats) {
+        stats->traj_steps = (int64_t)cnt[0]; stats->crossings = (int64_t)cnt[1]; stats->fallbacks = (int64_t)cnt[2];
+        stats->mode = tree ? MPC_LOCATE_TREE : walk ? MPC_LOCATE_WALK : 0;
+        stats->ms = ms;
+    }
     return MPC_OK;
 }
 

@@ -225,22 +225,17 @@ __global__ void __launch_bounds__(256) k_tree_owner(long long n_entries, int hw,
 // Descent: node_plane[k] < 0 marks a leaf with regions items[node_off[k] .. node_off[k + 1]) (ascending).  The "+" child is visited
 // if s >= -tau-, the "-" child if s <= tau+; the second child of a band goes on a stack of TR_STACK nodes per lane (LDS); a lane
 // whose stack overflows returns -2 and the host hands the point to the list scan.
+// The descent of one lane (shared by k_locate_tree and k_simulate, closed_loop.hpp): the region, -1 for none, -2 on a stack overflow.
+// stack: LDS of TR_STACK x 256 ints, the lane's column threadIdx.x (blocks of 256).
 template <int NT>
-__global__ void __launch_bounds__(256) k_locate_tree(long long m, int nt, int nx, const double *__restrict__ planes,
-                                                     const int32_t *__restrict__ node_plane, const int32_t *__restrict__ node_child,
-                                                     const double *__restrict__ node_tau, const long long *__restrict__ node_off,
-                                                     const int32_t *__restrict__ items, const long long *__restrict__ row_off,
-                                                     const double *__restrict__ ef, const double *__restrict__ xlaw,
-                                                     const double *__restrict__ Q, const double *__restrict__ cvec, const double *__restrict__ H,
-                                                     const double *__restrict__ theta, double tol, int overlapping, int inclusive,
-                                                     long long *__restrict__ region_out) {
-    __shared__ int stack[TR_STACK][256];
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
+__device__ __forceinline__ long long loc_tree(const double (&th)[NT], int nt, int nx, const double *__restrict__ planes,
+                                              const int32_t *__restrict__ node_plane, const int32_t *__restrict__ node_child,
+                                              const double *__restrict__ node_tau, const long long *__restrict__ node_off,
+                                              const int32_t *__restrict__ items, const long long *__restrict__ row_off,
+                                              const double *__restrict__ ef, const double *__restrict__ xlaw, const double *__restrict__ Q,
+                                              const double *__restrict__ cvec, const double *__restrict__ H, double tol, int overlapping,
+                                              int inclusive, int *stack) {
     const int nr = nt + 1;
-    double th[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) th[t] = t < nt ? theta[p * nt + t] : 0.0;
     long long found = -1;
     double best = INFINITY;
     int sp = 0, node = 0;
@@ -255,7 +250,7 @@ __global__ void __launch_bounds__(256) k_locate_tree(long long m, int nt, int nx
             const bool go_plus = s >= -node_tau[2 * node], go_minus = s <= node_tau[2 * node + 1];
             if (go_plus && go_minus) {
                 if (sp == TR_STACK) { overflow = true; break; }
-                stack[sp++][threadIdx.x] = node_child[2 * node + 1];
+                stack[sp++ * 256 + threadIdx.x] = node_child[2 * node + 1];
             }
             node = go_plus ? node_child[2 * node] : node_child[2 * node + 1];
         }
@@ -271,9 +266,29 @@ __global__ void __launch_bounds__(256) k_locate_tree(long long m, int nt, int nx
             if (obj < best || (obj == best && r > found)) { best = obj; found = r; }
         }
         if (sp == 0) break;
-        node = stack[--sp][threadIdx.x];
+        --sp;
+        node = stack[sp * 256 + threadIdx.x];
     }
-    region_out[p] = overflow ? -2 : found;
+    return overflow ? -2 : found;
+}
+
+template <int NT>
+__global__ void __launch_bounds__(256) k_locate_tree(long long m, int nt, int nx, const double *__restrict__ planes,
+                                                     const int32_t *__restrict__ node_plane, const int32_t *__restrict__ node_child,
+                                                     const double *__restrict__ node_tau, const long long *__restrict__ node_off,
+                                                     const int32_t *__restrict__ items, const long long *__restrict__ row_off,
+                                                     const double *__restrict__ ef, const double *__restrict__ xlaw,
+                                                     const double *__restrict__ Q, const double *__restrict__ cvec, const double *__restrict__ H,
+                                                     const double *__restrict__ theta, double tol, int overlapping, int inclusive,
+                                                     long long *__restrict__ region_out) {
+    __shared__ int stack[TR_STACK * 256];
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    double th[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) th[t] = t < nt ? theta[p * nt + t] : 0.0;
+    region_out[p] = loc_tree<NT>(th, nt, nx, planes, node_plane, node_child, node_tau, node_off, items, row_off, ef, xlaw, Q, cvec, H, tol, overlapping,
+                                 inclusive, stack);
 }
 
 }  // namespace mpc

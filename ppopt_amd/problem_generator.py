@@ -114,6 +114,17 @@ def double_integrator_data(horizon: int = 5, x_bound: float = 4.0, u_bound: floa
     return _pack(A, b, numpy.zeros((nz, 1)), numpy.zeros((nz, 2)), numpy.eye(nz), A_t, b_t, F, range(2 * N))
 
 
+def double_integrator_plant(horizon: int = 5) -> Dict:
+    """The plant of config 2 (``double_integrator_data(horizon)``) for closed-loop simulation: theta+ = A theta + B u with u = u_0 = x[2N],
+    the first input among the decision variables (x_1..x_N, then u_0..u_{N-1})."""
+    return {'A': numpy.array([[1.0, 1.0], [0.0, 1.0]]), 'B': numpy.array([[0.5], [1.0]]), 'inputs': [2 * int(horizon)]}
+
+
+def quad_tank_plant() -> Dict:
+    """The plant of config 3 (``quad_tank_data``): theta+ = _QT_A theta + _QT_B u with u = u_0 = x[0:2] of the condensed program."""
+    return {'A': _QT_A.copy(), 'B': _QT_B.copy(), 'inputs': [0, 1]}
+
+
 # discrete quadruple-tank model (Johansson 2000 minimum-phase parameters, zero-order hold, Ts = 5 s);
 # numbers are frozen here to six decimals -- they ARE the definition of config 3.
 _QT_A = numpy.array([[0.922521, 0.0, 0.187440, 0.0],

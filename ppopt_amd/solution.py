@@ -230,6 +230,15 @@ class Solution:
             cache[1][key] = SearchTree.build(self, **kw)
         return cache[1][key]
 
+    def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
+                 record: str = 'full', inclusive: bool = False, device: int = 0):
+        """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial
+        states in one device launch: a closed_loop.ClosedLoopResult (theta, u, region, status, exit_step, stats).  See
+        closed_loop.simulate and DESIGN §3.15."""
+        from .closed_loop import simulate
+        return simulate(self, theta0, steps, A, B, inputs, c=c, disturbance=disturbance, seed=seed, stop_tol=stop_tol, locate=locate,
+                        record=record, inclusive=inclusive, device=device)
+
     # ---- verification without a QP solver: the KKT conditions of the program at theta ----------------------------------------
     def kkt_residuals(self, region: CriticalRegion, theta_point: numpy.ndarray) -> dict:
         """Largest violation of each optimality condition of the program at ``theta_point`` by the region's laws
