@@ -606,6 +606,42 @@ int mpc_locator_simulate(mpc_locator *loc, int64_t n, int32_t steps, const doubl
                          double tol, double stop_tol, int32_t flags, int64_t budget, double *theta, double *u, int32_t *region, int32_t *status,
                          int32_t *exit_step, mpc_sim_stats *stats);
 
+/* ---- vertex enumeration of a batch of polytopes (geometry.polytope_vertices, Solution.vertices) ------------------------ */
+/* mpc_region_vertices: the vertices and rays of every polytope {theta : E theta <= f}, one workgroup each (k_region_vertices,
+ * vertices.hpp: the double-description method on the homogenised cone {(theta, t) : f t - E theta >= 0, t >= 0}).
+ *   ef_rows   [rows][n_t + 1] = [f | E], CSR over polytopes by row_off[n_poly + 1] (row_off[0] = 0): what the locator is built from
+ *   tol       incidence: row r is tight at v when |f_r - e_r v| <= tol (1 + |f_r|); vertices within tol (1 + |v|_inf) of a vertex before
+ *             them in lexicographic order are merged (counted in stats->merges)
+ *   slab      generators per list of the first pass (<= 0: 256); a polytope whose list outgrows it is repeated with a 4x larger slab
+ *             while that is <= max_slab (<= 0: 2^24) and one polytope's slab fits the budget; then it stays MPC_VX_OVERFLOW
+ *   budget    device bytes of the slabs in flight (<= 0: 4 GiB)
+ *   v_cap, r_cap  in: the rows of vertices / incidence and of rays; out: the rows needed.  MPC_ERR_CAPACITY when they do not fit
+ *             (status, n_vert, n_ray and stats are filled, the arrays are not written).
+ * Outputs: status[p] (MPC_VX_*), n_vert[p], n_ray[p]; vertices [sum n_vert][n_t] polytope by polytope, each polytope's in
+ * lexicographic order; incidence [sum n_vert][4] 64-bit masks over the polytope's rows; rays [sum n_ray][n_t] (unit 2-norm,
+ * lexicographic order).  MPC_VX_UNBOUNDED polytopes return their vertices and rays; NOT_POINTED (rank E < n_t), EMPTY (no interior:
+ * empty or lower dimensional) and OVERFLOW return none.  Two runs give the same bits.
+ * Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16, <= 256 rows per polytope, finite rows, tol >= 0,
+ * 18 <= slab <= max_slab <= 2^24, a budget that holds one polytope's first slab. */
+#define MPC_VX_OK 0
+#define MPC_VX_UNBOUNDED 1
+#define MPC_VX_NOT_POINTED 2
+#define MPC_VX_EMPTY 3
+#define MPC_VX_OVERFLOW 4
+typedef struct mpc_vertex_stats {
+    int64_t generators;   /* generators made (initial ones included), over all passes */
+    int64_t max_list;     /* the longest intermediate generator list */
+    int64_t merges;       /* vertices merged into a neighbour within tol */
+    int64_t repeats;      /* polytopes repeated with a larger slab */
+    int64_t overflow;     /* polytopes left MPC_VX_OVERFLOW */
+    int64_t launches;     /* launches of k_region_vertices */
+    int64_t slab;         /* generators per list of the last pass */
+    float ms;             /* device milliseconds of k_region_vertices */
+} mpc_vertex_stats;
+int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol, int64_t slab,
+                        int64_t max_slab, int64_t budget, int64_t *v_cap, int64_t *r_cap, int32_t *status, int64_t *n_vert, int64_t *n_ray,
+                        double *vertices, uint64_t *incidence, double *rays, mpc_vertex_stats *stats);
+
 /* ---- merging regions with equal laws into convex unions (Solution.merge_regions) --------------------------------- */
 /* Regions are polytopes {theta : n.theta <= o} of unit rows: ef_rows [rows][n_t + 1] = [o | n] (|n| = 1 within 1e-6, finite), CSR over
  * regions by row_off[n_regions + 1] (row_off[0] = 0).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16,

@@ -17,6 +17,8 @@ MPC_OK, MPC_ERR_INVALID, MPC_ERR_HIP, MPC_ERR_CAPACITY, MPC_ERR_STATE = range(5)
 MPC_LOCATE_OVERLAPPING, MPC_LOCATE_INCLUSIVE, MPC_LOCATE_WALK, MPC_LOCATE_TREE = 1, 2, 4, 8   # flags of mpc_locator_query
 MPC_SIM_FINAL, MPC_SIM_KEY_SALT = 16, 0x636c6f6f   # flag of mpc_locator_simulate (record the final states only); its Philox key salt
 SIM_MAX_DIM, SIM_MAX_INPUTS, SIM_DEFAULT_BUDGET = 16, 16, 4 << 30   # limits of mpc_locator_simulate
+VX_OK, VX_UNBOUNDED, VX_NOT_POINTED, VX_EMPTY, VX_OVERFLOW = range(5)   # statuses of mpc_region_vertices
+VX_MAX_DIM, VX_MAX_ROWS, VX_DEFAULT_BUDGET, VX_DEFAULT_SLAB, VX_MAX_SLAB = 16, 256, 4 << 30, 256, 1 << 24   # its limits
 TREE_MAX_DIM, TREE_MAX_ROWS, TREE_MAX_DEPTH = 16, 256, 64   # limits of mpc_tree_build
 MPC_SOLVE_MANY_BASE = 128   # flag of mpc_solve_many_start
 MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, MPC_LEVEL_ONLY_BASE = 1, 4, 8, 16, 32   # flags of mpc_level_start / mpc_level_run_ex
@@ -124,6 +126,12 @@ class SimStats(ctypes.Structure):
     """mpc_sim_stats (include/mpcombi.h)"""
     _fields_ = [('traj_steps', ctypes.c_int64), ('crossings', ctypes.c_int64), ('fallbacks', ctypes.c_int64), ('mode', ctypes.c_int32),
                 ('ms', ctypes.c_float)]
+
+
+class VertexStats(ctypes.Structure):
+    """mpc_vertex_stats (include/mpcombi.h)"""
+    _fields_ = [('generators', ctypes.c_int64), ('max_list', ctypes.c_int64), ('merges', ctypes.c_int64), ('repeats', ctypes.c_int64),
+                ('overflow', ctypes.c_int64), ('launches', ctypes.c_int64), ('slab', ctypes.c_int64), ('ms', ctypes.c_float)]
 
 
 def load():
@@ -241,6 +249,9 @@ def load():
         'mpc_locator_simulate': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _dp, ctypes.c_int32, _ip, _dp, _dp, _dp, _dp, _dp,
                                                  _dp, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, _dp, _dp,
                                                  _ip, _ip, _ip, ctypes.POINTER(SimStats)]),
+        'mpc_region_vertices': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_double, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_int64, _lp, _lp, _ip, _lp, _lp, _dp, ctypes.POINTER(ctypes.c_uint64), _dp,
+                                                ctypes.POINTER(VertexStats)]),
         'mpc_merge_regions': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _ip, _lp,
                                              ctypes.POINTER(ctypes.c_float)]),
         'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
@@ -264,7 +275,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
-                    'mpc_merge_pairs', 'mpc_locator_simulate']
+                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1023,6 +1034,34 @@ def hit_and_run(row_off, ab_rows, start, chains: int, samples: int, n_steps: int
 
 
 hit_and_run.last_ms = 0.0
+
+
+def region_vertices(row_off, ef_rows, n_t: int, tol: float = 1e-9, slab: int = 0, max_slab: int = 0, budget: int = 0, device: int = 0):
+    """mpc_region_vertices: the vertices and rays of every polytope {theta : E theta <= f} of the stacked [f | E] rows (CSR by row_off).
+    Returns (status [P] int32, n_vert [P], n_ray [P], vertices [V, n_t], incidence [V, 4] uint64, rays [R, n_t], stats dict).  The
+    outputs are sized by a first guess; when they do not fit, the call is repeated once with the sizes the library reported."""
+    L = load()
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ef = _f64(numpy.asarray(ef_rows, dtype=numpy.float64).reshape(-1, int(n_t) + 1))
+    P = len(off) - 1
+    status, nv, nr = numpy.zeros(P, dtype=numpy.int32), numpy.zeros(P, dtype=numpy.int64), numpy.zeros(P, dtype=numpy.int64)
+    vcap, rcap = 16 * P + 64, 64
+    for _ in range(2):
+        vert, inc, rays = numpy.empty((vcap, n_t)), numpy.empty((vcap, 4), dtype=numpy.uint64), numpy.empty((rcap, n_t))
+        vc, rc_ = ctypes.c_int64(vcap), ctypes.c_int64(rcap)
+        st = VertexStats()
+        rc = L.mpc_region_vertices(int(device), int(n_t), P, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), float(tol), int(slab), int(max_slab),
+                                   int(budget), ctypes.byref(vc), ctypes.byref(rc_), status.ctypes.data_as(_ip), nv.ctypes.data_as(_lp),
+                                   nr.ctypes.data_as(_lp), vert.ctypes.data_as(_dp), inc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                   rays.ctypes.data_as(_dp), ctypes.byref(st))
+        if rc == MPC_ERR_CAPACITY:
+            vcap, rcap = int(vc.value), int(rc_.value)
+            continue
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_region_vertices failed ({rc}): {L.mpc_last_global_error().decode()}')
+        stats = {name: getattr(st, name) for name, _ in VertexStats._fields_}
+        return status, nv, nr, vert[:vc.value], inc[:vc.value], rays[:rc_.value], stats
+    raise MpcError('mpc_region_vertices: the outputs did not fit the sizes it reported')
 
 
 def _slice_rows(who, row_off, ef_rows, n, eps):

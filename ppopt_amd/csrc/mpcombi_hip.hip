@@ -29,6 +29,7 @@
 #include "locate.hpp"
 #include "tree.hpp"
 #include "closed_loop.hpp"
+#include "vertices.hpp"
 #include "merge.hpp"
 #include "graph.hpp"
 #include "qp.hpp"
@@ -5354,6 +5355,193 @@ extern "C" int mpc_locator_simulate(mpc_locator *L, int64_t n, int32_t steps, co
         stats->traj_steps = (int64_t)cnt[0]; stats->crossings = (int64_t)cnt[1]; stats->fallbacks = (int64_t)cnt[2];
         stats->mode = tree ? MPC_LOCATE_TREE : walk ? MPC_LOCATE_WALK : 0;
         stats->ms = ms;
+    }
+    return MPC_OK;
+}
+
+// ---- vertex enumeration of a batch of polytopes (vertices.hpp) ---------------------------------------------------------
+constexpr long long VX_DEFAULT_BUDGET = 4ll << 30, VX_DEFAULT_SLAB = 256, VX_MAX_SLAB = 1ll << 24;
+
+// device bytes of one polytope's slab: two lists of generators (y, Z), the products s and the two index lists
+template <int NT> static double vx_slab_bytes(long long cap) { return (double)cap * (2.0 * (NT + 1) * 8 + 2.0 * VX_MW * 8 + 8 + 2 * 4); }
+
+template <int NT>
+static hipError_t vx_run(int nt, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol, long long cap, long long max_slab,
+                         double budget, std::vector<int32_t> &status, std::vector<int64_t> &nv, std::vector<int64_t> &nr,
+                         std::vector<std::vector<double>> &hv, std::vector<std::vector<uint64_t>> &hz, std::vector<std::vector<double>> &hr,
+                         mpc_vertex_stats &stats) {
+    hipError_t e = hipSuccess;
+#define VX_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
+    const long long rows = row_off[n_poly];
+    DevBuf d_off, d_ef, d_poly, d_y, d_z, d_s, d_i, d_st, d_nv, d_nr, d_buf, d_cnt, d_vo, d_ro, d_ov, d_oz, d_or;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto cleanup = [&]() {
+        (void)hipDeviceSynchronize();
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        for (DevBuf *b : {&d_off, &d_ef, &d_poly, &d_y, &d_z, &d_s, &d_i, &d_st, &d_nv, &d_nr, &d_buf, &d_cnt, &d_vo, &d_ro, &d_ov, &d_oz, &d_or})
+            b->release();
+    };
+    struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{cleanup};
+    VX_TRY(hipEventCreate(&e0));
+    VX_TRY(hipEventCreate(&e1));
+    VX_TRY(d_off.ensure((size_t)(n_poly + 1) * 8, nullptr));
+    VX_TRY(d_ef.ensure(std::max<size_t>(8, (size_t)rows * (nt + 1) * 8), nullptr));
+    VX_TRY(hipMemcpy(d_off.p, row_off, (size_t)(n_poly + 1) * 8, hipMemcpyHostToDevice));
+    if (rows) VX_TRY(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (nt + 1) * 8, hipMemcpyHostToDevice));
+    std::vector<int32_t> pending(n_poly);
+    for (int64_t p = 0; p < n_poly; ++p) pending[p] = (int32_t)p;
+    for (;;) {
+        const double per = vx_slab_bytes<NT>(cap);
+        const long long chunk = std::max(1ll, std::min<long long>({(long long)pending.size(), (long long)(budget / per), 1ll << 16}));
+        std::vector<int32_t> over;
+        for (size_t start = 0; start < pending.size(); start += (size_t)chunk) {
+            const long long nq = std::min<long long>(chunk, (long long)(pending.size() - start));
+            VX_TRY(d_poly.ensure((size_t)nq * 4, nullptr));
+            VX_TRY(d_y.ensure((size_t)nq * 2 * cap * (NT + 1) * 8, nullptr));
+            VX_TRY(d_z.ensure((size_t)nq * 2 * cap * VX_MW * 8, nullptr));
+            VX_TRY(d_s.ensure((size_t)nq * cap * 8, nullptr));
+            VX_TRY(d_i.ensure((size_t)nq * 2 * cap * 4, nullptr));
+            for (DevBuf *b : {&d_st, &d_nv, &d_nr, &d_buf}) VX_TRY(b->ensure((size_t)nq * 4, nullptr));
+            VX_TRY(d_cnt.ensure((size_t)nq * 3 * 8, nullptr));
+            VX_TRY(hipMemcpy(d_poly.p, pending.data() + start, (size_t)nq * 4, hipMemcpyHostToDevice));
+            VxArgs a{};
+            a.nt = nt; a.n = nq; a.poly = d_poly.as<int32_t>(); a.row_off = d_off.as<long long>(); a.ef = d_ef.as<double>(); a.cap = cap;
+            a.slab_y = d_y.as<double>(); a.slab_z = d_z.as<unsigned long long>(); a.slab_s = d_s.as<double>(); a.slab_i = d_i.as<int32_t>();
+            a.tol = tol; a.status = d_st.as<int32_t>(); a.n_vert = d_nv.as<int32_t>(); a.n_ray = d_nr.as<int32_t>(); a.buf = d_buf.as<int32_t>();
+            a.counters = d_cnt.as<unsigned long long>();
+            VX_TRY(hipEventRecord(e0, nullptr));
+            hipLaunchKernelGGL((k_region_vertices<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, a);
+            VX_TRY(hipGetLastError());
+            VX_TRY(hipEventRecord(e1, nullptr));
+            std::vector<int32_t> st(nq), cv(nq), cr(nq), cb(nq);
+            std::vector<unsigned long long> cnt((size_t)nq * 3);
+            VX_TRY(hipMemcpy(st.data(), d_st.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+            VX_TRY(hipMemcpy(cv.data(), d_nv.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+            VX_TRY(hipMemcpy(cr.data(), d_nr.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+            VX_TRY(hipMemcpy(cnt.data(), d_cnt.p, (size_t)nq * 3 * 8, hipMemcpyDeviceToHost));
+            float ms = 0.0f;
+            VX_TRY(hipEventElapsedTime(&ms, e0, e1));
+            stats.ms += ms;
+            stats.launches += 1;
+            std::vector<long long> vo(nq), ro(nq);
+            long long tv = 0, tr = 0;
+            for (long long i = 0; i < nq; ++i) {
+                const int32_t p = pending[start + i];
+                stats.generators += (int64_t)cnt[i * 3 + 0];
+                stats.max_list = std::max<int64_t>(stats.max_list, (int64_t)cnt[i * 3 + 1]);
+                stats.merges += (int64_t)cnt[i * 3 + 2];
+                status[p] = st[i];
+                if (st[i] == VX_OVERFLOW) { over.push_back(p); cv[i] = cr[i] = 0; }
+                nv[p] = cv[i]; nr[p] = cr[i];
+                vo[i] = tv; ro[i] = tr;
+                tv += cv[i]; tr += cr[i];
+            }
+            if (tv + tr == 0) continue;
+            // pack this launch's results (the counts of overflowed polytopes are 0 on the device too)
+            VX_TRY(d_vo.ensure((size_t)nq * 8, nullptr));
+            VX_TRY(d_ro.ensure((size_t)nq * 8, nullptr));
+            VX_TRY(d_ov.ensure(std::max<size_t>(8, (size_t)tv * nt * 8), nullptr));
+            VX_TRY(d_oz.ensure(std::max<size_t>(8, (size_t)tv * VX_OUT_MW * 8), nullptr));
+            VX_TRY(d_or.ensure(std::max<size_t>(8, (size_t)tr * nt * 8), nullptr));
+            VX_TRY(hipMemcpy(d_vo.p, vo.data(), (size_t)nq * 8, hipMemcpyHostToDevice));
+            VX_TRY(hipMemcpy(d_ro.p, ro.data(), (size_t)nq * 8, hipMemcpyHostToDevice));
+            hipLaunchKernelGGL((k_vertices_gather<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, nt, cap, d_y.as<double>(),
+                               d_z.as<unsigned long long>(), d_nv.as<int32_t>(), d_nr.as<int32_t>(), d_buf.as<int32_t>(), d_vo.as<long long>(),
+                               d_ro.as<long long>(), d_ov.as<double>(), d_oz.as<unsigned long long>(), d_or.as<double>());
+            VX_TRY(hipGetLastError());
+            std::vector<double> ov((size_t)tv * nt), orr((size_t)tr * nt);
+            std::vector<uint64_t> oz((size_t)tv * VX_OUT_MW);
+            if (tv) {
+                VX_TRY(hipMemcpy(ov.data(), d_ov.p, ov.size() * 8, hipMemcpyDeviceToHost));
+                VX_TRY(hipMemcpy(oz.data(), d_oz.p, oz.size() * 8, hipMemcpyDeviceToHost));
+            }
+            if (tr) VX_TRY(hipMemcpy(orr.data(), d_or.p, orr.size() * 8, hipMemcpyDeviceToHost));
+            for (long long i = 0; i < nq; ++i) {
+                const int32_t p = pending[start + i];
+                hv[p].assign(ov.begin() + vo[i] * nt, ov.begin() + (vo[i] + cv[i]) * nt);
+                hz[p].assign(oz.begin() + vo[i] * VX_OUT_MW, oz.begin() + (vo[i] + cv[i]) * VX_OUT_MW);
+                hr[p].assign(orr.begin() + ro[i] * nt, orr.begin() + (ro[i] + cr[i]) * nt);
+            }
+        }
+        stats.slab = cap;
+        if (over.empty()) break;
+        // repeat only the overflowed polytopes with a four times larger slab, while one polytope's slab fits the budget
+        const long long next = cap * 4;
+        if (next > max_slab || vx_slab_bytes<NT>(next) > budget) break;
+        stats.repeats += (int64_t)over.size();
+        pending.swap(over);
+        cap = next;
+    }
+#undef VX_TRY
+    return hipSuccess;
+}
+
+extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol,
+                                   int64_t slab, int64_t max_slab, int64_t budget, int64_t *v_cap, int64_t *r_cap, int32_t *status,
+                                   int64_t *n_vert, int64_t *n_ray, double *vertices, uint64_t *incidence, double *rays,
+                                   mpc_vertex_stats *stats) {
+    const char *who = "mpc_region_vertices";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
+    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
+    if (!row_off || !v_cap || !r_cap) return bad("missing row_off, v_cap or r_cap");
+    if (row_off[0] != 0) return bad("row_off[0] must be 0");
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int64_t r = row_off[p + 1] - row_off[p];
+        if (r < 0) return bad("row_off decreases");
+        if (r > VX_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VX_MAX_ROWS));
+    }
+    const long long rows = row_off[n_poly];
+    if (rows && !ef_rows) return bad("missing ef_rows");
+    for (long long i = 0; i < rows * (n_t + 1); ++i)
+        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    const long long slab0 = slab > 0 ? slab : VX_DEFAULT_SLAB, smax = max_slab > 0 ? max_slab : VX_MAX_SLAB;
+    if (slab0 < 18 || slab0 > smax || smax > VX_MAX_SLAB) return bad("need 18 <= slab <= max_slab <= 2^24 generators");
+    const double cap_bytes = budget > 0 ? (double)budget : (double)VX_DEFAULT_BUDGET;
+    const int ntk = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;
+    const double per = ntk == 4 ? vx_slab_bytes<4>(slab0) : ntk == 8 ? vx_slab_bytes<8>(slab0) : vx_slab_bytes<16>(slab0);
+    if (per > cap_bytes)
+        return bad("the budget of " + std::to_string((long long)cap_bytes) + " device bytes is too small for one polytope's slab (" +
+                   std::to_string((long long)per) + " bytes)");
+    if (n_poly > 0 && (!status || !n_vert || !n_ray)) return bad("missing status, n_vert or n_ray");
+    if (n_poly == 0) { *v_cap = 0; *r_cap = 0; return MPC_OK; }
+    const int ndev = device_count_cached();
+    if (ndev < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
+    if (device < 0 || device >= ndev) return bad("device index out of range");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    std::vector<int32_t> st(n_poly, VX_OVERFLOW);
+    std::vector<int64_t> nv(n_poly, 0), nr(n_poly, 0);
+    std::vector<std::vector<double>> hv(n_poly), hr(n_poly);
+    std::vector<std::vector<uint64_t>> hz(n_poly);
+    mpc_vertex_stats s{};
+    hipError_t e;
+    if (ntk == 4) e = vx_run<4>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
+    else if (ntk == 8) e = vx_run<8>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
+    else e = vx_run<16>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
+    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    long long tv = 0, tr = 0;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        status[p] = st[p]; n_vert[p] = nv[p]; n_ray[p] = nr[p];
+        if (st[p] == VX_OVERFLOW) s.overflow += 1;
+        tv += nv[p]; tr += nr[p];
+    }
+    if (stats) *stats = s;
+    const bool fits = tv <= *v_cap && tr <= *r_cap;
+    *v_cap = tv; *r_cap = tr;
+    if (!fits) return fail(nullptr, MPC_ERR_CAPACITY, std::string(who) + ": the outputs need " + std::to_string(tv) + " vertices and " +
+                                                            std::to_string(tr) + " rays (returned in v_cap, r_cap)");
+    if ((tv && (!vertices || !incidence)) || (tr && !rays)) return bad("missing vertices, incidence or rays");
+    long long pv = 0, pr = 0;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        if (nv[p]) {
+            std::memcpy(vertices + pv * n_t, hv[p].data(), hv[p].size() * 8);
+            std::memcpy(incidence + pv * VX_OUT_MW, hz[p].data(), hz[p].size() * 8);
+        }
+        if (nr[p]) std::memcpy(rays + pr * n_t, hr[p].data(), hr[p].size() * 8);
+        pv += nv[p]; pr += nr[p];
     }
     return MPC_OK;
 }

@@ -230,6 +230,28 @@ class Solution:
             cache[1][key] = SearchTree.build(self, **kw)
         return cache[1][key]
 
+    def vertices(self, tol: float = 1e-9, device: int = 0):
+        """The V-representation of every region (geometry.vertices.RegionVertices: vertices, offsets, incidence, rays, status, stats),
+        enumerated on the device from the rows the locator holds; built once per locator and tol.  See DESIGN §3.16."""
+        from .geometry.vertices import vertices_of_rows
+        self.locator(device)
+        cache = getattr(self, '_vertex_sets', None)
+        if cache is None or cache[0] != self._locator_key:
+            cache = (self._locator_key, {})
+            self._vertex_sets = cache
+        if tol not in cache[1]:
+            ef, row_off, _ = self._stacked()
+            n_t = ef.shape[1] - 1
+            cache[1][tol] = vertices_of_rows(row_off, ef, n_t, tol=tol, device=device, who='Solution.vertices')
+        return cache[1][tol]
+
+    def certify_recursive_feasibility(self, A, B, inputs, c=None, disturbance=None, tol: float = 1e-7, device: int = 0):
+        """Whether the plant theta+ = A theta + B u + c (+ a box disturbance (lo, hi)) under this controller's law u = x*(theta)[inputs]
+        stays where the program is feasible, region by region: an invariance.FeasibilityCertificate.  See
+        invariance.certify_recursive_feasibility and DESIGN §3.16."""
+        from .invariance import certify_recursive_feasibility
+        return certify_recursive_feasibility(self, A, B, inputs, c=c, disturbance=disturbance, tol=tol, device=device)
+
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):
         """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial
