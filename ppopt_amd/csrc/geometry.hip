@@ -1,0 +1,1091 @@
+// geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
+// location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration and region merging.
+// None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, merge.hpp, simplex.hpp); the pools and the scaffold
+// of a one-shot call (OneShot, select_device) are host_common.hpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/mpcombi.h"
+#include "locate.hpp"
+#include "tree.hpp"
+#include "closed_loop.hpp"
+#include "vertices.hpp"
+#include "merge.hpp"
+#include "host_common.hpp"
+
+using namespace mpc;
+
+// the two arrays every batch of polytopes starts with: row_off [n + 1] and the rows [row_off[n]][width]
+struct RegionsOnDevice { DevBuf &off, &ef; };
+static RegionsOnDevice upload_regions(OneShot &s, int64_t n, const int64_t *row_off, const double *rows, int width) {
+    DevBuf &off = s.upload(row_off, (size_t)(n + 1) * 8);
+    return {off, s.upload(rows, (size_t)row_off[n] * width * 8)};
+}
+
+// f(std::integral_constant<int, W>) with the kernels' compile-time width of nt parameters: W = 4, 8 or 16
+template <class F> static decltype(auto) with_width(int nt, F &&f) {
+    if (nt <= 4) return f(std::integral_constant<int, 4>{});
+    if (nt <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
+}
+
+// ---- hit-and-run chains in a batch of polytopes (k_hit_and_run, locate.hpp) -----------------------------------------------
+template <int NT, bool L>
+static void hr_launch(dim3 g, size_t lds, int n, long long n_poly, long long chains, long long wpp, const DevBuf &off, const DevBuf &ab,
+                      const DevBuf &st0, uint32_t samples, uint32_t n_steps, uint32_t k0, uint32_t k1, DevBuf &out, DevBuf &status) {
+    hipLaunchKernelGGL((k_hit_and_run<NT, L>), g, dim3(HR_BLOCK), lds, nullptr, n, n_poly, chains, wpp, off.as<long long>(), ab.as<double>(),
+                       st0.as<double>(), samples, n_steps, k0, k1, out.as<double>(), status.as<int32_t>());
+}
+
+extern "C" int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const int64_t *row_off, const double *ab_rows, const double *start,
+                               int64_t chains, int64_t samples, int64_t n_steps, uint64_t seed, double *out, int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (n < 1 || n > 64) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: n must lie in 1..64");
+    if (n_poly < 0 || chains < 0 || samples < 1 || n_steps < 1) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: bad sizes");
+    if (samples >= (1ll << 32) || n_steps >= (1ll << 32) || (unsigned long long)samples * (unsigned long long)n_steps >= (1ull << 32))
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: samples * n_steps must stay below 2^32");
+    if (!row_off) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing row_off");
+    if (row_off[0] != 0) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: row_off[0] must be 0");
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int64_t r = row_off[p + 1] - row_off[p];
+        if (r < 0 || r > 256) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: a polytope has more than 256 rows (or row_off decreases)");
+    }
+    if (n_poly == 0 || chains == 0) return MPC_OK;
+    if ((row_off[n_poly] && !ab_rows) || !start || !out || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing array");
+    const long long wpp = (chains + 63) / 64;
+    if (n_poly > (1ll << 40) / wpp) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains");
+    const long long n_blocks = (n_poly * wpp + HR_BLOCK / 64 - 1) / (HR_BLOCK / 64);
+    if (n_blocks > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains for one launch");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t n_chain = (size_t)n_poly * chains, n_out = n_chain * samples * n;
+    const int nt = n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
+    const size_t lds = nt == 64 ? (size_t)64 * HR_BLOCK * sizeof(double) : 0;
+    if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_hit_and_run<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    OneShot s("mpc_hit_and_run", nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_poly, row_off, ab_rows, n + 1);
+    DevBuf &d_st0 = s.upload(start, (size_t)n_poly * n * 8), &d_out = s.buf(n_out * 8), &d_status = s.buf(n_chain * 4);
+    s.launch_timed([&] {
+        const dim3 g((unsigned)n_blocks);
+        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), sm = (uint32_t)samples, ns = (uint32_t)n_steps;
+        switch (nt) {
+            case 2: hr_launch<2, false>(g, 0, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 4: hr_launch<4, false>(g, 0, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 8: hr_launch<8, false>(g, 0, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 16: hr_launch<16, false>(g, 0, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            case 32: hr_launch<32, false>(g, 0, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+            default: hr_launch<64, true>(g, lds, n, n_poly, chains, wpp, d.off, d.ef, d_st0, sm, ns, k0, k1, d_out, d_status); break;
+        }
+    });
+    s.download(out, d_out, n_out * 8);
+    s.download(status, d_status, n_chain * 4);
+    s.elapsed(ms);
+    return s.finish();
+}
+
+// ---- slices of a batch of polytopes by a plane or a line (k_slice_polygons / k_slice_intervals, locate.hpp) ---------------------
+static int slice_check(const char *who, int32_t n, int64_t n_regions, const int64_t *row_off, double eps) {
+    char msg[160];
+    if (n < 1 || n > 64) { snprintf(msg, sizeof msg, "%s: n must lie in 1..64", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    if (n_regions < 0 || !row_off || row_off[0] != 0) { snprintf(msg, sizeof msg, "%s: bad n_regions or row_off", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    if (!(eps > 0.0 && eps < 1.0)) { snprintf(msg, sizeof msg, "%s: eps must lie in (0, 1)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    for (int64_t r = 0; r < n_regions; ++r) {
+        const int64_t k = row_off[r + 1] - row_off[r];
+        if (k < 0 || k > 256) { snprintf(msg, sizeof msg, "%s: a region has more than 256 rows (or row_off decreases)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    }
+    if (n_regions > 4ll * 0x7fffffffll) { snprintf(msg, sizeof msg, "%s: too many regions for one launch", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
+    return MPC_OK;
+}
+
+// one launch of a slice kernel with its inputs copied in and its outputs copied out; launch(d_in...) enqueues the kernel
+template <class Launch>
+static int slice_run(const char *who, int32_t device, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int32_t n,
+                     const std::vector<double> &param, std::initializer_list<std::pair<void *, size_t>> outs, float *ms, Launch launch) {
+    if (int rc = select_device(nullptr, device)) return rc;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n + 1);
+    DevBuf &d_param = s.upload(param.data(), param.size() * 8);
+    DevBuf *d_out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    { size_t q = 0; for (auto &o : outs) d_out[q++] = &s.buf(std::max<size_t>(8, o.second)); }
+    s.launch_timed([&] { launch(dim3((unsigned)((n_regions + SP_WAVES - 1) / SP_WAVES)), d.off.as<long long>(), d.ef.as<double>(), d_param.as<double>(), d_out); });
+    { size_t q = 0; for (auto &o : outs) s.download(o.first, *d_out[q++], o.second); }
+    s.elapsed(ms);
+    return s.finish();
+}
+
+extern "C" int mpc_slice_polygons(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                                  const double *U, const double *box, double eps, double *vert, int32_t *edge_row, int32_t *count, double *area,
+                                  int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (int rc = slice_check("mpc_slice_polygons", n, n_regions, row_off, eps)) return rc;
+    if (!theta0 || !U || !box) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing theta0, U or box");
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(box[k]) || !std::isfinite(box[k + 2]) || !(box[k] < box[k + 2]))
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: the box must be finite with lo < hi");
+    if (n_regions == 0) return MPC_OK;
+    const long long rows = row_off[n_regions], slots = rows + 4 * n_regions;
+    if ((rows && !ef_rows) || !vert || !edge_row || !count || !area || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing array");
+    // z is measured from the box centre c: plane[t] = (theta0 + U c, U[t][0], U[t][1])
+    const double cx = 0.5 * (box[0] + box[2]), cy = 0.5 * (box[1] + box[3]), hx = 0.5 * (box[2] - box[0]), hy = 0.5 * (box[3] - box[1]);
+    std::vector<double> plane(3 * (size_t)n);
+    for (int t = 0; t < n; ++t) {
+        plane[3 * t] = theta0[t] + U[2 * t] * cx + U[2 * t + 1] * cy;
+        plane[3 * t + 1] = U[2 * t];
+        plane[3 * t + 2] = U[2 * t + 1];
+    }
+    return slice_run("mpc_slice_polygons", device, n_regions, row_off, ef_rows, n, plane,
+                     {{vert, (size_t)slots * 16}, {edge_row, (size_t)slots * 4}, {count, (size_t)n_regions * 4}, {area, (size_t)n_regions * 8},
+                      {status, (size_t)n_regions * 4}}, ms,
+                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *const *o) {
+                         hipLaunchKernelGGL(k_slice_polygons, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, hx, hy, cx, cy, eps,
+                                            o[0]->as<double>(), o[1]->as<int32_t>(), o[2]->as<int32_t>(), o[3]->as<double>(), o[4]->as<int32_t>());
+                     });
+}
+
+extern "C" int mpc_slice_intervals(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
+                                   const double *u, double t_lo, double t_hi, double eps, double *interval, int32_t *status, float *ms) {
+    if (ms) *ms = 0.0f;
+    if (int rc = slice_check("mpc_slice_intervals", n, n_regions, row_off, eps)) return rc;
+    if (!theta0 || !u) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing theta0 or u");
+    if (!std::isfinite(t_lo) || !std::isfinite(t_hi) || !(t_lo < t_hi)) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: the range must be finite with t_lo < t_hi");
+    if (n_regions == 0) return MPC_OK;
+    if ((row_off[n_regions] && !ef_rows) || !interval || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing array");
+    std::vector<double> line(2 * (size_t)n);
+    for (int t = 0; t < n; ++t) { line[2 * t] = theta0[t]; line[2 * t + 1] = u[t]; }
+    return slice_run("mpc_slice_intervals", device, n_regions, row_off, ef_rows, n, line,
+                     {{interval, (size_t)n_regions * 16}, {status, (size_t)n_regions * 4}}, ms,
+                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *const *o) {
+                         hipLaunchKernelGGL(k_slice_intervals, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, t_lo, t_hi, eps,
+                                            o[0]->as<double>(), o[1]->as<int32_t>());
+                     });
+}
+
+struct mpc_locator {
+    int device = 0, n_x = 0, n_t = 0;
+    long long n_regions = 0, n_rows = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf row_off, row_region, row_end, ef, xlaw, Q, c, H, theta, region, x;
+    // adjacency for the walk (mpc_locator_set_adjacency): active-set masks in region order and sorted, facet kind / id per row
+    DevBuf masks, sorted_masks, sorted_region, row_info, theta2, region2;
+    int mask_words = 0, n_c = 0;
+    bool has_adj = false;
+    long long last_unresolved = 0;   // points of the last walk query that went to the list scan
+    bool hasQ = false, hasc = false, hasH = false;
+    std::vector<int64_t> h_row_off;  // host copy of row_off (limits of mpc_tree_build)
+    // search tree (mpc_tree_build / mpc_locator_set_tree): host arrays as attached, and their device copies
+    bool has_tree = false;
+    double tree_tol = 0.0;
+    int tree_planes = 0;
+    std::vector<double> h_planes, h_tau;
+    std::vector<int32_t> h_plane, h_child, h_items;
+    std::vector<int64_t> h_off;
+    DevBuf t_planes, t_plane, t_child, t_tau, t_off, t_items;
+};
+
+static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xlaw, const double *Q,
+                        const double *c, const double *H);
+extern "C" int mpc_locator_destroy(mpc_locator *L);
+
+// host -> device on the locator's stream into b, grown to max(8, bytes); nothing is copied when bytes == 0
+static hipError_t locator_upload(mpc_locator *L, DevBuf &b, const void *src, size_t bytes) {
+    hipError_t e = b.ensure(std::max<size_t>(bytes, 8), L->stream);
+    if (e != hipSuccess || !bytes) return e;
+    return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, L->stream);
+}
+
+extern "C" int mpc_locator_create(int32_t device, int32_t n_x, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows,
+                                  const double *xlaw, const double *Q, const double *c, const double *H, mpc_locator **out) {
+    if (!out || n_x < 1 || n_t < 1 || n_t > 16 || n_regions < 0 || (n_regions > 0 && (!row_off || !ef_rows || !xlaw)))
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_create: bad arguments (1 <= n_t <= 16)");
+    HIP_TRY(nullptr, hipSetDevice(device));
+    mpc_locator *L = new mpc_locator();
+    L->device = device; L->n_x = n_x; L->n_t = n_t; L->n_regions = n_regions;
+    const int rc_fill = locator_fill(L, n_regions, row_off, ef_rows, xlaw, Q, c, H);
+    if (rc_fill != MPC_OK) { (void)mpc_locator_destroy(L); return rc_fill; }   // one cleanup path: nothing leaks on failure
+    *out = L;
+    return MPC_OK;
+}
+
+static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xlaw, const double *Q,
+                        const double *c, const double *H) {
+    const int n_x = L->n_x, n_t = L->n_t;
+    HIP_TRY(nullptr, hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
+    HIP_TRY(nullptr, hipEventCreate(&L->e0));
+    HIP_TRY(nullptr, hipEventCreate(&L->e1));
+    const long long rows = n_regions ? row_off[n_regions] : 0;
+    L->n_rows = rows;
+    L->h_row_off.assign(row_off, row_off + (n_regions ? n_regions + 1 : 0));
+    if (!n_regions) L->h_row_off.assign(1, 0);
+    const long long zero = 0;
+    HIP_TRY(nullptr, locator_upload(L, L->row_off, n_regions ? (const void *)row_off : (const void *)&zero, (size_t)(n_regions + 1) * sizeof(int64_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->ef, ef_rows, (size_t)rows * (n_t + 1) * sizeof(double)));
+    std::vector<int32_t> rr((size_t)std::max<long long>(rows, 1)), re((size_t)std::max<long long>(rows, 1));
+    for (long long r = 0; r < n_regions; ++r)
+        for (long long i = row_off[r]; i < row_off[r + 1]; ++i) { rr[(size_t)i] = (int32_t)r; re[(size_t)i] = (int32_t)row_off[r + 1]; }
+    HIP_TRY(nullptr, locator_upload(L, L->row_region, rr.data(), (size_t)rows * sizeof(int32_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->row_end, re.data(), (size_t)rows * sizeof(int32_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->xlaw, xlaw, (size_t)n_regions * n_x * (n_t + 1) * sizeof(double)));
+    if (Q) { HIP_TRY(nullptr, locator_upload(L, L->Q, Q, (size_t)n_x * n_x * sizeof(double))); L->hasQ = true; }
+    if (c) { HIP_TRY(nullptr, locator_upload(L, L->c, c, (size_t)n_x * sizeof(double))); L->hasc = true; }
+    if (H) { HIP_TRY(nullptr, locator_upload(L, L->H, H, (size_t)n_x * n_t * sizeof(double))); L->hasH = true; }
+    HIP_TRY(nullptr, hipStreamSynchronize(L->stream));
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_set_adjacency(mpc_locator *L, int32_t mask_words, int32_t n_c, const uint64_t *masks, const int32_t *row_info) {
+    if (!L || !masks || !row_info || (mask_words != 2 && mask_words != 4) || n_c < 1 || n_c > 64 * mask_words) return MPC_ERR_INVALID;
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    const long long n = L->n_regions, rows = L->n_rows;
+    if (n <= 0) return MPC_OK;
+    const int mw = mask_words;
+    // the mask table sorted ascending (most significant word last), with the region each mask belongs to
+    std::vector<int32_t> order((size_t)n);
+    for (long long i = 0; i < n; ++i) order[(size_t)i] = (int32_t)i;
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        for (int j = mw - 1; j >= 0; --j) { const uint64_t va = masks[(size_t)a * mw + j], vb = masks[(size_t)b * mw + j]; if (va != vb) return va < vb; }
+        return a < b;
+    });
+    std::vector<uint64_t> sorted((size_t)n * mw);
+    for (long long i = 0; i < n; ++i) for (int j = 0; j < mw; ++j) sorted[(size_t)i * mw + j] = masks[(size_t)order[(size_t)i] * mw + j];
+    for (long long i = 1; i < n; ++i) {   // two regions with one active set: no unique neighbour, no walk
+        bool same = true;
+        for (int j = 0; j < mw; ++j) same = same && sorted[(size_t)i * mw + j] == sorted[(size_t)(i - 1) * mw + j];
+        if (same) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_set_adjacency: two regions share one active set");
+    }
+    hipStream_t st = L->stream;
+    HIP_TRY(nullptr, locator_upload(L, L->masks, masks, (size_t)n * mw * sizeof(uint64_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->sorted_masks, sorted.data(), (size_t)n * mw * sizeof(uint64_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->sorted_region, order.data(), (size_t)n * sizeof(int32_t)));
+    HIP_TRY(nullptr, locator_upload(L, L->row_info, row_info, (size_t)rows * sizeof(int32_t)));
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    L->mask_words = mw;
+    L->n_c = n_c;
+    L->has_adj = true;
+    return MPC_OK;
+}
+
+// the list scan of k_locate over m points
+static void locate_scan(mpc_locator *L, long long m, const double *theta, double tol, int32_t flags, long long *out) {
+    const double *Q = L->hasQ ? L->Q.as<double>() : nullptr, *c = L->hasc ? L->c.as<double>() : nullptr, *H = L->hasH ? L->H.as<double>() : nullptr;
+    with_width(L->n_t, [&](auto W) {
+        hipLaunchKernelGGL((k_locate<decltype(W)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, L->stream, m, L->n_t, L->n_x, L->n_regions, L->n_rows,
+                           L->row_region.as<int32_t>(), L->row_end.as<int32_t>(), L->ef.as<double>(), L->xlaw.as<double>(), Q, c, H, theta, tol,
+                           (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), out);
+    });
+}
+
+// Behind a tree descent or a walk: fetches region[], locates the points left open (-2) again by the list scan, scatters the
+// results into region[] and uploads it again for k_evaluate.  few_ok (the walk): up to 16,384 open points go to k_locate_few.
+static int rescan_open(mpc_locator *L, int64_t m, const double *theta, double tol, int32_t flags, bool few_ok, int64_t *region) {
+    hipStream_t st = L->stream;
+    const int nt = L->n_t;
+    HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    std::vector<long long> open;
+    for (long long p = 0; p < m; ++p) if (region[p] == -2) open.push_back(p);
+    L->last_unresolved = (long long)open.size();
+    if (open.empty()) return MPC_OK;
+    const long long mo = (long long)open.size();
+    std::vector<double> tho((size_t)mo * nt);
+    for (long long i = 0; i < mo; ++i) std::memcpy(&tho[(size_t)i * nt], theta + (size_t)open[(size_t)i] * nt, sizeof(double) * nt);
+    std::vector<long long> ro((size_t)mo);
+    HIP_TRY(nullptr, L->theta2.ensure((size_t)mo * nt * sizeof(double), st));
+    HIP_TRY(nullptr, L->region2.ensure((size_t)mo * sizeof(long long), st));
+    HIP_TRY(nullptr, hipMemcpyAsync(L->theta2.p, tho.data(), (size_t)mo * nt * sizeof(double), hipMemcpyHostToDevice, st));
+    if (few_ok && mo <= 16384) {
+        // few points: every (point, region) pair in parallel, first containing region by atomicMin
+        HIP_TRY(nullptr, hipMemsetAsync(L->region2.p, 0xff, (size_t)mo * sizeof(long long), st));   // = "none yet" (max u64)
+        const dim3 gf((unsigned)((L->n_regions + 255) / 256), (unsigned)mo);
+        with_width(nt, [&](auto W) {
+            hipLaunchKernelGGL((k_locate_few<decltype(W)::value>), gf, dim3(256), 0, st, mo, nt, L->n_regions, L->row_off.as<long long>(), L->ef.as<double>(),
+                               L->theta2.as<double>(), tol, L->region2.as<long long>());
+        });
+    } else {
+        locate_scan(L, mo, L->theta2.as<double>(), tol, flags, L->region2.as<long long>());
+    }
+    HIP_TRY(nullptr, hipGetLastError());
+    HIP_TRY(nullptr, hipMemcpyAsync(ro.data(), L->region2.p, (size_t)mo * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    for (long long i = 0; i < mo; ++i) region[open[(size_t)i]] = ro[(size_t)i];   // -1 (all ones) where no region contains the point
+    HIP_TRY(nullptr, hipMemcpyAsync(L->region.p, region, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, st));   // k_evaluate reads it
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta, double tol, int32_t flags, int64_t *region, double *x,
+                                 float *ms_locate) {
+    if (!L || m < 0 || (m > 0 && (!theta || !region))) return MPC_ERR_INVALID;
+    if (ms_locate) *ms_locate = 0.0f;
+    const bool tree = (flags & MPC_LOCATE_TREE) != 0;
+    if (tree && !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: MPC_LOCATE_TREE without an attached tree");
+    if (tree && !(tol <= L->tree_tol)) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: tol is larger than the tolerance the tree was built for");
+    if (m == 0) return MPC_OK;
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    hipStream_t st = L->stream;
+    const int nt = L->n_t, nx = L->n_x;
+    HIP_TRY(nullptr, L->theta.ensure((size_t)m * nt * sizeof(double), st));
+    HIP_TRY(nullptr, L->region.ensure((size_t)m * sizeof(long long), st));
+    HIP_TRY(nullptr, hipMemcpyAsync(L->theta.p, theta, (size_t)m * nt * sizeof(double), hipMemcpyHostToDevice, st));
+    const dim3 g((unsigned)((m + 255) / 256)), b(256);
+    HIP_TRY(nullptr, hipEventRecord(L->e0, st));
+    const bool walk = (flags & MPC_LOCATE_WALK) && L->has_adj && !(flags & (MPC_LOCATE_OVERLAPPING | MPC_LOCATE_INCLUSIVE)) && L->n_regions > 0 && nt <= 16;
+    if (tree) {
+        // descent of the attached tree; points whose band stack overflowed (-2) go to the list scan
+        const double *Q = L->hasQ ? L->Q.as<double>() : nullptr, *c = L->hasc ? L->c.as<double>() : nullptr, *H = L->hasH ? L->H.as<double>() : nullptr;
+        with_width(nt, [&](auto W) {
+            hipLaunchKernelGGL((k_locate_tree<decltype(W)::value>), g, b, 0, st, (long long)m, nt, nx, L->t_planes.as<double>(), L->t_plane.as<int32_t>(),
+                               L->t_child.as<int32_t>(), L->t_tau.as<double>(), L->t_off.as<long long>(), L->t_items.as<int32_t>(),
+                               L->row_off.as<long long>(), L->ef.as<double>(), L->xlaw.as<double>(), Q, c, H, L->theta.as<double>(), tol,
+                               (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), L->region.as<long long>());
+        });
+        HIP_TRY(nullptr, hipGetLastError());
+        if (int rc = rescan_open(L, m, theta, tol, flags, false, region)) return rc;
+        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
+    } else if (!walk) {
+        locate_scan(L, m, L->theta.as<double>(), tol, flags, L->region.as<long long>());
+        HIP_TRY(nullptr, hipGetLastError());
+        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
+        HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
+    } else {
+        // walk through adjacent regions; what the walk cannot resolve goes to the list scan
+        const int max_steps = 384;   // walks are tens of steps long; what is still open then (points outside the solution, mostly) goes to k_locate_few
+        with_width(nt, [&](auto W) {
+            auto launch = [&](auto MW) {
+                hipLaunchKernelGGL((k_locate_walk<decltype(W)::value, decltype(MW)::value>), g, b, 0, st, (long long)m, nt, L->n_regions, L->row_off.as<long long>(),
+                                   L->ef.as<double>(), L->row_info.as<int32_t>(), L->masks.as<unsigned long long>(), L->sorted_masks.as<unsigned long long>(),
+                                   L->sorted_region.as<int32_t>(), L->theta.as<double>(), tol, 0, max_steps, L->n_c, L->region.as<long long>());
+            };
+            if (L->mask_words == 2) launch(std::integral_constant<int, 2>{}); else launch(std::integral_constant<int, 4>{});
+        });
+        HIP_TRY(nullptr, hipGetLastError());
+        if (int rc = rescan_open(L, m, theta, tol, flags, true, region)) return rc;
+        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
+    }
+    if (x) {
+        HIP_TRY(nullptr, L->x.ensure((size_t)m * nx * sizeof(double), st));
+        const long long tot = (long long)m * nx;
+        hipLaunchKernelGGL(k_evaluate, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (long long)m, nt, nx, L->xlaw.as<double>(), L->theta.as<double>(),
+                           L->region.as<long long>(), L->x.as<double>());
+        HIP_TRY(nullptr, hipGetLastError());
+        HIP_TRY(nullptr, hipMemcpyAsync(x, L->x.p, (size_t)m * nx * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    if (ms_locate) HIP_TRY(nullptr, hipEventElapsedTime(ms_locate, L->e0, L->e1));
+    return MPC_OK;
+}
+
+// ---- search trees (tree.hpp) ------------------------------------------------------------------------------------
+constexpr long long TREE_DEFAULT_BUDGET = 4ll << 30, TREE_MAX_LEVEL_ITEMS = 1ll << 28;
+
+static int tree_attach(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane, const int32_t *node_child,
+                       const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
+    const int nr = L->n_t + 1;
+    const int64_t n_items = node_off[n_nodes];
+    L->has_tree = false;
+    L->h_planes.assign(planes, planes + (size_t)n_planes * nr);
+    L->h_plane.assign(node_plane, node_plane + n_nodes);
+    L->h_child.assign(node_child, node_child + 2 * n_nodes);
+    L->h_tau.assign(node_tau, node_tau + 2 * n_nodes);
+    L->h_off.assign(node_off, node_off + n_nodes + 1);
+    L->h_items.assign(items, items + n_items);
+    hipStream_t st = L->stream;
+    HIP_TRY(nullptr, locator_upload(L, L->t_planes, L->h_planes.data(), L->h_planes.size() * 8));
+    HIP_TRY(nullptr, locator_upload(L, L->t_plane, L->h_plane.data(), L->h_plane.size() * 4));
+    HIP_TRY(nullptr, locator_upload(L, L->t_child, L->h_child.data(), L->h_child.size() * 4));
+    HIP_TRY(nullptr, locator_upload(L, L->t_tau, L->h_tau.data(), L->h_tau.size() * 8));
+    HIP_TRY(nullptr, locator_upload(L, L->t_off, L->h_off.data(), L->h_off.size() * 8));
+    HIP_TRY(nullptr, locator_upload(L, L->t_items, L->h_items.data(), L->h_items.size() * 4));
+    HIP_TRY(nullptr, hipStreamSynchronize(st));
+    L->tree_planes = n_planes;
+    L->tree_tol = tol;
+    L->has_tree = true;
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_set_tree(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
+                                    const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
+    const char *who = "mpc_locator_set_tree";
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (!L) return bad("no locator");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
+    if (n_nodes < 1 || !node_plane || !node_child || !node_tau || !node_off) return bad("missing node arrays");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (node_off[0] != 0) return bad("node_off[0] must be 0");
+    const int nr = L->n_t + 1;
+    for (int64_t i = 0; i < (int64_t)n_planes * nr; ++i) if (!std::isfinite(planes[i])) return bad("planes must be finite");
+    for (int64_t k = 0; k < n_nodes; ++k) {
+        if (node_off[k + 1] < node_off[k]) return bad("node_off decreases");
+        const int32_t h = node_plane[k];
+        if (h < -1 || h >= n_planes) return bad("a node plane is out of range");
+        if (h >= 0) {
+            for (int q = 0; q < 2; ++q) {
+                const int32_t ch = node_child[2 * k + q];
+                if (ch <= k || ch >= n_nodes) return bad("a child index is not after its parent or out of range");
+                if (!(node_tau[2 * k + q] >= 0.0)) return bad("tau must be >= 0");
+            }
+        }
+    }
+    if (node_off[n_nodes] > 0 && !items) return bad("missing items");
+    for (int64_t k = 0; k < n_nodes; ++k)
+        for (int64_t i = node_off[k]; i < node_off[k + 1]; ++i) {
+            if (items[i] < 0 || items[i] >= L->n_regions) return bad("a leaf item is not a region index");
+            if (i > node_off[k] && items[i] < items[i - 1]) return bad("a leaf list is not ascending");
+        }
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    return tree_attach(L, n_planes, planes, n_nodes, node_plane, node_child, node_tau, node_off, items, tol);
+}
+
+extern "C" int mpc_locator_tree_size(mpc_locator *L, int64_t *n_nodes, int64_t *n_items, int32_t *n_planes, double *tol) {
+    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_tree_size: no tree attached");
+    if (n_nodes) *n_nodes = (int64_t)L->h_plane.size();
+    if (n_items) *n_items = (int64_t)L->h_items.size();
+    if (n_planes) *n_planes = L->tree_planes;
+    if (tol) *tol = L->tree_tol;
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_get_tree(mpc_locator *L, double *planes, int32_t *node_plane, int32_t *node_child, double *node_tau, int64_t *node_off,
+                                    int32_t *items) {
+    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_get_tree: no tree attached");
+    auto put = [](void *dst, const auto &v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+    put(planes, L->h_planes); put(node_plane, L->h_plane); put(node_child, L->h_child); put(node_tau, L->h_tau); put(node_off, L->h_off);
+    put(items, L->h_items);
+    return MPC_OK;
+}
+
+extern "C" int mpc_tree_build(mpc_locator *L, int32_t n_planes, const double *planes, const int64_t *cand_off, const int32_t *cand_plane, double tol,
+                              double band, int32_t leaf_size, int32_t max_depth, int64_t budget, mpc_tree_stats *stats) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const char *who = "mpc_tree_build";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!L) return bad("no locator");
+    const int nt = L->n_t, nr = nt + 1;
+    const long long R = L->n_regions;
+    if (nt < 1 || nt > TR_MAX_NT) return bad("n_t must lie in 1..16");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (!std::isfinite(band) || band < 0.0) return bad("band must be finite and >= 0");
+    if (leaf_size < 1) return bad("leaf_size must be >= 1");
+    if (max_depth < 1 || max_depth > 64) return bad("max_depth must lie in 1..64");
+    if ((cand_off == nullptr) != (cand_plane == nullptr)) return bad("cand_off and cand_plane go together");
+    int m_max = 0;
+    for (long long r = 0; r < R; ++r) {
+        const long long k = L->h_row_off[(size_t)r + 1] - L->h_row_off[(size_t)r];
+        if (k > TR_MAX_ROWS) return bad("a region has more than 256 rows");
+        m_max = std::max<int>(m_max, (int)k);
+    }
+    for (int h = 0; h < n_planes; ++h) {
+        double nn = 0.0;
+        for (int t = 0; t < nt; ++t) nn += planes[(size_t)h * nr + t] * planes[(size_t)h * nr + t];
+        if (!std::isfinite(planes[(size_t)h * nr + nt]) || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("planes must be finite with unit normals");
+    }
+    if (cand_off) {
+        if (cand_off[0] != 0) return bad("cand_off[0] must be 0");
+        for (long long r = 0; r < R; ++r) if (cand_off[r + 1] < cand_off[r]) return bad("cand_off decreases");
+        for (long long i = 0; i < cand_off[R]; ++i) if (cand_plane[i] < 0 || cand_plane[i] >= n_planes) return bad("a candidate plane is out of range");
+    }
+    const int hw = (n_planes + 63) / 64;
+    const long long limit = budget > 0 ? budget : TREE_DEFAULT_BUDGET;
+    const long long bitset_bytes = (cand_off ? 3 : 2) * (long long)R * hw * 8;
+    if (bitset_bytes > limit) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "the classification bitsets need %lld bytes, over the budget of %lld bytes", bitset_bytes, limit);
+        return bad(msg);
+    }
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    hipStream_t st = L->stream;
+    OneShot s(who, st, true);   // owns the buffers and the two events on every way out, the early returns of HIP_TRY included
+    if (!s.ok()) return s.finish();
+    DevBuf &d_planes = s.buf(), &d_plus = s.buf(), &d_minus = s.buf(), &d_owner = s.buf(), &d_xs = s.buf(), &d_empty = s.buf(), &d_cnt = s.buf(),
+           &d_items = s.buf(), &d_off = s.buf(), &d_part = s.buf(), &d_iplane = s.buf(), &d_side = s.buf(), &d_pairs = s.buf(), &d_nplane = s.buf(),
+           &d_tau = s.buf(), &d_er = s.buf(), &d_ep = s.buf();
+    float ms_classify = 0.0f, ms_split = 0.0f, ms_tau = 0.0f;
+    auto timed = [&](float &acc, auto &&launch) -> hipError_t {
+        hipError_t e = hipEventRecord(s.e0, st);
+        if (e != hipSuccess) return e;
+        launch();
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipEventRecord(s.e1, st)) != hipSuccess) return e;
+        if ((e = hipEventSynchronize(s.e1)) != hipSuccess) return e;
+        float ms = 0.0f;
+        if ((e = hipEventElapsedTime(&ms, s.e0, s.e1)) != hipSuccess) return e;
+        acc += ms;
+        return hipSuccess;
+    };
+    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(nullptr, locator_upload(L, d_cnt, cnt, sizeof cnt));
+    TreeClassifyArgs a{};
+    a.nt = nt; a.m_max = std::max(m_max, 1); a.n_planes = n_planes; a.hw = hw; a.n_regions = R;
+    a.row_off = L->row_off.as<long long>(); a.ef = L->ef.as<double>(); a.tol = tol; a.band = band;
+    a.counters = d_cnt.as<unsigned long long>();
+    const size_t lds = tr_lds_bytes(a.m_max, nt);
+    if (R > 0 && n_planes > 0) {
+        HIP_TRY(nullptr, locator_upload(L, d_planes, planes, (size_t)n_planes * nr * 8));
+        const size_t bits = (size_t)R * hw * 8;
+        HIP_TRY(nullptr, d_plus.ensure(bits, st)); HIP_TRY(nullptr, d_minus.ensure(bits, st));
+        HIP_TRY(nullptr, hipMemsetAsync(d_plus.p, 0, bits, st)); HIP_TRY(nullptr, hipMemsetAsync(d_minus.p, 0, bits, st));
+        HIP_TRY(nullptr, d_xs.ensure((size_t)R * nt * 8, st)); HIP_TRY(nullptr, d_empty.ensure((size_t)R * 4, st));
+        if (cand_off && cand_off[R] > 0) {
+            HIP_TRY(nullptr, d_owner.ensure(bits, st));
+            HIP_TRY(nullptr, hipMemsetAsync(d_owner.p, 0, bits, st));
+            std::vector<int32_t> er((size_t)cand_off[R]);
+            for (long long r = 0; r < R; ++r) for (long long i = cand_off[r]; i < cand_off[r + 1]; ++i) er[(size_t)i] = (int32_t)r;
+            HIP_TRY(nullptr, locator_upload(L, d_er, er.data(), er.size() * 4));
+            HIP_TRY(nullptr, locator_upload(L, d_ep, cand_plane, er.size() * 4));
+            const long long ne = cand_off[R];
+            hipLaunchKernelGGL(k_tree_owner, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, ne, hw, d_er.as<int32_t>(), d_ep.as<int32_t>(),
+                               d_owner.as<unsigned long long>());
+            HIP_TRY(nullptr, hipGetLastError());
+        }
+        a.planes = d_planes.as<double>(); a.plus = d_plus.as<unsigned long long>(); a.minus = d_minus.as<unsigned long long>();
+        a.xs = d_xs.as<double>(); a.empty = d_empty.as<int32_t>();
+        HIP_TRY(nullptr, timed(ms_classify, [&] { hipLaunchKernelGGL((k_tree_classify<0>), dim3((unsigned)R), dim3(64), lds, st, a); }));
+    }
+    const unsigned long long *owner = (cand_off && cand_off[R] > 0) ? d_owner.as<unsigned long long>() : nullptr;
+    // the level loop: host node records, device counts
+    struct Node { int32_t plane = -1, child[2] = {-1, -1}; double tau[2] = {0.0, 0.0}; int depth = 0; std::vector<int32_t> list; };
+    std::vector<Node> nodes(1);
+    nodes[0].list.resize((size_t)R);
+    for (long long r = 0; r < R; ++r) nodes[0].list[(size_t)r] = (int32_t)r;
+    std::vector<int> level{0};
+    long long tau_lps = 0;
+    while (!level.empty() && n_planes > 0) {
+        std::vector<int> work;
+        for (int k : level) if ((long long)nodes[k].list.size() > leaf_size && nodes[k].depth < max_depth) work.push_back(k);
+        if (work.empty()) break;
+        std::vector<long long> off(work.size() + 1, 0);
+        for (size_t w = 0; w < work.size(); ++w) off[w + 1] = off[w] + (long long)nodes[work[w]].list.size();
+        if (off.back() > TREE_MAX_LEVEL_ITEMS) return fail(nullptr, MPC_ERR_CAPACITY, "mpc_tree_build: a level holds more than 2^28 (node, region) entries");
+        std::vector<int32_t> items((size_t)off.back());
+        for (size_t w = 0; w < work.size(); ++w) std::copy(nodes[work[w]].list.begin(), nodes[work[w]].list.end(), items.begin() + off[w]);
+        HIP_TRY(nullptr, locator_upload(L, d_items, items.data(), items.size() * 4));
+        HIP_TRY(nullptr, locator_upload(L, d_off, off.data(), off.size() * 8));
+        const long long nw = (long long)work.size();
+        const long long target_chunks = std::max<long long>(1, 4096 / nw);
+        const int chunk_len = (int)std::max<long long>(TS_BLOCK, (((n_planes + target_chunks - 1) / target_chunks) + TS_BLOCK - 1) / TS_BLOCK * TS_BLOCK);
+        const int chunks = (n_planes + chunk_len - 1) / chunk_len;
+        HIP_TRY(nullptr, d_part.ensure((size_t)nw * chunks * sizeof(int4), st));
+        HIP_TRY(nullptr, timed(ms_split, [&] {
+            hipLaunchKernelGGL(k_tree_split, dim3((unsigned)nw, (unsigned)chunks), dim3(TS_BLOCK), 0, st, n_planes, hw, chunk_len, d_off.as<long long>(),
+                               d_items.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(), owner, d_part.as<int4>());
+        }));
+        std::vector<int4> part((size_t)nw * chunks);
+        HIP_TRY(nullptr, hipMemcpy(part.data(), d_part.p, part.size() * sizeof(int4), hipMemcpyDeviceToHost));
+        std::vector<int32_t> item_plane(items.size(), 0);
+        std::vector<int> inner;
+        for (long long w = 0; w < nw; ++w) {
+            int bmx = TS_NONE, bn0 = TS_NONE, bh = -1;
+            for (int c = 0; c < chunks; ++c) {
+                const int4 q = part[(size_t)(w * chunks + c)];
+                if (q.z < 0) continue;
+                if (bh < 0 || q.x < bmx || (q.x == bmx && (q.y < bn0 || (q.y == bn0 && q.z < bh)))) { bmx = q.x; bn0 = q.y; bh = q.z; }
+            }
+            Node &nd = nodes[work[(size_t)w]];
+            if (bh < 0 || bmx >= (int)nd.list.size()) continue;   // no plane makes progress: a leaf
+            nd.plane = bh;
+            inner.push_back((int)w);
+            std::fill(item_plane.begin() + off[w], item_plane.begin() + off[w + 1], bh);
+        }
+        if (inner.empty()) break;
+        HIP_TRY(nullptr, locator_upload(L, d_iplane, item_plane.data(), item_plane.size() * 4));
+        HIP_TRY(nullptr, d_side.ensure(items.size(), st));
+        HIP_TRY(nullptr, timed(ms_split, [&] {
+            hipLaunchKernelGGL(k_tree_partition, dim3((unsigned)((items.size() + 255) / 256)), dim3(256), 0, st, (long long)items.size(), hw,
+                               d_items.as<int32_t>(), d_iplane.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(),
+                               d_side.as<int8_t>());
+        }));
+        std::vector<int8_t> side(items.size());
+        HIP_TRY(nullptr, hipMemcpy(side.data(), d_side.p, side.size(), hipMemcpyDeviceToHost));
+        // children and the one-sided (node, region) pairs of tau
+        std::vector<int32_t> pairs, nplane;
+        std::vector<int> next;
+        for (size_t q = 0; q < inner.size(); ++q) {
+            const long long w = inner[q];
+            const int k = work[(size_t)w];
+            Node cp, cm;
+            cp.depth = cm.depth = nodes[k].depth + 1;
+            for (long long i = off[w]; i < off[w + 1]; ++i) {
+                const int32_t j = items[(size_t)i];
+                const int sd = side[(size_t)i];
+                if (sd != 2) cp.list.push_back(j);
+                if (sd != 1) cm.list.push_back(j);
+                if (sd) { pairs.push_back((int32_t)q); pairs.push_back(j); pairs.push_back(sd - 1); }
+            }
+            nplane.push_back(nodes[k].plane);
+            const int ip = (int)nodes.size();
+            nodes[k].child[0] = ip; nodes[k].child[1] = ip + 1;
+            nodes[k].list.clear(); nodes[k].list.shrink_to_fit();
+            nodes.push_back(std::move(cp)); nodes.push_back(std::move(cm));
+            next.push_back(ip); next.push_back(ip + 1);
+        }
+        const long long n_pairs = (long long)pairs.size() / 3;
+        std::vector<unsigned long long> tau(2 * inner.size(), 0ull);
+        if (n_pairs > 0) {
+            HIP_TRY(nullptr, locator_upload(L, d_pairs, pairs.data(), pairs.size() * 4));
+            HIP_TRY(nullptr, locator_upload(L, d_nplane, nplane.data(), nplane.size() * 4));
+            HIP_TRY(nullptr, locator_upload(L, d_tau, tau.data(), tau.size() * 8));
+            TreeClassifyArgs b = a;
+            b.n_pairs = n_pairs; b.pair = d_pairs.as<int32_t>(); b.node_plane = d_nplane.as<int32_t>(); b.tau = d_tau.as<unsigned long long>();
+            HIP_TRY(nullptr, timed(ms_tau, [&] { hipLaunchKernelGGL((k_tree_classify<1>), dim3((unsigned)n_pairs), dim3(64), lds, st, b); }));
+            HIP_TRY(nullptr, hipMemcpy(tau.data(), d_tau.p, tau.size() * 8, hipMemcpyDeviceToHost));
+            tau_lps += n_pairs;
+        }
+        for (size_t q = 0; q < inner.size(); ++q) {
+            Node &nd = nodes[work[(size_t)inner[q]]];
+            for (int sd = 0; sd < 2; ++sd) { double v; std::memcpy(&v, &tau[2 * q + sd], 8); nd.tau[sd] = v; }
+        }
+        level.swap(next);
+    }
+    HIP_TRY(nullptr, hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
+    // flatten
+    const int64_t N = (int64_t)nodes.size();
+    std::vector<int32_t> plane_v((size_t)N), child_v((size_t)(2 * N)), items_v;
+    std::vector<double> tau_v((size_t)(2 * N));
+    std::vector<int64_t> off_v((size_t)N + 1, 0);
+    int64_t n_leaves = 0, max_leaf = 0, depth = 0;
+    for (int64_t k = 0; k < N; ++k) {
+        const Node &nd = nodes[(size_t)k];
+        plane_v[(size_t)k] = nd.plane;
+        for (int q = 0; q < 2; ++q) { child_v[(size_t)(2 * k + q)] = nd.child[q]; tau_v[(size_t)(2 * k + q)] = nd.tau[q]; }
+        if (nd.plane < 0) {
+            items_v.insert(items_v.end(), nd.list.begin(), nd.list.end());
+            ++n_leaves;
+            max_leaf = std::max<int64_t>(max_leaf, (int64_t)nd.list.size());
+        }
+        off_v[(size_t)k + 1] = (int64_t)items_v.size();
+        depth = std::max<int64_t>(depth, nd.depth);
+    }
+    if (int rc = tree_attach(L, n_planes, planes, N, plane_v.data(), child_v.data(), tau_v.data(), off_v.data(), items_v.data(), tol)) return rc;
+    if (stats) {
+        stats->n_nodes = N; stats->n_leaves = n_leaves; stats->depth = depth; stats->max_leaf = max_leaf;
+        stats->leaf_items = (int64_t)items_v.size();
+        stats->mean_leaf = n_leaves ? (double)items_v.size() / (double)n_leaves : 0.0;
+        stats->pairs = (int64_t)cnt[0]; stats->box_pairs = (int64_t)cnt[1]; stats->lps = (int64_t)cnt[2]; stats->pivots = (int64_t)cnt[3];
+        stats->capped = (int64_t)cnt[4]; stats->tau_lps = tau_lps; stats->bitset_bytes = bitset_bytes;
+        stats->ms_classify = ms_classify; stats->ms_split = ms_split; stats->ms_tau = ms_tau;
+        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    }
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_destroy(mpc_locator *L) {
+    if (!L) return MPC_OK;
+    (void)hipSetDevice(L->device);
+    if (L->stream) (void)hipStreamSynchronize(L->stream);
+    for (DevBuf *b : {&L->row_off, &L->row_region, &L->row_end, &L->ef, &L->xlaw, &L->Q, &L->c, &L->H, &L->theta, &L->region, &L->x, &L->masks, &L->sorted_masks,
+                      &L->sorted_region, &L->row_info, &L->theta2, &L->region2, &L->t_planes, &L->t_plane, &L->t_child, &L->t_tau, &L->t_off,
+                      &L->t_items}) b->release();
+    if (L->e0) (void)hipEventDestroy(L->e0);
+    if (L->e1) (void)hipEventDestroy(L->e1);
+    if (L->stream) (void)hipStreamDestroy(L->stream);
+    delete L;
+    return MPC_OK;
+}
+
+// ---- closed-loop simulation (closed_loop.hpp) --------------------------------------------------------------------------
+constexpr long long SIM_DEFAULT_BUDGET = 4ll << 30;
+
+extern "C" int mpc_locator_simulate(mpc_locator *L, int64_t n, int32_t steps, const double *theta0, int32_t n_u, const int32_t *inputs,
+                                    const double *A, const double *B, const double *c, const double *w, const double *box_lo,
+                                    const double *box_hi, uint64_t seed, double tol, double stop_tol, int32_t flags, int64_t budget,
+                                    double *theta, double *u, int32_t *region, int32_t *status, int32_t *exit_step, mpc_sim_stats *stats) {
+    const char *who = "mpc_locator_simulate";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!L) return bad("no locator");
+    const int nt = L->n_t, nx = L->n_x;
+    const bool final_only = (flags & MPC_SIM_FINAL) != 0, tree = (flags & MPC_LOCATE_TREE) != 0, walk = (flags & MPC_LOCATE_WALK) != 0;
+    const bool overlapping = (flags & MPC_LOCATE_OVERLAPPING) != 0, inclusive = (flags & MPC_LOCATE_INCLUSIVE) != 0;
+    if (n < 0 || n > (1ll << 40) || steps < 1 || steps > (1 << 30)) return bad("n must lie in 0..2^40 and steps in 1..2^30");
+    if (nt < 1 || nt > 16) return bad("n_theta must lie in 1..16");
+    if (n_u < 1 || n_u > 16) return bad("n_u must lie in 1..16");
+    if (L->n_regions < 1) return bad("the locator holds no region");
+    if (n > 0 && (!theta0 || !theta || !status || !exit_step)) return bad("missing theta0, theta, status or exit_step");
+    if (n > 0 && !final_only && (!u || !region)) return bad("a full record needs u and region");
+    if (!inputs || !A || !B) return bad("missing inputs, A or B");
+    for (int i = 0; i < n_u; ++i)
+        if (inputs[i] < 0 || inputs[i] >= nx) return bad("input index " + std::to_string(inputs[i]) + " is out of range (0 <= inputs < n_x = " + std::to_string(nx) + ")");
+    auto finite = [](const double *v, long long k) { for (long long i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false; return true; };
+    if (!finite(A, (long long)nt * nt) || !finite(B, (long long)nt * n_u) || (c && !finite(c, nt))) return bad("A, B and c must be finite");
+    if (n > 0 && !finite(theta0, n * nt)) return bad("theta0 must be finite");
+    if (w && (box_lo || box_hi)) return bad("a disturbance array and a box exclude each other");
+    if ((box_lo == nullptr) != (box_hi == nullptr)) return bad("box_lo and box_hi go together");
+    if (box_lo)
+        for (int t = 0; t < nt; ++t)
+            if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] <= box_hi[t])) return bad("the box must be finite with lo <= hi");
+    if (w && n > 0 && !finite(w, n * (long long)steps * nt)) return bad("the disturbance must be finite");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (std::isnan(stop_tol)) return bad("stop_tol must not be NaN (< 0: off)");
+    if (tree && walk) return bad("MPC_LOCATE_TREE and MPC_LOCATE_WALK exclude each other");
+    if (tree && !L->has_tree) return bad("MPC_LOCATE_TREE without an attached tree");
+    if (tree && !(tol <= L->tree_tol)) return bad("tol is larger than the tolerance the tree was built for");
+    if (walk && (!L->has_adj || overlapping || inclusive)) return bad("MPC_LOCATE_WALK needs adjacency, and neither MPC_LOCATE_OVERLAPPING nor MPC_LOCATE_INCLUSIVE");
+    // device bytes of the record and the inputs (doubles: no overflow for any n, steps that pass above)
+    const double rec = final_only ? (double)n * nt * 8 : (double)n * ((double)(steps + 1) * nt * 8 + (double)steps * (n_u * 8 + 4));
+    const double bytes = rec + (double)n * nt * 8 + (w ? (double)n * steps * nt * 8 : 0.0);
+    const double cap = budget > 0 ? (double)budget : (double)SIM_DEFAULT_BUDGET;
+    if (bytes > cap)
+        return bad("the run needs " + std::to_string((long long)bytes) + " device bytes, more than the budget of " + std::to_string((long long)cap) +
+                   " (record the final states only, or run fewer trajectories at a time)");
+    if (n == 0) return MPC_OK;
+    HIP_TRY(nullptr, hipSetDevice(L->device));
+    hipStream_t st = L->stream;
+    const size_t n_th = (size_t)(final_only ? 1 : steps + 1) * n * nt, n_uu = final_only ? 0 : (size_t)steps * n * n_u, n_rg = final_only ? 0 : (size_t)steps * n;
+    // the plant in one block: A [nt][nt], B [nt][n_u], c [nt], lo [nt], hi [nt], then the inputs
+    std::vector<double> plant((size_t)nt * nt + (size_t)nt * n_u + 3 * (size_t)nt, 0.0);
+    std::memcpy(plant.data(), A, sizeof(double) * nt * nt);
+    std::memcpy(plant.data() + nt * nt, B, sizeof(double) * nt * n_u);
+    const size_t oc = (size_t)nt * nt + (size_t)nt * n_u, olo = oc + nt, ohi = olo + nt;
+    if (c) std::memcpy(plant.data() + oc, c, sizeof(double) * nt);
+    if (box_lo) { std::memcpy(plant.data() + olo, box_lo, sizeof(double) * nt); std::memcpy(plant.data() + ohi, box_hi, sizeof(double) * nt); }
+    unsigned long long cnt[3] = {0, 0, 0};
+    float ms = 0.0f;
+    OneShot s(who, st);
+    DevBuf &d_th0 = s.upload(theta0, (size_t)n * nt * 8);
+    DevBuf &d_w = w ? s.upload(w, (size_t)n * steps * nt * 8) : s.buf();
+    DevBuf &d_plant = s.upload(plant.data(), plant.size() * 8), &d_in = s.upload(inputs, (size_t)n_u * 4);
+    DevBuf &d_cnt = s.buf(3 * 8), &d_th = s.buf(n_th * 8), &d_u = s.buf(n_uu * 8), &d_rg = s.buf(n_rg * 4);
+    DevBuf &d_st = s.buf((size_t)n * 4), &d_ex = s.buf((size_t)n * 4);
+    s.fill(d_cnt, 0, 3 * 8);
+    if (!final_only) {   // what lies after a trajectory's end is never written: NaN (all bits set) and region -1
+        s.fill(d_th, 0xff, n_th * 8);
+        s.fill(d_u, 0xff, n_uu * 8);
+        s.fill(d_rg, 0xff, n_rg * 4);
+    }
+    const double *pl = d_plant.as<double>();
+    SimArgs a{};
+    a.n = n; a.steps = steps; a.nt = nt; a.nx = nx; a.nu = n_u;
+    a.n_regions = L->n_regions; a.n_rows = L->n_rows;
+    a.row_off = L->row_off.as<long long>(); a.row_region = L->row_region.as<int32_t>(); a.row_end = L->row_end.as<int32_t>();
+    a.ef = L->ef.as<double>(); a.xlaw = L->xlaw.as<double>();
+    a.Q = L->hasQ ? L->Q.as<double>() : nullptr; a.cvec = L->hasc ? L->c.as<double>() : nullptr; a.H = L->hasH ? L->H.as<double>() : nullptr;
+    a.tol = tol; a.overlapping = overlapping; a.inclusive = inclusive;
+    if (walk) {
+        a.row_info = L->row_info.as<int32_t>(); a.sorted_region = L->sorted_region.as<int32_t>();
+        a.masks = L->masks.as<unsigned long long>(); a.sorted_masks = L->sorted_masks.as<unsigned long long>();
+        a.n_c = L->n_c; a.max_walk = 384;   // the step limit of mpc_locator_query's walk
+    }
+    if (tree) {
+        a.planes = L->t_planes.as<double>(); a.node_tau = L->t_tau.as<double>(); a.node_plane = L->t_plane.as<int32_t>();
+        a.node_child = L->t_child.as<int32_t>(); a.items = L->t_items.as<int32_t>(); a.node_off = L->t_off.as<long long>();
+    }
+    a.theta0 = d_th0.as<double>(); a.inputs = d_in.as<int32_t>();
+    a.A = pl; a.B = pl + nt * nt; a.c = c ? pl + oc : nullptr; a.w = w ? d_w.as<double>() : nullptr;
+    a.lo = box_lo ? pl + olo : nullptr; a.hi = box_lo ? pl + ohi : nullptr;
+    a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32) ^ MPC_SIM_KEY_SALT;
+    a.stop_tol = stop_tol; a.final_only = final_only;
+    a.theta = d_th.as<double>(); a.u = final_only ? nullptr : d_u.as<double>(); a.region = final_only ? nullptr : d_rg.as<int32_t>();
+    a.status = d_st.as<int32_t>(); a.exit_step = d_ex.as<int32_t>(); a.counters = d_cnt.as<unsigned long long>();
+    const dim3 g((unsigned)((n + SIM_BLOCK - 1) / SIM_BLOCK)), b(SIM_BLOCK);
+    // k_simulate<width of theta, width of u (4 | 16), mode>
+    auto launch = [&](auto MODE) {
+        with_width(nt, [&](auto W) {
+            if (n_u <= 4) hipLaunchKernelGGL((k_simulate<decltype(W)::value, 4, decltype(MODE)::value>), g, b, 0, st, a);
+            else hipLaunchKernelGGL((k_simulate<decltype(W)::value, 16, decltype(MODE)::value>), g, b, 0, st, a);
+        });
+    };
+    if (s.ok()) s.chk(hipEventRecord(L->e0, st));
+    s.launch([&] {
+        if (tree) launch(std::integral_constant<int, SIM_TREE>{});
+        else if (walk && L->mask_words == 2) launch(std::integral_constant<int, SIM_WALK2>{});
+        else if (walk) launch(std::integral_constant<int, SIM_WALK4>{});
+        else launch(std::integral_constant<int, SIM_SCAN>{});
+    });
+    if (s.ok()) s.chk(hipEventRecord(L->e1, st));
+    s.download(theta, d_th, n_th * 8);
+    s.download(u, d_u, n_uu * 8);        // nothing when only the final states are recorded
+    s.download(region, d_rg, n_rg * 4);
+    s.download(status, d_st, (size_t)n * 4);
+    s.download(exit_step, d_ex, (size_t)n * 4);
+    s.download(cnt, d_cnt, 3 * 8);
+    s.sync();   // the call's only wait: finish() does not repeat it
+    if (s.ok()) s.chk(hipEventElapsedTime(&ms, L->e0, L->e1));
+    if (int rc = s.finish()) return rc;
+    if (stats) {
+        stats->traj_steps = (int64_t)cnt[0]; stats->crossings = (int64_t)cnt[1]; stats->fallbacks = (int64_t)cnt[2];
+        stats->mode = tree ? MPC_LOCATE_TREE : walk ? MPC_LOCATE_WALK : 0;
+        stats->ms = ms;
+    }
+    return MPC_OK;
+}
+
+// ---- vertex enumeration of a batch of polytopes (vertices.hpp) ---------------------------------------------------------
+constexpr long long VX_DEFAULT_BUDGET = 4ll << 30, VX_DEFAULT_SLAB = 256, VX_MAX_SLAB = 1ll << 24;
+
+// device bytes of one polytope's slab: two lists of generators (y, Z), the products s and the two index lists
+template <int NT> static double vx_slab_bytes(long long cap) { return (double)cap * (2.0 * (NT + 1) * 8 + 2.0 * VX_MW * 8 + 8 + 2 * 4); }
+
+template <int NT>
+static int vx_run(const char *who, int nt, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol, long long cap, long long max_slab,
+                  double budget, std::vector<int32_t> &status, std::vector<int64_t> &nv, std::vector<int64_t> &nr,
+                  std::vector<std::vector<double>> &hv, std::vector<std::vector<uint64_t>> &hz, std::vector<std::vector<double>> &hr,
+                  mpc_vertex_stats &stats) {
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_poly, row_off, ef_rows, nt + 1);
+    DevBuf &d_poly = s.buf(), &d_y = s.buf(), &d_z = s.buf(), &d_s = s.buf(), &d_i = s.buf(), &d_st = s.buf(), &d_nv = s.buf(), &d_nr = s.buf(),
+           &d_buf = s.buf(), &d_cnt = s.buf(), &d_vo = s.buf(), &d_ro = s.buf(), &d_ov = s.buf(), &d_oz = s.buf(), &d_or = s.buf();
+    std::vector<int32_t> pending(n_poly);
+    for (int64_t p = 0; p < n_poly; ++p) pending[p] = (int32_t)p;
+    for (;;) {
+        const double per = vx_slab_bytes<NT>(cap);
+        const long long chunk = std::max(1ll, std::min<long long>({(long long)pending.size(), (long long)(budget / per), 1ll << 16}));
+        std::vector<int32_t> over;
+        for (size_t start = 0; start < pending.size(); start += (size_t)chunk) {
+            const long long nq = std::min<long long>(chunk, (long long)(pending.size() - start));
+            s.upload(d_poly, pending.data() + start, (size_t)nq * 4);
+            s.ensure(d_y, (size_t)nq * 2 * cap * (NT + 1) * 8);
+            s.ensure(d_z, (size_t)nq * 2 * cap * VX_MW * 8);
+            s.ensure(d_s, (size_t)nq * cap * 8);
+            s.ensure(d_i, (size_t)nq * 2 * cap * 4);
+            for (DevBuf *b : {&d_st, &d_nv, &d_nr, &d_buf}) s.ensure(*b, (size_t)nq * 4);
+            s.ensure(d_cnt, (size_t)nq * 3 * 8);
+            VxArgs a{};
+            a.nt = nt; a.n = nq; a.poly = d_poly.as<int32_t>(); a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cap = cap;
+            a.slab_y = d_y.as<double>(); a.slab_z = d_z.as<unsigned long long>(); a.slab_s = d_s.as<double>(); a.slab_i = d_i.as<int32_t>();
+            a.tol = tol; a.status = d_st.as<int32_t>(); a.n_vert = d_nv.as<int32_t>(); a.n_ray = d_nr.as<int32_t>(); a.buf = d_buf.as<int32_t>();
+            a.counters = d_cnt.as<unsigned long long>();
+            s.launch_timed([&] { hipLaunchKernelGGL((k_region_vertices<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, a); });
+            std::vector<int32_t> st(nq), cv(nq), cr(nq), cb(nq);
+            std::vector<unsigned long long> cnt((size_t)nq * 3);
+            s.download(st.data(), d_st, (size_t)nq * 4);
+            s.download(cv.data(), d_nv, (size_t)nq * 4);
+            s.download(cr.data(), d_nr, (size_t)nq * 4);
+            s.download(cnt.data(), d_cnt, (size_t)nq * 3 * 8);
+            float ms = 0.0f;
+            s.elapsed(&ms);
+            if (!s.ok()) return s.finish();
+            stats.ms += ms;
+            stats.launches += 1;
+            std::vector<long long> vo(nq), ro(nq);
+            long long tv = 0, tr = 0;
+            for (long long i = 0; i < nq; ++i) {
+                const int32_t p = pending[start + i];
+                stats.generators += (int64_t)cnt[i * 3 + 0];
+                stats.max_list = std::max<int64_t>(stats.max_list, (int64_t)cnt[i * 3 + 1]);
+                stats.merges += (int64_t)cnt[i * 3 + 2];
+                status[p] = st[i];
+                if (st[i] == VX_OVERFLOW) { over.push_back(p); cv[i] = cr[i] = 0; }
+                nv[p] = cv[i]; nr[p] = cr[i];
+                vo[i] = tv; ro[i] = tr;
+                tv += cv[i]; tr += cr[i];
+            }
+            if (tv + tr == 0) continue;
+            // pack this launch's results (the counts of overflowed polytopes are 0 on the device too)
+            s.upload(d_vo, vo.data(), (size_t)nq * 8);
+            s.upload(d_ro, ro.data(), (size_t)nq * 8);
+            s.ensure(d_ov, std::max<size_t>(8, (size_t)tv * nt * 8));
+            s.ensure(d_oz, std::max<size_t>(8, (size_t)tv * VX_OUT_MW * 8));
+            s.ensure(d_or, std::max<size_t>(8, (size_t)tr * nt * 8));
+            s.launch([&] {
+                hipLaunchKernelGGL((k_vertices_gather<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, nt, cap, d_y.as<double>(),
+                                   d_z.as<unsigned long long>(), d_nv.as<int32_t>(), d_nr.as<int32_t>(), d_buf.as<int32_t>(), d_vo.as<long long>(),
+                                   d_ro.as<long long>(), d_ov.as<double>(), d_oz.as<unsigned long long>(), d_or.as<double>());
+            });
+            std::vector<double> ov((size_t)tv * nt), orr((size_t)tr * nt);
+            std::vector<uint64_t> oz((size_t)tv * VX_OUT_MW);
+            s.download(ov.data(), d_ov, ov.size() * 8);
+            s.download(oz.data(), d_oz, oz.size() * 8);
+            s.download(orr.data(), d_or, orr.size() * 8);
+            if (!s.ok()) return s.finish();
+            for (long long i = 0; i < nq; ++i) {
+                const int32_t p = pending[start + i];
+                hv[p].assign(ov.begin() + vo[i] * nt, ov.begin() + (vo[i] + cv[i]) * nt);
+                hz[p].assign(oz.begin() + vo[i] * VX_OUT_MW, oz.begin() + (vo[i] + cv[i]) * VX_OUT_MW);
+                hr[p].assign(orr.begin() + ro[i] * nt, orr.begin() + (ro[i] + cr[i]) * nt);
+            }
+        }
+        stats.slab = cap;
+        if (over.empty()) break;
+        // repeat only the overflowed polytopes with a four times larger slab, while one polytope's slab fits the budget
+        const long long next = cap * 4;
+        if (next > max_slab || vx_slab_bytes<NT>(next) > budget) break;
+        stats.repeats += (int64_t)over.size();
+        pending.swap(over);
+        cap = next;
+    }
+    return s.finish();
+}
+
+extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol,
+                                   int64_t slab, int64_t max_slab, int64_t budget, int64_t *v_cap, int64_t *r_cap, int32_t *status,
+                                   int64_t *n_vert, int64_t *n_ray, double *vertices, uint64_t *incidence, double *rays,
+                                   mpc_vertex_stats *stats) {
+    const char *who = "mpc_region_vertices";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
+    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
+    if (!row_off || !v_cap || !r_cap) return bad("missing row_off, v_cap or r_cap");
+    if (row_off[0] != 0) return bad("row_off[0] must be 0");
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int64_t r = row_off[p + 1] - row_off[p];
+        if (r < 0) return bad("row_off decreases");
+        if (r > VX_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VX_MAX_ROWS));
+    }
+    const long long rows = row_off[n_poly];
+    if (rows && !ef_rows) return bad("missing ef_rows");
+    for (long long i = 0; i < rows * (n_t + 1); ++i)
+        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    const long long slab0 = slab > 0 ? slab : VX_DEFAULT_SLAB, smax = max_slab > 0 ? max_slab : VX_MAX_SLAB;
+    if (slab0 < 18 || slab0 > smax || smax > VX_MAX_SLAB) return bad("need 18 <= slab <= max_slab <= 2^24 generators");
+    const double cap_bytes = budget > 0 ? (double)budget : (double)VX_DEFAULT_BUDGET;
+    const double per = with_width(n_t, [&](auto W) { return vx_slab_bytes<decltype(W)::value>(slab0); });
+    if (per > cap_bytes)
+        return bad("the budget of " + std::to_string((long long)cap_bytes) + " device bytes is too small for one polytope's slab (" +
+                   std::to_string((long long)per) + " bytes)");
+    if (n_poly > 0 && (!status || !n_vert || !n_ray)) return bad("missing status, n_vert or n_ray");
+    if (n_poly == 0) { *v_cap = 0; *r_cap = 0; return MPC_OK; }
+    if (int rc = select_device(who, device)) return rc;
+    std::vector<int32_t> st(n_poly, VX_OVERFLOW);
+    std::vector<int64_t> nv(n_poly, 0), nr(n_poly, 0);
+    std::vector<std::vector<double>> hv(n_poly), hr(n_poly);
+    std::vector<std::vector<uint64_t>> hz(n_poly);
+    mpc_vertex_stats s{};
+    if (int rc = with_width(n_t, [&](auto W) {
+            return vx_run<decltype(W)::value>(who, n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
+        })) return rc;
+    long long tv = 0, tr = 0;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        status[p] = st[p]; n_vert[p] = nv[p]; n_ray[p] = nr[p];
+        if (st[p] == VX_OVERFLOW) s.overflow += 1;
+        tv += nv[p]; tr += nr[p];
+    }
+    if (stats) *stats = s;
+    const bool fits = tv <= *v_cap && tr <= *r_cap;
+    *v_cap = tv; *r_cap = tr;
+    if (!fits) return fail(nullptr, MPC_ERR_CAPACITY, std::string(who) + ": the outputs need " + std::to_string(tv) + " vertices and " +
+                                                            std::to_string(tr) + " rays (returned in v_cap, r_cap)");
+    if ((tv && (!vertices || !incidence)) || (tr && !rays)) return bad("missing vertices, incidence or rays");
+    long long pv = 0, pr = 0;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        if (nv[p]) {
+            std::memcpy(vertices + pv * n_t, hv[p].data(), hv[p].size() * 8);
+            std::memcpy(incidence + pv * VX_OUT_MW, hz[p].data(), hz[p].size() * 8);
+        }
+        if (nr[p]) std::memcpy(rays + pr * n_t, hr[p].data(), hr[p].size() * 8);
+        pv += nv[p]; pr += nr[p];
+    }
+    return MPC_OK;
+}
+
+// ---- merging regions with equal laws (merge.hpp) ---------------------------------------------------------------------
+static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (n_t < 1 || n_t > TR_MAX_NT) return bad("n_t must lie in 1..16");
+    if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad("bad region count or missing row_off");
+    if (n_regions > 0x7fffffffll) return bad("too many regions for one launch");
+    if (n_regions > 0 && row_off[0] != 0) return bad("row_off[0] must be 0");
+    *m_max = 1;
+    for (int64_t r = 0; r < n_regions; ++r) {
+        const int64_t k = row_off[r + 1] - row_off[r];
+        if (k < 1 || k > MG_MAX_ROWS) return bad("every region needs 1..256 rows");
+        *m_max = std::max<int>(*m_max, (int)k);
+    }
+    const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
+    if (rows > 0 && !ef_rows) return bad("missing ef_rows");
+    for (int64_t i = 0; i < rows; ++i) {
+        const double *row = ef_rows + i * (n_t + 1);
+        double nn = 0.0;
+        bool finite = std::isfinite(row[0]);
+        for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
+        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("rows must be finite with unit normals");
+    }
+    return MPC_OK;
+}
+
+extern "C" int mpc_merge_regions(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *xs,
+                                 double *box, int32_t *status, int64_t *stats, float *ms) {
+    const char *who = "mpc_merge_regions";
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (n_regions == 0) return MPC_OK;
+    if (!xs || !box || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_regions: missing output array");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(m_max, n_t);
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_xs = s.buf((size_t)n_regions * n_t * 8), &d_box = s.buf((size_t)n_regions * 2 * n_t * 8), &d_st = s.buf((size_t)n_regions * 4);
+    DevBuf &d_cnt = s.buf(3 * 8);
+    s.fill(d_cnt, 0, 3 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_regions), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        hipLaunchKernelGGL(k_merge_regions, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
+                           d.off.as<long long>(), d.ef.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_st.as<int32_t>(),
+                           d_cnt.as<unsigned long long>());
+    });
+    s.download(xs, d_xs, (size_t)n_regions * n_t * 8);
+    s.download(box, d_box, (size_t)n_regions * 2 * n_t * 8);
+    s.download(status, d_st, (size_t)n_regions * 4);
+    unsigned long long cnt[3] = {0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
+                               const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
+                               uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms) {
+    const char *who = "mpc_merge_pairs";
+    if (stats) for (int i = 0; i < 7; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: tol must be finite and >= 0");
+    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (n_pairs == 0) return MPC_OK;
+    if (!xs || !box || !pair_a || !pair_b || !env_a || !env_b || !verdict || !t_max)
+        return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: missing array");
+    int pair_rows = 2;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t p = pair_a[k], q = pair_b[k];
+        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: a pair names a region out of range, or the same region twice");
+        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q] + 2));
+    }
+    for (int64_t i = 0; i < n_regions * n_t; ++i)
+        if (std::isnan(xs[i]) || std::isinf(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: xs must be finite");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const int lds_rows = std::max(pair_rows, m_max);
+    const size_t lds = tr_lds_bytes(lds_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_env adds 64)
+    const size_t np = (size_t)n_pairs, words = np * MG_WORDS * 8;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_xs = s.upload(xs, (size_t)n_regions * n_t * 8), &d_box = s.upload(box, (size_t)n_regions * 2 * n_t * 8);
+    DevBuf &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
+    DevBuf &d_ea = s.buf(words), &d_eb = s.buf(words), &d_v = s.buf(np * 4), &d_t = s.buf(np * 8), &d_cnt = s.buf(7 * 8);
+    s.fill(d_cnt, 0, 7 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        MergePairArgs a{};
+        a.nt = n_t; a.m_max = lds_rows; a.n_pairs = n_pairs;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>(); a.box = d_box.as<double>();
+        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+        a.env_a = d_ea.as<unsigned long long>(); a.env_b = d_eb.as<unsigned long long>(); a.verdict = d_v.as<int32_t>(); a.t_max = d_t.as<double>();
+        a.counters = d_cnt.as<unsigned long long>();
+        hipLaunchKernelGGL(k_merge_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
+    });
+    s.download(env_a, d_ea, words);
+    s.download(env_b, d_eb, words);
+    s.download(verdict, d_v, np * 4);
+    s.download(t_max, d_t, np * 8);
+    unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 7; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}

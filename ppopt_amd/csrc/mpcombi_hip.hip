@@ -1,6 +1,9 @@
-// mpcombi_hip.hip -- C ABI (include/mpcombi.h) over the gfx950 kernels in kernels.hpp.
+// mpcombi_hip.hip -- the level engine behind the C ABI (include/mpcombi.h): mpc_handle and everything that needs it, over the
+// gfx950 kernels in kernels.hpp / kernels2.hpp, plus the batched LP / QP / MIQP plugs.  The stateless geometry entry points
+// (hit-and-run, slices, point location, search trees, closed loop, vertices, merging) are geometry.hip.
 //
-// Build:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared mpcombi_hip.hip -o libmpcombi_hip.so
+// Build:  one object per translation unit (this file, geometry.hip, batch_level.hip, setup_mfma.hip), linked into
+//         libmpcombi_hip.so:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c <unit>.hip   (__graft_entry__.build)
 //
 // Host side of the hot path: owns the device-resident program blocks, the frontier (to_check), the pruned list
 // (murder_list) and the per-level result buffers; launches the kernels on one HIP stream and times them with HIP
@@ -26,24 +29,23 @@
 #include "../../include/mpcombi.h"
 #include "kernels.hpp"
 #include "kernels2.hpp"
-#include "locate.hpp"
-#include "tree.hpp"
-#include "closed_loop.hpp"
-#include "vertices.hpp"
-#include "merge.hpp"
 #include "graph.hpp"
 #include "qp.hpp"
 #include <memory>
 
 #include "batch_level.hpp"
 #include "setup_mfma.hpp"
+#include "host_common.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
 
 using namespace mpc;
 
 namespace {
-
 thread_local std::string g_error;
+}
+
+// The one definition of what host_common.hpp declares: every translation unit of the library shares these pools.
+namespace mpc {
 
 // ---- process-wide recycling of device blocks, pinned host blocks, streams and events -----------------------------------
 // A caller that solves many small programs one after the other (the mixed-integer enumeration: one mpc_create /
@@ -51,12 +53,12 @@ thread_local std::string g_error;
 // stream creations per program -- 12 ms, several times the kernel time of such a program.  Blocks are kept in size
 // classes (powers of two up to 1 MiB, MiB multiples above) and handed to the next handle on the same device; a block
 // is only returned to the pool once the work that used it has completed (destroy synchronises its streams first).
-std::mutex g_dev_pool_mutex;
-std::multimap<std::pair<int, size_t>, void *> g_dev_pool_free;   // (device, size) -> block
-size_t g_dev_pool_bytes = 0;
+static std::mutex g_dev_pool_mutex;
+static std::multimap<std::pair<int, size_t>, void *> g_dev_pool_free;   // (device, size) -> block
+static size_t g_dev_pool_bytes = 0;
 // Free blocks kept: MPC_DEV_POOL_GB (default 48 -- a sixth of the 288 GB of an MI355X; a batch of 64 sub-programs of the
 // mixed-integer enumeration holds ~20 GB of level buffers at once, and the next enumeration takes them over as they are).
-const size_t DEV_POOL_MAX_BYTES = [] { const char *ev = std::getenv("MPC_DEV_POOL_GB"); const double gb = ev ? std::atof(ev) : 48.0; return (size_t)(std::max(gb, 0.0) * 1073741824.0); }();
+static const size_t DEV_POOL_MAX_BYTES = [] { const char *ev = std::getenv("MPC_DEV_POOL_GB"); const double gb = ev ? std::atof(ev) : 48.0; return (size_t)(std::max(gb, 0.0) * 1073741824.0); }();
 constexpr size_t DEV_POOL_MAX_BLOCK = size_t(8) << 30;
 
 // size classes: powers of two up to 1 MiB, above that four steps per octave (1, 1.25, 1.5, 1.75 x 2^k: at most 25 % slack, and
@@ -99,53 +101,18 @@ void dev_pool_give(void *p, size_t cls) {
     (void)hipFree(p);
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    // != nullptr: a block this buffer has outgrown is parked there instead of being waited for -- the owner (a handle) gives the parked
-    // blocks back to the pool behind its next synchronisation of all its streams (graveyard_flush).  A handle's first solve grows some
-    // twenty buffers on every level: one stream synchronisation each (round 4: 170 growths per first solve of config 4).
-    std::vector<std::pair<void *, size_t>> *parked = nullptr;
-    hipError_t ensure(size_t bytes, hipStream_t st, bool keep = false) {
-        if (bytes <= cap) return hipSuccess;
-        const size_t want = dev_size_class(std::max(bytes, cap + cap / 2));
-        void *q = nullptr;
-        hipError_t e = dev_pool_take(want, &q);
-        if (e != hipSuccess) return e;
-        if (p) {
-            if (keep && cap) {
-                e = hipMemcpyAsync(q, p, cap, hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) return e;
-            }
-            // the old block may still be read by work queued on this stream: it goes back to the pool only afterwards
-            if (parked) parked->emplace_back(p, cap);
-            else {
-                e = st ? hipStreamSynchronize(st) : hipDeviceSynchronize();
-                if (e != hipSuccess) return e;
-                dev_pool_give(p, cap);
-            }
-        }
-        p = q;
-        cap = want;
-        return hipSuccess;
-    }
-    // the caller has synchronised whatever used the block
-    void release() { if (p) dev_pool_give(p, cap); p = nullptr; cap = 0; }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // pooled page-locked host memory (also behind mpc_host_alloc / mpc_host_free)
 // Two classes of blocks that are never mixed: class 0 = staging for DMA copies (default, coarse-grained mapping); class 1 =
 // blocks a RUNNING kernel writes and the host polls (streamed region records, chunk flags, the list-length counters):
 // those are allocated hipHostMallocCoherent | hipHostMallocMapped, i.e. fine-grained, so that visibility of the kernel's
 // system-scope release does not depend on HIP_HOST_COHERENT or on an undocumented L2 write-back.
-std::mutex g_pool_mutex;
-std::multimap<size_t, void *> g_pool_free[2];       // [class] size -> block
-std::unordered_map<void *, std::pair<size_t, int>> g_pool_live;     // block -> (size, class)
-size_t g_pool_free_bytes = 0;
+static std::mutex g_pool_mutex;
+static std::multimap<size_t, void *> g_pool_free[2];       // [class] size -> block
+static std::unordered_map<void *, std::pair<size_t, int>> g_pool_live;     // block -> (size, class)
+static size_t g_pool_free_bytes = 0;
 constexpr size_t POOL_MAX_FREE = size_t(16) << 30;
 
-hipError_t host_pool_take(size_t bytes, void **out, size_t *got, bool coherent = false) {
+hipError_t host_pool_take(size_t bytes, void **out, size_t *got, bool coherent) {
     const size_t gran = bytes >= (size_t(1) << 20) ? (size_t(1) << 20) : (size_t(64) << 10);
     const size_t need = std::max<size_t>((bytes + gran - 1) / gran * gran, gran);
     const int cls = coherent ? 1 : 0;
@@ -189,26 +156,11 @@ bool host_pool_give(void *p) {
     return true;
 }
 
-// pinned (page-locked) host staging: device-to-host copies run at link speed and never page-fault
-struct HostBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    bool coherent = false;   // class 1 of the pool: written by running kernels, polled by the host
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        const size_t want = std::max(bytes, cap + cap / 2);
-        release();
-        return host_pool_take(want, &p, &cap, coherent);
-    }
-    void release() { if (p) (void)host_pool_give(p); p = nullptr; cap = 0; }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
 // streams and events
-std::mutex g_sync_pool_mutex;
-std::map<int, std::vector<hipStream_t>> g_stream_pool;
-std::map<std::pair<int, int>, std::vector<hipEvent_t>> g_event_pool;   // (device, timing?) -> events
-std::map<int, int> g_cu_count;
+static std::mutex g_sync_pool_mutex;
+static std::map<int, std::vector<hipStream_t>> g_stream_pool;
+static std::map<std::pair<int, int>, std::vector<hipEvent_t>> g_event_pool;   // (device, timing?) -> events
+static std::map<int, int> g_cu_count;
 
 hipError_t pooled_stream(hipStream_t *out) {
     int dev = 0;
@@ -267,9 +219,7 @@ int cu_count(int device) {
     return n;
 }
 
-int odd_at_least(int v) { return (v % 2) ? v : v + 1; }
-
-}  // namespace
+}  // namespace mpc
 
 struct mpc_handle {
     int device = 0;
@@ -452,19 +402,12 @@ struct mpc_handle {
     hipEvent_t kev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // around k_theta2 / the main k_x2 launch / k_region2 / k_kkt_thread / k_xq / k_xq_thread
 };
 
-namespace {
-
-int fail(mpc_handle *h, int code, const std::string &msg) {
+int mpc::fail(mpc_handle *h, int code, const std::string &msg) {
     if (h) { std::lock_guard<std::mutex> lk(h->em); h->error = msg; } else g_error = msg;
     return code;
 }
 
-#define HIP_TRY(h, expr)                                                                                   \
-    do {                                                                                                   \
-        hipError_t e__ = (expr);                                                                           \
-        if (e__ != hipSuccess)                                                                             \
-            return fail(h, MPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));               \
-    } while (0)
+namespace {
 
 struct Layout { int off_T, off_K, off_L, off_E, off_X, n_doubles, off_as, off_inact, off_colvar, off_rowvar, off_rowkind, off_kept, off_pri, off_stored, n_ints, bytes; };
 
@@ -488,8 +431,6 @@ void apply_layout(DevProblem &P, const Layout &l) {
     P.off_as = l.off_as; P.off_inact = l.off_inact; P.off_colvar = l.off_colvar; P.off_rowvar = l.off_rowvar;
     P.off_rowkind = l.off_rowkind; P.off_kept = l.off_kept; P.off_pri = l.off_pri; P.off_stored = l.off_stored; P.n_ints = l.n_ints;
 }
-
-int waves_per_cu(int lds_bytes) { return std::max(1, std::min(16, (160 * 1024) / std::max(lds_bytes, 1))); }
 
 // dense host helpers (one-off program setup; fp64)
 // LU with partial pivoting of the n x n matrix M (row major, overwritten); perm receives the row order.
@@ -543,7 +484,8 @@ extern "C" {
 
 int mpc_device_count(void) { return device_count_cached(); }
 
-// the build stamp says which binary a record was made with: the compiler's date / time of THIS translation unit and the hipcc version
+// the build stamp says which binary a record was made with: the compiler's date / time of THIS translation unit (the engine; the
+// other units carry no stamp of their own -- __graft_entry__.build prints every object's time) and the hipcc version
 #define MPC_STR2(x) #x
 #define MPC_STR(x) MPC_STR2(x)
 const char *mpc_version(void) {
@@ -4228,10 +4170,7 @@ extern "C" int mpc_facet_centres(int32_t device, int32_t n_t, int64_t n_regions,
     const long long rows = n_regions ? row_off[n_regions] : 0;
     if (rows == 0) return MPC_OK;
     if (!ef_rows) return fail(nullptr, MPC_ERR_INVALID, "bad argument");
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
+    if (int rc = select_device(nullptr, device)) return rc;
     int m_max = 0;
     std::vector<int32_t> reg((size_t)rows);
     for (long long r = 0; r < n_regions; ++r) {
@@ -4242,207 +4181,21 @@ extern "C" int mpc_facet_centres(int32_t device, int32_t n_t, int64_t n_regions,
     const size_t lds = (((size_t)(m + 1) * ld * 8 + (size_t)(ld + 1 + 3 * (m + 2)) * 4) + 15) & ~size_t(15);
     if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "a region has too many rows for the 160 KiB LDS of one CU");
     if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_facet_centres), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DevBuf d_ef, d_off, d_reg, d_c, d_r, d_s, d_w;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(d_ef.ensure((size_t)rows * (n_t + 1) * 8, nullptr)); chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_reg.ensure((size_t)rows * 4, nullptr));
-    chk(d_c.ensure((size_t)rows * n_t * 8, nullptr)); chk(d_r.ensure((size_t)rows * 8, nullptr)); chk(d_s.ensure((size_t)rows * 4, nullptr)); chk(d_w.ensure(256, nullptr));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n_t + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_reg.p, reg.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-        chk(hipMemset(d_w.p, 0, 4));
-    }
-    if (e == hipSuccess) {
+    OneShot s("mpc_facet_centres");
+    DevBuf &d_ef = s.upload(ef_rows, (size_t)rows * (n_t + 1) * 8), &d_off = s.upload(row_off, (size_t)(n_regions + 1) * 8);
+    DevBuf &d_reg = s.upload(reg.data(), (size_t)rows * 4);
+    DevBuf &d_c = s.buf((size_t)rows * n_t * 8), &d_r = s.buf((size_t)rows * 8), &d_s = s.buf((size_t)rows * 4), &d_w = s.buf(256);
+    s.fill(d_w, 0, 4);
+    s.launch([&] {
         const int per_cu = std::max(1, std::min(32, (int)((160 * 1024) / lds)));
         const dim3 g((unsigned)std::min<long long>(rows, (long long)cu_count(device) * per_cu)), b(64);
         hipLaunchKernelGGL(k_facet_centres, g, b, lds, nullptr, rows, (int)n_t, m_max, ld, d_ef.as<double>(), d_off.as<long long>(), d_reg.as<int32_t>(),
                            d_c.as<double>(), d_r.as<double>(), d_s.as<int32_t>(), d_w.as<unsigned int>());
-        chk(hipGetLastError());
-        chk(hipMemcpy(centre, d_c.p, (size_t)rows * n_t * 8, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(radius, d_r.p, (size_t)rows * 8, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(status, d_s.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
-    }
-    (void)hipDeviceSynchronize();
-    for (DevBuf *bf : {&d_ef, &d_off, &d_reg, &d_c, &d_r, &d_s, &d_w}) bf->release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string("mpc_facet_centres: ") + hipGetErrorString(e));
-    return MPC_OK;
-}
-
-// ---- hit-and-run chains in a batch of polytopes (k_hit_and_run, locate.hpp) -----------------------------------------------
-template <int NT, bool L>
-static void hr_launch(dim3 g, size_t lds, int n, long long n_poly, long long chains, long long wpp, const DevBuf &off, const DevBuf &ab,
-                      const DevBuf &st0, uint32_t samples, uint32_t n_steps, uint32_t k0, uint32_t k1, DevBuf &out, DevBuf &status) {
-    hipLaunchKernelGGL((k_hit_and_run<NT, L>), g, dim3(HR_BLOCK), lds, nullptr, n, n_poly, chains, wpp, off.as<long long>(), ab.as<double>(),
-                       st0.as<double>(), samples, n_steps, k0, k1, out.as<double>(), status.as<int32_t>());
-}
-
-extern "C" int mpc_hit_and_run(int32_t device, int32_t n, int64_t n_poly, const int64_t *row_off, const double *ab_rows, const double *start,
-                               int64_t chains, int64_t samples, int64_t n_steps, uint64_t seed, double *out, int32_t *status, float *ms) {
-    if (ms) *ms = 0.0f;
-    if (n < 1 || n > 64) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: n must lie in 1..64");
-    if (n_poly < 0 || chains < 0 || samples < 1 || n_steps < 1) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: bad sizes");
-    if (samples >= (1ll << 32) || n_steps >= (1ll << 32) || (unsigned long long)samples * (unsigned long long)n_steps >= (1ull << 32))
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: samples * n_steps must stay below 2^32");
-    if (!row_off) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing row_off");
-    if (row_off[0] != 0) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: row_off[0] must be 0");
-    for (int64_t p = 0; p < n_poly; ++p) {
-        const int64_t r = row_off[p + 1] - row_off[p];
-        if (r < 0 || r > 256) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: a polytope has more than 256 rows (or row_off decreases)");
-    }
-    if (n_poly == 0 || chains == 0) return MPC_OK;
-    const long long rows = row_off[n_poly];
-    if ((rows && !ab_rows) || !start || !out || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: missing array");
-    const long long wpp = (chains + 63) / 64;
-    if (n_poly > (1ll << 40) / wpp) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains");
-    const long long n_blocks = (n_poly * wpp + HR_BLOCK / 64 - 1) / (HR_BLOCK / 64);
-    if (n_blocks > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_hit_and_run: too many chains for one launch");
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    const size_t n_chain = (size_t)n_poly * chains, n_out = n_chain * samples * n;
-    const int nt = n <= 2 ? 2 : n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64;
-    const size_t lds = nt == 64 ? (size_t)64 * HR_BLOCK * sizeof(double) : 0;
-    if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_hit_and_run<64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DevBuf d_off, d_ab, d_st0, d_out, d_status;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(d_off.ensure((size_t)(n_poly + 1) * 8, nullptr)); chk(d_ab.ensure(std::max<size_t>(8, (size_t)rows * (n + 1) * 8), nullptr));
-    chk(d_st0.ensure((size_t)n_poly * n * 8, nullptr)); chk(d_out.ensure(n_out * 8, nullptr)); chk(d_status.ensure(n_chain * 4, nullptr));
-    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_poly + 1) * 8, hipMemcpyHostToDevice));
-        if (rows) chk(hipMemcpy(d_ab.p, ab_rows, (size_t)rows * (n + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_st0.p, start, (size_t)n_poly * n * 8, hipMemcpyHostToDevice));
-    }
-    if (e == hipSuccess) {
-        const dim3 g((unsigned)n_blocks);
-        const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), sm = (uint32_t)samples, ns = (uint32_t)n_steps;
-        chk(hipEventRecord(e0, nullptr));
-        switch (nt) {
-            case 2: hr_launch<2, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-            case 4: hr_launch<4, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-            case 8: hr_launch<8, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-            case 16: hr_launch<16, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-            case 32: hr_launch<32, false>(g, 0, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-            default: hr_launch<64, true>(g, lds, n, n_poly, chains, wpp, d_off, d_ab, d_st0, sm, ns, k0, k1, d_out, d_status); break;
-        }
-        chk(hipGetLastError());
-        chk(hipEventRecord(e1, nullptr));
-        chk(hipMemcpy(out, d_out.p, n_out * 8, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(status, d_status.p, n_chain * 4, hipMemcpyDeviceToHost));
-        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
-    }
-    (void)hipDeviceSynchronize();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    for (DevBuf *bf : {&d_off, &d_ab, &d_st0, &d_out, &d_status}) bf->release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string("mpc_hit_and_run: ") + hipGetErrorString(e));
-    return MPC_OK;
-}
-
-// ---- slices of a batch of polytopes by a plane or a line (k_slice_polygons / k_slice_intervals, locate.hpp) ---------------------
-static int slice_check(const char *who, int32_t n, int64_t n_regions, const int64_t *row_off, double eps) {
-    char msg[160];
-    if (n < 1 || n > 64) { snprintf(msg, sizeof msg, "%s: n must lie in 1..64", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
-    if (n_regions < 0 || !row_off || row_off[0] != 0) { snprintf(msg, sizeof msg, "%s: bad n_regions or row_off", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
-    if (!(eps > 0.0 && eps < 1.0)) { snprintf(msg, sizeof msg, "%s: eps must lie in (0, 1)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
-    for (int64_t r = 0; r < n_regions; ++r) {
-        const int64_t k = row_off[r + 1] - row_off[r];
-        if (k < 0 || k > 256) { snprintf(msg, sizeof msg, "%s: a region has more than 256 rows (or row_off decreases)", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
-    }
-    if (n_regions > 4ll * 0x7fffffffll) { snprintf(msg, sizeof msg, "%s: too many regions for one launch", who); return fail(nullptr, MPC_ERR_INVALID, msg); }
-    return MPC_OK;
-}
-
-// one launch of a slice kernel with its inputs copied in and its outputs copied out; launch(d_in...) enqueues the kernel
-template <class Launch>
-static int slice_run(const char *who, int32_t device, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int32_t n,
-                     const std::vector<double> &param, std::initializer_list<std::pair<void *, size_t>> outs, float *ms, Launch launch) {
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    const long long rows = row_off[n_regions];
-    DevBuf d_off, d_ef, d_param, d_out[5];
-    const size_t n_out = outs.size();
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure(std::max<size_t>(8, (size_t)rows * (n + 1) * 8), nullptr));
-    chk(d_param.ensure(param.size() * 8, nullptr));
-    { size_t q = 0; for (auto &o : outs) chk(d_out[q++].ensure(std::max<size_t>(8, o.second), nullptr)); }
-    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
-        if (rows) chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_param.p, param.data(), param.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (e == hipSuccess) {
-        chk(hipEventRecord(e0, nullptr));
-        launch(dim3((unsigned)((n_regions + SP_WAVES - 1) / SP_WAVES)), d_off.as<long long>(), d_ef.as<double>(), d_param.as<double>(), d_out);
-        chk(hipGetLastError());
-        chk(hipEventRecord(e1, nullptr));
-        size_t q = 0;
-        for (auto &o : outs) { if (o.second) chk(hipMemcpy(o.first, d_out[q].p, o.second, hipMemcpyDeviceToHost)); ++q; }
-        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
-    }
-    (void)hipDeviceSynchronize();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    d_off.release(); d_ef.release(); d_param.release();
-    for (size_t q = 0; q < n_out; ++q) d_out[q].release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return MPC_OK;
-}
-
-extern "C" int mpc_slice_polygons(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
-                                  const double *U, const double *box, double eps, double *vert, int32_t *edge_row, int32_t *count, double *area,
-                                  int32_t *status, float *ms) {
-    if (ms) *ms = 0.0f;
-    if (int rc = slice_check("mpc_slice_polygons", n, n_regions, row_off, eps)) return rc;
-    if (!theta0 || !U || !box) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing theta0, U or box");
-    for (int k = 0; k < 2; ++k)
-        if (!std::isfinite(box[k]) || !std::isfinite(box[k + 2]) || !(box[k] < box[k + 2]))
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: the box must be finite with lo < hi");
-    if (n_regions == 0) return MPC_OK;
-    const long long rows = row_off[n_regions], slots = rows + 4 * n_regions;
-    if ((rows && !ef_rows) || !vert || !edge_row || !count || !area || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_polygons: missing array");
-    // z is measured from the box centre c: plane[t] = (theta0 + U c, U[t][0], U[t][1])
-    const double cx = 0.5 * (box[0] + box[2]), cy = 0.5 * (box[1] + box[3]), hx = 0.5 * (box[2] - box[0]), hy = 0.5 * (box[3] - box[1]);
-    std::vector<double> plane(3 * (size_t)n);
-    for (int t = 0; t < n; ++t) {
-        plane[3 * t] = theta0[t] + U[2 * t] * cx + U[2 * t + 1] * cy;
-        plane[3 * t + 1] = U[2 * t];
-        plane[3 * t + 2] = U[2 * t + 1];
-    }
-    return slice_run("mpc_slice_polygons", device, n_regions, row_off, ef_rows, n, plane,
-                     {{vert, (size_t)slots * 16}, {edge_row, (size_t)slots * 4}, {count, (size_t)n_regions * 4}, {area, (size_t)n_regions * 8},
-                      {status, (size_t)n_regions * 4}}, ms,
-                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *o) {
-                         hipLaunchKernelGGL(k_slice_polygons, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, hx, hy, cx, cy, eps,
-                                            o[0].as<double>(), o[1].as<int32_t>(), o[2].as<int32_t>(), o[3].as<double>(), o[4].as<int32_t>());
-                     });
-}
-
-extern "C" int mpc_slice_intervals(int32_t device, int32_t n, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *theta0,
-                                   const double *u, double t_lo, double t_hi, double eps, double *interval, int32_t *status, float *ms) {
-    if (ms) *ms = 0.0f;
-    if (int rc = slice_check("mpc_slice_intervals", n, n_regions, row_off, eps)) return rc;
-    if (!theta0 || !u) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing theta0 or u");
-    if (!std::isfinite(t_lo) || !std::isfinite(t_hi) || !(t_lo < t_hi)) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: the range must be finite with t_lo < t_hi");
-    if (n_regions == 0) return MPC_OK;
-    if ((row_off[n_regions] && !ef_rows) || !interval || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_slice_intervals: missing array");
-    std::vector<double> line(2 * (size_t)n);
-    for (int t = 0; t < n; ++t) { line[2 * t] = theta0[t]; line[2 * t + 1] = u[t]; }
-    return slice_run("mpc_slice_intervals", device, n_regions, row_off, ef_rows, n, line,
-                     {{interval, (size_t)n_regions * 16}, {status, (size_t)n_regions * 4}}, ms,
-                     [&](dim3 g, const long long *off, const double *ef, const double *prm, DevBuf *o) {
-                         hipLaunchKernelGGL(k_slice_intervals, g, dim3(SP_BLOCK), 0, nullptr, n, (long long)n_regions, off, ef, prm, t_lo, t_hi, eps,
-                                            o[0].as<double>(), o[1].as<int32_t>());
-                     });
+    });
+    s.download(centre, d_c, (size_t)rows * n_t * 8);
+    s.download(radius, d_r, (size_t)rows * 8);
+    s.download(status, d_s, (size_t)rows * 4);
+    return s.finish();
 }
 
 // ---- batched LPs ------------------------------------------------------------------------------------------------
@@ -4451,10 +4204,7 @@ static int lp_batch_impl(int32_t device, int64_t n_lp, int32_t m, int32_t n, con
                          double *obj, int32_t *iters, int32_t *tight) {
     if (n_lp < 0 || m < 1 || n < 1 || !A || !b || !eq || !status) return fail(nullptr, MPC_ERR_INVALID, "bad argument");
     if (n_lp == 0) return MPC_OK;
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
+    if (int rc = select_device(nullptr, device)) return rc;
     const int ld = odd_at_least(n + 3);
     const size_t lds = (((size_t)(m + 1) * ld * 8 + (size_t)(ld + 1 + 3 * (m + 2)) * 4) + 15) & ~size_t(15);
     if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "LP does not fit the 160 KiB LDS of one CU");
@@ -4506,7 +4256,6 @@ extern "C" int mpc_lp_solve_batch(int32_t device, int64_t n_lp, int32_t m, int32
     return lp_batch_impl(device, n_lp, m, n, A, shared_A, b, shared_b, c, shared_c, eq, status, x, obj, iters, nullptr);
 }
 
-// ---- point location ---------------------------------------------------------------------------------------------------
 // ---- the QP of the program at fixed parameter points (qp.hpp) ------------------------------------------------------------------
 extern "C" int mpc_qp_solve_batch(mpc_handle *h, int64_t m, const double *theta, int32_t *status, double *x, double *lambda, uint8_t *active,
                                   int32_t *iters) {
@@ -4584,10 +4333,7 @@ extern "C" int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, i
         if (active) std::fill(active, active + (size_t)m * n_rows, (uint8_t)0);
         return MPC_OK;
     }
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
+    if (int rc = select_device(nullptr, device)) return rc;
     const int ld = odd_at_least(n_c + 3);
     // the k_qp_batch tableau and multipliers, then z and x
     const size_t lds = ((size_t)(n_c + 1) * ld + n_c + nz + nxc) * sizeof(double) + (size_t)(ld + 1 + 2 * (n_c + 2) + 2) * sizeof(int32_t) + 16;
@@ -4668,1036 +4414,4 @@ extern "C" int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, i
     if (st) return_stream(st);
     for (DevBuf *q : {&d_d, &d_i, &d_ck, &d_ps, &d_po, &d_st, &d_leaf, &d_best, &d_obj, &d_x, &d_l, &d_a, &d_w}) q->release();
     return rc;
-}
-
-struct mpc_locator {
-    int device = 0, n_x = 0, n_t = 0;
-    long long n_regions = 0, n_rows = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    DevBuf row_off, row_region, row_end, ef, xlaw, Q, c, H, theta, region, x;
-    // adjacency for the walk (mpc_locator_set_adjacency): active-set masks in region order and sorted, facet kind / id per row
-    DevBuf masks, sorted_masks, sorted_region, row_info, theta2, region2;
-    int mask_words = 0, n_c = 0;
-    bool has_adj = false;
-    long long last_unresolved = 0;   // points of the last walk query that went to the list scan
-    bool hasQ = false, hasc = false, hasH = false;
-    std::vector<int64_t> h_row_off;  // host copy of row_off (limits of mpc_tree_build)
-    // search tree (mpc_tree_build / mpc_locator_set_tree): host arrays as attached, and their device copies
-    bool has_tree = false;
-    double tree_tol = 0.0;
-    int tree_planes = 0;
-    std::vector<double> h_planes, h_tau;
-    std::vector<int32_t> h_plane, h_child, h_items;
-    std::vector<int64_t> h_off;
-    DevBuf t_planes, t_plane, t_child, t_tau, t_off, t_items;
-};
-
-static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xlaw, const double *Q,
-                        const double *c, const double *H);
-extern "C" int mpc_locator_destroy(mpc_locator *L);
-
-extern "C" int mpc_locator_create(int32_t device, int32_t n_x, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows,
-                                  const double *xlaw, const double *Q, const double *c, const double *H, mpc_locator **out) {
-    if (!out || n_x < 1 || n_t < 1 || n_t > 16 || n_regions < 0 || (n_regions > 0 && (!row_off || !ef_rows || !xlaw)))
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_create: bad arguments (1 <= n_t <= 16)");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    mpc_locator *L = new mpc_locator();
-    L->device = device; L->n_x = n_x; L->n_t = n_t; L->n_regions = n_regions;
-    const int rc_fill = locator_fill(L, n_regions, row_off, ef_rows, xlaw, Q, c, H);
-    if (rc_fill != MPC_OK) { (void)mpc_locator_destroy(L); return rc_fill; }   // one cleanup path: nothing leaks on failure
-    *out = L;
-    return MPC_OK;
-}
-
-static int locator_fill(mpc_locator *L, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xlaw, const double *Q,
-                        const double *c, const double *H) {
-    const int n_x = L->n_x, n_t = L->n_t;
-    HIP_TRY(nullptr, hipStreamCreateWithFlags(&L->stream, hipStreamNonBlocking));
-    HIP_TRY(nullptr, hipEventCreate(&L->e0));
-    HIP_TRY(nullptr, hipEventCreate(&L->e1));
-    const long long rows = n_regions ? row_off[n_regions] : 0;
-    L->n_rows = rows;
-    L->h_row_off.assign(row_off, row_off + (n_regions ? n_regions + 1 : 0));
-    if (!n_regions) L->h_row_off.assign(1, 0);
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), L->stream);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, L->stream);
-    };
-    const long long zero = 0;
-    HIP_TRY(nullptr, up(L->row_off, n_regions ? (const void *)row_off : (const void *)&zero, (size_t)(n_regions + 1) * sizeof(int64_t)));
-    HIP_TRY(nullptr, up(L->ef, ef_rows, (size_t)rows * (n_t + 1) * sizeof(double)));
-    std::vector<int32_t> rr((size_t)std::max<long long>(rows, 1)), re((size_t)std::max<long long>(rows, 1));
-    for (long long r = 0; r < n_regions; ++r)
-        for (long long i = row_off[r]; i < row_off[r + 1]; ++i) { rr[(size_t)i] = (int32_t)r; re[(size_t)i] = (int32_t)row_off[r + 1]; }
-    HIP_TRY(nullptr, up(L->row_region, rr.data(), (size_t)rows * sizeof(int32_t)));
-    HIP_TRY(nullptr, up(L->row_end, re.data(), (size_t)rows * sizeof(int32_t)));
-    HIP_TRY(nullptr, up(L->xlaw, xlaw, (size_t)n_regions * n_x * (n_t + 1) * sizeof(double)));
-    if (Q) { HIP_TRY(nullptr, up(L->Q, Q, (size_t)n_x * n_x * sizeof(double))); L->hasQ = true; }
-    if (c) { HIP_TRY(nullptr, up(L->c, c, (size_t)n_x * sizeof(double))); L->hasc = true; }
-    if (H) { HIP_TRY(nullptr, up(L->H, H, (size_t)n_x * n_t * sizeof(double))); L->hasH = true; }
-    HIP_TRY(nullptr, hipStreamSynchronize(L->stream));
-    return MPC_OK;
-}
-
-extern "C" int mpc_locator_set_adjacency(mpc_locator *L, int32_t mask_words, int32_t n_c, const uint64_t *masks, const int32_t *row_info) {
-    if (!L || !masks || !row_info || (mask_words != 2 && mask_words != 4) || n_c < 1 || n_c > 64 * mask_words) return MPC_ERR_INVALID;
-    HIP_TRY(nullptr, hipSetDevice(L->device));
-    const long long n = L->n_regions, rows = L->n_rows;
-    if (n <= 0) return MPC_OK;
-    const int mw = mask_words;
-    // the mask table sorted ascending (most significant word last), with the region each mask belongs to
-    std::vector<int32_t> order((size_t)n);
-    for (long long i = 0; i < n; ++i) order[(size_t)i] = (int32_t)i;
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        for (int j = mw - 1; j >= 0; --j) { const uint64_t va = masks[(size_t)a * mw + j], vb = masks[(size_t)b * mw + j]; if (va != vb) return va < vb; }
-        return a < b;
-    });
-    std::vector<uint64_t> sorted((size_t)n * mw);
-    for (long long i = 0; i < n; ++i) for (int j = 0; j < mw; ++j) sorted[(size_t)i * mw + j] = masks[(size_t)order[(size_t)i] * mw + j];
-    for (long long i = 1; i < n; ++i) {   // two regions with one active set: no unique neighbour, no walk
-        bool same = true;
-        for (int j = 0; j < mw; ++j) same = same && sorted[(size_t)i * mw + j] == sorted[(size_t)(i - 1) * mw + j];
-        if (same) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_set_adjacency: two regions share one active set");
-    }
-    hipStream_t st = L->stream;
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), st);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    HIP_TRY(nullptr, up(L->masks, masks, (size_t)n * mw * sizeof(uint64_t)));
-    HIP_TRY(nullptr, up(L->sorted_masks, sorted.data(), (size_t)n * mw * sizeof(uint64_t)));
-    HIP_TRY(nullptr, up(L->sorted_region, order.data(), (size_t)n * sizeof(int32_t)));
-    HIP_TRY(nullptr, up(L->row_info, row_info, (size_t)rows * sizeof(int32_t)));
-    HIP_TRY(nullptr, hipStreamSynchronize(st));
-    L->mask_words = mw;
-    L->n_c = n_c;
-    L->has_adj = true;
-    return MPC_OK;
-}
-
-extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta, double tol, int32_t flags, int64_t *region, double *x,
-                                 float *ms_locate) {
-    if (!L || m < 0 || (m > 0 && (!theta || !region))) return MPC_ERR_INVALID;
-    if (ms_locate) *ms_locate = 0.0f;
-    const bool tree = (flags & MPC_LOCATE_TREE) != 0;
-    if (tree && !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: MPC_LOCATE_TREE without an attached tree");
-    if (tree && !(tol <= L->tree_tol)) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: tol is larger than the tolerance the tree was built for");
-    if (m == 0) return MPC_OK;
-    HIP_TRY(nullptr, hipSetDevice(L->device));
-    hipStream_t st = L->stream;
-    const int nt = L->n_t, nx = L->n_x;
-    HIP_TRY(nullptr, L->theta.ensure((size_t)m * nt * sizeof(double), st));
-    HIP_TRY(nullptr, L->region.ensure((size_t)m * sizeof(long long), st));
-    HIP_TRY(nullptr, hipMemcpyAsync(L->theta.p, theta, (size_t)m * nt * sizeof(double), hipMemcpyHostToDevice, st));
-    const dim3 g((unsigned)((m + 255) / 256)), b(256);
-    const double *Q = L->hasQ ? L->Q.as<double>() : nullptr, *c = L->hasc ? L->c.as<double>() : nullptr, *H = L->hasH ? L->H.as<double>() : nullptr;
-    HIP_TRY(nullptr, hipEventRecord(L->e0, st));
-#define MPC_LOCATE(NT_, M_, TH_, OUT_) hipLaunchKernelGGL((k_locate<NT_>), dim3((unsigned)(((M_) + 255) / 256)), b, 0, st, (long long)(M_), nt, nx, L->n_regions, L->n_rows, L->row_region.as<int32_t>(), \
-                                           L->row_end.as<int32_t>(), L->ef.as<double>(), L->xlaw.as<double>(), Q, c, H, TH_, tol, \
-                                           (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), OUT_)
-#define MPC_LOCATE_ANY(M_, TH_, OUT_) do { if (nt <= 4) MPC_LOCATE(4, M_, TH_, OUT_); else if (nt <= 8) MPC_LOCATE(8, M_, TH_, OUT_); else MPC_LOCATE(16, M_, TH_, OUT_); } while (0)
-    const bool walk = (flags & MPC_LOCATE_WALK) && L->has_adj && !(flags & (MPC_LOCATE_OVERLAPPING | MPC_LOCATE_INCLUSIVE)) && L->n_regions > 0 && nt <= 16;
-    if (tree) {
-        // descent of the attached tree; points whose band stack overflowed (-2) go to the list scan
-#define MPC_TREE(NT_) hipLaunchKernelGGL((k_locate_tree<NT_>), g, b, 0, st, (long long)m, nt, nx, L->t_planes.as<double>(), L->t_plane.as<int32_t>(), \
-                                         L->t_child.as<int32_t>(), L->t_tau.as<double>(), L->t_off.as<long long>(), L->t_items.as<int32_t>(), \
-                                         L->row_off.as<long long>(), L->ef.as<double>(), L->xlaw.as<double>(), Q, c, H, L->theta.as<double>(), tol, \
-                                         (int)(flags & MPC_LOCATE_OVERLAPPING), (int)((flags & MPC_LOCATE_INCLUSIVE) != 0), L->region.as<long long>())
-        if (nt <= 4) MPC_TREE(4); else if (nt <= 8) MPC_TREE(8); else MPC_TREE(16);
-#undef MPC_TREE
-        HIP_TRY(nullptr, hipGetLastError());
-        HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(nullptr, hipStreamSynchronize(st));
-        std::vector<long long> open;
-        for (long long p = 0; p < m; ++p) if (region[p] == -2) open.push_back(p);
-        if (!open.empty()) {
-            const long long mo = (long long)open.size();
-            std::vector<double> tho((size_t)mo * nt);
-            for (long long i = 0; i < mo; ++i) std::memcpy(&tho[(size_t)i * nt], theta + (size_t)open[(size_t)i] * nt, sizeof(double) * nt);
-            std::vector<long long> ro((size_t)mo);
-            HIP_TRY(nullptr, L->theta2.ensure((size_t)mo * nt * sizeof(double), st));
-            HIP_TRY(nullptr, L->region2.ensure((size_t)mo * sizeof(long long), st));
-            HIP_TRY(nullptr, hipMemcpyAsync(L->theta2.p, tho.data(), (size_t)mo * nt * sizeof(double), hipMemcpyHostToDevice, st));
-            MPC_LOCATE_ANY(mo, L->theta2.as<double>(), L->region2.as<long long>());
-            HIP_TRY(nullptr, hipGetLastError());
-            HIP_TRY(nullptr, hipMemcpyAsync(ro.data(), L->region2.p, (size_t)mo * sizeof(long long), hipMemcpyDeviceToHost, st));
-            HIP_TRY(nullptr, hipStreamSynchronize(st));
-            for (long long i = 0; i < mo; ++i) region[open[(size_t)i]] = ro[(size_t)i];
-            HIP_TRY(nullptr, hipMemcpyAsync(L->region.p, region, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, st));   // k_evaluate reads it
-        }
-        L->last_unresolved = (long long)open.size();
-        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
-    } else if (!walk) {
-        MPC_LOCATE_ANY(m, L->theta.as<double>(), L->region.as<long long>());
-        HIP_TRY(nullptr, hipGetLastError());
-        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
-        HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
-    } else {
-        // walk through adjacent regions; what the walk cannot resolve goes to the list scan
-        const int max_steps = 384;   // walks are tens of steps long; what is still open then (points outside the solution, mostly) goes to k_locate_few
-#define MPC_WALK(NT_, MW_) hipLaunchKernelGGL((k_locate_walk<NT_, MW_>), g, b, 0, st, (long long)m, nt, L->n_regions, L->row_off.as<long long>(), L->ef.as<double>(), \
-                                              L->row_info.as<int32_t>(), L->masks.as<unsigned long long>(), L->sorted_masks.as<unsigned long long>(), \
-                                              L->sorted_region.as<int32_t>(), L->theta.as<double>(), tol, 0, max_steps, L->n_c, L->region.as<long long>())
-        if (L->mask_words == 2) { if (nt <= 4) MPC_WALK(4, 2); else if (nt <= 8) MPC_WALK(8, 2); else MPC_WALK(16, 2); }
-        else { if (nt <= 4) MPC_WALK(4, 4); else if (nt <= 8) MPC_WALK(8, 4); else MPC_WALK(16, 4); }
-#undef MPC_WALK
-        HIP_TRY(nullptr, hipGetLastError());
-        HIP_TRY(nullptr, hipMemcpyAsync(region, L->region.p, (size_t)m * sizeof(long long), hipMemcpyDeviceToHost, st));
-        HIP_TRY(nullptr, hipStreamSynchronize(st));
-        std::vector<long long> open;
-        for (long long p = 0; p < m; ++p) if (region[p] == -2) open.push_back(p);
-        if (!open.empty()) {
-            const long long mo = (long long)open.size();
-            std::vector<double> tho((size_t)mo * nt);
-            for (long long i = 0; i < mo; ++i) std::memcpy(&tho[(size_t)i * nt], theta + (size_t)open[(size_t)i] * nt, sizeof(double) * nt);
-            std::vector<long long> ro((size_t)mo);
-            HIP_TRY(nullptr, L->theta2.ensure((size_t)mo * nt * sizeof(double), st));
-            HIP_TRY(nullptr, L->region2.ensure((size_t)mo * sizeof(long long), st));
-            HIP_TRY(nullptr, hipMemcpyAsync(L->theta2.p, tho.data(), (size_t)mo * nt * sizeof(double), hipMemcpyHostToDevice, st));
-            if (mo <= 16384) {
-                // few points: every (point, region) pair in parallel, first containing region by atomicMin
-                HIP_TRY(nullptr, hipMemsetAsync(L->region2.p, 0xff, (size_t)mo * sizeof(long long), st));   // = "none yet" (max u64)
-                const dim3 gf((unsigned)((L->n_regions + 255) / 256), (unsigned)mo);
-                if (nt <= 4) hipLaunchKernelGGL((k_locate_few<4>), gf, b, 0, st, mo, nt, L->n_regions, L->row_off.as<long long>(), L->ef.as<double>(), L->theta2.as<double>(), tol, L->region2.as<long long>());
-                else if (nt <= 8) hipLaunchKernelGGL((k_locate_few<8>), gf, b, 0, st, mo, nt, L->n_regions, L->row_off.as<long long>(), L->ef.as<double>(), L->theta2.as<double>(), tol, L->region2.as<long long>());
-                else hipLaunchKernelGGL((k_locate_few<16>), gf, b, 0, st, mo, nt, L->n_regions, L->row_off.as<long long>(), L->ef.as<double>(), L->theta2.as<double>(), tol, L->region2.as<long long>());
-            } else {
-                MPC_LOCATE_ANY(mo, L->theta2.as<double>(), L->region2.as<long long>());
-            }
-            HIP_TRY(nullptr, hipGetLastError());
-            HIP_TRY(nullptr, hipMemcpyAsync(ro.data(), L->region2.p, (size_t)mo * sizeof(long long), hipMemcpyDeviceToHost, st));
-            HIP_TRY(nullptr, hipStreamSynchronize(st));
-            for (long long i = 0; i < mo; ++i) region[open[(size_t)i]] = ro[(size_t)i];   // -1 (all ones) where no region contains the point
-            HIP_TRY(nullptr, hipMemcpyAsync(L->region.p, region, (size_t)m * sizeof(long long), hipMemcpyHostToDevice, st));   // k_evaluate reads it
-        }
-        L->last_unresolved = (long long)open.size();
-        HIP_TRY(nullptr, hipEventRecord(L->e1, st));
-    }
-#undef MPC_LOCATE_ANY
-#undef MPC_LOCATE
-    if (x) {
-        HIP_TRY(nullptr, L->x.ensure((size_t)m * nx * sizeof(double), st));
-        const long long tot = (long long)m * nx;
-        hipLaunchKernelGGL(k_evaluate, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (long long)m, nt, nx, L->xlaw.as<double>(), L->theta.as<double>(),
-                           L->region.as<long long>(), L->x.as<double>());
-        HIP_TRY(nullptr, hipGetLastError());
-        HIP_TRY(nullptr, hipMemcpyAsync(x, L->x.p, (size_t)m * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(nullptr, hipStreamSynchronize(st));
-    if (ms_locate) HIP_TRY(nullptr, hipEventElapsedTime(ms_locate, L->e0, L->e1));
-    return MPC_OK;
-}
-
-// ---- search trees (tree.hpp) ------------------------------------------------------------------------------------
-constexpr long long TREE_DEFAULT_BUDGET = 4ll << 30, TREE_MAX_LEVEL_ITEMS = 1ll << 28;
-
-static int tree_attach(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane, const int32_t *node_child,
-                       const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
-    const int nr = L->n_t + 1;
-    const int64_t n_items = node_off[n_nodes];
-    L->has_tree = false;
-    L->h_planes.assign(planes, planes + (size_t)n_planes * nr);
-    L->h_plane.assign(node_plane, node_plane + n_nodes);
-    L->h_child.assign(node_child, node_child + 2 * n_nodes);
-    L->h_tau.assign(node_tau, node_tau + 2 * n_nodes);
-    L->h_off.assign(node_off, node_off + n_nodes + 1);
-    L->h_items.assign(items, items + n_items);
-    hipStream_t st = L->stream;
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), st);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    HIP_TRY(nullptr, up(L->t_planes, L->h_planes.data(), L->h_planes.size() * 8));
-    HIP_TRY(nullptr, up(L->t_plane, L->h_plane.data(), L->h_plane.size() * 4));
-    HIP_TRY(nullptr, up(L->t_child, L->h_child.data(), L->h_child.size() * 4));
-    HIP_TRY(nullptr, up(L->t_tau, L->h_tau.data(), L->h_tau.size() * 8));
-    HIP_TRY(nullptr, up(L->t_off, L->h_off.data(), L->h_off.size() * 8));
-    HIP_TRY(nullptr, up(L->t_items, L->h_items.data(), L->h_items.size() * 4));
-    HIP_TRY(nullptr, hipStreamSynchronize(st));
-    L->tree_planes = n_planes;
-    L->tree_tol = tol;
-    L->has_tree = true;
-    return MPC_OK;
-}
-
-extern "C" int mpc_locator_set_tree(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
-                                    const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
-    const char *who = "mpc_locator_set_tree";
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (!L) return bad("no locator");
-    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
-    if (n_nodes < 1 || !node_plane || !node_child || !node_tau || !node_off) return bad("missing node arrays");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (node_off[0] != 0) return bad("node_off[0] must be 0");
-    const int nr = L->n_t + 1;
-    for (int64_t i = 0; i < (int64_t)n_planes * nr; ++i) if (!std::isfinite(planes[i])) return bad("planes must be finite");
-    for (int64_t k = 0; k < n_nodes; ++k) {
-        if (node_off[k + 1] < node_off[k]) return bad("node_off decreases");
-        const int32_t h = node_plane[k];
-        if (h < -1 || h >= n_planes) return bad("a node plane is out of range");
-        if (h >= 0) {
-            for (int q = 0; q < 2; ++q) {
-                const int32_t ch = node_child[2 * k + q];
-                if (ch <= k || ch >= n_nodes) return bad("a child index is not after its parent or out of range");
-                if (!(node_tau[2 * k + q] >= 0.0)) return bad("tau must be >= 0");
-            }
-        }
-    }
-    if (node_off[n_nodes] > 0 && !items) return bad("missing items");
-    for (int64_t k = 0; k < n_nodes; ++k)
-        for (int64_t i = node_off[k]; i < node_off[k + 1]; ++i) {
-            if (items[i] < 0 || items[i] >= L->n_regions) return bad("a leaf item is not a region index");
-            if (i > node_off[k] && items[i] < items[i - 1]) return bad("a leaf list is not ascending");
-        }
-    HIP_TRY(nullptr, hipSetDevice(L->device));
-    return tree_attach(L, n_planes, planes, n_nodes, node_plane, node_child, node_tau, node_off, items, tol);
-}
-
-extern "C" int mpc_locator_tree_size(mpc_locator *L, int64_t *n_nodes, int64_t *n_items, int32_t *n_planes, double *tol) {
-    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_tree_size: no tree attached");
-    if (n_nodes) *n_nodes = (int64_t)L->h_plane.size();
-    if (n_items) *n_items = (int64_t)L->h_items.size();
-    if (n_planes) *n_planes = L->tree_planes;
-    if (tol) *tol = L->tree_tol;
-    return MPC_OK;
-}
-
-extern "C" int mpc_locator_get_tree(mpc_locator *L, double *planes, int32_t *node_plane, int32_t *node_child, double *node_tau, int64_t *node_off,
-                                    int32_t *items) {
-    if (!L || !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_get_tree: no tree attached");
-    auto put = [](void *dst, const auto &v) { if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-    put(planes, L->h_planes); put(node_plane, L->h_plane); put(node_child, L->h_child); put(node_tau, L->h_tau); put(node_off, L->h_off);
-    put(items, L->h_items);
-    return MPC_OK;
-}
-
-extern "C" int mpc_tree_build(mpc_locator *L, int32_t n_planes, const double *planes, const int64_t *cand_off, const int32_t *cand_plane, double tol,
-                              double band, int32_t leaf_size, int32_t max_depth, int64_t budget, mpc_tree_stats *stats) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const char *who = "mpc_tree_build";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!L) return bad("no locator");
-    const int nt = L->n_t, nr = nt + 1;
-    const long long R = L->n_regions;
-    if (nt < 1 || nt > TR_MAX_NT) return bad("n_t must lie in 1..16");
-    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (!std::isfinite(band) || band < 0.0) return bad("band must be finite and >= 0");
-    if (leaf_size < 1) return bad("leaf_size must be >= 1");
-    if (max_depth < 1 || max_depth > 64) return bad("max_depth must lie in 1..64");
-    if ((cand_off == nullptr) != (cand_plane == nullptr)) return bad("cand_off and cand_plane go together");
-    int m_max = 0;
-    for (long long r = 0; r < R; ++r) {
-        const long long k = L->h_row_off[(size_t)r + 1] - L->h_row_off[(size_t)r];
-        if (k > TR_MAX_ROWS) return bad("a region has more than 256 rows");
-        m_max = std::max<int>(m_max, (int)k);
-    }
-    for (int h = 0; h < n_planes; ++h) {
-        double nn = 0.0;
-        for (int t = 0; t < nt; ++t) nn += planes[(size_t)h * nr + t] * planes[(size_t)h * nr + t];
-        if (!std::isfinite(planes[(size_t)h * nr + nt]) || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("planes must be finite with unit normals");
-    }
-    if (cand_off) {
-        if (cand_off[0] != 0) return bad("cand_off[0] must be 0");
-        for (long long r = 0; r < R; ++r) if (cand_off[r + 1] < cand_off[r]) return bad("cand_off decreases");
-        for (long long i = 0; i < cand_off[R]; ++i) if (cand_plane[i] < 0 || cand_plane[i] >= n_planes) return bad("a candidate plane is out of range");
-    }
-    const int hw = (n_planes + 63) / 64;
-    const long long limit = budget > 0 ? budget : TREE_DEFAULT_BUDGET;
-    const long long bitset_bytes = (cand_off ? 3 : 2) * (long long)R * hw * 8;
-    if (bitset_bytes > limit) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "the classification bitsets need %lld bytes, over the budget of %lld bytes", bitset_bytes, limit);
-        return bad(msg);
-    }
-    HIP_TRY(nullptr, hipSetDevice(L->device));
-    hipStream_t st = L->stream;
-    DevBuf d_planes, d_plus, d_minus, d_owner, d_xs, d_empty, d_cnt, d_items, d_off, d_part, d_iplane, d_side, d_pairs, d_nplane, d_tau, d_er, d_ep;
-    DevBuf *all[] = {&d_planes, &d_plus, &d_minus, &d_owner, &d_xs, &d_empty, &d_cnt, &d_items, &d_off, &d_part, &d_iplane, &d_side, &d_pairs,
-                     &d_nplane, &d_tau, &d_er, &d_ep};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    struct Cleanup {
-        hipStream_t st; DevBuf **b; size_t n; hipEvent_t *ev;
-        ~Cleanup() { (void)hipStreamSynchronize(st); for (size_t i = 0; i < n; ++i) b[i]->release(); for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }
-    } cleanup{st, all, sizeof all / sizeof all[0], ev};
-    HIP_TRY(nullptr, hipEventCreate(&ev[0]));
-    HIP_TRY(nullptr, hipEventCreate(&ev[1]));
-    float ms_classify = 0.0f, ms_split = 0.0f, ms_tau = 0.0f;
-    auto timed = [&](float &acc, auto &&launch) -> hipError_t {
-        hipError_t e = hipEventRecord(ev[0], st);
-        if (e != hipSuccess) return e;
-        launch();
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
-        if ((e = hipEventSynchronize(ev[1])) != hipSuccess) return e;
-        float ms = 0.0f;
-        if ((e = hipEventElapsedTime(&ms, ev[0], ev[1])) != hipSuccess) return e;
-        acc += ms;
-        return hipSuccess;
-    };
-    auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-        hipError_t e = b.ensure(std::max<size_t>(bytes, 8), st);
-        if (e != hipSuccess || !bytes) return e;
-        return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    };
-    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(nullptr, up(d_cnt, cnt, sizeof cnt));
-    TreeClassifyArgs a{};
-    a.nt = nt; a.m_max = std::max(m_max, 1); a.n_planes = n_planes; a.hw = hw; a.n_regions = R;
-    a.row_off = L->row_off.as<long long>(); a.ef = L->ef.as<double>(); a.tol = tol; a.band = band;
-    a.counters = d_cnt.as<unsigned long long>();
-    const size_t lds = tr_lds_bytes(a.m_max, nt);
-    if (R > 0 && n_planes > 0) {
-        HIP_TRY(nullptr, up(d_planes, planes, (size_t)n_planes * nr * 8));
-        const size_t bits = (size_t)R * hw * 8;
-        HIP_TRY(nullptr, d_plus.ensure(bits, st)); HIP_TRY(nullptr, d_minus.ensure(bits, st));
-        HIP_TRY(nullptr, hipMemsetAsync(d_plus.p, 0, bits, st)); HIP_TRY(nullptr, hipMemsetAsync(d_minus.p, 0, bits, st));
-        HIP_TRY(nullptr, d_xs.ensure((size_t)R * nt * 8, st)); HIP_TRY(nullptr, d_empty.ensure((size_t)R * 4, st));
-        if (cand_off && cand_off[R] > 0) {
-            HIP_TRY(nullptr, d_owner.ensure(bits, st));
-            HIP_TRY(nullptr, hipMemsetAsync(d_owner.p, 0, bits, st));
-            std::vector<int32_t> er((size_t)cand_off[R]);
-            for (long long r = 0; r < R; ++r) for (long long i = cand_off[r]; i < cand_off[r + 1]; ++i) er[(size_t)i] = (int32_t)r;
-            HIP_TRY(nullptr, up(d_er, er.data(), er.size() * 4));
-            HIP_TRY(nullptr, up(d_ep, cand_plane, er.size() * 4));
-            const long long ne = cand_off[R];
-            hipLaunchKernelGGL(k_tree_owner, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, ne, hw, d_er.as<int32_t>(), d_ep.as<int32_t>(),
-                               d_owner.as<unsigned long long>());
-            HIP_TRY(nullptr, hipGetLastError());
-        }
-        a.planes = d_planes.as<double>(); a.plus = d_plus.as<unsigned long long>(); a.minus = d_minus.as<unsigned long long>();
-        a.xs = d_xs.as<double>(); a.empty = d_empty.as<int32_t>();
-        HIP_TRY(nullptr, timed(ms_classify, [&] { hipLaunchKernelGGL((k_tree_classify<0>), dim3((unsigned)R), dim3(64), lds, st, a); }));
-    }
-    const unsigned long long *owner = (cand_off && cand_off[R] > 0) ? d_owner.as<unsigned long long>() : nullptr;
-    // the level loop: host node records, device counts
-    struct Node { int32_t plane = -1, child[2] = {-1, -1}; double tau[2] = {0.0, 0.0}; int depth = 0; std::vector<int32_t> list; };
-    std::vector<Node> nodes(1);
-    nodes[0].list.resize((size_t)R);
-    for (long long r = 0; r < R; ++r) nodes[0].list[(size_t)r] = (int32_t)r;
-    std::vector<int> level{0};
-    long long tau_lps = 0;
-    while (!level.empty() && n_planes > 0) {
-        std::vector<int> work;
-        for (int k : level) if ((long long)nodes[k].list.size() > leaf_size && nodes[k].depth < max_depth) work.push_back(k);
-        if (work.empty()) break;
-        std::vector<long long> off(work.size() + 1, 0);
-        for (size_t w = 0; w < work.size(); ++w) off[w + 1] = off[w] + (long long)nodes[work[w]].list.size();
-        if (off.back() > TREE_MAX_LEVEL_ITEMS) return fail(nullptr, MPC_ERR_CAPACITY, "mpc_tree_build: a level holds more than 2^28 (node, region) entries");
-        std::vector<int32_t> items((size_t)off.back());
-        for (size_t w = 0; w < work.size(); ++w) std::copy(nodes[work[w]].list.begin(), nodes[work[w]].list.end(), items.begin() + off[w]);
-        HIP_TRY(nullptr, up(d_items, items.data(), items.size() * 4));
-        HIP_TRY(nullptr, up(d_off, off.data(), off.size() * 8));
-        const long long nw = (long long)work.size();
-        const long long target_chunks = std::max<long long>(1, 4096 / nw);
-        const int chunk_len = (int)std::max<long long>(TS_BLOCK, (((n_planes + target_chunks - 1) / target_chunks) + TS_BLOCK - 1) / TS_BLOCK * TS_BLOCK);
-        const int chunks = (n_planes + chunk_len - 1) / chunk_len;
-        HIP_TRY(nullptr, d_part.ensure((size_t)nw * chunks * sizeof(int4), st));
-        HIP_TRY(nullptr, timed(ms_split, [&] {
-            hipLaunchKernelGGL(k_tree_split, dim3((unsigned)nw, (unsigned)chunks), dim3(TS_BLOCK), 0, st, n_planes, hw, chunk_len, d_off.as<long long>(),
-                               d_items.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(), owner, d_part.as<int4>());
-        }));
-        std::vector<int4> part((size_t)nw * chunks);
-        HIP_TRY(nullptr, hipMemcpy(part.data(), d_part.p, part.size() * sizeof(int4), hipMemcpyDeviceToHost));
-        std::vector<int32_t> item_plane(items.size(), 0);
-        std::vector<int> inner;
-        for (long long w = 0; w < nw; ++w) {
-            int bmx = TS_NONE, bn0 = TS_NONE, bh = -1;
-            for (int c = 0; c < chunks; ++c) {
-                const int4 q = part[(size_t)(w * chunks + c)];
-                if (q.z < 0) continue;
-                if (bh < 0 || q.x < bmx || (q.x == bmx && (q.y < bn0 || (q.y == bn0 && q.z < bh)))) { bmx = q.x; bn0 = q.y; bh = q.z; }
-            }
-            Node &nd = nodes[work[(size_t)w]];
-            if (bh < 0 || bmx >= (int)nd.list.size()) continue;   // no plane makes progress: a leaf
-            nd.plane = bh;
-            inner.push_back((int)w);
-            std::fill(item_plane.begin() + off[w], item_plane.begin() + off[w + 1], bh);
-        }
-        if (inner.empty()) break;
-        HIP_TRY(nullptr, up(d_iplane, item_plane.data(), item_plane.size() * 4));
-        HIP_TRY(nullptr, d_side.ensure(items.size(), st));
-        HIP_TRY(nullptr, timed(ms_split, [&] {
-            hipLaunchKernelGGL(k_tree_partition, dim3((unsigned)((items.size() + 255) / 256)), dim3(256), 0, st, (long long)items.size(), hw,
-                               d_items.as<int32_t>(), d_iplane.as<int32_t>(), d_plus.as<unsigned long long>(), d_minus.as<unsigned long long>(),
-                               d_side.as<int8_t>());
-        }));
-        std::vector<int8_t> side(items.size());
-        HIP_TRY(nullptr, hipMemcpy(side.data(), d_side.p, side.size(), hipMemcpyDeviceToHost));
-        // children and the one-sided (node, region) pairs of tau
-        std::vector<int32_t> pairs, nplane;
-        std::vector<int> next;
-        for (size_t q = 0; q < inner.size(); ++q) {
-            const long long w = inner[q];
-            const int k = work[(size_t)w];
-            Node cp, cm;
-            cp.depth = cm.depth = nodes[k].depth + 1;
-            for (long long i = off[w]; i < off[w + 1]; ++i) {
-                const int32_t j = items[(size_t)i];
-                const int sd = side[(size_t)i];
-                if (sd != 2) cp.list.push_back(j);
-                if (sd != 1) cm.list.push_back(j);
-                if (sd) { pairs.push_back((int32_t)q); pairs.push_back(j); pairs.push_back(sd - 1); }
-            }
-            nplane.push_back(nodes[k].plane);
-            const int ip = (int)nodes.size();
-            nodes[k].child[0] = ip; nodes[k].child[1] = ip + 1;
-            nodes[k].list.clear(); nodes[k].list.shrink_to_fit();
-            nodes.push_back(std::move(cp)); nodes.push_back(std::move(cm));
-            next.push_back(ip); next.push_back(ip + 1);
-        }
-        const long long n_pairs = (long long)pairs.size() / 3;
-        std::vector<unsigned long long> tau(2 * inner.size(), 0ull);
-        if (n_pairs > 0) {
-            HIP_TRY(nullptr, up(d_pairs, pairs.data(), pairs.size() * 4));
-            HIP_TRY(nullptr, up(d_nplane, nplane.data(), nplane.size() * 4));
-            HIP_TRY(nullptr, up(d_tau, tau.data(), tau.size() * 8));
-            TreeClassifyArgs b = a;
-            b.n_pairs = n_pairs; b.pair = d_pairs.as<int32_t>(); b.node_plane = d_nplane.as<int32_t>(); b.tau = d_tau.as<unsigned long long>();
-            HIP_TRY(nullptr, timed(ms_tau, [&] { hipLaunchKernelGGL((k_tree_classify<1>), dim3((unsigned)n_pairs), dim3(64), lds, st, b); }));
-            HIP_TRY(nullptr, hipMemcpy(tau.data(), d_tau.p, tau.size() * 8, hipMemcpyDeviceToHost));
-            tau_lps += n_pairs;
-        }
-        for (size_t q = 0; q < inner.size(); ++q) {
-            Node &nd = nodes[work[(size_t)inner[q]]];
-            for (int sd = 0; sd < 2; ++sd) { double v; std::memcpy(&v, &tau[2 * q + sd], 8); nd.tau[sd] = v; }
-        }
-        level.swap(next);
-    }
-    HIP_TRY(nullptr, hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
-    // flatten
-    const int64_t N = (int64_t)nodes.size();
-    std::vector<int32_t> plane_v((size_t)N), child_v((size_t)(2 * N)), items_v;
-    std::vector<double> tau_v((size_t)(2 * N));
-    std::vector<int64_t> off_v((size_t)N + 1, 0);
-    int64_t n_leaves = 0, max_leaf = 0, depth = 0;
-    for (int64_t k = 0; k < N; ++k) {
-        const Node &nd = nodes[(size_t)k];
-        plane_v[(size_t)k] = nd.plane;
-        for (int q = 0; q < 2; ++q) { child_v[(size_t)(2 * k + q)] = nd.child[q]; tau_v[(size_t)(2 * k + q)] = nd.tau[q]; }
-        if (nd.plane < 0) {
-            items_v.insert(items_v.end(), nd.list.begin(), nd.list.end());
-            ++n_leaves;
-            max_leaf = std::max<int64_t>(max_leaf, (int64_t)nd.list.size());
-        }
-        off_v[(size_t)k + 1] = (int64_t)items_v.size();
-        depth = std::max<int64_t>(depth, nd.depth);
-    }
-    if (int rc = tree_attach(L, n_planes, planes, N, plane_v.data(), child_v.data(), tau_v.data(), off_v.data(), items_v.data(), tol)) return rc;
-    if (stats) {
-        stats->n_nodes = N; stats->n_leaves = n_leaves; stats->depth = depth; stats->max_leaf = max_leaf;
-        stats->leaf_items = (int64_t)items_v.size();
-        stats->mean_leaf = n_leaves ? (double)items_v.size() / (double)n_leaves : 0.0;
-        stats->pairs = (int64_t)cnt[0]; stats->box_pairs = (int64_t)cnt[1]; stats->lps = (int64_t)cnt[2]; stats->pivots = (int64_t)cnt[3];
-        stats->capped = (int64_t)cnt[4]; stats->tau_lps = tau_lps; stats->bitset_bytes = bitset_bytes;
-        stats->ms_classify = ms_classify; stats->ms_split = ms_split; stats->ms_tau = ms_tau;
-        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    }
-    return MPC_OK;
-}
-
-extern "C" int mpc_locator_destroy(mpc_locator *L) {
-    if (!L) return MPC_OK;
-    (void)hipSetDevice(L->device);
-    if (L->stream) (void)hipStreamSynchronize(L->stream);
-    for (DevBuf *b : {&L->row_off, &L->row_region, &L->row_end, &L->ef, &L->xlaw, &L->Q, &L->c, &L->H, &L->theta, &L->region, &L->x, &L->masks, &L->sorted_masks,
-                      &L->sorted_region, &L->row_info, &L->theta2, &L->region2, &L->t_planes, &L->t_plane, &L->t_child, &L->t_tau, &L->t_off,
-                      &L->t_items}) b->release();
-    if (L->e0) (void)hipEventDestroy(L->e0);
-    if (L->e1) (void)hipEventDestroy(L->e1);
-    if (L->stream) (void)hipStreamDestroy(L->stream);
-    delete L;
-    return MPC_OK;
-}
-
-// ---- closed-loop simulation (closed_loop.hpp) --------------------------------------------------------------------------
-constexpr long long SIM_DEFAULT_BUDGET = 4ll << 30;
-
-extern "C" int mpc_locator_simulate(mpc_locator *L, int64_t n, int32_t steps, const double *theta0, int32_t n_u, const int32_t *inputs,
-                                    const double *A, const double *B, const double *c, const double *w, const double *box_lo,
-                                    const double *box_hi, uint64_t seed, double tol, double stop_tol, int32_t flags, int64_t budget,
-                                    double *theta, double *u, int32_t *region, int32_t *status, int32_t *exit_step, mpc_sim_stats *stats) {
-    const char *who = "mpc_locator_simulate";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!L) return bad("no locator");
-    const int nt = L->n_t, nx = L->n_x;
-    const bool final_only = (flags & MPC_SIM_FINAL) != 0, tree = (flags & MPC_LOCATE_TREE) != 0, walk = (flags & MPC_LOCATE_WALK) != 0;
-    const bool overlapping = (flags & MPC_LOCATE_OVERLAPPING) != 0, inclusive = (flags & MPC_LOCATE_INCLUSIVE) != 0;
-    if (n < 0 || n > (1ll << 40) || steps < 1 || steps > (1 << 30)) return bad("n must lie in 0..2^40 and steps in 1..2^30");
-    if (nt < 1 || nt > 16) return bad("n_theta must lie in 1..16");
-    if (n_u < 1 || n_u > 16) return bad("n_u must lie in 1..16");
-    if (L->n_regions < 1) return bad("the locator holds no region");
-    if (n > 0 && (!theta0 || !theta || !status || !exit_step)) return bad("missing theta0, theta, status or exit_step");
-    if (n > 0 && !final_only && (!u || !region)) return bad("a full record needs u and region");
-    if (!inputs || !A || !B) return bad("missing inputs, A or B");
-    for (int i = 0; i < n_u; ++i)
-        if (inputs[i] < 0 || inputs[i] >= nx) return bad("input index " + std::to_string(inputs[i]) + " is out of range (0 <= inputs < n_x = " + std::to_string(nx) + ")");
-    auto finite = [](const double *v, long long k) { for (long long i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false; return true; };
-    if (!finite(A, (long long)nt * nt) || !finite(B, (long long)nt * n_u) || (c && !finite(c, nt))) return bad("A, B and c must be finite");
-    if (n > 0 && !finite(theta0, n * nt)) return bad("theta0 must be finite");
-    if (w && (box_lo || box_hi)) return bad("a disturbance array and a box exclude each other");
-    if ((box_lo == nullptr) != (box_hi == nullptr)) return bad("box_lo and box_hi go together");
-    if (box_lo)
-        for (int t = 0; t < nt; ++t)
-            if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] <= box_hi[t])) return bad("the box must be finite with lo <= hi");
-    if (w && n > 0 && !finite(w, n * (long long)steps * nt)) return bad("the disturbance must be finite");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (std::isnan(stop_tol)) return bad("stop_tol must not be NaN (< 0: off)");
-    if (tree && walk) return bad("MPC_LOCATE_TREE and MPC_LOCATE_WALK exclude each other");
-    if (tree && !L->has_tree) return bad("MPC_LOCATE_TREE without an attached tree");
-    if (tree && !(tol <= L->tree_tol)) return bad("tol is larger than the tolerance the tree was built for");
-    if (walk && (!L->has_adj || overlapping || inclusive)) return bad("MPC_LOCATE_WALK needs adjacency, and neither MPC_LOCATE_OVERLAPPING nor MPC_LOCATE_INCLUSIVE");
-    // device bytes of the record and the inputs (doubles: no overflow for any n, steps that pass above)
-    const double rec = final_only ? (double)n * nt * 8 : (double)n * ((double)(steps + 1) * nt * 8 + (double)steps * (n_u * 8 + 4));
-    const double bytes = rec + (double)n * nt * 8 + (w ? (double)n * steps * nt * 8 : 0.0);
-    const double cap = budget > 0 ? (double)budget : (double)SIM_DEFAULT_BUDGET;
-    if (bytes > cap)
-        return bad("the run needs " + std::to_string((long long)bytes) + " device bytes, more than the budget of " + std::to_string((long long)cap) +
-                   " (record the final states only, or run fewer trajectories at a time)");
-    if (n == 0) return MPC_OK;
-    HIP_TRY(nullptr, hipSetDevice(L->device));
-    hipStream_t st = L->stream;
-    const size_t n_th = (size_t)(final_only ? 1 : steps + 1) * n * nt, n_uu = final_only ? 0 : (size_t)steps * n * n_u, n_rg = final_only ? 0 : (size_t)steps * n;
-    // the plant in one block: A [nt][nt], B [nt][n_u], c [nt], lo [nt], hi [nt], then the inputs
-    std::vector<double> plant((size_t)nt * nt + (size_t)nt * n_u + 3 * (size_t)nt, 0.0);
-    std::memcpy(plant.data(), A, sizeof(double) * nt * nt);
-    std::memcpy(plant.data() + nt * nt, B, sizeof(double) * nt * n_u);
-    const size_t oc = (size_t)nt * nt + (size_t)nt * n_u, olo = oc + nt, ohi = olo + nt;
-    if (c) std::memcpy(plant.data() + oc, c, sizeof(double) * nt);
-    if (box_lo) { std::memcpy(plant.data() + olo, box_lo, sizeof(double) * nt); std::memcpy(plant.data() + ohi, box_hi, sizeof(double) * nt); }
-    DevBuf d_th0, d_th, d_u, d_rg, d_st, d_ex, d_w, d_plant, d_in, d_cnt;
-    unsigned long long cnt[3] = {0, 0, 0};
-    float ms = 0.0f;
-    auto run = [&]() -> hipError_t {
-        hipError_t e;
-#define SIM_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-        SIM_TRY(d_th0.ensure((size_t)n * nt * 8, st));
-        SIM_TRY(d_th.ensure(n_th * 8, st));
-        if (!final_only) { SIM_TRY(d_u.ensure(n_uu * 8, st)); SIM_TRY(d_rg.ensure(n_rg * 4, st)); }
-        SIM_TRY(d_st.ensure((size_t)n * 4, st));
-        SIM_TRY(d_ex.ensure((size_t)n * 4, st));
-        if (w) SIM_TRY(d_w.ensure((size_t)n * steps * nt * 8, st));
-        SIM_TRY(d_plant.ensure(plant.size() * 8, st));
-        SIM_TRY(d_in.ensure((size_t)n_u * 4, st));
-        SIM_TRY(d_cnt.ensure(3 * 8, st));
-        SIM_TRY(hipMemcpyAsync(d_th0.p, theta0, (size_t)n * nt * 8, hipMemcpyHostToDevice, st));
-        if (w) SIM_TRY(hipMemcpyAsync(d_w.p, w, (size_t)n * steps * nt * 8, hipMemcpyHostToDevice, st));
-        SIM_TRY(hipMemcpyAsync(d_plant.p, plant.data(), plant.size() * 8, hipMemcpyHostToDevice, st));
-        SIM_TRY(hipMemcpyAsync(d_in.p, inputs, (size_t)n_u * 4, hipMemcpyHostToDevice, st));
-        SIM_TRY(hipMemsetAsync(d_cnt.p, 0, 3 * 8, st));
-        if (!final_only) {   // what lies after a trajectory's end is never written: NaN (all bits set) and region -1
-            SIM_TRY(hipMemsetAsync(d_th.p, 0xff, n_th * 8, st));
-            SIM_TRY(hipMemsetAsync(d_u.p, 0xff, n_uu * 8, st));
-            SIM_TRY(hipMemsetAsync(d_rg.p, 0xff, n_rg * 4, st));
-        }
-        const double *pl = d_plant.as<double>();
-        SimArgs a{};
-        a.n = n; a.steps = steps; a.nt = nt; a.nx = nx; a.nu = n_u;
-        a.n_regions = L->n_regions; a.n_rows = L->n_rows;
-        a.row_off = L->row_off.as<long long>(); a.row_region = L->row_region.as<int32_t>(); a.row_end = L->row_end.as<int32_t>();
-        a.ef = L->ef.as<double>(); a.xlaw = L->xlaw.as<double>();
-        a.Q = L->hasQ ? L->Q.as<double>() : nullptr; a.cvec = L->hasc ? L->c.as<double>() : nullptr; a.H = L->hasH ? L->H.as<double>() : nullptr;
-        a.tol = tol; a.overlapping = overlapping; a.inclusive = inclusive;
-        if (walk) {
-            a.row_info = L->row_info.as<int32_t>(); a.sorted_region = L->sorted_region.as<int32_t>();
-            a.masks = L->masks.as<unsigned long long>(); a.sorted_masks = L->sorted_masks.as<unsigned long long>();
-            a.n_c = L->n_c; a.max_walk = 384;   // the step limit of mpc_locator_query's walk
-        }
-        if (tree) {
-            a.planes = L->t_planes.as<double>(); a.node_tau = L->t_tau.as<double>(); a.node_plane = L->t_plane.as<int32_t>();
-            a.node_child = L->t_child.as<int32_t>(); a.items = L->t_items.as<int32_t>(); a.node_off = L->t_off.as<long long>();
-        }
-        a.theta0 = d_th0.as<double>(); a.inputs = d_in.as<int32_t>();
-        a.A = pl; a.B = pl + nt * nt; a.c = c ? pl + oc : nullptr; a.w = w ? d_w.as<double>() : nullptr;
-        a.lo = box_lo ? pl + olo : nullptr; a.hi = box_lo ? pl + ohi : nullptr;
-        a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32) ^ MPC_SIM_KEY_SALT;
-        a.stop_tol = stop_tol; a.final_only = final_only;
-        a.theta = d_th.as<double>(); a.u = final_only ? nullptr : d_u.as<double>(); a.region = final_only ? nullptr : d_rg.as<int32_t>();
-        a.status = d_st.as<int32_t>(); a.exit_step = d_ex.as<int32_t>(); a.counters = d_cnt.as<unsigned long long>();
-        const dim3 g((unsigned)((n + SIM_BLOCK - 1) / SIM_BLOCK)), b(SIM_BLOCK);
-        SIM_TRY(hipEventRecord(L->e0, st));
-#define MPC_SIM(NT_, NU_, MODE_) hipLaunchKernelGGL((k_simulate<NT_, NU_, MODE_>), g, b, 0, st, a)
-#define MPC_SIM_NU(NT_, MODE_) do { if (n_u <= 4) MPC_SIM(NT_, 4, MODE_); else MPC_SIM(NT_, 16, MODE_); } while (0)
-#define MPC_SIM_NT(MODE_) do { if (nt <= 4) MPC_SIM_NU(4, MODE_); else if (nt <= 8) MPC_SIM_NU(8, MODE_); else MPC_SIM_NU(16, MODE_); } while (0)
-        if (tree) MPC_SIM_NT(SIM_TREE);
-        else if (walk && L->mask_words == 2) MPC_SIM_NT(SIM_WALK2);
-        else if (walk) MPC_SIM_NT(SIM_WALK4);
-        else MPC_SIM_NT(SIM_SCAN);
-#undef MPC_SIM_NT
-#undef MPC_SIM_NU
-#undef MPC_SIM
-        SIM_TRY(hipGetLastError());
-        SIM_TRY(hipEventRecord(L->e1, st));
-        SIM_TRY(hipMemcpyAsync(theta, d_th.p, n_th * 8, hipMemcpyDeviceToHost, st));
-        if (!final_only) {
-            SIM_TRY(hipMemcpyAsync(u, d_u.p, n_uu * 8, hipMemcpyDeviceToHost, st));
-            SIM_TRY(hipMemcpyAsync(region, d_rg.p, n_rg * 4, hipMemcpyDeviceToHost, st));
-        }
-        SIM_TRY(hipMemcpyAsync(status, d_st.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        SIM_TRY(hipMemcpyAsync(exit_step, d_ex.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-        SIM_TRY(hipMemcpyAsync(cnt, d_cnt.p, 3 * 8, hipMemcpyDeviceToHost, st));
-        SIM_TRY(hipStreamSynchronize(st));
-        SIM_TRY(hipEventElapsedTime(&ms, L->e0, L->e1));
-#undef SIM_TRY
-        return hipSuccess;
-    };
-    const hipError_t e = run();
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    for (DevBuf *q : {&d_th0, &d_th, &d_u, &d_rg, &d_st, &d_ex, &d_w, &d_plant, &d_in, &d_cnt}) q->release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    if (stats) {
-        stats->traj_steps = (int64_t)cnt[0]; stats->crossings = (int64_t)cnt[1]; stats->fallbacks = (int64_t)cnt[2];
-        stats->mode = tree ? MPC_LOCATE_TREE : walk ? MPC_LOCATE_WALK : 0;
-        stats->ms = ms;
-    }
-    return MPC_OK;
-}
-
-// ---- vertex enumeration of a batch of polytopes (vertices.hpp) ---------------------------------------------------------
-constexpr long long VX_DEFAULT_BUDGET = 4ll << 30, VX_DEFAULT_SLAB = 256, VX_MAX_SLAB = 1ll << 24;
-
-// device bytes of one polytope's slab: two lists of generators (y, Z), the products s and the two index lists
-template <int NT> static double vx_slab_bytes(long long cap) { return (double)cap * (2.0 * (NT + 1) * 8 + 2.0 * VX_MW * 8 + 8 + 2 * 4); }
-
-template <int NT>
-static hipError_t vx_run(int nt, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol, long long cap, long long max_slab,
-                         double budget, std::vector<int32_t> &status, std::vector<int64_t> &nv, std::vector<int64_t> &nr,
-                         std::vector<std::vector<double>> &hv, std::vector<std::vector<uint64_t>> &hz, std::vector<std::vector<double>> &hr,
-                         mpc_vertex_stats &stats) {
-    hipError_t e = hipSuccess;
-#define VX_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-    const long long rows = row_off[n_poly];
-    DevBuf d_off, d_ef, d_poly, d_y, d_z, d_s, d_i, d_st, d_nv, d_nr, d_buf, d_cnt, d_vo, d_ro, d_ov, d_oz, d_or;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto cleanup = [&]() {
-        (void)hipDeviceSynchronize();
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        for (DevBuf *b : {&d_off, &d_ef, &d_poly, &d_y, &d_z, &d_s, &d_i, &d_st, &d_nv, &d_nr, &d_buf, &d_cnt, &d_vo, &d_ro, &d_ov, &d_oz, &d_or})
-            b->release();
-    };
-    struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{cleanup};
-    VX_TRY(hipEventCreate(&e0));
-    VX_TRY(hipEventCreate(&e1));
-    VX_TRY(d_off.ensure((size_t)(n_poly + 1) * 8, nullptr));
-    VX_TRY(d_ef.ensure(std::max<size_t>(8, (size_t)rows * (nt + 1) * 8), nullptr));
-    VX_TRY(hipMemcpy(d_off.p, row_off, (size_t)(n_poly + 1) * 8, hipMemcpyHostToDevice));
-    if (rows) VX_TRY(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (nt + 1) * 8, hipMemcpyHostToDevice));
-    std::vector<int32_t> pending(n_poly);
-    for (int64_t p = 0; p < n_poly; ++p) pending[p] = (int32_t)p;
-    for (;;) {
-        const double per = vx_slab_bytes<NT>(cap);
-        const long long chunk = std::max(1ll, std::min<long long>({(long long)pending.size(), (long long)(budget / per), 1ll << 16}));
-        std::vector<int32_t> over;
-        for (size_t start = 0; start < pending.size(); start += (size_t)chunk) {
-            const long long nq = std::min<long long>(chunk, (long long)(pending.size() - start));
-            VX_TRY(d_poly.ensure((size_t)nq * 4, nullptr));
-            VX_TRY(d_y.ensure((size_t)nq * 2 * cap * (NT + 1) * 8, nullptr));
-            VX_TRY(d_z.ensure((size_t)nq * 2 * cap * VX_MW * 8, nullptr));
-            VX_TRY(d_s.ensure((size_t)nq * cap * 8, nullptr));
-            VX_TRY(d_i.ensure((size_t)nq * 2 * cap * 4, nullptr));
-            for (DevBuf *b : {&d_st, &d_nv, &d_nr, &d_buf}) VX_TRY(b->ensure((size_t)nq * 4, nullptr));
-            VX_TRY(d_cnt.ensure((size_t)nq * 3 * 8, nullptr));
-            VX_TRY(hipMemcpy(d_poly.p, pending.data() + start, (size_t)nq * 4, hipMemcpyHostToDevice));
-            VxArgs a{};
-            a.nt = nt; a.n = nq; a.poly = d_poly.as<int32_t>(); a.row_off = d_off.as<long long>(); a.ef = d_ef.as<double>(); a.cap = cap;
-            a.slab_y = d_y.as<double>(); a.slab_z = d_z.as<unsigned long long>(); a.slab_s = d_s.as<double>(); a.slab_i = d_i.as<int32_t>();
-            a.tol = tol; a.status = d_st.as<int32_t>(); a.n_vert = d_nv.as<int32_t>(); a.n_ray = d_nr.as<int32_t>(); a.buf = d_buf.as<int32_t>();
-            a.counters = d_cnt.as<unsigned long long>();
-            VX_TRY(hipEventRecord(e0, nullptr));
-            hipLaunchKernelGGL((k_region_vertices<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, a);
-            VX_TRY(hipGetLastError());
-            VX_TRY(hipEventRecord(e1, nullptr));
-            std::vector<int32_t> st(nq), cv(nq), cr(nq), cb(nq);
-            std::vector<unsigned long long> cnt((size_t)nq * 3);
-            VX_TRY(hipMemcpy(st.data(), d_st.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-            VX_TRY(hipMemcpy(cv.data(), d_nv.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-            VX_TRY(hipMemcpy(cr.data(), d_nr.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-            VX_TRY(hipMemcpy(cnt.data(), d_cnt.p, (size_t)nq * 3 * 8, hipMemcpyDeviceToHost));
-            float ms = 0.0f;
-            VX_TRY(hipEventElapsedTime(&ms, e0, e1));
-            stats.ms += ms;
-            stats.launches += 1;
-            std::vector<long long> vo(nq), ro(nq);
-            long long tv = 0, tr = 0;
-            for (long long i = 0; i < nq; ++i) {
-                const int32_t p = pending[start + i];
-                stats.generators += (int64_t)cnt[i * 3 + 0];
-                stats.max_list = std::max<int64_t>(stats.max_list, (int64_t)cnt[i * 3 + 1]);
-                stats.merges += (int64_t)cnt[i * 3 + 2];
-                status[p] = st[i];
-                if (st[i] == VX_OVERFLOW) { over.push_back(p); cv[i] = cr[i] = 0; }
-                nv[p] = cv[i]; nr[p] = cr[i];
-                vo[i] = tv; ro[i] = tr;
-                tv += cv[i]; tr += cr[i];
-            }
-            if (tv + tr == 0) continue;
-            // pack this launch's results (the counts of overflowed polytopes are 0 on the device too)
-            VX_TRY(d_vo.ensure((size_t)nq * 8, nullptr));
-            VX_TRY(d_ro.ensure((size_t)nq * 8, nullptr));
-            VX_TRY(d_ov.ensure(std::max<size_t>(8, (size_t)tv * nt * 8), nullptr));
-            VX_TRY(d_oz.ensure(std::max<size_t>(8, (size_t)tv * VX_OUT_MW * 8), nullptr));
-            VX_TRY(d_or.ensure(std::max<size_t>(8, (size_t)tr * nt * 8), nullptr));
-            VX_TRY(hipMemcpy(d_vo.p, vo.data(), (size_t)nq * 8, hipMemcpyHostToDevice));
-            VX_TRY(hipMemcpy(d_ro.p, ro.data(), (size_t)nq * 8, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL((k_vertices_gather<NT>), dim3((unsigned)nq), dim3(VX_BLOCK), 0, nullptr, nt, cap, d_y.as<double>(),
-                               d_z.as<unsigned long long>(), d_nv.as<int32_t>(), d_nr.as<int32_t>(), d_buf.as<int32_t>(), d_vo.as<long long>(),
-                               d_ro.as<long long>(), d_ov.as<double>(), d_oz.as<unsigned long long>(), d_or.as<double>());
-            VX_TRY(hipGetLastError());
-            std::vector<double> ov((size_t)tv * nt), orr((size_t)tr * nt);
-            std::vector<uint64_t> oz((size_t)tv * VX_OUT_MW);
-            if (tv) {
-                VX_TRY(hipMemcpy(ov.data(), d_ov.p, ov.size() * 8, hipMemcpyDeviceToHost));
-                VX_TRY(hipMemcpy(oz.data(), d_oz.p, oz.size() * 8, hipMemcpyDeviceToHost));
-            }
-            if (tr) VX_TRY(hipMemcpy(orr.data(), d_or.p, orr.size() * 8, hipMemcpyDeviceToHost));
-            for (long long i = 0; i < nq; ++i) {
-                const int32_t p = pending[start + i];
-                hv[p].assign(ov.begin() + vo[i] * nt, ov.begin() + (vo[i] + cv[i]) * nt);
-                hz[p].assign(oz.begin() + vo[i] * VX_OUT_MW, oz.begin() + (vo[i] + cv[i]) * VX_OUT_MW);
-                hr[p].assign(orr.begin() + ro[i] * nt, orr.begin() + (ro[i] + cr[i]) * nt);
-            }
-        }
-        stats.slab = cap;
-        if (over.empty()) break;
-        // repeat only the overflowed polytopes with a four times larger slab, while one polytope's slab fits the budget
-        const long long next = cap * 4;
-        if (next > max_slab || vx_slab_bytes<NT>(next) > budget) break;
-        stats.repeats += (int64_t)over.size();
-        pending.swap(over);
-        cap = next;
-    }
-#undef VX_TRY
-    return hipSuccess;
-}
-
-extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, double tol,
-                                   int64_t slab, int64_t max_slab, int64_t budget, int64_t *v_cap, int64_t *r_cap, int32_t *status,
-                                   int64_t *n_vert, int64_t *n_ray, double *vertices, uint64_t *incidence, double *rays,
-                                   mpc_vertex_stats *stats) {
-    const char *who = "mpc_region_vertices";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
-    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
-    if (!row_off || !v_cap || !r_cap) return bad("missing row_off, v_cap or r_cap");
-    if (row_off[0] != 0) return bad("row_off[0] must be 0");
-    for (int64_t p = 0; p < n_poly; ++p) {
-        const int64_t r = row_off[p + 1] - row_off[p];
-        if (r < 0) return bad("row_off decreases");
-        if (r > VX_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VX_MAX_ROWS));
-    }
-    const long long rows = row_off[n_poly];
-    if (rows && !ef_rows) return bad("missing ef_rows");
-    for (long long i = 0; i < rows * (n_t + 1); ++i)
-        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    const long long slab0 = slab > 0 ? slab : VX_DEFAULT_SLAB, smax = max_slab > 0 ? max_slab : VX_MAX_SLAB;
-    if (slab0 < 18 || slab0 > smax || smax > VX_MAX_SLAB) return bad("need 18 <= slab <= max_slab <= 2^24 generators");
-    const double cap_bytes = budget > 0 ? (double)budget : (double)VX_DEFAULT_BUDGET;
-    const int ntk = n_t <= 4 ? 4 : n_t <= 8 ? 8 : 16;
-    const double per = ntk == 4 ? vx_slab_bytes<4>(slab0) : ntk == 8 ? vx_slab_bytes<8>(slab0) : vx_slab_bytes<16>(slab0);
-    if (per > cap_bytes)
-        return bad("the budget of " + std::to_string((long long)cap_bytes) + " device bytes is too small for one polytope's slab (" +
-                   std::to_string((long long)per) + " bytes)");
-    if (n_poly > 0 && (!status || !n_vert || !n_ray)) return bad("missing status, n_vert or n_ray");
-    if (n_poly == 0) { *v_cap = 0; *r_cap = 0; return MPC_OK; }
-    const int ndev = device_count_cached();
-    if (ndev < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return bad("device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    std::vector<int32_t> st(n_poly, VX_OVERFLOW);
-    std::vector<int64_t> nv(n_poly, 0), nr(n_poly, 0);
-    std::vector<std::vector<double>> hv(n_poly), hr(n_poly);
-    std::vector<std::vector<uint64_t>> hz(n_poly);
-    mpc_vertex_stats s{};
-    hipError_t e;
-    if (ntk == 4) e = vx_run<4>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
-    else if (ntk == 8) e = vx_run<8>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
-    else e = vx_run<16>(n_t, n_poly, row_off, ef_rows, tol, slab0, smax, cap_bytes, st, nv, nr, hv, hz, hr, s);
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    long long tv = 0, tr = 0;
-    for (int64_t p = 0; p < n_poly; ++p) {
-        status[p] = st[p]; n_vert[p] = nv[p]; n_ray[p] = nr[p];
-        if (st[p] == VX_OVERFLOW) s.overflow += 1;
-        tv += nv[p]; tr += nr[p];
-    }
-    if (stats) *stats = s;
-    const bool fits = tv <= *v_cap && tr <= *r_cap;
-    *v_cap = tv; *r_cap = tr;
-    if (!fits) return fail(nullptr, MPC_ERR_CAPACITY, std::string(who) + ": the outputs need " + std::to_string(tv) + " vertices and " +
-                                                            std::to_string(tr) + " rays (returned in v_cap, r_cap)");
-    if ((tv && (!vertices || !incidence)) || (tr && !rays)) return bad("missing vertices, incidence or rays");
-    long long pv = 0, pr = 0;
-    for (int64_t p = 0; p < n_poly; ++p) {
-        if (nv[p]) {
-            std::memcpy(vertices + pv * n_t, hv[p].data(), hv[p].size() * 8);
-            std::memcpy(incidence + pv * VX_OUT_MW, hz[p].data(), hz[p].size() * 8);
-        }
-        if (nr[p]) std::memcpy(rays + pr * n_t, hr[p].data(), hr[p].size() * 8);
-        pv += nv[p]; pr += nr[p];
-    }
-    return MPC_OK;
-}
-
-// ---- merging regions with equal laws (merge.hpp) ---------------------------------------------------------------------
-static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (n_t < 1 || n_t > TR_MAX_NT) return bad("n_t must lie in 1..16");
-    if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad("bad region count or missing row_off");
-    if (n_regions > 0x7fffffffll) return bad("too many regions for one launch");
-    if (n_regions > 0 && row_off[0] != 0) return bad("row_off[0] must be 0");
-    *m_max = 1;
-    for (int64_t r = 0; r < n_regions; ++r) {
-        const int64_t k = row_off[r + 1] - row_off[r];
-        if (k < 1 || k > MG_MAX_ROWS) return bad("every region needs 1..256 rows");
-        *m_max = std::max<int>(*m_max, (int)k);
-    }
-    const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
-    if (rows > 0 && !ef_rows) return bad("missing ef_rows");
-    for (int64_t i = 0; i < rows; ++i) {
-        const double *row = ef_rows + i * (n_t + 1);
-        double nn = 0.0;
-        bool finite = std::isfinite(row[0]);
-        for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
-        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("rows must be finite with unit normals");
-    }
-    return MPC_OK;
-}
-
-extern "C" int mpc_merge_regions(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *xs,
-                                 double *box, int32_t *status, int64_t *stats, float *ms) {
-    const char *who = "mpc_merge_regions";
-    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
-    int m_max = 1;
-    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (n_regions == 0) return MPC_OK;
-    if (!xs || !box || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_regions: missing output array");
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    const long long rows = row_off[n_regions];
-    const size_t lds = tr_lds_bytes(m_max, n_t);
-    DevBuf d_off, d_ef, d_xs, d_box, d_st, d_cnt;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure((size_t)rows * (n_t + 1) * 8, nullptr));
-    chk(d_xs.ensure((size_t)n_regions * n_t * 8, nullptr)); chk(d_box.ensure((size_t)n_regions * 2 * n_t * 8, nullptr));
-    chk(d_st.ensure((size_t)n_regions * 4, nullptr)); chk(d_cnt.ensure(3 * 8, nullptr));
-    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n_t + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemset(d_cnt.p, 0, 3 * 8));
-    }
-    if (e == hipSuccess && lds > 48 * 1024)
-        chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_regions), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (e == hipSuccess) {
-        chk(hipEventRecord(e0, nullptr));
-        hipLaunchKernelGGL(k_merge_regions, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
-                           d_off.as<long long>(), d_ef.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_st.as<int32_t>(),
-                           d_cnt.as<unsigned long long>());
-        chk(hipGetLastError());
-        chk(hipEventRecord(e1, nullptr));
-        chk(hipMemcpy(xs, d_xs.p, (size_t)n_regions * n_t * 8, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(box, d_box.p, (size_t)n_regions * 2 * n_t * 8, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(status, d_st.p, (size_t)n_regions * 4, hipMemcpyDeviceToHost));
-        unsigned long long cnt[3] = {0, 0, 0};
-        chk(hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
-        if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
-        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
-    }
-    (void)hipDeviceSynchronize();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    for (DevBuf *bf : {&d_off, &d_ef, &d_xs, &d_box, &d_st, &d_cnt}) bf->release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return MPC_OK;
-}
-
-extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
-                               const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
-                               uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms) {
-    const char *who = "mpc_merge_pairs";
-    if (stats) for (int i = 0; i < 7; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
-    int m_max = 1;
-    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: tol must be finite and >= 0");
-    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: n_pairs must lie in 0..2^31 - 1");
-    if (n_pairs == 0) return MPC_OK;
-    if (!xs || !box || !pair_a || !pair_b || !env_a || !env_b || !verdict || !t_max)
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: missing array");
-    int pair_rows = 2;
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t p = pair_a[k], q = pair_b[k];
-        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: a pair names a region out of range, or the same region twice");
-        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q] + 2));
-    }
-    for (int64_t i = 0; i < n_regions * n_t; ++i)
-        if (std::isnan(xs[i]) || std::isinf(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: xs must be finite");
-    int ndev = 0;
-    if ((ndev = device_count_cached()) < 1) return fail(nullptr, MPC_ERR_HIP, "no HIP device available (libmpcombi_hip has no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(nullptr, MPC_ERR_INVALID, "device index out of range");
-    HIP_TRY(nullptr, hipSetDevice(device));
-    const long long rows = row_off[n_regions];
-    const int lds_rows = std::max(pair_rows, m_max);
-    const size_t lds = tr_lds_bytes(lds_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_env adds 64)
-    DevBuf d_off, d_ef, d_xs, d_box, d_pa, d_pb, d_ea, d_eb, d_v, d_t, d_cnt;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    const size_t np = (size_t)n_pairs, words = np * MG_WORDS * 8;
-    chk(d_off.ensure((size_t)(n_regions + 1) * 8, nullptr)); chk(d_ef.ensure((size_t)rows * (n_t + 1) * 8, nullptr));
-    chk(d_xs.ensure((size_t)n_regions * n_t * 8, nullptr)); chk(d_box.ensure((size_t)n_regions * 2 * n_t * 8, nullptr));
-    chk(d_pa.ensure(np * 4, nullptr)); chk(d_pb.ensure(np * 4, nullptr)); chk(d_ea.ensure(words, nullptr)); chk(d_eb.ensure(words, nullptr));
-    chk(d_v.ensure(np * 4, nullptr)); chk(d_t.ensure(np * 8, nullptr)); chk(d_cnt.ensure(7 * 8, nullptr));
-    chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1));
-    if (e == hipSuccess) {
-        chk(hipMemcpy(d_off.p, row_off, (size_t)(n_regions + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_ef.p, ef_rows, (size_t)rows * (n_t + 1) * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_xs.p, xs, (size_t)n_regions * n_t * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_box.p, box, (size_t)n_regions * 2 * n_t * 8, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_pa.p, pair_a, np * 4, hipMemcpyHostToDevice));
-        chk(hipMemcpy(d_pb.p, pair_b, np * 4, hipMemcpyHostToDevice));
-        chk(hipMemset(d_cnt.p, 0, 7 * 8));
-    }
-    if (e == hipSuccess && lds > 48 * 1024)
-        chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (e == hipSuccess) {
-        MergePairArgs a{};
-        a.nt = n_t; a.m_max = lds_rows; a.n_pairs = n_pairs;
-        a.row_off = d_off.as<long long>(); a.ef = d_ef.as<double>(); a.xs = d_xs.as<double>(); a.box = d_box.as<double>();
-        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
-        a.env_a = d_ea.as<unsigned long long>(); a.env_b = d_eb.as<unsigned long long>(); a.verdict = d_v.as<int32_t>(); a.t_max = d_t.as<double>();
-        a.counters = d_cnt.as<unsigned long long>();
-        chk(hipEventRecord(e0, nullptr));
-        hipLaunchKernelGGL(k_merge_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
-        chk(hipGetLastError());
-        chk(hipEventRecord(e1, nullptr));
-        chk(hipMemcpy(env_a, d_ea.p, words, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(env_b, d_eb.p, words, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(verdict, d_v.p, np * 4, hipMemcpyDeviceToHost));
-        chk(hipMemcpy(t_max, d_t.p, np * 8, hipMemcpyDeviceToHost));
-        unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
-        chk(hipMemcpy(cnt, d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost));
-        if (stats) for (int i = 0; i < 7; ++i) stats[i] = (int64_t)cnt[i];
-        if (e == hipSuccess && ms) chk(hipEventElapsedTime(ms, e0, e1));
-    }
-    (void)hipDeviceSynchronize();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    for (DevBuf *bf : {&d_off, &d_ef, &d_xs, &d_box, &d_pa, &d_pb, &d_ea, &d_eb, &d_v, &d_t, &d_cnt}) bf->release();
-    if (e != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    return MPC_OK;
 }

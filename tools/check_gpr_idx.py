@@ -4,7 +4,7 @@ vector instruction is index-shifted, so a region must be short, closed, and free
 build with an early `return` between an indexed read and an indexed write produced wrong verdicts and memory faults; the
 source was restructured, and this check makes the property visible.)
 
-    python tools/check_gpr_idx.py [file.s]      # without an argument: compiles ppopt_amd/csrc/mpcombi_hip.hip with --save-temps
+    python tools/check_gpr_idx.py [file.s]      # without an argument: compiles every unit of the library with --save-temps
 """
 import os
 import re
@@ -39,13 +39,27 @@ def audit(text: str):
 
 
 def assembly() -> str:
+    """The gfx950 assembly of every translation unit of the library (the list and the flags of __graft_entry__.py, so that a unit
+    which starts to use the index mode cannot be missed), compiled side by side and concatenated."""
+    sys.path.insert(0, ROOT)
+    try:
+        import __graft_entry__ as entry
+    finally:
+        sys.path.remove(ROOT)
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     with tempfile.TemporaryDirectory() as tmp:
-        subprocess.check_call([hipcc, '--offload-arch=gfx950', '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-c',
-                               os.path.join(ROOT, 'ppopt_amd', 'csrc', 'mpcombi_hip.hip'), '-o', os.path.join(tmp, 'x.o'), '--save-temps'],
-                              cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        name = [f for f in os.listdir(tmp) if f.endswith('gfx950.s')][0]
-        return open(os.path.join(tmp, name)).read()
+        jobs = []
+        for src, _ in entry.HIP_UNITS:
+            d = os.path.join(tmp, os.path.splitext(src)[0])
+            os.mkdir(d)
+            jobs.append((d, subprocess.Popen([hipcc, *entry.HIPCC_FLAGS, '-c', os.path.join(entry.CSRC, src), '-o', os.path.join(d, 'x.o'), '--save-temps'],
+                                             cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)))
+        text = []
+        for d, proc in jobs:
+            if proc.wait() != 0:
+                raise subprocess.CalledProcessError(proc.returncode, 'hipcc --save-temps in ' + d)
+            text += [open(os.path.join(d, f)).read() for f in os.listdir(d) if f.endswith('gfx950.s')]
+        return '\n'.join(text)
 
 
 if __name__ == '__main__':
