@@ -642,6 +642,41 @@ int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, const int64
                         int64_t max_slab, int64_t budget, int64_t *v_cap, int64_t *r_cap, int32_t *status, int64_t *n_vert, int64_t *n_ray,
                         double *vertices, uint64_t *incidence, double *rays, mpc_vertex_stats *stats);
 
+/* ---- volumes and centroids of a batch of polytopes (geometry.polytope_volumes, Solution.volumes) ------------------------ */
+/* mpc_region_volumes: the volume and the centroid of every polytope {theta : E theta <= f} from what mpc_region_vertices returned for the
+ * same rows: vert_off[n_poly + 1] (the running sums of n_vert), vertices, incidence and vx_status.  The boundary triangulation of Cohen &
+ * Hickey on the face lattice the incidence masks give (volume.hpp): the vertices are taken in the order they arrive, the apex of a
+ * face is its lowest vertex, and every simplex adds |det| / n_t! and that times the mean of its points.  One wavefront per (polytope,
+ * row); the sums of the waves are added in row order by a second kernel, so two runs give the same bits.
+ *   ef_rows        [rows][n_t + 1]: only its row counts and its finiteness are used
+ *   tol            the tolerance the incidence was computed with; checked, not applied again
+ *   max_simplices  the most simplices one polytope may take (>= 1); a polytope over it ends MPC_VOL_TOO_LARGE, as does one of more than
+ *                  16,384 vertices (the stack of a wave lives in LDS)
+ *   budget         device bytes of the row-to-vertex bitsets in flight (<= 0: 4 GiB); polytopes run in chunks that fit
+ * Outputs per polytope: status (MPC_VOL_*), volume, centroid [n_t], n_simplices (0 unless MPC_VOL_OK).
+ *   vx_status EMPTY -> EMPTY, 0, NaN;  UNBOUNDED / NOT_POINTED -> the same status, +inf, NaN;  OVERFLOW -> OVERFLOW, NaN, NaN;
+ *   MPC_VOL_TOO_LARGE and MPC_VOL_INCONSISTENT (a face without a facet, an edge without two ends: the incidence masks were blurred by
+ *   a vertex merge) -> NaN, NaN, never a partial sum.
+ * Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16, <= 256 rows per polytope, finite rows and vertices,
+ * tol >= 0, max_simplices >= 1, a budget that holds one polytope. */
+#define MPC_VOL_OK 0
+#define MPC_VOL_UNBOUNDED 1
+#define MPC_VOL_NOT_POINTED 2
+#define MPC_VOL_EMPTY 3
+#define MPC_VOL_OVERFLOW 4
+#define MPC_VOL_TOO_LARGE 5
+#define MPC_VOL_INCONSISTENT 6
+typedef struct mpc_volume_stats {
+    int64_t simplices;          /* simplices of all MPC_VOL_OK polytopes */
+    int64_t max_simplices;      /* the most of one polytope */
+    int64_t launches;           /* kernel launches */
+    int64_t status_counts[7];   /* polytopes per MPC_VOL_* */
+    float ms;                   /* device milliseconds of the three kernels */
+} mpc_volume_stats;
+int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
+                       const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
+                       int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats *stats);
+
 /* ---- merging regions with equal laws into convex unions (Solution.merge_regions) --------------------------------- */
 /* Regions are polytopes {theta : n.theta <= o} of unit rows: ef_rows [rows][n_t + 1] = [o | n] (|n| = 1 within 1e-6, finite), CSR over
  * regions by row_off[n_regions + 1] (row_off[0] = 0).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16,

@@ -19,6 +19,8 @@ MPC_SIM_FINAL, MPC_SIM_KEY_SALT = 16, 0x636c6f6f   # flag of mpc_locator_simulat
 SIM_MAX_DIM, SIM_MAX_INPUTS, SIM_DEFAULT_BUDGET = 16, 16, 4 << 30   # limits of mpc_locator_simulate
 VX_OK, VX_UNBOUNDED, VX_NOT_POINTED, VX_EMPTY, VX_OVERFLOW = range(5)   # statuses of mpc_region_vertices
 VX_MAX_DIM, VX_MAX_ROWS, VX_DEFAULT_BUDGET, VX_DEFAULT_SLAB, VX_MAX_SLAB = 16, 256, 4 << 30, 256, 1 << 24   # its limits
+VOL_OK, VOL_UNBOUNDED, VOL_NOT_POINTED, VOL_EMPTY, VOL_OVERFLOW, VOL_TOO_LARGE, VOL_INCONSISTENT = range(7)   # statuses of mpc_region_volumes
+VOL_MAX_VERTS, VOL_DEFAULT_BUDGET, VOL_DEFAULT_MAX_SIMPLICES = 16384, 4 << 30, 1 << 16   # its limits and the default work cap
 TREE_MAX_DIM, TREE_MAX_ROWS, TREE_MAX_DEPTH = 16, 256, 64   # limits of mpc_tree_build
 MPC_SOLVE_MANY_BASE = 128   # flag of mpc_solve_many_start
 MPC_LEVEL_STREAM, MPC_LEVEL_GRAPH, MPC_LEVEL_THEN_BASE, MPC_LEVEL_KEEP_LOWDIM, MPC_LEVEL_ONLY_BASE = 1, 4, 8, 16, 32   # flags of mpc_level_start / mpc_level_run_ex
@@ -132,6 +134,12 @@ class VertexStats(ctypes.Structure):
     """mpc_vertex_stats (include/mpcombi.h)"""
     _fields_ = [('generators', ctypes.c_int64), ('max_list', ctypes.c_int64), ('merges', ctypes.c_int64), ('repeats', ctypes.c_int64),
                 ('overflow', ctypes.c_int64), ('launches', ctypes.c_int64), ('slab', ctypes.c_int64), ('ms', ctypes.c_float)]
+
+
+class VolumeStats(ctypes.Structure):
+    """mpc_volume_stats (include/mpcombi.h)"""
+    _fields_ = [('simplices', ctypes.c_int64), ('max_simplices', ctypes.c_int64), ('launches', ctypes.c_int64),
+                ('status_counts', ctypes.c_int64 * 7), ('ms', ctypes.c_float)]
 
 
 def load():
@@ -252,6 +260,8 @@ def load():
         'mpc_region_vertices': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_double, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_int64, _lp, _lp, _ip, _lp, _lp, _dp, ctypes.POINTER(ctypes.c_uint64), _dp,
                                                 ctypes.POINTER(VertexStats)]),
+        'mpc_region_volumes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _lp, _dp, ctypes.POINTER(ctypes.c_uint64), _ip,
+                                               ctypes.c_double, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _lp, _ip, ctypes.POINTER(VolumeStats)]),
         'mpc_merge_regions': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _ip, _lp,
                                              ctypes.POINTER(ctypes.c_float)]),
         'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
@@ -275,7 +285,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
-                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices']
+                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1062,6 +1072,35 @@ def region_vertices(row_off, ef_rows, n_t: int, tol: float = 1e-9, slab: int = 0
         stats = {name: getattr(st, name) for name, _ in VertexStats._fields_}
         return status, nv, nr, vert[:vc.value], inc[:vc.value], rays[:rc_.value], stats
     raise MpcError('mpc_region_vertices: the outputs did not fit the sizes it reported')
+
+
+def region_volumes(row_off, ef_rows, n_t: int, vert_off, vertices, incidence, vx_status, tol: float = 1e-9,
+                   max_simplices: int = VOL_DEFAULT_MAX_SIMPLICES, budget: int = 0, device: int = 0):
+    """mpc_region_volumes: the volume and centroid of every polytope of the stacked [f | E] rows from the vertices, incidence masks and
+    statuses mpc_region_vertices returned for them (vert_off [P + 1] into vertices).  Returns (volume [P], centroid [P, n_t],
+    simplices [P] int64, status [P] int32, stats dict)."""
+    L = load()
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ef = _f64(numpy.asarray(ef_rows, dtype=numpy.float64).reshape(-1, int(n_t) + 1))
+    voff = numpy.ascontiguousarray(vert_off, dtype=numpy.int64).reshape(-1)
+    vert = _f64(numpy.asarray(vertices, dtype=numpy.float64).reshape(-1, int(n_t)))
+    inc = numpy.ascontiguousarray(incidence, dtype=numpy.uint64).reshape(-1, 4)
+    vst = numpy.ascontiguousarray(vx_status, dtype=numpy.int32).reshape(-1)
+    P = len(off) - 1
+    if len(voff) != P + 1 or len(vst) != P or len(vert) != len(inc) or (P and (int(voff[-1]) != len(vert) or int(off[-1]) != len(ef))):
+        raise MpcError('mpc_region_volumes: the offsets, statuses, vertices and incidence do not belong together')
+    volume, centroid = numpy.empty(P), numpy.empty((P, int(n_t)))
+    simplices, status = numpy.zeros(P, dtype=numpy.int64), numpy.zeros(P, dtype=numpy.int32)
+    st = VolumeStats()
+    rc = L.mpc_region_volumes(int(device), int(n_t), P, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), voff.ctypes.data_as(_lp),
+                              vert.ctypes.data_as(_dp), inc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), vst.ctypes.data_as(_ip), float(tol),
+                              int(max_simplices), int(budget), volume.ctypes.data_as(_dp), centroid.ctypes.data_as(_dp),
+                              simplices.ctypes.data_as(_lp), status.ctypes.data_as(_ip), ctypes.byref(st))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_region_volumes failed ({rc}): {L.mpc_last_global_error().decode()}')
+    stats = {'ms': float(st.ms), 'simplices': int(st.simplices), 'max_simplices': int(st.max_simplices), 'launches': int(st.launches),
+             'status_counts': [int(v) for v in st.status_counts]}
+    return volume, centroid, simplices, status, stats
 
 
 def _slice_rows(who, row_off, ef_rows, n, eps):

@@ -1,7 +1,7 @@
 // geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
-// location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration and region merging.
-// None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
-// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, merge.hpp, simplex.hpp); the pools and the scaffold
+// location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration, region volumes and region
+// merging.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +19,7 @@
 #include "tree.hpp"
 #include "closed_loop.hpp"
 #include "vertices.hpp"
+#include "volume.hpp"
 #include "merge.hpp"
 #include "host_common.hpp"
 
@@ -975,6 +976,156 @@ extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, 
         if (nr[p]) std::memcpy(rays + pr * n_t, hr[p].data(), hr[p].size() * 8);
         pv += nv[p]; pr += nr[p];
     }
+    return MPC_OK;
+}
+
+// ---- volumes and centroids of a batch of polytopes from their vertex lists (volume.hpp) ---------------------------------
+constexpr long long VOL_DEFAULT_BUDGET = 4ll << 30, VOL_MAX_CHUNK_ITEMS = 1ll << 26;
+constexpr long long VOL_LDS_WORDS[3] = {512, 2048, 5120};   // classes of stack + Ct words per wave: 4, 16, 40 KB of LDS; beyond: Ct in global memory
+
+// device bytes one polytope of m rows and nv vertices adds to a chunk: its Ct (m words per 64 vertices), its counter and its chunk entries
+static long long vol_poly_bytes(long long m, long long nv) { return m * ((nv + 63) / 64) * 8 + 8 + 4 + 8 + m * 8; }
+
+template <int NT>
+static int vol_run(const char *who, int nt, int64_t n_poly, const int64_t *row_off, const int64_t *vert_off, const double *vertices,
+                   const uint64_t *incidence, const std::vector<int32_t> &todo, long long max_simplices, long long budget, double *volume,
+                   double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats &stats) {
+    OneShot s(who, nullptr, true);
+    const long long rows = row_off[n_poly], nv_all = vert_off[n_poly];
+    DevBuf &d_roff = s.upload(row_off, (size_t)(n_poly + 1) * 8), &d_voff = s.upload(vert_off, (size_t)(n_poly + 1) * 8);
+    DevBuf &d_vert = s.upload(vertices, (size_t)nv_all * nt * 8), &d_inc = s.upload(incidence, (size_t)nv_all * 4 * 8);
+    DevBuf &d_svol = s.buf((size_t)rows * 8), &d_smom = s.buf((size_t)rows * nt * 8), &d_scnt = s.buf((size_t)rows * 8), &d_sst = s.buf((size_t)rows * 4);
+    DevBuf &d_vol = s.buf((size_t)n_poly * 8), &d_cen = s.buf((size_t)n_poly * nt * 8), &d_ns = s.buf((size_t)n_poly * 8), &d_st = s.buf((size_t)n_poly * 4);
+    DevBuf &d_chunk = s.buf(), &d_ctoff = s.buf(), &d_ct = s.buf(), &d_count = s.buf();
+    DevBuf *d_iq[4], *d_ir[4];
+    for (int c = 0; c < 4; ++c) { d_iq[c] = &s.buf(); d_ir[c] = &s.buf(); }
+    for (size_t start = 0; start < todo.size();) {
+        // a chunk: as many polytopes as the budget holds
+        std::vector<int32_t> chunk;
+        std::vector<long long> ct_off;
+        std::vector<int32_t> iq[4], ir[4];
+        long long lds_words[4] = {0, 0, 0, 0};
+        long long bytes = 0, words = 0, items = 0;
+        while (start < todo.size()) {
+            const int32_t p = todo[start];
+            const long long m = row_off[p + 1] - row_off[p], nv = vert_off[p + 1] - vert_off[p], W = (nv + 63) / 64;
+            if (!chunk.empty() && (bytes + vol_poly_bytes(m, nv) > budget || items + m > VOL_MAX_CHUNK_ITEMS)) break;
+            const long long stack = (long long)nt * W, need = stack + m * W;
+            const int cls = need <= VOL_LDS_WORDS[0] ? 0 : need <= VOL_LDS_WORDS[1] ? 1 : need <= VOL_LDS_WORDS[2] ? 2 : 3;
+            lds_words[cls] = std::max(lds_words[cls], cls < 3 ? need : stack);
+            for (long long r = 0; r < m; ++r) { iq[cls].push_back((int32_t)chunk.size()); ir[cls].push_back((int32_t)r); }
+            chunk.push_back(p);
+            ct_off.push_back(words);
+            bytes += vol_poly_bytes(m, nv); words += m * W; items += m;
+            ++start;
+        }
+        const long long nq = (long long)chunk.size();
+        s.upload(d_chunk, chunk.data(), (size_t)nq * 4);
+        s.upload(d_ctoff, ct_off.data(), (size_t)nq * 8);
+        s.ensure(d_ct, std::max<size_t>(8, (size_t)words * 8));
+        s.ensure(d_count, (size_t)nq * 8);
+        s.fill(d_count, 0, (size_t)nq * 8);
+        for (int c = 0; c < 4; ++c) { s.upload(*d_iq[c], iq[c].data(), iq[c].size() * 4); s.upload(*d_ir[c], ir[c].data(), ir[c].size() * 4); }
+        int launches = 0;
+        s.launch_timed([&] {
+            hipLaunchKernelGGL(k_volume_rowsets, dim3((unsigned)nq), dim3(VOL_ROWSET_BLOCK), 0, nullptr, d_chunk.as<int32_t>(), d_roff.as<long long>(),
+                               d_voff.as<long long>(), d_inc.as<unsigned long long>(), d_ctoff.as<long long>(), d_ct.as<unsigned long long>());
+            ++launches;
+            for (int c = 0; c < 4; ++c) {
+                if (iq[c].empty()) continue;
+                VolArgs a{};
+                a.nt = nt; a.c_in_lds = c < 3; a.n_items = (long long)iq[c].size(); a.item_q = d_iq[c]->as<int32_t>(); a.item_row = d_ir[c]->as<int32_t>();
+                a.chunk_poly = d_chunk.as<int32_t>(); a.row_off = d_roff.as<long long>(); a.vert_off = d_voff.as<long long>(); a.vert = d_vert.as<double>();
+                a.ct = d_ct.as<unsigned long long>(); a.ct_off = d_ctoff.as<long long>(); a.max_simplices = max_simplices;
+                a.poly_count = d_count.as<unsigned long long>(); a.slot_vol = d_svol.as<double>(); a.slot_mom = d_smom.as<double>();
+                a.slot_cnt = d_scnt.as<long long>(); a.slot_st = d_sst.as<int32_t>();
+                hipLaunchKernelGGL((k_volume_walk<NT>), dim3((unsigned)iq[c].size()), dim3(64), (size_t)lds_words[c] * 8, nullptr, a);
+                ++launches;
+            }
+            hipLaunchKernelGGL(k_volume_reduce, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, nullptr, nt, nq, d_chunk.as<int32_t>(), d_roff.as<long long>(),
+                               max_simplices, d_svol.as<double>(), d_smom.as<double>(), d_scnt.as<long long>(), d_sst.as<int32_t>(), d_vol.as<double>(),
+                               d_cen.as<double>(), d_ns.as<long long>(), d_st.as<int32_t>());
+            ++launches;
+        });
+        s.sync();
+        s.synced = false;
+        float ms = 0.0f;
+        s.elapsed(&ms);
+        if (!s.ok()) return s.finish();
+        stats.ms += ms;
+        stats.launches += launches;
+    }
+    std::vector<double> hv((size_t)n_poly), hc((size_t)n_poly * nt);
+    std::vector<long long> hn((size_t)n_poly);
+    std::vector<int32_t> hs((size_t)n_poly);
+    s.download(hv.data(), d_vol, hv.size() * 8);
+    s.download(hc.data(), d_cen, hc.size() * 8);
+    s.download(hn.data(), d_ns, hn.size() * 8);
+    s.download(hs.data(), d_st, hs.size() * 4);
+    if (!s.ok()) return s.finish();
+    for (int32_t p : todo) {
+        volume[p] = hv[(size_t)p]; n_simplices[p] = hn[(size_t)p]; status[p] = hs[(size_t)p];
+        std::memcpy(centroid + (size_t)p * nt, hc.data() + (size_t)p * nt, (size_t)nt * 8);
+    }
+    return s.finish();
+}
+
+extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
+                                  const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
+                                  int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats *stats) {
+    const char *who = "mpc_region_volumes";
+    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
+    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
+    if (!row_off || !vert_off) return bad("missing row_off or vert_off");
+    if (row_off[0] != 0 || vert_off[0] != 0) return bad("row_off[0] and vert_off[0] must be 0");
+    if (max_simplices < 1) return bad("max_simplices must be >= 1");
+    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    const long long limit = budget > 0 ? budget : VOL_DEFAULT_BUDGET;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int64_t r = row_off[p + 1] - row_off[p], v = vert_off[p + 1] - vert_off[p];
+        if (r < 0 || v < 0) return bad("row_off or vert_off decreases");
+        if (r > VOL_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VOL_MAX_ROWS));
+        if (v <= VOL_MAX_VERTS && vol_poly_bytes(r, v) > limit)
+            return bad("the budget of " + std::to_string(limit) + " device bytes is too small for polytope " + std::to_string(p) + " (" +
+                       std::to_string(vol_poly_bytes(r, v)) + " bytes)");
+    }
+    const long long rows = row_off[n_poly], nv_all = vert_off[n_poly];
+    if ((rows && !ef_rows) || (nv_all && (!vertices || !incidence))) return bad("missing ef_rows, vertices or incidence");
+    for (long long i = 0; i < rows * (n_t + 1); ++i)
+        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
+    for (long long i = 0; i < nv_all * n_t; ++i)
+        if (!std::isfinite(vertices[i])) return bad("the vertices must be finite (vertex " + std::to_string(i / n_t) + ")");
+    if (n_poly == 0) return MPC_OK;
+    if (!vx_status || !volume || !centroid || !n_simplices || !status) return bad("missing vx_status or an output array");
+    const double nan = std::nan(""), inf = HUGE_VAL;
+    std::vector<int32_t> todo;
+    for (int64_t p = 0; p < n_poly; ++p) {
+        const int32_t vs = vx_status[p];
+        if (vs < VOL_OK || vs > VOL_OVERFLOW) return bad("vx_status[" + std::to_string(p) + "] is not a status of mpc_region_vertices");
+        const int64_t v = vert_off[p + 1] - vert_off[p];
+        // what needs no walk: the statuses of the vertex pass, and a vertex list too long for the stack of a wave
+        status[p] = vs != VOL_OK ? vs : v > VOL_MAX_VERTS ? VOL_TOO_LARGE : v < 1 || row_off[p + 1] == row_off[p] ? VOL_INCONSISTENT : VOL_OK;
+        n_simplices[p] = 0;
+        volume[p] = vs == VOL_EMPTY ? 0.0 : (vs == VOL_UNBOUNDED || vs == VOL_NOT_POINTED) ? inf : nan;
+        for (int c = 0; c < n_t; ++c) centroid[p * n_t + c] = nan;
+        if (status[p] == VOL_OK && vs == VOL_OK) todo.push_back((int32_t)p);
+    }
+    mpc_volume_stats st{};
+    if (!todo.empty()) {
+        if (int rc = select_device(who, device)) return rc;
+        if (int rc = with_width(n_t, [&](auto W) {
+                return vol_run<decltype(W)::value>(who, n_t, n_poly, row_off, vert_off, vertices, incidence, todo, max_simplices, limit, volume, centroid,
+                                                   n_simplices, status, st);
+            })) return rc;
+    }
+    for (int64_t p = 0; p < n_poly; ++p) {
+        st.status_counts[status[p]] += 1;
+        st.simplices += n_simplices[p];
+        st.max_simplices = std::max<int64_t>(st.max_simplices, n_simplices[p]);
+    }
+    if (stats) *stats = st;
     return MPC_OK;
 }
 

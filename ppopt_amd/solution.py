@@ -245,6 +245,21 @@ class Solution:
             cache[1][tol] = vertices_of_rows(row_off, ef, n_t, tol=tol, device=device, who='Solution.vertices')
         return cache[1][tol]
 
+    def volumes(self, tol: float = 1e-9, max_simplices=None, device: int = 0):
+        """The volume and centroid of every region (geometry.volume.RegionVolumes: volume, centroid, simplices, status, stats, vertices),
+        triangulated on the device from the vertex lists of ``vertices(tol)``; one entry per region.  See DESIGN §3.17."""
+        from .geometry.volume import volumes_of_rows
+        rv = self.vertices(tol=tol, device=device)
+        ef, row_off, _ = self._stacked()
+        return volumes_of_rows(row_off, ef, ef.shape[1] - 1, tol=tol, max_simplices=max_simplices, device=device, who='Solution.volumes', vertices=rv)
+
+    def coverage_volume(self, device: int = 0):
+        """The exact share of the parameter space {A_t theta <= b_t} the regions cover: a geometry.volume.CoverageVolume with total (the
+        summed volume of the OK regions), theta_volume, fraction, status_counts and ok (no region left undecided).  ValueError for
+        overlapping (mpLP) and mixed-integer solutions, whose regions may overlap; merged solutions are fine.  See DESIGN §3.17."""
+        from .geometry.volume import coverage_volume
+        return coverage_volume(self, device=device)
+
     def certify_recursive_feasibility(self, A, B, inputs, c=None, disturbance=None, tol: float = 1e-7, device: int = 0):
         """Whether the plant theta+ = A theta + B u + c (+ a box disturbance (lo, hi)) under this controller's law u = x*(theta)[inputs]
         stays where the program is feasible, region by region: an invariance.FeasibilityCertificate.  See
