@@ -677,6 +677,19 @@ int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, const int64_
                        const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
                        int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats *stats);
 
+/* ---- second moments of a batch of polytopes (geometry.polytope_moments, Solution.moments) ------------------------------ */
+/* mpc_region_moments: mpc_region_volumes with one more output, second_moment [n_poly][n_t][n_t], the integral of theta theta^T over every
+ * polytope (symmetric, both triangles written).  The same walk with one more sum per wave (volume.hpp, M2 = true): every simplex adds
+ * |det| / (n_t! (n_t + 1)(n_t + 2)) (sum_i v_i v_i^T + s s^T), s the sum of its vertices.  No floating-point atomics; volume, centroid,
+ * n_simplices and status are bit for bit those of mpc_region_volumes for the same arguments.
+ *   second_moment by status: MPC_VOL_OK -> the integral;  EMPTY -> zeros;  every other status -> NaN, never a partial sum.
+ *   budget         also counts the second-moment slots, n_t (n_t + 1) / 2 doubles per row
+ * The limits, the statuses and the statistics are those of mpc_region_volumes. */
+int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
+                       const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
+                       int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, double *second_moment,
+                       mpc_volume_stats *stats);
+
 /* ---- merging regions with equal laws into convex unions (Solution.merge_regions) --------------------------------- */
 /* Regions are polytopes {theta : n.theta <= o} of unit rows: ef_rows [rows][n_t + 1] = [o | n] (|n| = 1 within 1e-6, finite), CSR over
  * regions by row_off[n_regions + 1] (row_off[0] = 0).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16,

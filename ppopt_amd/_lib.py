@@ -262,6 +262,8 @@ def load():
                                                 ctypes.POINTER(VertexStats)]),
         'mpc_region_volumes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _lp, _dp, ctypes.POINTER(ctypes.c_uint64), _ip,
                                                ctypes.c_double, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _lp, _ip, ctypes.POINTER(VolumeStats)]),
+        'mpc_region_moments': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _lp, _dp, ctypes.POINTER(ctypes.c_uint64), _ip,
+                                               ctypes.c_double, ctypes.c_int64, ctypes.c_int64, _dp, _dp, _lp, _ip, _dp, ctypes.POINTER(VolumeStats)]),
         'mpc_merge_regions': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _ip, _lp,
                                              ctypes.POINTER(ctypes.c_float)]),
         'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
@@ -285,7 +287,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
-                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes']
+                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1074,11 +1076,8 @@ def region_vertices(row_off, ef_rows, n_t: int, tol: float = 1e-9, slab: int = 0
     raise MpcError('mpc_region_vertices: the outputs did not fit the sizes it reported')
 
 
-def region_volumes(row_off, ef_rows, n_t: int, vert_off, vertices, incidence, vx_status, tol: float = 1e-9,
-                   max_simplices: int = VOL_DEFAULT_MAX_SIMPLICES, budget: int = 0, device: int = 0):
-    """mpc_region_volumes: the volume and centroid of every polytope of the stacked [f | E] rows from the vertices, incidence masks and
-    statuses mpc_region_vertices returned for them (vert_off [P + 1] into vertices).  Returns (volume [P], centroid [P, n_t],
-    simplices [P] int64, status [P] int32, stats dict)."""
+def _region_walk(name, row_off, ef_rows, n_t, vert_off, vertices, incidence, vx_status, tol, max_simplices, budget, device):
+    """mpc_region_volumes or mpc_region_moments (``name``): (volume, centroid, second_moment or None, simplices, status, stats)."""
     L = load()
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
     ef = _f64(numpy.asarray(ef_rows, dtype=numpy.float64).reshape(-1, int(n_t) + 1))
@@ -1088,19 +1087,40 @@ def region_volumes(row_off, ef_rows, n_t: int, vert_off, vertices, incidence, vx
     vst = numpy.ascontiguousarray(vx_status, dtype=numpy.int32).reshape(-1)
     P = len(off) - 1
     if len(voff) != P + 1 or len(vst) != P or len(vert) != len(inc) or (P and (int(voff[-1]) != len(vert) or int(off[-1]) != len(ef))):
-        raise MpcError('mpc_region_volumes: the offsets, statuses, vertices and incidence do not belong together')
+        raise MpcError(f'{name}: the offsets, statuses, vertices and incidence do not belong together')
     volume, centroid = numpy.empty(P), numpy.empty((P, int(n_t)))
     simplices, status = numpy.zeros(P, dtype=numpy.int64), numpy.zeros(P, dtype=numpy.int32)
     st = VolumeStats()
-    rc = L.mpc_region_volumes(int(device), int(n_t), P, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), voff.ctypes.data_as(_lp),
-                              vert.ctypes.data_as(_dp), inc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), vst.ctypes.data_as(_ip), float(tol),
-                              int(max_simplices), int(budget), volume.ctypes.data_as(_dp), centroid.ctypes.data_as(_dp),
-                              simplices.ctypes.data_as(_lp), status.ctypes.data_as(_ip), ctypes.byref(st))
+    m2 = numpy.empty((P, int(n_t), int(n_t))) if name == 'mpc_region_moments' else None
+    args = [int(device), int(n_t), P, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), voff.ctypes.data_as(_lp), vert.ctypes.data_as(_dp),
+            inc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), vst.ctypes.data_as(_ip), float(tol), int(max_simplices), int(budget),
+            volume.ctypes.data_as(_dp), centroid.ctypes.data_as(_dp), simplices.ctypes.data_as(_lp), status.ctypes.data_as(_ip)]
+    if m2 is not None:
+        args.append(m2.ctypes.data_as(_dp))
+    rc = getattr(L, name)(*args, ctypes.byref(st))
     if rc != MPC_OK:
-        raise MpcError(f'mpc_region_volumes failed ({rc}): {L.mpc_last_global_error().decode()}')
+        raise MpcError(f'{name} failed ({rc}): {L.mpc_last_global_error().decode()}')
     stats = {'ms': float(st.ms), 'simplices': int(st.simplices), 'max_simplices': int(st.max_simplices), 'launches': int(st.launches),
              'status_counts': [int(v) for v in st.status_counts]}
+    return volume, centroid, m2, simplices, status, stats
+
+
+def region_volumes(row_off, ef_rows, n_t: int, vert_off, vertices, incidence, vx_status, tol: float = 1e-9,
+                   max_simplices: int = VOL_DEFAULT_MAX_SIMPLICES, budget: int = 0, device: int = 0):
+    """mpc_region_volumes: the volume and centroid of every polytope of the stacked [f | E] rows from the vertices, incidence masks and
+    statuses mpc_region_vertices returned for them (vert_off [P + 1] into vertices).  Returns (volume [P], centroid [P, n_t],
+    simplices [P] int64, status [P] int32, stats dict)."""
+    volume, centroid, _, simplices, status, stats = _region_walk('mpc_region_volumes', row_off, ef_rows, n_t, vert_off, vertices, incidence,
+                                                                 vx_status, tol, max_simplices, budget, device)
     return volume, centroid, simplices, status, stats
+
+
+def region_moments(row_off, ef_rows, n_t: int, vert_off, vertices, incidence, vx_status, tol: float = 1e-9,
+                   max_simplices: int = VOL_DEFAULT_MAX_SIMPLICES, budget: int = 0, device: int = 0):
+    """mpc_region_moments: region_volumes with the second moment of every polytope.  Returns (volume [P], centroid [P, n_t],
+    second_moment [P, n_t, n_t], simplices [P] int64, status [P] int32, stats dict)."""
+    return _region_walk('mpc_region_moments', row_off, ef_rows, n_t, vert_off, vertices, incidence, vx_status, tol, max_simplices, budget,
+                        device)
 
 
 def _slice_rows(who, row_off, ef_rows, n, eps):

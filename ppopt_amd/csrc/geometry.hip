@@ -983,20 +983,27 @@ extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, 
 constexpr long long VOL_DEFAULT_BUDGET = 4ll << 30, VOL_MAX_CHUNK_ITEMS = 1ll << 26;
 constexpr long long VOL_LDS_WORDS[3] = {512, 2048, 5120};   // classes of stack + Ct words per wave: 4, 16, 40 KB of LDS; beyond: Ct in global memory
 
-// device bytes one polytope of m rows and nv vertices adds to a chunk: its Ct (m words per 64 vertices), its counter and its chunk entries
-static long long vol_poly_bytes(long long m, long long nv) { return m * ((nv + 63) / 64) * 8 + 8 + 4 + 8 + m * 8; }
+// device bytes one polytope of m rows and nv vertices adds to a chunk: its Ct (m words per 64 vertices), its counter and its chunk entries;
+// m2_entries: the entries of a second-moment slot (0: the volume pass), one slot per row
+static long long vol_poly_bytes(long long m, long long nv, long long m2_entries) {
+    return m * ((nv + 63) / 64) * 8 + 8 + 4 + 8 + m * 8 + m * m2_entries * 8;
+}
 
+// second_moment: [n_poly][nt][nt], or nullptr for the volume pass (the M2 = false kernels)
 template <int NT>
 static int vol_run(const char *who, int nt, int64_t n_poly, const int64_t *row_off, const int64_t *vert_off, const double *vertices,
                    const uint64_t *incidence, const std::vector<int32_t> &todo, long long max_simplices, long long budget, double *volume,
-                   double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats &stats) {
+                   double *centroid, int64_t *n_simplices, int32_t *status, double *second_moment, mpc_volume_stats &stats) {
     OneShot s(who, nullptr, true);
     const long long rows = row_off[n_poly], nv_all = vert_off[n_poly];
+    const bool m2 = second_moment != nullptr;
+    const long long ne = m2 ? (long long)nt * (nt + 1) / 2 : 0;
     DevBuf &d_roff = s.upload(row_off, (size_t)(n_poly + 1) * 8), &d_voff = s.upload(vert_off, (size_t)(n_poly + 1) * 8);
     DevBuf &d_vert = s.upload(vertices, (size_t)nv_all * nt * 8), &d_inc = s.upload(incidence, (size_t)nv_all * 4 * 8);
     DevBuf &d_svol = s.buf((size_t)rows * 8), &d_smom = s.buf((size_t)rows * nt * 8), &d_scnt = s.buf((size_t)rows * 8), &d_sst = s.buf((size_t)rows * 4);
     DevBuf &d_vol = s.buf((size_t)n_poly * 8), &d_cen = s.buf((size_t)n_poly * nt * 8), &d_ns = s.buf((size_t)n_poly * 8), &d_st = s.buf((size_t)n_poly * 4);
     DevBuf &d_chunk = s.buf(), &d_ctoff = s.buf(), &d_ct = s.buf(), &d_count = s.buf();
+    DevBuf &d_sm2 = s.buf((size_t)rows * ne * 8), &d_m2 = s.buf((size_t)(m2 ? n_poly * nt * nt : 0) * 8);
     DevBuf *d_iq[4], *d_ir[4];
     for (int c = 0; c < 4; ++c) { d_iq[c] = &s.buf(); d_ir[c] = &s.buf(); }
     for (size_t start = 0; start < todo.size();) {
@@ -1009,14 +1016,14 @@ static int vol_run(const char *who, int nt, int64_t n_poly, const int64_t *row_o
         while (start < todo.size()) {
             const int32_t p = todo[start];
             const long long m = row_off[p + 1] - row_off[p], nv = vert_off[p + 1] - vert_off[p], W = (nv + 63) / 64;
-            if (!chunk.empty() && (bytes + vol_poly_bytes(m, nv) > budget || items + m > VOL_MAX_CHUNK_ITEMS)) break;
+            if (!chunk.empty() && (bytes + vol_poly_bytes(m, nv, ne) > budget || items + m > VOL_MAX_CHUNK_ITEMS)) break;
             const long long stack = (long long)nt * W, need = stack + m * W;
             const int cls = need <= VOL_LDS_WORDS[0] ? 0 : need <= VOL_LDS_WORDS[1] ? 1 : need <= VOL_LDS_WORDS[2] ? 2 : 3;
             lds_words[cls] = std::max(lds_words[cls], cls < 3 ? need : stack);
             for (long long r = 0; r < m; ++r) { iq[cls].push_back((int32_t)chunk.size()); ir[cls].push_back((int32_t)r); }
             chunk.push_back(p);
             ct_off.push_back(words);
-            bytes += vol_poly_bytes(m, nv); words += m * W; items += m;
+            bytes += vol_poly_bytes(m, nv, ne); words += m * W; items += m;
             ++start;
         }
         const long long nq = (long long)chunk.size();
@@ -1038,13 +1045,19 @@ static int vol_run(const char *who, int nt, int64_t n_poly, const int64_t *row_o
                 a.chunk_poly = d_chunk.as<int32_t>(); a.row_off = d_roff.as<long long>(); a.vert_off = d_voff.as<long long>(); a.vert = d_vert.as<double>();
                 a.ct = d_ct.as<unsigned long long>(); a.ct_off = d_ctoff.as<long long>(); a.max_simplices = max_simplices;
                 a.poly_count = d_count.as<unsigned long long>(); a.slot_vol = d_svol.as<double>(); a.slot_mom = d_smom.as<double>();
-                a.slot_cnt = d_scnt.as<long long>(); a.slot_st = d_sst.as<int32_t>();
-                hipLaunchKernelGGL((k_volume_walk<NT>), dim3((unsigned)iq[c].size()), dim3(64), (size_t)lds_words[c] * 8, nullptr, a);
+                a.slot_cnt = d_scnt.as<long long>(); a.slot_st = d_sst.as<int32_t>(); a.slot_m2 = d_sm2.as<double>();
+                const dim3 grid((unsigned)iq[c].size());
+                if (m2) hipLaunchKernelGGL((k_volume_walk<NT, true>), grid, dim3(64), (size_t)lds_words[c] * 8, nullptr, a);
+                else hipLaunchKernelGGL((k_volume_walk<NT, false>), grid, dim3(64), (size_t)lds_words[c] * 8, nullptr, a);
                 ++launches;
             }
-            hipLaunchKernelGGL(k_volume_reduce, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, nullptr, nt, nq, d_chunk.as<int32_t>(), d_roff.as<long long>(),
-                               max_simplices, d_svol.as<double>(), d_smom.as<double>(), d_scnt.as<long long>(), d_sst.as<int32_t>(), d_vol.as<double>(),
-                               d_cen.as<double>(), d_ns.as<long long>(), d_st.as<int32_t>());
+            const dim3 rgrid((unsigned)((nq + 63) / 64), m2 ? (unsigned)ne : 1u);
+            auto reduce = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, rgrid, dim3(64), 0, nullptr, nt, nq, d_chunk.as<int32_t>(), d_roff.as<long long>(), max_simplices,
+                                   d_svol.as<double>(), d_smom.as<double>(), d_scnt.as<long long>(), d_sst.as<int32_t>(), d_sm2.as<double>(),
+                                   d_vol.as<double>(), d_cen.as<double>(), d_ns.as<long long>(), d_st.as<int32_t>(), d_m2.as<double>());
+            };
+            if (m2) reduce(k_volume_reduce<true>); else reduce(k_volume_reduce<false>);
             ++launches;
         });
         s.sync();
@@ -1062,18 +1075,22 @@ static int vol_run(const char *who, int nt, int64_t n_poly, const int64_t *row_o
     s.download(hc.data(), d_cen, hc.size() * 8);
     s.download(hn.data(), d_ns, hn.size() * 8);
     s.download(hs.data(), d_st, hs.size() * 4);
+    std::vector<double> hm((size_t)(m2 ? n_poly * nt * nt : 0));
+    if (m2) s.download(hm.data(), d_m2, hm.size() * 8);
     if (!s.ok()) return s.finish();
     for (int32_t p : todo) {
         volume[p] = hv[(size_t)p]; n_simplices[p] = hn[(size_t)p]; status[p] = hs[(size_t)p];
         std::memcpy(centroid + (size_t)p * nt, hc.data() + (size_t)p * nt, (size_t)nt * 8);
+        if (m2) std::memcpy(second_moment + (size_t)p * nt * nt, hm.data() + (size_t)p * nt * nt, (size_t)nt * nt * 8);
     }
     return s.finish();
 }
 
-extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
-                                  const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
-                                  int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats *stats) {
-    const char *who = "mpc_region_volumes";
+// mpc_region_volumes (want_m2 = false) and mpc_region_moments: the checks, what needs no walk, the walk and the statistics
+static int vol_entry(const char *who, bool want_m2, int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows,
+                     const int64_t *vert_off, const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol,
+                     int64_t max_simplices, int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status,
+                     double *second_moment, mpc_volume_stats *stats) {
     auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
@@ -1083,13 +1100,14 @@ extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, c
     if (max_simplices < 1) return bad("max_simplices must be >= 1");
     if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
     const long long limit = budget > 0 ? budget : VOL_DEFAULT_BUDGET;
+    const long long ne = want_m2 ? (long long)n_t * (n_t + 1) / 2 : 0;
     for (int64_t p = 0; p < n_poly; ++p) {
         const int64_t r = row_off[p + 1] - row_off[p], v = vert_off[p + 1] - vert_off[p];
         if (r < 0 || v < 0) return bad("row_off or vert_off decreases");
         if (r > VOL_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VOL_MAX_ROWS));
-        if (v <= VOL_MAX_VERTS && vol_poly_bytes(r, v) > limit)
+        if (v <= VOL_MAX_VERTS && vol_poly_bytes(r, v, ne) > limit)
             return bad("the budget of " + std::to_string(limit) + " device bytes is too small for polytope " + std::to_string(p) + " (" +
-                       std::to_string(vol_poly_bytes(r, v)) + " bytes)");
+                       std::to_string(vol_poly_bytes(r, v, ne)) + " bytes)");
     }
     const long long rows = row_off[n_poly], nv_all = vert_off[n_poly];
     if ((rows && !ef_rows) || (nv_all && (!vertices || !incidence))) return bad("missing ef_rows, vertices or incidence");
@@ -1098,7 +1116,7 @@ extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, c
     for (long long i = 0; i < nv_all * n_t; ++i)
         if (!std::isfinite(vertices[i])) return bad("the vertices must be finite (vertex " + std::to_string(i / n_t) + ")");
     if (n_poly == 0) return MPC_OK;
-    if (!vx_status || !volume || !centroid || !n_simplices || !status) return bad("missing vx_status or an output array");
+    if (!vx_status || !volume || !centroid || !n_simplices || !status || (want_m2 && !second_moment)) return bad("missing vx_status or an output array");
     const double nan = std::nan(""), inf = HUGE_VAL;
     std::vector<int32_t> todo;
     for (int64_t p = 0; p < n_poly; ++p) {
@@ -1110,6 +1128,7 @@ extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, c
         n_simplices[p] = 0;
         volume[p] = vs == VOL_EMPTY ? 0.0 : (vs == VOL_UNBOUNDED || vs == VOL_NOT_POINTED) ? inf : nan;
         for (int c = 0; c < n_t; ++c) centroid[p * n_t + c] = nan;
+        if (want_m2) for (int c = 0; c < n_t * n_t; ++c) second_moment[p * n_t * n_t + c] = vs == VOL_EMPTY ? 0.0 : nan;
         if (status[p] == VOL_OK && vs == VOL_OK) todo.push_back((int32_t)p);
     }
     mpc_volume_stats st{};
@@ -1117,7 +1136,7 @@ extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, c
         if (int rc = select_device(who, device)) return rc;
         if (int rc = with_width(n_t, [&](auto W) {
                 return vol_run<decltype(W)::value>(who, n_t, n_poly, row_off, vert_off, vertices, incidence, todo, max_simplices, limit, volume, centroid,
-                                                   n_simplices, status, st);
+                                                   n_simplices, status, want_m2 ? second_moment : nullptr, st);
             })) return rc;
     }
     for (int64_t p = 0; p < n_poly; ++p) {
@@ -1127,6 +1146,22 @@ extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, c
     }
     if (stats) *stats = st;
     return MPC_OK;
+}
+
+extern "C" int mpc_region_volumes(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
+                                  const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
+                                  int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, mpc_volume_stats *stats) {
+    return vol_entry("mpc_region_volumes", false, device, n_t, n_poly, row_off, ef_rows, vert_off, vertices, incidence, vx_status, tol, max_simplices,
+                     budget, volume, centroid, n_simplices, status, nullptr, stats);
+}
+
+// second moments with the volumes and centroids (volume.hpp M2 = true)
+extern "C" int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *vert_off,
+                                  const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol, int64_t max_simplices,
+                                  int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status, double *second_moment,
+                                  mpc_volume_stats *stats) {
+    return vol_entry("mpc_region_moments", true, device, n_t, n_poly, row_off, ef_rows, vert_off, vertices, incidence, vx_status, tol, max_simplices,
+                     budget, volume, centroid, n_simplices, status, second_moment, stats);
 }
 
 // ---- merging regions with equal laws (merge.hpp) ---------------------------------------------------------------------

@@ -21,6 +21,14 @@
 // not hold one, or a polytope without any simplex -> VOL_INCONSISTENT (the incidence was blurred by a vertex merge).  More than
 // max_simplices simplices in one polytope -> VOL_TOO_LARGE: every wave counts its own, and adds them to the polytope's counter (an
 // integer atomic) every VOL_BATCH simplices to stop early.
+//
+// Second moments (M2 = true): a simplex with vertices v_0..v_n, vertex sum s and volume |D| has the integral of
+// theta theta^T = |D| / ((n + 1)(n + 2)) (sum_i v_i v_i^T + s s^T).  The M2 walk is the walk above with one more sum per wave: the packed
+// upper triangle of sum |det| (sum_i v_i v_i^T + s s^T), n (n + 1) / 2 entries, entry e = lane + 64 u in accumulator u of its lane.  The
+// Gram sum of the chain comes from LDS: at NT = 4 and 8 a chain Gs[k] = sum_{i<=k} a_i a_i^T pushed with the apex like Cs[k]; at NT = 16
+// that chain would take 18.5 KB, so the chain's vertices Vx[k] are kept (2 KB) and the leaf adds their products.  The wave writes the
+// entries to slot_m2 of its row; k_volume_reduce<true> has one thread per (polytope, entry), adds the slots in row order and writes the
+// symmetric matrix.  Volume, centroid, count and status of the M2 pass are the additions of the volume pass: the same bits.
 #pragma once
 #include <stdint.h>
 
@@ -44,7 +52,15 @@ struct VolArgs {
     double *slot_vol, *slot_mom;       // [rows], [rows][nt]
     long long *slot_cnt;               // [rows]
     int32_t *slot_st;                  // [rows]
+    double *slot_m2;                   // [rows][nt (nt + 1) / 2], M2 only
 };
+
+// entry e of the packed upper triangle of an n x n matrix (row major, i <= j): i | j << 4
+__device__ inline int vol_tri_ij(int n, int e) {
+    int i = 0;
+    while (e >= n - i) { e -= n - i; ++i; }
+    return i | (i + e) << 4;
+}
 
 __device__ inline int vol_wave_min(int v) {
     for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
@@ -76,8 +92,10 @@ __global__ void __launch_bounds__(VOL_ROWSET_BLOCK) k_volume_rowsets(const int32
     }
 }
 
-template <int NT>
+template <int NT, bool M2>
 __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
+    constexpr bool GRAM = M2 && NT <= 8;              // the Gram chain in LDS; otherwise (M2) the chain's vertices
+    constexpr int NTRI = NT * (NT + 1) / 2, NE = M2 ? (NTRI + 63) / 64 : 0;
     extern __shared__ unsigned long long vol_dyn[];   // stack [nt][W], then Ct [W][m] when c_in_lds
     __shared__ double Rr[NT + 1][NT];                 // row k of the eliminated chain (k = 1..nt)
     __shared__ double Cs[NT + 1][NT];                 // a_0 + ... + a_k
@@ -86,6 +104,8 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
     __shared__ unsigned Um[NT + 1];                   // pivot columns of rows 1..k
     __shared__ unsigned long long Cand[NT + 1][4];    // rows still to try at level t
     __shared__ int Found[NT + 1];
+    __shared__ double Gs[GRAM ? NT + 1 : 1][GRAM ? NTRI : 1];             // packed a_0 a_0^T + ... + a_k a_k^T
+    __shared__ double Vx[M2 && !GRAM ? NT + 1 : 1][M2 && !GRAM ? NT : 1];  // a_k
     const int lane = threadIdx.x, nt = a.nt;
     const long long item = blockIdx.x;
     const int q = a.item_q[item], r_top = a.item_row[item];
@@ -105,6 +125,19 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
     for (int w = lane; w < W; w += 64) St[w] = (w == W - 1 && (nv & 63)) ? (1ull << (nv & 63)) - 1ull : ~0ull;
     if (lane < nt) Cs[0][lane] = X[lane];
     if (lane == 0) { Pr[0] = 1.0; Um[0] = 0u; }
+    const int ne = nt * (nt + 1) / 2;
+    double acc_m2[NE > 0 ? NE : 1];        // entry lane + 64 u of the packed triangle
+    int eij[NE > 0 ? NE : 1];
+    if constexpr (M2) {
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+            const int e = lane + 64 * u;
+            acc_m2[u] = 0.0;
+            eij[u] = e < ne ? vol_tri_ij(nt, e) : 0;
+            if constexpr (GRAM) { if (e < ne) Gs[0][e] = X[eij[u] & 15] * X[eij[u] >> 4]; }
+        }
+        if constexpr (!GRAM) { if (lane < nt) Vx[0][lane] = X[lane]; }
+    }
     __syncthreads();
 
     double acc_vol = 0.0, acc_mom = 0.0;   // acc_mom: coordinate `lane`
@@ -143,6 +176,19 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
         const double vol = Pr[nt - 1] * fabs(pivot_of(nt, x, pc));
         acc_vol += vol;
         if (lane < nt) acc_mom += vol * (Cs[nt - 1][lane] + X[(long long)v * nt + lane]);
+        if constexpr (M2) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) {
+                const int e = lane + 64 * u, i = eij[u] & 15, j = eij[u] >> 4;
+                if (e < ne) {
+                    const double vi = X[(long long)v * nt + i], vj = X[(long long)v * nt + j];
+                    double g = vi * vj + (Cs[nt - 1][i] + vi) * (Cs[nt - 1][j] + vj);
+                    if constexpr (GRAM) g += Gs[nt - 1][e];
+                    else for (int k = 0; k < nt; ++k) g += Vx[k][i] * Vx[k][j];
+                    acc_m2[u] += vol * g;
+                }
+            }
+        }
         ++count;
         if ((count & (VOL_BATCH - 1)) == 0) {
             unsigned long long tot = 0ull;
@@ -171,6 +217,10 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
     auto write_slot = [&]() {
         if (lane == 0) { a.slot_vol[slot] = acc_vol; a.slot_cnt[slot] = count; a.slot_st[slot] = status; }
         if (lane < nt) a.slot_mom[slot * nt + lane] = acc_mom;
+        if constexpr (M2) {
+#pragma unroll
+            for (int u = 0; u < NE; ++u) if (lane + 64 * u < ne) a.slot_m2[slot * ne + lane + 64 * u] = acc_m2[u];
+        }
     };
 
     if (!is_facet(St, r_top, 0)) { write_slot(); return; }
@@ -204,6 +254,11 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
             __syncthreads();
             if (lane < nt) { Rr[t][lane] = x; Cs[t][lane] = Cs[t - 1][lane] + X[(long long)apex * nt + lane]; }
             if (lane == 0) { Pc[t] = pc; Um[t] = Um[t - 1] | 1u << pc; Pr[t] = Pr[t - 1] * fabs(pv); Found[t] = 0; }
+            if constexpr (GRAM) {
+                if (lane < ne) Gs[t][lane] = Gs[t - 1][lane] + X[(long long)apex * nt + (eij[0] & 15)] * X[(long long)apex * nt + (eij[0] >> 4)];
+            } else if constexpr (M2) {
+                if (lane < nt) Vx[t][lane] = X[(long long)apex * nt + lane];
+            }
             __syncthreads();
             if (t == nt - 1) {
                 // an edge: its facet without the apex is its other vertex
@@ -246,15 +301,20 @@ __global__ void __launch_bounds__(64) k_volume_walk(VolArgs a) {
     write_slot();
 }
 
-// adds the slots of every polytope of a chunk in row order and scales: volume = sum / n!, centroid = moment / ((n + 1) sum)
+// adds the slots of every polytope of a chunk in row order and scales: volume = sum / n!, centroid = moment / ((n + 1) sum).  M2: the grid
+// has one row of blocks per entry of the packed triangle; a thread adds that entry too, second moment = sum / (n! (n + 1)(n + 2)), and
+// the threads of entry 0 write what the volume pass writes
+template <bool M2>
 __global__ void __launch_bounds__(64) k_volume_reduce(int nt, long long n, const int32_t *chunk_poly, const long long *row_off, long long max_simplices,
                                                       const double *slot_vol, const double *slot_mom, const long long *slot_cnt,
-                                                      const int32_t *slot_st, double *volume, double *centroid, long long *n_simplices,
-                                                      int32_t *status) {
+                                                      const int32_t *slot_st, const double *slot_m2, double *volume, double *centroid,
+                                                      long long *n_simplices, int32_t *status, double *second_moment) {
     const long long q = (long long)blockIdx.x * 64 + threadIdx.x;
     if (q >= n) return;
     const long long p = chunk_poly[q];
-    double vol = 0.0, mom[16];
+    const bool lead = !M2 || blockIdx.y == 0;
+    const int e = M2 ? (int)blockIdx.y : 0, ne = nt * (nt + 1) / 2;
+    double vol = 0.0, mom[16], m2 = 0.0;
     for (int c = 0; c < 16; ++c) mom[c] = 0.0;
     long long cnt = 0;
     bool large = false, bad = false;
@@ -263,18 +323,29 @@ __global__ void __launch_bounds__(64) k_volume_reduce(int nt, long long n, const
         cnt += slot_cnt[s];
         large = large || slot_st[s] == VOL_TOO_LARGE;
         bad = bad || slot_st[s] == VOL_INCONSISTENT;
+        if constexpr (M2) m2 += slot_m2[s * ne + e];
+        if (lead) {
 #pragma unroll
-        for (int c = 0; c < 16; ++c) if (c < nt) mom[c] += slot_mom[s * nt + c];
+            for (int c = 0; c < 16; ++c) if (c < nt) mom[c] += slot_mom[s * nt + c];
+        }
     }
     const int st = (large || cnt > max_simplices) ? VOL_TOO_LARGE : (bad || cnt == 0) ? VOL_INCONSISTENT : VOL_OK;
     double fact = 1.0;
     for (int k = 2; k <= nt; ++k) fact *= k;
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    status[p] = st;
-    n_simplices[p] = st == VOL_OK ? cnt : 0;
-    volume[p] = st == VOL_OK ? vol / fact : nan;
+    if (lead) {
+        status[p] = st;
+        n_simplices[p] = st == VOL_OK ? cnt : 0;
+        volume[p] = st == VOL_OK ? vol / fact : nan;
 #pragma unroll
-    for (int c = 0; c < 16; ++c) if (c < nt) centroid[p * nt + c] = st == VOL_OK ? mom[c] / ((nt + 1) * vol) : nan;
+        for (int c = 0; c < 16; ++c) if (c < nt) centroid[p * nt + c] = st == VOL_OK ? mom[c] / ((nt + 1) * vol) : nan;
+    }
+    if constexpr (M2) {
+        const int ij = vol_tri_ij(nt, e), i = ij & 15, j = ij >> 4;
+        const double v = st == VOL_OK ? m2 / (fact * ((nt + 1) * (nt + 2))) : nan;
+        second_moment[(p * nt + i) * nt + j] = v;
+        second_moment[(p * nt + j) * nt + i] = v;
+    }
 }
 
 }  // namespace mpc

@@ -253,6 +253,29 @@ class Solution:
         ef, row_off, _ = self._stacked()
         return volumes_of_rows(row_off, ef, ef.shape[1] - 1, tol=tol, max_simplices=max_simplices, device=device, who='Solution.volumes', vertices=rv)
 
+    def moments(self, tol: float = 1e-9, max_simplices=None, device: int = 0):
+        """Volume, centroid and second moment (the integral of theta theta^T) of every region: a geometry.moments.RegionMoments, from the
+        vertex lists of ``vertices(tol)`` like ``volumes()``, whose volume, centroid, simplices and status it repeats bit for bit.  See
+        DESIGN §3.18."""
+        from .geometry.moments import moments_of_rows
+        rv = self.vertices(tol=tol, device=device)
+        ef, row_off, _ = self._stacked()
+        return moments_of_rows(row_off, ef, ef.shape[1] - 1, tol=tol, max_simplices=max_simplices, device=device, who='Solution.moments', vertices=rv)
+
+    def value_function(self):
+        """(Qv [R, n, n], qv [R, n], rv [R]): J*(theta) = 1/2 theta^T Qv theta + qv^T theta + rv on region R, the objective of
+        ``program.evaluate_objective`` along the region's law x = A theta + b.  ValueError for a merged solution."""
+        from .geometry.moments import value_function
+        return value_function(self)
+
+    def expected_values(self, max_simplices=None, device: int = 0):
+        """Exact averages for theta uniform on the union of the OK regions: a geometry.moments.ExpectedValues with the volume, the
+        integral and the mean of the value function, mean and covariance of x* and of theta, the integral and volume per region,
+        status_counts and ok (no region left undecided).  ValueError for overlapping (mpLP), mixed-integer and merged solutions.  See
+        DESIGN §3.18."""
+        from .geometry.moments import expected_values
+        return expected_values(self, max_simplices=max_simplices, device=device)
+
     def coverage_volume(self, device: int = 0):
         """The exact share of the parameter space {A_t theta <= b_t} the regions cover: a geometry.volume.CoverageVolume with total (the
         summed volume of the OK regions), theta_volume, fraction, status_counts and ok (no region left undecided).  ValueError for
