@@ -517,9 +517,13 @@ int mpc_slice_intervals(int32_t device, int32_t n, int64_t n_regions, const int6
 #define MPC_LOCATE_OVERLAPPING 1
 #define MPC_LOCATE_INCLUSIVE 2
 /* MPC_LOCATE_WALK: locate by walking through adjacent regions instead of scanning the list (needs
- * mpc_locator_set_adjacency; ignored with the two flags above).  Same result as the scan -- the first region of the list that
- * contains the point within tol -- at a cost that follows the length of the walk, not the number of regions; points the walk
- * cannot resolve (no neighbour behind any violated row, step limit) are tested against every region in parallel. */
+ * mpc_locator_set_adjacency; ignored with the two flags above).  A region that contains the point within tol, at a cost that
+ * follows the length of the walk, not the number of regions; points the walk cannot resolve (no neighbour behind any violated
+ * row, step limit) or cannot certify as the first match (two or more rows of the located region within 2 tol, or one whose
+ * neighbour is unknown) are tested against every region in parallel.  Same result as the scan -- the FIRST such region of the
+ * list -- provided the rows of neighbouring regions have comparable scale (unit rows) and no region reaches a corner with a
+ * wedge angle under 60 degrees: there a point 2 tol inside the located region can lie within tol in an earlier one
+ * (csrc/locate.hpp, loc_walk). */
 #define MPC_LOCATE_WALK 4
 typedef struct mpc_locator mpc_locator;
 int mpc_locator_create(int32_t device, int32_t n_x, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows,
@@ -531,6 +535,9 @@ int mpc_locator_create(int32_t device, int32_t n_x, int32_t n_t, int64_t n_regio
 int mpc_locator_set_adjacency(mpc_locator *loc, int32_t mask_words, int32_t n_c, const uint64_t *masks, const int32_t *row_info);
 int mpc_locator_query(mpc_locator *loc, int64_t m, const double *theta, double tol, int32_t flags, int64_t *region,
                       double *x, float *ms_locate);
+/* The number of points that the last MPC_LOCATE_WALK / MPC_LOCATE_TREE query handed to the exhaustive pass (more than 16,384 of
+ * a walk: the list scan; fewer: every (point, region) pair in parallel); 0 after a query that needed none. */
+int mpc_locator_last_unresolved(mpc_locator *loc, int64_t *n_points);
 int mpc_locator_destroy(mpc_locator *loc);
 
 /* ---- point-location search trees over a solution's hyperplanes ------------------------------------------------- */

@@ -218,6 +218,7 @@ def load():
                                                ctypes.POINTER(ctypes.c_void_p)]),
         'mpc_locator_query': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _dp, ctypes.c_double, ctypes.c_int32, _lp, _dp,
                                               ctypes.POINTER(ctypes.c_float)]),
+        'mpc_locator_last_unresolved': (ctypes.c_int, [ctypes.c_void_p, _lp]),
         'mpc_locator_destroy': (ctypes.c_int, [ctypes.c_void_p]),
         'mpc_locator_set_adjacency': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, _u64p, _ip]),
         'mpc_host_alloc': (ctypes.c_int, [ctypes.c_uint64, ctypes.POINTER(ctypes.c_void_p)]),
@@ -284,7 +285,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_frontier_root', 'mpc_frontier_set', 'mpc_frontier_set_device', 'mpc_frontier_info',
                     'mpc_frontier_get', 'mpc_pruned_clear', 'mpc_pruned_add', 'mpc_pruned_add_device',
                     'mpc_pruned_count', 'mpc_pruned_get', 'mpc_level_run', 'mpc_level_run_ex', 'mpc_level_run_batch', 'mpc_frontier_advance_batch', 'mpc_level_memory_gb', 'mpc_trim', 'mpc_level_batch_start', 'mpc_level_batch_wait', 'mpc_level_regions_slots_nowait', 'mpc_level_batch_fetch', 'mpc_level_status', 'mpc_level_start', 'mpc_level_stream_info', 'mpc_level_chunk_wait', 'mpc_level_wait', 'mpc_level_stream_fixup', 'mpc_base_result', 'mpc_solve_start', 'mpc_solve_level', 'mpc_solve_chunk_wait', 'mpc_solve_level_wait', 'mpc_solve_wait', 'mpc_level_regions', 'mpc_compact_strides',
-                    'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
+                    'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_last_unresolved', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments']
@@ -1384,6 +1385,15 @@ class Locator:
             raise MpcError(f'mpc_locator_query failed ({rc}): {self._L.mpc_last_global_error().decode()}')
         self.last_ms = float(ms.value)
         return region, x
+
+    @property
+    def last_unresolved(self) -> int:
+        """Points of the last walk or tree query that went to the exhaustive pass (mpc_locator_last_unresolved)."""
+        n = ctypes.c_int64(0)
+        rc = self._L.mpc_locator_last_unresolved(self._h, ctypes.byref(n))
+        if rc != MPC_OK:
+            raise MpcError(f'mpc_locator_last_unresolved failed ({rc})')
+        return int(n.value)
 
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, w=None, box=None, seed: int = 0, tol: float = 1e-5,
                  stop_tol: Optional[float] = None, overlapping: bool = False, inclusive: bool = False, walk: bool = False, tree: bool = False,

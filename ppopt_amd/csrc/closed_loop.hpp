@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(SIM_BLOCK) k_simulate(SimArgs a) {
                                  a.cvec, a.H, a.tol, a.overlapping, a.inclusive, stack);
             else
                 r = loc_walk<NT, MODE == SIM_WALK2 ? 2 : 4>(th, nt, a.n_regions, a.row_off, a.ef, a.row_info, a.masks, a.sorted_masks,
-                                                            a.sorted_region, a.tol, prev, a.max_walk, a.n_c, n_cross, true);
+                                                            a.sorted_region, a.tol, prev, a.max_walk, a.n_c, n_cross);
             if (r == -2) {
                 r = loc_scan_lane<NT>(th, nt, a.nx, a.n_regions, a.row_off, a.ef, a.xlaw, a.Q, a.cvec, a.H, a.tol, a.overlapping, a.inclusive);
                 ++n_fb;

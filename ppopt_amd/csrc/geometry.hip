@@ -328,6 +328,7 @@ extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta,
     const bool tree = (flags & MPC_LOCATE_TREE) != 0;
     if (tree && !L->has_tree) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: MPC_LOCATE_TREE without an attached tree");
     if (tree && !(tol <= L->tree_tol)) return fail(nullptr, MPC_ERR_INVALID, "mpc_locator_query: tol is larger than the tolerance the tree was built for");
+    L->last_unresolved = 0;
     if (m == 0) return MPC_OK;
     HIP_TRY(nullptr, hipSetDevice(L->device));
     hipStream_t st = L->stream;
@@ -380,6 +381,12 @@ extern "C" int mpc_locator_query(mpc_locator *L, int64_t m, const double *theta,
     }
     HIP_TRY(nullptr, hipStreamSynchronize(st));
     if (ms_locate) HIP_TRY(nullptr, hipEventElapsedTime(ms_locate, L->e0, L->e1));
+    return MPC_OK;
+}
+
+extern "C" int mpc_locator_last_unresolved(mpc_locator *L, int64_t *n_points) {
+    if (!L || !n_points) return MPC_ERR_INVALID;
+    *n_points = L->last_unresolved;
     return MPC_OK;
 }
 

@@ -173,20 +173,30 @@ __device__ __forceinline__ long long loc_scan_lane(const double (&th)[NT], int n
 // parameter set is outside the solution (-1); a walk that finds no neighbour behind any violated row (not even with a second
 // row exchanged, the degenerate case), meets a region without facet information or reaches the step limit leaves the point
 // UNRESOLVED (-2), and the host hands it to k_locate_few / the list scan.
-// To return the region the scan would return (the FIRST containing region of the list), a located point is also offered to
-// the neighbours across the rows it satisfies by less than 2*tol, if their index is smaller.
+// To return the region the scan would return (the FIRST containing region of the list), the located region is certified by the
+// 2*tol rule: a point that satisfies every row by 2*tol or more is taken to lie in no other region within tol.  With exactly ONE row
+// nearer than that, the only other candidate is taken to be the neighbour across it, which wins if it comes earlier in the list and
+// contains the point within tol; if that neighbour is unknown the point is left unresolved.  With TWO OR MORE near rows the point
+// is next to a face of codimension >= 2, where regions that are no neighbours across a row (diagonally across a corner) may contain
+// it too: unresolved (-2) as well, and the exhaustive pass decides.  A row value that is not a number (NaN in theta) is never
+// certified either.
+// ASSUMPTION of the 2*tol rule: tol is applied to the row values as they are stored, so the rows of neighbouring regions have
+// comparable scale (unit rows: the values are distances), and the facets that meet in a corner do so at a right or obtuse angle.  A
+// region diagonally across a corner of acute wedge angle alpha holds points up to tol / sin(alpha / 2) from the corner, which exceeds
+// 2 tol below 60 degrees: such a point can be 2 tol from both rows of the located region and still lie within tol in an earlier
+// region, and the walk then returns the located one.  The same holds where one region's rows are scaled far below its neighbour's.
+// Within the assumption the walk returns the scan's region; outside it, a region that contains the point within tol, not always
+// the first of the list.
 // row_info[row] = kind << 16 | id:  kind 0 multiplier row of active constraint id, 1 inactive constraint id, 2 A_t row, 3 unknown.
 // The walk of one lane from start_region (shared by k_locate_walk and k_simulate): the region (-1 outside, -2 unresolved); `crossings`
-// counts the regions crossed.  certify_first (k_simulate, whose walks start anywhere): a located point with a row within 2 tol whose
-// neighbour is unknown is left unresolved, since an earlier region behind that row may contain it too.
+// counts the regions crossed.
 template <int NT, int MW>
 __device__ __forceinline__ long long loc_walk(const double (&th)[NT], int nt, long long n_regions, const long long *__restrict__ row_off,
                                               const double *__restrict__ ef, const int32_t *__restrict__ row_info,
                                               const unsigned long long *__restrict__ masks,          // [n_regions][MW], region order
                                               const unsigned long long *__restrict__ sorted_masks,   // [n_regions][MW], ascending
                                               const int32_t *__restrict__ sorted_region,             // region of sorted_masks[i]
-                                              double tol, long long start_region, int max_steps, int n_c, unsigned long long &crossings,
-                                              bool certify_first = false) {
+                                              double tol, long long start_region, int max_steps, int n_c, unsigned long long &crossings) {
     const int nr = nt + 1;
     auto lookup = [&](const unsigned long long (&key)[MW]) -> long long {
         long long lo = 0, hi = n_regions;
@@ -298,25 +308,26 @@ __device__ __forceinline__ long long loc_walk(const double (&th)[NT], int nt, lo
         break;
     }
     if (found >= 0) {
-        // first-match rule of the list scan: an earlier region that also contains the point within the tolerance wins
-        long long best = found;
+        // first-match rule of the list scan: certify the located region (see above)
+        int near = 0;
+        long long near_row = -1;
         for (long long i = row_off[found]; i < row_off[found + 1]; ++i) {
             double v = -ef[i * nr];
 #pragma unroll
             for (int t = 0; t < NT; ++t) if (t < nt) v = fma(ef[i * nr + 1 + t], th[t], v);
-            if (v > -2.0 * tol) {
-                const long long q = neighbour(found, i);
-                if (q >= 0 && q < best) {
-                    double w; long long wr;
-                    worst_row(q, w, wr);
-                    if (wr >= 0 && w < tol) best = q;
-                } else if (certify_first && q == -2) {   // what lies behind this near row is unknown: the rule cannot be certified
-                    best = -2;
-                    break;
-                }
+            if (!(v < tol)) { near = 2; break; }   // NaN: not located at all
+            if (v > -2.0 * tol) { ++near; near_row = i; }
+        }
+        if (near >= 2) found = -2;
+        else if (near == 1) {
+            const long long q = neighbour(found, near_row);
+            if (q == -2) found = -2;               // what lies behind the near row is unknown
+            else if (q >= 0 && q < found) {
+                double w; long long wr;
+                worst_row(q, w, wr);
+                if (wr >= 0 && w < tol) found = q;
             }
         }
-        found = best;
     }
     return found;
 }
