@@ -34,6 +34,7 @@
 #include <memory>
 
 #include "batch_level.hpp"
+#include "level_launch.hpp"
 #include "setup_mfma.hpp"
 #include "host_common.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -1313,6 +1314,80 @@ static void small_debug_note(const int32_t *cnt_host) {
     g_small_levels++; g_small_retry_theta += (cnt_host[12] + cnt_host[4]) > 0; g_small_retry_x += cnt_host[24] > 0; g_small_retry_cands += cnt_host[12] + cnt_host[4] + cnt_host[24];
 }
 
+// ---- what the three forms of a level (no round trips, batch member, classic) share besides their kernels (level_launch.hpp) ---------
+// shape of the level's region records (doubles / ints per slot) and the region stage's per-level state
+static void level_record_shape(mpc_handle *h, int k) {
+    h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
+    h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
+    h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
+}
+// partition spec of k_partition_small / k_part_*: status -> class nibble, 15 = none
+static unsigned long long part_spec(std::initializer_list<std::pair<int, int>> classes) {
+    unsigned long long spec = ~0ull;
+    for (const auto &sc : classes) spec = (spec & ~(15ull << (4 * sc.first))) | ((unsigned long long)sc.second << (4 * sc.first));
+    return spec;
+}
+static int dict_nxc(const mpc_handle *h) { return h->fast_x >= 2 ? 32 : 16; }   // dictionary columns k_x2 keeps
+// does a level of nn candidates keep its dictionaries for its children?  (one record per candidate, within dict_budget_gb)
+static bool dict_will_store(const mpc_handle *h, size_t nn, int32_t gen_children) {
+    const int nxc = dict_nxc(h);
+    const double need_gb = (double)nn * ((long long)nxc * h->Pf.n_d0r * 8.0 + dict_ints(h->Pf.n_d0r, nxc, h->n_c) * 4.0) / 1e9;
+    return gen_children && need_gb <= h->dict_budget_gb;
+}
+// The dictionary cache of a level's (x,theta) stage: record strides, the previous level's records if its children know their parent
+// slots, and -- if the level stores (h->storing) -- this level's buffers.  The clearing of dict_stored[dict_cur] is the caller's.
+static int dict_cache_begin(mpc_handle *h, size_t nn, int32_t gen_children, hipStream_t st, DictCache &dc) {
+    const int nxc = dict_nxc(h);
+    h->dict_stride_d = (long long)nxc * h->Pf.n_d0r;   // column-major tableau
+    h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
+    dc = DictCache{};
+    dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
+    dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
+    if (h->have_prev_dict && h->have_parent_slot) {
+        dc.parent_slot = h->parent_slot.as<int32_t>();
+        dc.prev_d = h->dict_d[1 - h->dict_cur].as<double>(); dc.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
+    }
+    h->storing = false;
+    if (dict_will_store(h, nn, gen_children)) {
+        HIP_TRY(h, h->dict_d[h->dict_cur].ensure(nn * h->dict_stride_d * sizeof(double), st));
+        HIP_TRY(h, h->dict_i[h->dict_cur].ensure(nn * h->dict_stride_i * sizeof(int32_t), st));
+        HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
+        dc.cur_d = h->dict_d[h->dict_cur].as<double>(); dc.cur_i = h->dict_i[h->dict_cur].as<int32_t>(); dc.stored = h->dict_stored[h->dict_cur].as<uint8_t>();
+        h->storing = true;
+    }
+    return MPC_OK;
+}
+// the end of a level that ran to its end (behind its closing synchronisation; not on a path's fallback return)
+static void level_close(mpc_handle *h, long long n) { graveyard_flush(h); h->level_done = true; h->last_level_n = n; stream_ready(h); }
+// bytes of one dictionary record that are actually moved: the used columns (value + D0 columns) and the integer part
+// (what k_x2 reads of a record; the stored record also carries the children's look-up bytes)
+static long long dict_record_bytes(const mpc_handle *h) { return (long long)(h->Pf.n_d0c + 1) * h->Pf.n_d0r * 8 + (long long)dict_ints_head(h->Pf.n_d0r, dict_nxc(h)) * 4; }
+// the statistics every form of a level reports alike; the caller adds its own (times, work-item counts, dictionary traffic)
+static void level_stats_common(const mpc_handle *h, const LevelCounters &host_ctr, mpc_level_stats *stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->n = h->n; stats->k = h->k; stats->kkt_mode = h->kkt_mode;
+    for (int i = 0; i < 6; ++i) stats->n_status[i] = (int64_t)host_ctr.status[i];
+    stats->n_regions = h->n_regions; stats->n_children = h->n_children; stats->n_pruned_new = h->n_pruned_new;
+    stats->lp_pivots = (int64_t)host_ctr.pivots; stats->n_xtheta_fallback = (int64_t)host_ctr.xtheta_fallbacks;
+    for (int i = 0; i < 4; ++i) stats->wave_cycles[i] = (int64_t)host_ctr.cycles[i];
+    stats->n_x_cached = (int64_t)host_ctr.x_cached; stats->n_region_rows = h->n_erows; stats->n_opt = h->n_opt; stats->xq_pivots = (int64_t)host_ctr.xq_pivots;
+    stats->xq_record_ints = dict_ints_head(h->Pf.n_d0r, dict_nxc(h)) - 1; stats->xq_record_rows = h->Pf.n_d0r; stats->xq_record_cols = h->Pf.n_d0c + 1;
+}
+
+// ... and what the two forms without host round trips add alike: the work-item counts from the published list lengths (dcnt layout below),
+// k_region2's own wall-clock time, the dictionary traffic
+static void level_stats_small(const mpc_handle *h, const LevelCounters &host_ctr, const int32_t *cnt_host, bool kkt, bool quick_test, mpc_level_stats *stats) {
+    level_stats_common(h, host_ctr, stats);
+    stats->n_xtheta_lp = h->n_needx;
+    stats->n_theta_items = kkt ? cnt_host[0] : h->n;
+    if (h->n_opt > 0 && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)   // k_region2 times itself on the wall clock
+        stats->ms_region2 = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);
+    stats->n_xq_items = quick_test ? cnt_host[7] : 0;
+    stats->n_x_items = (quick_test ? cnt_host[8] : cnt_host[7]) + (h->storing ? (long long)cnt_host[5] + cnt_host[6] : 0);
+    stats->dict_read_bytes = (h->have_prev_dict && h->have_parent_slot) ? dict_record_bytes(h) : 0;
+    stats->dict_write_bytes = h->storing ? dict_record_bytes(h) : 0;
+}
+
 static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, mpc_level_stats *stats, bool *fallback) {
     *fallback = false;
     { int rcj = x1_join(h); if (rcj) return rcj; }
@@ -1330,9 +1405,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
     {
         // counters, list lengths, the region kernel's completion flags and the "dictionary stored" flags: cleared by one launch
-        const int nxc_ = h->fast_x >= 2 ? 32 : 16;
-        const double need_gb_ = (double)nn * ((double)nxc_ * h->Pf.n_d0r * 8.0 + (double)dict_ints(h->Pf.n_d0r, nxc_, h->n_c) * 4.0) / 1e9;
-        const bool will_store = gen_children && need_gb_ <= h->dict_budget_gb;
+        const bool will_store = dict_will_store(h, nn, gen_children);
         HIP_TRY(h, h->done_g.ensure(nn * 2 * sizeof(unsigned int), st));
         if (will_store) HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
         ZeroBufs z{};
@@ -1348,15 +1421,8 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     uint8_t *stp = h->status.as<uint8_t>();
     const DevProblem *pf = h->pf_dev.as<DevProblem>();
     auto part_list = [&](int c) -> int32_t * { return h->part_lists.as<int32_t>() + (size_t)c * nn; };
-    auto spec_of = [](std::initializer_list<std::pair<int, int>> classes) {
-        unsigned long long spec = ~0ull;
-        for (const auto &sc : classes) spec = (spec & ~(15ull << (4 * sc.first))) | ((unsigned long long)sc.second << (4 * sc.first));
-        return spec;
-    };
     const int blocks256 = (int)((n + 255) / 256);
-    h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
-    h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
-    h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
+    level_record_shape(h, k);
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[0], st));
     // ---- KKT solves + box screen, theta stage ----------------------------------------------------------------------------------
     const uint8_t *kkc = nullptr;
@@ -1379,31 +1445,13 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         }
         // KKT_SPREAD lanes per candidate while the active set is small (the kernel's comment): the level's 50 us floor becomes ~15
         const bool spread = h->kkt_spread > 0 && kd <= KKT_SPREAD_KMAX;
-        const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256)), b(256);
-#define MPC_LAUNCH_KKT_(K_, SP_) if (h->fast_t >= 4) hipLaunchKernelGGL((k_kkt_thread<K_, 10, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr); \
-                                    else if (h->fast_t >= 2) hipLaunchKernelGGL((k_kkt_thread<K_, 8, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr); \
-                                    else hipLaunchKernelGGL((k_kkt_thread<K_, 4, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr)
-#define MPC_LAUNCH_KKT(K_) case K_: MPC_LAUNCH_KKT_(K_, 1); break
-#define MPC_LAUNCH_KKT_S(K_) case K_: if (spread) { MPC_LAUNCH_KKT_(K_, KKT_SPREAD); } else { MPC_LAUNCH_KKT_(K_, 1); } break
-        switch (kd) { MPC_LAUNCH_KKT_S(1); MPC_LAUNCH_KKT_S(2); MPC_LAUNCH_KKT_S(3); MPC_LAUNCH_KKT_S(4); MPC_LAUNCH_KKT_S(5); MPC_LAUNCH_KKT_S(6); MPC_LAUNCH_KKT(7); MPC_LAUNCH_KKT(8); MPC_LAUNCH_KKT(9); MPC_LAUNCH_KKT(10); }
-#undef MPC_LAUNCH_KKT_S
-#undef MPC_LAUNCH_KKT
-#undef MPC_LAUNCH_KKT_
+        const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256));
+        launch_kkt_thread(kd, h->fast_t, spread, g, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr);
         if (!kkt_lists) hipLaunchKernelGGL(k_compact_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, ST_TODO, ST_TODO, h->theta_list.as<int32_t>(), dcnt + 0);
         theta_list = h->theta_list.as<int32_t>();
         ta.n_dev = dcnt + 0;
     }
-    {
-        const dim3 g((unsigned)std::min<long long>(n, h->grid_f)), b(64);
-        switch (h->fast_t) {
-            case 0: hipLaunchKernelGGL((k_theta2<4, 1>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-            case 1: hipLaunchKernelGGL((k_theta2<4, 2>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-            case 2: hipLaunchKernelGGL((k_theta2<8, 1>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-            case 3: hipLaunchKernelGGL((k_theta2<8, 2>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-            case 4: hipLaunchKernelGGL((k_theta2<10, 1>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-            default: hipLaunchKernelGGL((k_theta2<10, 2>), g, b, h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-        }
-    }
+    launch_theta2(h->fast_t, dim3((unsigned)std::min<long long>(n, h->grid_f)), h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list);
     // the doubtful candidates of the theta stage are re-solved in place by the LDS engine first (the classic path does this on a
     // side stream under the (x,theta) stage), so that the partition below already knows every optimal candidate they yield
     // Round 5 (`fused`): doubtful candidates are rare (numerically doubtful pivots of the register simplex), so the level does not spend
@@ -1412,15 +1460,15 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     // the other rare cases.  The end of the level is one launch (k_small_end) instead of five, the scan carries the publish.
     const bool fused = !h->theta_open && !h->no_small_fuse;
     if (!fused) {
-        hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, spec_of({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 12);
+        hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 12);
         hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 12);
         // open parameter set: "optimal" only if the reference's max-t LP is bounded (k_recession), decided before the region launch below
         if (h->theta_open) hipLaunchKernelGGL(k_recession, dim3((unsigned)std::min<long long>(n, 256)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp);
     }
     // classes after the theta stage: [1] feasible, [2] optimal, [3] feasibility open ([0] doubtful, fused form only)
     hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n,
-                       fused ? spec_of({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}})
-                             : spec_of({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 4);
+                       fused ? part_spec({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}})
+                             : part_spec({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 4);
     HIP_TRY(h, hipGetLastError());
     // ---- region stage: one slot per optimal candidate, buffers sized by the bound.  It needs the theta stage's verdicts only; a
     // candidate that turns out optimal only later -- a doubtful one of the (x,theta) stage, re-solved -- sends the level to the classic
@@ -1444,7 +1492,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         const int W = h->no_rsplit ? 1 : 0;   // 0: chosen in the kernel from the number of optimal candidates
         grid_r = (unsigned)std::min<long long>(n * std::max(h->rsplit_max, 1), h->grid_r2);
         const DevProblem *pr = h->pr2_dev.as<DevProblem>();
-        const int nt_r = h->fast_r <= 1 ? 4 : (h->fast_r <= 3 ? 8 : 10);
+        const int nt_r = region2_nt(h->fast_r);
         rx.pr = pr; rx.fr = h->frontier.as<int32_t>(); rx.k = k; rx.opt_list = h->opt_ptr; rx.n = (int)n; rx.status = h->status.as<uint8_t>();
         rx.headd = h->headd.as<double>(); rx.headi = h->headi.as<int32_t>(); rx.fd = h->fd; rx.fi = h->fi; rx.epool = h->epool.as<double>(); rx.ctr = ctr;
         rx.kkc = kkc; rx.kkl = kkl; rx.W = W; rx.kept_g = h->kept_g.as<uint8_t>(); rx.ldk = ldk; rx.done_g = h->done_g.as<unsigned int>();
@@ -1452,44 +1500,18 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         h->used_region2 = true;
     }
     // (the launch itself comes below: together with the (x,theta) kernel in one grid where an instantiation of the pair exists)
-    auto launch_region2 = [&]() -> int {
-        const dim3 g(grid_r), b(64);
-#define MPC_LAUNCH_R2(NT_, SL_) hipLaunchKernelGGL((k_region2<NT_, SL_>), g, b, h->lds_r2, st, rx.pr, rx.fr, rx.k, rx.opt_list, rx.n, rx.status, rx.headd, rx.headi, rx.fd, rx.fi, rx.epool, \
-                                                   rx.ctr, rx.kkc, rx.kkl, rx.W, rx.kept_g, rx.ldk, rx.done_g, rx.tvp_box, rx.rs)
-        switch (h->fast_r) {
-            case 0: MPC_LAUNCH_R2(4, 1); break;
-            case 1: MPC_LAUNCH_R2(4, 2); break;
-            case 2: MPC_LAUNCH_R2(8, 1); break;
-            case 3: MPC_LAUNCH_R2(8, 2); break;
-            case 4: MPC_LAUNCH_R2(10, 1); break;
-            default: MPC_LAUNCH_R2(10, 2); break;
-        }
-#undef MPC_LAUNCH_R2
+    auto region2_alone = [&]() -> int {
+        launch_region2(h->fast_r, dim3(grid_r), h->lds_r2, st, rx.pr, rx.fr, rx.k, rx.opt_list, rx.n, rx.status, rx.headd, rx.headi, rx.fd, rx.fi, rx.epool,
+                       rx.ctr, rx.kkc, rx.kkl, rx.W, rx.kept_g, rx.ldk, rx.done_g, rx.tvp_box, rx.rs);
         HIP_TRY(h, hipGetLastError());
         return MPC_OK;
     };
     if (!fused) HIP_TRY(h, hipMemsetAsync(&ctr->work_retry, 0, sizeof(unsigned int), st));
     // ---- (x,theta) stage with the dictionary cache ---------------------------------------------------------------------------------
-    const int nxc = h->fast_x >= 2 ? 32 : 16;
-    h->dict_stride_d = (long long)nxc * h->Pf.n_d0r;
-    h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
-    DictCache dc{};
-    dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
-    dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
-    if (h->have_prev_dict && h->have_parent_slot) {
-        dc.parent_slot = h->parent_slot.as<int32_t>();
-        dc.prev_d = h->dict_d[1 - h->dict_cur].as<double>();
-        dc.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
-    }
-    h->storing = false;
-    const double need_gb = (double)nn * (h->dict_stride_d * 8.0 + h->dict_stride_i * 4.0) / 1e9;
-    if (gen_children && need_gb <= h->dict_budget_gb) {
-        HIP_TRY(h, h->dict_d[h->dict_cur].ensure(nn * h->dict_stride_d * sizeof(double), st));
-        HIP_TRY(h, h->dict_i[h->dict_cur].ensure(nn * h->dict_stride_i * sizeof(int32_t), st));
-        HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
-        dc.cur_d = h->dict_d[h->dict_cur].as<double>(); dc.cur_i = h->dict_i[h->dict_cur].as<int32_t>();
-        dc.stored = h->dict_stored[h->dict_cur].as<uint8_t>();
-        h->storing = true;
+    const int nxc = dict_nxc(h);
+    DictCache dc;
+    { int rcd = dict_cache_begin(h, nn, gen_children, st, dc); if (rcd) return rcd; }
+    if (h->storing) {
         dc.pre1 = part_list(1); dc.n_pre1_dev = dcnt + 5;
         dc.pre2 = part_list(2); dc.n_pre2_dev = dcnt + 6;
     }
@@ -1507,13 +1529,12 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         merged_rx = small_region2_x2_launch(h->fast_r, h->fast_x, grid_r, (unsigned)std::min<long long>(n, (long long)h->n_cu * 16), h->lds_r2, st, rx, &e_rx);
         if (merged_rx) HIP_TRY(h, e_rx);
     }
-    if (!merged_rx) { int rcr = launch_region2(); if (rcr) return rcr; }
+    if (!merged_rx) { int rcr = region2_alone(); if (rcr) return rcr; }
     if (quick_test) {   // last level: decisions only -- the quick test on a few vectors of the parent's dictionary first
         DictCache dq = dc;
         dq.n_list_dev = needx_n;
-        const dim3 gg((unsigned)std::min<long long>(n, (long long)h->n_cu * 32)), bb(64);
-        if (h->fast_x & 1) hipLaunchKernelGGL((k_xq<2>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, dq, nxc);
-        else hipLaunchKernelGGL((k_xq<1>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, dq, nxc);
+        const dim3 gg((unsigned)std::min<long long>(n, (long long)h->n_cu * 32));
+        launch_xq(h->fast_x, gg, st, pf, fr, k, needx_list, (int)n, stp, ctr, dq, nxc);
         hipLaunchKernelGGL(k_compact_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, ST_NEEDX, ST_NEEDX_SING, h->retry_list.as<int32_t>(), dcnt + 8);
         needx_list = h->retry_list.as<int32_t>();
         needx_n = dcnt + 8;
@@ -1522,13 +1543,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         DictCache d = dc;
         d.n_list_dev = needx_n;
         // bound of the work items: every candidate once (open, or decided and expanded for its dictionary)
-        const dim3 gg((unsigned)std::min<long long>(n, (long long)h->n_cu * 16)), bb(64);
-        switch (h->fast_x) {
-            case 0: hipLaunchKernelGGL((k_x2<16, 1>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, d); break;
-            case 1: hipLaunchKernelGGL((k_x2<16, 2>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, d); break;
-            case 2: hipLaunchKernelGGL((k_x2<32, 1>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, d); break;
-            default: hipLaunchKernelGGL((k_x2<32, 2>), gg, bb, 0, st, pf, fr, k, needx_list, (int)n, stp, ctr, d); break;
-        }
+        launch_x2(h->fast_x, dim3((unsigned)std::min<long long>(n, (long long)h->n_cu * 16)), st, pf, fr, k, needx_list, (int)n, stp, ctr, d);
     }
     HIP_TRY(h, hipGetLastError());
     const int keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
@@ -1539,26 +1554,22 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         // pruned masks (and, on a level without children, the publish): one launch
         if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev[1], st)); HIP_TRY(h, hipEventRecord(h->ev[2], st)); }
         unsigned long long *pout = h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw;
-        if (h->mw == 2) hipLaunchKernelGGL(k_small_end<2>, dim3(1), dim3(1024), 0, st, fr, (int)n, k, stp, pout, ctr, keep_lowdim, dcnt + 24, dcnt + 17,
-                                           reinterpret_cast<const unsigned int *>(dcnt), 32, gen_children ? (unsigned int *)nullptr : pub_dst);
-        else hipLaunchKernelGGL(k_small_end<4>, dim3(1), dim3(1024), 0, st, fr, (int)n, k, stp, pout, ctr, keep_lowdim, dcnt + 24, dcnt + 17,
-                                reinterpret_cast<const unsigned int *>(dcnt), 32, gen_children ? (unsigned int *)nullptr : pub_dst);
+        launch_small_end(h->mw, st, fr, (int)n, k, stp, pout, ctr, keep_lowdim, dcnt + 24, dcnt + 17, reinterpret_cast<const unsigned int *>(dcnt), 32,
+                         gen_children ? (unsigned int *)nullptr : pub_dst);
         HIP_TRY(h, hipGetLastError());
     } else {
     // doubtful candidates of the (x,theta) stage (rare): re-solved in place as well
-    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, spec_of({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 24);
+    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 24);
     hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 24);
     HIP_TRY(h, hipGetLastError());
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], st));
     // a candidate that is still "optimal, region pending" now was not in the region launch: counted in [17]
-    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, spec_of({{ST_OPT_PENDING, 1}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 16);
+    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_OPT_PENDING, 1}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 16);
     HIP_TRY(h, hipGetLastError());
     if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[2], st));
     // ---- pruned masks of this level + children -------------------------------------------------------------------------------------
-    if (h->mw == 2) hipLaunchKernelGGL(k_pruned_append<2>, dim3(blocks256), dim3(256), 0, st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                       h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
-    else hipLaunchKernelGGL(k_pruned_append<4>, dim3(blocks256), dim3(256), 0, st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                            h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
+    launch_pruned_append(h->mw, dim3(blocks256), st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
+                         h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
     }
     if (gen_children) {
         HIP_TRY(h, h->childmask.ensure(nn * h->mw * sizeof(uint64_t), st));
@@ -1567,10 +1578,8 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         const size_t child_bound = nn * (size_t)std::max(h->n_c - k, 1);
         HIP_TRY(h, h->children.ensure(child_bound * (k + 1) * sizeof(int32_t), st));
         HIP_TRY(h, h->parent_slot_next.ensure(child_bound * sizeof(int32_t), st));
-        if (h->mw == 2) hipLaunchKernelGGL(k_children_count<2>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                           h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
-        else hipLaunchKernelGGL(k_children_count<4>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
+        launch_children_count(h->mw, dim3((unsigned)n), st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
+                              h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
         if (fused) hipLaunchKernelGGL(k_scan_publish, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20,
                                       reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4), reinterpret_cast<const unsigned int *>(dcnt), 32, pub_dst);
         else hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20);
@@ -1614,31 +1623,9 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     h->n_pruned_new = host_ctr.n_pruned_new;
     h->n_erows = host_ctr.e_rows;
     h->n_regions = (long long)host_ctr.status[ST_REGION];
-    graveyard_flush(h);   // (behind the level's closing synchronisation)
-    h->level_done = true;
-    h->last_level_n = n;
-    stream_ready(h);
+    level_close(h, n);
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n = n; stats->k = k; stats->kkt_mode = h->kkt_mode;
-        for (int i = 0; i < 6; ++i) stats->n_status[i] = (int64_t)host_ctr.status[i];
-        stats->n_regions = h->n_regions; stats->n_children = h->n_children; stats->n_pruned_new = h->n_pruned_new;
-        stats->lp_pivots = (int64_t)host_ctr.pivots;
-        stats->n_xtheta_lp = h->n_needx;
-        stats->n_xtheta_fallback = (int64_t)host_ctr.xtheta_fallbacks;
-        for (int i = 0; i < 4; ++i) stats->wave_cycles[i] = (int64_t)host_ctr.cycles[i];
-        stats->n_x_cached = (int64_t)host_ctr.x_cached;
-        stats->n_region_rows = h->n_erows;
-        stats->n_opt = h->n_opt;
-        stats->n_theta_items = kkc ? cnt_host[0] : n;
-        if (h->n_opt > 0 && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)   // k_region2 times itself on the wall clock
-            stats->ms_region2 = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);
-        stats->n_xq_items = quick_test ? cnt_host[7] : 0; stats->xq_pivots = (int64_t)host_ctr.xq_pivots;
-        stats->n_x_items = (quick_test ? cnt_host[8] : cnt_host[7]) + (h->storing ? (long long)cnt_host[5] + cnt_host[6] : 0);
-        stats->xq_record_ints = dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) - 1; stats->xq_record_rows = h->Pf.n_d0r; stats->xq_record_cols = h->Pf.n_d0c + 1;
-        const long long rec_bytes = (long long)(h->Pf.n_d0c + 1) * h->Pf.n_d0r * 8 + (long long)dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) * 4;   // (what k_x2 reads of a record; the stored record also carries the children's look-up bytes)
-        stats->dict_read_bytes = (h->have_prev_dict && h->have_parent_slot) ? rec_bytes : 0;
-        stats->dict_write_bytes = h->storing ? rec_bytes : 0;
+        level_stats_small(h, host_ctr, cnt_host, kkc != nullptr, quick_test, stats);
         stats->ms_verdict = ms[0]; stats->ms_region = ms[1]; stats->ms_children = ms[2]; stats->ms_total = ms[0] + ms[1] + ms[2];
     }
     return MPC_OK;
@@ -1661,9 +1648,7 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
     HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
     HIP_TRY(h, h->part_lists.ensure((size_t)PART_CLASSES * nn * sizeof(int32_t), st));
     HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
-    h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
-    h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
-    h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
+    level_record_shape(h, k);
     m.k = k; m.kd = k - h->targs.ne; m.fast_t = h->fast_t; m.fast_x = h->fast_x; m.fast_r = h->fast_r; m.mw = h->mw;
     m.gen_children = gen_children ? 1 : 0;
     m.n = n; m.grid_f = h->grid_f; m.grid_r2 = h->grid_r2; m.n_cu = h->n_cu; m.lds_f = h->lds_f; m.lds_v = h->lds_v; m.lds_r2 = h->lds_r2;
@@ -1716,28 +1701,11 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
         m.rec_d = h->rec_d; m.rec_i = h->rec_i; m.Pr = h->Pr; m.lds_r = h->lds_r;
     }
     // (x,theta) stage with the dictionary cache
-    const int nxc = h->fast_x >= 2 ? 32 : 16;
-    m.nxc = nxc;
-    h->dict_stride_d = (long long)nxc * h->Pf.n_d0r;
-    h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
-    DictCache dc{};
-    dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
-    dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
-    if (h->have_prev_dict && h->have_parent_slot) {
-        dc.parent_slot = h->parent_slot.as<int32_t>();
-        dc.prev_d = h->dict_d[1 - h->dict_cur].as<double>();
-        dc.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
-    }
-    h->storing = false;
-    const double need_gb = (double)nn * (h->dict_stride_d * 8.0 + h->dict_stride_i * 4.0) / 1e9;
-    if (gen_children && need_gb <= h->dict_budget_gb) {
-        HIP_TRY(h, h->dict_d[h->dict_cur].ensure(nn * h->dict_stride_d * sizeof(double), st));
-        HIP_TRY(h, h->dict_i[h->dict_cur].ensure(nn * h->dict_stride_i * sizeof(int32_t), st));
-        HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
+    m.nxc = dict_nxc(h);
+    DictCache dc;
+    { int rcd = dict_cache_begin(h, nn, gen_children, st, dc); if (rcd) return rcd; }
+    if (h->storing) {
         m.zero[m.n_zero++] = {h->dict_stored[h->dict_cur].p, nn};
-        dc.cur_d = h->dict_d[h->dict_cur].as<double>(); dc.cur_i = h->dict_i[h->dict_cur].as<int32_t>();
-        dc.stored = h->dict_stored[h->dict_cur].as<uint8_t>();
-        h->storing = true;
         dc.pre1 = part_list(1); dc.n_pre1_dev = m.dcnt + 5;
         dc.pre2 = part_list(2); dc.n_pre2_dev = m.dcnt + 6;
     }
@@ -1788,32 +1756,10 @@ static int batch_finish(mpc_handle *h, int32_t gen_children, const BatchMember &
     h->n_pruned_new = host_ctr.n_pruned_new;
     h->n_erows = host_ctr.e_rows;
     h->n_regions = (long long)host_ctr.status[ST_REGION];
-    graveyard_flush(h);   // (behind the level's closing synchronisation)
-    h->level_done = true;
-    h->last_level_n = n;
-    stream_ready(h);
+    level_close(h, n);
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n = n; stats->k = h->k; stats->kkt_mode = h->kkt_mode;
-        for (int i = 0; i < 6; ++i) stats->n_status[i] = (int64_t)host_ctr.status[i];
-        stats->n_regions = h->n_regions; stats->n_children = h->n_children; stats->n_pruned_new = h->n_pruned_new;
-        stats->lp_pivots = (int64_t)host_ctr.pivots;
-        stats->n_xtheta_lp = h->n_needx;
-        stats->n_xtheta_fallback = (int64_t)host_ctr.xtheta_fallbacks;
-        for (int i = 0; i < 4; ++i) stats->wave_cycles[i] = (int64_t)host_ctr.cycles[i];
-        stats->n_x_cached = (int64_t)host_ctr.x_cached;
-        stats->n_region_rows = h->n_erows;
-        stats->n_opt = h->n_opt;
-        stats->n_theta_items = m.use_kkt ? cnt_host[0] : n;
+        level_stats_small(h, host_ctr, cnt_host, m.use_kkt != 0, m.quick_test != 0, stats);
         stats->n_region_retry = h->n_rretry;
-        if (h->n_opt > 0 && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)
-            stats->ms_region2 = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);
-        stats->n_xq_items = m.quick_test ? cnt_host[7] : 0; stats->xq_pivots = (int64_t)host_ctr.xq_pivots;
-        stats->n_x_items = (m.quick_test ? cnt_host[8] : cnt_host[7]) + (h->storing ? (long long)cnt_host[5] + cnt_host[6] : 0);
-        stats->xq_record_ints = dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) - 1; stats->xq_record_rows = h->Pf.n_d0r; stats->xq_record_cols = h->Pf.n_d0c + 1;
-        const long long rec_bytes = (long long)(h->Pf.n_d0c + 1) * h->Pf.n_d0r * 8 + (long long)dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) * 4;   // (what k_x2 reads of a record; the stored record also carries the children's look-up bytes)
-        stats->dict_read_bytes = (h->have_prev_dict && h->have_parent_slot) ? rec_bytes : 0;
-        stats->dict_write_bytes = h->storing ? rec_bytes : 0;
         stats->ms_total = ms_total;   // the batch's launches, first to last (shared by all members)
     }
     return MPC_OK;
@@ -2034,13 +1980,11 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             HIP_TRY(h, h->pruned_b.ensure((size_t)h->n_pruned * h->mw * sizeof(uint64_t), st));
             HIP_TRY(h, h->pruned_head.ensure((size_t)PB_WORDS * sizeof(int32_t), st));
             HIP_TRY(h, hipMemsetAsync(h->pruned_head.p, 0, (size_t)PB_WORDS * sizeof(int32_t), st));
-            const dim3 gb((unsigned)((h->n_pruned + 255) / 256)), bb(256);
+            const dim3 gb((unsigned)((h->n_pruned + 255) / 256));
             const int ne_b = h->n_eq;
-            if (h->mw == 2) hipLaunchKernelGGL(k_pruned_bucket_count<2>, gb, bb, 0, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>());
-            else hipLaunchKernelGGL(k_pruned_bucket_count<4>, gb, bb, 0, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>());
+            launch_pruned_bucket_count(h->mw, gb, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>());
             hipLaunchKernelGGL(k_pruned_bucket_scan, dim3(1), dim3(256), 0, st, h->pruned_head.as<int32_t>());
-            if (h->mw == 2) hipLaunchKernelGGL(k_pruned_bucket_scatter<2>, gb, bb, 0, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>(), h->pruned_b.as<unsigned long long>());
-            else hipLaunchKernelGGL(k_pruned_bucket_scatter<4>, gb, bb, 0, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>(), h->pruned_b.as<unsigned long long>());
+            launch_pruned_bucket_scatter(h->mw, gb, st, h->pruned.as<unsigned long long>(), (long long)h->n_pruned, ne_b, h->pruned_head.as<int32_t>(), h->pruned_b.as<unsigned long long>());
             HIP_TRY(h, hipGetLastError());
             pruned_bucketed = true;
         }
@@ -2051,8 +1995,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         const int nb1024 = (int)((n + 1023) / 1024);
         // deferred: the counts go to the pinned words [12..15] and nobody waits here (the caller reads them after a later synchronisation)
         auto partition = [&](std::initializer_list<std::pair<int, int>> classes, int32_t counts[PART_CLASSES], bool deferred = false, int32_t *tot_dev_mem = nullptr) -> int {
-            unsigned long long spec = ~0ull;
-            for (const auto &sc : classes) spec = (spec & ~(15ull << (4 * sc.first))) | ((unsigned long long)sc.second << (4 * sc.first));
+            const unsigned long long spec = part_spec(classes);
             HIP_TRY(h, h->part_counts.ensure((size_t)PART_CLASSES * nb1024 * sizeof(int32_t), st));
             HIP_TRY(h, h->part_lists.ensure((size_t)PART_CLASSES * nn * sizeof(int32_t), st));
             int32_t *tot = tot_dev_mem ? tot_dev_mem : (deferred ? total + 12 : total);   // tot_dev_mem: the lengths stay in device memory (the caller publishes them)
@@ -2098,9 +2041,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         const double *kkl = nullptr;
         // region stage on the register engine: one slot per candidate of h->opt_ptr.  Buffers are prepared on the main stream; the
         // kernel goes to `rst` (the main stream, or stream3 when the stage runs under the level's (x,theta) stage)
-        h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
-        h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
-        h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
+        level_record_shape(h, k);
         int32_t *region_out_hi = nullptr;   // head_i of the level's slots as the device sees it (device buffer or mapped host block)
         auto region2_launch = [&](int32_t n_opt, int32_t extra, hipStream_t rst, bool one_wave) -> int {
             const int rows_t_ = h->n_c - h->n_eq + h->n_tc;
@@ -2120,7 +2061,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
             // an overlapped launch may take only a share of the wave slots (r2_cap_pct): its 256-register wavefronts otherwise fill the
             // register file of every SIMD they sit on and the (x,theta) kernel beside them gets no slot there until they leave
             const long long grid_cap = (rst != st && one_wave) ? std::max<long long>(h->n_cu, (long long)h->grid_r2 * h->r2_cap_pct / 100) : h->grid_r2;
-            const dim3 g((unsigned)std::min<long long>((long long)n_opt * W, grid_cap)), b(64);
+            const dim3 g((unsigned)std::min<long long>((long long)n_opt * W, grid_cap));
             const DevProblem *pr = h->pr2_dev.as<DevProblem>();
             // where the records go: device buffers (fetched / gathered later), or -- streaming -- page-locked host blocks the
             // kernel writes directly, in chunks the host consumes while the kernel is still running
@@ -2153,10 +2094,6 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 rs.count = h->chunk_count.as<unsigned int>(); rs.flags = static_cast<int32_t *>(d_fl); rs.shift = so.shift; rs.n_slots = n_opt;
                 so.active = true;
             }
-#define MPC_LAUNCH_R2(NT_, SL_) hipLaunchKernelGGL((k_region2<NT_, SL_>), g, b, h->lds_r2, rst, pr, h->frontier.as<int32_t>(), k, h->opt_ptr, n_opt, \
-                                                   h->status.as<uint8_t>(), out_hd, out_hi, h->fd, h->fi, out_er, ctr, kkc, kkl, \
-                                                   W, h->kept_g.as<uint8_t>(), ldk, h->done_g.as<unsigned int>(), \
-                                                   h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)NT_ * NT_ + NT_, rs)
             region_out_hi = out_hi;
             if (extra > 0) { rprep.head_i = out_hi; rprep.fi = h->fi; rprep.first = n_opt; rprep.extra = extra; rprep_any = true; }
             if (rst != st) {
@@ -2174,15 +2111,10 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 { int rcs = prep_flush_on(rprep, rprep_any, st); if (rcs) return rcs; }
             }
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[4], rst));
-            switch (h->fast_r) {
-                case 0: MPC_LAUNCH_R2(4, 1); break;
-                case 1: MPC_LAUNCH_R2(4, 2); break;
-                case 2: MPC_LAUNCH_R2(8, 1); break;
-                case 3: MPC_LAUNCH_R2(8, 2); break;
-                case 4: MPC_LAUNCH_R2(10, 1); break;
-                default: MPC_LAUNCH_R2(10, 2); break;
-            }
-#undef MPC_LAUNCH_R2
+            const int nt_r = region2_nt(h->fast_r);
+            launch_region2(h->fast_r, g, h->lds_r2, rst, pr, h->frontier.as<int32_t>(), k, h->opt_ptr, n_opt, h->status.as<uint8_t>(), out_hd, out_hi, h->fd, h->fi, out_er,
+                           ctr, kkc, kkl, W, h->kept_g.as<uint8_t>(), ldk, h->done_g.as<unsigned int>(),
+                           h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r, rs);
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[5], rst));
             if (rst != st) { h->r3_dirty = true; h->region_side_stream = true; HIP_TRY(h, hipEventRecord(h->ev_rjoin, rst)); }
             kernel_timed[2] = true;
@@ -2199,24 +2131,18 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         auto queue_tail = [&]() -> int {
             const int keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
             if (flags & MPC_LEVEL_GRAPH) { /* no pruning in the graph traversal */ }
-            else if (h->mw == 2) hipLaunchKernelGGL(k_pruned_append<2>, dim3(blocks256), dim3(256), 0, st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                               h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
-            else hipLaunchKernelGGL(k_pruned_append<4>, dim3(blocks256), dim3(256), 0, st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                    h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
+            else launch_pruned_append(h->mw, dim3(blocks256), st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
+                                      h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
             if (gen_children) {
                 HIP_TRY(h, h->childmask.ensure(nn * h->mw * sizeof(uint64_t), st));
                 HIP_TRY(h, h->count.ensure(nn * sizeof(int32_t), st));
                 HIP_TRY(h, h->offset.ensure(nn * sizeof(int32_t), st));
-                if (pruned_bucketed) {
-                    if (h->mw == 2) hipLaunchKernelGGL(k_children_count_b<2>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                                       h->pruned_b.as<unsigned long long>(), h->pruned_head.as<int32_t>(), h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
-                    else hipLaunchKernelGGL(k_children_count_b<4>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
+                if (pruned_bucketed)
+                    launch_children_count_b(h->mw, dim3((unsigned)n), st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
                                             h->pruned_b.as<unsigned long long>(), h->pruned_head.as<int32_t>(), h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
-                } else
-                if (h->mw == 2) hipLaunchKernelGGL(k_children_count<2>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                                   h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
-                else hipLaunchKernelGGL(k_children_count<4>, dim3((unsigned)n), dim3(64), 0, st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                                        h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
+                else
+                    launch_children_count(h->mw, dim3((unsigned)n), st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
+                                          h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
                 // lean: children and their parent slots are sized by the bound n (n_c - k) and written without waiting for the count
                 const double child_bound_bytes = (double)nn * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
                 children_lean = child_bound_bytes <= 1.5e9;
@@ -2269,7 +2195,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 kkc = h->kkt_code.as<uint8_t>(); kkl = h->kkt_L.as<double>();
                 // (round 6) KKT_SPREAD lanes per candidate while that still leaves the level short of the chip's thread slots (k_kkt_thread's comment)
                 const bool spread = h->kkt_spread > 0 && kd <= KKT_SPREAD_KMAX && n * KKT_SPREAD <= (long long)h->kkt_spread_threads;
-                const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256)), b(256);
+                const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256));
                 ThetaArgs ta = h->targs;
                 // (round 5) the kernel lists its own output: the theta stage's work list and the candidates its box screen sends to
                 // the (x,theta) question -- two compactions of five launches each saved on the level's critical path
@@ -2281,15 +2207,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                     ta.kx_list = h->xq_list.as<int32_t>(); ta.kx_n = dcnt + 10;
                 }
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[6], st));
-#define MPC_LAUNCH_KKT_(K_, SP_) if (h->fast_t >= 4) hipLaunchKernelGGL((k_kkt_thread<K_, 10, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, ta, ctr); \
-                                    else if (h->fast_t >= 2) hipLaunchKernelGGL((k_kkt_thread<K_, 8, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, ta, ctr); \
-                                    else hipLaunchKernelGGL((k_kkt_thread<K_, 4, SP_>), g, b, 0, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, ta, ctr)
-#define MPC_LAUNCH_KKT(K_) case K_: MPC_LAUNCH_KKT_(K_, 1); break
-#define MPC_LAUNCH_KKT_S(K_) case K_: if (spread) { MPC_LAUNCH_KKT_(K_, KKT_SPREAD); } else { MPC_LAUNCH_KKT_(K_, 1); } break
-                switch (kd) { MPC_LAUNCH_KKT_S(1); MPC_LAUNCH_KKT_S(2); MPC_LAUNCH_KKT_S(3); MPC_LAUNCH_KKT_S(4); MPC_LAUNCH_KKT_S(5); MPC_LAUNCH_KKT_S(6); MPC_LAUNCH_KKT(7); MPC_LAUNCH_KKT(8); MPC_LAUNCH_KKT(9); MPC_LAUNCH_KKT(10); }
-#undef MPC_LAUNCH_KKT_S
-#undef MPC_LAUNCH_KKT
-#undef MPC_LAUNCH_KKT_
+                launch_kkt_thread(kd, h->fast_t, spread, g, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, ta, ctr);
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[7], st));
                 kernel_timed[3] = true;
                 HIP_TRY(h, hipGetLastError());
@@ -2317,10 +2235,9 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 //  and the optimal candidates -- classes the pass never touches --, the region kernel starts on its stream, and the open
                 //  candidates are listed when the pass has ended.  Config 4's last level: 1.86 ms with the pass behind the theta stage,
                 //  1.72 beside it; config 3's: 3.45 / 3.25.)
-                const int nxc_e = h->fast_x >= 2 ? 32 : 16;
+                const int nxc_e = dict_nxc(h);
                 const long long sd_e = (long long)nxc_e * h->Pf.n_d0r, si_e = dict_ints(h->Pf.n_d0r, nxc_e, h->n_c);
-                const bool will_store = gen_children && (double)nn * (sd_e * 8.0 + si_e * 4.0) / 1e9 <= h->dict_budget_gb;
-                if (!will_store) {
+                if (!dict_will_store(h, nn, gen_children)) {
                     if (!kkt_listed) {      // (else k_kkt_thread has listed them in xq_list, length in dcnt[10])
                         { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 10); if (rcs) return rcs; }
                         HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
@@ -2360,44 +2277,19 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 if (ta.wave_max > 0) grid_th = std::min<long long>(grid_th, ta.wave_max);
                 if (!theta_lean && ta.wave_div > 0) grid_th = std::min<long long>(grid_th, std::max<long long>(256, n_theta / ta.wave_div));
                 if (!theta_lean) ta.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_theta / (grid_th * 8)));
-                const dim3 g((unsigned)std::min<long long>(theta_lean ? n_theta : (n_theta + ta.chunk - 1) / ta.chunk, grid_th)), b(64);
+                const dim3 g((unsigned)std::min<long long>(theta_lean ? n_theta : (n_theta + ta.chunk - 1) / ta.chunk, grid_th));
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[0], st));
-                switch (h->fast_t) {
-                    case 0: hipLaunchKernelGGL((k_theta2<4, 1>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                    case 1: hipLaunchKernelGGL((k_theta2<4, 2>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                    case 2: hipLaunchKernelGGL((k_theta2<8, 1>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                    case 3: hipLaunchKernelGGL((k_theta2<8, 2>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                    case 4: hipLaunchKernelGGL((k_theta2<10, 1>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                    default: hipLaunchKernelGGL((k_theta2<10, 2>), g, b, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list); break;
-                }
+                launch_theta2(h->fast_t, g, h->lds_f, st, pf, fr, n_theta, k, stp, ctr, kkc, kkl, ta, theta_list);
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[1], st));
                 kernel_timed[0] = true;
                 n_theta_items = n_theta;
                 HIP_TRY(h, hipGetLastError());
             }
             // ---- (x,theta) stage with the dictionary cache -------------------------------------------------------------
-            const int nxc = h->fast_x >= 2 ? 32 : 16;
-            h->dict_stride_d = (long long)nxc * h->Pf.n_d0r;   // column-major tableau
-            h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
-            DictCache dc{};
-            dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
-            dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
-            if (h->have_prev_dict && h->have_parent_slot) {
-                dc.parent_slot = h->parent_slot.as<int32_t>();
-                dc.prev_d = h->dict_d[1 - h->dict_cur].as<double>();
-                dc.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
-            }
-            h->storing = false;
-            const double need_gb = (double)nn * (h->dict_stride_d * 8.0 + h->dict_stride_i * 4.0) / 1e9;
-            if (gen_children && need_gb <= h->dict_budget_gb) {
-                HIP_TRY(h, h->dict_d[h->dict_cur].ensure(nn * h->dict_stride_d * sizeof(double), st));
-                HIP_TRY(h, h->dict_i[h->dict_cur].ensure(nn * h->dict_stride_i * sizeof(int32_t), st));
-                HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
-                { int rcs = prep_zero(h->dict_stored[h->dict_cur].p, nn); if (rcs) return rcs; }
-                dc.cur_d = h->dict_d[h->dict_cur].as<double>(); dc.cur_i = h->dict_i[h->dict_cur].as<int32_t>();
-                dc.stored = h->dict_stored[h->dict_cur].as<uint8_t>();
-                h->storing = true;
-            }
+            const int nxc = dict_nxc(h);
+            DictCache dc;
+            { int rcs = dict_cache_begin(h, nn, gen_children, st, dc); if (rcs) return rcs; }
+            if (h->storing) { int rcs = prep_zero(h->dict_stored[h->dict_cur].p, nn); if (rcs) return rcs; }
             // The (x,theta) stage of a level that keeps dictionaries, in its one-step-plan form, needs no count from the host: its lists
             // come from the partition below, their lengths stay in device memory (dcnt[28..31]), its launches are sized by the bound n.
             // Round 5 (`x_first`): it is queued BEHIND THE PARTITION AT ONCE, and only then does the host wait for the counts that size
@@ -2443,8 +2335,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1go, st)); HIP_TRY(h, hipStreamWaitEvent(sx1, h->ev_x1go, 0)); }
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[12], st));
                 LevelCounters *ctr_x1 = defer ? (LevelCounters *)nullptr : ctr;   // (its pivot count would land in the next level's counters)
-                if (h->fast_x & 1) hipLaunchKernelGGL((k_x1<2>), dim3(g1), dim3(64), 0, sx1, pfx, pl.x1_list, pl.x1_n, ctr_x1, dc, nxc, pl.plan_slot, pl.plan_step);
-                else hipLaunchKernelGGL((k_x1<1>), dim3(g1), dim3(64), 0, sx1, pfx, pl.x1_list, pl.x1_n, ctr_x1, dc, nxc, pl.plan_slot, pl.plan_step);
+                launch_x1(h->fast_x, dim3(g1), sx1, pfx, pl.x1_list, pl.x1_n, ctr_x1, dc, nxc, pl.plan_slot, pl.plan_step);
                 HIP_TRY(h, hipGetLastError());
                 if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1done, sx1)); h->x1_pending = true; }
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[13], st));
@@ -2454,13 +2345,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 dr.pre2 = pl.rest[1]; dr.n_pre2 = 0; dr.n_pre2_dev = pl.rest_n[1];
                 dr.n_list_dev = pl.rest_n[2]; dr.chunk = 0;
                 const long long grid_r = (long long)h->n_cu * std::min<long long>(4, h->x2_wpc);
-                const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(n_bound, grid_r))), bb(64);
-                switch (h->fast_x) {
-                    case 0: hipLaunchKernelGGL((k_x2<16, 1>), gg, bb, 0, st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr); break;
-                    case 1: hipLaunchKernelGGL((k_x2<16, 2>), gg, bb, 0, st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr); break;
-                    case 2: hipLaunchKernelGGL((k_x2<32, 1>), gg, bb, 0, st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr); break;
-                    default: hipLaunchKernelGGL((k_x2<32, 2>), gg, bb, 0, st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr); break;
-                }
+                launch_x2(h->fast_x, dim3((unsigned)std::max<long long>(1, std::min<long long>(n_bound, grid_r))), st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr);
                 HIP_TRY(h, hipGetLastError());
                 x1_ran = true;
                 return MPC_OK;
@@ -2555,13 +2440,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 const long long grid_x = (long long)h->n_cu * wpc;
                 d.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_all / (grid_x * 8)));
                 if (xq_lean) { d.n_list_dev = dcnt + 8; d.chunk = 0; }   // length of `ls` and chunk rule on the device
-                const dim3 gg((unsigned)std::min<long long>(xq_lean ? n_all : (n_all + d.chunk - 1) / d.chunk, grid_x)), bb(64);
-                switch (h->fast_x) {
-                    case 0: hipLaunchKernelGGL((k_x2<16, 1>), gg, bb, 0, st, pf, fr, k, ls, n_items, stp, ctr, d); break;
-                    case 1: hipLaunchKernelGGL((k_x2<16, 2>), gg, bb, 0, st, pf, fr, k, ls, n_items, stp, ctr, d); break;
-                    case 2: hipLaunchKernelGGL((k_x2<32, 1>), gg, bb, 0, st, pf, fr, k, ls, n_items, stp, ctr, d); break;
-                    default: hipLaunchKernelGGL((k_x2<32, 2>), gg, bb, 0, st, pf, fr, k, ls, n_items, stp, ctr, d); break;
-                }
+                launch_x2(h->fast_x, dim3((unsigned)std::min<long long>(xq_lean ? n_all : (n_all + d.chunk - 1) / d.chunk, grid_x)), st, pf, fr, k, ls, n_items, stp, ctr, d);
                 HIP_TRY(h, hipGetLastError());
                 return MPC_OK;
             };
@@ -2626,7 +2505,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                 }
                 dq.chunk = (int)std::max<long long>(1, std::min<long long>(16, xq_n / (grid_q * 4)));
                 if (xqt_lean) { dq.n_list_dev = dcnt + 9; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
-                const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(xqt_lean ? (long long)xq_n : ((long long)xq_n + dq.chunk - 1) / dq.chunk, grid_q))), bb(64);
+                const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(xqt_lean ? (long long)xq_n : ((long long)xq_n + dq.chunk - 1) / dq.chunk, grid_q)));
                 // Grouped by parent when a parent has many open children (config 3: 12.6 per parent, -0.5 ms; config 4: 7.1 per
                 // parent, where the per-candidate reads of k_xq are cheaper than one 16 KB copy per parent, +0.45 ms): threshold 10.
                 if (use_grouped && xq_n > 0) {
@@ -2646,8 +2525,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
                     else hipLaunchKernelGGL((k_xq_grouped<1>), gq, bq, lds_q, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc, h->xq_groups.as<int32_t>(), h->scratch.as<int32_t>());
                 } else if (xq_n == 0) { /* the first pass decided everything (host-known length) */ }
                 else if (!xqt_lean && !(h->fast_x & 1) && xq_n < h->xq_skip_below) { /* a short list (host-known length) is left to k_x2: k_xq's comment */ }
-                else if (h->fast_x & 1) hipLaunchKernelGGL((k_xq<2>), gg, bb, 0, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc);
-                else hipLaunchKernelGGL((k_xq<1>), gg, bb, 0, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc);
+                else launch_xq(h->fast_x, gg, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc);
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[9], st));
                 kernel_timed[4] = true;
                 HIP_TRY(h, hipGetLastError());
@@ -2831,36 +2709,21 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
         h->n_erows = host_ctr.e_rows;
         h->n_regions = (long long)host_ctr.status[ST_REGION];
     }
-    graveyard_flush(h);   // (behind the level's closing synchronisation)
-    h->level_done = true;
-    h->last_level_n = n;
-    stream_ready(h);
+    level_close(h, n);
     if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->n = n; stats->k = k; stats->kkt_mode = h->kkt_mode;
-        for (int i = 0; i < 6; ++i) stats->n_status[i] = (int64_t)host_ctr.status[i];
-        stats->n_regions = h->n_regions; stats->n_children = h->n_children; stats->n_pruned_new = h->n_pruned_new;
-        stats->lp_pivots = (int64_t)host_ctr.pivots;
+        level_stats_common(h, host_ctr, stats);
         stats->n_xtheta_lp = (h->fast && !h->force_v1) ? h->n_needx : (int64_t)host_ctr.xtheta_lps;
-        stats->n_xtheta_fallback = (int64_t)host_ctr.xtheta_fallbacks;
-        for (int i = 0; i < 4; ++i) stats->wave_cycles[i] = (int64_t)host_ctr.cycles[i];
         stats->n_region_retry = h->n_rretry;
-        stats->n_x_cached = (int64_t)host_ctr.x_cached;
         stats->ms_theta = kms[0]; stats->ms_x = kms[1]; stats->ms_region2 = kms[2];
         stats->region_side_stream = h->region_side_stream ? 1.0f : 0.0f;
         stats->n_x_items = n_x_items;
         stats->n_theta_items = n_theta_items;
         stats->ms_kkt = kms[3]; stats->ms_xq = kms[4];
-        stats->n_xq_items = n_xq_items; stats->xq_pivots = (int64_t)host_ctr.xq_pivots;
-        stats->xq_record_ints = dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) - 1; stats->xq_record_rows = h->Pf.n_d0r; stats->xq_record_cols = h->Pf.n_d0c + 1;
+        stats->n_xq_items = n_xq_items;
         stats->n_xq_thread = h->n_xq_thread; stats->ms_xq_thread = h->ms_xq_thread; stats->xq_thread_beside_theta = xq_early_ran ? 1.0f : 0.0f;
         stats->n_x1 = h->n_x1; stats->ms_x1 = h->ms_x1; stats->ms_x_plan = x1_ran ? h->ms_xq_thread : 0.0f;
-        stats->n_region_rows = h->n_erows;
-        stats->n_opt = h->n_opt;
-        // bytes of one dictionary record that are actually moved: the used columns (value + D0 columns) and the integer part
-        const long long rec_bytes = (long long)(h->Pf.n_d0c + 1) * h->Pf.n_d0r * 8 + (long long)dict_ints_head(h->Pf.n_d0r, h->fast_x >= 2 ? 32 : 16) * 4;   // (what k_x2 reads of a record; the stored record also carries the children's look-up bytes)
-        stats->dict_read_bytes = (h->fast && h->have_prev_dict && h->have_parent_slot) ? rec_bytes : 0;
-        stats->dict_write_bytes = (h->fast && h->storing) ? rec_bytes : 0;
+        stats->dict_read_bytes = (h->fast && h->have_prev_dict && h->have_parent_slot) ? dict_record_bytes(h) : 0;
+        stats->dict_write_bytes = (h->fast && h->storing) ? dict_record_bytes(h) : 0;
         stats->ms_verdict = ms[0]; stats->ms_region = ms[1]; stats->ms_children = ms[2]; stats->ms_total = ms[0] + ms[1] + ms[2];
     }
     return MPC_OK;
