@@ -721,6 +721,39 @@ int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_
                     const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
                     uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms);
 
+/* ---- overlap removal by lowest objective (Solution.remove_overlaps) ------------------------------------------------- */
+/* Regions and pieces are polytopes of unit rows [o | n] in CSR form, as for the merge calls above.  Both calls are stateless; an error
+ * text is read with mpc_last_error(NULL).  Limits (MPC_ERR_INVALID with a message, before any launch): 1 <= n_t <= 16, 1..256 rows per
+ * region and per piece, finite rows with unit normals, indices in range, finite xs / start, tol finite and >= 0.
+ *
+ * mpc_overlap_pairs: for every pair (i, j) = (pair_a[k], pair_b[k]) over the rows of R_i and R_j together (k_overlap_pairs)
+ *   radius[k]  the largest t with n.theta + t <= o for every row: the Chebyshev radius of R_i n R_j (negative: empty); the run starts
+ *              at xs[i] (any finite point; a point of R_i saves pivots)
+ *   d_min[k], d_max[k]  where radius[k] > tol and has_cut[k]: the range over R_i n R_j of d(theta) = o - n.theta for the cut row
+ *              [o | n] = cut_rows[k] (the unit row of {J_j <= J_i}: d = (J_i - J_j) / |g|).  NaN where not computed.
+ *   flag[k]    1: a run was unbounded or stopped at the pivot cap (radius, d_min, d_max are then bounds, not values)
+ *   cut_rows may be NULL when no has_cut[k] is set.  stats (may be NULL): [0] pairs, [1] LPs, [2] pivots, [3] capped runs.
+ * mpc_overlap_split: one step of the region difference for every item k = (piece item_piece[k], cutter region item_cutter[k], and the
+ *   cut row cut_rows[k] where has_cut[k]); the cutter C is the region's rows followed by the cut row (k_overlap_split)
+ *   flag[k]    bit 0 (MPC_OVERLAP_MEETS): radius(P n C) > tol.  Clear: the piece stays whole and nothing else is set.
+ *              bit 1 (MPC_OVERLAP_CUT_ROW): the cut row cuts.  bit 2 (MPC_OVERLAP_WIDE): some run was unbounded or capped.
+ *   mask[k][MPC_MERGE_WORDS]  bit r: row r of the cutter's region cuts, i.e. P n {earlier cutting rows} n {n_r.theta >= o_r} has a radius
+ *              above tol, taken in row order; every such set is a child piece (rows: P's, the earlier cutting rows, the reversed row)
+ *              and P n C is dropped.  An unbounded or capped run counts as "cuts".
+ *   start      [n_items][n_t] where the first run of an item starts, or NULL: the origin.
+ *   stats (may be NULL): [0] items, [1] items whose piece meets the cutter, [2] LPs, [3] pivots, [4] unbounded or capped runs.
+ * Deterministic: atomics only in the counters. */
+#define MPC_OVERLAP_MEETS 1
+#define MPC_OVERLAP_CUT_ROW 2
+#define MPC_OVERLAP_WIDE 4
+int mpc_overlap_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
+                      int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, const int32_t *has_cut, const double *cut_rows,
+                      double tol, double *radius, double *d_min, double *d_max, int32_t *flag, int64_t *stats, float *ms);
+int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int64_t n_pieces,
+                      const int64_t *piece_off, const double *piece_rows, int64_t n_items, const int32_t *item_piece,
+                      const int32_t *item_cutter, const int32_t *has_cut, const double *cut_rows, const double *start, double tol,
+                      int32_t *flag, uint64_t *mask, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

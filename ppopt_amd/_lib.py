@@ -269,6 +269,10 @@ def load():
                                              ctypes.POINTER(ctypes.c_float)]),
         'mpc_merge_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
                                            ctypes.c_double, _u64p, _u64p, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_overlap_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_int64, _ip, _ip, _ip, _dp,
+                                             ctypes.c_double, _dp, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_overlap_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
+                                             _ip, _ip, _ip, _dp, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -288,7 +292,8 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_regions_compact', 'mpc_frontier_shard', 'mpc_level_slots', 'mpc_level_regions_slots', 'mpc_level_regions_slots_async', 'mpc_sync', 'mpc_fetch_wait', 'mpc_solve_many_start', 'mpc_solve_many_level', 'mpc_solve_many_wait', 'mpc_host_alloc', 'mpc_host_free', 'mpc_locator_create', 'mpc_locator_query', 'mpc_locator_last_unresolved', 'mpc_locator_destroy', 'mpc_locator_set_adjacency', 'mpc_level_children', 'mpc_level_children_device', 'mpc_level_pruned_new',
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
-                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments']
+                    'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
+                    'mpc_overlap_pairs', 'mpc_overlap_split']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1273,6 +1278,71 @@ def merge_pairs(row_off, ef_rows, xs, box, pair_a, pair_b, tol: float, device: i
         raise MpcError(f'mpc_merge_pairs failed ({rc}): {L.mpc_last_global_error().decode()}')
     names = ('pairs', 'box_pairs', 'rows', 'box_rows', 'lps', 'pivots', 'capped')
     return env_a, env_b, verdict, t_max, dict({k: int(v) for k, v in zip(names, st)}, ms=float(ms.value))
+
+
+OVERLAP_MEETS, OVERLAP_CUT_ROW, OVERLAP_WIDE = 1, 2, 4   # flag bits of mpc_overlap_split (include/mpcombi.h)
+
+
+def _cut_rows(who, n, n_t, has_cut, cut_rows):
+    hc = numpy.ascontiguousarray(has_cut, dtype=numpy.int32).reshape(-1)
+    if len(hc) != n:
+        raise MpcError(f'{who}: has_cut must have one entry per item')
+    cut = None
+    if cut_rows is not None:
+        cut = _f64(numpy.asarray(cut_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
+        if len(cut) != n:
+            raise MpcError(f'{who}: cut_rows must be [items, n_t + 1]')
+    return hc, cut
+
+
+def overlap_pairs(row_off, ef_rows, xs, pair_a, pair_b, has_cut, cut_rows, tol: float, device: int = 0):
+    """The pair stage of the overlap removal (include/mpcombi.h, mpc_overlap_pairs): (radius [n_pairs], d_min, d_max, flag int32, stats)."""
+    off, ef = _merge_rows('overlap_pairs', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    x = _f64(numpy.asarray(xs, dtype=numpy.float64)).reshape(R, n_t)
+    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
+    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
+    if pa.shape != pb.shape:
+        raise MpcError('overlap_pairs: pair_a and pair_b must have the same length')
+    n = len(pa)
+    hc, cut = _cut_rows('overlap_pairs', n, n_t, has_cut, cut_rows)
+    L = load()
+    radius, d_min, d_max, flag = numpy.zeros(n), numpy.zeros(n), numpy.zeros(n), numpy.zeros(n, dtype=numpy.int32)
+    st, ms = numpy.zeros(4, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_overlap_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), x.ctypes.data_as(_dp), n,
+                             pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), hc.ctypes.data_as(_ip),
+                             None if cut is None else cut.ctypes.data_as(_dp), float(tol), radius.ctypes.data_as(_dp),
+                             d_min.ctypes.data_as(_dp), d_max.ctypes.data_as(_dp), flag.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_overlap_pairs failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return radius, d_min, d_max, flag, dict({k: int(v) for k, v in zip(('pairs', 'lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+
+
+def overlap_split(row_off, ef_rows, piece_off, piece_rows, item_piece, item_cutter, has_cut, cut_rows, start, tol: float, device: int = 0):
+    """One round of the region difference (include/mpcombi.h, mpc_overlap_split): (flag [n_items] int32, mask [n_items, MERGE_WORDS]
+    uint64, stats)."""
+    off, ef = _merge_rows('overlap_split', row_off, ef_rows)
+    poff, pef = _merge_rows('overlap_split', piece_off, piece_rows)
+    n_t, R, P = ef.shape[1] - 1, len(off) - 1, len(poff) - 1
+    if pef.shape[1] != n_t + 1:
+        raise MpcError('overlap_split: regions and pieces must have the same n_t')
+    ip = numpy.ascontiguousarray(item_piece, dtype=numpy.int32).reshape(-1)
+    ic = numpy.ascontiguousarray(item_cutter, dtype=numpy.int32).reshape(-1)
+    if ip.shape != ic.shape:
+        raise MpcError('overlap_split: item_piece and item_cutter must have the same length')
+    n = len(ip)
+    hc, cut = _cut_rows('overlap_split', n, n_t, has_cut, cut_rows)
+    s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
+    L = load()
+    flag, mask = numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
+    st, ms = numpy.zeros(5, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_overlap_split(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P, poff.ctypes.data_as(_lp),
+                             pef.ctypes.data_as(_dp), n, ip.ctypes.data_as(_ip), ic.ctypes.data_as(_ip), hc.ctypes.data_as(_ip),
+                             None if cut is None else cut.ctypes.data_as(_dp), None if s0 is None else s0.ctypes.data_as(_dp), float(tol),
+                             flag.ctypes.data_as(_ip), mask.ctypes.data_as(_u64p), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_overlap_split failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return flag, mask, dict({k: int(v) for k, v in zip(('items', 'meets', 'lps', 'pivots', 'wide'), st)}, ms=float(ms.value))
 
 
 class Locator:

@@ -1,7 +1,7 @@
 // geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
 // location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration, region volumes and region
-// merging.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
-// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, simplex.hpp); the pools and the scaffold
+// merging and the overlap removal.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "vertices.hpp"
 #include "volume.hpp"
 #include "merge.hpp"
+#include "overlap.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1279,6 +1280,134 @@ extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, c
     unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
     s.download(cnt, d_cnt, sizeof cnt);
     if (stats) for (int i = 0; i < 7; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+// ---- overlap removal by lowest objective (overlap.hpp) --------------------------------------------------------------
+// has_cut [n] and the cut rows [n][n_t + 1] it selects: finite with unit normals
+static int overlap_check_cuts(const char *who, int32_t n_t, int64_t n, const int32_t *has_cut, const double *cut_rows) {
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (!has_cut) return bad("missing has_cut");
+    for (int64_t k = 0; k < n; ++k) {
+        if (!has_cut[k]) continue;
+        if (!cut_rows) return bad("missing cut_rows");
+        const double *row = cut_rows + k * (n_t + 1);
+        double nn = 0.0;
+        bool finite = std::isfinite(row[0]);
+        for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
+        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("cut rows must be finite with unit normals");
+    }
+    return MPC_OK;
+}
+
+extern "C" int mpc_overlap_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
+                                 int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, const int32_t *has_cut, const double *cut_rows,
+                                 double tol, double *radius, double *d_min, double *d_max, int32_t *flag, int64_t *stats, float *ms) {
+    const char *who = "mpc_overlap_pairs";
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: tol must be finite and >= 0");
+    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (n_pairs == 0) return MPC_OK;
+    if (!xs || !pair_a || !pair_b || !radius || !d_min || !d_max || !flag) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: missing array");
+    int pair_rows = 2;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t p = pair_a[k], q = pair_b[k];
+        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: a pair names a region out of range, or the same region twice");
+        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q]));
+    }
+    if (int rc = overlap_check_cuts(who, n_t, n_pairs, has_cut, cut_rows)) return rc;
+    for (int64_t i = 0; i < n_regions * n_t; ++i)
+        if (!std::isfinite(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: xs must be finite");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(pair_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes
+    const size_t np = (size_t)n_pairs;
+    const double zero_row = 0.0;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_xs = s.upload(xs, (size_t)n_regions * n_t * 8), &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
+    DevBuf &d_hc = s.upload(has_cut, np * 4), &d_cut = cut_rows ? s.upload(cut_rows, np * (n_t + 1) * 8) : s.upload(&zero_row, 8);
+    DevBuf &d_r = s.buf(np * 8), &d_lo = s.buf(np * 8), &d_hi = s.buf(np * 8), &d_f = s.buf(np * 4), &d_cnt = s.buf(4 * 8);
+    s.fill(d_cnt, 0, 4 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_overlap_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        OverlapPairArgs a{};
+        a.nt = n_t; a.m_max = pair_rows; a.n_pairs = n_pairs;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>();
+        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>(); a.tol = tol;
+        a.radius = d_r.as<double>(); a.d_min = d_lo.as<double>(); a.d_max = d_hi.as<double>(); a.flag = d_f.as<int32_t>();
+        a.counters = d_cnt.as<unsigned long long>();
+        hipLaunchKernelGGL(k_overlap_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
+    });
+    s.download(radius, d_r, np * 8);
+    s.download(d_min, d_lo, np * 8);
+    s.download(d_max, d_hi, np * 8);
+    s.download(flag, d_f, np * 4);
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int64_t n_pieces,
+                                 const int64_t *piece_off, const double *piece_rows, int64_t n_items, const int32_t *item_piece,
+                                 const int32_t *item_cutter, const int32_t *has_cut, const double *cut_rows, const double *start, double tol,
+                                 int32_t *flag, uint64_t *mask, int64_t *stats, float *ms) {
+    const char *who = "mpc_overlap_split";
+    if (stats) for (int i = 0; i < 5; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_reg = 1, m_piece = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
+    if (int rc = merge_check("mpc_overlap_split (pieces)", n_t, n_pieces, piece_off, piece_rows, &m_piece)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: tol must be finite and >= 0");
+    if (n_items < 0 || n_items > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: n_items must lie in 0..2^31 - 1");
+    if (n_items == 0) return MPC_OK;
+    if (!item_piece || !item_cutter || !flag || !mask) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: missing array");
+    int item_rows = 4;
+    for (int64_t k = 0; k < n_items; ++k) {
+        const int64_t p = item_piece[k], c = item_cutter[k];
+        if (p < 0 || p >= n_pieces || c < 0 || c >= n_regions)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: an item names a piece or a cutter out of range");
+        item_rows = std::max<int>(item_rows, (int)(piece_off[p + 1] - piece_off[p] + row_off[c + 1] - row_off[c] + 2));
+    }
+    if (int rc = overlap_check_cuts(who, n_t, n_items, has_cut, cut_rows)) return rc;
+    if (start)
+        for (int64_t i = 0; i < n_items * n_t; ++i)
+            if (!std::isfinite(start[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: start must be finite");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(item_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_mask adds 32)
+    const size_t ni = (size_t)n_items, words = ni * OV_WORDS * 8;
+    const double zero_row = 0.0;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    const RegionsOnDevice pc = upload_regions(s, n_pieces, piece_off, piece_rows, n_t + 1);
+    DevBuf &d_ip = s.upload(item_piece, ni * 4), &d_ic = s.upload(item_cutter, ni * 4), &d_hc = s.upload(has_cut, ni * 4);
+    DevBuf &d_cut = cut_rows ? s.upload(cut_rows, ni * (n_t + 1) * 8) : s.upload(&zero_row, 8);
+    DevBuf *d_start = start ? &s.upload(start, ni * n_t * 8) : nullptr;
+    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = s.buf(5 * 8);
+    s.fill(d_cnt, 0, 5 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_overlap_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        OverlapSplitArgs a{};
+        a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
+        a.item_piece = d_ip.as<int32_t>(); a.item_cutter = d_ic.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>();
+        a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+        a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
+        hipLaunchKernelGGL(k_overlap_split, dim3((unsigned)n_items), dim3(64), lds, nullptr, a);
+    });
+    s.download(flag, d_f, ni * 4);
+    s.download(mask, d_m, words);
+    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 5; ++i) stats[i] = (int64_t)cnt[i];
     s.elapsed(ms);
     return s.finish();
 }

@@ -89,7 +89,8 @@ def polytope_volumes(polytopes: Union[Polytope, Sequence[Polytope]], tol: float 
 
 def coverage_volume(solution, device: int = 0) -> CoverageVolume:
     """Solution.coverage_volume: see there."""
-    if solution.is_mixed_integer_sol() or any(r.y_fixation is not None for r in solution.critical_regions):
+    reduced = getattr(solution, 'overlap_info', None) is not None and not solution.is_overlapping     # pieces share boundaries only
+    if not reduced and (solution.is_mixed_integer_sol() or any(r.y_fixation is not None for r in solution.critical_regions)):
         raise ValueError('coverage_volume: mixed-integer solutions are not summed (their regions may overlap)')
     if solution.is_overlapping:
         raise ValueError('coverage_volume: the solution is overlapping (every mpLP solution is): a point may lie in several regions, and '

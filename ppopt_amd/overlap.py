@@ -1,0 +1,308 @@
+"""Partitioning an overlapping solution by lowest objective (Solution.remove_overlaps).
+
+Every mpLP solution, and every mixed-integer one with more than one parameter, is overlapping: a parameter point may lie in several
+regions R_i = {E_i theta <= f_i} and the answer there is the one with the lowest value J_i(theta).  When all value functions share
+one quadratic part, J_i - J_j is affine and "i is cheaper than j" is a half-space, so the comparison procedure of the mpMILP
+literature needs LPs only.  Region i owns theta in R_i iff for every other j with theta in R_j: J_i < J_j, or J_i = J_j and i > j (the
+tie rule of Solution.get_region).  The procedure is deterministic:
+
+  1. unit rows [o | n] of every region (region_merge.unit_rows); feasible points and bounding boxes by _lib.merge_regions;
+  2. D = J_i - J_j = g.theta + h.  The pair is value-equal when |g| <= value_tol (1 + max |qv|) and |h| <= value_tol (1 + max |rv|);
+     with |g| that small and |h| not, the cheaper region is cheaper everywhere (d_min = d_max = +-inf by the sign of h, no LP);
+     otherwise the cut row of the pair is the unit row of {J_j <= J_i}, [h / |g| | -g / |g|], and d(theta) = (J_i - J_j) / |g| the depth
+     behind it;
+  3. candidate pairs i < j: boxes overlapping by more than tol in every coordinate.  On the device (csrc/overlap.hpp,
+     k_overlap_pairs): r = the Chebyshev radius of R_i n R_j, and d_min, d_max over it.  Verdicts, first match:
+       a radius run unbounded or capped  EQUAL when value-equal, else CROSSING      r <= tol          DISJOINT
+       value-equal                       EQUAL    (i is cut by R_j)                  d_max <= tol      I_WINS  (j is cut by R_i)
+       d_min >= -tol                     J_WINS   (i is cut by R_j)                  a d run unbounded or capped, or neither: CROSSING
+     CROSSING: i is cut by R_j and the cut row, j by R_i and the reversed cut row;
+  4. region i's cutters in ascending j; pieces start as [R_i]; in round r every live piece of a region with more than r cutters meets
+     its r-th cutter C (rows c_1 .. c_p: the region's, then the cut row), one launch per round (k_overlap_split): where
+     radius(P n C) <= tol the piece stays; otherwise the children P n {earlier cutting rows} n {n_k.theta >= o_k} for every row k
+     that cuts (the child's radius exceeds tol) replace it in row order, with rows: P's, the earlier cutting rows, the reversed row.
+
+The pieces of one source are convex, closed, and share boundaries only; they are not merged back and keep redundant rows.
+"""
+import time
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy
+
+from .critical_region import CriticalRegion
+from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, unit_rows
+
+__all__ = ['ReducedRegion', 'OverlapPartition', 'remove_overlaps', 'partition_by_value', 'build_reduced_solution', 'VERDICTS']
+
+VERDICTS = ('DISJOINT', 'EQUAL', 'I_WINS', 'J_WINS', 'CROSSING')
+DISJOINT, EQUAL, I_WINS, J_WINS, CROSSING = range(5)
+
+
+@dataclass(eq=False)
+class ReducedRegion(CriticalRegion):
+    """A piece of region ``source`` of the solution remove_overlaps was given: the source's laws, active set and binaries on the part
+    {E theta <= f} of the source region where its value is the lowest."""
+    source: int = -1
+
+
+@dataclass
+class OverlapPartition:
+    """What partition_by_value returns.  pieces[k]: unit rows [o | n] of piece k, or None for a source that lost nothing (its own rows
+    stand); sources[k]: its source; pairs: (i, j, verdict, radius, d_min, d_max) arrays of the candidate pairs."""
+    pieces: List[Optional[numpy.ndarray]]
+    sources: numpy.ndarray
+    vanished: List[int]
+    pairs: dict
+    verdict_counts: dict
+    stats: dict
+
+
+def box_pairs(box: numpy.ndarray, usable: numpy.ndarray, tol: float):
+    """(i, j) with i < j, ascending, of the usable regions whose boxes [R, 2, n_t] overlap by more than tol in every coordinate: a sweep
+    along the first coordinate."""
+    idx = numpy.flatnonzero(usable)
+    if len(idx) < 2:
+        return numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int64)
+    lo, hi = box[idx, 0], box[idx, 1]
+    order = numpy.argsort(lo[:, 0], kind='stable')
+    lo, hi, idx = lo[order], hi[order], idx[order]
+    end = numpy.searchsorted(lo[:, 0], hi[:, 0] - tol, side='left')    # lo_j < hi_i - tol for j in (k, end[k])
+    pa, pb = [], []
+    with numpy.errstate(invalid='ignore'):
+        for k in range(len(idx) - 1):
+            e = int(end[k])
+            if e <= k + 1:
+                continue
+            hit = numpy.all(numpy.minimum(hi[k], hi[k + 1:e]) - numpy.maximum(lo[k], lo[k + 1:e]) > tol, axis=1)
+            other = idx[k + 1:e][hit]
+            pa.append(numpy.minimum(idx[k], other))
+            pb.append(numpy.maximum(idx[k], other))
+    if not pa:
+        return numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int64)
+    pa, pb = numpy.concatenate(pa), numpy.concatenate(pb)
+    o = numpy.lexsort((pb, pa))
+    return pa[o].astype(numpy.int64), pb[o].astype(numpy.int64)
+
+
+def classify_pairs(radius, d_min, d_max, flag, equal, tol: float) -> numpy.ndarray:
+    """The host verdicts of step 3 from what k_overlap_pairs wrote (d_min, d_max NaN where it ran no d LP and the host filled none)."""
+    n = len(radius)
+    v = numpy.full(n, CROSSING, dtype=numpy.int32)
+    with numpy.errstate(invalid='ignore'):
+        radius_open = (flag != 0) & numpy.isnan(d_min)            # the radius run itself was unbounded or capped
+        done = numpy.zeros(n, dtype=bool)
+        for cond, verdict in ((radius_open & equal, EQUAL), (radius_open & ~equal, CROSSING), (radius <= tol, DISJOINT), (equal, EQUAL),
+                              ((flag == 0) & (d_max <= tol), I_WINS), ((flag == 0) & (d_min >= -tol), J_WINS)):
+            take = cond & ~done
+            v[take] = verdict
+            done |= take
+    return v
+
+
+def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20,
+                       device: int = 0, void=()) -> OverlapPartition:
+    """The partition of the polytopes {n.theta <= o} (unit rows ef_rows = [o | n] in CSR form by row_off) by the lowest affine value
+    g_i.theta + h_i: an OverlapPartition.  Steps 2 to 4 of the module docstring; every LP runs on the device.  ``void``: polytopes
+    known to be empty (they vanish and cut nothing), like the ones the device finds empty."""
+    from . import _lib
+    t0 = time.perf_counter()
+    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
+    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
+    g = numpy.ascontiguousarray(g, dtype=numpy.float64).reshape(-1, n_t)
+    h = numpy.ascontiguousarray(h, dtype=numpy.float64).reshape(-1)
+    R = len(off) - 1
+    if not (1 <= n_t <= MAX_DIM):
+        raise ValueError(f'partition_by_value: n_theta = {n_t} is outside 1..{MAX_DIM}')
+    if not (numpy.isfinite(tol) and tol >= 0.0 and numpy.isfinite(value_tol) and value_tol >= 0.0):
+        raise ValueError('partition_by_value: tol and value_tol must be finite and >= 0')
+    if R < 1 or len(g) != R or len(h) != R or off[0] != 0 or off[-1] != len(ef):
+        raise ValueError('partition_by_value: row_off [R + 1], g [R, n_t] and h [R] must describe R >= 1 polytopes')
+    counts = numpy.diff(off)
+    if counts.min() < 1 or counts.max() > MAX_ROWS:
+        raise ValueError(f'partition_by_value: every polytope needs 1..{MAX_ROWS} rows')
+    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(g)) and numpy.all(numpy.isfinite(h))):
+        raise ValueError('partition_by_value: rows and values must be finite')
+    stats = {'regions_before': R, 'candidate_pairs': 0, 'rounds': 0, 'work_items': 0, 'max_item_rows': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0}
+    xs, box, status, s = _lib.merge_regions(off, ef, device)
+    stats['lps'] += s['lps']
+    stats['pivots'] += s['pivots']
+    stats['device_ms'] += s['ms']
+    usable = status == 0
+    usable[list(void)] = False
+    xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
+    # 2. values
+    pa, pb = box_pairs(box, usable, tol)
+    n_pairs = len(pa)
+    stats['candidate_pairs'] = n_pairs
+    g_thr = value_tol * (1.0 + float(numpy.max(numpy.linalg.norm(g, axis=1))))
+    h_thr = value_tol * (1.0 + float(numpy.max(numpy.abs(h))))
+    dg, dh = g[pa] - g[pb], h[pa] - h[pb]
+    gn = numpy.linalg.norm(dg, axis=1)
+    flat = gn <= g_thr
+    equal = flat & (numpy.abs(dh) <= h_thr)
+    has_cut = ~flat
+    safe = numpy.where(has_cut, gn, 1.0)
+    cut = numpy.hstack([(dh / safe).reshape(-1, 1), -dg / safe[:, None]])
+    cut[~has_cut] = 0.0
+    # 3. the pair stage
+    if n_pairs:
+        radius, d_min, d_max, flag, s = _lib.overlap_pairs(off, ef, xs, pa, pb, has_cut.astype(numpy.int32), cut, tol, device)
+        for k in ('lps', 'pivots'):
+            stats[k] += s[k]
+        stats['wide'] += s['capped']
+        stats['device_ms'] += s['ms']
+    else:
+        radius = d_min = d_max = numpy.zeros(0)
+        flag = numpy.zeros(0, dtype=numpy.int32)
+    const = flat & ~equal & (flag == 0)      # a constant difference: the sign of h decides everywhere
+    d_min, d_max = d_min.copy(), d_max.copy()
+    d_min[const] = d_max[const] = numpy.where(dh[const] > 0.0, numpy.inf, -numpy.inf)
+    radius_open = (flag != 0) & numpy.isnan(d_min)
+    verdict = classify_pairs(radius, d_min, d_max, flag, equal, tol)
+    # a constant difference behind an open radius run has no cut row to cross at: the cheaper region cuts the other
+    fix = radius_open & flat & ~equal
+    verdict[fix] = numpy.where(dh[fix] > 0.0, J_WINS, I_WINS)
+    cutters = [[] for _ in range(R)]          # (cutter region, cut row or None), ascending by cutter
+    for k in numpy.flatnonzero(verdict != DISJOINT).tolist():
+        i, j, v = int(pa[k]), int(pb[k]), int(verdict[k])
+        if v in (EQUAL, J_WINS):
+            cutters[i].append((j, None))
+        elif v == I_WINS:
+            cutters[j].append((i, None))
+        else:
+            cutters[i].append((j, cut[k]))
+            cutters[j].append((i, -cut[k]))
+    for c in cutters:
+        c.sort(key=lambda jc: jc[0])
+    # 4. the difference stage: per source its live pieces in order; None stands for the source's own rows
+    live = [[None] if usable[i] else [] for i in range(R)]
+    n_rounds = max((len(c) for c in cutters), default=0)
+    for rnd in range(n_rounds):
+        active = [i for i in range(R) if len(cutters[i]) > rnd and live[i]]
+        if not active:
+            continue
+        p_rows, p_counts, item_piece, item_cutter, item_cut, item_has, item_start = [], [], [], [], [], [], []
+        for i in active:
+            j, c = cutters[i][rnd]
+            for pc in live[i]:
+                rows = ef[off[i]:off[i + 1]] if pc is None else pc
+                item_piece.append(len(p_rows))
+                p_rows.append(rows)
+                p_counts.append(len(rows))
+                item_cutter.append(j)
+                item_has.append(0 if c is None else 1)
+                item_cut.append(numpy.zeros(n_t + 1) if c is None else c)
+                item_start.append(xs[i])
+        poff = numpy.concatenate([[0], numpy.cumsum(p_counts)]).astype(numpy.int64)
+        fl, mask, s = _lib.overlap_split(off, ef, poff, numpy.vstack(p_rows), item_piece, item_cutter, item_has, numpy.asarray(item_cut),
+                                         numpy.asarray(item_start), tol, device)
+        stats['rounds'] += 1
+        stats['work_items'] += len(item_piece)
+        stats['max_item_rows'] = max(stats['max_item_rows'], max(p_counts[p] + int(counts[c]) + hc for p, c, hc in zip(item_piece, item_cutter, item_has)))
+        for k in ('lps', 'pivots', 'wide'):
+            stats[k] += s[k]
+        stats['device_ms'] += s['ms']
+        q = 0
+        for i in active:
+            j, c = cutters[i][rnd]
+            cj = ef[off[j]:off[j + 1]]
+            nxt = []
+            for pc in live[i]:
+                if not fl[q] & _lib.OVERLAP_MEETS:
+                    nxt.append(pc)
+                else:
+                    rows = ef[off[i]:off[i + 1]] if pc is None else pc
+                    cutting = [cj[r] for r in mask_rows(mask[q], len(cj)).tolist()]
+                    if fl[q] & _lib.OVERLAP_CUT_ROW:
+                        cutting.append(c)
+                    for k, row in enumerate(cutting):
+                        nxt.append(numpy.vstack([rows] + cutting[:k] + [-row]))
+                q += 1
+            live[i] = nxt
+        if any(pc is not None and len(pc) > MAX_ROWS for i in active for pc in live[i]):
+            raise ValueError(f'remove_overlaps: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
+        if sum(len(p) for p in live) > max_pieces:
+            raise ValueError(f'remove_overlaps: more than max_pieces = {max_pieces} pieces after round {rnd + 1}')
+    pieces = [pc for i in range(R) for pc in live[i]]
+    sources = numpy.asarray([i for i in range(R) for _ in live[i]], dtype=numpy.int64)
+    counts_v = {name: int(numpy.sum(verdict == k)) for k, name in enumerate(VERDICTS)}
+    stats['regions_after'] = len(pieces)
+    stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
+    return OverlapPartition(pieces=pieces, sources=sources, vanished=[i for i in range(R) if not live[i]],
+                            pairs={'i': pa, 'j': pb, 'verdict': verdict, 'radius': radius, 'd_min': d_min, 'd_max': d_max},
+                            verdict_counts=counts_v, stats=stats)
+
+
+def build_reduced_solution(source, sources, rows, verdict_counts: Optional[dict] = None, vanished=None, stats: Optional[dict] = None):
+    """The reduced Solution from ``sources`` (non-decreasing source index per piece) and ``rows`` (per piece [m, n_t + 1] unit rows
+    [o | n], or None for a source that lost nothing, whose E, f are copied unchanged).  Host only: no device is touched."""
+    from .solution import Solution
+    regs = source.critical_regions
+    n_t = source.theta_dim() if source.program is not None else numpy.asarray(regs[0].E).shape[1]
+    sources = numpy.asarray(sources, dtype=numpy.int64).reshape(-1)
+    if len(sources) != len(rows) or numpy.any(sources < 0) or numpy.any(sources >= len(regs)) or numpy.any(numpy.diff(sources) < 0):
+        raise ValueError('build_reduced_solution: sources must be non-decreasing indices into the source regions, one per piece')
+    copy = lambda a: None if a is None else numpy.array(a, copy=True)
+    out = []
+    for i, rk in zip(sources.tolist(), rows):
+        src = regs[i]
+        if rk is None:
+            E, f = numpy.array(src.E, dtype=numpy.float64, copy=True), numpy.array(src.f, dtype=numpy.float64, copy=True)
+        else:
+            rk = numpy.asarray(rk, dtype=numpy.float64).reshape(-1, n_t + 1)
+            E, f = rk[:, 1:].copy(), rk[:, :1].copy()
+        out.append(ReducedRegion(copy(src.A), copy(src.b), copy(src.C), copy(src.d), E, f, list(src.active_set), list(src.omega_set),
+                                 list(src.lambda_set), [list(v) for v in src.regular_set], copy(src.y_fixation), copy(src.y_indices),
+                                 copy(src.x_indices), source=int(i)))
+    sol = Solution(source.program, out, is_overlapping=False, point_location_tolerance=source.point_location_tolerance)
+    sol.is_complete = source.is_complete
+    present = set(sources.tolist())
+    sol.overlap_info = {'source': source, 'sources': sources.copy(), 'verdict_counts': dict(verdict_counts or {}),
+                        'vanished': sorted(int(i) for i in vanished) if vanished is not None else
+                        [i for i in range(len(regs)) if i not in present], 'stats': dict(stats or {})}
+    return sol
+
+
+def check_source(source, tol: float, value_tol: float, max_pieces: int):
+    """(n_theta, qv, rv) of a solution remove_overlaps accepts; ValueError otherwise, before anything reaches the device."""
+    if not source.critical_regions:
+        raise ValueError('remove_overlaps: the solution has no regions')
+    if source.merge_info is not None:
+        raise ValueError('remove_overlaps: a merged solution keeps no full law to compare values with: reduce the source '
+                         '(merge_info["source"]) instead')
+    n_t = source.theta_dim() if source.program is not None else numpy.asarray(source.critical_regions[0].E).shape[1]
+    if n_t > MAX_DIM:
+        raise ValueError(f'remove_overlaps: n_theta = {n_t} > {MAX_DIM}')
+    for i, r in enumerate(source.critical_regions):
+        if numpy.asarray(r.E).reshape(-1, n_t).shape[0] > MAX_ROWS:
+            raise ValueError(f'remove_overlaps: region {i} has more than {MAX_ROWS} rows')
+    if not (numpy.isfinite(tol) and tol >= 0.0 and numpy.isfinite(value_tol) and value_tol >= 0.0):
+        raise ValueError('remove_overlaps: tol and value_tol must be finite and >= 0')
+    if int(max_pieces) < 1:
+        raise ValueError('remove_overlaps: max_pieces must be >= 1')
+    Qv, qv, rv = source.value_function()
+    if numpy.max(numpy.abs(Qv - Qv[0])) > value_tol * (1.0 + numpy.max(numpy.abs(Qv))):
+        raise ValueError('remove_overlaps: the value functions do not share one quadratic part; the comparison of quadratic value '
+                         'functions is not convex and is out of scope (mpLP and mpMILP solutions without bilinear terms qualify)')
+    return n_t, qv, rv
+
+
+def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0):
+    """Solution.remove_overlaps (the module docstring).  Returns a new Solution of ReducedRegion; the source is not modified."""
+    t0 = time.perf_counter()
+    n_t, qv, rv = check_source(source, tol, value_tol, max_pieces)
+    regs = source.critical_regions
+    rows, void = [], []
+    for i, r in enumerate(regs):
+        u, empty = unit_rows(r.E, r.f, n_t)
+        if not len(u):
+            raise ValueError(f'remove_overlaps: region {i} has no row with a normal (the whole space, or nothing)')
+        rows.append(u)
+        if empty:
+            void.append(i)
+    off = numpy.concatenate([[0], numpy.cumsum([len(u) for u in rows])]).astype(numpy.int64)
+    part = partition_by_value(off, numpy.vstack(rows), qv, rv, n_t, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device,
+                              void=void)
+    part.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
+    return build_reduced_solution(source, part.sources, part.pieces, part.verdict_counts, part.vanished, part.stats)

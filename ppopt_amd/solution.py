@@ -43,6 +43,8 @@ class Solution:
     is_complete = False
     # set on the result of merge_regions (region_merge.build_merged_solution): source, outputs, members, stats
     merge_info = None
+    # set on the result of remove_overlaps (overlap.build_reduced_solution): source, sources, verdict_counts, vanished, stats
+    overlap_info = None
 
     def __init__(self, program, critical_regions: List[CriticalRegion], is_overlapping: bool = False,
                  point_location_tolerance: float = 1e-5):
@@ -50,6 +52,7 @@ class Solution:
         self.critical_regions = critical_regions
         self.is_overlapping = is_overlapping
         self.point_location_tolerance = point_location_tolerance
+        self.overlap_info = None
 
     def add_region(self, region: CriticalRegion) -> None:
         self.critical_regions.append(region)
@@ -88,6 +91,17 @@ class Solution:
         256 rows and outputs out of range."""
         from .region_merge import merge_regions
         return merge_regions(self, outputs=outputs, tol=tol, law_tol=law_tol, device=device)
+
+    def remove_overlaps(self, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0) -> 'Solution':
+        """A new, non-overlapping solution: every region keeps only the part of the parameter space where its value function is the
+        lowest among the regions that contain the point (ties to the higher index, as get_region resolves them), as convex pieces
+        (overlap.ReducedRegion with ``source``), ordered by source; the pair comparisons and the region differences are LPs on the device
+        (overlap.py).  ``overlap_info`` of the result holds the source, sources, verdict_counts, vanished and stats.
+        ValueError before any launch for an empty or merged solution, n_theta > 16, a region of more than 256 rows, non-finite
+        tolerances and value functions with different quadratic parts (mpQP / mpMIQP); after a round for a piece of more than 256
+        rows or more than max_pieces pieces."""
+        from .overlap import remove_overlaps
+        return remove_overlaps(self, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device)
 
     def evaluate_objective(self, theta_point) -> Optional[float]:
         self._refuse_merged('evaluate_objective')
@@ -192,7 +206,8 @@ class Solution:
             P_obj = None if self.merge_info is not None else P
             self._locator = _lib.Locator(row_off, ef, xlaw, getattr(P_obj, 'Q', None), getattr(P_obj, 'c', None), getattr(P_obj, 'H', None), device)
             adj = getattr(self, '_adjacency', None)
-            if adj is not None and self.merge_info is None and len(adj[1]) == int(row_off[-1]) and len(self.critical_regions) >= self.WALK_MIN_REGIONS:
+            # (nor through a reduced one: the pieces of one source share its active set)
+            if adj is not None and self.merge_info is None and self.overlap_info is None and len(adj[1]) == int(row_off[-1]) and len(self.critical_regions) >= self.WALK_MIN_REGIONS:
                 self._locator.set_adjacency(adj[0], adj[1], P.num_constraints())
             self._locator_key = key
         return self._locator
@@ -279,7 +294,8 @@ class Solution:
     def coverage_volume(self, device: int = 0):
         """The exact share of the parameter space {A_t theta <= b_t} the regions cover: a geometry.volume.CoverageVolume with total (the
         summed volume of the OK regions), theta_volume, fraction, status_counts and ok (no region left undecided).  ValueError for
-        overlapping (mpLP) and mixed-integer solutions, whose regions may overlap; merged solutions are fine.  See DESIGN §3.17."""
+        overlapping (mpLP) and mixed-integer solutions, whose regions may overlap; merged solutions and the results of remove_overlaps
+        are fine.  See DESIGN §3.17."""
         from .geometry.volume import coverage_volume
         return coverage_volume(self, device=device)
 
