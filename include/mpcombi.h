@@ -754,6 +754,35 @@ int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions, const int6
                       const int32_t *item_cutter, const int32_t *has_cut, const double *cut_rows, const double *start, double tol,
                       int32_t *flag, uint64_t *mask, int64_t *stats, float *ms);
 
+/* ---- transition graph of a closed loop between regions (Solution.transition_graph) --------------------------------- */
+/* Regions are polytopes of unit rows [o | n] in CSR form, as for the merge and overlap calls above; region i has the closed-loop map
+ * theta+ = Phi_i theta + phi_i (Phi n_regions x n_t x n_t row-major, phi n_regions x n_t).  xs (n_regions x n_t) is a point of every
+ * region, from mpc_merge_regions.  Both calls are stateless; an error text is read with mpc_last_error(NULL).  MPC_ERR_INVALID with a
+ * message, before a device is selected: a missing array, 1 <= n_t <= 16, 1..256 rows per region, finite rows with unit normals, finite
+ * Phi, phi, xs, tol finite and >= 0, n_pairs in 0..2^31 - 1, pair indices in range (pair_a[k] == pair_b[k] is legal: a self loop).
+ *
+ * mpc_transition_boxes: image_box n_regions x 2 x n_t (lower, upper), the exact bounding box of Phi_i R_i + phi_i (k_transition_boxes);
+ *   -inf / +inf where the image is unbounded or the run stopped at the pivot cap; flag[i] = 1: some run of region i was capped.
+ *   stats (may be NULL): [0] LPs, [1] pivots, [2] capped runs.
+ * mpc_transition_pairs: for every pair (i, j) = (pair_a[k], pair_b[k]) the Chebyshev radius of T_ij = {theta in R_i : Phi_i theta + phi_i
+ *   in R_j}, over the rows of R_i and the rows of R_j pulled back through the map of i and scaled to unit normals (k_transition_pairs).
+ *   A pulled-back row whose normal is no longer than 1e-12 max(1, max |Phi_i|) is constant: it empties T_ij when its right-hand side is
+ *   below -tol (radius -inf, no LP) and is dropped otherwise.
+ *   full_radius != 0: the run goes to the optimum; 0: it stops once the radius exceeds tol (radius[k] is then a lower bound above tol).
+ *   status[k]  MPC_TRANSITION_NO_EDGE (radius <= tol), _EDGE, _UNBOUNDED (an edge, radius +inf), _UNDECIDED (the run stopped at the pivot
+ *              cap; kept as an edge by the host).  witness[k][n_t]: the theta where the run ended.
+ *   n_pairs == 0: MPC_OK without a launch.  stats (may be NULL): [0] pairs, [1] LPs, [2] pivots, [3] capped runs.
+ * Deterministic: atomics only in the counters. */
+#define MPC_TRANSITION_NO_EDGE 0
+#define MPC_TRANSITION_EDGE 1
+#define MPC_TRANSITION_UNBOUNDED 2
+#define MPC_TRANSITION_UNDECIDED 3
+int mpc_transition_boxes(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                         const double *phi, const double *xs, double *image_box, int32_t *flag, int64_t *stats, float *ms);
+int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                         const double *phi, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                         int32_t full_radius, double tol, double *radius, int32_t *status, double *witness, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

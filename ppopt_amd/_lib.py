@@ -273,6 +273,10 @@ def load():
                                              ctypes.c_double, _dp, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_overlap_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
                                              _ip, _ip, _ip, _dp, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_transition_boxes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _dp, _ip, _lp,
+                                                ctypes.POINTER(ctypes.c_float)]),
+        'mpc_transition_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
+                                                ctypes.c_int32, ctypes.c_double, _dp, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -293,7 +297,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
-                    'mpc_overlap_pairs', 'mpc_overlap_split']
+                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1343,6 +1347,57 @@ def overlap_split(row_off, ef_rows, piece_off, piece_rows, item_piece, item_cutt
     if rc != MPC_OK:
         raise MpcError(f'mpc_overlap_split failed ({rc}): {L.mpc_last_error(None).decode()}')
     return flag, mask, dict({k: int(v) for k, v in zip(('items', 'meets', 'lps', 'pivots', 'wide'), st)}, ms=float(ms.value))
+
+
+TRANSITION_NO_EDGE, TRANSITION_EDGE, TRANSITION_UNBOUNDED, TRANSITION_UNDECIDED = range(4)   # status of mpc_transition_pairs (include/mpcombi.h)
+
+
+def _transition_maps(who, R, n_t, Phi, phi, xs):
+    P = _f64(numpy.asarray(Phi, dtype=numpy.float64))
+    p = _f64(numpy.asarray(phi, dtype=numpy.float64))
+    x = _f64(numpy.asarray(xs, dtype=numpy.float64))
+    if P.size != R * n_t * n_t or p.size != R * n_t or x.size != R * n_t:
+        raise MpcError(f'{who}: Phi must be [regions, n_t, n_t], phi and xs [regions, n_t]')
+    return P.reshape(R, n_t, n_t), p.reshape(R, n_t), x.reshape(R, n_t)
+
+
+def transition_boxes(row_off, ef_rows, Phi, phi, xs, device: int = 0):
+    """The bounding boxes of the images Phi_i R_i + phi_i (include/mpcombi.h, mpc_transition_boxes): (image_box [R, 2, n_t] lower /
+    upper bounds, flag [R] int32 (1: a run was capped), stats)."""
+    off, ef = _merge_rows('transition_boxes', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    P, p, x = _transition_maps('transition_boxes', R, n_t, Phi, phi, xs)
+    L = load()
+    box, flag = numpy.zeros((R, 2, n_t)), numpy.zeros(R, dtype=numpy.int32)
+    st, ms = numpy.zeros(3, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_transition_boxes(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P.ctypes.data_as(_dp), p.ctypes.data_as(_dp),
+                                x.ctypes.data_as(_dp), box.ctypes.data_as(_dp), flag.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_transition_boxes failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return box, flag, dict({k: int(v) for k, v in zip(('lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+
+
+def transition_pairs(row_off, ef_rows, Phi, phi, xs, pair_a, pair_b, full_radius: bool, tol: float, device: int = 0):
+    """The pair stage of the transition graph (include/mpcombi.h, mpc_transition_pairs): (radius [n_pairs], status int32, witness
+    [n_pairs, n_t], stats)."""
+    off, ef = _merge_rows('transition_pairs', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    P, p, x = _transition_maps('transition_pairs', R, n_t, Phi, phi, xs)
+    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
+    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
+    if pa.shape != pb.shape:
+        raise MpcError('transition_pairs: pair_a and pair_b must have the same length')
+    n = len(pa)
+    L = load()
+    radius, status, witness = numpy.zeros(n), numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, n_t))
+    st, ms = numpy.zeros(4, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_transition_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P.ctypes.data_as(_dp), p.ctypes.data_as(_dp),
+                                x.ctypes.data_as(_dp), n, pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), 1 if full_radius else 0, float(tol),
+                                radius.ctypes.data_as(_dp), status.ctypes.data_as(_ip), witness.ctypes.data_as(_dp), st.ctypes.data_as(_lp),
+                                ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_transition_pairs failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return radius, status, witness, dict({k: int(v) for k, v in zip(('pairs', 'lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
 
 
 class Locator:

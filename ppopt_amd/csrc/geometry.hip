@@ -1,7 +1,7 @@
 // geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
 // location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration, region volumes and region
 // merging and the overlap removal.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
-// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, simplex.hpp); the pools and the scaffold
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +22,7 @@
 #include "volume.hpp"
 #include "merge.hpp"
 #include "overlap.hpp"
+#include "transition.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1408,6 +1409,102 @@ extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions,
     unsigned long long cnt[5] = {0, 0, 0, 0, 0};
     s.download(cnt, d_cnt, sizeof cnt);
     if (stats) for (int i = 0; i < 5; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+// ---- transition graph of a closed loop (transition.hpp) ---------------------------------------------------------------
+// Phi [n_regions][n_t][n_t], phi and xs [n_regions][n_t]: present and finite
+static int transition_check_maps(const char *who, int32_t n_t, int64_t n_regions, const double *Phi, const double *phi, const double *xs) {
+    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+    if (n_regions == 0) return MPC_OK;
+    if (!Phi || !phi || !xs) return bad("missing array (Phi, phi or xs)");
+    for (int64_t i = 0; i < n_regions * n_t * n_t; ++i)
+        if (!std::isfinite(Phi[i])) return bad("Phi must be finite");
+    for (int64_t i = 0; i < n_regions * n_t; ++i)
+        if (!std::isfinite(phi[i]) || !std::isfinite(xs[i])) return bad("phi and xs must be finite");
+    return MPC_OK;
+}
+
+extern "C" int mpc_transition_boxes(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                                    const double *phi, const double *xs, double *image_box, int32_t *flag, int64_t *stats, float *ms) {
+    const char *who = "mpc_transition_boxes";
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, xs)) return rc;
+    if (n_regions == 0) return MPC_OK;
+    if (!image_box || !flag) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_boxes: missing output array");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(m_max, n_t), nr = (size_t)n_regions;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
+    DevBuf &d_box = s.buf(nr * 2 * n_t * 8), &d_f = s.buf(nr * 4), &d_cnt = s.buf(3 * 8);
+    s.fill(d_cnt, 0, 3 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_transition_boxes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        hipLaunchKernelGGL(k_transition_boxes, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
+                           d.off.as<long long>(), d.ef.as<double>(), d_Phi.as<double>(), d_phi.as<double>(), d_xs.as<double>(),
+                           d_box.as<double>(), d_f.as<int32_t>(), d_cnt.as<unsigned long long>());
+    });
+    s.download(image_box, d_box, nr * 2 * n_t * 8);
+    s.download(flag, d_f, nr * 4);
+    unsigned long long cnt[3] = {0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+extern "C" int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                                    const double *phi, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                                    int32_t full_radius, double tol, double *radius, int32_t *status, double *witness, int64_t *stats, float *ms) {
+    const char *who = "mpc_transition_pairs";
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: tol must be finite and >= 0");
+    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, xs)) return rc;
+    if (n_pairs == 0) return MPC_OK;
+    if (!pair_a || !pair_b || !radius || !status || !witness) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: missing array");
+    int pair_rows = 2;
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t p = pair_a[k], q = pair_b[k];     // p == q is a self loop
+        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: a pair names a region out of range");
+        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q]));
+    }
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(pair_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes
+    const size_t np = (size_t)n_pairs, nr = (size_t)n_regions;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
+    DevBuf &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
+    DevBuf &d_r = s.buf(np * 8), &d_st = s.buf(np * 4), &d_w = s.buf(np * n_t * 8), &d_cnt = s.buf(4 * 8);
+    s.fill(d_cnt, 0, 4 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_transition_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        TransitionPairArgs a{};
+        a.nt = n_t; a.m_max = pair_rows; a.full_radius = full_radius ? 1 : 0; a.n_pairs = n_pairs;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
+        a.xs = d_xs.as<double>(); a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+        a.radius = d_r.as<double>(); a.witness = d_w.as<double>(); a.status = d_st.as<int32_t>();
+        a.counters = d_cnt.as<unsigned long long>();
+        hipLaunchKernelGGL(k_transition_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
+    });
+    s.download(radius, d_r, np * 8);
+    s.download(status, d_st, np * 4);
+    s.download(witness, d_w, np * n_t * 8);
+    unsigned long long cnt[4] = {0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 4; ++i) stats[i] = (int64_t)cnt[i];
     s.elapsed(ms);
     return s.finish();
 }

@@ -39,15 +39,15 @@ class FeasibilityCertificate:
     stats: dict = field(default_factory=dict)
 
 
-def _finite(name, a):
+def _finite(name, a, who='certify_recursive_feasibility'):
     if not numpy.all(numpy.isfinite(a)):
-        raise ValueError(f'certify_recursive_feasibility: {name} must be finite')
+        raise ValueError(f'{who}: {name} must be finite')
     return a
 
 
-def _check(solution, A, B, inputs, c, disturbance, tol):
+def _check(solution, A, B, inputs, c, disturbance, tol, who='certify_recursive_feasibility'):
+    """The argument checks certify_recursive_feasibility and transition.transition_graph (``who``) share."""
     from .closed_loop import _law_rows
-    who = 'certify_recursive_feasibility'
     if not solution.critical_regions:
         raise ValueError(f'{who}: the solution has no region')
     if getattr(solution.critical_regions[0], 'y_fixation', None) is not None or hasattr(solution.program, 'binary_indices'):
@@ -68,13 +68,13 @@ def _check(solution, A, B, inputs, c, disturbance, tol):
     n_x = _law_rows(solution, n_t)
     if inp.min() < 0 or inp.max() >= n_x:
         raise ValueError(f'{who}: inputs {inp.tolist()} out of range: the law has {n_x} rows')
-    _finite('A', A)
-    _finite('B', B)
+    _finite('A', A, who)
+    _finite('B', B, who)
     if c is not None:
         c = numpy.asarray(c, dtype=numpy.float64).reshape(-1)
         if len(c) != n_t:
             raise ValueError(f'{who}: c must have {n_t} entries')
-        _finite('c', c)
+        _finite('c', c, who)
     box = None
     if disturbance is not None:
         if not (isinstance(disturbance, (tuple, list)) and len(disturbance) == 2):
@@ -82,7 +82,7 @@ def _check(solution, A, B, inputs, c, disturbance, tol):
         lo, hi = (numpy.asarray(v, dtype=numpy.float64).reshape(-1) for v in disturbance)
         if len(lo) != n_t or len(hi) != n_t:
             raise ValueError(f'{who}: the box (lo, hi) needs two vectors of {n_t} entries')
-        _finite('the box', numpy.concatenate([lo, hi]))
+        _finite('the box', numpy.concatenate([lo, hi]), who)
         if numpy.any(lo > hi):
             raise ValueError(f'{who}: the box needs lo <= hi')
         if n_t > MAX_BOX_DIM:

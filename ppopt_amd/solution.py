@@ -306,6 +306,17 @@ class Solution:
         from .invariance import certify_recursive_feasibility
         return certify_recursive_feasibility(self, A, B, inputs, c=c, disturbance=disturbance, tol=tol, device=device)
 
+    def transition_graph(self, A, B, inputs, c=None, tol: float = 1e-8, full_radius: bool = False, device: int = 0):
+        """Which region can follow which under the plant theta+ = A theta + B u + c with this controller's law u = x*(theta)[inputs]: a
+        transition.TransitionGraph (successors in CSR form, per edge radius, status and witness; reachable, steps_to, cycles_outside).
+        i -> j is an edge iff {theta in R_i : its image lies in R_j} has a Chebyshev radius above tol, one LP per candidate pair on the
+        device; ``full_radius`` runs every LP to its optimum.  Transitions through a facet or a vertex are not edges, so statements about
+        trajectories hold for almost every initial state.  ValueError before any launch for mixed-integer solutions, solutions flagged
+        overlapping that have not been through remove_overlaps, and the arguments certify_recursive_feasibility refuses; merged
+        solutions and reduced continuous ones are accepted.  See transition.py and DESIGN §3.20."""
+        from .transition import transition_graph
+        return transition_graph(self, A, B, inputs, c=c, tol=tol, full_radius=full_radius, device=device)
+
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):
         """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial
