@@ -783,6 +783,29 @@ int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regions, const i
                          const double *phi, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                          int32_t full_radius, double tol, double *radius, int32_t *status, double *witness, int64_t *stats, float *ms);
 
+/* ---- exit sets of a closed loop (Solution.exit_sets) ---------------------------------------------------------------- */
+/* Regions, maps and pieces as for the overlap and transition calls above.  Stateless; an error text is read with mpc_last_error(NULL).
+ * MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n_t <= 16, 1..256 rows per region and per piece,
+ * finite rows with unit normals, finite Phi, phi, start, tol finite and >= 0, n_items in 0..2^31 - 1, indices in range.
+ *
+ * mpc_exit_split: one step of the region difference for every item k = (piece item_piece[k], source region i = item_source[k], target
+ *   region j = item_target[k]).  The cutter is C_ij = {theta : Phi_i theta + phi_i in R_j}: the rows of R_j pulled back through the map
+ *   of i exactly as mpc_transition_pairs forms them (a constant row with right-hand side below -tol empties C_ij: the piece stays and no
+ *   LP runs; any other constant row is dropped and never cuts) (k_exit_split).
+ *   flag[k]    bit 0 (MPC_OVERLAP_MEETS): radius(P n C_ij) > tol.  Clear: the piece stays whole and the mask is empty.
+ *              bit 2 (MPC_OVERLAP_WIDE): some run was unbounded or capped.  Bit 1 is never set.
+ *   mask[k][MPC_MERGE_WORDS]  bit r: row r of region j, pulled back, cuts, i.e. P n {earlier cutting rows} n {the reversed row} has a
+ *              radius above tol, taken in row order; every such set is a child piece (rows: P's, the earlier cutting pulled-back rows,
+ *              the reversed one) and P n C_ij is dropped.  An unbounded or capped run counts as "cuts".
+ *   start      [n_items][n_t] where the first run of an item starts, or NULL: the origin.
+ *   n_items == 0: MPC_OK without a launch.
+ *   stats (may be NULL): [0] items, [1] items whose piece meets the cutter, [2] LPs, [3] pivots, [4] unbounded or capped runs.
+ * Deterministic: atomics only in the counters. */
+int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                   const double *phi, int64_t n_pieces, const int64_t *piece_off, const double *piece_rows, int64_t n_items,
+                   const int32_t *item_piece, const int32_t *item_source, const int32_t *item_target, const double *start, double tol,
+                   int32_t *flag, uint64_t *mask, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,8 @@ def load():
                                                 ctypes.POINTER(ctypes.c_float)]),
         'mpc_transition_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, ctypes.c_int64, _ip, _ip,
                                                 ctypes.c_int32, ctypes.c_double, _dp, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_exit_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
+                                          _ip, _ip, _ip, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -297,7 +299,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
-                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs']
+                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1398,6 +1400,37 @@ def transition_pairs(row_off, ef_rows, Phi, phi, xs, pair_a, pair_b, full_radius
     if rc != MPC_OK:
         raise MpcError(f'mpc_transition_pairs failed ({rc}): {L.mpc_last_error(None).decode()}')
     return radius, status, witness, dict({k: int(v) for k, v in zip(('pairs', 'lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+
+
+def exit_split(row_off, ef_rows, Phi, phi, piece_off, piece_rows, item_piece, item_source, item_target, start, tol: float, device: int = 0):
+    """One round of the region difference against pulled-back cutters (include/mpcombi.h, mpc_exit_split): (flag [n_items] int32 with the
+    bits OVERLAP_MEETS and OVERLAP_WIDE, mask [n_items, MERGE_WORDS] uint64, stats)."""
+    off, ef = _merge_rows('exit_split', row_off, ef_rows)
+    poff, pef = _merge_rows('exit_split', piece_off, piece_rows)
+    n_t, R, P = ef.shape[1] - 1, len(off) - 1, len(poff) - 1
+    if pef.shape[1] != n_t + 1:
+        raise MpcError('exit_split: regions and pieces must have the same n_t')
+    M = _f64(numpy.asarray(Phi, dtype=numpy.float64))
+    p = _f64(numpy.asarray(phi, dtype=numpy.float64))
+    if M.size != R * n_t * n_t or p.size != R * n_t:
+        raise MpcError('exit_split: Phi must be [regions, n_t, n_t] and phi [regions, n_t]')
+    ip = numpy.ascontiguousarray(item_piece, dtype=numpy.int32).reshape(-1)
+    src = numpy.ascontiguousarray(item_source, dtype=numpy.int32).reshape(-1)
+    dst = numpy.ascontiguousarray(item_target, dtype=numpy.int32).reshape(-1)
+    if not (ip.shape == src.shape == dst.shape):
+        raise MpcError('exit_split: item_piece, item_source and item_target must have the same length')
+    n = len(ip)
+    s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
+    L = load()
+    flag, mask = numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
+    st, ms = numpy.zeros(5, dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = L.mpc_exit_split(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), M.ctypes.data_as(_dp), p.ctypes.data_as(_dp), P,
+                          poff.ctypes.data_as(_lp), pef.ctypes.data_as(_dp), n, ip.ctypes.data_as(_ip), src.ctypes.data_as(_ip),
+                          dst.ctypes.data_as(_ip), None if s0 is None else s0.ctypes.data_as(_dp), float(tol), flag.ctypes.data_as(_ip),
+                          mask.ctypes.data_as(_u64p), st.ctypes.data_as(_lp), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'mpc_exit_split failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return flag, mask, dict({k: int(v) for k, v in zip(('items', 'meets', 'lps', 'pivots', 'wide'), st)}, ms=float(ms.value))
 
 
 class Locator:

@@ -23,6 +23,7 @@
 #include "merge.hpp"
 #include "overlap.hpp"
 #include "transition.hpp"
+#include "exit_sets.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1505,6 +1506,70 @@ extern "C" int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regio
     unsigned long long cnt[4] = {0, 0, 0, 0};
     s.download(cnt, d_cnt, sizeof cnt);
     if (stats) for (int i = 0; i < 4; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+// ---- exit sets of a closed loop (exit_sets.hpp) -------------------------------------------------------------------------
+extern "C" int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                              const double *phi, int64_t n_pieces, const int64_t *piece_off, const double *piece_rows, int64_t n_items,
+                              const int32_t *item_piece, const int32_t *item_source, const int32_t *item_target, const double *start, double tol,
+                              int32_t *flag, uint64_t *mask, int64_t *stats, float *ms) {
+    const char *who = "mpc_exit_split";
+    if (stats) for (int i = 0; i < 5; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+    int m_reg = 1, m_piece = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
+    if (int rc = merge_check("mpc_exit_split (pieces)", n_t, n_pieces, piece_off, piece_rows, &m_piece)) return rc;
+    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: tol must be finite and >= 0");
+    if (n_items < 0 || n_items > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: n_items must lie in 0..2^31 - 1");
+    if (n_regions > 0) {
+        if (!Phi || !phi) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: missing array (Phi or phi)");
+        for (int64_t i = 0; i < n_regions * n_t * n_t; ++i)
+            if (!std::isfinite(Phi[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: Phi must be finite");
+        for (int64_t i = 0; i < n_regions * n_t; ++i)
+            if (!std::isfinite(phi[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: phi must be finite");
+    }
+    if (n_items == 0) return MPC_OK;
+    if (!item_piece || !item_source || !item_target || !flag || !mask) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: missing array");
+    int item_rows = 4;
+    for (int64_t k = 0; k < n_items; ++k) {
+        const int64_t p = item_piece[k], i = item_source[k], j = item_target[k];     // i == j: the piece minus the part that stays in its region
+        if (p < 0 || p >= n_pieces || i < 0 || i >= n_regions || j < 0 || j >= n_regions)
+            return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: an item names a piece or a region out of range");
+        item_rows = std::max<int>(item_rows, (int)(piece_off[p + 1] - piece_off[p] + row_off[j + 1] - row_off[j]));
+    }
+    if (start)
+        for (int64_t i = 0; i < n_items * n_t; ++i)
+            if (!std::isfinite(start[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: start must be finite");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_mask adds 32)
+    const size_t ni = (size_t)n_items, nr = (size_t)n_regions, words = ni * OV_WORDS * 8;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    const RegionsOnDevice pc = upload_regions(s, n_pieces, piece_off, piece_rows, n_t + 1);
+    DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8);
+    DevBuf &d_ip = s.upload(item_piece, ni * 4), &d_is = s.upload(item_source, ni * 4), &d_it = s.upload(item_target, ni * 4);
+    DevBuf *d_start = start ? &s.upload(start, ni * n_t * 8) : nullptr;
+    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = s.buf(5 * 8);
+    s.fill(d_cnt, 0, 5 * 8);
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_exit_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] {
+        ExitSplitArgs a{};
+        a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
+        a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
+        a.item_piece = d_ip.as<int32_t>(); a.item_source = d_is.as<int32_t>(); a.item_target = d_it.as<int32_t>();
+        a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+        a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
+        hipLaunchKernelGGL(k_exit_split, dim3((unsigned)n_items), dim3(64), lds, nullptr, a);
+    });
+    s.download(flag, d_f, ni * 4);
+    s.download(mask, d_m, words);
+    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (stats) for (int i = 0; i < 5; ++i) stats[i] = (int64_t)cnt[i];
     s.elapsed(ms);
     return s.finish();
 }

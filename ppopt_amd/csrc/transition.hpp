@@ -63,6 +63,45 @@ __global__ void __launch_bounds__(64) k_transition_boxes(int nt, int m_max, long
     }
 }
 
+// the m_j rows of a target region (rows [r0_j, r0_j + m_j) of ef) pulled back through theta+ = P theta + sh into the LDS rows
+// [at, at + m_j), lanes over rows: unit rows, or flag 2 with right-hand side +inf for a constant row (the header comment).  Returns, per
+// lane, 1 where a constant row of that lane empties the pulled-back set (the caller votes with __any); no barrier.
+__device__ inline int ts_pull_back(const TrLds &S, const double *ef, long long r0_j, int m_j, int nt, int at, const double *P, const double *sh,
+                                   double tol) {
+    const int lane = threadIdx.x & 63, nr = nt + 1;
+    double big = 0.0;
+    for (int e = lane; e < nt * nt; e += 64) big = fmax(big, fabs(P[e]));
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) big = fmax(big, __shfl_xor(big, off));
+    const double thr = TS_ROW_EPS * fmax(1.0, big);
+    int empty = 0;
+    for (int r = lane; r < m_j; r += 64) {
+        const double *row = ef + (r0_j + r) * (long long)nr;
+        double *out = S.A + (size_t)(at + r) * nr;
+        double beta = row[0], ss = 0.0;
+        for (int t = 0; t < nt; ++t) beta = fma(-row[1 + t], sh[t], beta);
+        for (int k = 0; k < nt; ++k) {
+            double v = 0.0;
+            for (int t = 0; t < nt; ++t) v = fma(P[t * nt + k], row[1 + t], v);
+            out[k] = v;
+            ss = fma(v, v, ss);
+        }
+        const double s = sqrt(ss);
+        if (s > thr) {
+            for (int k = 0; k < nt; ++k) out[k] /= s;
+            out[nt] = 1.0;
+            S.b[at + r] = beta / s;
+            S.flag[at + r] = 0;
+        } else {
+            if (beta < -tol) empty = 1;
+            for (int k = 0; k <= nt; ++k) out[k] = 0.0;
+            S.b[at + r] = INFINITY;
+            S.flag[at + r] = 2;
+        }
+    }
+    return empty;
+}
+
 struct TransitionPairArgs {
     int nt, m_max, full_radius;      // m_max: LDS rows, at least m_i + m_j of every pair
     long long n_pairs;
@@ -79,7 +118,7 @@ struct TransitionPairArgs {
 
 __global__ void __launch_bounds__(64) k_transition_pairs(TransitionPairArgs a) {
     extern __shared__ double ts_smem[];
-    const int lane = threadIdx.x & 63, nt = a.nt, nr = nt + 1;
+    const int lane = threadIdx.x & 63, nt = a.nt;
     const long long q = blockIdx.x;
     if (q >= a.n_pairs) return;
     const TrLds S = tr_lds(ts_smem, a.m_max, nt);
@@ -88,36 +127,7 @@ __global__ void __launch_bounds__(64) k_transition_pairs(TransitionPairArgs a) {
     const double *P = a.Phi + reg_i * (long long)nt * nt, *sh = a.phi + reg_i * nt;
     unsigned long long pivots = 0, lps = 0;
     ov_load(S, a.ef, r0_i, m_i, nt, 0);
-    double big = 0.0;
-    for (int e = lane; e < nt * nt; e += 64) big = fmax(big, fabs(P[e]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) big = fmax(big, __shfl_xor(big, off));
-    const double thr = TS_ROW_EPS * fmax(1.0, big);
-    int empty = 0;
-    for (int r = lane; r < m_j; r += 64) {
-        const double *row = a.ef + (r0_j + r) * (long long)nr;
-        double *out = S.A + (size_t)(m_i + r) * nr;
-        double beta = row[0], ss = 0.0;
-        for (int t = 0; t < nt; ++t) beta = fma(-row[1 + t], sh[t], beta);
-        for (int k = 0; k < nt; ++k) {
-            double v = 0.0;
-            for (int t = 0; t < nt; ++t) v = fma(P[t * nt + k], row[1 + t], v);
-            out[k] = v;
-            ss = fma(v, v, ss);
-        }
-        const double s = sqrt(ss);
-        if (s > thr) {
-            for (int k = 0; k < nt; ++k) out[k] /= s;
-            out[nt] = 1.0;
-            S.b[m_i + r] = beta / s;
-            S.flag[m_i + r] = 0;
-        } else {
-            if (beta < -a.tol) empty = 1;
-            for (int k = 0; k <= nt; ++k) out[k] = 0.0;
-            S.b[m_i + r] = INFINITY;
-            S.flag[m_i + r] = 2;
-        }
-    }
+    const int empty = ts_pull_back(S, a.ef, r0_j, m_j, nt, m_i, P, sh, a.tol);
     double r = -INFINITY;
     int status = TS_NO_EDGE;
     if (lane < TR_D) S.x[lane] = lane < nt ? a.xs[reg_i * nt + lane] : 0.0;

@@ -317,6 +317,17 @@ class Solution:
         from .transition import transition_graph
         return transition_graph(self, A, B, inputs, c=c, tol=tol, full_radius=full_radius, device=device)
 
+    def exit_sets(self, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0):
+        """Where each region's next state leaves the solution under the plant theta+ = A theta + B u + c with this controller's law
+        u = x*(theta)[inputs]: an exit_sets.ExitSets, the convex pieces of Chebyshev radius above tol of X_i = R_i minus the states whose
+        image lies in some region (pieces_of, contains, polytopes, volumes; whole[i]: region i leaves entirely).  The regions cut out of
+        R_i are its successors in ``graph``, the transition_graph of the same arguments (built when None); one device launch per round
+        of the region difference.  A run that is unbounded or capped keeps its piece and flags it wide: the pieces never lose a state
+        that exits.  Refusals as for transition_graph, and ValueError after a round that leaves a piece above 256 rows or more than
+        max_pieces pieces.  See exit_sets.py and DESIGN §3.21."""
+        from .exit_sets import exit_sets
+        return exit_sets(self, A, B, inputs, c=c, tol=tol, graph=graph, max_pieces=max_pieces, device=device)
+
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):
         """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial
