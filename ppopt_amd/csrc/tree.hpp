@@ -258,6 +258,7 @@ __device__ __forceinline__ long long loc_tree(const double (&th)[NT], int nt, in
         for (long long i = node_off[node]; i < node_off[node + 1]; ++i) {
             const long long r = items[i];
             if (!overlapping && found >= 0 && r >= found) break;   // ascending lists: nothing earlier is left in this leaf
+            if (row_off[r + 1] <= row_off[r]) continue;   // the scan walks rows: a region without rows is never met, here neither
             bool inside = true;
             for (long long k = row_off[r]; k < row_off[r + 1] && inside; ++k) inside = loc_row_inside<NT>(ef + k * nr, th, nt, tol, inclusive);
             if (!inside) continue;

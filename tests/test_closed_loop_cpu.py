@@ -1,6 +1,8 @@
 """Closed-loop simulation without a device: argument validation before any device call, the box disturbance against an
 independent Philox replay, the plant helpers against the programs' prediction matrices, the C ABI's stats struct, and the host reference
-loop on a hand-built 1-D piecewise-affine controller with a hand-computed trajectory."""
+loop on a hand-built 1-D piecewise-affine controller with a hand-computed trajectory.  The exact reference on stacked rows
+(closed_loop_reference.simulate_rows) is held against the same hand computation and against the host loop, and every case of
+tests/closed_loop_cases.py, which the device tests run, has to be exact and to exercise what it is there for."""
 import ctypes
 import os
 import subprocess
@@ -9,6 +11,7 @@ import tempfile
 import numpy
 import pytest
 
+import closed_loop_cases as cases
 import closed_loop_reference as ref
 import hit_and_run_reference as hr
 from ppopt_amd import _lib, closed_loop, problem_generator as pg
@@ -32,10 +35,18 @@ def _interval(lo, hi, slope, offset):
                           numpy.array([[-1.0], [1.0]]), numpy.array([[-lo], [hi]]), [])
 
 
-def pwa_1d():
+def pwa_1d(tol=1e-5):
     """u = 1 on [-2, -1], u = -theta / 2 on [-1, 1], u = -1 on [1, 2]"""
     regs = [_interval(-2.0, -1.0, 0.0, 1.0), _interval(-1.0, 1.0, -0.5, 0.0), _interval(1.0, 2.0, 0.0, -1.0)]
-    return Solution(_Prog(1), regs, point_location_tolerance=1e-5)
+    return Solution(_Prog(1), regs, point_location_tolerance=tol)
+
+
+def as_rows(sol):
+    """(row_off, ef, xlaw) of a Solution: rows [f | E], laws [b | A], in list order"""
+    regs = sol.critical_regions
+    off = numpy.cumsum([0] + [len(cr.E) for cr in regs])
+    ef = numpy.vstack([numpy.c_[cr.f.reshape(-1, 1), cr.E] for cr in regs])
+    return off, ef, numpy.array([numpy.c_[cr.b.reshape(-1, 1), cr.A] for cr in regs])
 
 
 def test_host_reference_gives_the_hand_computed_trajectory():
@@ -59,6 +70,95 @@ def test_host_reference_gives_the_hand_computed_trajectory():
     # c and w enter after the B terms
     cw = ref.simulate(sol, [[1.75]], 1, A, B, [0], c=[0.25], w=numpy.full((1, 1, 1), 0.125))
     assert cw['theta'][0, 1, 0] == 0.25 + 1.75 - 1.0 + 0.125
+
+
+def test_exact_reference_gives_the_hand_computed_trajectory():
+    """the trajectories of test_host_reference_gives_the_hand_computed_trajectory from the rows alone, with a lattice tolerance"""
+    row_off, ef, xlaw = as_rows(pwa_1d())
+    tol = 2.0 ** -10
+    A, B = [[1.0]], [[1.0]]
+    out = ref.simulate_rows(row_off, ef, xlaw, [[-2.0], [1.75], [2.5]], 4, A, B, [0], tol=tol)
+    numpy.testing.assert_array_equal(out['theta'][0, :, 0], [-2.0, -1.0, 0.0, 0.0, 0.0])
+    numpy.testing.assert_array_equal(out['region'][0], [0, 0, 1, 1])
+    numpy.testing.assert_array_equal(out['u'][0, :, 0], [1.0, 1.0, 0.0, 0.0])
+    numpy.testing.assert_array_equal(out['theta'][1, :, 0], [1.75, 0.75, 0.375, 0.1875, 0.09375])
+    numpy.testing.assert_array_equal(out['region'][1], [2, 1, 1, 1])
+    assert out['status'].tolist() == [0, 0, 2] and out['exit_step'].tolist() == [4, 4, 0]
+    assert out['theta'][2, 0, 0] == 2.5 and numpy.isnan(out['theta'][2, 1:]).all() and (out['region'][2] == -1).all()
+    assert numpy.isnan(out['u'][2]).all()
+    assert out['traj_steps'] == 4 + 4 + 1     # the step that finds no region counts
+    # 0.09375 = 3 / 32 is the finest number met: 3 / 32 against +-2 needs six bits, and the row tests with tol = 2^-10 eleven more
+    assert 6 <= out['bits'] <= 17
+    st = ref.simulate_rows(row_off, ef, xlaw, [[-2.0]], 6, A, B, [0], tol=tol, stop_tol=0.0)
+    assert st['status'].tolist() == [1] and st['exit_step'].tolist() == [3] and st['traj_steps'] == 3
+    assert numpy.isnan(st['theta'][0, 4:]).all() and st['theta'][0, 3, 0] == 0.0
+    cw = ref.simulate_rows(row_off, ef, xlaw, [[1.75]], 1, A, B, [0], c=[0.25], w=numpy.full((1, 1, 1), 0.125), tol=tol)
+    assert cw['theta'][0, 1, 0] == 0.25 + 1.75 - 1.0 + 0.125
+    # exactly tol beyond the last row: outside by the strict rule, inside by the inclusive one; and a non-finite start
+    edge = ref.simulate_rows(row_off, ef, xlaw, [[2.0 + tol], [numpy.inf]], 1, A, B, [0], tol=tol)
+    assert edge['status'].tolist() == [2, 3] and edge['exit_step'].tolist() == [0, 0] and edge['traj_steps'] == 1
+    assert ref.simulate_rows(row_off, ef, xlaw, [[2.0 + tol]], 1, A, B, [0], tol=tol, inclusive=True)['region'].tolist() == [[2]]
+    # a number that is no float64 is refused, not rounded: 1 + 2^-60
+    with pytest.raises(AssertionError):
+        ref.simulate_rows(row_off, ef, xlaw, [[1.0]], 1, [[2.0 ** -60]], B, [0], c=[1.5], tol=tol)
+
+
+def test_exact_reference_agrees_with_the_host_loop():
+    """two regions of two parameters with a law in R^3, wrapped as rows: on lattice data the float64 loop rounds nothing either, so
+    the two references have to agree in every field, NaN tails included"""
+    tol = 2.0 ** -10
+    sol = _sol2(tol)
+    rng = numpy.random.default_rng(5)
+    n, steps = 60, 5
+    theta0 = ref.lattice_starts(rng, n, 2, tol, reach=1.25, edge=1.0)
+    A, B, c = numpy.array([[0.5, 0.25], [-0.25, 0.75]]), numpy.array([[0.25, 0.0, -0.5], [0.0, 0.5, 0.25]]), numpy.array([0.25, -0.5])
+    w = ref.lattice_disturbance(rng, n, steps, 2)
+    for kw in (dict(), dict(c=c), dict(w=w), dict(c=c, w=w, stop_tol=0.25)):
+        want = ref.simulate(sol, theta0, steps, A, B, [2, 0, 2], **kw)
+        got = ref.simulate_rows(*as_rows(sol), theta0, steps, A, B, [2, 0, 2], tol=tol, **kw)
+        for key in ('theta', 'u', 'region', 'status', 'exit_step'):
+            assert numpy.array_equal(got[key], want[key], equal_nan=True), (kw.keys(), key)
+        assert set(want['status']) >= {0, 2} and (want['region'] == 1).any() and (want['region'] == 0).any()
+    assert set(want['status']) == {0, 1, 2}
+
+
+def test_the_exact_cases_cover_every_width():
+    """both edges of every theta width with both input widths, every input count of the issue, every combination of c and w, a stop
+    tolerance at every theta width, n_x above n_u, and inputs that are neither sorted nor distinct"""
+    seen = {(cases.case(name)['n_t'], cases.case(name)['n_u']) for name in cases.WIDTH_CASES}
+    assert {n_t for n_t, _ in seen} == {1, 4, 5, 8, 9, 16} and {n_u for _, n_u in seen} == {1, 4, 5, 16}
+    width = lambda n_t: 4 if n_t <= 4 else 8 if n_t <= 8 else 16
+    assert {(width(n_t), n_u <= 4) for n_t, n_u in seen} == {(wd, small) for wd in (4, 8, 16) for small in (False, True)}
+    for n_t in (1, 4, 5, 8, 9, 16):
+        assert len({n_u for t, n_u in seen if t == n_t}) == 2
+    ks = [cases.case(name) for name in cases.WIDTH_CASES]
+    assert {(k['c'] is not None, k['w'] is not None) for k in ks} == {(a, b) for a in (False, True) for b in (False, True)}
+    assert {width(k['n_t']) for k in ks if k['stop_tol'] is not None} == {4, 8, 16}
+    for k in ks:
+        assert k['n_x'] in (17, 20) and k['n_x'] > k['n_u'] and len(k['inputs']) == k['n_u'] and max(k['inputs']) < k['n_x']
+        if k['n_u'] >= 2:
+            assert len(set(k['inputs'])) < k['n_u'] and k['inputs'] != sorted(k['inputs'])
+        # the two adjacency tables describe the same cells: ids across bits 63 / 64, and in words 2 and 3
+        m2, m4 = k['walk2'][0], k['walk4'][0]
+        assert m2.shape[1] == 2 and m4.shape[1] == 4 and m2[:, 0].any() and m2[:, 1].any() and m4[:, 2].any() and m4[:, 3].any()
+    assert {cases.case(name)['n_t'] for name in cases.RULES_CASES} == {4, 9}
+
+
+@pytest.mark.parametrize('name', cases.LATTICE_CASES)
+def test_every_exact_case_is_exact_and_exercises_the_kernel(name):
+    """conditions on the inputs, shown by the reference alone: the certificate (at most 53 bits), a fifth of the trajectories run every
+    step, five or more lose their region at a step >= 1, a steady end wherever a stop tolerance is set, the region changes in a
+    quarter of the consecutive step pairs, and in some block of 256 trajectories three different exit steps occur while another
+    trajectory runs on (the barrier-synchronised continuation of the scan)"""
+    k, out = cases.case(name), cases.expected(name)
+    q = cases.quality(out, k['steps'])
+    print(name, q)
+    assert q['bits'] <= 53
+    assert q['full'] >= 0.2 and q['lost_later'] >= 5 and q['lost_at_start'] >= 1 and q['changes'] >= 0.25 and q['staggered'] >= 3
+    assert (q['steady'] >= 1) == (k['stop_tol'] is not None)
+    assert q['regions'] >= 0.8 * sum(1 for r in range(len(k['row_off']) - 1) if k['row_off'][r + 1] > k['row_off'][r])
+    if k['flags'].get('overlapping'):
+        assert k['steps'] >= 2
 
 
 def test_replay_step_is_the_documented_order():
@@ -137,14 +237,14 @@ def _no_device(monkeypatch):
     monkeypatch.setattr(Solution, 'locator', boom)
 
 
-def _sol2():
+def _sol2(tol=1e-5):
     """two regions of two parameters, law x in R^3"""
     regs = []
     for s in (1.0, -1.0):
         E = numpy.array([[s, 0.0], [0.0, 1.0], [0.0, -1.0], [-s, 0.0]])
         regs.append(CriticalRegion(numpy.ones((3, 2)), numpy.zeros((3, 1)), numpy.zeros((0, 2)), numpy.zeros((0, 1)), E,
                                    numpy.array([[1.0], [1.0], [1.0], [0.0]]), []))
-    return Solution(_Prog(2), regs, point_location_tolerance=1e-5)
+    return Solution(_Prog(2), regs, point_location_tolerance=tol)
 
 
 BAD = [
