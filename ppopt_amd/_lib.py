@@ -1246,19 +1246,41 @@ def _merge_rows(who, row_off, ef_rows):
     return off, ef
 
 
+_PTR = {numpy.dtype(numpy.float64): _dp, numpy.dtype(numpy.int64): _lp, numpy.dtype(numpy.int32): _ip, numpy.dtype(numpy.uint64): _u64p}
+
+
+def _ptr(a):
+    """the ctypes pointer of an array by its dtype; None (an optional array left out) stays None"""
+    return None if a is None else a.ctypes.data_as(_PTR[a.dtype])
+
+
+def _index_arrays(who, names, *arrays):
+    """int32 index vectors of one length; ``names`` words the refusal"""
+    out = [numpy.ascontiguousarray(a, dtype=numpy.int32).reshape(-1) for a in arrays]
+    if any(a.shape != out[0].shape for a in out):
+        raise MpcError(f'{who}: {names} must have the same length')
+    return out
+
+
+def _geometry_call(name, keys, *args):
+    """One call of the merge / overlap / transition / exit family: L.<name>(*args, stats, ms), arrays (and None) passed as pointers.
+    The stats dict, the counters under ``keys`` and the device time under 'ms'; MpcError with the library's message when it refuses."""
+    L = load()
+    st, ms = numpy.zeros(len(keys), dtype=numpy.int64), ctypes.c_float(0.0)
+    rc = getattr(L, name)(*[_ptr(a) if a is None or isinstance(a, numpy.ndarray) else a for a in args], _ptr(st), ctypes.byref(ms))
+    if rc != MPC_OK:
+        raise MpcError(f'{name} failed ({rc}): {L.mpc_last_error(None).decode()}')
+    return dict({k: int(v) for k, v in zip(keys, st)}, ms=float(ms.value))
+
+
 def merge_regions(row_off, ef_rows, device: int = 0):
     """(xs [R, n_t] a feasible point, box [R, 2, n_t] lower / upper bounds, status [R] (1: empty), stats) of every region of unit rows
     ef_rows = [o | n] (include/mpcombi.h, mpc_merge_regions).  The limits are checked by the library before any launch (MpcError)."""
     off, ef = _merge_rows('merge_regions', row_off, ef_rows)
     n_t, R = ef.shape[1] - 1, len(off) - 1
-    L = load()
     xs, box, status = numpy.zeros((R, n_t)), numpy.zeros((R, 2, n_t)), numpy.zeros(R, dtype=numpy.int32)
-    st, ms = numpy.zeros(3, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_merge_regions(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), xs.ctypes.data_as(_dp), box.ctypes.data_as(_dp),
-                             status.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_merge_regions failed ({rc}): {L.mpc_last_global_error().decode()}')
-    return xs, box, status, {'lps': int(st[0]), 'pivots': int(st[1]), 'capped': int(st[2]), 'ms': float(ms.value)}
+    stats = _geometry_call('mpc_merge_regions', ('lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, xs, box, status)
+    return xs, box, status, stats
 
 
 def merge_pairs(row_off, ef_rows, xs, box, pair_a, pair_b, tol: float, device: int = 0):
@@ -1268,22 +1290,13 @@ def merge_pairs(row_off, ef_rows, xs, box, pair_a, pair_b, tol: float, device: i
     n_t, R = ef.shape[1] - 1, len(off) - 1
     x = _f64(numpy.asarray(xs, dtype=numpy.float64)).reshape(R, n_t)
     bx = _f64(numpy.asarray(box, dtype=numpy.float64)).reshape(R, 2, n_t)
-    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
-    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
-    if pa.shape != pb.shape:
-        raise MpcError('merge_pairs: pair_a and pair_b must have the same length')
+    pa, pb = _index_arrays('merge_pairs', 'pair_a and pair_b', pair_a, pair_b)
     n = len(pa)
-    L = load()
     env_a, env_b = numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
     verdict, t_max = numpy.zeros(n, dtype=numpy.int32), numpy.zeros(n)
-    st, ms = numpy.zeros(7, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_merge_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), x.ctypes.data_as(_dp), bx.ctypes.data_as(_dp), n,
-                           pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), float(tol), env_a.ctypes.data_as(_u64p), env_b.ctypes.data_as(_u64p),
-                           verdict.ctypes.data_as(_ip), t_max.ctypes.data_as(_dp), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_merge_pairs failed ({rc}): {L.mpc_last_global_error().decode()}')
-    names = ('pairs', 'box_pairs', 'rows', 'box_rows', 'lps', 'pivots', 'capped')
-    return env_a, env_b, verdict, t_max, dict({k: int(v) for k, v in zip(names, st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_merge_pairs', ('pairs', 'box_pairs', 'rows', 'box_rows', 'lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, x, bx,
+                           n, pa, pb, float(tol), env_a, env_b, verdict, t_max)
+    return env_a, env_b, verdict, t_max, stats
 
 
 OVERLAP_MEETS, OVERLAP_CUT_ROW, OVERLAP_WIDE = 1, 2, 4   # flag bits of mpc_overlap_split (include/mpcombi.h)
@@ -1301,54 +1314,44 @@ def _cut_rows(who, n, n_t, has_cut, cut_rows):
     return hc, cut
 
 
+def _pieces(who, row_off, ef_rows, piece_off, piece_rows):
+    """the regions and the pieces of a split call: (off, ef, poff, pef, n_t)"""
+    off, ef = _merge_rows(who, row_off, ef_rows)
+    poff, pef = _merge_rows(who, piece_off, piece_rows)
+    if pef.shape[1] != ef.shape[1]:
+        raise MpcError(f'{who}: regions and pieces must have the same n_t')
+    return off, ef, poff, pef, ef.shape[1] - 1
+
+
+_SPLIT_KEYS = ('items', 'meets', 'lps', 'pivots', 'wide')
+
+
 def overlap_pairs(row_off, ef_rows, xs, pair_a, pair_b, has_cut, cut_rows, tol: float, device: int = 0):
     """The pair stage of the overlap removal (include/mpcombi.h, mpc_overlap_pairs): (radius [n_pairs], d_min, d_max, flag int32, stats)."""
     off, ef = _merge_rows('overlap_pairs', row_off, ef_rows)
     n_t, R = ef.shape[1] - 1, len(off) - 1
     x = _f64(numpy.asarray(xs, dtype=numpy.float64)).reshape(R, n_t)
-    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
-    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
-    if pa.shape != pb.shape:
-        raise MpcError('overlap_pairs: pair_a and pair_b must have the same length')
+    pa, pb = _index_arrays('overlap_pairs', 'pair_a and pair_b', pair_a, pair_b)
     n = len(pa)
     hc, cut = _cut_rows('overlap_pairs', n, n_t, has_cut, cut_rows)
-    L = load()
     radius, d_min, d_max, flag = numpy.zeros(n), numpy.zeros(n), numpy.zeros(n), numpy.zeros(n, dtype=numpy.int32)
-    st, ms = numpy.zeros(4, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_overlap_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), x.ctypes.data_as(_dp), n,
-                             pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), hc.ctypes.data_as(_ip),
-                             None if cut is None else cut.ctypes.data_as(_dp), float(tol), radius.ctypes.data_as(_dp),
-                             d_min.ctypes.data_as(_dp), d_max.ctypes.data_as(_dp), flag.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_overlap_pairs failed ({rc}): {L.mpc_last_error(None).decode()}')
-    return radius, d_min, d_max, flag, dict({k: int(v) for k, v in zip(('pairs', 'lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_overlap_pairs', ('pairs', 'lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, x, n, pa, pb, hc, cut, float(tol),
+                           radius, d_min, d_max, flag)
+    return radius, d_min, d_max, flag, stats
 
 
 def overlap_split(row_off, ef_rows, piece_off, piece_rows, item_piece, item_cutter, has_cut, cut_rows, start, tol: float, device: int = 0):
     """One round of the region difference (include/mpcombi.h, mpc_overlap_split): (flag [n_items] int32, mask [n_items, MERGE_WORDS]
     uint64, stats)."""
-    off, ef = _merge_rows('overlap_split', row_off, ef_rows)
-    poff, pef = _merge_rows('overlap_split', piece_off, piece_rows)
-    n_t, R, P = ef.shape[1] - 1, len(off) - 1, len(poff) - 1
-    if pef.shape[1] != n_t + 1:
-        raise MpcError('overlap_split: regions and pieces must have the same n_t')
-    ip = numpy.ascontiguousarray(item_piece, dtype=numpy.int32).reshape(-1)
-    ic = numpy.ascontiguousarray(item_cutter, dtype=numpy.int32).reshape(-1)
-    if ip.shape != ic.shape:
-        raise MpcError('overlap_split: item_piece and item_cutter must have the same length')
+    off, ef, poff, pef, n_t = _pieces('overlap_split', row_off, ef_rows, piece_off, piece_rows)
+    ip, ic = _index_arrays('overlap_split', 'item_piece and item_cutter', item_piece, item_cutter)
     n = len(ip)
     hc, cut = _cut_rows('overlap_split', n, n_t, has_cut, cut_rows)
     s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
-    L = load()
     flag, mask = numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
-    st, ms = numpy.zeros(5, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_overlap_split(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P, poff.ctypes.data_as(_lp),
-                             pef.ctypes.data_as(_dp), n, ip.ctypes.data_as(_ip), ic.ctypes.data_as(_ip), hc.ctypes.data_as(_ip),
-                             None if cut is None else cut.ctypes.data_as(_dp), None if s0 is None else s0.ctypes.data_as(_dp), float(tol),
-                             flag.ctypes.data_as(_ip), mask.ctypes.data_as(_u64p), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_overlap_split failed ({rc}): {L.mpc_last_error(None).decode()}')
-    return flag, mask, dict({k: int(v) for k, v in zip(('items', 'meets', 'lps', 'pivots', 'wide'), st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_overlap_split', _SPLIT_KEYS, int(device), n_t, len(off) - 1, off, ef, len(poff) - 1, poff, pef, n, ip, ic, hc, cut, s0,
+                           float(tol), flag, mask)
+    return flag, mask, stats
 
 
 TRANSITION_NO_EDGE, TRANSITION_EDGE, TRANSITION_UNBOUNDED, TRANSITION_UNDECIDED = range(4)   # status of mpc_transition_pairs (include/mpcombi.h)
@@ -1369,14 +1372,9 @@ def transition_boxes(row_off, ef_rows, Phi, phi, xs, device: int = 0):
     off, ef = _merge_rows('transition_boxes', row_off, ef_rows)
     n_t, R = ef.shape[1] - 1, len(off) - 1
     P, p, x = _transition_maps('transition_boxes', R, n_t, Phi, phi, xs)
-    L = load()
     box, flag = numpy.zeros((R, 2, n_t)), numpy.zeros(R, dtype=numpy.int32)
-    st, ms = numpy.zeros(3, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_transition_boxes(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P.ctypes.data_as(_dp), p.ctypes.data_as(_dp),
-                                x.ctypes.data_as(_dp), box.ctypes.data_as(_dp), flag.ctypes.data_as(_ip), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_transition_boxes failed ({rc}): {L.mpc_last_error(None).decode()}')
-    return box, flag, dict({k: int(v) for k, v in zip(('lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_transition_boxes', ('lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, P, p, x, box, flag)
+    return box, flag, stats
 
 
 def transition_pairs(row_off, ef_rows, Phi, phi, xs, pair_a, pair_b, full_radius: bool, tol: float, device: int = 0):
@@ -1385,52 +1383,30 @@ def transition_pairs(row_off, ef_rows, Phi, phi, xs, pair_a, pair_b, full_radius
     off, ef = _merge_rows('transition_pairs', row_off, ef_rows)
     n_t, R = ef.shape[1] - 1, len(off) - 1
     P, p, x = _transition_maps('transition_pairs', R, n_t, Phi, phi, xs)
-    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int32).reshape(-1)
-    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int32).reshape(-1)
-    if pa.shape != pb.shape:
-        raise MpcError('transition_pairs: pair_a and pair_b must have the same length')
+    pa, pb = _index_arrays('transition_pairs', 'pair_a and pair_b', pair_a, pair_b)
     n = len(pa)
-    L = load()
     radius, status, witness = numpy.zeros(n), numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, n_t))
-    st, ms = numpy.zeros(4, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_transition_pairs(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), P.ctypes.data_as(_dp), p.ctypes.data_as(_dp),
-                                x.ctypes.data_as(_dp), n, pa.ctypes.data_as(_ip), pb.ctypes.data_as(_ip), 1 if full_radius else 0, float(tol),
-                                radius.ctypes.data_as(_dp), status.ctypes.data_as(_ip), witness.ctypes.data_as(_dp), st.ctypes.data_as(_lp),
-                                ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_transition_pairs failed ({rc}): {L.mpc_last_error(None).decode()}')
-    return radius, status, witness, dict({k: int(v) for k, v in zip(('pairs', 'lps', 'pivots', 'capped'), st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_transition_pairs', ('pairs', 'lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, P, p, x, n, pa, pb,
+                           1 if full_radius else 0, float(tol), radius, status, witness)
+    return radius, status, witness, stats
 
 
 def exit_split(row_off, ef_rows, Phi, phi, piece_off, piece_rows, item_piece, item_source, item_target, start, tol: float, device: int = 0):
     """One round of the region difference against pulled-back cutters (include/mpcombi.h, mpc_exit_split): (flag [n_items] int32 with the
     bits OVERLAP_MEETS and OVERLAP_WIDE, mask [n_items, MERGE_WORDS] uint64, stats)."""
-    off, ef = _merge_rows('exit_split', row_off, ef_rows)
-    poff, pef = _merge_rows('exit_split', piece_off, piece_rows)
-    n_t, R, P = ef.shape[1] - 1, len(off) - 1, len(poff) - 1
-    if pef.shape[1] != n_t + 1:
-        raise MpcError('exit_split: regions and pieces must have the same n_t')
+    off, ef, poff, pef, n_t = _pieces('exit_split', row_off, ef_rows, piece_off, piece_rows)
+    R = len(off) - 1
     M = _f64(numpy.asarray(Phi, dtype=numpy.float64))
     p = _f64(numpy.asarray(phi, dtype=numpy.float64))
     if M.size != R * n_t * n_t or p.size != R * n_t:
         raise MpcError('exit_split: Phi must be [regions, n_t, n_t] and phi [regions, n_t]')
-    ip = numpy.ascontiguousarray(item_piece, dtype=numpy.int32).reshape(-1)
-    src = numpy.ascontiguousarray(item_source, dtype=numpy.int32).reshape(-1)
-    dst = numpy.ascontiguousarray(item_target, dtype=numpy.int32).reshape(-1)
-    if not (ip.shape == src.shape == dst.shape):
-        raise MpcError('exit_split: item_piece, item_source and item_target must have the same length')
+    ip, src, dst = _index_arrays('exit_split', 'item_piece, item_source and item_target', item_piece, item_source, item_target)
     n = len(ip)
     s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
-    L = load()
     flag, mask = numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, MERGE_WORDS), dtype=numpy.uint64)
-    st, ms = numpy.zeros(5, dtype=numpy.int64), ctypes.c_float(0.0)
-    rc = L.mpc_exit_split(int(device), n_t, R, off.ctypes.data_as(_lp), ef.ctypes.data_as(_dp), M.ctypes.data_as(_dp), p.ctypes.data_as(_dp), P,
-                          poff.ctypes.data_as(_lp), pef.ctypes.data_as(_dp), n, ip.ctypes.data_as(_ip), src.ctypes.data_as(_ip),
-                          dst.ctypes.data_as(_ip), None if s0 is None else s0.ctypes.data_as(_dp), float(tol), flag.ctypes.data_as(_ip),
-                          mask.ctypes.data_as(_u64p), st.ctypes.data_as(_lp), ctypes.byref(ms))
-    if rc != MPC_OK:
-        raise MpcError(f'mpc_exit_split failed ({rc}): {L.mpc_last_error(None).decode()}')
-    return flag, mask, dict({k: int(v) for k, v in zip(('items', 'meets', 'lps', 'pivots', 'wide'), st)}, ms=float(ms.value))
+    stats = _geometry_call('mpc_exit_split', _SPLIT_KEYS, int(device), n_t, R, off, ef, M, p, len(poff) - 1, poff, pef, n, ip, src, dst, s0, float(tol),
+                           flag, mask)
+    return flag, mask, stats
 
 
 class Locator:

@@ -9,11 +9,8 @@
 //   k_exit_split  LDS rows [0, m_P): P; [m_P, m_P + m_j): the pulled-back rows, a constant one as flag 2 with right-hand side +inf.
 //     empty cutter  a constant row with beta < -tol: C_ij is empty, P stays (flag 0, empty mask), no LP.
 //     intersection  radius(P n C), the run stops once t > tol.  Not above tol: P stays.
-//     row loop      in place.  Row k of the cutter is read from its own slot m_P + k (dropped rows are skipped) and written reversed
-//                   into slot m_P + n_cut, n_cut the number of rows that have cut so far (n_cut <= k: the slot never lies behind the one
-//                   just read, and the slots of the later rows are untouched).  P n {earlier cutting rows} n {reversed row k} has
-//                   radius > tol (the run stops there) iff row k cuts; the row is then turned forward in that slot and bounds every
-//                   later candidate.  A run that is unbounded or capped counts as "cuts".
+//     row loop      ov_difference (overlap.hpp), the one loop of the two difference kernels, in place over the slots [m_P, m_P + m_j):
+//                   dropped rows (flag 2) are skipped, every row of the target region has a mask bit.
 //     output        flag[item]: bit 0 P meets C, bit 2 some run was unbounded or capped (the bits of k_overlap_split; bit 1 is never set);
 //                   mask[item][OV_WORDS]: bit k, row k of the target region cuts.  The host assembles the child pieces from these alone.
 //   The only atomics are the counters; no floating-point atomics: a rerun gives the same bits.
@@ -41,7 +38,7 @@ struct ExitSplitArgs {
 __global__ void __launch_bounds__(64) k_exit_split(ExitSplitArgs a) {
     extern __shared__ double ex_smem[];
     __shared__ unsigned long long s_mask[OV_WORDS];
-    const int lane = threadIdx.x & 63, nt = a.nt, nr = nt + 1;
+    const int lane = threadIdx.x & 63, nt = a.nt;
     const long long q = blockIdx.x;
     if (q >= a.n_items) return;
     const TrLds S = tr_lds(ex_smem, a.m_max, nt);
@@ -60,40 +57,8 @@ __global__ void __launch_bounds__(64) k_exit_split(ExitSplitArgs a) {
         wide += st == TR_UNBOUNDED || st == TR_CAPPED;
         meets = !(st == TR_OPTIMAL && !(S.x[nt] > tol));
     }
-    if (meets) {
-        int n_cut = 0;
-        for (int k = 0; k < m_c; ++k) {
-            const int src = m_p + k, at = m_p + n_cut;
-            __syncthreads();
-            if (S.flag[src] == 2) continue;
-            const double v = lane < nt ? S.A[src * nr + lane] : 0.0, rhs = S.b[src];
-            __syncthreads();
-            if (lane < nt) S.A[at * nr + lane] = -v;
-            if (lane == 0) { S.A[at * nr + nt] = 1.0; S.b[at] = -rhs; S.flag[at] = 0; }
-            const int st = ov_radius(S, at + 1, nt, tol, pivots);
-            ++lps;
-            wide += st == TR_UNBOUNDED || st == TR_CAPPED;
-            if (st == TR_OPTIMAL && !(S.x[nt] > tol)) continue;
-            // row k cuts: it bounds every later candidate
-            __syncthreads();
-            if (lane < nt) S.A[at * nr + lane] = v;
-            if (lane == 0) {
-                S.b[at] = rhs;
-                s_mask[k >> 6] |= 1ull << (k & 63);
-            }
-            ++n_cut;
-        }
-    }
-    __syncthreads();
-    if (lane < OV_WORDS) a.mask[q * OV_WORDS + lane] = s_mask[lane];
-    if (lane == 0) {
-        a.flag[q] = (meets ? 1 : 0) | (wide ? 4 : 0);
-        atomicAdd(a.counters + 0, 1ull);
-        atomicAdd(a.counters + 1, meets ? 1ull : 0ull);
-        atomicAdd(a.counters + 2, lps);
-        atomicAdd(a.counters + 3, pivots);
-        atomicAdd(a.counters + 4, wide);
-    }
+    if (meets) ov_difference(S, m_p, m_c, m_c, nt, tol, pivots, lps, wide, s_mask);
+    ov_finish(q, meets, false, lps, pivots, wide, s_mask, a.flag, a.mask, a.counters);
 }
 
 }  // namespace mpc

@@ -28,6 +28,9 @@
 
 using namespace mpc;
 
+// the refusal of an entry point: MPC_ERR_INVALID with the message "<who>: <why>"
+static int bad(const char *who, const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); }
+
 // the two arrays every batch of polytopes starts with: row_off [n + 1] and the rows [row_off[n]][width]
 struct RegionsOnDevice { DevBuf &off, &ef; };
 static RegionsOnDevice upload_regions(OneShot &s, int64_t n, const int64_t *row_off, const double *rows, int width) {
@@ -424,31 +427,30 @@ static int tree_attach(mpc_locator *L, int32_t n_planes, const double *planes, i
 extern "C" int mpc_locator_set_tree(mpc_locator *L, int32_t n_planes, const double *planes, int64_t n_nodes, const int32_t *node_plane,
                                     const int32_t *node_child, const double *node_tau, const int64_t *node_off, const int32_t *items, double tol) {
     const char *who = "mpc_locator_set_tree";
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (!L) return bad("no locator");
-    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
-    if (n_nodes < 1 || !node_plane || !node_child || !node_tau || !node_off) return bad("missing node arrays");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (node_off[0] != 0) return bad("node_off[0] must be 0");
+    if (!L) return bad(who, "no locator");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad(who, "bad planes");
+    if (n_nodes < 1 || !node_plane || !node_child || !node_tau || !node_off) return bad(who, "missing node arrays");
+    if (!std::isfinite(tol) || tol < 0.0) return bad(who, "tol must be finite and >= 0");
+    if (node_off[0] != 0) return bad(who, "node_off[0] must be 0");
     const int nr = L->n_t + 1;
-    for (int64_t i = 0; i < (int64_t)n_planes * nr; ++i) if (!std::isfinite(planes[i])) return bad("planes must be finite");
+    for (int64_t i = 0; i < (int64_t)n_planes * nr; ++i) if (!std::isfinite(planes[i])) return bad(who, "planes must be finite");
     for (int64_t k = 0; k < n_nodes; ++k) {
-        if (node_off[k + 1] < node_off[k]) return bad("node_off decreases");
+        if (node_off[k + 1] < node_off[k]) return bad(who, "node_off decreases");
         const int32_t h = node_plane[k];
-        if (h < -1 || h >= n_planes) return bad("a node plane is out of range");
+        if (h < -1 || h >= n_planes) return bad(who, "a node plane is out of range");
         if (h >= 0) {
             for (int q = 0; q < 2; ++q) {
                 const int32_t ch = node_child[2 * k + q];
-                if (ch <= k || ch >= n_nodes) return bad("a child index is not after its parent or out of range");
-                if (!(node_tau[2 * k + q] >= 0.0)) return bad("tau must be >= 0");
+                if (ch <= k || ch >= n_nodes) return bad(who, "a child index is not after its parent or out of range");
+                if (!(node_tau[2 * k + q] >= 0.0)) return bad(who, "tau must be >= 0");
             }
         }
     }
-    if (node_off[n_nodes] > 0 && !items) return bad("missing items");
+    if (node_off[n_nodes] > 0 && !items) return bad(who, "missing items");
     for (int64_t k = 0; k < n_nodes; ++k)
         for (int64_t i = node_off[k]; i < node_off[k + 1]; ++i) {
-            if (items[i] < 0 || items[i] >= L->n_regions) return bad("a leaf item is not a region index");
-            if (i > node_off[k] && items[i] < items[i - 1]) return bad("a leaf list is not ascending");
+            if (items[i] < 0 || items[i] >= L->n_regions) return bad(who, "a leaf item is not a region index");
+            if (i > node_off[k] && items[i] < items[i - 1]) return bad(who, "a leaf list is not ascending");
         }
     HIP_TRY(nullptr, hipSetDevice(L->device));
     return tree_attach(L, n_planes, planes, n_nodes, node_plane, node_child, node_tau, node_off, items, tol);
@@ -476,33 +478,32 @@ extern "C" int mpc_tree_build(mpc_locator *L, int32_t n_planes, const double *pl
                               double band, int32_t leaf_size, int32_t max_depth, int64_t budget, mpc_tree_stats *stats) {
     const auto t_start = std::chrono::steady_clock::now();
     const char *who = "mpc_tree_build";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!L) return bad("no locator");
+    if (!L) return bad(who, "no locator");
     const int nt = L->n_t, nr = nt + 1;
     const long long R = L->n_regions;
-    if (nt < 1 || nt > TR_MAX_NT) return bad("n_t must lie in 1..16");
-    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad("bad planes");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (!std::isfinite(band) || band < 0.0) return bad("band must be finite and >= 0");
-    if (leaf_size < 1) return bad("leaf_size must be >= 1");
-    if (max_depth < 1 || max_depth > 64) return bad("max_depth must lie in 1..64");
-    if ((cand_off == nullptr) != (cand_plane == nullptr)) return bad("cand_off and cand_plane go together");
+    if (nt < 1 || nt > TR_MAX_NT) return bad(who, "n_t must lie in 1..16");
+    if (n_planes < 0 || (n_planes > 0 && !planes)) return bad(who, "bad planes");
+    if (!std::isfinite(tol) || tol < 0.0) return bad(who, "tol must be finite and >= 0");
+    if (!std::isfinite(band) || band < 0.0) return bad(who, "band must be finite and >= 0");
+    if (leaf_size < 1) return bad(who, "leaf_size must be >= 1");
+    if (max_depth < 1 || max_depth > 64) return bad(who, "max_depth must lie in 1..64");
+    if ((cand_off == nullptr) != (cand_plane == nullptr)) return bad(who, "cand_off and cand_plane go together");
     int m_max = 0;
     for (long long r = 0; r < R; ++r) {
         const long long k = L->h_row_off[(size_t)r + 1] - L->h_row_off[(size_t)r];
-        if (k > TR_MAX_ROWS) return bad("a region has more than 256 rows");
+        if (k > TR_MAX_ROWS) return bad(who, "a region has more than 256 rows");
         m_max = std::max<int>(m_max, (int)k);
     }
     for (int h = 0; h < n_planes; ++h) {
         double nn = 0.0;
         for (int t = 0; t < nt; ++t) nn += planes[(size_t)h * nr + t] * planes[(size_t)h * nr + t];
-        if (!std::isfinite(planes[(size_t)h * nr + nt]) || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("planes must be finite with unit normals");
+        if (!std::isfinite(planes[(size_t)h * nr + nt]) || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad(who, "planes must be finite with unit normals");
     }
     if (cand_off) {
-        if (cand_off[0] != 0) return bad("cand_off[0] must be 0");
-        for (long long r = 0; r < R; ++r) if (cand_off[r + 1] < cand_off[r]) return bad("cand_off decreases");
-        for (long long i = 0; i < cand_off[R]; ++i) if (cand_plane[i] < 0 || cand_plane[i] >= n_planes) return bad("a candidate plane is out of range");
+        if (cand_off[0] != 0) return bad(who, "cand_off[0] must be 0");
+        for (long long r = 0; r < R; ++r) if (cand_off[r + 1] < cand_off[r]) return bad(who, "cand_off decreases");
+        for (long long i = 0; i < cand_off[R]; ++i) if (cand_plane[i] < 0 || cand_plane[i] >= n_planes) return bad(who, "a candidate plane is out of range");
     }
     const int hw = (n_planes + 63) / 64;
     const long long limit = budget > 0 ? budget : TREE_DEFAULT_BUDGET;
@@ -510,7 +511,7 @@ extern "C" int mpc_tree_build(mpc_locator *L, int32_t n_planes, const double *pl
     if (bitset_bytes > limit) {
         char msg[200];
         snprintf(msg, sizeof msg, "the classification bitsets need %lld bytes, over the budget of %lld bytes", bitset_bytes, limit);
-        return bad(msg);
+        return bad(who, msg);
     }
     HIP_TRY(nullptr, hipSetDevice(L->device));
     hipStream_t st = L->stream;
@@ -710,42 +711,41 @@ extern "C" int mpc_locator_simulate(mpc_locator *L, int64_t n, int32_t steps, co
                                     const double *box_hi, uint64_t seed, double tol, double stop_tol, int32_t flags, int64_t budget,
                                     double *theta, double *u, int32_t *region, int32_t *status, int32_t *exit_step, mpc_sim_stats *stats) {
     const char *who = "mpc_locator_simulate";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!L) return bad("no locator");
+    if (!L) return bad(who, "no locator");
     const int nt = L->n_t, nx = L->n_x;
     const bool final_only = (flags & MPC_SIM_FINAL) != 0, tree = (flags & MPC_LOCATE_TREE) != 0, walk = (flags & MPC_LOCATE_WALK) != 0;
     const bool overlapping = (flags & MPC_LOCATE_OVERLAPPING) != 0, inclusive = (flags & MPC_LOCATE_INCLUSIVE) != 0;
-    if (n < 0 || n > (1ll << 40) || steps < 1 || steps > (1 << 30)) return bad("n must lie in 0..2^40 and steps in 1..2^30");
-    if (nt < 1 || nt > 16) return bad("n_theta must lie in 1..16");
-    if (n_u < 1 || n_u > 16) return bad("n_u must lie in 1..16");
-    if (L->n_regions < 1) return bad("the locator holds no region");
-    if (n > 0 && (!theta0 || !theta || !status || !exit_step)) return bad("missing theta0, theta, status or exit_step");
-    if (n > 0 && !final_only && (!u || !region)) return bad("a full record needs u and region");
-    if (!inputs || !A || !B) return bad("missing inputs, A or B");
+    if (n < 0 || n > (1ll << 40) || steps < 1 || steps > (1 << 30)) return bad(who, "n must lie in 0..2^40 and steps in 1..2^30");
+    if (nt < 1 || nt > 16) return bad(who, "n_theta must lie in 1..16");
+    if (n_u < 1 || n_u > 16) return bad(who, "n_u must lie in 1..16");
+    if (L->n_regions < 1) return bad(who, "the locator holds no region");
+    if (n > 0 && (!theta0 || !theta || !status || !exit_step)) return bad(who, "missing theta0, theta, status or exit_step");
+    if (n > 0 && !final_only && (!u || !region)) return bad(who, "a full record needs u and region");
+    if (!inputs || !A || !B) return bad(who, "missing inputs, A or B");
     for (int i = 0; i < n_u; ++i)
-        if (inputs[i] < 0 || inputs[i] >= nx) return bad("input index " + std::to_string(inputs[i]) + " is out of range (0 <= inputs < n_x = " + std::to_string(nx) + ")");
+        if (inputs[i] < 0 || inputs[i] >= nx) return bad(who, "input index " + std::to_string(inputs[i]) + " is out of range (0 <= inputs < n_x = " + std::to_string(nx) + ")");
     auto finite = [](const double *v, long long k) { for (long long i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false; return true; };
-    if (!finite(A, (long long)nt * nt) || !finite(B, (long long)nt * n_u) || (c && !finite(c, nt))) return bad("A, B and c must be finite");
-    if (n > 0 && !finite(theta0, n * nt)) return bad("theta0 must be finite");
-    if (w && (box_lo || box_hi)) return bad("a disturbance array and a box exclude each other");
-    if ((box_lo == nullptr) != (box_hi == nullptr)) return bad("box_lo and box_hi go together");
+    if (!finite(A, (long long)nt * nt) || !finite(B, (long long)nt * n_u) || (c && !finite(c, nt))) return bad(who, "A, B and c must be finite");
+    if (n > 0 && !finite(theta0, n * nt)) return bad(who, "theta0 must be finite");
+    if (w && (box_lo || box_hi)) return bad(who, "a disturbance array and a box exclude each other");
+    if ((box_lo == nullptr) != (box_hi == nullptr)) return bad(who, "box_lo and box_hi go together");
     if (box_lo)
         for (int t = 0; t < nt; ++t)
-            if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] <= box_hi[t])) return bad("the box must be finite with lo <= hi");
-    if (w && n > 0 && !finite(w, n * (long long)steps * nt)) return bad("the disturbance must be finite");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
-    if (std::isnan(stop_tol)) return bad("stop_tol must not be NaN (< 0: off)");
-    if (tree && walk) return bad("MPC_LOCATE_TREE and MPC_LOCATE_WALK exclude each other");
-    if (tree && !L->has_tree) return bad("MPC_LOCATE_TREE without an attached tree");
-    if (tree && !(tol <= L->tree_tol)) return bad("tol is larger than the tolerance the tree was built for");
-    if (walk && (!L->has_adj || overlapping || inclusive)) return bad("MPC_LOCATE_WALK needs adjacency, and neither MPC_LOCATE_OVERLAPPING nor MPC_LOCATE_INCLUSIVE");
+            if (!std::isfinite(box_lo[t]) || !std::isfinite(box_hi[t]) || !(box_lo[t] <= box_hi[t])) return bad(who, "the box must be finite with lo <= hi");
+    if (w && n > 0 && !finite(w, n * (long long)steps * nt)) return bad(who, "the disturbance must be finite");
+    if (!std::isfinite(tol) || tol < 0.0) return bad(who, "tol must be finite and >= 0");
+    if (std::isnan(stop_tol)) return bad(who, "stop_tol must not be NaN (< 0: off)");
+    if (tree && walk) return bad(who, "MPC_LOCATE_TREE and MPC_LOCATE_WALK exclude each other");
+    if (tree && !L->has_tree) return bad(who, "MPC_LOCATE_TREE without an attached tree");
+    if (tree && !(tol <= L->tree_tol)) return bad(who, "tol is larger than the tolerance the tree was built for");
+    if (walk && (!L->has_adj || overlapping || inclusive)) return bad(who, "MPC_LOCATE_WALK needs adjacency, and neither MPC_LOCATE_OVERLAPPING nor MPC_LOCATE_INCLUSIVE");
     // device bytes of the record and the inputs (doubles: no overflow for any n, steps that pass above)
     const double rec = final_only ? (double)n * nt * 8 : (double)n * ((double)(steps + 1) * nt * 8 + (double)steps * (n_u * 8 + 4));
     const double bytes = rec + (double)n * nt * 8 + (w ? (double)n * steps * nt * 8 : 0.0);
     const double cap = budget > 0 ? (double)budget : (double)SIM_DEFAULT_BUDGET;
     if (bytes > cap)
-        return bad("the run needs " + std::to_string((long long)bytes) + " device bytes, more than the budget of " + std::to_string((long long)cap) +
+        return bad(who, "the run needs " + std::to_string((long long)bytes) + " device bytes, more than the budget of " + std::to_string((long long)cap) +
                    " (record the final states only, or run fewer trajectories at a time)");
     if (n == 0) return MPC_OK;
     HIP_TRY(nullptr, hipSetDevice(L->device));
@@ -931,30 +931,29 @@ extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, 
                                    int64_t *n_vert, int64_t *n_ray, double *vertices, uint64_t *incidence, double *rays,
                                    mpc_vertex_stats *stats) {
     const char *who = "mpc_region_vertices";
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
-    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
-    if (!row_off || !v_cap || !r_cap) return bad("missing row_off, v_cap or r_cap");
-    if (row_off[0] != 0) return bad("row_off[0] must be 0");
+    if (n_t < 1 || n_t > 16) return bad(who, "n_theta must lie in 1..16");
+    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad(who, "n_poly must lie in 0..2^31-1");
+    if (!row_off || !v_cap || !r_cap) return bad(who, "missing row_off, v_cap or r_cap");
+    if (row_off[0] != 0) return bad(who, "row_off[0] must be 0");
     for (int64_t p = 0; p < n_poly; ++p) {
         const int64_t r = row_off[p + 1] - row_off[p];
-        if (r < 0) return bad("row_off decreases");
-        if (r > VX_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VX_MAX_ROWS));
+        if (r < 0) return bad(who, "row_off decreases");
+        if (r > VX_MAX_ROWS) return bad(who, "polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VX_MAX_ROWS));
     }
     const long long rows = row_off[n_poly];
-    if (rows && !ef_rows) return bad("missing ef_rows");
+    if (rows && !ef_rows) return bad(who, "missing ef_rows");
     for (long long i = 0; i < rows * (n_t + 1); ++i)
-        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+        if (!std::isfinite(ef_rows[i])) return bad(who, "the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
+    if (!std::isfinite(tol) || tol < 0.0) return bad(who, "tol must be finite and >= 0");
     const long long slab0 = slab > 0 ? slab : VX_DEFAULT_SLAB, smax = max_slab > 0 ? max_slab : VX_MAX_SLAB;
-    if (slab0 < 18 || slab0 > smax || smax > VX_MAX_SLAB) return bad("need 18 <= slab <= max_slab <= 2^24 generators");
+    if (slab0 < 18 || slab0 > smax || smax > VX_MAX_SLAB) return bad(who, "need 18 <= slab <= max_slab <= 2^24 generators");
     const double cap_bytes = budget > 0 ? (double)budget : (double)VX_DEFAULT_BUDGET;
     const double per = with_width(n_t, [&](auto W) { return vx_slab_bytes<decltype(W)::value>(slab0); });
     if (per > cap_bytes)
-        return bad("the budget of " + std::to_string((long long)cap_bytes) + " device bytes is too small for one polytope's slab (" +
+        return bad(who, "the budget of " + std::to_string((long long)cap_bytes) + " device bytes is too small for one polytope's slab (" +
                    std::to_string((long long)per) + " bytes)");
-    if (n_poly > 0 && (!status || !n_vert || !n_ray)) return bad("missing status, n_vert or n_ray");
+    if (n_poly > 0 && (!status || !n_vert || !n_ray)) return bad(who, "missing status, n_vert or n_ray");
     if (n_poly == 0) { *v_cap = 0; *r_cap = 0; return MPC_OK; }
     if (int rc = select_device(who, device)) return rc;
     std::vector<int32_t> st(n_poly, VX_OVERFLOW);
@@ -976,7 +975,7 @@ extern "C" int mpc_region_vertices(int32_t device, int32_t n_t, int64_t n_poly, 
     *v_cap = tv; *r_cap = tr;
     if (!fits) return fail(nullptr, MPC_ERR_CAPACITY, std::string(who) + ": the outputs need " + std::to_string(tv) + " vertices and " +
                                                             std::to_string(tr) + " rays (returned in v_cap, r_cap)");
-    if ((tv && (!vertices || !incidence)) || (tr && !rays)) return bad("missing vertices, incidence or rays");
+    if ((tv && (!vertices || !incidence)) || (tr && !rays)) return bad(who, "missing vertices, incidence or rays");
     long long pv = 0, pr = 0;
     for (int64_t p = 0; p < n_poly; ++p) {
         if (nv[p]) {
@@ -1101,37 +1100,36 @@ static int vol_entry(const char *who, bool want_m2, int32_t device, int32_t n_t,
                      const int64_t *vert_off, const double *vertices, const uint64_t *incidence, const int32_t *vx_status, double tol,
                      int64_t max_simplices, int64_t budget, double *volume, double *centroid, int64_t *n_simplices, int32_t *status,
                      double *second_moment, mpc_volume_stats *stats) {
-    auto bad = [&](const std::string &why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n_t < 1 || n_t > 16) return bad("n_theta must lie in 1..16");
-    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad("n_poly must lie in 0..2^31-1");
-    if (!row_off || !vert_off) return bad("missing row_off or vert_off");
-    if (row_off[0] != 0 || vert_off[0] != 0) return bad("row_off[0] and vert_off[0] must be 0");
-    if (max_simplices < 1) return bad("max_simplices must be >= 1");
-    if (!std::isfinite(tol) || tol < 0.0) return bad("tol must be finite and >= 0");
+    if (n_t < 1 || n_t > 16) return bad(who, "n_theta must lie in 1..16");
+    if (n_poly < 0 || n_poly > (1ll << 31) - 1) return bad(who, "n_poly must lie in 0..2^31-1");
+    if (!row_off || !vert_off) return bad(who, "missing row_off or vert_off");
+    if (row_off[0] != 0 || vert_off[0] != 0) return bad(who, "row_off[0] and vert_off[0] must be 0");
+    if (max_simplices < 1) return bad(who, "max_simplices must be >= 1");
+    if (!std::isfinite(tol) || tol < 0.0) return bad(who, "tol must be finite and >= 0");
     const long long limit = budget > 0 ? budget : VOL_DEFAULT_BUDGET;
     const long long ne = want_m2 ? (long long)n_t * (n_t + 1) / 2 : 0;
     for (int64_t p = 0; p < n_poly; ++p) {
         const int64_t r = row_off[p + 1] - row_off[p], v = vert_off[p + 1] - vert_off[p];
-        if (r < 0 || v < 0) return bad("row_off or vert_off decreases");
-        if (r > VOL_MAX_ROWS) return bad("polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VOL_MAX_ROWS));
+        if (r < 0 || v < 0) return bad(who, "row_off or vert_off decreases");
+        if (r > VOL_MAX_ROWS) return bad(who, "polytope " + std::to_string(p) + " has " + std::to_string(r) + " rows, more than " + std::to_string(VOL_MAX_ROWS));
         if (v <= VOL_MAX_VERTS && vol_poly_bytes(r, v, ne) > limit)
-            return bad("the budget of " + std::to_string(limit) + " device bytes is too small for polytope " + std::to_string(p) + " (" +
+            return bad(who, "the budget of " + std::to_string(limit) + " device bytes is too small for polytope " + std::to_string(p) + " (" +
                        std::to_string(vol_poly_bytes(r, v, ne)) + " bytes)");
     }
     const long long rows = row_off[n_poly], nv_all = vert_off[n_poly];
-    if ((rows && !ef_rows) || (nv_all && (!vertices || !incidence))) return bad("missing ef_rows, vertices or incidence");
+    if ((rows && !ef_rows) || (nv_all && (!vertices || !incidence))) return bad(who, "missing ef_rows, vertices or incidence");
     for (long long i = 0; i < rows * (n_t + 1); ++i)
-        if (!std::isfinite(ef_rows[i])) return bad("the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
+        if (!std::isfinite(ef_rows[i])) return bad(who, "the rows must be finite (row " + std::to_string(i / (n_t + 1)) + ")");
     for (long long i = 0; i < nv_all * n_t; ++i)
-        if (!std::isfinite(vertices[i])) return bad("the vertices must be finite (vertex " + std::to_string(i / n_t) + ")");
+        if (!std::isfinite(vertices[i])) return bad(who, "the vertices must be finite (vertex " + std::to_string(i / n_t) + ")");
     if (n_poly == 0) return MPC_OK;
-    if (!vx_status || !volume || !centroid || !n_simplices || !status || (want_m2 && !second_moment)) return bad("missing vx_status or an output array");
+    if (!vx_status || !volume || !centroid || !n_simplices || !status || (want_m2 && !second_moment)) return bad(who, "missing vx_status or an output array");
     const double nan = std::nan(""), inf = HUGE_VAL;
     std::vector<int32_t> todo;
     for (int64_t p = 0; p < n_poly; ++p) {
         const int32_t vs = vx_status[p];
-        if (vs < VOL_OK || vs > VOL_OVERFLOW) return bad("vx_status[" + std::to_string(p) + "] is not a status of mpc_region_vertices");
+        if (vs < VOL_OK || vs > VOL_OVERFLOW) return bad(who, "vx_status[" + std::to_string(p) + "] is not a status of mpc_region_vertices");
         const int64_t v = vert_off[p + 1] - vert_off[p];
         // what needs no walk: the statuses of the vertex pass, and a vertex list too long for the stack of a wave
         status[p] = vs != VOL_OK ? vs : v > VOL_MAX_VERTS ? VOL_TOO_LARGE : v < 1 || row_off[p + 1] == row_off[p] ? VOL_INCONSISTENT : VOL_OK;
@@ -1174,86 +1172,137 @@ extern "C" int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, c
                      budget, volume, centroid, n_simplices, status, second_moment, stats);
 }
 
-// ---- merging regions with equal laws (merge.hpp, DESIGN §3.14) ---------------------------------------------------------------------
-static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (n_t < 1 || n_t > TR_MAX_NT) return bad("n_t must lie in 1..16");
-    if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad("bad region count or missing row_off");
-    if (n_regions > 0x7fffffffll) return bad("too many regions for one launch");
-    if (n_regions > 0 && row_off[0] != 0) return bad("row_off[0] must be 0");
-    *m_max = 1;
-    for (int64_t r = 0; r < n_regions; ++r) {
-        const int64_t k = row_off[r + 1] - row_off[r];
-        if (k < 1 || k > MG_MAX_ROWS) return bad("every region needs 1..256 rows");
-        *m_max = std::max<int>(*m_max, (int)k);
-    }
-    const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
-    if (rows > 0 && !ef_rows) return bad("missing ef_rows");
-    for (int64_t i = 0; i < rows; ++i) {
-        const double *row = ef_rows + i * (n_t + 1);
+// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets ---------------------------
+// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp)  Every call checks its arguments in one order
+// (regions, pieces, tol, the item count, the dense arrays, the empty batch, missing arrays, the index arrays, the rest), uploads,
+// launches one wavefront per item over unit rows [o | n] in LDS, and downloads the results and its counters.  What the calls share is
+// here once: the checkers return the refusal, family_launch and family_close are the two ends of the device part.
+static void family_open(int64_t *stats, int n_stats, float *ms) {
+    if (stats) for (int i = 0; i < n_stats; ++i) stats[i] = 0;
+    if (ms) *ms = 0.0f;
+}
+
+static int check_tol(const char *who, double tol) { return std::isfinite(tol) && tol >= 0.0 ? (int)MPC_OK : bad(who, "tol must be finite and >= 0"); }
+
+// name: "n_pairs" or "n_items"
+static int check_count(const char *who, const char *name, int64_t n) {
+    return n >= 0 && n <= 0x7fffffffll ? (int)MPC_OK : bad(who, std::string(name) + " must lie in 0..2^31 - 1");
+}
+
+static int check_finite(const char *who, const char *name, const double *v, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return bad(who, std::string(name) + " must be finite");
+    return MPC_OK;
+}
+
+// the rows k of [n][n_t + 1] with only[k] != 0 (only == nullptr: all of them) are finite with unit normals
+static int check_unit_rows(const char *who, const char *what, int32_t n_t, int64_t n, const double *rows, const int32_t *only) {
+    for (int64_t k = 0; k < n; ++k) {
+        if (only && !only[k]) continue;
+        const double *row = rows + k * (n_t + 1);
         double nn = 0.0;
         bool finite = std::isfinite(row[0]);
         for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
-        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("rows must be finite with unit normals");
+        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad(who, std::string(what) + " must be finite with unit normals");
     }
     return MPC_OK;
+}
+
+// One index array of a call's items: item k names polytope v[k] of 0..n-1; off != nullptr: its rows off[v + 1] - off[v] lie in LDS.
+struct IndexArray { const int32_t *v; int64_t n; const int64_t *off; };
+// Refuses with ``why`` an item with an index out of range or, with ``distinct``, the same index in the first two arrays; raises *rows
+// to the largest sum over an item of the rows in LDS plus ``extra``.
+static int check_indices(const char *who, const char *why, int64_t n_items, std::initializer_list<IndexArray> arrays, bool distinct, int extra,
+                         int *rows) {
+    for (int64_t k = 0; k < n_items; ++k) {
+        int64_t sum = extra;
+        for (const IndexArray &a : arrays) {
+            const int64_t i = a.v[k];
+            if (i < 0 || i >= a.n) return bad(who, why);
+            if (a.off) sum += a.off[i + 1] - a.off[i];
+        }
+        if (distinct && arrays.begin()[0].v[k] == arrays.begin()[1].v[k]) return bad(who, why);
+        *rows = std::max<int>(*rows, (int)sum);
+    }
+    return MPC_OK;
+}
+
+// a zeroed buffer of n counters
+static DevBuf &family_counters(OneShot &s, int n) {
+    DevBuf &d_cnt = s.buf((size_t)n * 8);
+    s.fill(d_cnt, 0, (size_t)n * 8);
+    return d_cnt;
+}
+
+// kernel<<<n wavefronts, 64, lds>>>(args...) between the two events of s
+template <class K, class... A> static void family_launch(OneShot &s, K kernel, int64_t n, size_t lds, A... args) {
+    if (s.ok() && lds > 48 * 1024)
+        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    s.launch_timed([&] { hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(64), lds, nullptr, args...); });
+}
+
+// the n counters to stats, the device time to ms, and the call's code
+static int family_close(OneShot &s, const DevBuf &d_cnt, int n, int64_t *stats, float *ms) {
+    unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, (size_t)n * 8);
+    if (stats) for (int i = 0; i < n; ++i) stats[i] = (int64_t)cnt[i];
+    s.elapsed(ms);
+    return s.finish();
+}
+
+// ---- merging regions with equal laws (merge.hpp, DESIGN §3.14) ---------------------------------------------------------------------
+static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
+    if (n_t < 1 || n_t > TR_MAX_NT) return bad(who, "n_t must lie in 1..16");
+    if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad(who, "bad region count or missing row_off");
+    if (n_regions > 0x7fffffffll) return bad(who, "too many regions for one launch");
+    if (n_regions > 0 && row_off[0] != 0) return bad(who, "row_off[0] must be 0");
+    *m_max = 1;
+    for (int64_t r = 0; r < n_regions; ++r) {
+        const int64_t k = row_off[r + 1] - row_off[r];
+        if (k < 1 || k > MG_MAX_ROWS) return bad(who, "every region needs 1..256 rows");
+        *m_max = std::max<int>(*m_max, (int)k);
+    }
+    const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
+    if (rows > 0 && !ef_rows) return bad(who, "missing ef_rows");
+    return check_unit_rows(who, "rows", n_t, rows, ef_rows, nullptr);
 }
 
 extern "C" int mpc_merge_regions(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *xs,
                                  double *box, int32_t *status, int64_t *stats, float *ms) {
     const char *who = "mpc_merge_regions";
-    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 3, ms);
     int m_max = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
     if (n_regions == 0) return MPC_OK;
-    if (!xs || !box || !status) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_regions: missing output array");
+    if (!xs || !box || !status) return bad(who, "missing output array");
     if (int rc = select_device(nullptr, device)) return rc;
-    const size_t lds = tr_lds_bytes(m_max, n_t);
+    const size_t nr = (size_t)n_regions;
     OneShot s(who, nullptr, true);
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
-    DevBuf &d_xs = s.buf((size_t)n_regions * n_t * 8), &d_box = s.buf((size_t)n_regions * 2 * n_t * 8), &d_st = s.buf((size_t)n_regions * 4);
-    DevBuf &d_cnt = s.buf(3 * 8);
-    s.fill(d_cnt, 0, 3 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_regions), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        hipLaunchKernelGGL(k_merge_regions, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
-                           d.off.as<long long>(), d.ef.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_st.as<int32_t>(),
-                           d_cnt.as<unsigned long long>());
-    });
-    s.download(xs, d_xs, (size_t)n_regions * n_t * 8);
-    s.download(box, d_box, (size_t)n_regions * 2 * n_t * 8);
-    s.download(status, d_st, (size_t)n_regions * 4);
-    unsigned long long cnt[3] = {0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    DevBuf &d_xs = s.buf(nr * n_t * 8), &d_box = s.buf(nr * 2 * n_t * 8), &d_st = s.buf(nr * 4), &d_cnt = family_counters(s, 3);
+    family_launch(s, k_merge_regions, n_regions, tr_lds_bytes(m_max, n_t), (int)n_t, m_max, (long long)n_regions, d.off.as<long long>(),
+                  d.ef.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_st.as<int32_t>(), d_cnt.as<unsigned long long>());
+    s.download(xs, d_xs, nr * n_t * 8);
+    s.download(box, d_box, nr * 2 * n_t * 8);
+    s.download(status, d_st, nr * 4);
+    return family_close(s, d_cnt, 3, stats, ms);
 }
 
 extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
                                const double *box, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol, uint64_t *env_a,
                                uint64_t *env_b, int32_t *verdict, double *t_max, int64_t *stats, float *ms) {
     const char *who = "mpc_merge_pairs";
-    if (stats) for (int i = 0; i < 7; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 7, ms);
     int m_max = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: tol must be finite and >= 0");
-    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
     if (n_pairs == 0) return MPC_OK;
-    if (!xs || !box || !pair_a || !pair_b || !env_a || !env_b || !verdict || !t_max)
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: missing array");
+    if (!xs || !box || !pair_a || !pair_b || !env_a || !env_b || !verdict || !t_max) return bad(who, "missing array");
     int pair_rows = 2;
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t p = pair_a[k], q = pair_b[k];
-        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: a pair names a region out of range, or the same region twice");
-        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q] + 2));
-    }
-    for (int64_t i = 0; i < n_regions * n_t; ++i)
-        if (std::isnan(xs[i]) || std::isinf(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_merge_pairs: xs must be finite");
+    if (int rc = check_indices(who, "a pair names a region out of range, or the same region twice", n_pairs,
+                               {{pair_a, n_regions, row_off}, {pair_b, n_regions, row_off}}, true, 2, &pair_rows)) return rc;
+    if (int rc = check_finite(who, "xs", xs, n_regions * n_t)) return rc;
     if (int rc = select_device(nullptr, device)) return rc;
     const int lds_rows = std::max(pair_rows, m_max);
     const size_t lds = tr_lds_bytes(lds_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_env adds 64)
@@ -1262,69 +1311,45 @@ extern "C" int mpc_merge_pairs(int32_t device, int32_t n_t, int64_t n_regions, c
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_xs = s.upload(xs, (size_t)n_regions * n_t * 8), &d_box = s.upload(box, (size_t)n_regions * 2 * n_t * 8);
     DevBuf &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
-    DevBuf &d_ea = s.buf(words), &d_eb = s.buf(words), &d_v = s.buf(np * 4), &d_t = s.buf(np * 8), &d_cnt = s.buf(7 * 8);
-    s.fill(d_cnt, 0, 7 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_merge_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        MergePairArgs a{};
-        a.nt = n_t; a.m_max = lds_rows; a.n_pairs = n_pairs;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>(); a.box = d_box.as<double>();
-        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
-        a.env_a = d_ea.as<unsigned long long>(); a.env_b = d_eb.as<unsigned long long>(); a.verdict = d_v.as<int32_t>(); a.t_max = d_t.as<double>();
-        a.counters = d_cnt.as<unsigned long long>();
-        hipLaunchKernelGGL(k_merge_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
-    });
+    DevBuf &d_ea = s.buf(words), &d_eb = s.buf(words), &d_v = s.buf(np * 4), &d_t = s.buf(np * 8), &d_cnt = family_counters(s, 7);
+    MergePairArgs a{};
+    a.nt = n_t; a.m_max = lds_rows; a.n_pairs = n_pairs;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>(); a.box = d_box.as<double>();
+    a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+    a.env_a = d_ea.as<unsigned long long>(); a.env_b = d_eb.as<unsigned long long>(); a.verdict = d_v.as<int32_t>(); a.t_max = d_t.as<double>();
+    a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_merge_pairs, n_pairs, lds, a);
     s.download(env_a, d_ea, words);
     s.download(env_b, d_eb, words);
     s.download(verdict, d_v, np * 4);
     s.download(t_max, d_t, np * 8);
-    unsigned long long cnt[7] = {0, 0, 0, 0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 7; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 7, stats, ms);
 }
 
 // ---- overlap removal by lowest objective (overlap.hpp) --------------------------------------------------------------
 // has_cut [n] and the cut rows [n][n_t + 1] it selects: finite with unit normals
 static int overlap_check_cuts(const char *who, int32_t n_t, int64_t n, const int32_t *has_cut, const double *cut_rows) {
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
-    if (!has_cut) return bad("missing has_cut");
-    for (int64_t k = 0; k < n; ++k) {
-        if (!has_cut[k]) continue;
-        if (!cut_rows) return bad("missing cut_rows");
-        const double *row = cut_rows + k * (n_t + 1);
-        double nn = 0.0;
-        bool finite = std::isfinite(row[0]);
-        for (int t = 0; t < n_t; ++t) { nn += row[1 + t] * row[1 + t]; finite = finite && std::isfinite(row[1 + t]); }
-        if (!finite || !(std::fabs(std::sqrt(nn) - 1.0) <= 1e-6)) return bad("cut rows must be finite with unit normals");
-    }
-    return MPC_OK;
+    if (!has_cut) return bad(who, "missing has_cut");
+    if (cut_rows) return check_unit_rows(who, "cut rows", n_t, n, cut_rows, has_cut);
+    return std::any_of(has_cut, has_cut + n, [](int32_t h) { return h != 0; }) ? bad(who, "missing cut_rows") : (int)MPC_OK;
 }
 
 extern "C" int mpc_overlap_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *xs,
                                  int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, const int32_t *has_cut, const double *cut_rows,
                                  double tol, double *radius, double *d_min, double *d_max, int32_t *flag, int64_t *stats, float *ms) {
     const char *who = "mpc_overlap_pairs";
-    if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 4, ms);
     int m_max = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: tol must be finite and >= 0");
-    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: n_pairs must lie in 0..2^31 - 1");
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
     if (n_pairs == 0) return MPC_OK;
-    if (!xs || !pair_a || !pair_b || !radius || !d_min || !d_max || !flag) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: missing array");
+    if (!xs || !pair_a || !pair_b || !radius || !d_min || !d_max || !flag) return bad(who, "missing array");
     int pair_rows = 2;
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t p = pair_a[k], q = pair_b[k];
-        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions || p == q)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: a pair names a region out of range, or the same region twice");
-        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q]));
-    }
+    if (int rc = check_indices(who, "a pair names a region out of range, or the same region twice", n_pairs,
+                               {{pair_a, n_regions, row_off}, {pair_b, n_regions, row_off}}, true, 0, &pair_rows)) return rc;
     if (int rc = overlap_check_cuts(who, n_t, n_pairs, has_cut, cut_rows)) return rc;
-    for (int64_t i = 0; i < n_regions * n_t; ++i)
-        if (!std::isfinite(xs[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_pairs: xs must be finite");
+    if (int rc = check_finite(who, "xs", xs, n_regions * n_t)) return rc;
     if (int rc = select_device(nullptr, device)) return rc;
     const size_t lds = tr_lds_bytes(pair_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes
     const size_t np = (size_t)n_pairs;
@@ -1333,28 +1358,19 @@ extern "C" int mpc_overlap_pairs(int32_t device, int32_t n_t, int64_t n_regions,
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_xs = s.upload(xs, (size_t)n_regions * n_t * 8), &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
     DevBuf &d_hc = s.upload(has_cut, np * 4), &d_cut = cut_rows ? s.upload(cut_rows, np * (n_t + 1) * 8) : s.upload(&zero_row, 8);
-    DevBuf &d_r = s.buf(np * 8), &d_lo = s.buf(np * 8), &d_hi = s.buf(np * 8), &d_f = s.buf(np * 4), &d_cnt = s.buf(4 * 8);
-    s.fill(d_cnt, 0, 4 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_overlap_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        OverlapPairArgs a{};
-        a.nt = n_t; a.m_max = pair_rows; a.n_pairs = n_pairs;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>();
-        a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>(); a.tol = tol;
-        a.radius = d_r.as<double>(); a.d_min = d_lo.as<double>(); a.d_max = d_hi.as<double>(); a.flag = d_f.as<int32_t>();
-        a.counters = d_cnt.as<unsigned long long>();
-        hipLaunchKernelGGL(k_overlap_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
-    });
+    DevBuf &d_r = s.buf(np * 8), &d_lo = s.buf(np * 8), &d_hi = s.buf(np * 8), &d_f = s.buf(np * 4), &d_cnt = family_counters(s, 4);
+    OverlapPairArgs a{};
+    a.nt = n_t; a.m_max = pair_rows; a.n_pairs = n_pairs;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.xs = d_xs.as<double>();
+    a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>(); a.tol = tol;
+    a.radius = d_r.as<double>(); a.d_min = d_lo.as<double>(); a.d_max = d_hi.as<double>(); a.flag = d_f.as<int32_t>();
+    a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_overlap_pairs, n_pairs, lds, a);
     s.download(radius, d_r, np * 8);
     s.download(d_min, d_lo, np * 8);
     s.download(d_max, d_hi, np * 8);
     s.download(flag, d_f, np * 4);
-    unsigned long long cnt[4] = {0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 4; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 4, stats, ms);
 }
 
 extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int64_t n_pieces,
@@ -1362,26 +1378,20 @@ extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions,
                                  const int32_t *item_cutter, const int32_t *has_cut, const double *cut_rows, const double *start, double tol,
                                  int32_t *flag, uint64_t *mask, int64_t *stats, float *ms) {
     const char *who = "mpc_overlap_split";
-    if (stats) for (int i = 0; i < 5; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 5, ms);
     int m_reg = 1, m_piece = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
     if (int rc = merge_check("mpc_overlap_split (pieces)", n_t, n_pieces, piece_off, piece_rows, &m_piece)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: tol must be finite and >= 0");
-    if (n_items < 0 || n_items > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: n_items must lie in 0..2^31 - 1");
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_items", n_items)) return rc;
     if (n_items == 0) return MPC_OK;
-    if (!item_piece || !item_cutter || !flag || !mask) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: missing array");
+    if (!item_piece || !item_cutter || !flag || !mask) return bad(who, "missing array");
     int item_rows = 4;
-    for (int64_t k = 0; k < n_items; ++k) {
-        const int64_t p = item_piece[k], c = item_cutter[k];
-        if (p < 0 || p >= n_pieces || c < 0 || c >= n_regions)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: an item names a piece or a cutter out of range");
-        item_rows = std::max<int>(item_rows, (int)(piece_off[p + 1] - piece_off[p] + row_off[c + 1] - row_off[c] + 2));
-    }
+    if (int rc = check_indices(who, "an item names a piece or a cutter out of range", n_items,
+                               {{item_piece, n_pieces, piece_off}, {item_cutter, n_regions, row_off}}, false, 2, &item_rows)) return rc;
     if (int rc = overlap_check_cuts(who, n_t, n_items, has_cut, cut_rows)) return rc;
     if (start)
-        for (int64_t i = 0; i < n_items * n_t; ++i)
-            if (!std::isfinite(start[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_overlap_split: start must be finite");
+        if (int rc = check_finite(who, "start", start, n_items * n_t)) return rc;
     if (int rc = select_device(nullptr, device)) return rc;
     const size_t lds = tr_lds_bytes(item_rows, n_t);   // 514 rows at n_t = 16: 79,132 bytes (the static s_mask adds 32)
     const size_t ni = (size_t)n_items, words = ni * OV_WORDS * 8;
@@ -1392,94 +1402,69 @@ extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions,
     DevBuf &d_ip = s.upload(item_piece, ni * 4), &d_ic = s.upload(item_cutter, ni * 4), &d_hc = s.upload(has_cut, ni * 4);
     DevBuf &d_cut = cut_rows ? s.upload(cut_rows, ni * (n_t + 1) * 8) : s.upload(&zero_row, 8);
     DevBuf *d_start = start ? &s.upload(start, ni * n_t * 8) : nullptr;
-    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = s.buf(5 * 8);
-    s.fill(d_cnt, 0, 5 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_overlap_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        OverlapSplitArgs a{};
-        a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
-        a.item_piece = d_ip.as<int32_t>(); a.item_cutter = d_ic.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>();
-        a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
-        a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
-        hipLaunchKernelGGL(k_overlap_split, dim3((unsigned)n_items), dim3(64), lds, nullptr, a);
-    });
+    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = family_counters(s, 5);
+    OverlapSplitArgs a{};
+    a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
+    a.item_piece = d_ip.as<int32_t>(); a.item_cutter = d_ic.as<int32_t>(); a.has_cut = d_hc.as<int32_t>(); a.cut = d_cut.as<double>();
+    a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+    a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_overlap_split, n_items, lds, a);
     s.download(flag, d_f, ni * 4);
     s.download(mask, d_m, words);
-    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 5; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 5, stats, ms);
 }
 
 // ---- transition graph of a closed loop (transition.hpp) ---------------------------------------------------------------
-// Phi [n_regions][n_t][n_t], phi and xs [n_regions][n_t]: present and finite
-static int transition_check_maps(const char *who, int32_t n_t, int64_t n_regions, const double *Phi, const double *phi, const double *xs) {
-    auto bad = [&](const char *why) { return fail(nullptr, MPC_ERR_INVALID, std::string(who) + ": " + why); };
+// Phi [n_regions][n_t][n_t], phi and, with want_xs, xs [n_regions][n_t]: present and finite
+static int transition_check_maps(const char *who, int32_t n_t, int64_t n_regions, const double *Phi, const double *phi, bool want_xs,
+                                 const double *xs) {
     if (n_regions == 0) return MPC_OK;
-    if (!Phi || !phi || !xs) return bad("missing array (Phi, phi or xs)");
-    for (int64_t i = 0; i < n_regions * n_t * n_t; ++i)
-        if (!std::isfinite(Phi[i])) return bad("Phi must be finite");
-    for (int64_t i = 0; i < n_regions * n_t; ++i)
-        if (!std::isfinite(phi[i]) || !std::isfinite(xs[i])) return bad("phi and xs must be finite");
-    return MPC_OK;
+    if (!Phi || !phi || (want_xs && !xs)) return bad(who, want_xs ? "missing array (Phi, phi or xs)" : "missing array (Phi or phi)");
+    if (int rc = check_finite(who, "Phi", Phi, n_regions * n_t * n_t)) return rc;
+    const char *name = want_xs ? "phi and xs" : "phi";
+    if (int rc = check_finite(who, name, phi, n_regions * n_t)) return rc;
+    return want_xs ? check_finite(who, name, xs, n_regions * n_t) : (int)MPC_OK;
 }
 
 extern "C" int mpc_transition_boxes(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
                                     const double *phi, const double *xs, double *image_box, int32_t *flag, int64_t *stats, float *ms) {
     const char *who = "mpc_transition_boxes";
-    if (stats) for (int i = 0; i < 3; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 3, ms);
     int m_max = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, xs)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, true, xs)) return rc;
     if (n_regions == 0) return MPC_OK;
-    if (!image_box || !flag) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_boxes: missing output array");
+    if (!image_box || !flag) return bad(who, "missing output array");
     if (int rc = select_device(nullptr, device)) return rc;
-    const size_t lds = tr_lds_bytes(m_max, n_t), nr = (size_t)n_regions;
+    const size_t nr = (size_t)n_regions;
     OneShot s(who, nullptr, true);
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
-    DevBuf &d_box = s.buf(nr * 2 * n_t * 8), &d_f = s.buf(nr * 4), &d_cnt = s.buf(3 * 8);
-    s.fill(d_cnt, 0, 3 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_transition_boxes), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        hipLaunchKernelGGL(k_transition_boxes, dim3((unsigned)n_regions), dim3(64), lds, nullptr, (int)n_t, m_max, (long long)n_regions,
-                           d.off.as<long long>(), d.ef.as<double>(), d_Phi.as<double>(), d_phi.as<double>(), d_xs.as<double>(),
-                           d_box.as<double>(), d_f.as<int32_t>(), d_cnt.as<unsigned long long>());
-    });
+    DevBuf &d_box = s.buf(nr * 2 * n_t * 8), &d_f = s.buf(nr * 4), &d_cnt = family_counters(s, 3);
+    family_launch(s, k_transition_boxes, n_regions, tr_lds_bytes(m_max, n_t), (int)n_t, m_max, (long long)n_regions, d.off.as<long long>(),
+                  d.ef.as<double>(), d_Phi.as<double>(), d_phi.as<double>(), d_xs.as<double>(), d_box.as<double>(), d_f.as<int32_t>(),
+                  d_cnt.as<unsigned long long>());
     s.download(image_box, d_box, nr * 2 * n_t * 8);
     s.download(flag, d_f, nr * 4);
-    unsigned long long cnt[3] = {0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 3; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 3, stats, ms);
 }
 
 extern "C" int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
                                     const double *phi, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
                                     int32_t full_radius, double tol, double *radius, int32_t *status, double *witness, int64_t *stats, float *ms) {
     const char *who = "mpc_transition_pairs";
-    if (stats) for (int i = 0; i < 4; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 4, ms);
     int m_max = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: tol must be finite and >= 0");
-    if (n_pairs < 0 || n_pairs > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: n_pairs must lie in 0..2^31 - 1");
-    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, xs)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, true, xs)) return rc;
     if (n_pairs == 0) return MPC_OK;
-    if (!pair_a || !pair_b || !radius || !status || !witness) return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: missing array");
-    int pair_rows = 2;
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const int64_t p = pair_a[k], q = pair_b[k];     // p == q is a self loop
-        if (p < 0 || q < 0 || p >= n_regions || q >= n_regions)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_transition_pairs: a pair names a region out of range");
-        pair_rows = std::max<int>(pair_rows, (int)(row_off[p + 1] - row_off[p] + row_off[q + 1] - row_off[q]));
-    }
+    if (!pair_a || !pair_b || !radius || !status || !witness) return bad(who, "missing array");
+    int pair_rows = 2;     // p == q is a self loop
+    if (int rc = check_indices(who, "a pair names a region out of range", n_pairs, {{pair_a, n_regions, row_off}, {pair_b, n_regions, row_off}}, false,
+                               0, &pair_rows)) return rc;
     if (int rc = select_device(nullptr, device)) return rc;
     const size_t lds = tr_lds_bytes(pair_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes
     const size_t np = (size_t)n_pairs, nr = (size_t)n_regions;
@@ -1487,27 +1472,18 @@ extern "C" int mpc_transition_pairs(int32_t device, int32_t n_t, int64_t n_regio
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
     DevBuf &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
-    DevBuf &d_r = s.buf(np * 8), &d_st = s.buf(np * 4), &d_w = s.buf(np * n_t * 8), &d_cnt = s.buf(4 * 8);
-    s.fill(d_cnt, 0, 4 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_transition_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        TransitionPairArgs a{};
-        a.nt = n_t; a.m_max = pair_rows; a.full_radius = full_radius ? 1 : 0; a.n_pairs = n_pairs;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
-        a.xs = d_xs.as<double>(); a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
-        a.radius = d_r.as<double>(); a.witness = d_w.as<double>(); a.status = d_st.as<int32_t>();
-        a.counters = d_cnt.as<unsigned long long>();
-        hipLaunchKernelGGL(k_transition_pairs, dim3((unsigned)n_pairs), dim3(64), lds, nullptr, a);
-    });
+    DevBuf &d_r = s.buf(np * 8), &d_st = s.buf(np * 4), &d_w = s.buf(np * n_t * 8), &d_cnt = family_counters(s, 4);
+    TransitionPairArgs a{};
+    a.nt = n_t; a.m_max = pair_rows; a.full_radius = full_radius ? 1 : 0; a.n_pairs = n_pairs;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
+    a.xs = d_xs.as<double>(); a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+    a.radius = d_r.as<double>(); a.witness = d_w.as<double>(); a.status = d_st.as<int32_t>();
+    a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_transition_pairs, n_pairs, lds, a);
     s.download(radius, d_r, np * 8);
     s.download(status, d_st, np * 4);
     s.download(witness, d_w, np * n_t * 8);
-    unsigned long long cnt[4] = {0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 4; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 4, stats, ms);
 }
 
 // ---- exit sets of a closed loop (exit_sets.hpp) -------------------------------------------------------------------------
@@ -1516,32 +1492,21 @@ extern "C" int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, co
                               const int32_t *item_piece, const int32_t *item_source, const int32_t *item_target, const double *start, double tol,
                               int32_t *flag, uint64_t *mask, int64_t *stats, float *ms) {
     const char *who = "mpc_exit_split";
-    if (stats) for (int i = 0; i < 5; ++i) stats[i] = 0;
-    if (ms) *ms = 0.0f;
+    family_open(stats, 5, ms);
     int m_reg = 1, m_piece = 1;
     if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
     if (int rc = merge_check("mpc_exit_split (pieces)", n_t, n_pieces, piece_off, piece_rows, &m_piece)) return rc;
-    if (!std::isfinite(tol) || tol < 0.0) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: tol must be finite and >= 0");
-    if (n_items < 0 || n_items > 0x7fffffffll) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: n_items must lie in 0..2^31 - 1");
-    if (n_regions > 0) {
-        if (!Phi || !phi) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: missing array (Phi or phi)");
-        for (int64_t i = 0; i < n_regions * n_t * n_t; ++i)
-            if (!std::isfinite(Phi[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: Phi must be finite");
-        for (int64_t i = 0; i < n_regions * n_t; ++i)
-            if (!std::isfinite(phi[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: phi must be finite");
-    }
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_items", n_items)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, false, nullptr)) return rc;
     if (n_items == 0) return MPC_OK;
-    if (!item_piece || !item_source || !item_target || !flag || !mask) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: missing array");
-    int item_rows = 4;
-    for (int64_t k = 0; k < n_items; ++k) {
-        const int64_t p = item_piece[k], i = item_source[k], j = item_target[k];     // i == j: the piece minus the part that stays in its region
-        if (p < 0 || p >= n_pieces || i < 0 || i >= n_regions || j < 0 || j >= n_regions)
-            return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: an item names a piece or a region out of range");
-        item_rows = std::max<int>(item_rows, (int)(piece_off[p + 1] - piece_off[p] + row_off[j + 1] - row_off[j]));
-    }
+    if (!item_piece || !item_source || !item_target || !flag || !mask) return bad(who, "missing array");
+    int item_rows = 4;     // source == target: the piece minus the part that stays in its region
+    if (int rc = check_indices(who, "an item names a piece or a region out of range", n_items,
+                               {{item_piece, n_pieces, piece_off}, {item_source, n_regions, nullptr}, {item_target, n_regions, row_off}}, false, 0,
+                               &item_rows)) return rc;
     if (start)
-        for (int64_t i = 0; i < n_items * n_t; ++i)
-            if (!std::isfinite(start[i])) return fail(nullptr, MPC_ERR_INVALID, "mpc_exit_split: start must be finite");
+        if (int rc = check_finite(who, "start", start, n_items * n_t)) return rc;
     if (int rc = select_device(nullptr, device)) return rc;
     const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_mask adds 32)
     const size_t ni = (size_t)n_items, nr = (size_t)n_regions, words = ni * OV_WORDS * 8;
@@ -1551,25 +1516,16 @@ extern "C" int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, co
     DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8);
     DevBuf &d_ip = s.upload(item_piece, ni * 4), &d_is = s.upload(item_source, ni * 4), &d_it = s.upload(item_target, ni * 4);
     DevBuf *d_start = start ? &s.upload(start, ni * n_t * 8) : nullptr;
-    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = s.buf(5 * 8);
-    s.fill(d_cnt, 0, 5 * 8);
-    if (s.ok() && lds > 48 * 1024)
-        s.chk(hipFuncSetAttribute(reinterpret_cast<const void *>(k_exit_split), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    s.launch_timed([&] {
-        ExitSplitArgs a{};
-        a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
-        a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
-        a.item_piece = d_ip.as<int32_t>(); a.item_source = d_is.as<int32_t>(); a.item_target = d_it.as<int32_t>();
-        a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
-        a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
-        hipLaunchKernelGGL(k_exit_split, dim3((unsigned)n_items), dim3(64), lds, nullptr, a);
-    });
+    DevBuf &d_f = s.buf(ni * 4), &d_m = s.buf(words), &d_cnt = family_counters(s, 5);
+    ExitSplitArgs a{};
+    a.nt = n_t; a.m_max = item_rows; a.n_items = n_items;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.piece_off = pc.off.as<long long>(); a.piece_ef = pc.ef.as<double>();
+    a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>();
+    a.item_piece = d_ip.as<int32_t>(); a.item_source = d_is.as<int32_t>(); a.item_target = d_it.as<int32_t>();
+    a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+    a.flag = d_f.as<int32_t>(); a.mask = d_m.as<unsigned long long>(); a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_exit_split, n_items, lds, a);
     s.download(flag, d_f, ni * 4);
     s.download(mask, d_m, words);
-    unsigned long long cnt[5] = {0, 0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (stats) for (int i = 0; i < 5; ++i) stats[i] = (int64_t)cnt[i];
-    s.elapsed(ms);
-    return s.finish();
+    return family_close(s, d_cnt, 5, stats, ms);
 }

@@ -9,13 +9,20 @@
 //                   and, when r > tol and the pair has a cut row [o | n] (the unit row of {J_j <= J_i}), d_min and d_max over the
 //                   intersection of the depth d(theta) = o - n.theta = (J_i - J_j) / |g| behind the cut plane, from the Chebyshev
 //                   centre with a warm start between the two.  flag[pair] = 1: a run was unbounded or stopped at the pivot cap.
-//   k_overlap_split one wavefront per (piece P, cutter C): C = the rows of a region, then the item's cut row if it has one.
+//   k_overlap_split one wavefront per (piece P, cutter C): C = the rows of a region, then the item's cut row if it has one.  LDS rows
+//                   [0, m_P): P; [m_P, m_P + m_C): the region's rows; m_P + m_C: the cut row.
 //     intersection  radius(P n C), the run stops once t > tol.  Not above tol: P stays (flag bit 0 clear, empty mask).
-//     row loop      for the rows c_k of C in order: P n {earlier cutting rows} n {n_k.theta >= o_k} has radius > tol (the run stops
-//                   there) iff row k cuts; the row then joins the LDS rows of the later candidates.  A run that is unbounded or
-//                   capped counts as "cuts" (an empty child is found empty later; a dropped one would lose area).
-//     output        flag[item]: bit 0 P meets C, bit 1 the cut row cuts, bit 2 some run was unbounded or capped; mask[item][OV_WORDS]:
-//                   bit k, row k of the cutter's region cuts.  The host assembles the child pieces from these alone.
+//     row loop      ov_difference, the one loop of the two difference kernels (k_exit_split of exit_sets.hpp is the other), in place.
+//                   Row k of the cutter is read from its own slot m_P + k (a slot with flag 2, a row k_exit_split dropped, is skipped)
+//                   and written reversed into slot m_P + n_cut, n_cut the number of rows that have cut so far.  P n {earlier cutting
+//                   rows} n {n_k.theta >= o_k} has radius > tol (the run stops there) iff row k cuts; the row is then turned forward
+//                   in that slot and bounds every later candidate.  A run that is unbounded or capped counts as "cuts" (an empty
+//                   child is found empty later; a dropped one would lose area).
+//                   The slots hold the bits of the rows in global memory: ov_load stored exactly row[1 + t] and row[0], and
+//                   tr_simplex writes neither A nor b.  n_cut <= k, so slot m_P + n_cut never lies behind slot m_P + k: the rows
+//                   still to be read are untouched.  k_overlap_split has no flag 2 rows.
+//     output        ov_finish.  flag[item]: bit 0 P meets C, bit 1 the cut row cuts, bit 2 some run was unbounded or capped;
+//                   mask[item][OV_WORDS]: bit k, row k of the cutter's region cuts.  The host assembles the child pieces from these alone.
 //   The only atomics are the counters; no floating-point atomics: a rerun gives the same bits.
 #pragma once
 #include <stdint.h>
@@ -58,6 +65,55 @@ __device__ inline int ov_radius(const TrLds &S, int m, int nt, double stop_t, un
     const int st = tr_simplex(S, m, nt, nt + 1, false, pivots, stop_t);
     __syncthreads();
     return st;
+}
+
+// The row loop of a region difference (the header comment): the candidates are the LDS rows [m_p, m_p + n_rows) behind the piece's rows
+// [0, m_p); mask bit k is set for a cutting row k < n_mask.  Returns whether a row k >= n_mask cut.  s_mask is zeroed by the caller.
+__device__ inline bool ov_difference(const TrLds &S, int m_p, int n_rows, int n_mask, int nt, double tol, unsigned long long &pivots,
+                                     unsigned long long &lps, unsigned long long &wide, unsigned long long *s_mask) {
+    const int lane = threadIdx.x & 63, nr = nt + 1;
+    int n_cut = 0;
+    bool tail_cuts = false;
+    for (int k = 0; k < n_rows; ++k) {
+        const int src = m_p + k, at = m_p + n_cut;
+        __syncthreads();
+        if (S.flag[src] == 2) continue;
+        const double v = lane < nt ? S.A[src * nr + lane] : 0.0, rhs = S.b[src];
+        __syncthreads();
+        if (lane < nt) S.A[at * nr + lane] = -v;
+        if (lane == 0) { S.A[at * nr + nt] = 1.0; S.b[at] = -rhs; S.flag[at] = 0; }
+        const int st = ov_radius(S, at + 1, nt, tol, pivots);
+        ++lps;
+        wide += st == TR_UNBOUNDED || st == TR_CAPPED;
+        if (st == TR_OPTIMAL && !(S.x[nt] > tol)) continue;
+        // row k cuts: it bounds every later candidate
+        __syncthreads();
+        if (lane < nt) S.A[at * nr + lane] = v;
+        if (lane == 0) {
+            S.b[at] = rhs;
+            if (k < n_mask) s_mask[k >> 6] |= 1ull << (k & 63);
+        }
+        if (k >= n_mask) tail_cuts = true;
+        ++n_cut;
+    }
+    return tail_cuts;
+}
+
+// what an item of a difference kernel leaves: its flag bits, its mask from s_mask, and the counters items, meets, LPs, pivots, wide
+__device__ inline void ov_finish(long long q, bool meets, bool cut_row_cuts, unsigned long long lps, unsigned long long pivots,
+                                 unsigned long long wide, const unsigned long long *s_mask, int32_t *flag, unsigned long long *mask,
+                                 unsigned long long *counters) {
+    const int lane = threadIdx.x & 63;
+    __syncthreads();
+    if (lane < OV_WORDS) mask[q * OV_WORDS + lane] = s_mask[lane];
+    if (lane == 0) {
+        flag[q] = (meets ? 1 : 0) | (cut_row_cuts ? 2 : 0) | (wide ? 4 : 0);
+        atomicAdd(counters + 0, 1ull);
+        atomicAdd(counters + 1, meets ? 1ull : 0ull);
+        atomicAdd(counters + 2, lps);
+        atomicAdd(counters + 3, pivots);
+        atomicAdd(counters + 4, wide);
+    }
 }
 
 struct OverlapPairArgs {
@@ -131,7 +187,7 @@ struct OverlapSplitArgs {
 __global__ void __launch_bounds__(64) k_overlap_split(OverlapSplitArgs a) {
     extern __shared__ double ov_smem[];
     __shared__ unsigned long long s_mask[OV_WORDS];
-    const int lane = threadIdx.x & 63, nt = a.nt, nr = nt + 1;
+    const int lane = threadIdx.x & 63, nt = a.nt;
     const long long q = blockIdx.x;
     if (q >= a.n_items) return;
     const TrLds S = tr_lds(ov_smem, a.m_max, nt);
@@ -147,39 +203,8 @@ __global__ void __launch_bounds__(64) k_overlap_split(OverlapSplitArgs a) {
     int st = ov_radius(S, m_p + p, nt, tol, pivots);
     wide += st == TR_UNBOUNDED || st == TR_CAPPED;
     const bool meets = !(st == TR_OPTIMAL && !(S.x[nt] > tol));
-    int n_cut = 0, cut_row_cuts = 0;
-    if (meets) {
-        for (int k = 0; k < p; ++k) {
-            const double *row = k < m_c ? a.ef + (c0 + k) * nr : a.cut + q * nr;
-            const int at = m_p + n_cut;
-            __syncthreads();
-            if (lane < nt) S.A[at * nr + lane] = -row[1 + lane];
-            if (lane == 0) { S.A[at * nr + nt] = 1.0; S.b[at] = -row[0]; S.flag[at] = 0; }
-            st = ov_radius(S, at + 1, nt, tol, pivots);
-            ++lps;
-            wide += st == TR_UNBOUNDED || st == TR_CAPPED;
-            if (st == TR_OPTIMAL && !(S.x[nt] > tol)) continue;
-            // row k cuts: it bounds every later candidate
-            __syncthreads();
-            if (lane < nt) S.A[at * nr + lane] = row[1 + lane];
-            if (lane == 0) {
-                S.b[at] = row[0];
-                if (k < m_c) s_mask[k >> 6] |= 1ull << (k & 63);
-            }
-            if (k >= m_c) cut_row_cuts = 1;
-            ++n_cut;
-        }
-    }
-    __syncthreads();
-    if (lane < OV_WORDS) a.mask[q * OV_WORDS + lane] = s_mask[lane];
-    if (lane == 0) {
-        a.flag[q] = (meets ? 1 : 0) | (cut_row_cuts ? 2 : 0) | (wide ? 4 : 0);
-        atomicAdd(a.counters + 0, 1ull);
-        atomicAdd(a.counters + 1, meets ? 1ull : 0ull);
-        atomicAdd(a.counters + 2, lps);
-        atomicAdd(a.counters + 3, pivots);
-        atomicAdd(a.counters + 4, wide);
-    }
+    const bool cut_row_cuts = meets && ov_difference(S, m_p, p, m_c, nt, tol, pivots, lps, wide, s_mask);
+    ov_finish(q, meets, cut_row_cuts, lps, pivots, wide, s_mask, a.flag, a.mask, a.counters);
 }
 
 }  // namespace mpc

@@ -29,7 +29,8 @@ from typing import List, Optional
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, unit_rows
+from .overlap import difference_rounds
+from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, solution_rows
 
 __all__ = ['ExitSets', 'ExitVolumes', 'exit_sets', 'exit_pieces', 'pulled_back_rows', 'ROW_EPS']
 
@@ -170,55 +171,22 @@ def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1
     usable = status == 0
     usable[list(void)] = False
     xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
-    # per source its live pieces in order: (rows or None for the source's own rows, wide)
-    live = [[(None, False)] if usable[i] else [] for i in range(R)]
-    for rnd in range(max((len(c) for c in cutters), default=0)):
-        active = [i for i in range(R) if len(cutters[i]) > rnd and live[i]]
-        if not active:
-            continue
-        p_rows, p_counts, item_source, item_target, item_start = [], [], [], [], []
-        for i in active:
-            j = cutters[i][rnd]
-            for pc, _ in live[i]:
-                rows = ef[off[i]:off[i + 1]] if pc is None else pc
-                p_rows.append(rows)
-                p_counts.append(len(rows))
-                item_source.append(i)
-                item_target.append(j)
-                item_start.append(xs[i])
-        poff = numpy.concatenate([[0], numpy.cumsum(p_counts)]).astype(numpy.int64)
-        fl, mask, s = _lib.exit_split(off, ef, Phi, phi, poff, numpy.vstack(p_rows), numpy.arange(len(p_rows)), item_source, item_target,
-                                      numpy.asarray(item_start), tol, device)
-        stats['rounds'] += 1
-        stats['items'] += len(p_rows)
-        stats['max_item_rows'] = max(stats['max_item_rows'], max(m + int(counts[j]) for m, j in zip(p_counts, item_target)))
-        for k in ('lps', 'pivots', 'wide'):
-            stats[k] += s[k]
-        stats['device_ms'] += s['ms']
-        stats['round_ms'].append(s['ms'])
-        q = 0
-        for i in active:
-            j = cutters[i][rnd]
-            back = None
-            nxt = []
-            for pc, wide in live[i]:
-                if not fl[q] & _lib.OVERLAP_MEETS:
-                    nxt.append((pc, wide))
-                else:
-                    if back is None:
-                        back = pulled_back_rows(ef[off[j]:off[j + 1]], Phi[i], phi[i])
-                    rows = ef[off[i]:off[i + 1]] if pc is None else pc
-                    cutting = back[mask_rows(mask[q], len(back))]
-                    cutting = cutting[~numpy.isnan(cutting[:, 0])]
-                    w = wide or bool(fl[q] & _lib.OVERLAP_WIDE)
-                    for k in range(len(cutting)):
-                        nxt.append((numpy.vstack([rows, cutting[:k], -cutting[k:k + 1]]), w))
-                q += 1
-            live[i] = nxt
-        if any(pc is not None and len(pc) > MAX_ROWS for i in active for pc, _ in live[i]):
-            raise ValueError(f'exit_sets: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
-        if sum(len(p) for p in live) > max_pieces:
-            raise ValueError(f'exit_sets: more than max_pieces = {max_pieces} pieces after round {rnd + 1}')
+
+    # 2. the rounds of the difference (overlap.difference_rounds) against pulled-back cutters
+    def launch(poff, prows, item_source, entries, start):
+        return _lib.exit_split(off, ef, Phi, phi, poff, prows, numpy.arange(len(entries)), item_source, [j for j, _ in entries], start, tol, device)
+
+    back = [None, None]      # (source, target) and its pulled-back rows: the items of one source in a round follow each other
+
+    def cutting_rows(i, entry, mask, flag):
+        j = entry[0]
+        if back[0] != (i, j):
+            back[:] = (i, j), pulled_back_rows(ef[off[j]:off[j + 1]], Phi[i], phi[i])
+        rows = back[1][mask_rows(mask, len(back[1]))]
+        return list(rows[~numpy.isnan(rows[:, 0])])
+
+    live, stats['round_ms'] = difference_rounds('exit_sets', off, ef, xs, usable, [[(j, None) for j in c] for c in cutters], launch, cutting_rows,
+                                                max_pieces, stats, 'items')
     # 3. only a piece behind an unbounded or capped run can be empty
     suspects = [(i, k) for i in range(R) for k, (pc, wide) in enumerate(live[i]) if wide and pc is not None]
     if suspects:
@@ -252,20 +220,12 @@ def exit_sets(source, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_p
     regs = source.critical_regions
     if graph is not None and graph.n_regions != len(regs):
         raise ValueError(f'exit_sets: the graph has {graph.n_regions} regions, the solution {len(regs)}')
-    rows, void = [], []
-    for i, r in enumerate(regs):
-        u, empty = unit_rows(r.E, r.f, n_t)
-        if not len(u):
-            raise ValueError(f'exit_sets: region {i} has no row with a normal (the whole space, or nothing)')
-        rows.append(u)
-        if empty:
-            void.append(i)
+    off, rows, void = solution_rows(regs, n_t, 'exit_sets')
     if graph is None:
         graph = transition_graph(source, A, B, inp, c=c, tol=tol, device=device)
-    off = numpy.concatenate([[0], numpy.cumsum([len(u) for u in rows])]).astype(numpy.int64)
     _, _, xlaw = source._stacked()
     Phi, phi = closed_loop_maps(xlaw, A, B, inp, c)
-    out = exit_pieces(off, numpy.vstack(rows), Phi, phi, n_t, [graph.successors(i) for i in range(len(regs))], tol=tol, max_pieces=max_pieces,
+    out = exit_pieces(off, rows, Phi, phi, n_t, [graph.successors(i) for i in range(len(regs))], tol=tol, max_pieces=max_pieces,
                       device=device, void=void)
     out.stats['graph_ms'] = float(graph.stats.get('wall_ms', 0.0))
     out.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3

@@ -31,9 +31,9 @@ from typing import List, Optional
 import numpy
 
 from .critical_region import CriticalRegion
-from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, unit_rows
+from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, solution_rows
 
-__all__ = ['ReducedRegion', 'OverlapPartition', 'remove_overlaps', 'partition_by_value', 'build_reduced_solution', 'VERDICTS']
+__all__ = ['ReducedRegion', 'OverlapPartition', 'remove_overlaps', 'partition_by_value', 'difference_rounds', 'build_reduced_solution', 'VERDICTS']
 
 VERDICTS = ('DISJOINT', 'EQUAL', 'I_WINS', 'J_WINS', 'CROSSING')
 DISJOINT, EQUAL, I_WINS, J_WINS, CROSSING = range(5)
@@ -98,6 +98,58 @@ def classify_pairs(radius, d_min, d_max, flag, equal, tol: float) -> numpy.ndarr
             v[take] = verdict
             done |= take
     return v
+
+
+def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces: int, stats: dict, items_key: str):
+    """The rounds of a region difference (step 4 of the module docstring; exit_sets.py runs the same rounds against pulled-back
+    cutters).  cutters[i]: the entries (cutter region j, extra row or None) that polytope i meets, one per round, in order.
+    ``launch(piece_off, piece_rows, item_source, item_entries, item_start)`` runs the items of a round, item k being piece k, and returns
+    (flag, mask, stats) of the library's split call; ``cutting_rows(source, entry, mask, flag)`` gives the ordered rows that cut an item
+    whose piece meets its cutter.  Returns (live, round_ms): per source its pieces in order as (rows, or None for the source's own rows,
+    wide: a run on the way to the piece was unbounded or capped), and the device ms of every round.  rounds, ``items_key``, lps, pivots,
+    wide, device_ms and max_item_rows are accumulated into ``stats``; ValueError in the name of ``who`` past MAX_ROWS or max_pieces."""
+    from . import _lib
+    R, counts = len(off) - 1, numpy.diff(off)
+    live = [[(None, False)] if usable[i] else [] for i in range(R)]
+    round_ms = []
+    for rnd in range(max((len(c) for c in cutters), default=0)):
+        active = [i for i in range(R) if len(cutters[i]) > rnd and live[i]]
+        if not active:
+            continue
+        p_rows, item_source, entries = [], [], []
+        for i in active:
+            for pc, _ in live[i]:
+                p_rows.append(ef[off[i]:off[i + 1]] if pc is None else pc)
+                item_source.append(i)
+                entries.append(cutters[i][rnd])
+        p_counts = [len(rows) for rows in p_rows]
+        poff = numpy.concatenate([[0], numpy.cumsum(p_counts)]).astype(numpy.int64)
+        fl, mask, s = launch(poff, numpy.vstack(p_rows), item_source, entries, numpy.asarray([xs[i] for i in item_source]))
+        stats['rounds'] += 1
+        stats[items_key] += len(p_rows)
+        stats['max_item_rows'] = max(stats['max_item_rows'], max(m + int(counts[j]) + (c is not None) for m, (j, c) in zip(p_counts, entries)))
+        for k in ('lps', 'pivots', 'wide'):
+            stats[k] += s[k]
+        stats['device_ms'] += s['ms']
+        round_ms.append(s['ms'])
+        q = 0
+        for i in active:
+            nxt = []
+            for pc, wide in live[i]:
+                if not fl[q] & _lib.OVERLAP_MEETS:
+                    nxt.append((pc, wide))
+                else:
+                    cutting = cutting_rows(i, entries[q], mask[q], int(fl[q]))
+                    w = wide or bool(fl[q] & _lib.OVERLAP_WIDE)
+                    for k, row in enumerate(cutting):
+                        nxt.append((numpy.vstack([p_rows[q]] + cutting[:k] + [-row]), w))
+                q += 1
+            live[i] = nxt
+        if any(pc is not None and len(pc) > MAX_ROWS for i in active for pc, _ in live[i]):
+            raise ValueError(f'{who}: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
+        if sum(len(p) for p in live) > max_pieces:
+            raise ValueError(f'{who}: more than max_pieces = {max_pieces} pieces after round {rnd + 1}')
+    return live, round_ms
 
 
 def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20,
@@ -175,55 +227,19 @@ def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, valu
             cutters[j].append((i, -cut[k]))
     for c in cutters:
         c.sort(key=lambda jc: jc[0])
-    # 4. the difference stage: per source its live pieces in order; None stands for the source's own rows
-    live = [[None] if usable[i] else [] for i in range(R)]
-    n_rounds = max((len(c) for c in cutters), default=0)
-    for rnd in range(n_rounds):
-        active = [i for i in range(R) if len(cutters[i]) > rnd and live[i]]
-        if not active:
-            continue
-        p_rows, p_counts, item_piece, item_cutter, item_cut, item_has, item_start = [], [], [], [], [], [], []
-        for i in active:
-            j, c = cutters[i][rnd]
-            for pc in live[i]:
-                rows = ef[off[i]:off[i + 1]] if pc is None else pc
-                item_piece.append(len(p_rows))
-                p_rows.append(rows)
-                p_counts.append(len(rows))
-                item_cutter.append(j)
-                item_has.append(0 if c is None else 1)
-                item_cut.append(numpy.zeros(n_t + 1) if c is None else c)
-                item_start.append(xs[i])
-        poff = numpy.concatenate([[0], numpy.cumsum(p_counts)]).astype(numpy.int64)
-        fl, mask, s = _lib.overlap_split(off, ef, poff, numpy.vstack(p_rows), item_piece, item_cutter, item_has, numpy.asarray(item_cut),
-                                         numpy.asarray(item_start), tol, device)
-        stats['rounds'] += 1
-        stats['work_items'] += len(item_piece)
-        stats['max_item_rows'] = max(stats['max_item_rows'], max(p_counts[p] + int(counts[c]) + hc for p, c, hc in zip(item_piece, item_cutter, item_has)))
-        for k in ('lps', 'pivots', 'wide'):
-            stats[k] += s[k]
-        stats['device_ms'] += s['ms']
-        q = 0
-        for i in active:
-            j, c = cutters[i][rnd]
-            cj = ef[off[j]:off[j + 1]]
-            nxt = []
-            for pc in live[i]:
-                if not fl[q] & _lib.OVERLAP_MEETS:
-                    nxt.append(pc)
-                else:
-                    rows = ef[off[i]:off[i + 1]] if pc is None else pc
-                    cutting = [cj[r] for r in mask_rows(mask[q], len(cj)).tolist()]
-                    if fl[q] & _lib.OVERLAP_CUT_ROW:
-                        cutting.append(c)
-                    for k, row in enumerate(cutting):
-                        nxt.append(numpy.vstack([rows] + cutting[:k] + [-row]))
-                q += 1
-            live[i] = nxt
-        if any(pc is not None and len(pc) > MAX_ROWS for i in active for pc in live[i]):
-            raise ValueError(f'remove_overlaps: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
-        if sum(len(p) for p in live) > max_pieces:
-            raise ValueError(f'remove_overlaps: more than max_pieces = {max_pieces} pieces after round {rnd + 1}')
+    # 4. the difference stage
+    def launch(poff, prows, item_source, entries, start):
+        zero = numpy.zeros(n_t + 1)
+        return _lib.overlap_split(off, ef, poff, prows, numpy.arange(len(entries)), [j for j, _ in entries], [0 if c is None else 1 for _, c in entries],
+                                  numpy.asarray([zero if c is None else c for _, c in entries]), start, tol, device)
+
+    def cutting_rows(i, entry, mask, flag):
+        j, c = entry
+        cj = ef[off[j]:off[j + 1]]
+        return [cj[r] for r in mask_rows(mask, len(cj)).tolist()] + ([c] if flag & _lib.OVERLAP_CUT_ROW else [])
+
+    live, _ = difference_rounds('remove_overlaps', off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces, stats, 'work_items')
+    live = [[pc for pc, _ in p] for p in live]
     pieces = [pc for i in range(R) for pc in live[i]]
     sources = numpy.asarray([i for i in range(R) for _ in live[i]], dtype=numpy.int64)
     counts_v = {name: int(numpy.sum(verdict == k)) for k, name in enumerate(VERDICTS)}
@@ -292,17 +308,8 @@ def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_piec
     """Solution.remove_overlaps (the module docstring).  Returns a new Solution of ReducedRegion; the source is not modified."""
     t0 = time.perf_counter()
     n_t, qv, rv = check_source(source, tol, value_tol, max_pieces)
-    regs = source.critical_regions
-    rows, void = [], []
-    for i, r in enumerate(regs):
-        u, empty = unit_rows(r.E, r.f, n_t)
-        if not len(u):
-            raise ValueError(f'remove_overlaps: region {i} has no row with a normal (the whole space, or nothing)')
-        rows.append(u)
-        if empty:
-            void.append(i)
-    off = numpy.concatenate([[0], numpy.cumsum([len(u) for u in rows])]).astype(numpy.int64)
-    part = partition_by_value(off, numpy.vstack(rows), qv, rv, n_t, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device,
+    off, rows, void = solution_rows(source.critical_regions, n_t, 'remove_overlaps')
+    part = partition_by_value(off, rows, qv, rv, n_t, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device,
                               void=void)
     part.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
     return build_reduced_solution(source, part.sources, part.pieces, part.verdict_counts, part.vanished, part.stats)

@@ -26,7 +26,7 @@ from .critical_region import CriticalRegion
 MAX_DIM = 16      # n_theta of the device kernels
 MAX_ROWS = 256    # rows of a region (source regions and merged ones)
 
-__all__ = ['MergedRegion', 'merge_regions', 'build_merged_solution', 'unit_rows', 'law_groups', 'dedupe_rows', 'check_source']
+__all__ = ['MergedRegion', 'merge_regions', 'build_merged_solution', 'unit_rows', 'solution_rows','law_groups', 'dedupe_rows', 'check_source']
 
 
 @dataclass(eq=False)
@@ -70,6 +70,20 @@ def unit_rows(E, f, n_t: int):
     keep = nrm > 0.0
     empty = bool(numpy.any(~keep & (f < 0.0)))
     return numpy.hstack([(f[keep] / nrm[keep]).reshape(-1, 1), E[keep] / nrm[keep, None]]), empty
+
+
+def solution_rows(regions, n_t: int, who: str):
+    """(row_off [R + 1] int64, rows [total, n_t + 1], void) of a solution's regions: their unit rows stacked in CSR form and the indices
+    of the regions unit_rows finds empty.  ValueError in the name of ``who`` for a region that keeps no row."""
+    rows, void = [], []
+    for i, r in enumerate(regions):
+        u, empty = unit_rows(r.E, r.f, n_t)
+        if not len(u):
+            raise ValueError(f'{who}: region {i} has no row with a normal (the whole space, or nothing)')
+        rows.append(u)
+        if empty:
+            void.append(i)
+    return numpy.concatenate([[0], numpy.cumsum([len(u) for u in rows])]).astype(numpy.int64), numpy.vstack(rows), void
 
 
 def law_of(region, outputs, n_t: int) -> numpy.ndarray:

@@ -24,7 +24,7 @@ from typing import Optional
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS, unit_rows
+from .region_merge import MAX_DIM, MAX_ROWS, solution_rows
 
 __all__ = ['TransitionGraph', 'transition_graph', 'transition_pairs', 'image_box_pairs', 'STATUS', 'NO_EDGE', 'EDGE', 'UNBOUNDED', 'UNDECIDED']
 
@@ -286,20 +286,12 @@ def transition_graph(source, A, B, inputs, c=None, tol: float = 1e-8, full_radiu
     from .invariance import closed_loop_maps
     t0 = time.perf_counter()
     A, B, inp, c, n_t = check_source(source, A, B, inputs, c, tol)
-    rows, void = [], []
-    for i, r in enumerate(source.critical_regions):
-        u, empty = unit_rows(r.E, r.f, n_t)
-        if not len(u):
-            raise ValueError(f'transition_graph: region {i} has no row with a normal (the whole space, or nothing)')
-        rows.append(u)
-        if empty:
-            void.append(i)
-    off = numpy.concatenate([[0], numpy.cumsum([len(u) for u in rows])]).astype(numpy.int64)
+    off, rows, void = solution_rows(source.critical_regions, n_t, 'transition_graph')
     _, _, xlaw = source._stacked()
     Phi, phi = closed_loop_maps(xlaw, A, B, inp, c)
-    res = transition_pairs(off, numpy.vstack(rows), Phi, phi, n_t, tol=tol, full_radius=full_radius, device=device, void=void)
+    res = transition_pairs(off, rows, Phi, phi, n_t, tol=tol, full_radius=full_radius, device=device, void=void)
     keep = res['status'] != NO_EDGE
     stats = dict(res['stats'])
     stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
-    return TransitionGraph.from_edges(len(rows), res['i'][keep], res['j'][keep], res['radius'][keep], res['status'][keep], res['witness'][keep],
+    return TransitionGraph.from_edges(len(off) - 1, res['i'][keep], res['j'][keep], res['radius'][keep], res['status'][keep], res['witness'][keep],
                                       res['region_status'], stats)

@@ -1,6 +1,7 @@
 """Solution.remove_overlaps on the device: partition_by_value against the independent CPU reference on the hand-built
 cases and on random polytopes in a box up to n_theta = 16 and 200 rows, properties that need no reference (ownership by sampling,
-volumes, determinism), solved programs (an mpLP and a two-parameter mpMILP) and the refusals of the two library calls."""
+volumes, determinism), solved programs (an mpLP and a two-parameter mpMILP), the refusals of the two library calls and one raw item
+of the row loop with a result derived by hand."""
 import warnings
 
 import numpy
@@ -300,3 +301,18 @@ def test_library_refusals():
                            (pairs, {'hc': [1], 'cut': [[0.0, 2.0, 0.0]]}, 'unit normals'), (pairs, {'xs': xs * numpy.inf}, 'finite')):
         with pytest.raises(_lib.MpcError, match=text):
             call(**kw)
+
+
+def test_the_row_loop_with_rows_that_do_not_cut_between_rows_that_do():
+    """One raw item of mpc_overlap_split, expected result derived by hand.  Piece [0, 1]^2 from (0.5, 0.5); cutter x <= 2, x <= 0.5, y <= 3,
+    y <= 0.5, -x <= 0.25 and the cut row x + y <= 0.75.  Rows 1 and 3 cut, rows 0, 2 and 4 do not (the reversed row leaves the piece), so
+    the slot a reversed row is written to falls behind the slot its row is read from; the cut row cuts last, in the triangle
+    (0.25, 0.5), (0.5, 0.25), (0.5, 0.5).  Seven LPs: the intersection and six rows."""
+    cutter = numpy.array([[2, 1, 0], [0.5, 1, 0], [3, 0, 1], [0.5, 0, 1], [0.25, -1, 0]], dtype=float)
+    s = 1.0 / numpy.sqrt(2.0)
+    flag, mask, stats = _lib.overlap_split([0, 5], cutter, [0, 4], box_rows([0, 0], [1, 1]), [0], [0], [1], [[0.75 * s, s, s]], [[0.5, 0.5]], TOL)
+    assert mask[0].tolist() == [0b01010, 0, 0, 0]
+    assert flag[0] == _lib.OVERLAP_MEETS | _lib.OVERLAP_CUT_ROW
+    assert stats['items'] == stats['meets'] == 1
+    assert stats['lps'] == 7
+    assert stats['wide'] == 0

@@ -12,7 +12,7 @@ from ppopt_amd import MPQP_Program, _lib, invariance, problem_generator as pg, t
 from ppopt_amd.geometry.polytope import Polytope
 from ppopt_amd.geometry.polytope_operations import hit_and_run_batch
 from ppopt_amd.mp_solvers.solve_mpqp import mpqp_algorithm, solve_mpqp
-from ppopt_amd.region_merge import unit_rows
+from ppopt_amd.region_merge import solution_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -86,7 +86,8 @@ def _unflagged(sol):
 def _arrays(sol, plant):
     """(unit-row polytopes, Phi, phi) of a solution under its plant, assembled here from the regions and laws"""
     n_t = sol.theta_dim()
-    polys = [unit_rows(r.E, r.f, n_t)[0] for r in sol.critical_regions]
+    off, rows, _ = solution_rows(sol.critical_regions, n_t, 'test')
+    polys = numpy.split(rows, off[1:-1])
     _, _, xlaw = sol._stacked()
     Phi, phi = invariance.closed_loop_maps(xlaw, numpy.asarray(plant['A'], dtype=float), numpy.asarray(plant['B'], dtype=float).reshape(n_t, -1),
                                            numpy.asarray(plant['inputs']))

@@ -1,0 +1,295 @@
+// geometry_refusals.hip -- the argument checking of the merge, overlap, transition and exit calls (mpc_merge_regions, mpc_merge_pairs,
+// mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split) as a stand-alone host program for a
+// sanitizer build:
+//   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/geometry_refusals.hip -o geometry_refusals
+// It includes geometry.hip itself and stands in for the pools of mpcombi_hip.hip, which a refusal never reaches: every call below must
+// come back MPC_ERR_INVALID with a message before a device is selected (an empty batch: MPC_OK), so the program needs no GPU and
+// launches nothing.  The arguments are heap copies of exactly the sizes they promise: a read past them is the sanitizer's to report.
+#include "../ppopt_amd/csrc/geometry.hip"
+
+#include <cstdlib>
+
+static std::string g_msg;
+namespace mpc {
+int fail(mpc_handle *, int code, const std::string &msg) { g_msg = msg; return code; }
+size_t dev_size_class(size_t bytes) { return bytes; }
+hipError_t dev_pool_take(size_t, void **) { std::abort(); }
+void dev_pool_give(void *, size_t) { std::abort(); }
+hipError_t host_pool_take(size_t, void **, size_t *, bool) { std::abort(); }
+bool host_pool_give(void *) { std::abort(); }
+hipError_t pooled_stream(hipStream_t *) { std::abort(); }
+void return_stream(hipStream_t) { std::abort(); }
+hipError_t pooled_event(hipEvent_t *, bool) { std::abort(); }
+void return_event(hipEvent_t, bool) { std::abort(); }
+int device_count_cached() { std::abort(); }      // reached only by a call that was not refused
+int cu_count(int) { std::abort(); }
+}  // namespace mpc
+
+static int n_bad = 0;
+static void expect(const char *what, int rc, int want = MPC_ERR_INVALID) {
+    const bool ok = rc == want && (want == MPC_OK) == g_msg.empty();
+    std::printf("%-44s rc = %d  %s\n", what, rc, g_msg.c_str());
+    if (!ok) ++n_bad;
+    g_msg.clear();
+}
+
+using VD = std::vector<double>;
+using VI = std::vector<int32_t>;
+using VL = std::vector<int64_t>;
+
+// mpc_merge_regions, mpc_merge_pairs
+static void merge_cases() {
+    const int nt = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    VD out_xs(4), out_box(8), t_max(1);
+    VI status(2), verdict(1);
+    std::vector<uint64_t> env_a(MPC_MERGE_WORDS), env_b(MPC_MERGE_WORDS);
+    int64_t stats[7];
+    float ms = 0.0f;
+    struct Args { int n_t; VL off; VD ef, xs, box; VI a, b; double tol; };
+    const Args good{nt, {0, 4, 8}, ef, {0.5, 0.5, 1.0, 0.5}, {0, 0, 1, 1, 0.5, 0, 1.5, 1}, {0}, {1}, 1e-8};
+    auto regions = [&](const Args &g) {
+        return mpc_merge_regions(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), out_xs.data(), out_box.data(), status.data(), stats, &ms);
+    };
+    auto pairs = [&](const Args &g, int64_t n_pairs = -2) {
+        return mpc_merge_pairs(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), g.xs.data(), g.box.data(),
+                               n_pairs == -2 ? (int64_t)g.a.size() : n_pairs, g.a.data(), g.b.data(), g.tol, env_a.data(), env_b.data(), verdict.data(),
+                               t_max.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;                                                                                            // 257 rows
+    for (int r = 0; r < 64; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    big.insert(big.end(), sq.begin(), sq.begin() + 3);
+    auto one_big = [&](Args &g) { g.off = {0, 257}; g.ef = big; g.xs.resize(2); g.box.resize(4); g.a = {0}; g.b = {0}; };
+    expect("merge_regions: n_t = 0", regions(with([](Args &g) { g.n_t = 0; })));
+    expect("merge_regions: n_t = 17", regions(with([](Args &g) { g.n_t = 17; })));
+    expect("merge_regions: row_off[0] != 0", regions(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("merge_regions: a region without rows", regions(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("merge_regions: a region of 257 rows", regions(with(one_big)));
+    expect("merge_regions: a non-finite row", regions(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("merge_regions: a row that is not unit", regions(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("merge_regions: n_regions < 0", mpc_merge_regions(0, nt, -1, good.off.data(), ef.data(), out_xs.data(), out_box.data(), status.data(), nullptr, nullptr));
+    expect("merge_regions: missing row_off", mpc_merge_regions(0, nt, 2, nullptr, ef.data(), out_xs.data(), out_box.data(), status.data(), nullptr, nullptr));
+    expect("merge_regions: missing ef_rows", mpc_merge_regions(0, nt, 2, good.off.data(), nullptr, out_xs.data(), out_box.data(), status.data(), nullptr, nullptr));
+    expect("merge_regions: missing xs", mpc_merge_regions(0, nt, 2, good.off.data(), ef.data(), nullptr, out_box.data(), status.data(), nullptr, nullptr));
+    expect("merge_regions: missing box", mpc_merge_regions(0, nt, 2, good.off.data(), ef.data(), out_xs.data(), nullptr, status.data(), nullptr, nullptr));
+    expect("merge_regions: missing status", mpc_merge_regions(0, nt, 2, good.off.data(), ef.data(), out_xs.data(), out_box.data(), nullptr, nullptr, nullptr));
+    expect("merge_regions: no regions is MPC_OK without a launch", mpc_merge_regions(0, nt, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), MPC_OK);
+    expect("merge_pairs: n_t = 0", pairs(with([](Args &g) { g.n_t = 0; })));
+    expect("merge_pairs: n_t = 17", pairs(with([](Args &g) { g.n_t = 17; })));
+    expect("merge_pairs: row_off[0] != 0", pairs(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("merge_pairs: a region without rows", pairs(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("merge_pairs: a region of 257 rows", pairs(with(one_big)));
+    expect("merge_pairs: a non-finite row", pairs(with([](Args &g) { g.ef[12] = INFINITY; })));
+    expect("merge_pairs: a row that is not unit", pairs(with([](Args &g) { g.ef[14] = 0.5; })));
+    expect("merge_pairs: tol < 0", pairs(with([](Args &g) { g.tol = -1.0; })));
+    expect("merge_pairs: tol NaN", pairs(with([&](Args &g) { g.tol = nan; })));
+    expect("merge_pairs: tol inf", pairs(with([](Args &g) { g.tol = INFINITY; })));
+    expect("merge_pairs: n_pairs < 0", pairs(good, -1));
+    expect("merge_pairs: n_pairs = 2^31", pairs(good, 0x80000000ll));
+    expect("merge_pairs: region index out of range", pairs(with([](Args &g) { g.b = {2}; })));
+    expect("merge_pairs: negative region index", pairs(with([](Args &g) { g.a = {-1}; })));
+    expect("merge_pairs: the same region twice", pairs(with([](Args &g) { g.b = {0}; })));
+    expect("merge_pairs: xs NaN", pairs(with([&](Args &g) { g.xs[3] = nan; })));
+    expect("merge_pairs: xs inf", pairs(with([](Args &g) { g.xs[0] = -INFINITY; })));
+    const Args &g = good;
+    auto raw = [&](const double *xs, const double *box, const int32_t *a, const int32_t *b, uint64_t *ea, uint64_t *eb, int32_t *v, double *t) {
+        return mpc_merge_pairs(0, nt, 2, g.off.data(), g.ef.data(), xs, box, 1, a, b, 1e-8, ea, eb, v, t, nullptr, nullptr);
+    };
+    expect("merge_pairs: missing xs", raw(nullptr, g.box.data(), g.a.data(), g.b.data(), env_a.data(), env_b.data(), verdict.data(), t_max.data()));
+    expect("merge_pairs: missing box", raw(g.xs.data(), nullptr, g.a.data(), g.b.data(), env_a.data(), env_b.data(), verdict.data(), t_max.data()));
+    expect("merge_pairs: missing pair_a", raw(g.xs.data(), g.box.data(), nullptr, g.b.data(), env_a.data(), env_b.data(), verdict.data(), t_max.data()));
+    expect("merge_pairs: missing pair_b", raw(g.xs.data(), g.box.data(), g.a.data(), nullptr, env_a.data(), env_b.data(), verdict.data(), t_max.data()));
+    expect("merge_pairs: missing env_a", raw(g.xs.data(), g.box.data(), g.a.data(), g.b.data(), nullptr, env_b.data(), verdict.data(), t_max.data()));
+    expect("merge_pairs: missing env_b", raw(g.xs.data(), g.box.data(), g.a.data(), g.b.data(), env_a.data(), nullptr, verdict.data(), t_max.data()));
+    expect("merge_pairs: missing verdict", raw(g.xs.data(), g.box.data(), g.a.data(), g.b.data(), env_a.data(), env_b.data(), nullptr, t_max.data()));
+    expect("merge_pairs: missing t_max", raw(g.xs.data(), g.box.data(), g.a.data(), g.b.data(), env_a.data(), env_b.data(), verdict.data(), nullptr));
+    expect("merge_pairs: no pairs is MPC_OK without a launch", pairs(with([](Args &a) { a.a.clear(); a.b.clear(); })), MPC_OK);
+    expect("merge_pairs: no pairs, no pair arrays", mpc_merge_pairs(0, nt, 2, g.off.data(), g.ef.data(), nullptr, nullptr, 0, nullptr, nullptr, 1e-8, nullptr, nullptr,
+                                                                    nullptr, nullptr, nullptr, nullptr), MPC_OK);
+}
+
+// mpc_overlap_pairs, mpc_overlap_split
+static void overlap_cases() {
+    const int nt = 2;
+    std::vector<int64_t> off{0, 4, 8};
+    std::vector<double> ef{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1, 1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1};
+    std::vector<double> xs{0.5, 0.5, 1.0, 0.5}, cut{0.0, 1.0, 0.0}, out(3);
+    std::vector<int32_t> a{0}, b{1}, hc{1}, flag(1);
+    std::vector<uint64_t> mask(4);
+    std::vector<int64_t> poff{0, 4};
+    std::vector<double> pef(ef.begin(), ef.begin() + 12);
+    auto pairs = [&](int n_t, const std::vector<int64_t> &o, const std::vector<double> &e, const std::vector<int32_t> &pa,
+                     const std::vector<int32_t> &pb, const std::vector<double> &c, double tol) {
+        return mpc_overlap_pairs(0, n_t, (int64_t)o.size() - 1, o.data(), e.data(), xs.data(), (int64_t)pa.size(), pa.data(), pb.data(), hc.data(),
+                                 c.data(), tol, &out[0], &out[1], &out[2], flag.data(), nullptr, nullptr);
+    };
+    auto split = [&](const std::vector<int64_t> &po, const std::vector<double> &pe, const std::vector<int32_t> &ip, const std::vector<int32_t> &ic,
+                     double tol) {
+        return mpc_overlap_split(0, nt, 2, off.data(), ef.data(), (int64_t)po.size() - 1, po.data(), pe.data(), (int64_t)ip.size(), ip.data(),
+                                 ic.data(), hc.data(), cut.data(), nullptr, tol, flag.data(), mask.data(), nullptr, nullptr);
+    };
+    expect("pairs: n_t = 0", pairs(0, off, ef, a, b, cut, 1e-8));
+    expect("pairs: n_t = 17", pairs(17, off, ef, a, b, cut, 1e-8));
+    expect("pairs: tol < 0", pairs(nt, off, ef, a, b, cut, -1.0));
+    expect("pairs: tol NaN", pairs(nt, off, ef, a, b, cut, std::nan("")));
+    expect("pairs: region index out of range", pairs(nt, off, ef, a, std::vector<int32_t>{2}, cut, 1e-8));
+    expect("pairs: negative region index", pairs(nt, off, ef, std::vector<int32_t>{-1}, b, cut, 1e-8));
+    expect("pairs: a region without rows", pairs(nt, std::vector<int64_t>{0, 0, 8}, ef, a, b, cut, 1e-8));
+    { std::vector<double> big; for (int r = 0; r < 65; ++r) big.insert(big.end(), ef.begin(), ef.begin() + 12);
+      expect("pairs: a region of 260 rows", pairs(nt, std::vector<int64_t>{0, 260}, big, std::vector<int32_t>{}, std::vector<int32_t>{}, cut, 1e-8)); }
+    { std::vector<double> v = ef; v[4] = std::nan(""); expect("pairs: a non-finite row", pairs(nt, off, v, a, b, cut, 1e-8)); }
+    expect("pairs: a cut row that is not unit", pairs(nt, off, ef, a, b, std::vector<double>{0.0, 2.0, 0.0}, 1e-8));
+    expect("split: tol < 0", split(poff, pef, a, b, -1.0));
+    expect("split: piece index out of range", split(poff, pef, std::vector<int32_t>{1}, b, 1e-8));
+    expect("split: cutter index out of range", split(poff, pef, a, std::vector<int32_t>{2}, 1e-8));
+    expect("split: a piece without rows", split(std::vector<int64_t>{0, 0, 4}, pef, std::vector<int32_t>{1}, b, 1e-8));
+    { std::vector<double> v = pef; v[0] = INFINITY; expect("split: a non-finite piece row", split(poff, v, a, b, 1e-8)); }
+}
+
+// mpc_transition_boxes, mpc_transition_pairs
+static void transition_cases() {
+    const int nt = 2;
+    std::vector<int64_t> off{0, 4, 8};
+    VD ef{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1, 1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1};
+    VD Phi{1, 0, 0, 1, 0.5, 0, 0, 0.5}, phi{0, 0, 0.1, 0.1}, xs{0.5, 0.5, 1.0, 0.5}, radius(1), witness(2), box(8);
+    VI a{0}, b{1}, status(1), flag(2), none;
+    int64_t stats[4];
+    float ms = 0.0f;
+    struct Args { int n_t; std::vector<int64_t> off; VD ef, Phi, phi, xs; VI a, b; double tol; };
+    const Args good{nt, off, ef, Phi, phi, xs, a, b, 1e-8};
+    auto pairs = [&](const Args &g, int64_t n_pairs = -2) {
+        return mpc_transition_pairs(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.xs.data(),
+                                    n_pairs == -2 ? (int64_t)g.a.size() : n_pairs, g.a.data(), g.b.data(), 1, g.tol, radius.data(), status.data(),
+                                    witness.data(), stats, &ms);
+    };
+    auto boxes = [&](const Args &g) {
+        return mpc_transition_boxes(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.xs.data(), box.data(),
+                                    flag.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    expect("pairs: n_t = 0", pairs(with([](Args &g) { g.n_t = 0; })));
+    expect("pairs: n_t = 17", pairs(with([](Args &g) { g.n_t = 17; })));
+    expect("pairs: tol < 0", pairs(with([](Args &g) { g.tol = -1.0; })));
+    expect("pairs: tol NaN", pairs(with([&](Args &g) { g.tol = nan; })));
+    expect("pairs: tol inf", pairs(with([](Args &g) { g.tol = INFINITY; })));
+    expect("pairs: n_pairs < 0", pairs(good, -1));
+    expect("pairs: n_pairs = 2^31", pairs(good, 0x80000000ll));
+    expect("pairs: region index out of range", pairs(with([](Args &g) { g.b = {2}; })));
+    expect("pairs: negative region index", pairs(with([](Args &g) { g.a = {-1}; })));
+    expect("pairs: a region without rows", pairs(with([](Args &g) { g.off = {0, 0, 8}; })));
+    { VD big; for (int r = 0; r < 65; ++r) big.insert(big.end(), ef.begin(), ef.begin() + 12);
+      expect("pairs: a region of 260 rows", pairs(with([&](Args &g) { g.off = {0, 260}; g.ef = big; g.a = {0}; g.b = {0}; }))); }
+    expect("pairs: a non-finite row", pairs(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("pairs: a row that is not unit", pairs(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("pairs: Phi NaN", pairs(with([&](Args &g) { g.Phi[7] = nan; })));
+    expect("pairs: Phi inf", pairs(with([](Args &g) { g.Phi[0] = INFINITY; })));
+    expect("pairs: phi NaN", pairs(with([&](Args &g) { g.phi[3] = nan; })));
+    expect("pairs: xs inf", pairs(with([](Args &g) { g.xs[2] = -INFINITY; })));
+    expect("pairs: missing Phi", mpc_transition_pairs(0, nt, 2, off.data(), ef.data(), nullptr, phi.data(), xs.data(), 1, a.data(), b.data(), 1, 1e-8,
+                                                      radius.data(), status.data(), witness.data(), nullptr, nullptr));
+    expect("pairs: missing xs", mpc_transition_pairs(0, nt, 2, off.data(), ef.data(), Phi.data(), phi.data(), nullptr, 1, a.data(), b.data(), 1, 1e-8,
+                                                     radius.data(), status.data(), witness.data(), nullptr, nullptr));
+    expect("pairs: missing pair_b", mpc_transition_pairs(0, nt, 2, off.data(), ef.data(), Phi.data(), phi.data(), xs.data(), 1, a.data(), nullptr, 1, 1e-8,
+                                                         radius.data(), status.data(), witness.data(), nullptr, nullptr));
+    expect("pairs: missing witness", mpc_transition_pairs(0, nt, 2, off.data(), ef.data(), Phi.data(), phi.data(), xs.data(), 1, a.data(), b.data(), 1, 1e-8,
+                                                          radius.data(), status.data(), nullptr, nullptr, nullptr));
+    expect("pairs: missing row_off", mpc_transition_pairs(0, nt, 2, nullptr, ef.data(), Phi.data(), phi.data(), xs.data(), 1, a.data(), b.data(), 1, 1e-8,
+                                                          radius.data(), status.data(), witness.data(), nullptr, nullptr));
+    expect("pairs: no pairs is MPC_OK without a launch", pairs(with([&](Args &g) { g.a = none; g.b = none; })), MPC_OK);
+    expect("boxes: n_t = 17", boxes(with([](Args &g) { g.n_t = 17; })));
+    expect("boxes: a region without rows", boxes(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("boxes: a non-finite row", boxes(with([](Args &g) { g.ef[0] = INFINITY; })));
+    expect("boxes: Phi NaN", boxes(with([&](Args &g) { g.Phi[3] = nan; })));
+    expect("boxes: phi inf", boxes(with([](Args &g) { g.phi[0] = INFINITY; })));
+    expect("boxes: xs NaN", boxes(with([&](Args &g) { g.xs[3] = nan; })));
+    expect("boxes: missing phi", mpc_transition_boxes(0, nt, 2, off.data(), ef.data(), Phi.data(), nullptr, xs.data(), box.data(), flag.data(), nullptr, nullptr));
+    expect("boxes: missing image_box", mpc_transition_boxes(0, nt, 2, off.data(), ef.data(), Phi.data(), phi.data(), xs.data(), nullptr, flag.data(), nullptr,
+                                                            nullptr));
+    expect("boxes: missing flag", mpc_transition_boxes(0, nt, 2, off.data(), ef.data(), Phi.data(), phi.data(), xs.data(), box.data(), nullptr, nullptr, nullptr));
+    expect("boxes: no regions is MPC_OK without a launch", mpc_transition_boxes(0, nt, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                                                nullptr, nullptr), MPC_OK);
+}
+
+// mpc_exit_split
+static void exit_cases() {
+    const int nt = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    VI flag(1);
+    std::vector<uint64_t> mask(MPC_MERGE_WORDS);
+    int64_t stats[5];
+    float ms = 0.0f;
+    struct Args { int n_t; VL off; VD ef, Phi, phi; VL poff; VD pef; VI p, i, j; VD start; double tol; };
+    const Args good{nt, {0, 4, 8}, ef, {1, 0, 0, 1, 0.5, 0, 0, 0.5}, {0, 0, 0.1, 0.1}, {0, 4}, sq, {0}, {0}, {1}, {0.5, 0.5}, 1e-8};
+    auto split = [&](const Args &g, int64_t n_items = -2) {
+        return mpc_exit_split(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), (int64_t)g.poff.size() - 1,
+                              g.poff.data(), g.pef.data(), n_items == -2 ? (int64_t)g.p.size() : n_items, g.p.data(), g.i.data(), g.j.data(),
+                              g.start.data(), g.tol, flag.data(), mask.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;
+    for (int r = 0; r < 65; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    expect("n_t = 0", split(with([](Args &g) { g.n_t = 0; })));
+    expect("n_t = 17", split(with([](Args &g) { g.n_t = 17; })));
+    expect("tol < 0", split(with([](Args &g) { g.tol = -1.0; })));
+    expect("tol NaN", split(with([&](Args &g) { g.tol = nan; })));
+    expect("tol inf", split(with([](Args &g) { g.tol = INFINITY; })));
+    expect("n_items < 0", split(good, -1));
+    expect("n_items = 2^31", split(good, 0x80000000ll));
+    expect("piece index out of range", split(with([](Args &g) { g.p = {1}; })));
+    expect("negative piece index", split(with([](Args &g) { g.p = {-1}; })));
+    expect("source index out of range", split(with([](Args &g) { g.i = {2}; })));
+    expect("negative source index", split(with([](Args &g) { g.i = {-1}; })));
+    expect("target index out of range", split(with([](Args &g) { g.j = {2}; })));
+    expect("negative target index", split(with([](Args &g) { g.j = {-3}; })));
+    expect("a region without rows", split(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("a piece without rows", split(with([](Args &g) { g.poff = {0, 0}; })));
+    expect("row_off[0] != 0", split(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("a region of 260 rows", split(with([&](Args &g) { g.off = {0, 260}; g.ef = big; g.Phi.resize(4); g.phi.resize(2); g.j = {0}; })));
+    expect("a piece of 260 rows", split(with([&](Args &g) { g.poff = {0, 260}; g.pef = big; })));
+    expect("a non-finite region row", split(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("a region row that is not unit", split(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("a non-finite piece row", split(with([](Args &g) { g.pef[3] = INFINITY; })));
+    expect("a piece row that is not unit", split(with([](Args &g) { g.pef[1] = 0.5; })));
+    expect("Phi NaN", split(with([&](Args &g) { g.Phi[7] = nan; })));
+    expect("Phi inf", split(with([](Args &g) { g.Phi[0] = INFINITY; })));
+    expect("phi NaN", split(with([&](Args &g) { g.phi[3] = nan; })));
+    expect("phi inf", split(with([](Args &g) { g.phi[0] = -INFINITY; })));
+    expect("start NaN", split(with([&](Args &g) { g.start[1] = nan; })));
+    expect("start inf", split(with([](Args &g) { g.start[0] = INFINITY; })));
+    const Args &g = good;
+    auto raw = [&](const int64_t *off, const double *rows, const double *Phi, const double *phi, const int64_t *poff, const double *pef, const int32_t *p,
+                   const int32_t *i, const int32_t *j, int32_t *fl, uint64_t *mk) {
+        return mpc_exit_split(0, nt, 2, off, rows, Phi, phi, 1, poff, pef, 1, p, i, j, nullptr, 1e-8, fl, mk, nullptr, nullptr);
+    };
+    expect("missing row_off", raw(nullptr, g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing ef_rows", raw(g.off.data(), nullptr, g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing Phi", raw(g.off.data(), g.ef.data(), nullptr, g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing phi", raw(g.off.data(), g.ef.data(), g.Phi.data(), nullptr, g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing piece_off", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), nullptr, g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing piece_rows", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), nullptr, g.p.data(), g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing item_piece", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), nullptr, g.i.data(), g.j.data(), flag.data(), mask.data()));
+    expect("missing item_source", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), nullptr, g.j.data(), flag.data(), mask.data()));
+    expect("missing item_target", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), nullptr, flag.data(), mask.data()));
+    expect("missing flag", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), nullptr, mask.data()));
+    expect("missing mask", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.poff.data(), g.pef.data(), g.p.data(), g.i.data(), g.j.data(), flag.data(), nullptr));
+    expect("no items is MPC_OK without a launch", split(with([](Args &a) { a.p.clear(); a.i.clear(); a.j.clear(); a.start.clear(); })), MPC_OK);
+    expect("no items, no pieces, no item arrays", mpc_exit_split(0, nt, 2, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), 0, nullptr, nullptr, 0, nullptr,
+                                                                nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr), MPC_OK);
+}
+
+int main() {
+    merge_cases();
+    overlap_cases();
+    transition_cases();
+    exit_cases();
+    std::printf("%d unexpected\n", n_bad);
+    return n_bad ? 1 : 0;
+}
