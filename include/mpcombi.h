@@ -806,6 +806,29 @@ int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t
                    const int32_t *item_piece, const int32_t *item_source, const int32_t *item_target, const double *start, double tol,
                    int32_t *flag, uint64_t *mask, int64_t *stats, float *ms);
 
+/* ---- redundant rows of polytopes (geometry.reduce_rows_of) ----------------------------------------------------------- */
+/* Polytopes as unit rows [o | n] in CSR form by row_off, as above, but up to MPC_REDUCE_MAX_ROWS rows each.  Stateless; an error text is
+ * read with mpc_last_error(NULL).  MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n_t <= 16, 1..512
+ * rows per polytope, finite rows with unit normals, finite start, tol finite and >= 0, n_poly in 0..2^31 - 1, row_off non-decreasing from 0.
+ *
+ * mpc_reduce_rows: the sequential rule for every polytope P (k_reduce_rows).  radius(P) <= tol: P is thin, status MPC_REDUCE_THIN, every
+ *   mask bit set, no row tested.  Otherwise for k = 0 .. m - 1 in order: row k is redundant iff the rows still live (the kept rows before k
+ *   and all rows after k) together with the reversed row {n_k.theta >= o_k} have a Chebyshev radius <= tol; a redundant row is removed at
+ *   once.  A run that is unbounded or stopped at the pivot cap counts as "kept".
+ *   status[q]  MPC_REDUCE_OK or MPC_REDUCE_THIN.   wide[q]: the number of unbounded or capped runs of polytope q.
+ *   kept[q][MPC_REDUCE_WORDS]  bit k: row k stays.
+ *   start      [n_poly][n_t] where the first run of a polytope starts, or NULL: the origin.
+ *   point      [n_poly][n_t] or NULL: where the first run ended (interior when it was neither thin nor wide), the start of every row run.
+ *   n_poly == 0: MPC_OK without a launch.
+ *   stats (may be NULL): [0] polytopes, [1] thin ones, [2] LPs, [3] pivots, [4] unbounded or capped runs.
+ * Deterministic: atomics only in the counters. */
+#define MPC_REDUCE_MAX_ROWS 512
+#define MPC_REDUCE_WORDS 8
+#define MPC_REDUCE_OK 0
+#define MPC_REDUCE_THIN 1
+int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const double *start, double tol,
+                    int32_t *status, int32_t *wide, uint64_t *kept, double *point, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

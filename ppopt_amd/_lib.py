@@ -279,6 +279,8 @@ def load():
                                                 ctypes.c_int32, ctypes.c_double, _dp, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_exit_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
                                           _ip, _ip, _ip, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_reduce_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double, _ip, _ip, _u64p, _dp, _lp,
+                                           ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -299,7 +301,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
-                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split']
+                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1407,6 +1409,28 @@ def exit_split(row_off, ef_rows, Phi, phi, piece_off, piece_rows, item_piece, it
     stats = _geometry_call('mpc_exit_split', _SPLIT_KEYS, int(device), n_t, R, off, ef, M, p, len(poff) - 1, poff, pef, n, ip, src, dst, s0, float(tol),
                            flag, mask)
     return flag, mask, stats
+
+
+REDUCE_MAX_ROWS = 512   # rows per polytope of mpc_reduce_rows (include/mpcombi.h)
+REDUCE_WORDS = 8        # 64-bit words of its kept mask (MPC_REDUCE_WORDS)
+REDUCE_OK, REDUCE_THIN = 0, 1
+
+
+def reduce_rows(row_off, ef_rows, start, tol: float, device: int = 0):
+    """The redundant rows of every polytope by the sequential rule (include/mpcombi.h, mpc_reduce_rows): (kept [rows] bool, one per input
+    row, status [n_poly] int32 (REDUCE_OK, REDUCE_THIN), wide [n_poly] int32, point [n_poly, n_t], stats)."""
+    off, ef = _merge_rows('reduce_rows', row_off, ef_rows)
+    n_t, n = ef.shape[1] - 1, len(off) - 1
+    s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
+    status, wide, mask = numpy.zeros(n, dtype=numpy.int32), numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, REDUCE_WORDS), dtype=numpy.uint64)
+    point = numpy.zeros((n, n_t))
+    stats = _geometry_call('mpc_reduce_rows', ('polytopes', 'thin', 'lps', 'pivots', 'wide'), int(device), n_t, n, off, ef, s0, float(tol), status,
+                           wide, mask, point)
+    counts = numpy.diff(off)
+    poly = numpy.repeat(numpy.arange(n), counts)
+    k = numpy.arange(len(ef)) - numpy.repeat(off[:-1], counts)
+    kept = ((mask[poly, k >> 6] >> (k & 63).astype(numpy.uint64)) & numpy.uint64(1)).astype(bool)
+    return kept, status, wide, point, stats
 
 
 class Locator:

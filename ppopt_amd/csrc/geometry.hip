@@ -1,7 +1,7 @@
 // geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
 // location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration, region volumes and region
 // merging and the overlap removal.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
-// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, simplex.hpp); the pools and the scaffold
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 #include "overlap.hpp"
 #include "transition.hpp"
 #include "exit_sets.hpp"
+#include "reduce.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1172,8 +1173,8 @@ extern "C" int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, c
                      budget, volume, centroid, n_simplices, status, second_moment, stats);
 }
 
-// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets ---------------------------
-// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp)  Every call checks its arguments in one order
+// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets, row reduction ----------
+// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp)  Every call checks its arguments in one order
 // (regions, pieces, tol, the item count, the dense arrays, the empty batch, missing arrays, the index arrays, the rest), uploads,
 // launches one wavefront per item over unit rows [o | n] in LDS, and downloads the results and its counters.  What the calls share is
 // here once: the checkers return the refusal, family_launch and family_close are the two ends of the device part.
@@ -1251,7 +1252,9 @@ static int family_close(OneShot &s, const DevBuf &d_cnt, int n, int64_t *stats, 
 }
 
 // ---- merging regions with equal laws (merge.hpp) ---------------------------------------------------------------------
-static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max) {
+// max_rows: MG_MAX_ROWS for every call but mpc_reduce_rows (RD_MAX_ROWS)
+static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int *m_max,
+                       int max_rows = MG_MAX_ROWS) {
     if (n_t < 1 || n_t > TR_MAX_NT) return bad(who, "n_t must lie in 1..16");
     if (n_regions < 0 || (n_regions > 0 && !row_off)) return bad(who, "bad region count or missing row_off");
     if (n_regions > 0x7fffffffll) return bad(who, "too many regions for one launch");
@@ -1259,7 +1262,7 @@ static int merge_check(const char *who, int32_t n_t, int64_t n_regions, const in
     *m_max = 1;
     for (int64_t r = 0; r < n_regions; ++r) {
         const int64_t k = row_off[r + 1] - row_off[r];
-        if (k < 1 || k > MG_MAX_ROWS) return bad(who, "every region needs 1..256 rows");
+        if (k < 1 || k > max_rows) return bad(who, "every region needs 1.." + std::to_string(max_rows) + " rows");
         *m_max = std::max<int>(*m_max, (int)k);
     }
     const int64_t rows = n_regions > 0 ? row_off[n_regions] : 0;
@@ -1527,5 +1530,37 @@ extern "C" int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, co
     family_launch(s, k_exit_split, n_items, lds, a);
     s.download(flag, d_f, ni * 4);
     s.download(mask, d_m, words);
+    return family_close(s, d_cnt, 5, stats, ms);
+}
+
+// ---- redundant rows of polytopes (reduce.hpp) ---------------------------------------------------------------------------
+extern "C" int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const double *start,
+                               double tol, int32_t *status, int32_t *wide, uint64_t *kept, double *point, int64_t *stats, float *ms) {
+    const char *who = "mpc_reduce_rows";
+    family_open(stats, 5, ms);
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_poly, row_off, ef_rows, &m_max, RD_MAX_ROWS)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (n_poly == 0) return MPC_OK;
+    if (!status || !wide || !kept) return bad(who, "missing array");
+    if (start)
+        if (int rc = check_finite(who, "start", start, n_poly * n_t)) return rc;
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(m_max, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_kept adds 64)
+    const size_t np = (size_t)n_poly, words = np * RD_WORDS * 8;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_poly, row_off, ef_rows, n_t + 1);
+    DevBuf *d_start = start ? &s.upload(start, np * n_t * 8) : nullptr, *d_point = point ? &s.buf(np * n_t * 8) : nullptr;
+    DevBuf &d_st = s.buf(np * 4), &d_w = s.buf(np * 4), &d_k = s.buf(words), &d_cnt = family_counters(s, 5);
+    ReduceArgs a{};
+    a.nt = n_t; a.m_max = m_max; a.n_poly = n_poly;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+    a.status = d_st.as<int32_t>(); a.wide = d_w.as<int32_t>(); a.kept = d_k.as<unsigned long long>();
+    a.point = d_point ? d_point->as<double>() : nullptr; a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_reduce_rows, n_poly, lds, a);
+    s.download(status, d_st, np * 4);
+    s.download(wide, d_w, np * 4);
+    s.download(kept, d_k, words);
+    if (point) s.download(point, *d_point, np * n_t * 8);
     return family_close(s, d_cnt, 5, stats, ms);
 }

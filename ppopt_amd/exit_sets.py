@@ -21,7 +21,9 @@ The procedure is deterministic, the difference of overlap.py step 4 against pull
      order, with rows: P's, the earlier cutting rows, the reversed row; P n C is dropped.
   3. pieces the device finds empty (only a wide one can be) are dropped.
 
-The pieces of one region are convex, closed, and share boundaries only; they are not merged back and keep redundant rows.
+The pieces of one region are convex, closed, and share boundaries only; they are not merged back.  They keep redundant rows unless
+``reduce_rows`` is set, which removes them round by round, or ExitSets.reduced() is called on the result (geometry/reduce.py, DESIGN
+§3.22; off by default).
 """
 import time
 from dataclasses import dataclass, field
@@ -78,6 +80,7 @@ class ExitSets:
     stats: dict = field(default_factory=dict)
     region_off: Optional[numpy.ndarray] = None
     region_rows: Optional[numpy.ndarray] = None
+    tol: Optional[float] = None      # the tol the pieces were cut with; the default of reduced()
 
     def __len__(self) -> int:
         return len(self.source)
@@ -111,6 +114,24 @@ class ExitSets:
             out[a:a + chunk] = numpy.where(inside.any(axis=0), inside.argmax(axis=0), -1)
         return out
 
+    def reduced(self, tol: Optional[float] = None, device: int = 0) -> 'ExitSets':
+        """These exit sets with every piece reduced to its irredundant rows in one device call (geometry.reduce_rows_of):
+        a new ExitSets with the same pieces in the same order; source and whole are kept, wide is or-ed with the reduction's, region_off
+        and region_rows are unchanged, and stats gains reduce_lps, reduce_ms and rows_removed.  ``tol``: None takes the tol the pieces
+        were cut with (1e-8 when unknown).  A piece thinner than tol stays as it is.  This object is not modified."""
+        from .geometry.reduce import reduce_rows_of
+        tol = (1e-8 if self.tol is None else self.tol) if tol is None else tol
+        stats = dict(self.stats, reduce_lps=0, reduce_ms=0.0, rows_removed=0)
+        off, rows, wide = self.piece_off.copy(), self.piece_rows.copy(), self.wide.copy()
+        if len(self):
+            r = reduce_rows_of(self.piece_off, self.piece_rows, self.piece_rows.shape[1] - 1, tol=tol, device=device, who='ExitSets.reduced')
+            off, rows, wide = r.row_off, r.rows, wide | (r.wide > 0)
+            stats.update(reduce_lps=r.stats['lps'], reduce_ms=r.stats['device_ms'], rows_removed=r.stats['rows_before'] - r.stats['rows_after'])
+        elif not (numpy.isfinite(tol) and tol >= 0.0):
+            raise ValueError('ExitSets.reduced: tol must be finite and >= 0')
+        return ExitSets(n_regions=self.n_regions, piece_off=off, piece_rows=rows, source=self.source.copy(), wide=wide, whole=self.whole.copy(),
+                        stats=stats, region_off=self.region_off, region_rows=self.region_rows, tol=self.tol)
+
     def volumes(self, tol: float = 1e-9, max_simplices=None, device: int = 0) -> ExitVolumes:
         """The volumes of the pieces and of the regions on the device (geometry.volume, with its limits): an ExitVolumes."""
         from . import _lib
@@ -133,10 +154,12 @@ class ExitSets:
 
 
 def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1e-8, max_pieces: int = 1 << 20, device: int = 0,
-                void=()) -> ExitSets:
+                void=(), reduce_rows: bool = False) -> ExitSets:
     """The exit sets on arrays: polytopes of unit rows ef_rows = [o | n] in CSR form by row_off with the maps Phi [R, n_t, n_t], phi
     [R, n_t]; successors[i]: the polytopes whose pulled-back sets are cut out of polytope i (taken ascending, once each).  Steps 2 and 3
-    of the module docstring; every LP runs on the device.  ``void``: polytopes known to be empty: they have no piece."""
+    of the module docstring; every LP runs on the device.  ``void``: polytopes known to be empty: they have no piece.
+    ``reduce_rows``: the children of every round lose their redundant rows before the row limit is checked (overlap.difference_rounds,
+    ``reduce``)."""
     from . import _lib
     t0 = time.perf_counter()
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
@@ -185,8 +208,9 @@ def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1
         rows = back[1][mask_rows(mask, len(back[1]))]
         return list(rows[~numpy.isnan(rows[:, 0])])
 
+    reduce = (lambda poff, prows, start: _lib.reduce_rows(poff, prows, start, tol, device)) if reduce_rows else None
     live, stats['round_ms'] = difference_rounds('exit_sets', off, ef, xs, usable, [[(j, None) for j in c] for c in cutters], launch, cutting_rows,
-                                                max_pieces, stats, 'items')
+                                                max_pieces, stats, 'items', reduce=reduce)
     # 3. only a piece behind an unbounded or capped run can be empty
     suspects = [(i, k) for i in range(R) for k, (pc, wide) in enumerate(live[i]) if wide and pc is not None]
     if suspects:
@@ -204,13 +228,14 @@ def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1
     stats['pieces'] = len(pieces)
     stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
     return ExitSets(n_regions=R, piece_off=piece_off, piece_rows=piece_rows, source=source, wide=wide, whole=whole, stats=stats, region_off=off,
-                    region_rows=ef)
+                    region_rows=ef, tol=float(tol))
 
 
-def exit_sets(source, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0) -> ExitSets:
+def exit_sets(source, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0,
+              reduce_rows: bool = False) -> ExitSets:
     """Solution.exit_sets (the module docstring): the states of every region whose next state under the plant theta+ = A theta + B u + c,
     u = x*(theta)[inputs], lies in no region.  ``graph``: the TransitionGraph of the same (A, B, inputs, c, tol); built here when None.
-    The source is not modified."""
+    ``reduce_rows``: as in exit_pieces.  The source is not modified."""
     from .invariance import closed_loop_maps
     from .transition import check_source, transition_graph
     t0 = time.perf_counter()
@@ -226,7 +251,7 @@ def exit_sets(source, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_p
     _, _, xlaw = source._stacked()
     Phi, phi = closed_loop_maps(xlaw, A, B, inp, c)
     out = exit_pieces(off, rows, Phi, phi, n_t, [graph.successors(i) for i in range(len(regs))], tol=tol, max_pieces=max_pieces,
-                      device=device, void=void)
+                      device=device, void=void, reduce_rows=reduce_rows)
     out.stats['graph_ms'] = float(graph.stats.get('wall_ms', 0.0))
     out.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
     return out

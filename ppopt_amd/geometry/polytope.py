@@ -16,3 +16,10 @@ class Polytope:
         if A.ndim != 2 or A.shape[0] != b.shape[0]:
             raise ValueError(f'Polytope: A has shape {A.shape} but b has {b.shape[0]} rows')
         return numpy.hstack([b, A])
+
+    def reduced(self, tol: float = 1e-8, device: int = 0) -> 'Polytope':
+        """This polytope without its redundant rows (geometry.reduce): the rows are scaled to unit normals for the test
+        (a zero row is a ValueError) and the kept ones are returned as they are here, in order.  A polytope of Chebyshev radius <= tol
+        comes back unchanged."""
+        from .reduce import reduced_polytope
+        return reduced_polytope(self, tol=tol, device=device)

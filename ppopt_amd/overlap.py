@@ -22,7 +22,8 @@ tie rule of Solution.get_region).  The procedure is deterministic:
      radius(P n C) <= tol the piece stays; otherwise the children P n {earlier cutting rows} n {n_k.theta >= o_k} for every row k
      that cuts (the child's radius exceeds tol) replace it in row order, with rows: P's, the earlier cutting rows, the reversed row.
 
-The pieces of one source are convex, closed, and share boundaries only; they are not merged back and keep redundant rows.
+The pieces of one source are convex, closed, and share boundaries only; they are not merged back.  They keep redundant rows unless
+``reduce_rows`` is set, which removes them round by round (geometry/reduce.py; off by default).
 """
 import time
 from dataclasses import dataclass
@@ -100,16 +101,23 @@ def classify_pairs(radius, d_min, d_max, flag, equal, tol: float) -> numpy.ndarr
     return v
 
 
-def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces: int, stats: dict, items_key: str):
+def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces: int, stats: dict, items_key: str, reduce=None):
     """The rounds of a region difference (step 4 of the module docstring; exit_sets.py runs the same rounds against pulled-back
     cutters).  cutters[i]: the entries (cutter region j, extra row or None) that polytope i meets, one per round, in order.
     ``launch(piece_off, piece_rows, item_source, item_entries, item_start)`` runs the items of a round, item k being piece k, and returns
     (flag, mask, stats) of the library's split call; ``cutting_rows(source, entry, mask, flag)`` gives the ordered rows that cut an item
     whose piece meets its cutter.  Returns (live, round_ms): per source its pieces in order as (rows, or None for the source's own rows,
     wide: a run on the way to the piece was unbounded or capped), and the device ms of every round.  rounds, ``items_key``, lps, pivots,
-    wide, device_ms and max_item_rows are accumulated into ``stats``; ValueError in the name of ``who`` past MAX_ROWS or max_pieces."""
+    wide, device_ms and max_item_rows are accumulated into ``stats``; ValueError in the name of ``who`` past MAX_ROWS or max_pieces.
+    ``reduce(piece_off, piece_rows, start)``, when given, answers like _lib.reduce_rows (kept per row, status, wide, point, stats): the
+    children made in a round lose their redundant rows in one call per round, started from the source's point of xs, before the MAX_ROWS
+    check, which then applies to the reduced pieces; a child found thin is dropped, a wide one flags its piece, and ``stats`` gains
+    reduce_lps, reduce_ms and rows_removed (geometry/reduce.py)."""
     from . import _lib
     R, counts = len(off) - 1, numpy.diff(off)
+    if reduce is not None:
+        for k in ('reduce_lps', 'reduce_ms', 'rows_removed'):
+            stats.setdefault(k, 0.0 if k == 'reduce_ms' else 0)
     live = [[(None, False)] if usable[i] else [] for i in range(R)]
     round_ms = []
     for rnd in range(max((len(c) for c in cutters), default=0)):
@@ -133,6 +141,7 @@ def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, m
         stats['device_ms'] += s['ms']
         round_ms.append(s['ms'])
         q = 0
+        fresh = []     # (source, place in live[source]) of the children of this round, for ``reduce``
         for i in active:
             nxt = []
             for pc, wide in live[i]:
@@ -142,9 +151,29 @@ def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, m
                     cutting = cutting_rows(i, entries[q], mask[q], int(fl[q]))
                     w = wide or bool(fl[q] & _lib.OVERLAP_WIDE)
                     for k, row in enumerate(cutting):
+                        if reduce is not None:
+                            fresh.append((i, len(nxt)))
                         nxt.append((numpy.vstack([p_rows[q]] + cutting[:k] + [-row]), w))
                 q += 1
             live[i] = nxt
+        if fresh:
+            c_rows = [live[i][k][0] for i, k in fresh]
+            if max(len(rows) for rows in c_rows) > _lib.REDUCE_MAX_ROWS:
+                raise ValueError(f'{who}: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
+            coff = numpy.concatenate([[0], numpy.cumsum([len(rows) for rows in c_rows])]).astype(numpy.int64)
+            kept, c_status, c_wide, _, s = reduce(coff, numpy.vstack(c_rows), numpy.asarray([xs[i] for i, _ in fresh]))
+            stats['reduce_lps'] += s['lps']
+            stats['reduce_ms'] += s['ms']
+            stats['rows_removed'] += int(numpy.sum(~kept))
+            gone = set()
+            for n, (i, k) in enumerate(fresh):
+                if c_status[n] == _lib.REDUCE_THIN:
+                    gone.add((i, k))
+                else:
+                    live[i][k] = (c_rows[n][kept[coff[n]:coff[n + 1]]], live[i][k][1] or bool(c_wide[n]))
+            if gone:
+                for i in active:
+                    live[i] = [p for k, p in enumerate(live[i]) if (i, k) not in gone]
         if any(pc is not None and len(pc) > MAX_ROWS for i in active for pc, _ in live[i]):
             raise ValueError(f'{who}: a piece has more than {MAX_ROWS} rows after round {rnd + 1}')
         if sum(len(p) for p in live) > max_pieces:
@@ -153,10 +182,11 @@ def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, m
 
 
 def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20,
-                       device: int = 0, void=()) -> OverlapPartition:
+                       device: int = 0, void=(), reduce_rows: bool = False) -> OverlapPartition:
     """The partition of the polytopes {n.theta <= o} (unit rows ef_rows = [o | n] in CSR form by row_off) by the lowest affine value
     g_i.theta + h_i: an OverlapPartition.  Steps 2 to 4 of the module docstring; every LP runs on the device.  ``void``: polytopes
-    known to be empty (they vanish and cut nothing), like the ones the device finds empty."""
+    known to be empty (they vanish and cut nothing), like the ones the device finds empty.  ``reduce_rows``: the children of every
+    round lose their redundant rows (difference_rounds, ``reduce``)."""
     from . import _lib
     t0 = time.perf_counter()
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
@@ -238,7 +268,8 @@ def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, valu
         cj = ef[off[j]:off[j + 1]]
         return [cj[r] for r in mask_rows(mask, len(cj)).tolist()] + ([c] if flag & _lib.OVERLAP_CUT_ROW else [])
 
-    live, _ = difference_rounds('remove_overlaps', off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces, stats, 'work_items')
+    reduce = (lambda poff, prows, start: _lib.reduce_rows(poff, prows, start, tol, device)) if reduce_rows else None
+    live, _ = difference_rounds('remove_overlaps', off, ef, xs, usable, cutters, launch, cutting_rows, max_pieces, stats, 'work_items', reduce=reduce)
     live = [[pc for pc, _ in p] for p in live]
     pieces = [pc for i in range(R) for pc in live[i]]
     sources = numpy.asarray([i for i in range(R) for _ in live[i]], dtype=numpy.int64)
@@ -304,12 +335,13 @@ def check_source(source, tol: float, value_tol: float, max_pieces: int):
     return n_t, qv, rv
 
 
-def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0):
-    """Solution.remove_overlaps (the module docstring).  Returns a new Solution of ReducedRegion; the source is not modified."""
+def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0, reduce_rows: bool = False):
+    """Solution.remove_overlaps (the module docstring).  Returns a new Solution of ReducedRegion; the source is not modified.
+    ``reduce_rows``: the pieces lose their redundant rows round by round (partition_by_value)."""
     t0 = time.perf_counter()
     n_t, qv, rv = check_source(source, tol, value_tol, max_pieces)
     off, rows, void = solution_rows(source.critical_regions, n_t, 'remove_overlaps')
     part = partition_by_value(off, rows, qv, rv, n_t, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device,
-                              void=void)
+                              void=void, reduce_rows=reduce_rows)
     part.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
     return build_reduced_solution(source, part.sources, part.pieces, part.verdict_counts, part.vanished, part.stats)

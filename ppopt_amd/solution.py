@@ -45,6 +45,8 @@ class Solution:
     merge_info = None
     # set on the result of remove_overlaps (overlap.build_reduced_solution): source, sources, verdict_counts, vanished, stats
     overlap_info = None
+    # set on the result of reduce_rows (geometry.reduce.reduce_solution): source, kept, status, wide, stats
+    reduce_info = None
 
     def __init__(self, program, critical_regions: List[CriticalRegion], is_overlapping: bool = False,
                  point_location_tolerance: float = 1e-5):
@@ -92,16 +94,27 @@ class Solution:
         from .region_merge import merge_regions
         return merge_regions(self, outputs=outputs, tol=tol, law_tol=law_tol, device=device)
 
-    def remove_overlaps(self, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0) -> 'Solution':
+    def remove_overlaps(self, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0,
+                        reduce_rows: bool = False) -> 'Solution':
         """A new, non-overlapping solution: every region keeps only the part of the parameter space where its value function is the
         lowest among the regions that contain the point (ties to the higher index, as get_region resolves them), as convex pieces
         (overlap.ReducedRegion with ``source``), ordered by source; the pair comparisons and the region differences are LPs on the device
         (overlap.py).  ``overlap_info`` of the result holds the source, sources, verdict_counts, vanished and stats.
         ValueError before any launch for an empty or merged solution, n_theta > 16, a region of more than 256 rows, non-finite
         tolerances and value functions with different quadratic parts (mpQP / mpMIQP); after a round for a piece of more than 256
-        rows or more than max_pieces pieces."""
+        rows or more than max_pieces pieces.  ``reduce_rows``: the pieces lose their redundant rows round by round on the device, before
+        the row limit is checked (off by default)."""
         from .overlap import remove_overlaps
-        return remove_overlaps(self, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device)
+        return remove_overlaps(self, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows)
+
+    def reduce_rows(self, tol: float = 1e-8, device: int = 0) -> 'Solution':
+        """A new solution whose regions have lost their redundant rows by the sequential rule of geometry.reduce, for
+        the results of merge_regions and remove_overlaps: every region is copied and only its E, f are replaced by the rows that are kept,
+        in order and with their bits unchanged; merge_info and overlap_info are carried over and ``reduce_info`` holds the stats.  The
+        source is not modified.  ValueError before any launch for other solutions, n_theta > 16, a region of more than 512 rows and a
+        tol that is not finite and >= 0."""
+        from .geometry.reduce import reduce_solution
+        return reduce_solution(self, tol=tol, device=device)
 
     def evaluate_objective(self, theta_point) -> Optional[float]:
         self._refuse_merged('evaluate_objective')
@@ -317,16 +330,18 @@ class Solution:
         from .transition import transition_graph
         return transition_graph(self, A, B, inputs, c=c, tol=tol, full_radius=full_radius, device=device)
 
-    def exit_sets(self, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0):
+    def exit_sets(self, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0,
+                  reduce_rows: bool = False):
         """Where each region's next state leaves the solution under the plant theta+ = A theta + B u + c with this controller's law
         u = x*(theta)[inputs]: an exit_sets.ExitSets, the convex pieces of Chebyshev radius above tol of X_i = R_i minus the states whose
         image lies in some region (pieces_of, contains, polytopes, volumes; whole[i]: region i leaves entirely).  The regions cut out of
         R_i are its successors in ``graph``, the transition_graph of the same arguments (built when None); one device launch per round
         of the region difference.  A run that is unbounded or capped keeps its piece and flags it wide: the pieces never lose a state
         that exits.  Refusals as for transition_graph, and ValueError after a round that leaves a piece above 256 rows or more than
-        max_pieces pieces.  See exit_sets.py and DESIGN §3.21."""
+        max_pieces pieces.  ``reduce_rows``: the pieces lose their redundant rows round by round on the device, before the row limit is
+        checked (off by default); ExitSets.reduced() does the same to a finished result.  See exit_sets.py and DESIGN §3.21."""
         from .exit_sets import exit_sets
-        return exit_sets(self, A, B, inputs, c=c, tol=tol, graph=graph, max_pieces=max_pieces, device=device)
+        return exit_sets(self, A, B, inputs, c=c, tol=tol, graph=graph, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows)
 
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):

@@ -1,6 +1,6 @@
-// geometry_refusals.hip -- the argument checking of the merge, overlap, transition and exit calls (mpc_merge_regions, mpc_merge_pairs,
-// mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split) as a stand-alone host program for a
-// sanitizer build:
+// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit and reduce calls (mpc_merge_regions, mpc_merge_pairs,
+// mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split, mpc_reduce_rows) as a stand-alone host
+// program for a sanitizer build:
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/geometry_refusals.hip -o geometry_refusals
 // It includes geometry.hip itself and stands in for the pools of mpcombi_hip.hip, which a refusal never reaches: every call below must
 // come back MPC_ERR_INVALID with a message before a device is selected (an empty batch: MPC_OK), so the program needs no GPU and
@@ -285,11 +285,62 @@ static void exit_cases() {
                                                                 nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr), MPC_OK);
 }
 
+// mpc_reduce_rows
+static void reduce_cases() {
+    const int nt = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    VI status(2), wide(2);
+    std::vector<uint64_t> kept(2 * MPC_REDUCE_WORDS);
+    VD point(4);
+    int64_t stats[5];
+    float ms = 0.0f;
+    struct Args { int n_t; VL off; VD ef, start; double tol; };
+    const Args good{nt, {0, 4, 8}, ef, {0.5, 0.5, 1.0, 0.5}, 1e-8};
+    auto reduce = [&](const Args &g, int64_t n_poly = -2) {
+        return mpc_reduce_rows(0, g.n_t, n_poly == -2 ? (int64_t)g.off.size() - 1 : n_poly, g.off.data(), g.ef.data(), g.start.data(), g.tol, status.data(),
+                               wide.data(), kept.data(), point.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;                                                                                            // 513 rows
+    for (int r = 0; r < 128; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    big.insert(big.end(), sq.begin(), sq.begin() + 3);
+    expect("n_t = 0", reduce(with([](Args &g) { g.n_t = 0; })));
+    expect("n_t = 17", reduce(with([](Args &g) { g.n_t = 17; })));
+    expect("tol < 0", reduce(with([](Args &g) { g.tol = -1.0; })));
+    expect("tol NaN", reduce(with([&](Args &g) { g.tol = nan; })));
+    expect("tol inf", reduce(with([](Args &g) { g.tol = INFINITY; })));
+    expect("n_poly < 0", reduce(good, -1));
+    expect("n_poly = 2^31", reduce(good, 0x80000000ll));
+    expect("row_off[0] != 0", reduce(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("row_off decreases", reduce(with([](Args &g) { g.off = {0, 8, 4}; })));
+    expect("a polytope without rows", reduce(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("a polytope of 513 rows", reduce(with([&](Args &g) { g.off = {0, 513}; g.ef = big; g.start.resize(2); })));
+    expect("a non-finite row", reduce(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("a row that is not unit", reduce(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("start NaN", reduce(with([&](Args &g) { g.start[1] = nan; })));
+    expect("start inf", reduce(with([](Args &g) { g.start[2] = INFINITY; })));
+    const Args &g = good;
+    auto raw = [&](const int64_t *off, const double *rows, int32_t *st, int32_t *wd, uint64_t *kp) {
+        return mpc_reduce_rows(0, nt, 2, off, rows, nullptr, 1e-8, st, wd, kp, nullptr, nullptr, nullptr);
+    };
+    expect("missing row_off", raw(nullptr, g.ef.data(), status.data(), wide.data(), kept.data()));
+    expect("missing ef_rows", raw(g.off.data(), nullptr, status.data(), wide.data(), kept.data()));
+    expect("missing status", raw(g.off.data(), g.ef.data(), nullptr, wide.data(), kept.data()));
+    expect("missing wide", raw(g.off.data(), g.ef.data(), status.data(), nullptr, kept.data()));
+    expect("missing kept", raw(g.off.data(), g.ef.data(), status.data(), wide.data(), nullptr));
+    expect("no polytopes is MPC_OK without a launch", reduce(with([](Args &a) { a.off = {0}; a.ef.clear(); a.start.clear(); })), MPC_OK);
+    expect("no polytopes, no arrays", mpc_reduce_rows(0, nt, 0, nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), MPC_OK);
+}
+
 int main() {
     merge_cases();
     overlap_cases();
     transition_cases();
     exit_cases();
+    reduce_cases();
     std::printf("%d unexpected\n", n_bad);
     return n_bad ? 1 : 0;
 }
