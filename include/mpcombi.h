@@ -829,6 +829,45 @@ int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t
 int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const double *start, double tol,
                     int32_t *status, int32_t *wide, uint64_t *kept, double *point, int64_t *stats, float *ms);
 
+/* ---- backward exit cells of a closed loop (Solution.invariant_set) --------------------------------------------------- */
+/* Regions and maps as for the transition and exit calls above; xs [n_regions][n_t] is a feasible point of every region (mpc_merge_regions).
+ * A CELL is a polytope of 1..256 unit rows that lies in region source[c].  The cells of step 0 are given (the exit pieces of
+ * Solution.exit_sets); a cell of step k + 1 is R_i n f_i^-1(Q) for a cell Q of step k and a region i of pred_idx[pred_off[j] ..
+ * pred_off[j + 1]), j = source(Q): the states of R_i whose next state lies in Q.  Stateless; an error text is read with mpc_last_error(NULL).
+ *
+ * mpc_backward_exits runs every step itself.  The items of a step are ordered by parent cell, then as the predecessor list is; per item
+ *   (k_pre_cells, one wavefront): the rows of Q pulled back through the map of i exactly as mpc_transition_pairs forms them (a constant row
+ *   with right-hand side below -tol: no cell and no LP; any other constant row is dropped); the radius of R_i's rows and the pulled-back
+ *   ones from xs[i], stopped once it exceeds tol (optimal and not above tol: no cell; unbounded or capped: a cell, flagged wide: it may hold states that stay); for a cell
+ *   the sequential rule of mpc_reduce_rows over R_i's rows, then the pulled-back ones, every run started where the radius run ended.  The
+ *   kept rows become the cell (k_pre_emit), appended to the cell table ON THE DEVICE: between steps only per-item status words and counts
+ *   come to the host, which scans the offsets and lists the next items.  The iteration ends when a step yields no cell.
+ *   max_steps        at most so many steps are run (>= 0).  max_cells, max_rows_total: the capacity of the output arrays, step 0 included.
+ *   n_cells, cell_off [n_cells + 1], cell_rows [cell_off[n_cells]][n_t + 1], cell_source, cell_step, cell_parent (-1 at step 0, else the
+ *   index of Q), cell_wide (its own radius run or an ancestor's was unbounded or capped): all cells, step by step, a step in item order.
+ *   cell_point       [max_cells][n_t] or NULL: for the cells of the steps >= 1, where the radius run ended (rows of step 0 are not written).
+ *   status           MPC_BACKWARD_CONVERGED; MPC_BACKWARD_MAX_STEPS: max_steps steps were run and the last one had cells with
+ *                    predecessors; MPC_BACKWARD_ROWS: a reduced cell keeps more than 256 rows; MPC_BACKWARD_MAX_CELLS,
+ *                    MPC_BACKWARD_MAX_ROWS_TOTAL: a step did not fit.  After the last three the cells of the completed steps are returned.
+ *   steps            the completed steps that yielded cells; converged: status == MPC_BACKWARD_CONVERGED.
+ *   cells_per_step   [max_steps + 1]; step_ms [max_steps] (either may be NULL): device ms of step k + 1, the one that found nothing included.
+ *   stats (may be NULL): [0] items, [1] cells found, [2] items emptied by a constant row, [3] LPs, [4] pivots, [5] unbounded or capped runs.
+ *   n_cells0 == 0 or max_steps == 0: MPC_OK without a launch (step 0 is returned).
+ * MPC_ERR_INVALID with a message, before a device is selected: everything mpc_exit_split refuses (cells for pieces), xs not finite, an index
+ * out of range in pred_idx or cell_source0, pred_off not non-decreasing from 0, max_steps < 0, step 0 larger than max_cells or
+ * max_rows_total, a missing array.  Deterministic: atomics only in the counters. */
+#define MPC_BACKWARD_CONVERGED 0
+#define MPC_BACKWARD_MAX_STEPS 1
+#define MPC_BACKWARD_ROWS 2
+#define MPC_BACKWARD_MAX_CELLS 3
+#define MPC_BACKWARD_MAX_ROWS_TOTAL 4
+int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                       const double *phi, const double *xs, const int64_t *pred_off, const int32_t *pred_idx, int64_t n_cells0,
+                       const int64_t *cell_off0, const double *cell_rows0, const int32_t *cell_source0, double tol, int32_t max_steps,
+                       int64_t max_cells, int64_t max_rows_total, int64_t *n_cells, int64_t *cell_off, double *cell_rows, int32_t *cell_source,
+                       int32_t *cell_step, int32_t *cell_parent, int32_t *cell_wide, double *cell_point, int32_t *status, int32_t *steps,
+                       int32_t *converged, int64_t *cells_per_step, float *step_ms, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,6 +281,9 @@ def load():
                                           _ip, _ip, _ip, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_reduce_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double, _ip, _ip, _u64p, _dp, _lp,
                                            ctypes.POINTER(ctypes.c_float)]),
+        'mpc_backward_exits': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _lp, _ip, ctypes.c_int64, _lp, _dp,
+                                              _ip, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _lp, _lp, _dp, _ip, _ip, _ip, _ip, _dp,
+                                              _ip, _ip, _ip, _lp, ctypes.POINTER(ctypes.c_float), _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -301,7 +304,8 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_level_pruned_new_device', 'mpc_level_regions_device', 'mpc_frontier_advance', 'mpc_qp_solve_batch', 'mpc_facet_centres', 'mpc_graph_begin', 'mpc_graph_wave', 'mpc_graph_group_run', 'mpc_graph_wave_close', 'mpc_check_level', 'mpc_lp_solve_batch', 'mpc_miqp_solve_batch', 'mpc_hit_and_run', 'mpc_slice_polygons', 'mpc_slice_intervals',
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
-                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows']
+                    'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
+                    'mpc_backward_exits']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1431,6 +1435,51 @@ def reduce_rows(row_off, ef_rows, start, tol: float, device: int = 0):
     k = numpy.arange(len(ef)) - numpy.repeat(off[:-1], counts)
     kept = ((mask[poly, k >> 6] >> (k & 63).astype(numpy.uint64)) & numpy.uint64(1)).astype(bool)
     return kept, status, wide, point, stats
+
+
+# status of mpc_backward_exits (include/mpcombi.h)
+BACKWARD_CONVERGED, BACKWARD_MAX_STEPS, BACKWARD_ROWS, BACKWARD_MAX_CELLS, BACKWARD_MAX_ROWS_TOTAL = range(5)
+BACKWARD_STATUS = ('CONVERGED', 'MAX_STEPS', 'ROWS', 'MAX_CELLS', 'MAX_ROWS_TOTAL')
+
+
+def backward_exits(row_off, ef_rows, Phi, phi, xs, pred_off, pred_idx, cell_off, cell_rows, cell_source, tol: float, max_steps: int, max_cells: int,
+                   max_rows_total: int, device: int = 0):
+    """The backward exit cells of a closed loop, every step in one call (include/mpcombi.h, mpc_backward_exits).  A dict: cell_off,
+    cell_rows, source, step, parent, wide (bool), point (NaN rows at step 0), status (BACKWARD_*), steps, converged, cells_per_step
+    [steps + 1], step_ms [max_steps] and stats (items, cells, empty, lps, pivots, wide, ms)."""
+    who = 'backward_exits'
+    off, ef = _merge_rows(who, row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    P, p, x = _transition_maps(who, R, n_t, Phi, phi, xs)
+    poff = numpy.ascontiguousarray(pred_off, dtype=numpy.int64).reshape(-1)
+    pidx = numpy.ascontiguousarray(pred_idx, dtype=numpy.int32).reshape(-1)
+    if len(poff) != R + 1 or (len(poff) and poff[-1] != len(pidx)):
+        raise MpcError(f'{who}: pred_off [regions + 1] must end at the length of pred_idx')
+    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
+    crow = _f64(numpy.asarray(cell_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
+    csrc = numpy.ascontiguousarray(cell_source, dtype=numpy.int32).reshape(-1)
+    if len(coff) != len(csrc) + 1 or coff[0] != 0 or coff[-1] != len(crow):
+        raise MpcError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one source per cell')
+    max_steps, max_cells, max_rows_total = int(max_steps), int(max_cells), int(max_rows_total)
+    if max_cells < 0 or max_rows_total < 0:
+        raise MpcError(f'{who}: max_cells and max_rows_total must be >= 0')
+    # capacity, not contents: pages the library never writes are never touched
+    out_off, out_rows = numpy.empty(max_cells + 1, dtype=numpy.int64), numpy.empty((max_rows_total, n_t + 1))
+    src, step, parent, wide = (numpy.empty(max_cells, dtype=numpy.int32) for _ in range(4))
+    point = numpy.empty((max_cells, n_t))
+    n, status, steps, conv = numpy.zeros(1, dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32)
+    per_step = numpy.zeros(max(max_steps, 0) + 1, dtype=numpy.int64)
+    step_ms = numpy.zeros(max(max_steps, 1), dtype=numpy.float32)
+    stats = _geometry_call('mpc_backward_exits', ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'), int(device), n_t, R, off, ef, P, p, x, poff, pidx,
+                           len(csrc), coff, crow, csrc, float(tol), max_steps, max_cells, max_rows_total, n, out_off, out_rows, src, step, parent, wide,
+                           point, status, steps, conv, per_step, step_ms.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    n, n0, k = int(n[0]), len(csrc), int(steps[0])
+    pt = point[:n].copy()
+    pt[:min(n0, n)] = numpy.nan
+    return {'cell_off': out_off[:n + 1].copy(), 'cell_rows': out_rows[:int(out_off[n])].copy(), 'source': src[:n].astype(numpy.int64),
+            'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': pt,
+            'status': int(status[0]), 'steps': k, 'converged': bool(conv[0]), 'cells_per_step': per_step[:k + 1].copy(),
+            'step_ms': step_ms[:max(max_steps, 0)].astype(numpy.float64), 'stats': stats}
 
 
 class Locator:

@@ -25,6 +25,7 @@
 #include "transition.hpp"
 #include "exit_sets.hpp"
 #include "reduce.hpp"
+#include "invariant.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1173,8 +1174,8 @@ extern "C" int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, c
                      budget, volume, centroid, n_simplices, status, second_moment, stats);
 }
 
-// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets, row reduction ----------
-// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp)  Every call checks its arguments in one order
+// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets, row reduction, backward exits
+// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, invariant.hpp)  Every call checks its arguments in one order
 // (regions, pieces, tol, the item count, the dense arrays, the empty batch, missing arrays, the index arrays, the rest), uploads,
 // launches one wavefront per item over unit rows [o | n] in LDS, and downloads the results and its counters.  What the calls share is
 // here once: the checkers return the refusal, family_launch and family_close are the two ends of the device part.
@@ -1563,4 +1564,191 @@ extern "C" int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, cons
     s.download(kept, d_k, words);
     if (point) s.download(point, *d_point, np * n_t * 8);
     return family_close(s, d_cnt, 5, stats, ms);
+}
+
+// ---- backward exit cells of a closed loop (invariant.hpp) ---------------------------------------------------------------
+// The one call of the family that loops: the cell table (offsets, rows, points) stays on the device and grows step by step; per step the
+// item list goes up, status and n_kept come down, the host scans the offsets and lists the next items.
+extern "C" int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                                  const double *phi, const double *xs, const int64_t *pred_off, const int32_t *pred_idx, int64_t n_cells0,
+                                  const int64_t *cell_off0, const double *cell_rows0, const int32_t *cell_source0, double tol, int32_t max_steps,
+                                  int64_t max_cells, int64_t max_rows_total, int64_t *n_cells, int64_t *cell_off, double *cell_rows,
+                                  int32_t *cell_source, int32_t *cell_step, int32_t *cell_parent, int32_t *cell_wide, double *cell_point,
+                                  int32_t *status, int32_t *steps, int32_t *converged, int64_t *cells_per_step, float *step_ms, int64_t *stats,
+                                  float *ms) {
+    const char *who = "mpc_backward_exits";
+    family_open(stats, 6, ms);
+    if (n_cells) *n_cells = 0;
+    if (steps) *steps = 0;
+    if (converged) *converged = 0;
+    if (status) *status = MPC_BACKWARD_MAX_STEPS;
+    int m_reg = 1, m_cell = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
+    if (int rc = merge_check("mpc_backward_exits (cells)", n_t, n_cells0, cell_off0, cell_rows0, &m_cell)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, true, xs)) return rc;
+    if (max_steps < 0) return bad(who, "max_steps must be >= 0");
+    if (max_cells < 0 || max_cells > 0x7fffffffll || max_rows_total < 0) return bad(who, "max_cells must lie in 0..2^31 - 1 and max_rows_total be >= 0");
+    if (!n_cells || !status || !steps || !converged) return bad(who, "missing output (n_cells, status, steps or converged)");
+    if (n_regions > 0) {
+        if (!pred_off || pred_off[0] != 0) return bad(who, "pred_off must start at 0");
+        for (int64_t i = 0; i < n_regions; ++i)
+            if (pred_off[i + 1] < pred_off[i]) return bad(who, "pred_off must not decrease");
+        if (pred_off[n_regions] > 0 && !pred_idx) return bad(who, "missing pred_idx");
+        for (int64_t k = 0; k < pred_off[n_regions]; ++k)
+            if (pred_idx[k] < 0 || pred_idx[k] >= n_regions) return bad(who, "a predecessor list names a region out of range");
+    }
+    const int64_t rows0 = n_cells0 > 0 ? cell_off0[n_cells0] : 0;
+    if (n_cells0 > 0) {
+        if (!cell_source0) return bad(who, "missing cell_source0");
+        for (int64_t c = 0; c < n_cells0; ++c)
+            if (cell_source0[c] < 0 || cell_source0[c] >= n_regions) return bad(who, "a cell names a source region out of range");
+        if (n_cells0 > max_cells || rows0 > max_rows_total) return bad(who, "the cells of step 0 exceed max_cells or max_rows_total");
+        if (!cell_off || !cell_rows || !cell_source || !cell_step || !cell_parent || !cell_wide) return bad(who, "missing output array");
+    }
+    // the host's side of the cell table: everything but the rows
+    std::vector<int64_t> off(1, 0);
+    std::vector<int32_t> src, stp, par, wid;
+    if (n_cells0 > 0) {
+        off.assign(cell_off0, cell_off0 + n_cells0 + 1);
+        src.assign(cell_source0, cell_source0 + n_cells0);
+        stp.assign((size_t)n_cells0, 0);
+        par.assign((size_t)n_cells0, -1);
+        wid.assign((size_t)n_cells0, 0);
+    }
+    const size_t nr = (size_t)n_regions, w = (size_t)n_t + 1;
+    auto deliver = [&](int code, int n_steps) {
+        const size_t nc = src.size();
+        *n_cells = (int64_t)nc;
+        *status = code;
+        *steps = n_steps;
+        *converged = code == MPC_BACKWARD_CONVERGED;
+        if (cell_off) std::memcpy(cell_off, off.data(), (nc + 1) * 8);
+        if (nc) {
+            std::memcpy(cell_source, src.data(), nc * 4);
+            std::memcpy(cell_step, stp.data(), nc * 4);
+            std::memcpy(cell_parent, par.data(), nc * 4);
+            std::memcpy(cell_wide, wid.data(), nc * 4);
+        }
+    };
+    if (cells_per_step) {
+        for (int k = 0; k <= max_steps; ++k) cells_per_step[k] = 0;
+        cells_per_step[0] = n_cells0;
+    }
+    if (step_ms) for (int k = 0; k < max_steps; ++k) step_ms[k] = 0.0f;
+    if (n_cells0 == 0 || max_steps == 0) {
+        deliver(n_cells0 == 0 ? MPC_BACKWARD_CONVERGED : MPC_BACKWARD_MAX_STEPS, 0);
+        if (n_cells0 > 0) std::memcpy(cell_rows, cell_rows0, (size_t)rows0 * w * 8);
+        return MPC_OK;
+    }
+    if (int rc = select_device(nullptr, device)) return rc;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
+    DevBuf &d_coff = s.upload(off.data(), off.size() * 8), &d_crow = s.upload(cell_rows0, (size_t)rows0 * w * 8);
+    DevBuf &d_cpt = s.buf((size_t)n_cells0 * n_t * 8), &d_cnt = family_counters(s, 6);
+    DevBuf &d_ir = s.buf(), &d_ic = s.buf(), &d_ci = s.buf(), &d_st = s.buf(), &d_nk = s.buf(), &d_kept = s.buf(), &d_pt = s.buf();
+    auto grow = [&](DevBuf &b, size_t bytes) { if (s.ok()) s.chk(b.ensure(bytes, s.st, true)); };   // keeps what the table holds
+    std::vector<int32_t> item_region, item_cell, st, nk, cell_item;
+    int64_t lo = 0, hi = n_cells0;      // the cells of the last completed step
+    int step = 0, code = MPC_BACKWARD_CONVERGED;
+    float total_ms = 0.0f;
+    for (;;) {
+        // the items of step + 1: by parent cell, then as the predecessor list is
+        item_region.clear();
+        item_cell.clear();
+        int item_rows = 2;
+        bool too_many = false;
+        for (int64_t c = lo; c < hi && !too_many; ++c) {
+            const int64_t j = src[(size_t)c], m_q = off[(size_t)c + 1] - off[(size_t)c];
+            for (int64_t k = pred_off[j]; k < pred_off[j + 1]; ++k) {
+                const int32_t i = pred_idx[k];
+                item_region.push_back(i);
+                item_cell.push_back((int32_t)c);
+                item_rows = std::max<int>(item_rows, (int)(row_off[i + 1] - row_off[i] + m_q));
+            }
+            too_many = item_region.size() > 0x7fffffffull;
+        }
+        if (item_region.empty()) break;                                       // nothing can precede the last cells: converged
+        if (step == max_steps) { code = MPC_BACKWARD_MAX_STEPS; break; }
+        if (too_many) { code = MPC_BACKWARD_MAX_CELLS; break; }
+        const size_t ni = item_region.size();
+        const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_kept adds 64)
+        s.upload(d_ir, item_region.data(), ni * 4);
+        s.upload(d_ic, item_cell.data(), ni * 4);
+        s.ensure(d_st, ni * 4); s.ensure(d_nk, ni * 4); s.ensure(d_kept, ni * RD_WORDS * 8); s.ensure(d_pt, ni * n_t * 8);
+        PreCellArgs a{};
+        a.nt = n_t; a.m_max = item_rows; a.n_items = (long long)ni;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = d_coff.as<long long>(); a.cell_ef = d_crow.as<double>();
+        a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>(); a.xs = d_xs.as<double>();
+        a.item_region = d_ir.as<int32_t>(); a.item_cell = d_ic.as<int32_t>(); a.tol = tol;
+        a.status = d_st.as<int32_t>(); a.n_kept = d_nk.as<int32_t>(); a.kept = d_kept.as<unsigned long long>();
+        a.point = d_pt.as<double>(); a.counters = d_cnt.as<unsigned long long>();
+        family_launch(s, k_pre_cells, (int64_t)ni, lds, a);
+        st.resize(ni); nk.resize(ni);
+        s.download(st.data(), d_st, ni * 4);        // blocking copies on the null stream: the launch has ended
+        s.download(nk.data(), d_nk, ni * 4);
+        float t_cells = 0.0f, t_emit = 0.0f;
+        s.elapsed(&t_cells);
+        if (!s.ok()) break;
+        // the scan: the cells of this step in item order
+        cell_item.clear();
+        int64_t new_rows = 0;
+        bool fat = false;
+        for (size_t q = 0; q < ni; ++q) {
+            if (st[q] != PC_CELL && st[q] != PC_CELL_WIDE) continue;
+            fat = fat || nk[q] < 1 || nk[q] > OV_MAX_ROWS;
+            cell_item.push_back((int32_t)q);
+            new_rows += nk[q];
+        }
+        const size_t nn = cell_item.size(), nc = src.size();
+        if (nn && fat) code = MPC_BACKWARD_ROWS;
+        else if (nn && (int64_t)(nc + nn) > max_cells) code = MPC_BACKWARD_MAX_CELLS;
+        else if (nn && off.back() + new_rows > max_rows_total) code = MPC_BACKWARD_MAX_ROWS_TOTAL;
+        if (nn && code == MPC_BACKWARD_CONVERGED) {
+            for (size_t c = 0; c < nn; ++c) {
+                const size_t q = (size_t)cell_item[c], parent = (size_t)item_cell[q];
+                off.push_back(off.back() + nk[q]);
+                src.push_back(item_region[q]);
+                stp.push_back(step + 1);
+                par.push_back((int32_t)parent);
+                wid.push_back(st[q] == PC_CELL_WIDE || wid[parent] ? 1 : 0);
+            }
+            grow(d_coff, (nc + nn + 1) * 8);
+            grow(d_crow, (size_t)off.back() * w * 8);
+            grow(d_cpt, (nc + nn) * n_t * 8);
+            if (s.ok()) s.chk(hipMemcpy(d_coff.as<int64_t>() + nc + 1, off.data() + nc + 1, nn * 8, hipMemcpyHostToDevice));
+            s.upload(d_ci, cell_item.data(), nn * 4);
+            PreEmitArgs e{};
+            e.nt = n_t; e.m_max = item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc;
+            e.row_off = d.off.as<long long>(); e.cell_off = d_coff.as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = d_crow.as<double>();
+            e.Phi = d_Phi.as<double>(); e.phi = d_phi.as<double>(); e.item_region = d_ir.as<int32_t>(); e.item_cell = d_ic.as<int32_t>();
+            e.cell_item = d_ci.as<int32_t>(); e.kept = d_kept.as<unsigned long long>(); e.point = d_pt.as<double>();
+            e.cell_point = d_cpt.as<double>(); e.tol = tol;
+            family_launch(s, k_pre_emit, (int64_t)nn, lds, e);
+            if (s.ok()) s.chk(hipEventSynchronize(s.e1));
+            s.elapsed(&t_emit);
+            if (!s.ok()) break;
+        }
+        if (step_ms && step < max_steps) step_ms[step] = t_cells + t_emit;
+        total_ms += t_cells + t_emit;
+        if (!nn || code != MPC_BACKWARD_CONVERGED) break;                     // a step without a cell: converged
+        ++step;
+        if (cells_per_step) cells_per_step[step] = (int64_t)nn;
+        lo = hi;
+        hi += (int64_t)nn;
+    }
+    if (!s.ok()) return s.finish();
+    const size_t nc = src.size();
+    s.download(cell_rows, d_crow, (size_t)off.back() * w * 8);
+    if (cell_point && nc > (size_t)n_cells0 && s.ok())
+        s.chk(hipMemcpy(cell_point + (size_t)n_cells0 * n_t, d_cpt.as<double>() + (size_t)n_cells0 * n_t, (nc - (size_t)n_cells0) * n_t * 8,
+                        hipMemcpyDeviceToHost));
+    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (const int rc = s.finish()) return rc;
+    if (stats) for (int i = 0; i < 6; ++i) stats[i] = (int64_t)cnt[i];
+    if (ms) *ms = total_ms;
+    deliver(code, step);
+    return MPC_OK;
 }

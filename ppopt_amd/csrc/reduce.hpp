@@ -41,10 +41,39 @@ struct ReduceArgs {
     unsigned long long *counters;         // polytopes, thin ones, LPs, pivots, unbounded or capped runs
 };
 
+// The row loop of the header comment over the LDS rows [0, m), every run started from px (lane i holds theta_i): kept bit k is set for
+// a row that stays.  SKIP_DROPPED: a slot that is a dropped row already (flag 2, a constant row of ts_pull_back; k_reduce_rows has
+// none) is passed over without an LP and without a bit.  s_kept is zeroed by the caller; no barrier behind the last row.
+template <bool SKIP_DROPPED>
+__device__ inline void rd_row_loop(const TrLds &S, int m, int nt, double tol, double px, unsigned long long &pivots, unsigned long long &lps,
+                                   unsigned long long &wide, unsigned long long *s_kept) {
+    const int lane = threadIdx.x & 63, nr = nt + 1;
+    for (int k = 0; k < m; ++k) {
+        __syncthreads();
+        if (SKIP_DROPPED && S.flag[k] == 2) continue;
+        const double v = lane < nt ? S.A[k * nr + lane] : 0.0, rhs = S.b[k];
+        __syncthreads();
+        if (lane < nt) { S.A[k * nr + lane] = -v; S.x[lane] = px; }
+        if (lane == 0) { S.b[k] = -rhs; S.flag[k] = 0; }
+        const int st = ov_radius(S, m, nt, tol, pivots);
+        ++lps;
+        wide += st == TR_UNBOUNDED || st == TR_CAPPED;
+        const bool redundant = st == TR_OPTIMAL && !(S.x[nt] > tol);
+        __syncthreads();
+        if (redundant) {
+            if (lane <= nt) S.A[k * nr + lane] = 0.0;
+            if (lane == 0) { S.b[k] = INFINITY; S.flag[k] = 2; }
+        } else {
+            if (lane < nt) S.A[k * nr + lane] = v;
+            if (lane == 0) { S.b[k] = rhs; s_kept[k >> 6] |= 1ull << (k & 63); }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(64) k_reduce_rows(ReduceArgs a) {
     extern __shared__ double rd_smem[];
     __shared__ unsigned long long s_kept[RD_WORDS];
-    const int lane = threadIdx.x & 63, nt = a.nt, nr = nt + 1;
+    const int lane = threadIdx.x & 63, nt = a.nt;
     const long long q = blockIdx.x;
     if (q >= a.n_poly) return;
     const TrLds S = tr_lds(rd_smem, a.m_max, nt);
@@ -65,25 +94,7 @@ __global__ void __launch_bounds__(64) k_reduce_rows(ReduceArgs a) {
             s_kept[lane] = left >= 64 ? ~0ull : left > 0 ? (1ull << left) - 1ull : 0ull;
         }
     } else {
-        for (int k = 0; k < m; ++k) {
-            __syncthreads();
-            const double v = lane < nt ? S.A[k * nr + lane] : 0.0, rhs = S.b[k];
-            __syncthreads();
-            if (lane < nt) { S.A[k * nr + lane] = -v; S.x[lane] = px; }
-            if (lane == 0) { S.b[k] = -rhs; S.flag[k] = 0; }
-            st = ov_radius(S, m, nt, tol, pivots);
-            ++lps;
-            wide += st == TR_UNBOUNDED || st == TR_CAPPED;
-            const bool redundant = st == TR_OPTIMAL && !(S.x[nt] > tol);
-            __syncthreads();
-            if (redundant) {
-                if (lane <= nt) S.A[k * nr + lane] = 0.0;
-                if (lane == 0) { S.b[k] = INFINITY; S.flag[k] = 2; }
-            } else {
-                if (lane < nt) S.A[k * nr + lane] = v;
-                if (lane == 0) { S.b[k] = rhs; s_kept[k >> 6] |= 1ull << (k & 63); }
-            }
-        }
+        rd_row_loop<false>(S, m, nt, tol, px, pivots, lps, wide, s_kept);
     }
     __syncthreads();
     if (lane < RD_WORDS) a.kept[q * RD_WORDS + lane] = s_kept[lane];

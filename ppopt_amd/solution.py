@@ -343,6 +343,19 @@ class Solution:
         from .exit_sets import exit_sets
         return exit_sets(self, A, B, inputs, c=c, tol=tol, graph=graph, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows)
 
+    def invariant_set(self, A, B, inputs, c=None, tol: float = 1e-8, graph=None, exits=None, max_steps: int = 64, max_cells: int = 1 << 20,
+                      reduce_rows: bool = True, device: int = 0):
+        """From which states the loop under the plant theta+ = A theta + B u + c with this controller's law u = x*(theta)[inputs] stays
+        inside the solution for ever, and after how many steps the others leave: an invariant_set.InvariantSet, the cells of radius above
+        tol whose states leave after exactly step + 1 steps (cells_of, exit_step, contains, polytopes, volumes, pieces).  Step 0 is
+        ``exits``, the exit_sets of the same arguments, the predecessors come from ``graph``, the transition_graph (each built when None);
+        every later step runs on the device inside one library call, until a step yields no cell (converged) or max_steps, max_cells or
+        the 256-row limit of a cell stops it (status).  Wide cells over-approximate what leaves; parts thinner than tol are not reported.
+        Refusals as for transition_graph.  See invariant_set.py and DESIGN §3.23."""
+        from .invariant_set import invariant_set
+        return invariant_set(self, A, B, inputs, c=c, tol=tol, graph=graph, exits=exits, max_steps=max_steps, max_cells=max_cells,
+                             reduce_rows=reduce_rows, device=device)
+
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):
         """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial
