@@ -1,5 +1,6 @@
-// host_common.hpp -- what the host code of mpcombi_hip.hip (the engine) and geometry.hip shares: the process-wide pools of device
-// blocks, pinned host blocks, streams and events, the error channel, and the scaffold of a one-shot call (OneShot).
+// host_common.hpp -- what the host code of mpcombi_hip.hip (the engine), geometry.hip and points.hip shares: the process-wide pools
+// of device blocks, pinned host blocks, streams and events, the error channel, the scaffold of a one-shot call (OneShot), and the two
+// calls of points.hip that the engine makes.
 //
 // Host code only; no kernels.  The pool state itself (mutexes, free maps, the thread-local error string, the CU-count cache) is
 // defined exactly once, in mpcombi_hip.hip: every unit recycles the same blocks, streams and events.
@@ -115,18 +116,21 @@ inline int select_device(const char *who, int32_t device) {
 // the launch.  OneShot owns them.  Its error is sticky: once a step has failed, buffers, copies and launches become no-ops, so the
 // steps can be written one after the other; a caller looks at ok() only before the HOST reads what a download brought.
 // stream == nullptr: the default stream with blocking copies and hipDeviceSynchronize at the end; otherwise asynchronous copies
-// on that stream and hipStreamSynchronize.
+// on that stream and hipStreamSynchronize.  OwnStream: a stream of the pool, taken for this call and returned behind its last
+// wait -- callers on other threads / handles keep running (no device-wide synchronisation).
 struct OneShot {
+    struct OwnStream {};
     const char *who;   // the entry point: the error text is "<who>: <hipGetErrorString>"
     hipStream_t st;
     hipEvent_t e0 = nullptr, e1 = nullptr;   // timed: around launch_timed
     hipError_t err = hipSuccess;
     std::deque<DevBuf> bufs;   // a deque: references handed out stay valid
-    bool open = true, synced = false;
+    bool open = true, synced = false, own = false;
 
     explicit OneShot(const char *who_, hipStream_t st_ = nullptr, bool timed = false) : who(who_), st(st_) {
         if (timed) { chk(hipEventCreate(&e0)); chk(hipEventCreate(&e1)); }
     }
+    OneShot(const char *who_, OwnStream) : who(who_), st(nullptr), own(true) { chk(pooled_stream(&st)); }
     OneShot(const OneShot &) = delete;
     OneShot &operator=(const OneShot &) = delete;
     ~OneShot() { close(); }
@@ -159,8 +163,8 @@ struct OneShot {
     void elapsed(float *ms) { if (ok() && ms) chk(hipEventElapsedTime(ms, e0, e1)); }
     // waits for everything queued so far and reports its error: for a caller that reads elapsed times or enqueues nothing more
     void sync() { synced = chk(st ? hipStreamSynchronize(st) : hipDeviceSynchronize()); }
-    // synchronises (unless sync() just has; what that last wait returns is not the call's error), then gives the events and
-    // every buffer back; the destructor does it on any other way out
+    // synchronises (unless sync() just has; what that last wait returns is not the call's error), then gives the events, every
+    // buffer and an own stream back; the destructor does it on any other way out
     void close() {
         if (!open) return;
         open = false;
@@ -168,12 +172,23 @@ struct OneShot {
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
         for (DevBuf &b : bufs) b.release();
+        if (own && st) return_stream(st);
     }
-    // closes and returns the call's code
-    int finish() {
+    // closes and returns the call's code; the text of a HIP error goes to h (a handle-bound call) or to the calling thread
+    int finish(mpc_handle *h = nullptr) {
         close();
-        return ok() ? (int)MPC_OK : fail(nullptr, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(err));
+        return ok() ? (int)MPC_OK : fail(h, MPC_ERR_HIP, std::string(who) + ": " + hipGetErrorString(err));
     }
 };
+
+// ---- programs at fixed points (points.hip) that the engine calls ---------------------------------------------------------------------
+// mpc_lp_solve_batch with one more output: tight[n_lp x m] = 1 where a row's slack is nonbasic at the vertex found (nullptr: none)
+int lp_batch(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b, int32_t shared_b,
+             const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x, double *obj, int32_t *iters, int32_t *tight);
+// the device pointers and sizes of a handle's QP blocks: W [n_c x n_c], UV [n_c x (n_t + 1)], X0H [n_x x (n_t + 1)], Gt [n_c x n_x]
+struct QpProgram { int n_c, n_eq, n_t, n_x; const double *W, *UV, *X0H, *Gt; };
+// mpc_qp_solve_batch behind its checks, on stream st of the calling thread's device; h only receives the error text
+int qp_batch(mpc_handle *h, hipStream_t st, int n_cu, const QpProgram &P, int64_t m, const double *theta, int32_t *status, double *x,
+             double *lambda, uint8_t *active, int32_t *iters);
 
 }  // namespace mpc

@@ -1,8 +1,8 @@
 // mpcombi_hip.hip -- the level engine behind the C ABI (include/mpcombi.h): mpc_handle and everything that needs it, over the
-// gfx950 kernels in kernels.hpp / kernels2.hpp, plus the batched LP / QP / MIQP plugs.  The stateless geometry entry points
-// (hit-and-run, slices, point location, search trees, closed loop, vertices, merging) are geometry.hip.
+// gfx950 kernels in kernels.hpp / kernels2.hpp.  The stateless geometry entry points (hit-and-run, slices, point location, search
+// trees, closed loop, vertices, merging) are geometry.hip; the LPs, QPs and MIQPs solved at fixed points are points.hip.
 //
-// Build:  one object per translation unit (this file, geometry.hip, batch_level.hip, setup_mfma.hip), linked into
+// Build:  one object per translation unit (this file, geometry.hip, points.hip, batch_level.hip, setup_mfma.hip), linked into
 //         libmpcombi_hip.so:  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -c <unit>.hip   (__graft_entry__.build)
 //
 // Host side of the hot path: owns the device-resident program blocks, the frontier (to_check), the pruned list
@@ -30,7 +30,6 @@
 #include "kernels.hpp"
 #include "kernels2.hpp"
 #include "graph.hpp"
-#include "qp.hpp"
 #include <memory>
 
 #include "batch_level.hpp"
@@ -477,9 +476,6 @@ static void stream_release(mpc_handle *h);
 static void solve_release(mpc_handle *h);
 static double batch_level_gb(const mpc_handle *h, int32_t gen_children);
 static int fetch_many_wait(int device);
-static int lp_batch_impl(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b,
-                         int32_t shared_b, const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x,
-                         double *obj, int32_t *iters, int32_t *tight);
 
 extern "C" {
 
@@ -612,7 +608,7 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
         for (int i = 0; i < ne; ++i) eqf[i] = 1;
         std::vector<int32_t> tight(rows_x, 0);
         int32_t lp_status = -1;
-        int rc0 = rows_x > nv ? lp_batch_impl(device, 1, rows_x, nv, Alp.data(), 1, blp.data(), 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data()) : MPC_ERR_INVALID;
+        int rc0 = rows_x > nv ? lp_batch(device, 1, rows_x, nv, Alp.data(), 1, blp.data(), 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data()) : MPC_ERR_INVALID;
         HIP_TRY(nullptr, hipSetDevice(device));
         std::vector<int> B;
         for (int i = 0; i < rows_x; ++i) if (tight[i]) B.push_back(i);
@@ -663,7 +659,7 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
                 for (int i = 0; i < ntc; ++i) tight[i] = 1;
                 lp_status = LP_OPTIMAL;
             } else {
-                int rc0 = lp_batch_impl(device, 1, ntc, nt, p->A_t, 1, p->b_t, 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data());
+                int rc0 = lp_batch(device, 1, ntc, nt, p->A_t, 1, p->b_t, 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data());
                 HIP_TRY(nullptr, hipSetDevice(device));
                 ok = rc0 == MPC_OK && lp_status == LP_OPTIMAL;
             }
@@ -862,7 +858,7 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
                     for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
                     std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
                     std::vector<int32_t> stt(2 * nt, -1);
-                    int rcb = lp_batch_impl(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
+                    int rcb = lp_batch(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
                     HIP_TRY(nullptr, hipSetDevice(device));
                     for (int t = 0; t < nt; ++t) {
                         const bool ok_lo = rcb == MPC_OK && stt[2 * t] == LP_OPTIMAL, ok_hi = rcb == MPC_OK && stt[2 * t + 1] == LP_OPTIMAL;
@@ -931,7 +927,7 @@ static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_h
                 for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
                 std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
                 std::vector<int32_t> stt(2 * nt, -1);
-                const int rcb = lp_batch_impl(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
+                const int rcb = lp_batch(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
                 HIP_TRY(nullptr, hipSetDevice(device));
                 for (int t = 0; t < 2 * nt; ++t) box_open = box_open || rcb != MPC_OK || stt[t] != LP_OPTIMAL;
             }
@@ -4026,100 +4022,7 @@ int mpc_check_level(mpc_handle *h, const int32_t *cand, int64_t n, int32_t k, co
 
 }  // extern "C"
 
-// ---- facet centres of a batch of polytopes (geometric algorithm) --------------------------------------------------------------
-extern "C" int mpc_facet_centres(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, double *centre,
-                                 double *radius, int32_t *status) {
-    if (n_t < 1 || n_regions < 0 || !row_off || !centre || !radius || !status) return fail(nullptr, MPC_ERR_INVALID, "bad argument");
-    const long long rows = n_regions ? row_off[n_regions] : 0;
-    if (rows == 0) return MPC_OK;
-    if (!ef_rows) return fail(nullptr, MPC_ERR_INVALID, "bad argument");
-    if (int rc = select_device(nullptr, device)) return rc;
-    int m_max = 0;
-    std::vector<int32_t> reg((size_t)rows);
-    for (long long r = 0; r < n_regions; ++r) {
-        m_max = std::max<int>(m_max, (int)(row_off[r + 1] - row_off[r]));
-        for (long long i = row_off[r]; i < row_off[r + 1]; ++i) reg[(size_t)i] = (int32_t)r;
-    }
-    const int n = n_t + 1, ld = odd_at_least(n + 3), m = m_max + 1;
-    const size_t lds = (((size_t)(m + 1) * ld * 8 + (size_t)(ld + 1 + 3 * (m + 2)) * 4) + 15) & ~size_t(15);
-    if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "a region has too many rows for the 160 KiB LDS of one CU");
-    if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_facet_centres), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OneShot s("mpc_facet_centres");
-    DevBuf &d_ef = s.upload(ef_rows, (size_t)rows * (n_t + 1) * 8), &d_off = s.upload(row_off, (size_t)(n_regions + 1) * 8);
-    DevBuf &d_reg = s.upload(reg.data(), (size_t)rows * 4);
-    DevBuf &d_c = s.buf((size_t)rows * n_t * 8), &d_r = s.buf((size_t)rows * 8), &d_s = s.buf((size_t)rows * 4), &d_w = s.buf(256);
-    s.fill(d_w, 0, 4);
-    s.launch([&] {
-        const int per_cu = std::max(1, std::min(32, (int)((160 * 1024) / lds)));
-        const dim3 g((unsigned)std::min<long long>(rows, (long long)cu_count(device) * per_cu)), b(64);
-        hipLaunchKernelGGL(k_facet_centres, g, b, lds, nullptr, rows, (int)n_t, m_max, ld, d_ef.as<double>(), d_off.as<long long>(), d_reg.as<int32_t>(),
-                           d_c.as<double>(), d_r.as<double>(), d_s.as<int32_t>(), d_w.as<unsigned int>());
-    });
-    s.download(centre, d_c, (size_t)rows * n_t * 8);
-    s.download(radius, d_r, (size_t)rows * 8);
-    s.download(status, d_s, (size_t)rows * 4);
-    return s.finish();
-}
-
-// ---- batched LPs ------------------------------------------------------------------------------------------------
-static int lp_batch_impl(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b,
-                         int32_t shared_b, const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x,
-                         double *obj, int32_t *iters, int32_t *tight) {
-    if (n_lp < 0 || m < 1 || n < 1 || !A || !b || !eq || !status) return fail(nullptr, MPC_ERR_INVALID, "bad argument");
-    if (n_lp == 0) return MPC_OK;
-    if (int rc = select_device(nullptr, device)) return rc;
-    const int ld = odd_at_least(n + 3);
-    const size_t lds = (((size_t)(m + 1) * ld * 8 + (size_t)(ld + 1 + 3 * (m + 2)) * 4) + 15) & ~size_t(15);
-    if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "LP does not fit the 160 KiB LDS of one CU");
-    if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_lp_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int n_cu = cu_count(device);
-    const size_t szA = (shared_A ? 1 : (size_t)n_lp) * m * n * 8, szb = (shared_b ? 1 : (size_t)n_lp) * m * 8;
-    const size_t szc = c ? (shared_c ? 1 : (size_t)n_lp) * n * 8 : 0, szeq = (size_t)n_lp * m;
-    DevBuf bA, bb, bc, beq, bst, bit, bx, bobj, bwork, btight;   // pooled blocks (see dev_pool_take)
-    int rc = MPC_OK;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(bA.ensure(szA, nullptr)); chk(bb.ensure(szb, nullptr));
-    if (c) chk(bc.ensure(szc, nullptr));
-    chk(beq.ensure(szeq, nullptr)); chk(bst.ensure((size_t)n_lp * 4, nullptr)); chk(bit.ensure((size_t)n_lp * 4, nullptr));
-    chk(bx.ensure((size_t)n_lp * n * 8, nullptr)); chk(bobj.ensure((size_t)n_lp * 8, nullptr)); chk(bwork.ensure(4, nullptr));
-    if (tight) chk(btight.ensure((size_t)n_lp * m * 4, nullptr));
-    double *dA = bA.as<double>(), *db = bb.as<double>(), *dc = c ? bc.as<double>() : nullptr, *dx = bx.as<double>(), *dobj = bobj.as<double>();
-    uint8_t *deq = beq.as<uint8_t>();
-    int32_t *dst = bst.as<int32_t>(), *dit = bit.as<int32_t>(), *dtight = tight ? btight.as<int32_t>() : nullptr;
-    unsigned int *dwork = bwork.as<unsigned int>();
-    // own (pooled) stream: callers on other threads / handles keep running (no device-wide synchronisation)
-    hipStream_t st = nullptr;
-    chk(pooled_stream(&st));
-    if (e == hipSuccess) {
-        chk(hipMemcpyAsync(dA, A, szA, hipMemcpyHostToDevice, st)); chk(hipMemcpyAsync(db, b, szb, hipMemcpyHostToDevice, st));
-        if (c) chk(hipMemcpyAsync(dc, c, szc, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(deq, eq, szeq, hipMemcpyHostToDevice, st)); chk(hipMemsetAsync(dwork, 0, 4, st));
-    }
-    if (e == hipSuccess) {
-        const int grid = (int)std::min<long long>(n_lp, (long long)std::max(n_cu, 1) * waves_per_cu((int)lds));
-        hipLaunchKernelGGL(k_lp_batch, dim3(grid), dim3(64), lds, st, (long long)n_lp, m, n, ld, dA, shared_A, db, shared_b, dc, shared_c, deq, dst, dx, dobj, dit, dtight, dwork);
-        chk(hipGetLastError());
-        chk(hipMemcpyAsync(status, dst, (size_t)n_lp * 4, hipMemcpyDeviceToHost, st));
-        if (x) chk(hipMemcpyAsync(x, dx, (size_t)n_lp * n * 8, hipMemcpyDeviceToHost, st));
-        if (obj) chk(hipMemcpyAsync(obj, dobj, (size_t)n_lp * 8, hipMemcpyDeviceToHost, st));
-        if (iters) chk(hipMemcpyAsync(iters, dit, (size_t)n_lp * 4, hipMemcpyDeviceToHost, st));
-        if (tight) chk(hipMemcpyAsync(tight, dtight, (size_t)n_lp * m * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (st) { hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess && es != hipSuccess) e = es; }
-    if (e != hipSuccess) { rc = fail(nullptr, MPC_ERR_HIP, std::string("mpc_lp_solve_batch: ") + hipGetErrorString(e)); (void)hipDeviceSynchronize(); }
-    if (st) return_stream(st);
-    for (DevBuf *q : {&bA, &bb, &bc, &beq, &bst, &bit, &bx, &bobj, &bwork, &btight}) q->release();
-    return rc;
-}
-
-extern "C" int mpc_lp_solve_batch(int32_t device, int64_t n_lp, int32_t m, int32_t n, const double *A, int32_t shared_A, const double *b,
-                                  int32_t shared_b, const double *c, int32_t shared_c, const uint8_t *eq, int32_t *status, double *x,
-                                  double *obj, int32_t *iters) {
-    return lp_batch_impl(device, n_lp, m, n, A, shared_A, b, shared_b, c, shared_c, eq, status, x, obj, iters, nullptr);
-}
-
-// ---- the QP of the program at fixed parameter points (qp.hpp) ------------------------------------------------------------------
+// ---- the QP of the program at fixed parameter points (qp_batch of points.hip) ---------------------------------------------------
 extern "C" int mpc_qp_solve_batch(mpc_handle *h, int64_t m, const double *theta, int32_t *status, double *x, double *lambda, uint8_t *active,
                                   int32_t *iters) {
     if (!h || m < 0 || (m > 0 && (!theta || !status))) return MPC_ERR_INVALID;
@@ -4127,154 +4030,6 @@ extern "C" int mpc_qp_solve_batch(mpc_handle *h, int64_t m, const double *theta,
     if (m == 0) return MPC_OK;
     { std::lock_guard<std::mutex> lk(h->wm); if (h->w_busy) return fail(h, MPC_ERR_STATE, "a level started with mpc_level_start is still running"); }
     HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    const int nc = h->n_c, nt = h->n_t, nx = h->n_x;
-    const int ld = odd_at_least(nc + 3);
-    const size_t lds = ((size_t)(nc + 1) * ld + nc) * sizeof(double) + (size_t)(ld + 1 + 2 * (nc + 2) + 2) * sizeof(int32_t) + 16;
-    if (lds > 160 * 1024) return fail(h, MPC_ERR_INVALID, "the QP tableau (n_c x n_c) does not fit the 160 KiB LDS of one CU");
-    if (lds > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_qp_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    DevBuf d_th, d_st, d_x, d_l, d_a, d_it;
-    auto cleanup = [&]() { for (DevBuf *b : {&d_th, &d_st, &d_x, &d_l, &d_a, &d_it}) b->release(); };
-    int rc = MPC_OK;
-    do {
-#define QP_TRY(expr) { hipError_t e__ = (expr); if (e__ != hipSuccess) { rc = fail(h, MPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__)); break; } }
-        QP_TRY(d_th.ensure((size_t)m * nt * sizeof(double), st));
-        QP_TRY(d_st.ensure((size_t)m * sizeof(int32_t), st));
-        QP_TRY(d_it.ensure((size_t)m * sizeof(int32_t), st));
-        if (x) QP_TRY(d_x.ensure((size_t)m * nx * sizeof(double), st));
-        if (lambda) QP_TRY(d_l.ensure((size_t)m * nc * sizeof(double), st));
-        if (active) QP_TRY(d_a.ensure((size_t)m * nc, st));
-        QP_TRY(hipMemcpyAsync(d_th.p, theta, (size_t)m * nt * sizeof(double), hipMemcpyHostToDevice, st));
-        QP_TRY(hipMemsetAsync(h->scratch.p, 0, sizeof(unsigned int), st));
-        const int per_cu = std::max(1, std::min(16, (int)((160 * 1024) / lds)));
-        const dim3 g((unsigned)std::min<long long>(m, (long long)h->n_cu * per_cu)), b(64);
-        hipLaunchKernelGGL(k_qp_batch, g, b, lds, st, (long long)m, nc, h->n_eq, nt, nx, ld, h->Pv.W, h->Pv.UV, h->Pv.X0H, h->Pv.Gt, d_th.as<double>(),
-                           d_st.as<int32_t>(), x ? d_x.as<double>() : (double *)nullptr, lambda ? d_l.as<double>() : (double *)nullptr,
-                           active ? d_a.as<uint8_t>() : (uint8_t *)nullptr, d_it.as<int32_t>(), h->scratch.as<unsigned int>());
-        QP_TRY(hipGetLastError());
-        QP_TRY(hipMemcpyAsync(status, d_st.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (iters) QP_TRY(hipMemcpyAsync(iters, d_it.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (x) QP_TRY(hipMemcpyAsync(x, d_x.p, (size_t)m * nx * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (lambda) QP_TRY(hipMemcpyAsync(lambda, d_l.p, (size_t)m * nc * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (active) QP_TRY(hipMemcpyAsync(active, d_a.p, (size_t)m * nc, hipMemcpyDeviceToHost, st));
-        QP_TRY(hipStreamSynchronize(st));
-#undef QP_TRY
-    } while (0);
-    if (rc != MPC_OK) (void)hipStreamSynchronize(st);
-    cleanup();
-    return rc;
-}
-
-// ---- the MIQP at fixed parameter points: every (point, fixation) pair, pick, winners (qp.hpp) ------------------------------------
-extern "C" int mpc_miqp_solve_batch(int32_t device, int32_t n_c, int32_t n_eq, int32_t n_x, int32_t n_t, int32_t n_b, const double *W,
-                                    const double *UV, const double *X0, const double *Gt, const double *Q_c, const double *G, const double *K,
-                                    int32_t n_check, const double *check, const uint8_t *check_eq, const int32_t *binary_index, int32_t n_rows,
-                                    const int32_t *lcp_row, int64_t n_leaves, const double *Y, int64_t m, const double *theta, int32_t *status,
-                                    int32_t *leaf, double *obj, double *x, double *lambda, uint8_t *active) {
-    const int nxc = n_x - n_b, nz = 1 + n_t + n_b;
-    if (n_c < 0 || n_eq < 0 || n_eq > n_c || n_t < 0 || n_b < 0 || nxc < 1 || n_check < 0 || n_rows < n_c || n_leaves < 0 || m < 0)
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad sizes");
-    if ((n_c && (!W || !UV || !Gt || !lcp_row)) || !X0 || !Q_c || !G || !K || (n_check && (!check || !check_eq)) || (n_b && !binary_index) ||
-        (n_leaves && n_b && !Y) || (m && (!status || !leaf || !obj)) || (m && n_t && !theta))
-        return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: missing array");
-    // every index the kernels write through is checked here
-    std::vector<int32_t> cont;
-    {
-        std::vector<char> is_bin((size_t)n_x, 0);
-        for (int k = 0; k < n_b; ++k) {
-            if (binary_index[k] < 0 || binary_index[k] >= n_x || is_bin[binary_index[k]]) return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad binary_index");
-            is_bin[binary_index[k]] = 1;
-        }
-        for (int a = 0; a < n_x; ++a) if (!is_bin[a]) cont.push_back(a);
-        for (int i = 0; i < n_c; ++i) if (lcp_row[i] < 0 || lcp_row[i] >= n_rows) return fail(nullptr, MPC_ERR_INVALID, "mpc_miqp_solve_batch: bad lcp_row");
-    }
-    if (m == 0) return MPC_OK;
-    if (n_leaves == 0) {
-        for (long long p = 0; p < m; ++p) { status[p] = QP_INFEASIBLE; leaf[p] = -1; obj[p] = NAN; }
-        if (x) std::fill(x, x + (size_t)m * n_x, NAN);
-        if (lambda) std::fill(lambda, lambda + (size_t)m * n_rows, 0.0);
-        if (active) std::fill(active, active + (size_t)m * n_rows, (uint8_t)0);
-        return MPC_OK;
-    }
-    if (int rc = select_device(nullptr, device)) return rc;
-    const int ld = odd_at_least(n_c + 3);
-    // the k_qp_batch tableau and multipliers, then z and x
-    const size_t lds = ((size_t)(n_c + 1) * ld + n_c + nz + nxc) * sizeof(double) + (size_t)(ld + 1 + 2 * (n_c + 2) + 2) * sizeof(int32_t) + 16;
-    if (lds > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "the QP tableau (n_c x n_c) does not fit the 160 KiB LDS of one CU");
-    for (const void *k : {reinterpret_cast<const void *>(k_miqp_pairs), reinterpret_cast<const void *>(k_miqp_winners)})
-        if (lds > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    // constant blocks in one allocation: W UV X0 Gt Qc G K CK Y theta | ck_eq | cont bin lcp_row
-    const size_t nW = (size_t)n_c * n_c, nUV = (size_t)n_c * nz, nX0 = (size_t)nxc * nz, nGt = (size_t)n_c * nxc, nQ = (size_t)nxc * nxc;
-    const size_t nG = (size_t)nxc * nz, nK = (size_t)nz * nz, nCK = (size_t)n_check * nz, nY = (size_t)n_leaves * n_b, nTh = (size_t)m * n_t;
-    const size_t nd = nW + nUV + nX0 + nGt + nQ + nG + nK + nCK + nY + nTh, ni = (size_t)nxc + n_b + n_c;
-    std::vector<double> hd(std::max<size_t>(nd, 1));
-    std::vector<int32_t> hi(std::max<size_t>(ni, 1));
-    size_t o = 0;
-    auto put = [&](const double *src, size_t n) { const size_t at = o; if (n) std::copy(src, src + n, hd.begin() + at); o += n; return at; };
-    const size_t oW = put(W, nW), oUV = put(UV, nUV), oX0 = put(X0, nX0), oGt = put(Gt, nGt), oQ = put(Q_c, nQ), oG = put(G, nG), oK = put(K, nK);
-    const size_t oCK = put(check, nCK), oY = put(Y, nY), oTh = put(theta, nTh);
-    std::copy(cont.begin(), cont.end(), hi.begin());
-    if (n_b) std::copy(binary_index, binary_index + n_b, hi.begin() + nxc);
-    if (n_c) std::copy(lcp_row, lcp_row + n_c, hi.begin() + nxc + n_b);
-    const long long n_pairs = m * n_leaves;
-    DevBuf d_d, d_i, d_ck, d_ps, d_po, d_st, d_leaf, d_best, d_obj, d_x, d_l, d_a, d_w;
-    int rc = MPC_OK;
-    hipError_t e = hipSuccess;
-    auto chk = [&](hipError_t err) { if (e == hipSuccess && err != hipSuccess) e = err; return err == hipSuccess; };
-    chk(d_d.ensure(hd.size() * 8, nullptr)); chk(d_i.ensure(hi.size() * 4, nullptr)); chk(d_ck.ensure(std::max(n_check, 1), nullptr));
-    chk(d_ps.ensure((size_t)n_pairs * 4, nullptr)); chk(d_po.ensure((size_t)n_pairs * 8, nullptr));
-    chk(d_st.ensure((size_t)m * 4, nullptr)); chk(d_leaf.ensure((size_t)m * 4, nullptr)); chk(d_best.ensure((size_t)m * 8, nullptr));
-    chk(d_obj.ensure((size_t)m * 8, nullptr)); chk(d_w.ensure(16, nullptr));
-    if (x) chk(d_x.ensure((size_t)m * n_x * 8, nullptr));
-    if (lambda) chk(d_l.ensure((size_t)m * n_rows * 8, nullptr));
-    if (active) chk(d_a.ensure((size_t)m * n_rows, nullptr));
-    hipStream_t st = nullptr;
-    chk(pooled_stream(&st));
-    if (e == hipSuccess) {
-        chk(hipMemcpyAsync(d_d.p, hd.data(), hd.size() * 8, hipMemcpyHostToDevice, st));
-        chk(hipMemcpyAsync(d_i.p, hi.data(), hi.size() * 4, hipMemcpyHostToDevice, st));
-        if (n_check) chk(hipMemcpyAsync(d_ck.p, check_eq, (size_t)n_check, hipMemcpyHostToDevice, st));
-        chk(hipMemsetAsync(d_w.p, 0, 16, st));
-        if (x) chk(hipMemsetAsync(d_x.p, 0xff, (size_t)m * n_x * 8, st));   // all-ones bytes: a NaN where no pair is optimal
-        if (lambda) chk(hipMemsetAsync(d_l.p, 0, (size_t)m * n_rows * 8, st));
-        if (active) chk(hipMemsetAsync(d_a.p, 0, (size_t)m * n_rows, st));
-    }
-    if (e == hipSuccess) {
-        const double *dd = d_d.as<double>();
-        const int32_t *di = d_i.as<int32_t>();
-        MiqpBlocks B{n_c, n_eq, nxc, n_t, n_b, nz, n_check, n_x, n_rows, dd + oW, dd + oUV, dd + oX0, dd + oGt, dd + oQ, dd + oG, dd + oK,
-                     dd + oCK, dd + oY, dd + oTh, d_ck.as<uint8_t>(), di, di + nxc, di + nxc + n_b};
-        const int n_cu = std::max(cu_count(device), 1), per_cu = waves_per_cu((int)lds);
-        unsigned int *work = d_w.as<unsigned int>();
-        hipLaunchKernelGGL(k_miqp_pairs, dim3((unsigned)std::min<long long>(n_pairs, (long long)n_cu * per_cu)), dim3(64), lds, st, B, (long long)m,
-                           (long long)n_leaves, ld, d_ps.as<int32_t>(), d_po.as<double>(), work);
-        chk(hipGetLastError());
-        hipLaunchKernelGGL(k_miqp_pick, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (long long)m, (long long)n_leaves, d_ps.as<int32_t>(),
-                           d_po.as<double>(), d_st.as<int32_t>(), d_leaf.as<int32_t>(), d_best.as<double>());
-        chk(hipGetLastError());
-        hipLaunchKernelGGL(k_miqp_winners, dim3((unsigned)std::min<long long>(m, (long long)n_cu * per_cu)), dim3(64), lds, st, B, (long long)m, ld,
-                           d_leaf.as<int32_t>(), d_obj.as<double>(), x ? d_x.as<double>() : (double *)nullptr, lambda ? d_l.as<double>() : (double *)nullptr,
-                           active ? d_a.as<uint8_t>() : (uint8_t *)nullptr, work + 2);
-        chk(hipGetLastError());
-        chk(hipMemcpyAsync(status, d_st.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(leaf, d_leaf.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
-        chk(hipMemcpyAsync(obj, d_best.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        if (x) chk(hipMemcpyAsync(x, d_x.p, (size_t)m * n_x * 8, hipMemcpyDeviceToHost, st));
-        if (lambda) chk(hipMemcpyAsync(lambda, d_l.p, (size_t)m * n_rows * 8, hipMemcpyDeviceToHost, st));
-        if (active) chk(hipMemcpyAsync(active, d_a.p, (size_t)m * n_rows, hipMemcpyDeviceToHost, st));
-    }
-    if (st) { hipError_t es = hipStreamSynchronize(st); if (e == hipSuccess && es != hipSuccess) e = es; }
-    std::vector<double> again;
-    if (e == hipSuccess) {
-        // the winner pass repeats the arithmetic of pass 1: its objective must be the one that won, bit for bit
-        again.resize((size_t)m);
-        e = hipMemcpy(again.data(), d_obj.p, (size_t)m * 8, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) { rc = fail(nullptr, MPC_ERR_HIP, std::string("mpc_miqp_solve_batch: ") + hipGetErrorString(e)); (void)hipDeviceSynchronize(); }
-    else
-        for (long long p = 0; p < m; ++p)
-            if (leaf[p] >= 0 && std::memcmp(&again[(size_t)p], &obj[p], 8) != 0) { rc = fail(nullptr, MPC_ERR_STATE, "mpc_miqp_solve_batch: the winner pass disagrees with pass 1"); break; }
-    if (st) return_stream(st);
-    for (DevBuf *q : {&d_d, &d_i, &d_ck, &d_ps, &d_po, &d_st, &d_leaf, &d_best, &d_obj, &d_x, &d_l, &d_a, &d_w}) q->release();
-    return rc;
+    return qp_batch(h, h->stream, h->n_cu, QpProgram{h->n_c, h->n_eq, h->n_t, h->n_x, h->Pv.W, h->Pv.UV, h->Pv.X0H, h->Pv.Gt}, m, theta, status, x, lambda,
+                    active, iters);
 }

@@ -45,7 +45,7 @@ def _facet_centres(E_rows: numpy.ndarray, row_off: numpy.ndarray, device: int):
         radius[:] = 1.0
         ok[:] = True
         return centre, radius, ok
-    # one wavefront per facet builds its LP in LDS from the region's rows and solves it (csrc/kernels.hpp, k_facet_centres)
+    # one wavefront per facet builds its LP in LDS from the region's rows and solves it (csrc/lp_batch.hpp, k_facet_centres)
     centre, radius, status = _lib.facet_centres(E_rows, row_off, device)
     ok = (status == _lib.LP_OPTIMAL) & (numpy.abs(radius) > 1e-12)   # solver_utils.py:245-247: facets of numerically zero radius are skipped
     return centre, radius, ok

@@ -658,6 +658,51 @@ def test_milp_against_highs():
                 assert abs(res[p].obj - (f + const)) <= 1e-9 * max(1.0, abs(f)), (seed, p, res[p].obj, f)
 
 
+# ---- the stateless calls from several threads ---------------------------------------------------------------------------------
+def test_stateless_point_calls_from_four_threads():
+    """lp_solve_batch, miqp_solve_batch and facet_centres hold no handle: each call has buffers of its own, and the first two a
+    stream of their own.  Four threads make the three calls eight times each, all at once; every array of every call is bit for
+    bit what the same call returned serially beforehand."""
+    import threading
+    rng = numpy.random.default_rng(141)
+    A, b, c, _ = _random_lps(rng, 64, 30, 6)
+    eq = numpy.zeros((64, 30), dtype=bool)
+    prog = make_miqp(3 * 1000 + 1 * 100 + 6, 3, 1, 6)   # the first (and smallest) case of test_miqp_against_brute_force
+    B, Y = prog.theta_blocks(), numpy.asarray(prog.feasible_combinations(), dtype=numpy.float64)
+    th = rng.uniform(-1, 1, (50, 2))
+    # n_theta = 2: three boxes |theta_i - o_i| <= r and two simplices theta >= o, sum(theta - o) <= r, rows [f | E]
+    E_box, E_sim = numpy.vstack([numpy.eye(2), -numpy.eye(2)]), numpy.vstack([-numpy.eye(2), numpy.ones((1, 2))])
+    polys = []
+    for k in range(5):
+        o, r = rng.uniform(-1, 1, 2), rng.uniform(0.5, 2.0)
+        E = E_box if k % 2 == 0 else E_sim
+        f = E @ o + (r if k % 2 == 0 else numpy.array([0.0, 0.0, r]))
+        polys.append(numpy.hstack([f.reshape(-1, 1), E]))
+    ef, row_off = numpy.vstack(polys), numpy.cumsum([0] + [len(p) for p in polys])
+    calls = [lambda: _lib.lp_solve_batch(A, b, c, eq), lambda: _lib.miqp_solve_batch(B, Y, th), lambda: _lib.facet_centres(ef, row_off)]
+    want = [f() for f in calls]
+    assert numpy.all(want[0][0] == 0) and numpy.any(want[1][0] == 0) and numpy.all(want[2][2] == 0) and numpy.all(want[2][1] > 0)
+    bad, start = [], threading.Barrier(4)
+
+    def worker(t):
+        try:
+            start.wait()
+            for r in range(8):
+                for k, f in enumerate(calls):
+                    got = f()
+                    if len(got) != len(want[k]) or not all(_same(g, w) for g, w in zip(got, want[k])):
+                        bad.append((t, r, k))
+        except Exception as e:   # an MpcError of a call: reported by the main thread
+            bad.append((t, repr(e)))
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not bad, bad
+
+
 def test_knife_edge_count_is_small():
     """Runs last in this module: the knife-edge points excluded across the QP tests, capped."""
     if KNIFE_EDGE['points']:
