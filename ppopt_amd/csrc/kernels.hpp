@@ -1406,7 +1406,7 @@ MPC_GLOBAL void k_apply_status(const int32_t *__restrict__ list, int n_list, con
     if (w < n_list) { const int c = list[w]; status[c] = tmp[c]; }
 }
 
-// Spare region slots behind the slots of the overlapped region launch (level_run_impl): slot first + j gets status word `st`
+// Spare region slots behind the slots of the overlapped region launch (LevelRun::region2_launch, level_classic.hpp): slot first + j gets status word `st`
 // and candidate list[j] (or -1).  st = 0: unused slot; st = 7 (ST_RETRY): a candidate that turned out optimal after the launch,
 // its record comes from the LDS-engine kernel like that of a candidate k_region2 gave up on.
 MPC_GLOBAL void k_init_slots(int32_t *__restrict__ head_i, int fi, int first, int count, int st, const int32_t *__restrict__ list) {
