@@ -8,6 +8,7 @@
 #define MPC_GLOBAL __device__ __forceinline__
 #define MPC_LB(...)
 #include "batch_level.hpp"
+#include "knobs.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -173,8 +174,6 @@ unsigned long long spec_of(std::initializer_list<std::pair<int, int>> classes) {
 
 auto group_key(const BatchMember &m) { return std::make_tuple(m.k, m.kd, m.fast_t, m.fast_x, m.fast_r, m.mw, m.use_kkt, m.kkt_listed, m.quick_test, m.gen_children); }
 
-int env_int(const char *name, int dflt) { const char *v = std::getenv(name); return v && *v ? std::atoi(v) : dflt; }
-
 template <class F>
 hipError_t raise_lds(F *fn, int bytes) {
     if (bytes <= 48 * 1024) return hipSuccess;
@@ -208,8 +207,8 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
     // of a single program's launch: 64 members x 4,096 blocks, the members one after the other, each with its own tail.)
     // (budgets in wavefronts per CU, swept on the bench enumeration -- four-parameter sub-programs, the NT = 4 instantiations: the theta
     //  kernel 8 / 16 / 32 -> 67.5 / 60.3 / 58.3 ms of shared levels, the region kernel 8 / 16 -> 67.5 / 66.4, k_x2 8 / 12 / 16 -> 63.0 / 60.3 / 62.4)
-    static const int wpc_th = env_int("MPC_BATCH_WPC_TH", 32), wpc_xq = env_int("MPC_BATCH_WPC_XQ", 20), wpc_x2 = env_int("MPC_BATCH_WPC_X2", 12),
-                     wpc_r2 = env_int("MPC_BATCH_WPC_R2", 16), use_shares = env_int("MPC_BATCH_SHARES", 1), w_share = env_int("MPC_BATCH_WSHARE", 1);
+    static const int wpc_th = (int)knob_process("MPC_BATCH_WPC_TH"), wpc_xq = (int)knob_process("MPC_BATCH_WPC_XQ"), wpc_x2 = (int)knob_process("MPC_BATCH_WPC_X2"),
+                     wpc_r2 = (int)knob_process("MPC_BATCH_WPC_R2"), use_shares = (int)knob_process("MPC_BATCH_SHARES"), w_share = (int)knob_process("MPC_BATCH_WSHARE");   // (defaults 32, 20, 12, 16, 1, 1: knobs.hpp)
     for (int g0 = 0; g0 < B && use_shares;) {
         int g1 = g0 + 1;
         while (g1 < B && group_key(members[g1]) == group_key(members[g0])) ++g1;

@@ -53,7 +53,7 @@ struct LevelRun {
     int32_t n_late = 0;             // set by retry_and_late: optimal candidates found after an overlapped region launch (spare slots); read by region_stage
     int32_t n_opt_fast = -1;        // set by retry_and_late: >= 0: the fast path has already built h->opt_list; read by region_stage
     bool tail_done = false;         // set by second_partition_and_tail: the speculative end of the level stands; read by region_stage, tail
-    // ---- the register-engine path (h->fast && !h->force_v1), stage to stage -------------------------------------------------------------
+    // ---- the register-engine path (h->fast && !h->kn.force_v1), stage to stage -------------------------------------------------------------
     const int32_t *fr = nullptr;    // set by kkt_stage: the frontier; read by every later stage of the path
     uint8_t *stp = nullptr;         // set by kkt_stage: the status array; read by every later stage of the path
     const DevProblem *pf = nullptr; // set by kkt_stage: k_verdict2's view of the program on the device; read by every later stage of the path
@@ -169,7 +169,7 @@ struct LevelRun {
         HIP_TRY(h, h->headi.ensure(n_tot * h->fi * sizeof(int32_t), st));
         HIP_TRY(h, h->epool.ensure(n_tot * rows_t_ * (h->n_t + 1) * sizeof(double), st));
         // few optimal candidates: several wavefronts per candidate (the facet tests are split among them)
-        int W = (h->no_rsplit || one_wave) ? 1 : h->rsplit_max;
+        int W = (h->kn.no_rsplit || one_wave) ? 1 : h->kn.rsplit_max;
         while (W > 1 && (long long)n_opt * W > h->grid_r2) W >>= 1;
         const int ldk = (rows_t_ + 1 + 63) & ~63;
         if (W > 1) {
@@ -179,7 +179,7 @@ struct LevelRun {
         }
         // an overlapped launch may take only a share of the wave slots (r2_cap_pct): its 256-register wavefronts otherwise fill the
         // register file of every SIMD they sit on and the (x,theta) kernel beside them gets no slot there until they leave
-        const long long grid_cap = (rst != st && one_wave) ? std::max<long long>(h->n_cu, (long long)h->grid_r2 * h->r2_cap_pct / 100) : h->grid_r2;
+        const long long grid_cap = (rst != st && one_wave) ? std::max<long long>(h->n_cu, (long long)h->grid_r2 * h->kn.r2_cap_pct / 100) : h->grid_r2;
         const dim3 g((unsigned)std::min<long long>((long long)n_opt * W, grid_cap));
         const DevProblem *pr = h->pr2_dev.as<DevProblem>();
         // where the records go: device buffers (fetched / gathered later), or -- streaming -- page-locked host blocks the
@@ -233,7 +233,7 @@ struct LevelRun {
         const int nt_r = region2_nt(h->fast_r);
         launch_region2(h->fast_r, g, h->lds_r2, rst, pr, h->frontier.as<int32_t>(), k, h->opt_ptr, n_opt, h->status.as<uint8_t>(), out_hd, out_hi, h->fd, h->fi, out_er,
                        ctr, kkc, kkl, W, h->kept_g.as<uint8_t>(), ldk, h->done_g.as<unsigned int>(),
-                       h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r, rs);
+                       h->kn.no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r, rs);
         if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[5], rst));
         if (rst != st) { h->r3_dirty = true; h->region_side_stream = true; HIP_TRY(h, hipEventRecord(h->ev_rjoin, rst)); }
         kernel_timed[2] = true;
@@ -313,23 +313,23 @@ struct LevelRun {
         pl.pre1 = dc.pre1; pl.n_pre1 = dc.n_pre1; pl.pre2 = dc.pre2; pl.n_pre2 = dc.n_pre2;
         pl.n_pre1_dev = n_pre1_dev; pl.n_pre2_dev = n_pre2_dev;
         XqAlt alt{};
-        if (h->x1 >= 2) alt = other_parents(MPC_MAX_NC);
+        if (h->kn.x1 >= 2) alt = other_parents(MPC_MAX_NC);
         DictCache dq = dc;
         dq.n_list_dev = n_needx_dev;
         const DevProblem *pfx = h->pf_dev.as<DevProblem>();
         const int32_t *frx = h->frontier.as<int32_t>();
         uint8_t *stx = h->status.as<uint8_t>();
-        const unsigned gt = (unsigned)std::min<long long>((n_bound + 63) / 64, (long long)h->n_cu * h->xqt_wpc);
+        const unsigned gt = (unsigned)std::min<long long>((n_bound + 63) / 64, (long long)h->n_cu * h->kn.xqt_wpc);
         if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[10], st));
         hipLaunchKernelGGL(k_xq_thread, dim3(gt), dim3(64), 0, st, pfx, frx, k, needx_list_, n_needx_, stx, ctr, dq, nxc, alt, pl);
         if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[11], st));
         xq_thread_timed = true;
-        const unsigned g1 = (unsigned)std::min<long long>(n_bound, (long long)h->n_cu * h->x1_wpc);
+        const unsigned g1 = (unsigned)std::min<long long>(n_bound, (long long)h->n_cu * h->kn.x1_wpc);
         // Round 6: the stream of one-step dictionaries goes to stream4 and is NOT waited for by this level: its records are read
         // by the next level's (x,theta) kernels only (x1_join), the plan pass has already marked the planned candidates as
         // "dictionary stored" for k_children_write.  The end of this level (k_x2 for the unplanned rest, children, counters), the
         // hand-over and the next level's KKT kernel run beside it.
-        const bool defer = h->x1_defer > 0 && !h->timing && h->stream4;
+        const bool defer = h->kn.x1_defer > 0 && !h->timing && h->stream4;
         hipStream_t sx1 = defer ? h->stream4 : st;
         if (defer) { HIP_TRY(h, hipEventRecord(h->ev_x1go, st)); HIP_TRY(h, hipStreamWaitEvent(sx1, h->ev_x1go, 0)); }
         if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[12], st));
@@ -343,7 +343,7 @@ struct LevelRun {
         dr.pre1 = pl.rest[0]; dr.n_pre1 = 0; dr.n_pre1_dev = pl.rest_n[0];
         dr.pre2 = pl.rest[1]; dr.n_pre2 = 0; dr.n_pre2_dev = pl.rest_n[1];
         dr.n_list_dev = pl.rest_n[2]; dr.chunk = 0;
-        const long long grid_r = (long long)h->n_cu * std::min<long long>(4, h->x2_wpc);
+        const long long grid_r = (long long)h->n_cu * std::min<long long>(4, h->kn.x2_wpc);
         launch_x2(h->fast_x, dim3((unsigned)std::max<long long>(1, std::min<long long>(n_bound, grid_r))), st, pfx, frx, k, pl.rest[2], n_needx_, stx, ctr, dr);
         HIP_TRY(h, hipGetLastError());
         x1_ran = true;
@@ -357,7 +357,7 @@ struct LevelRun {
         // wavefronts per CU of the persistent launch: fewer for fewer items (an item is faster the fewer wavefronts share its SIMD; round 4,
         // config 4: level 3, 15.7 k items, 0.445 ms with 16 per CU, 0.33 with 4; level 4, 138 k items, 1.134 / 1.083 / 1.161 ms with 16 / 12 / 8)
         const long long n_all = (long long)n_items + d.n_pre1 + d.n_pre2;
-        const long long wpc = std::max<long long>(std::min<long long>(4, h->x2_wpc), std::min<long long>(h->x2_wpc, n_all / ((long long)h->x2_div * h->n_cu)));
+        const long long wpc = std::max<long long>(std::min<long long>(4, h->kn.x2_wpc), std::min<long long>(h->kn.x2_wpc, n_all / ((long long)h->kn.x2_div * h->n_cu)));
         const long long grid_x = (long long)h->n_cu * wpc;
         d.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_all / (grid_x * 8)));
         if (xq_lean) { d.n_list_dev = dcnt + 8; d.chunk = 0; }   // length of `ls` and chunk rule on the device
@@ -391,8 +391,8 @@ struct LevelRun {
         }
         // (round 6) the pruned list of the earlier levels, bucketed by smallest non-equality member, for this level's children stage: three
         // small launches at the level's start (nothing waits for them before k_children_count_b)
-        if (gen_children && !(flags & MPC_LEVEL_GRAPH) && h->pruned_bucket_min > 0 && h->n_c <= 256 && h->n_pruned >= std::max<long long>(1, h->pruned_bucket_np) &&
-            (double)n * (double)h->n_pruned >= h->pruned_bucket_min && h->n_pruned <= 0x7fffffffLL) {
+        if (gen_children && !(flags & MPC_LEVEL_GRAPH) && h->kn.pruned_bucket_min > 0 && h->n_c <= 256 && h->n_pruned >= std::max<long long>(1, h->kn.pruned_bucket_np) &&
+            (double)n * (double)h->n_pruned >= h->kn.pruned_bucket_min && h->n_pruned <= 0x7fffffffLL) {
             HIP_TRY(h, h->pruned_b.ensure((size_t)h->n_pruned * h->mw * sizeof(uint64_t), st));
             HIP_TRY(h, h->pruned_head.ensure((size_t)PB_WORDS * sizeof(int32_t), st));
             HIP_TRY(h, hipMemsetAsync(h->pruned_head.p, 0, (size_t)PB_WORDS * sizeof(int32_t), st));
@@ -418,17 +418,17 @@ struct LevelRun {
         stp = h->status.as<uint8_t>();
         pf = h->pf_dev.as<DevProblem>();
         const int kd = k - h->targs.ne;   // rows the one-thread KKT kernel solves for (the equality rows are eliminated)
-        if (h->kkt_mode == 0 && kd >= 1 && kd <= KKT_THREAD_MAX && h->no_kkt_thread != 1) {
+        if (h->kkt_mode == 0 && kd >= 1 && kd <= KKT_THREAD_MAX && h->kn.no_kkt_thread != 1) {
             HIP_TRY(h, h->kkt_code.ensure(nn, st));
             HIP_TRY(h, h->kkt_L.ensure(nn * (size_t)k * (h->n_t + 1) * sizeof(double), st));
             kkc = h->kkt_code.as<uint8_t>(); kkl = h->kkt_L.as<double>();
             // (round 6) KKT_SPREAD lanes per candidate while that still leaves the level short of the chip's thread slots (k_kkt_thread's comment)
-            const bool spread = h->kkt_spread > 0 && kd <= KKT_SPREAD_KMAX && n * KKT_SPREAD <= (long long)h->kkt_spread_threads;
+            const bool spread = h->kn.kkt_spread > 0 && kd <= KKT_SPREAD_KMAX && n * KKT_SPREAD <= (long long)h->kn.kkt_spread_threads;
             const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256));
             ThetaArgs ta = h->targs;
             // (round 5) the kernel lists its own output: the theta stage's work list and the candidates its box screen sends to
             // the (x,theta) question -- two compactions of five launches each saved on the level's critical path
-            const bool kkt_lists = !h->no_kkt_lists && n <= 0x7fffffffLL;
+            const bool kkt_lists = !h->kn.no_kkt_lists && n <= 0x7fffffffLL;
             if (kkt_lists) {
                 HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
                 HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
@@ -461,8 +461,8 @@ struct LevelRun {
     // (the previous level's deferred k_x1 is joined by whoever reads dictionary records first: the thread pass on the second stream
     //  below -- the theta kernel reads none and goes ahead --, else the (x,theta) stage behind the theta stage)
     int early_thread_pass() {
-        if (kkc && h->xq_thread != 0 && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
-            n >= h->xqt_min && (h->prev_regions < h->xq_early_regions || h->xq_early_regions <= 0)) {
+        if (kkc && h->kn.xq_thread != 0 && !(flags & MPC_LEVEL_GRAPH) && h->have_prev_dict && h->have_parent_slot &&
+            n >= h->kn.xqt_min && (h->prev_regions < h->kn.xq_early_regions || h->kn.xq_early_regions <= 0)) {
             // (The pass then overlaps the theta stage AND the region stage: the partition behind the theta stage lists only the doubtful
             //  and the optimal candidates -- classes the pass never touches --, the region kernel starts on its stream, and the open
             //  candidates are listed when the pass has ended.  Config 4's last level: 1.86 ms with the pass behind the theta stage,
@@ -481,11 +481,11 @@ struct LevelRun {
                 dq.prev_d = h->dict_d[1 - h->dict_cur].as<double>(); dq.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
                 dq.n_list_dev = dcnt + 10;
                 XqAlt alt{};
-                if (h->xq_thread >= 2 || h->xq_thread < 0) alt = other_parents(h->xq_thread < 0 ? MPC_MAX_NC : h->xq_thread - 1);
+                if (h->kn.xq_thread >= 2 || h->kn.xq_thread < 0) alt = other_parents(h->kn.xq_thread < 0 ? MPC_MAX_NC : h->kn.xq_thread - 1);
                 HIP_TRY(h, hipEventRecord(h->ev_xfork, st));
                 HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_xfork, 0));
                 if (h->x1_pending) HIP_TRY(h, hipStreamWaitEvent(h->stream2, h->ev_x1done, 0));   // (the main stream joins later: x1_join before its own first reader)
-                const unsigned gt = (unsigned)std::min<long long>((n + 63) / 64, (long long)h->n_cu * h->xqt_wpc);
+                const unsigned gt = (unsigned)std::min<long long>((n + 63) / 64, (long long)h->n_cu * h->kn.xqt_wpc);
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[10], h->stream2));
                 hipLaunchKernelGGL(k_xq_thread, dim3(gt), dim3(64), 0, h->stream2, pf, fr, k, h->xq_list.as<int32_t>(), (int)n, stp, ctr, dq, nxc_e, alt, XqPlan{});
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[11], h->stream2));
@@ -530,7 +530,7 @@ struct LevelRun {
         { int rcj = x1_join(h); if (rcj) return rcj; }
         // One partition after the theta stage: [0] numerically doubtful (status 7), [1] feasible and [2] optimal (decided
         // in theta space; they only need a dictionary for their children), [3] feasibility still open.
-        const bool x_first = !early_xq && h->storing && dc.parent_slot && h->x1 > 0 && n >= std::max<long long>(h->x1_min, h->x_first_min) && n <= h->x_first_max &&
+        const bool x_first = !early_xq && h->storing && dc.parent_slot && h->kn.x1 > 0 && n >= std::max<long long>(h->kn.x1_min, h->kn.x_first_min) && n <= h->kn.x_first_max &&
                              n <= 0x7fffffffLL && !(flags & MPC_LEVEL_GRAPH);
         if (x_first) {
             { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA, true, dcnt + 28); if (rcs) return rcs; }
@@ -593,7 +593,7 @@ struct LevelRun {
         quick_test_on = cntA[3] > 0 && !(flags & MPC_LEVEL_GRAPH) && !h->storing && dc.parent_slot;
         use_grouped = quick_test_on && h->last_level_n > 0 && (long long)cntA[3] >= 10 * h->last_level_n &&
                       cntA[3] >= 4096 && lds_q <= 64 * 1024 && !early_xq;   // (after the thread pass few candidates per parent are left)
-        if (!h->no_roverlap && !h->theta_open && cntA[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH) && x_items >= h->roverlap_min && !use_grouped) {
+        if (!h->kn.no_roverlap && !h->theta_open && cntA[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH) && x_items >= h->kn.roverlap_min && !use_grouped) {
             // Candidates that turn out optimal later -- re-solved doubtful ones: the n_early of the theta stage, rarely one of
             // the (x,theta) stage -- get spare slots behind the launch's and take the LDS-engine route of the candidates
             // k_region2 gives up on.  The spare slots cover every re-solved candidate of the theta stage plus up to 1,024 of the
@@ -601,13 +601,13 @@ struct LevelRun {
             // calls them optimal: none has been seen).  A candidate is never demoted for want of a slot: late candidates beyond
             // the spare slots make the level fail with MPC_ERR_CAPACITY, and the driver repeats the solve with the region stage
             // behind the (x,theta) stage (mpc_set_region_overlap(h, 0)), where every optimal candidate is known at launch.
-            const int32_t hold = std::min<int32_t>(std::max(h->test_late, 0), cntA[2] - 1);
+            const int32_t hold = std::min<int32_t>(std::max(h->kn.test_late, 0), cntA[2] - 1);
             const int32_t n_launch = cntA[2] - hold;
-            region_extra = std::max(0, n_early + hold + std::min<int32_t>(cntA[3], 1024) - std::max(h->test_spare, 0));
+            region_extra = std::max(0, n_early + hold + std::min<int32_t>(cntA[3], 1024) - std::max(h->kn.test_spare, 0));
             rprep.copy_dst = h->opt_list.as<int32_t>(); rprep.copy_src = part_list(2); rprep.copy_n = n_launch; rprep_any = true;
             h->opt_ptr = h->opt_list.as<int32_t>();
             h->n_opt = n_launch;
-            int rcs = region2_launch(n_launch, region_extra, h->stream3, x_items >= h->roverlap_long);
+            int rcs = region2_launch(n_launch, region_extra, h->stream3, x_items >= h->kn.roverlap_long);
             if (rcs) return rcs;
             region_launched = true;
         }
@@ -647,7 +647,7 @@ struct LevelRun {
         if (quick_test_on) {
             // last level: decisions only -- the quick test on three vectors of the parent's dictionary first
             DictCache dq = dc;
-            const long long grid_q = (long long)h->n_cu * h->xq_wpc;
+            const long long grid_q = (long long)h->n_cu * h->kn.xq_wpc;
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[8], st));
             n_xq_items = n_needx;
             // First pass, one THREAD per candidate (k_xq_thread, round 5): whatever the first ratio test of the hinted column
@@ -660,11 +660,11 @@ struct LevelRun {
             const int32_t *xq_list = needx_list;
             int32_t xq_n = n_needx;
             bool xqt_lean = false;
-            if (h->xq_thread != 0 && n_needx >= h->xqt_min && !early_xq) {
-                const unsigned gt = (unsigned)std::min<long long>(((long long)n_needx + 63) / 64, (long long)h->n_cu * h->xqt_wpc);
+            if (h->kn.xq_thread != 0 && n_needx >= h->kn.xqt_min && !early_xq) {
+                const unsigned gt = (unsigned)std::min<long long>(((long long)n_needx + 63) / 64, (long long)h->n_cu * h->kn.xqt_wpc);
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[10], st));
                 XqAlt alt{};
-                if ((h->xq_thread >= 2 || h->xq_thread < 0) && h->have_prev_dict) alt = other_parents(h->xq_thread < 0 ? MPC_MAX_NC : h->xq_thread - 1);
+                if ((h->kn.xq_thread >= 2 || h->kn.xq_thread < 0) && h->have_prev_dict) alt = other_parents(h->kn.xq_thread < 0 ? MPC_MAX_NC : h->kn.xq_thread - 1);
                 hipLaunchKernelGGL(k_xq_thread, dim3(gt), dim3(64), 0, st, pf, fr, k, needx_list, n_needx, stp, ctr, dq, nxc, alt, XqPlan{});
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[11], st));
                 HIP_TRY(h, hipGetLastError());
@@ -676,7 +676,7 @@ struct LevelRun {
                 xq_list = h->xq_list.as<int32_t>();
             }
             dq.chunk = (int)std::max<long long>(1, std::min<long long>(16, xq_n / (grid_q * 4)));
-            if (xqt_lean) { dq.n_list_dev = dcnt + 9; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
+            if (xqt_lean) { dq.n_list_dev = dcnt + 9; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->kn.xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
             const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(xqt_lean ? (long long)xq_n : ((long long)xq_n + dq.chunk - 1) / dq.chunk, grid_q)));
             // Grouped by parent when a parent has many open children (config 3: 12.6 per parent, -0.5 ms; config 4: 7.1 per
             // parent, where the per-candidate reads of k_xq are cheaper than one 16 KB copy per parent, +0.45 ms): threshold 10.
@@ -687,7 +687,7 @@ struct LevelRun {
                 hipLaunchKernelGGL(k_group_flags, dim3(nbq), dim3(256), 0, st, xq_list, xq_n, dq.parent_slot, h->flag.as<int32_t>());
                 { int rcs = launch_scan(h, h->flag.as<int32_t>(), h->pos.as<int32_t>(), xq_n, h->scratch.as<int32_t>()); if (rcs) return rcs; }
                 hipLaunchKernelGGL(k_scatter_index, dim3(nbq), dim3(256), 0, st, h->flag.as<int32_t>(), h->pos.as<int32_t>(), (long long)xq_n, h->xq_groups.as<int32_t>());
-                const int per_cu = std::max(1, std::min(h->xqg_per_cu, (int)((160 * 1024) / (lds_q + 64))));
+                const int per_cu = std::max(1, std::min(h->kn.xqg_per_cu, (int)((160 * 1024) / (lds_q + 64))));
                 const dim3 gq((unsigned)std::min<long long>(xq_n, (long long)h->n_cu * per_cu)), bq(256);
                 if (lds_q > 48 * 1024) {
                     HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void *>(k_xq_grouped<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
@@ -696,7 +696,7 @@ struct LevelRun {
                 if (h->fast_x & 1) hipLaunchKernelGGL((k_xq_grouped<2>), gq, bq, lds_q, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc, h->xq_groups.as<int32_t>(), h->scratch.as<int32_t>());
                 else hipLaunchKernelGGL((k_xq_grouped<1>), gq, bq, lds_q, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc, h->xq_groups.as<int32_t>(), h->scratch.as<int32_t>());
             } else if (xq_n == 0) { /* the first pass decided everything (host-known length) */ }
-            else if (!xqt_lean && !(h->fast_x & 1) && xq_n < h->xq_skip_below) { /* a short list (host-known length) is left to k_x2: k_xq's comment */ }
+            else if (!xqt_lean && !(h->fast_x & 1) && xq_n < h->kn.xq_skip_below) { /* a short list (host-known length) is left to k_x2: k_xq's comment */ }
             else launch_xq(h->fast_x, gg, st, pf, fr, k, xq_list, xq_n, stp, ctr, dq, nxc);
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[9], st));
             kernel_timed[4] = true;
@@ -714,7 +714,7 @@ struct LevelRun {
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[2], st));
             int rcs = MPC_OK;
             const long long n_dict = (long long)n_needx + dc.n_pre1 + dc.n_pre2;
-            if (h->storing && dc.parent_slot && h->x1 > 0 && !xq_lean && n_dict >= h->x1_min) {
+            if (h->storing && dc.parent_slot && h->kn.x1 > 0 && !xq_lean && n_dict >= h->kn.x1_min) {
                 rcs = launch_plans(needx_list, n_needx, n_dict, nullptr, nullptr, nullptr);
             } else rcs = launch_x(needx_list, n_needx, dc);
             if (rcs) return rcs;
@@ -773,7 +773,7 @@ struct LevelRun {
         { int rcs = recession(); if (rcs) return rcs; }
         if (!have_cntB) { int rcs = partition({{ST_RETRY, 0}, {ST_OPT_PENDING, 2}}, cntB); if (rcs) return rcs; }
         n_retry = cntB[0];
-        if (n_retry > 0 && !region_launched && !h->no_roverlap && !h->theta_open && cntB[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH)) {
+        if (n_retry > 0 && !region_launched && !h->kn.no_roverlap && !h->theta_open && cntB[2] > 0 && h->fast_r >= 0 && !(flags & MPC_LEVEL_GRAPH)) {
             // the region stage was not started under the (x,theta) stage (grouped quick test, short stage): it runs beside the
             // re-solve of the doubtful candidates instead -- two small, latency-bound kernels; what the re-solve finds optimal
             // takes the spare slots (config 3's last level: 235 re-solved candidates, 0.4 ms)
@@ -838,7 +838,7 @@ struct LevelRun {
         }
         h->n_opt = n_opt;
         if (tail_done) { /* the overlapped region stage left nothing to do: see the speculative end of the level above */ }
-        else if (n_opt > 0 && h->fast && h->fast_r >= 0 && !h->force_v1) {
+        else if (n_opt > 0 && h->fast && h->fast_r >= 0 && !h->kn.force_v1) {
             if (!region_launched) { int rcs = region2_launch(n_opt, 0, st, false); if (rcs) return rcs; }
             // candidates k_region2 gave up on (counted by the kernel; normally none): the LDS-engine kernel, fixed-stride records
             hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, &ctr->n_rretry, reinterpret_cast<unsigned int *>(h->tot_dev + 8), 1);
@@ -891,15 +891,15 @@ struct LevelRun {
         h->ms_x1 = 0;
         if ((x1_ran) && h->timing) HIP_TRY(h, hipEventElapsedTime(&h->ms_x1, h->kev[12], h->kev[13]));
         h->n_x1 = x1_ran ? (long long)cnt_host[12] : 0;   // dictionaries k_x1 wrote
-        if (h->debug_cycles && x1_ran) { const int32_t *ch = cnt_host; std::fprintf(stderr, "[mpc] k=%d one-step plans: %d streamed by k_x1, %d + %d + %d left to k_x2 (plan pass %.3f ms)\n", k, ch[12], ch[13], ch[14], ch[15], h->ms_xq_thread); }
+        if (h->kn.debug_cycles && x1_ran) { const int32_t *ch = cnt_host; std::fprintf(stderr, "[mpc] k=%d one-step plans: %d streamed by k_x1, %d + %d + %d left to k_x2 (plan pass %.3f ms)\n", k, ch[12], ch[13], ch[14], ch[15], h->ms_xq_thread); }
         if (xq_early_ran) { n_xq_items += host_ctr.xq_thread; h->n_needx += host_ctr.xq_thread; }   // what the pass beside the theta stage decided never reached the partition's count
         if (kernel_timed[2] && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)   // k_region2 times itself (see the kernel)
             kms[2] = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);
-        if (h->debug_cycles)
+        if (h->kn.debug_cycles)
             std::fprintf(stderr, "[mpc] k=%d n=%lld cycles/cand: kkt %.0f theta %.0f (rows %.0f, stage2 %.0f) x %.0f region %.0f; pivots %.2f; box screen %.3f / %.3f; x quick %.3f; retries theta %u of %llu\n", k, n,
                          host_ctr.cycles[0] / (double)n, host_ctr.cycles[1] / (double)n, host_ctr.cycles[4] / (double)n, host_ctr.cycles[5] / (double)n,
                          host_ctr.cycles[2] / (double)n, host_ctr.cycles[3] / (double)n, host_ctr.pivots / (double)n, host_ctr.cycles[6] / (double)n, host_ctr.cycles[7] / (double)n, host_ctr.xtheta_lps / (double)n, host_ctr.n_retry_theta, (unsigned long long)host_ctr.xtheta_fallbacks);
-        if (h->debug_cycles && h->n_opt > 0)
+        if (h->kn.debug_cycles && h->n_opt > 0)
             std::fprintf(stderr, "[mpc] k=%d region2 per optimal candidate (%lld): rows %.0f chebyshev %.0f facets %.0f total %.0f cycles; refactors %.2f facet pivots %.1f box-screened rows %.1f\n", k,
                          h->n_opt, host_ctr.rcycles[0] / (double)h->n_opt, host_ctr.rcycles[1] / (double)h->n_opt, host_ctr.rcycles[2] / (double)h->n_opt,
                          host_ctr.rcycles[3] / (double)h->n_opt, host_ctr.rcycles[4] / (double)h->n_opt, host_ctr.rcycles[5] / (double)h->n_opt, host_ctr.r_box / (double)h->n_opt);
@@ -911,7 +911,7 @@ struct LevelRun {
 
     void fill_stats(mpc_level_stats *stats) const {
         level_stats_common(h, host_ctr, stats);
-        stats->n_xtheta_lp = (h->fast && !h->force_v1) ? h->n_needx : (int64_t)host_ctr.xtheta_lps;
+        stats->n_xtheta_lp = (h->fast && !h->kn.force_v1) ? h->n_needx : (int64_t)host_ctr.xtheta_lps;
         stats->n_region_retry = h->n_rretry;
         stats->ms_theta = kms[0]; stats->ms_x = kms[1]; stats->ms_region2 = kms[2];
         stats->region_side_stream = h->region_side_stream ? 1.0f : 0.0f;

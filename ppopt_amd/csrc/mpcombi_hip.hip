@@ -1,5 +1,5 @@
 // mpcombi_hip.hip -- the level engine behind the C ABI (include/mpcombi.h): mpc_handle and everything that needs it, over the
-// gfx950 kernels in kernels.hpp / kernels2.hpp; the stages of a large level's host path are level_classic.hpp.  The stateless geometry entry points (hit-and-run, slices, point location, search
+// gfx950 kernels in kernels.hpp / kernels2.hpp; the stages of a large level's host path are level_classic.hpp, those of handle creation create.hpp, the environment knobs knobs.hpp.  The stateless geometry entry points (hit-and-run, slices, point location, search
 // trees, closed loop, vertices, merging) are geometry.hip; the LPs, QPs and MIQPs solved at fixed points are points.hip.
 //
 // Build:  one object per translation unit (this file, geometry.hip, points.hip, batch_level.hip, setup_mfma.hip), linked into
@@ -36,6 +36,7 @@
 #include "level_launch.hpp"
 #include "setup_mfma.hpp"
 #include "host_common.hpp"
+#include "knobs.hpp"
 #include <rocprim/device/device_radix_sort.hpp>
 
 using namespace mpc;
@@ -58,7 +59,7 @@ static std::multimap<std::pair<int, size_t>, void *> g_dev_pool_free;   // (devi
 static size_t g_dev_pool_bytes = 0;
 // Free blocks kept: MPC_DEV_POOL_GB (default 48 -- a sixth of the 288 GB of an MI355X; a batch of 64 sub-programs of the
 // mixed-integer enumeration holds ~20 GB of level buffers at once, and the next enumeration takes them over as they are).
-static const size_t DEV_POOL_MAX_BYTES = [] { const char *ev = std::getenv("MPC_DEV_POOL_GB"); const double gb = ev ? std::atof(ev) : 48.0; return (size_t)(std::max(gb, 0.0) * 1073741824.0); }();
+static const size_t DEV_POOL_MAX_BYTES = (size_t)(std::max(knob_process("MPC_DEV_POOL_GB"), 0.0) * 1073741824.0);
 constexpr size_t DEV_POOL_MAX_BLOCK = size_t(8) << 30;
 
 // size classes: powers of two up to 1 MiB, above that four steps per octave (1, 1.25, 1.5, 1.75 x 2^k: at most 25 % slack, and
@@ -233,51 +234,23 @@ struct mpc_handle {
     // does waits for ev_x1done (x1_join).  MPC_X1_DEFER=0: in line, as round 5.  Not when a profile asks for per-kernel event times.
     hipEvent_t ev_x1go = nullptr, ev_x1done = nullptr;
     bool x1_pending = false;
-    int x1_defer = 1;           // 1: k_x1 on its own stream from the plan pass on; 0: in line
-    int xq_skip_below = 100000;  // the last level's product-form quick test leaves a list shorter than this to k_x2 when a tableau row is one lane's (MPC_XQ_SKIP_BELOW; 0: never).  Measured: config 3 (62 k left over) 4.26 -> 4.18 ms, config 4 (2.7 k) unchanged -- its last level ends with the region kernel
-    int x_second_max = 1024;     // k_x2: a level's budget of doubtful cached runs repeated from D0 in the kernel (MPC_X_SECOND_MAX; 0: all go to the LDS engine)
-    double x_fresh_limit = 1e6;   // k_x2: growth up to which a run from D0 decides (DictCache::fresh_limit; MPC_X_FRESH_LIMIT=0: GROWTH_SAFE)
-    int kkt_spread_threads = 1 << 19;   // classic path: the spread form while candidates x KKT_SPREAD stays below this (MPC_KKT_SPREAD_THREADS)
-    int kkt_spread = 1;         // small levels: k_kkt_thread with KKT_SPREAD lanes per candidate (MPC_KKT_SPREAD=0: one lane)
+    Knobs kn;                        // what the environment said at creation (knobs.hpp: every member with its variable, its default and its measurements)
     // Round 6: the pruned list bucketed by smallest non-equality member (kernels.hpp, k_children_count_b), rebuilt at the start of every level
-    // whose children stage is large enough to pay for it (MPC_PRUNED_BUCKET_MIN: parents x pruned sets; 0 = never)
+    // whose children stage is large enough to pay for it (kn.pruned_bucket_min)
     DevBuf pruned_b, pruned_head;
-    double pruned_bucket_min = 2.0e7;
-    long long pruned_bucket_np = 1024;   // MPC_PRUNED_BUCKET_NP: ... and at least this many pruned sets (tests: 1)
     hipEvent_t ev_rjoin = nullptr, ev_rgo = nullptr;
-    bool no_roverlap = false;        // MPC_NO_ROVERLAP=1 / mpc_set_region_overlap(h, 0): region stage after the (x,theta) stage (no overlap)
     bool r3_dirty = false;           // a region kernel launched on stream3 has not been joined by a completed level yet
-    int test_spare = 0;              // MPC_TEST_SPARE=N (tests): N fewer spare region slots than the overlapped launch would reserve
-    int rsplit_max = 4;              // MPC_RSPLIT_MAX: most wavefronts that share one optimal candidate in k_region2 (power of two, <= 16; measured:
-                                     // 8 and 16 shorten no level of config 4 or 2 -- every wavefront repeats the row build and the Chebyshev LP, 40 % of
-                                     // a region at 4 -- and move the facet list of one sliver region)
     bool theta_open = false;         // the parameter set is open in some direction (or the program has equality rows only): the reference's
                                      // optimality LP can be unbounded -> k_recession behind every verdict stage, no overlapped region launch,
                                      // no level without host round trips, no shared launches
-    int xqg_per_cu = XQG_WAVES;      // MPC_XQG_PER_CU: workgroups (of four wavefronts) per CU of the persistent k_xq_grouped launch
-    int x2_wpc = 12, x2_div = 16, xq_wpc = 20;    // MPC_X2_WPC (most) / MPC_X2_DIV (items per wavefront) / MPC_XQ_WPC: wavefronts per CU of the persistent
-                                     // k_x2 / k_xq launches (round 3: 16 and 32 whatever the size of the level)
     std::vector<std::pair<void *, size_t>> parked_blocks;   // device blocks the level buffers have outgrown (DevBuf::parked), given back by graveyard_flush
     bool region_side_stream = false; // this level's k_region2 launch ran on the side stream, under the (x,theta) stage (mpc_level_stats)
-    int r2_cap_pct = 100;            // MPC_R2_CAP: share (per cent) of k_region2's wave slots an overlapped one-wave-per-candidate launch may take
-    bool test_small_fallback = false; // MPC_TEST_SMALL_FALLBACK=1 (tests): every level run without host round trips reports "repeat on the classic path"
     bool timing = true;              // mpc_set_timing: HIP-event records around the stages and kernels of a level (off: their times in the stats are 0)
-    bool no_smallpath = false;       // MPC_NO_SMALLPATH=1: levels of any size take the classic path with its host round trips (A/B)
-    long long smallpath_max = 4096;  // MPC_SMALLPATH_MAX: largest level (candidates) that runs without host round trips (measured: config 4 is
-                                     // fastest with 1,024-4,096 -- a level of 15,691 candidates prefers the classic path, which streams its records)
-    long long x_first_min = 4096, x_first_max = 65536;   // MPC_X_FIRST_MIN / _MAX: levels (candidates) whose (x,theta) stage is queued before the read-back.  Measured, config 4: level 3
-                                     // (9,880 candidates) 0.72 -> 0.67 ms; level 4 (181 k) 1.51 -> 1.58: there the stage fills the GPU before the region kernel's long wavefronts are placed
-                                     // (region kernel 0.48 -> 0.60 ms, the stage itself 0.93 -> 1.03) -- large levels keep the region launch first
     hipEvent_t ev_part = nullptr;
-    bool no_kkt_lists = false;       // MPC_NO_KKT_LISTS=1: the work lists behind k_kkt_thread by compaction of the status array (round 4; A/B, tests)
-    bool no_small_rx = false;        // MPC_NO_SMALL_RX=1: region kernel and (x,theta) kernel of a small level as two launches (A/B, tests)
-    bool no_small_fuse = false;      // MPC_NO_SMALL_FUSE=1: the small path with its round-4 launches (doubtful candidates re-solved in place; A/B, tests)
     long long n_smallpath_doubtful = 0;   // small levels repeated because the fused form met a doubtful candidate
     long long n_smallpath = 0, n_smallpath_fallback = 0;   // levels run that way / of which repeated on the classic path
     DevBuf dcnt;                     // device-resident list lengths of such a level
-    long long roverlap_min = 2048, roverlap_long = 50000;   // MPC_ROVERLAP_MIN / MPC_ROVERLAP_LONG (items of the (x,theta) stage)
     int wall_khz = 100000;           // rate of wall_clock64() on the device
-    int test_late = 0;               // MPC_TEST_LATE=N (tests): the overlapped launch leaves N optimal candidates to the late path
     bool own_stream = false;
     int n_cu = 256;
     std::string error;
@@ -289,25 +262,15 @@ struct mpc_handle {
     DevBuf iblocks;           // integer blocks (row / column maps of the pre-crashed dictionary)
     DevProblem Pv{}, Pr{};    // verdict / region kernel views (same blocks, different LDS layouts)
     int lds_v = 0, lds_r = 0; // dynamic LDS bytes per wavefront
-    int debug_cycles = 0;     // MPC_DEBUG_CYCLES=1: per-level cycle breakdown on stderr
     long long last_level_n = 0;   // candidates of the previous level (= the parents of this one)
-    int no_rbox = 0;          // MPC_NO_RBOX=1: no bounding-box screen of the region rows in k_region2 (A/B)
-    int no_rsplit = 0;        // MPC_NO_RSPLIT=1: one wavefront per candidate in k_region2 whatever the load (A/B)
-    int x1 = 1;               // MPC_X1=0: every dictionary of a storing level by the register simplex k_x2 (rounds 1-4); 1: one-step plans (k_xq_thread, plan mode) streamed by k_x1, from the generating parent only; 2 (default): ... and from the candidate's other parents
-    long long xqt_min = 4096, x1_min = 2048;   // MPC_XQT_MIN / MPC_X1_MIN: smallest list the one-thread pass / the one-step plans take (tests set 1: every level of a small program goes through them)
-    int x1_wpc = 16;          // MPC_X1_WPC: wavefronts per CU of k_x1 (config 4, level 4, beside the region kernel: x stage 1.13 / 0.95 / 1.02 ms with 8 / 16 / 32)
     long long n_x1 = 0;       // dictionaries of the last level run that k_x1 wrote
     float ms_x1 = 0;
-    long long prev_regions = 0, xq_early_regions = 0;   // MPC_XQ_EARLY_REGIONS = r > 0: the pass runs beside the theta stage only when the level before found fewer than r regions (0: always)
-    int xqt_wpc = 16;         // MPC_XQT_WPC: wavefronts per CU of k_xq_thread (it is bound by the cache's request rate: config 4's level 0.45 ms alone with 8 per CU, 0.49 with 24; beside the region kernel 0.92 / 0.70 / 0.78 / 0.75 with 4 / 8 / 12 / 16)
-    int xq_thread = -1;       // MPC_XQ_THREAD: 0 = the quick test without its one-thread-per-candidate first pass k_xq_thread (round 5); 1 = the pass against the generating parent only; n >= 2 = ... and up to n - 1 other parents; default: every other parent
+    long long prev_regions = 0;   // regions the level before found (kn.xq_early_regions compares against it)
     long long n_xq_thread = 0; float ms_xq_thread = 0;   // the last level run: candidates that pass decided, its time
     bool fetch_nowait = false; // mpc_level_regions_slots_nowait: even the integer heads are only queued
     bool skip_small = false;  // mpc_level_run_batch: this level already went through the no-round-trip launches and has to be repeated classically
     size_t o_elim[6] = {0, 0, 0, 0, 0, 0};   // offsets of Wr, UVr, AATr, Me, Ne, gE in `blocks` (mpc_program_block)
     bool elim_ok = false;     // the blocks with the equality rows eliminated are valid
-    int no_kkt_thread = 0;    // MPC_NO_KKT_THREAD=1: KKT solves stay inside the wave kernels (A/B)
-    int force_v1 = 0;         // MPC_FORCE_V1=1 in the environment: never use k_verdict2 (A/B comparisons, tests)
     int fast = 0;             // 1: register-engine kernels (k_theta2 / k_x2) with k_verdict as the retry path
     int fast_t = 0, fast_x = 0; // instantiation selectors
     long long n_needx = 0;
@@ -320,7 +283,6 @@ struct mpc_handle {
     int dict_cur = 0;
     bool have_prev_dict = false, have_parent_slot = false, storing = false;
     long long dict_stride_d = 0, dict_stride_i = 0;
-    double dict_budget_gb = 48.0;
 
     DevProblem Pr2{};         // view for k_region2
     int lds_r2 = 0, grid_r2 = 0, fast_r = -1;   // fast_r: k_region2 instantiation, -1 = none (n_t == 1 or too many rows)
@@ -472,6 +434,12 @@ static std::vector<DevBuf *> level_buffers(mpc_handle *h) {
             &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
             &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next};
 }
+// the handle's three side streams and its events without timing, in the order sync_objects (create.hpp) takes them from the pools and
+// mpc_destroy returns them
+static std::vector<hipStream_t *> side_streams(mpc_handle *h) { return {&h->stream2, &h->stream3, &h->stream4}; }
+static std::vector<hipEvent_t *> untimed_events(mpc_handle *h) {
+    return {&h->ev_hi, &h->ev_fork, &h->ev_join, &h->ev_xfork, &h->ev_part, &h->ev_xjoin, &h->ev_x1go, &h->ev_x1done, &h->ev_rjoin, &h->ev_rgo};
+}
 static void graveyard_flush(mpc_handle *h) {
     for (auto &b : h->parked_blocks) dev_pool_give(b.first, b.second);
     h->parked_blocks.clear();
@@ -481,6 +449,11 @@ static void stream_release(mpc_handle *h);
 static void solve_release(mpc_handle *h);
 static double batch_level_gb(const mpc_handle *h, int32_t gen_children);
 static int fetch_many_wait(int device);
+// MPC_BATCH_BUDGET_GB (default 160): device memory the members of one shared launch may hold, read at every call that charges against it
+static double batch_budget_gb() { return knob_process("MPC_BATCH_BUDGET_GB"); }
+// MPC_DEBUG_MANY=1: the times and misses of mpc_solve_many on stderr; read once, by whichever of its two users comes first
+static bool debug_many() { static const bool on = knob_process("MPC_DEBUG_MANY") != 0.0; return on; }
+static_assert(XQG_WAVES == 4, "Knobs::xqg_per_cu (knobs.hpp) defaults to XQG_WAVES");
 
 extern "C" {
 
@@ -520,441 +493,24 @@ int mpc_create(const mpc_problem *p, int32_t device, void *stream, mpc_handle **
 
 }  // extern "C"
 
-// fills a fresh handle; on failure the caller destroys it (error text in the thread-local g_error, see mpc_last_global_error)
-static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_handle *h) {
-    const int nx = p->n_x, nt = p->n_t, nc = p->n_c, ne = p->n_eq, ntc = p->n_tc;
-    h->device = device;
-    HIP_TRY(nullptr, hipSetDevice(device));
-    h->n_cu = cu_count(device);
-    { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) h->wall_khz = khz; }
-    if (stream) { h->stream = reinterpret_cast<hipStream_t>(stream); h->own_stream = false; }
-    else { HIP_TRY(nullptr, pooled_stream(&h->stream)); h->own_stream = true; }
-    for (auto &e : h->ev) HIP_TRY(nullptr, pooled_event(&e, true));
-    for (auto &e : h->kev) HIP_TRY(nullptr, pooled_event(&e, true));
-    HIP_TRY(nullptr, pooled_stream(&h->stream2));
-    HIP_TRY(nullptr, pooled_event(&h->ev_hi, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_fork, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_join, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_xfork, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_part, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_xjoin, false));
-    HIP_TRY(nullptr, pooled_stream(&h->stream3));
-    HIP_TRY(nullptr, pooled_stream(&h->stream4));
-    HIP_TRY(nullptr, pooled_event(&h->ev_x1go, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_x1done, false));
-    { const char *ev = std::getenv("MPC_X1_DEFER"); if (ev) h->x1_defer = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_KKT_SPREAD"); if (ev) h->kkt_spread = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_KKT_SPREAD_THREADS"); if (ev) h->kkt_spread_threads = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_X_FRESH_LIMIT"); if (ev) h->x_fresh_limit = std::atof(ev); }
-    { const char *ev = std::getenv("MPC_X_SECOND_MAX"); if (ev) h->x_second_max = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_XQ_SKIP_BELOW"); if (ev) h->xq_skip_below = std::max(0, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_PRUNED_BUCKET_MIN"); if (ev) h->pruned_bucket_min = std::atof(ev); }
-    { const char *ev = std::getenv("MPC_PRUNED_BUCKET_NP"); if (ev) h->pruned_bucket_np = std::atoll(ev); }
-    HIP_TRY(nullptr, pooled_event(&h->ev_rjoin, false));
-    HIP_TRY(nullptr, pooled_event(&h->ev_rgo, false));
-    h->n_x = nx; h->n_t = nt; h->n_c = nc; h->n_eq = ne; h->n_tc = ntc; h->is_qp = p->Q != nullptr;
-    h->mw = nc <= 64 * MPC_MASK_WORDS ? MPC_MASK_WORDS : 4;
-    { const char *ev = std::getenv("MPC_FORCE_V1"); h->force_v1 = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_DEBUG_CYCLES"); h->debug_cycles = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_RSPLIT"); h->no_rsplit = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_RBOX"); h->no_rbox = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_XQ_THREAD"); h->xq_thread = ev ? std::atoi(ev) : -1; }
-    { const char *ev = std::getenv("MPC_XQT_WPC"); if (ev && std::atoi(ev) > 0) h->xqt_wpc = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_X1"); h->x1 = ev ? std::atoi(ev) : 2; }
-    { const char *ev = std::getenv("MPC_X1_WPC"); if (ev && std::atoi(ev) > 0) h->x1_wpc = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_XQT_MIN"); if (ev) h->xqt_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_X1_MIN"); if (ev) h->x1_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_XQ_EARLY_REGIONS"); if (ev) h->xq_early_regions = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_NO_KKT_THREAD"); h->no_kkt_thread = ev ? std::atoi(ev) : 0; }   // 2: only the small-level path
-    { const char *ev = std::getenv("MPC_NO_ROVERLAP"); h->no_roverlap = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_TEST_LATE"); h->test_late = ev ? std::atoi(ev) : 0; }
-    { const char *ev = std::getenv("MPC_TEST_SPARE"); h->test_spare = ev ? std::atoi(ev) : 0; }
-    { const char *ev = std::getenv("MPC_X_FIRST_MIN"); if (ev) h->x_first_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_X_FIRST_MAX"); if (ev) h->x_first_max = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_NO_KKT_LISTS"); h->no_kkt_lists = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_SMALL_RX"); h->no_small_rx = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_SMALL_FUSE"); h->no_small_fuse = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_NO_SMALLPATH"); h->no_smallpath = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_X2_WPC"); if (ev && std::atoi(ev) > 0) h->x2_wpc = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_XQ_WPC"); if (ev && std::atoi(ev) > 0) h->xq_wpc = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_XQG_PER_CU"); if (ev && std::atoi(ev) > 0) h->xqg_per_cu = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_X2_DIV"); if (ev && std::atoi(ev) > 0) h->x2_div = std::atoi(ev); }
-    { const char *ev = std::getenv("MPC_R2_CAP"); if (ev && std::atoi(ev) > 0) h->r2_cap_pct = std::min(100, std::atoi(ev)); }
-    { const char *ev = std::getenv("MPC_TEST_SMALL_FALLBACK"); h->test_small_fallback = ev && ev[0] == '1'; }
-    { const char *ev = std::getenv("MPC_RSPLIT_MAX"); if (ev) { int v = std::atoi(ev); h->rsplit_max = v >= 16 ? 16 : (v >= 8 ? 8 : (v >= 4 ? 4 : (v >= 2 ? 2 : 1))); } }
-    { const char *ev = std::getenv("MPC_SMALLPATH_MAX"); if (ev) h->smallpath_max = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_ROVERLAP_MIN"); if (ev) h->roverlap_min = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_ROVERLAP_LONG"); if (ev) h->roverlap_long = std::atoll(ev); }
-    { const char *ev = std::getenv("MPC_DICT_BUDGET_GB"); if (ev) h->dict_budget_gb = std::atof(ev); }
+#include "create.hpp"
 
-    const int nr = nt + 1;
-    const int cols = 1 + nx + nt, rows_x = nc + ntc;
-    std::vector<double> base((size_t)rows_x * cols, 0.0);
-    for (int i = 0; i < nc; ++i) {
-        base[(size_t)i * cols] = p->b[i];
-        for (int j = 0; j < nx; ++j) base[(size_t)i * cols + 1 + j] = p->A[(size_t)i * nx + j];
-        for (int j = 0; j < nt; ++j) base[(size_t)i * cols + 1 + nx + j] = -p->F[(size_t)i * nt + j];
-    }
-    for (int i = 0; i < ntc; ++i) {
-        base[(size_t)(nc + i) * cols] = p->b_t[i];
-        for (int j = 0; j < nt; ++j) base[(size_t)(nc + i) * cols + 1 + nx + j] = p->A_t[(size_t)i * nt + j];
-    }
-    // ---- pre-crashed dictionary D0 of the (x,theta) LP (see xtheta_from_vertex in kernels.hpp) --------------------
-    // A feasible vertex of the base polytope {A x - F theta <= b (first n_eq rows =), A_t theta <= b_t} is found once by
-    // the device simplex; the dictionary at that vertex is then rebuilt from the original rows by a fresh LU, so its
-    // entries carry factorisation-level accuracy, not the accumulated error of the pivot sequence.
-    std::vector<double> d0;
-    std::vector<int> d0_rows, d0_cols;
-    {
-        const int nv = nx + nt;
-        std::vector<double> Alp((size_t)rows_x * nv), blp(rows_x);
-        for (int i = 0; i < rows_x; ++i) { blp[i] = base[(size_t)i * cols]; for (int j = 0; j < nv; ++j) Alp[(size_t)i * nv + j] = base[(size_t)i * cols + 1 + j]; }
-        std::vector<uint8_t> eqf(rows_x, 0);
-        for (int i = 0; i < ne; ++i) eqf[i] = 1;
-        std::vector<int32_t> tight(rows_x, 0);
-        int32_t lp_status = -1;
-        int rc0 = rows_x > nv ? lp_batch(device, 1, rows_x, nv, Alp.data(), 1, blp.data(), 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data()) : MPC_ERR_INVALID;
-        HIP_TRY(nullptr, hipSetDevice(device));
-        std::vector<int> B;
-        for (int i = 0; i < rows_x; ++i) if (tight[i]) B.push_back(i);
-        bool ok = rc0 == MPC_OK && lp_status == LP_OPTIMAL && (int)B.size() == nv;
-        std::vector<double> MT;
-        std::vector<int> perm;
-        if (ok) {
-            MT.assign((size_t)nv * nv, 0.0);  // M^T, M = rows B of [A | -F ; 0 | A_t]
-            for (int r = 0; r < nv; ++r) for (int j = 0; j < nv; ++j) MT[(size_t)j * nv + r] = Alp[(size_t)B[r] * nv + j];
-            ok = lu_factor(MT, nv, perm);
-        }
-        if (ok) {
-            std::vector<char> inB(rows_x, 0);
-            for (int r : B) inB[r] = 1;
-            std::vector<int> colpos;  // positions in B of the inequality rows (the alive nonbasic columns)
-            for (int r = 0; r < nv; ++r) if (B[r] >= ne) { colpos.push_back(r); d0_cols.push_back(B[r]); }
-            std::vector<double> y(nv);
-            const int nc0 = (int)d0_cols.size();
-            for (int i = 0; i < rows_x && ok; ++i) {
-                if (inB[i]) continue;
-                lu_solve_host(MT, perm, nv, &Alp[(size_t)i * nv], y.data());  // y = a_i M^-1
-                double beta = blp[i];
-                for (int r = 0; r < nv; ++r) beta -= y[r] * blp[B[r]];
-                if (beta < -1e-7) ok = false;
-                d0_rows.push_back(i);
-                d0.push_back(beta);
-                for (int q = 0; q < nc0; ++q) d0.push_back(-y[colpos[q]]);
-            }
-        }
-        if (!ok) { d0.clear(); d0_rows.clear(); d0_cols.clear(); }
-        if (std::getenv("MPC_DEBUG_CREATE"))
-            std::fprintf(stderr, "[mpc] create: base vertex rc %d status %d, %d tight rows of n_x + n_t = %d -> pre-crashed dictionary %s\n", rc0, (int)lp_status,
-                         (int)B.size(), nv, ok ? "built" : "NOT built (no register-resident fast path for this program)");
-    }
-    // ---- vertex of the parameter polytope {A_t theta <= b_t} (kernels2.hpp) ----------------------------------------
-    std::vector<double> tv_theta, tv_minv, tv_rows, d0T;
-    std::vector<int> tv_tight;
-    {
-        bool ok = ntc >= nt;
-        std::vector<int32_t> tight(std::max(ntc, 1), 0);
-        int32_t lp_status = -1;
-        if (ok) {
-            std::vector<uint8_t> eqf(ntc, 0);
-            if (ntc == nt) {
-                // Exactly n_theta rows (round 6): if they are independent (the LU below decides) their common point is the set's only vertex
-                // -- a pointed cone, e.g. the lower bounds of theta that a presolve leaves when the main rows imply the upper ones
-                // (profiles/r05_sweep.json: mpqp_10_2_20 / _30 ran on the LDS-engine kernels for want of this case).
-                for (int i = 0; i < ntc; ++i) tight[i] = 1;
-                lp_status = LP_OPTIMAL;
-            } else {
-                int rc0 = lp_batch(device, 1, ntc, nt, p->A_t, 1, p->b_t, 1, nullptr, 1, eqf.data(), &lp_status, nullptr, nullptr, nullptr, tight.data());
-                HIP_TRY(nullptr, hipSetDevice(device));
-                ok = rc0 == MPC_OK && lp_status == LP_OPTIMAL;
-            }
-        }
-        std::vector<int> B;
-        for (int i = 0; i < ntc && ok; ++i) if (tight[i]) B.push_back(i);
-        ok = ok && (int)B.size() == nt;
-        std::vector<double> M, MTf;
-        std::vector<int> perm;
-        if (ok) {
-            M.assign((size_t)nt * nt, 0.0);
-            for (int r = 0; r < nt; ++r) for (int j = 0; j < nt; ++j) M[(size_t)r * nt + j] = p->A_t[(size_t)B[r] * nt + j];
-            std::vector<double> LU(M);
-            ok = lu_factor(LU, nt, perm);
-            if (ok) {
-                tv_minv.assign((size_t)nt * nt, 0.0);
-                std::vector<double> e(nt), x(nt);
-                for (int j = 0; j < nt; ++j) {   // column j of M^-1
-                    std::fill(e.begin(), e.end(), 0.0); e[j] = 1.0;
-                    lu_solve_host(LU, perm, nt, e.data(), x.data());
-                    for (int t = 0; t < nt; ++t) tv_minv[(size_t)t * nt + j] = x[t];
-                }
-                std::vector<double> bB(nt);
-                for (int r = 0; r < nt; ++r) bB[r] = p->b_t[B[r]];
-                tv_theta.assign(nt, 0.0);
-                lu_solve_host(LU, perm, nt, bB.data(), tv_theta.data());
-                std::vector<char> inB(ntc, 0);
-                for (int r : B) inB[r] = 1;
-                for (int i = 0; i < ntc; ++i) {
-                    if (inB[i]) continue;
-                    double mx = 0; for (int t = 0; t < nt; ++t) mx = std::max(mx, std::fabs(p->A_t[(size_t)i * nt + t]));
-                    double sc = 1.0;
-                    if (mx > 1e-8) { int ex; std::frexp(mx, &ex); sc = std::ldexp(1.0, -ex); }
-                    double beta = p->b_t[i] * sc;
-                    for (int t = 0; t < nt; ++t) beta -= (mx > 1e-8 ? p->A_t[(size_t)i * nt + t] * sc : 0.0) * tv_theta[t];
-                    tv_rows.push_back(beta);
-                    for (int j = 0; j < nt; ++j) {
-                        double acc = 0; for (int t = 0; t < nt; ++t) acc += (mx > 1e-8 ? p->A_t[(size_t)i * nt + t] * sc : 0.0) * tv_minv[(size_t)t * nt + j];
-                        tv_rows.push_back(-acc);
-                    }
-                }
-            }
-        }
-        if (!ok) { tv_theta.clear(); tv_minv.clear(); tv_rows.clear(); } else tv_tight = B;
-        if (!d0.empty()) {
-            const int mr = (int)d0_rows.size(), cc = 1 + (int)d0_cols.size();
-            d0T.assign((size_t)mr * cc, 0.0);
-            for (int i = 0; i < mr; ++i) for (int j = 0; j < cc; ++j) d0T[(size_t)j * mr + i] = d0[(size_t)i * cc + j];
-        }
-    }
-    // ---- one device allocation for every read-only block -------------------------------------------------
-    std::vector<double> host;
-    auto put = [&](const double *src, size_t cnt) { size_t off = host.size(); host.insert(host.end(), src, src + cnt); while (host.size() % 2) host.push_back(0.0); return off; };
-    std::vector<double> zeros((size_t)std::max(nx * nx, 1), 0.0);
-    const size_t oA = put(p->A, (size_t)nc * nx), ob = put(p->b, nc), oF = put(p->F, (size_t)nc * nt), oc = put(p->c, nx), oH = put(p->H, (size_t)nx * nt);
-    const size_t oQ = put(p->Q ? p->Q : zeros.data(), (size_t)nx * nx);
-    const size_t oAt = put(ntc ? p->A_t : zeros.data(), (size_t)std::max(ntc * nt, 1)), obt = put(ntc ? p->b_t : zeros.data(), std::max(ntc, 1));
-    // the blocks the set-up kernel fills are reserved at full size (zero until then)
-    auto reserve = [&](size_t cnt) { const std::vector<double> z(std::max<size_t>(cnt, 1), 0.0); return put(z.data(), z.size()); };
-    const bool dev_schur = p->Q != nullptr;
-    const size_t oW = reserve(dev_schur ? (size_t)nc * nc : 1), oUV = reserve(dev_schur ? (size_t)nc * nr : 1);
-    const size_t oGt = reserve(dev_schur ? (size_t)nc * nx : 1), oX0H = reserve(dev_schur ? (size_t)nx * nr : 1);
-    const size_t oAAT = reserve((size_t)nc * nc);
-    std::vector<double> ATr((size_t)std::max(nx * nc, 1), 0.0);      // A transposed (k_region2's row build reads a column of A per step)
-    for (int i = 0; i < nc; ++i) for (int l = 0; l < nx; ++l) ATr[(size_t)l * nc + i] = p->A[(size_t)i * nx + l];
-    const size_t oATr = put(ATr.data(), ATr.size());
-    // equality rows eliminated from the Schur blocks (setup_mfma.hpp): lets k_kkt_thread take active sets of ne + (1..8) rows
-    const bool want_elim = ne > 0 && dev_schur && ![] { const char *ev = std::getenv("MPC_NO_EQ_ELIM"); return ev && ev[0] == '1'; }();
-    const size_t oWr = reserve(want_elim ? (size_t)nc * nc : 1), oUVr = reserve(want_elim ? (size_t)nc * nr : 1);
-    const size_t oAATr = reserve(want_elim ? (size_t)nc * nc : 1), oMe = reserve(want_elim ? (size_t)ne * nr : 1);
-    const size_t oNe = reserve(want_elim ? (size_t)ne * nc : 1), ogE = reserve(want_elim ? (size_t)2 * ne : 1);
-    const size_t obase = put(base.data(), base.size());
-    const size_t od0 = put(d0.empty() ? zeros.data() : d0.data(), d0.empty() ? 1 : d0.size());
-    const size_t od0T = put(d0T.empty() ? zeros.data() : d0T.data(), d0T.empty() ? 1 : d0T.size());
-    const size_t otvt = put(tv_theta.empty() ? zeros.data() : tv_theta.data(), tv_theta.empty() ? 1 : tv_theta.size());
-    const size_t otvm = put(tv_minv.empty() ? zeros.data() : tv_minv.data(), tv_minv.empty() ? 1 : tv_minv.size());
-    const size_t otvr = put(tv_rows.empty() ? zeros.data() : tv_rows.data(), tv_rows.empty() ? 1 : tv_rows.size());
-    HIP_TRY(nullptr, h->blocks.ensure(host.size() * sizeof(double), h->stream));
-    HIP_TRY(nullptr, hipMemcpyAsync(h->blocks.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    // ---- the dense Hessian factor and the one-off Schur blocks W = A Q^-1 A', UV, G', X0H, A A' on the matrix cores (setup_mfma.hip) ----
-    std::vector<double> UV, UVr;
-    int mode = 1;
-    bool elim_ok = false;
-    {
-        double *db = h->blocks.as<double>();
-        SetupJob job{};
-        job.nx = nx; job.nt = nt; job.nc = nc; job.NP = setup_pad16(nx); job.MP = setup_pad16(nc); job.RP = setup_pad16(nr);
-        job.A = db + oA; job.b = db + ob; job.F = db + oF; job.c = db + oc; job.H = db + oH; job.Q = p->Q ? db + oQ : nullptr;
-        job.W = db + oW; job.UV = db + oUV; job.Gt = db + oGt; job.X0H = db + oX0H; job.AAT = db + oAAT;
-        DevBuf work, jobbuf;
-        const size_t job_bytes = (sizeof(SetupJob) + 15) & ~size_t(15);
-        hipError_t e1 = work.ensure(setup_work_doubles(nx, nt, nc) * sizeof(double), h->stream);
-        hipError_t e2 = e1 == hipSuccess ? jobbuf.ensure(job_bytes + 16, h->stream) : e1;
-        int flag = 1, flag_e = 1;
-        if (e2 == hipSuccess) {
-            job.work = work.as<double>();
-            job.flag = reinterpret_cast<int *>(jobbuf.as<char>() + job_bytes);
-            if (want_elim) {
-                job.ne = ne; job.Wr = db + oWr; job.UVr = db + oUVr; job.AATr = db + oAATr; job.Me = db + oMe; job.Ne = db + oNe; job.gE = db + ogE;
-                job.flag_e = job.flag + 1;
-            }
-            e2 = hipMemcpyAsync(jobbuf.p, &job, sizeof(SetupJob), hipMemcpyHostToDevice, h->stream);
-            if (e2 == hipSuccess) e2 = setup_launch(jobbuf.as<SetupJob>(), 1, h->stream);
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(&flag, job.flag, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-            if (e2 == hipSuccess && p->Q) { UV.assign((size_t)nc * nr, 0.0); e2 = hipMemcpyAsync(UV.data(), job.UV, UV.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream); }
-            if (e2 == hipSuccess && want_elim) {
-                UVr.assign((size_t)nc * nr, 0.0);
-                e2 = hipMemcpyAsync(UVr.data(), job.UVr, UVr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-                if (e2 == hipSuccess) e2 = hipMemcpyAsync(&flag_e, job.flag_e, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-            }
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(h->stream);
-        }
-        work.release(); jobbuf.release();   // the stream has been synchronised (or nothing was queued)
-        if (e2 != hipSuccess) return fail(nullptr, MPC_ERR_HIP, std::string("MFMA set-up kernel: ") + hipGetErrorString(e2));
-        mode = (p->Q && flag == 0) ? 0 : 1;
-        elim_ok = want_elim && mode == 0 && flag_e == 0;
-        h->elim_ok = elim_ok;
-        h->o_elim[0] = oWr; h->o_elim[1] = oUVr; h->o_elim[2] = oAATr; h->o_elim[3] = oMe; h->o_elim[4] = oNe; h->o_elim[5] = ogE;
-    }
-    HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
-    h->kkt_mode = mode;
-    const double *d = h->blocks.as<double>();
-    DevProblem P{};
-    P.n_x = nx; P.n_t = nt; P.n_c = nc; P.n_eq = ne; P.n_tc = ntc; P.is_qp = h->is_qp; P.kkt_mode = mode;
-    P.A = d + oA; P.b = d + ob; P.F = d + oF; P.c = d + oc; P.H = d + oH; P.Q = d + oQ; P.A_t = d + oAt; P.b_t = d + obt;
-    P.W = d + oW; P.UV = d + oUV; P.Gt = d + oGt; P.X0H = d + oX0H; P.base = d + obase; P.AAT = d + oAAT; P.AT = d + oATr;
-    P.d0T = d + od0T; P.tv_theta = d + otvt; P.tv_minv = d + otvm; P.tv_rows = d + otvr;
-    P.has_tv = tv_theta.empty() ? 0 : 1; P.n_tpre = tv_theta.empty() ? 0 : ntc - nt;
-    P.d0 = d + od0; P.has_d0 = d0.empty() ? 0 : 1; P.n_d0r = (int)d0_rows.size(); P.n_d0c = (int)d0_cols.size();
-    {
-        std::vector<int> maps(d0_rows);
-        maps.insert(maps.end(), d0_cols.begin(), d0_cols.end());
-        maps.insert(maps.end(), tv_tight.begin(), tv_tight.end());
-        if (maps.empty()) maps.push_back(0);
-        HIP_TRY(nullptr, h->iblocks.ensure(maps.size() * sizeof(int), h->stream));
-        HIP_TRY(nullptr, hipMemcpyAsync(h->iblocks.p, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
-        P.d0_rows = h->iblocks.as<int>();
-        P.d0_cols = h->iblocks.as<int>() + d0_rows.size();
-        P.tv_tight = h->iblocks.as<int>() + d0_rows.size() + d0_cols.size();
-    }
-    // ---- LDS layouts ---------------------------------------------------------------------------------------
-    const int kmax = std::min(nc, nx);
-    const int rows_t = nc - ne + ntc;
-    P.kmax = kmax;
-    P.ld_x = odd_at_least(nx + nt + 3);
-    P.ld_t = odd_at_least(nt + 4);
-    const int size_K = mode == 0 ? std::max(kmax * kmax + kmax, kmax * nx) : std::max({(nx + kmax) * (nx + kmax) + (nx + kmax) * nr, kmax * nx, nx * nx});
-    const int size_L = std::max(kmax * nr, 1), size_X = nx * nr;
-    const int T_v = std::max((rows_x + 1) * P.ld_x, (rows_t + 1) * P.ld_t);
-    const int T_r = std::max((rows_t + 2) * P.ld_t, rows_t * nr);
-    const Layout lv = make_layout(T_v, size_K, size_L, 0, mode == 1 ? size_X : 0, kmax, nc, std::max(P.ld_x, P.ld_t), rows_x + 1, rows_t);
-    const Layout lr = make_layout(T_r, size_K, size_L, rows_t * nr, size_X, kmax, nc, P.ld_t, rows_t + 2, rows_t);
-    h->Pv = P; apply_layout(h->Pv, lv); h->lds_v = lv.bytes;
-    h->Pr = P; apply_layout(h->Pr, lr); h->lds_r = lr.bytes;
-    if (h->lds_v > 160 * 1024 || h->lds_r > 160 * 1024) return fail(nullptr, MPC_ERR_INVALID, "problem does not fit the 160 KiB LDS of one CU");
-    if (h->lds_v > 48 * 1024) HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_verdict), hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_v));
-    if (h->lds_r > 48 * 1024) {
-        HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_region<RG_FULL>), hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_r));
-        HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_region<RG_FACET>), hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_r));
-        HIP_TRY(nullptr, hipFuncSetAttribute(reinterpret_cast<const void *>(k_region<RG_ASSEMBLE>), hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_r));
-    }
-    h->grid_v = h->n_cu * waves_per_cu(h->lds_v);
-    // fast path (k_verdict2): needs the theta vertex, the pre-crashed dictionary and sizes inside the instantiations
-    bool box_done = false, box_open = false;   // the bounding box of the parameter set has been computed / has an infinite side
-    {
-        const int rows_th = rows_t - nt, rows_x = P.n_d0r;
-        const int slots_t = rows_th <= 64 ? 1 : (rows_th <= 128 ? 2 : 0), slots_x = rows_x <= 64 ? 1 : (rows_x <= 128 ? 2 : 0);
-        const int tsel = nt <= 4 ? 0 : (nt <= 8 ? 1 : (nt <= 10 ? 2 : -1));   // kernels are instantiated for n_theta <= 4, 8, 10
-        const int xsel = P.n_d0c <= 14 ? 0 : (P.n_d0c <= 30 ? 1 : -1);
-        if (std::getenv("MPC_DEBUG_CREATE"))
-            std::fprintf(stderr, "[mpc] create: vertex of the parameter set %d, dictionary %d (rows %d, columns %d), theta rows %d -> slots %d / %d, n_theta class %d, column class %d: register-resident kernels %s\n",
-                         (int)P.has_tv, (int)P.has_d0, rows_x, (int)P.n_d0c, rows_th, slots_t, slots_x, tsel, xsel,
-                         (P.has_tv && P.has_d0 && slots_t && slots_x && tsel >= 0 && xsel >= 0) ? "ON" : "OFF (LDS-engine kernels)");
-        if (P.has_tv && P.has_d0 && slots_t && slots_x && tsel >= 0 && xsel >= 0) {
-            h->fast = 1;
-            h->fast_t = tsel * 2 + (slots_t - 1);
-            h->fast_x = xsel * 2 + (slots_x - 1);
-            if (xsel >= 1) h->x2_wpc = std::min(h->x2_wpc, 4 * X2_WAVES);   // the 32-column instantiations of k_x2 are built for two wavefronts per SIMD
-            // zero-padded blocks of k_theta2 (ThetaArgs) for its compile-time NT
-            const int NTP = tsel == 0 ? 4 : (tsel == 1 ? 8 : 10), LS = NTP + 1;
-            {
-                std::vector<double> tb;
-                const size_t oUVp = tb.size(); tb.resize(tb.size() + (size_t)nc * LS, 0.0);
-                if (mode == 0) for (int i = 0; i < nc; ++i) for (int t = 0; t < nr; ++t) tb[oUVp + (size_t)i * LS + t] = UV[(size_t)i * nr + t];
-                const size_t oUVrp = tb.size();
-                if (elim_ok) {
-                    tb.resize(tb.size() + (size_t)nc * LS, 0.0);
-                    for (int i = 0; i < nc; ++i) for (int t = 0; t < nr; ++t) tb[oUVrp + (size_t)i * LS + t] = UVr[(size_t)i * nr + t];
-                }
-                const size_t otvp = tb.size(); tb.resize(tb.size() + (size_t)NTP * NTP + 3 * NTP, 0.0);
-                for (int t = 0; t < nt; ++t) for (int j = 0; j < nt; ++j) tb[otvp + (size_t)t * NTP + j] = tv_minv[(size_t)t * nt + j];
-                for (int t = 0; t < nt; ++t) tb[otvp + (size_t)NTP * NTP + t] = tv_theta[t];
-                {   // bounding box of the parameter polytope: 2 n_t LPs on the device (an unbounded direction gives +-inf)
-                    std::vector<double> cc((size_t)2 * nt * nt, 0.0), obj(2 * nt, 0.0);
-                    for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
-                    std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
-                    std::vector<int32_t> stt(2 * nt, -1);
-                    int rcb = lp_batch(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
-                    HIP_TRY(nullptr, hipSetDevice(device));
-                    for (int t = 0; t < nt; ++t) {
-                        const bool ok_lo = rcb == MPC_OK && stt[2 * t] == LP_OPTIMAL, ok_hi = rcb == MPC_OK && stt[2 * t + 1] == LP_OPTIMAL;
-                        // the LP optimum carries the simplex tolerance: widen the box a little (the screen only needs an outer box)
-                        const double lo = ok_lo ? obj[2 * t] : -INFINITY, hi = ok_hi ? -obj[2 * t + 1] : INFINITY;
-                        box_done = true; box_open = box_open || !ok_lo || !ok_hi;
-                        const double pad = 1e-6 * (1.0 + std::max(std::fabs(ok_lo ? lo : 0.0), std::fabs(ok_hi ? hi : 0.0)));
-                        tb[otvp + (size_t)NTP * NTP + NTP + t] = lo - pad;
-                        tb[otvp + (size_t)NTP * NTP + 2 * NTP + t] = hi + pad;
-                    }
-                }
-                const int npre = ntc - nt;
-                const size_t otvr = tb.size(); tb.resize(tb.size() + (size_t)std::max(npre, 1) * LS, 0.0);
-                for (int i = 0; i < npre; ++i) for (int t = 0; t < nr; ++t) tb[otvr + (size_t)i * LS + t] = tv_rows[(size_t)i * nr + t];
-                HIP_TRY(nullptr, h->theta_blocks.ensure(tb.size() * sizeof(double), h->stream));
-                HIP_TRY(nullptr, hipMemcpyAsync(h->theta_blocks.p, tb.data(), tb.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
-                const double *tbd = h->theta_blocks.as<double>();
-                { const char *ev = std::getenv("MPC_KKT_BOX_SELECT"); h->targs.box_finite = (box_done && !box_open && !(ev && ev[0] == '1')) ? 1 : 0; }   // (=1: the select form of the screen's row test on every program; tests)
-                h->targs.W = P.W; h->targs.UVp = tbd + oUVp; h->targs.tvp = tbd + otvp; h->targs.tv_rows = tbd + otvr; h->targs.chunk = 1;
-                h->targs.ne = elim_ok ? ne : 0;
-                {   // MPC_TH_DIV (work items per wavefront of k_theta2, default 4; 0 = round-3 behaviour) / MPC_TH_MAXW (waves per SIMD, default 2)
-                    const char *e1 = std::getenv("MPC_TH_DIV"), *e2 = std::getenv("MPC_TH_MAXW");
-                    h->targs.wave_div = e1 ? std::atoi(e1) : 4;
-                    h->targs.wave_max = (e2 ? std::atoi(e2) : 2) * 4 * h->n_cu;
-                    if (h->targs.wave_div <= 0) { h->targs.wave_div = 0; h->targs.wave_max = 0; }
-                }
-                h->targs.Wr = elim_ok ? d + oWr : P.W; h->targs.UVrp = elim_ok ? tbd + oUVrp : h->targs.UVp; h->targs.AATr = elim_ok ? d + oAATr : P.AAT;
-                h->targs.Me = d + oMe; h->targs.Ne = d + oNe; h->targs.gE = d + ogE;
-            }
-            const Layout lf = make_layout(NTP * NTP + 3 * NTP + kmax * LS, size_K, size_L, 0, mode == 1 ? size_X : 0, kmax, nc, 2, 2, 2);
-            h->Pf = P; apply_layout(h->Pf, lf); h->lds_f = lf.bytes;
-            h->targs.cbuf_off = 0;
-            if (slots_t == 2) {   // scratch of the live-row compaction of k_theta2<., 2>: 64 rows of NT+4 doubles and 2 ints
-                h->targs.cbuf_off = h->lds_f / 8;
-                h->lds_f += 64 * (NTP + 4) * 8 + 64 * 2 * 4;
-                h->lds_f = (h->lds_f + 15) & ~15;
-            }
-            h->grid_f = h->n_cu * std::min(16, waves_per_cu(h->lds_f));
-            HIP_TRY(nullptr, h->pf_dev.ensure(sizeof(DevProblem), h->stream));
-            HIP_TRY(nullptr, hipMemcpyAsync(h->pf_dev.p, &h->Pf, sizeof(DevProblem), hipMemcpyHostToDevice, h->stream));
-            HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
-            // k_region2: all rows_t region rows plus the cost row, n_t >= 2 (the one-parameter variant stays on k_region)
-            const int slots_r = rows_t + 1 <= 64 ? 1 : (rows_t + 1 <= 128 ? 2 : 0);
-            if (nt >= 2 && slots_r) {
-                h->fast_r = tsel * 2 + (slots_r - 1);
-                // (T: the staged [tv_minv | tv_theta | box] block, round 6)
-                const Layout l2 = make_layout(NTP * NTP + 3 * NTP, std::max(size_K, nt * (2 * nt + 1)), size_L, rows_t * nr, size_X, kmax, nc, nt + 2, 2, rows_t);
-                h->Pr2 = P; apply_layout(h->Pr2, l2); h->lds_r2 = l2.bytes;
-                h->Pr2.tvp = h->targs.tvp;
-                h->grid_r2 = h->n_cu * std::min(4 * (slots_r >= 2 ? 2 : R2W), waves_per_cu(h->lds_r2));   // waves per SIMD of the launch bounds
-                HIP_TRY(nullptr, h->pr2_dev.ensure(sizeof(DevProblem), h->stream));
-                HIP_TRY(nullptr, hipMemcpyAsync(h->pr2_dev.p, &h->Pr2, sizeof(DevProblem), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
-            }
-        }
-    }
-    // ---- is the parameter set open in some direction?  (then the reference's optimality LP can be unbounded: k_recession) -------------
-    {
-        bool open = false;
-        if (nc == ne) open = true;                                     // no multiplier / slack row at all bounds t (the base set)
-        else if (nt > 0 && (ntc == 0 || tv_theta.empty())) open = true;   // no row, or no vertex: the set contains a line (or the search failed: the test is always safe)
-        else if (nt > 0) {
-            if (!box_done) {   // a vertex, but maybe an open cone: the bounding box (2 n_t LPs on the device, as for the register-resident kernels)
-                std::vector<double> cc((size_t)2 * nt * nt, 0.0), obj(2 * nt, 0.0);
-                for (int t = 0; t < nt; ++t) { cc[(size_t)(2 * t) * nt + t] = 1.0; cc[(size_t)(2 * t + 1) * nt + t] = -1.0; }
-                std::vector<uint8_t> eqz((size_t)2 * nt * ntc, 0);
-                std::vector<int32_t> stt(2 * nt, -1);
-                const int rcb = lp_batch(device, 2 * nt, ntc, nt, p->A_t, 1, p->b_t, 1, cc.data(), 0, eqz.data(), stt.data(), nullptr, obj.data(), nullptr, nullptr);
-                HIP_TRY(nullptr, hipSetDevice(device));
-                for (int t = 0; t < 2 * nt; ++t) box_open = box_open || rcb != MPC_OK || stt[t] != LP_OPTIMAL;
-            }
-            open = box_open;
-        }
-        h->theta_open = open;
-        if (std::getenv("MPC_DEBUG_CREATE")) std::fprintf(stderr, "[mpc] create: parameter set %s\n", open ? "OPEN in some direction (k_recession behind the verdict stages)" : "bounded");
-    }
-    h->grid_r = h->n_cu * waves_per_cu(h->lds_r);
-    h->rec_d = (long long)nx * nt + nx + (long long)nc * nt + nc + (long long)(nc + ntc) * nt + (nc + ntc);
-    h->rec_i = 5 + (long long)nc + ntc + nc + nc + nc;
-    HIP_TRY(nullptr, h->ctr.ensure(sizeof(LevelCounters), h->stream));
-    HIP_TRY(nullptr, h->scratch.ensure(256, h->stream));
-    {
-        void *hp = nullptr, *dp = nullptr;
-        HIP_TRY(nullptr, host_pool_take(4096, &hp, nullptr, true));
-        HIP_TRY(nullptr, hipHostGetDevicePointer(&dp, hp, 0));
-        h->tot_host = static_cast<int32_t *>(hp);
-        h->tot_dev = static_cast<int32_t *>(dp);
-        std::memset(hp, 0, 64);
-    }
-    return MPC_OK;
+// fills a fresh handle: the stages of create.hpp over one CreateRun, in creation's order; on failure the caller destroys it
+// (error text in the thread-local g_error, see mpc_last_global_error)
+static int create_fill(const mpc_problem *p, int32_t device, void *stream, mpc_handle *h) {
+    CreateRun c(p, device, stream, h);
+    int rc = c.sync_objects();                      // device, streams and events from the pools, the environment (Knobs)
+    if (rc != MPC_OK) return rc;
+    c.base_rows();                                  // [b | A | -F ; b_t | 0 | A_t]
+    if ((rc = c.base_dictionary()) != MPC_OK) return rc;   // a vertex of the base polytope (one LP), the dictionary there by a fresh LU
+    if ((rc = c.theta_vertex()) != MPC_OK) return rc;      // a vertex of the parameter set (one LP, none when n_tc == n_t)
+    if ((rc = c.pack_blocks()) != MPC_OK) return rc;       // every read-only block in one allocation, one upload
+    if ((rc = c.schur_setup()) != MPC_OK) return rc;       // the MFMA set-up kernel: Schur blocks, kkt_mode, the eliminated blocks
+    if ((rc = c.problem_views()) != MPC_OK) return rc;     // DevProblem over the blocks, the integer maps
+    if ((rc = c.lds_layouts()) != MPC_OK) return rc;       // Pv, Pr, the 160 KiB check
+    if ((rc = c.register_path()) != MPC_OK) return rc;     // the register-resident kernels' selectors; theta_blocks and targs, Pf, then Pr2 (region2_view)
+    if ((rc = c.theta_open()) != MPC_OK) return rc;        // open parameter set?  (the bounding box, unless register_path has it)
+    return c.records_and_counters();                       // record sizes, counters, the pinned counter block
 }
 
 extern "C" {
@@ -983,19 +539,8 @@ int mpc_destroy(mpc_handle *h) {
     for (DevBuf *b : {&h->g.wave, &h->g.visited, &h->g.pending, &h->g.tmp_a, &h->g.tmp_b, &h->g.sort_tmp, &h->g.card, &h->g.idx, &h->g.card2, &h->g.idx2, &h->g.facet, &h->g.cnt, &h->g.off, &h->g.hist}) b->release();
     for (auto &e : h->ev) return_event(e, true);
     for (auto &e : h->kev) return_event(e, true);
-    return_event(h->ev_hi, false);
-    return_event(h->ev_fork, false);
-    return_event(h->ev_join, false);
-    return_event(h->ev_xfork, false);
-    return_event(h->ev_part, false);
-    return_event(h->ev_xjoin, false);
-    return_event(h->ev_rjoin, false);
-    return_event(h->ev_rgo, false);
-    return_stream(h->stream2);
-    return_stream(h->stream3);
-    return_stream(h->stream4);
-    return_event(h->ev_x1go, false);
-    return_event(h->ev_x1done, false);
+    for (hipEvent_t *e : untimed_events(h)) return_event(*e, false);
+    for (hipStream_t *s : side_streams(h)) return_stream(*s);
     if (h->own_stream) return_stream(h->stream);
     delete h;
     return MPC_OK;
@@ -1060,7 +605,7 @@ int mpc_program_block(mpc_handle *h, int32_t which, double *out, int64_t cap, in
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MPC_OK;
 }
-int mpc_set_region_overlap(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->no_roverlap = !on; return MPC_OK; }
+int mpc_set_region_overlap(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->kn.no_roverlap = !on; return MPC_OK; }
 int mpc_set_timing(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->timing = on; return MPC_OK; }
 int64_t mpc_region_doubles(const mpc_handle *h) { return h ? h->rec_d : 0; }
 int64_t mpc_region_ints(const mpc_handle *h) { return h ? h->rec_i : 0; }
@@ -1289,9 +834,9 @@ static int x1_join(mpc_handle *h) {
     return MPC_OK;
 }
 static bool small_path_ok(const mpc_handle *h, long long n, int k, int32_t flags, int32_t gen_children) {
-    if (h->no_smallpath || !h->fast || h->force_v1 || h->fast_r < 0 || n < 1 || n > h->smallpath_max) return false;
+    if (h->kn.no_smallpath || !h->fast || h->kn.force_v1 || h->fast_r < 0 || n < 1 || n > h->kn.smallpath_max) return false;
     if (flags & MPC_LEVEL_GRAPH) return false;
-    if (h->test_late > 0 || h->debug_cycles) return false;
+    if (h->kn.test_late > 0 || h->kn.debug_cycles) return false;
     // children and their parent slots are sized by the bound n (n_c - k) candidates of k + 1 indices
     const double child_bytes = (double)n * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
     if (gen_children && child_bytes > 512e6) return false;
@@ -1305,8 +850,7 @@ static bool small_path_ok(const mpc_handle *h, long long n, int k, int32_t flags
 static std::atomic<long long> g_small_levels{0}, g_small_retry_theta{0}, g_small_retry_x{0}, g_small_retry_cands{0}, g_small_repeats{0}, g_small_repeats_doubtful{0};
 static void small_debug_note(const int32_t *cnt_host) {
     static const bool on = [] {
-        const char *ev = std::getenv("MPC_DEBUG_SMALL");
-        if (!(ev && ev[0] == '1')) return false;
+        if (knob_process("MPC_DEBUG_SMALL") == 0.0) return false;
         std::atexit([] { std::fprintf(stderr, "[mpc] small levels %lld: with doubtful candidates after the theta stage %lld, after the (x,theta) stage %lld (candidates %lld); repeated on the classic path %lld (because of doubtful candidates %lld)\n",
                                       g_small_levels.load(), g_small_retry_theta.load(), g_small_retry_x.load(), g_small_retry_cands.load(), g_small_repeats.load(), g_small_repeats_doubtful.load()); });
         return true;
@@ -1333,7 +877,7 @@ static int dict_nxc(const mpc_handle *h) { return h->fast_x >= 2 ? 32 : 16; }   
 static bool dict_will_store(const mpc_handle *h, size_t nn, int32_t gen_children) {
     const int nxc = dict_nxc(h);
     const double need_gb = (double)nn * ((long long)nxc * h->Pf.n_d0r * 8.0 + dict_ints(h->Pf.n_d0r, nxc, h->n_c) * 4.0) / 1e9;
-    return gen_children && need_gb <= h->dict_budget_gb;
+    return gen_children && need_gb <= h->kn.dict_budget_gb;
 }
 // The dictionary cache of a level's (x,theta) stage: record strides, the previous level's records if its children know their parent
 // slots, and -- if the level stores (h->storing) -- this level's buffers.  The clearing of dict_stored[dict_cur] is the caller's.
@@ -1342,7 +886,7 @@ static int dict_cache_begin(mpc_handle *h, size_t nn, int32_t gen_children, hipS
     h->dict_stride_d = (long long)nxc * h->Pf.n_d0r;   // column-major tableau
     h->dict_stride_i = dict_ints(h->Pf.n_d0r, nxc, h->n_c);
     dc = DictCache{};
-    dc.fresh_limit = h->x_fresh_limit; dc.second_max = h->x_second_max;
+    dc.fresh_limit = h->kn.x_fresh_limit; dc.second_max = h->kn.x_second_max;
     dc.stride_d = h->dict_stride_d; dc.stride_i = h->dict_stride_i;
     if (h->have_prev_dict && h->have_parent_slot) {
         dc.parent_slot = h->parent_slot.as<int32_t>();
@@ -1470,20 +1014,20 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     ThetaArgs ta = h->targs;
     ta.chunk = 1;
     const int kd = k - h->targs.ne;   // rows the one-thread KKT kernel solves for (the equality rows are eliminated)
-    if (h->kkt_mode == 0 && kd >= 1 && kd <= KKT_THREAD_MAX && !h->no_kkt_thread) {
+    if (h->kkt_mode == 0 && kd >= 1 && kd <= KKT_THREAD_MAX && !h->kn.no_kkt_thread) {
         HIP_TRY(h, h->kkt_code.ensure(nn, st));
         HIP_TRY(h, h->kkt_L.ensure(nn * (size_t)k * (h->n_t + 1) * sizeof(double), st));
         kkc = h->kkt_code.as<uint8_t>(); kkl = h->kkt_L.as<double>();
         ThetaArgs tk = h->targs;
         // the kernel lists the candidates it leaves to the theta stage itself (one atomic per workgroup; a work list: its order changes nothing)
-        const bool kkt_lists = !h->no_kkt_lists;
+        const bool kkt_lists = !h->kn.no_kkt_lists;
         if (kkt_lists) {
             HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
             tk.kt_list = h->theta_list.as<int32_t>(); tk.kt_n = dcnt + 0;
             tk.kx_list = h->xq_list.as<int32_t>(); tk.kx_n = dcnt + 10;
         }
         // KKT_SPREAD lanes per candidate while the active set is small (the kernel's comment): the level's 50 us floor becomes ~15
-        const bool spread = h->kkt_spread > 0 && kd <= KKT_SPREAD_KMAX;
+        const bool spread = h->kn.kkt_spread > 0 && kd <= KKT_SPREAD_KMAX;
         const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256));
         launch_kkt_thread(kd, h->fast_t, spread, g, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr);
         if (!kkt_lists) hipLaunchKernelGGL(k_compact_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, ST_TODO, ST_TODO, h->theta_list.as<int32_t>(), dcnt + 0);
@@ -1497,7 +1041,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     // three launches on them at each of its two verdict stages: ONE partition lists them as class 0 beside the classes below, the level
     // goes on without them, and if there was one (counted in [4] / [24]) the host repeats the level on the classic path -- as it does for
     // the other rare cases.  The end of the level is one launch (k_small_end) instead of five, the scan carries the publish.
-    const bool fused = !h->theta_open && !h->no_small_fuse;
+    const bool fused = !h->theta_open && !h->kn.no_small_fuse;
     if (!fused) {
         hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 12);
         hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 12);
@@ -1521,15 +1065,15 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         { int rcb = small_region_slots(h, nn, st, ldk); if (rcb) return rcb; }
         RegionStream rs{};
         rs.n_opt_dev = dcnt + 6;
-        rs.w_cap = h->grid_r2; rs.w_max = h->rsplit_max;
-        const int W = h->no_rsplit ? 1 : 0;   // 0: chosen in the kernel from the number of optimal candidates
-        grid_r = (unsigned)std::min<long long>(n * std::max(h->rsplit_max, 1), h->grid_r2);
+        rs.w_cap = h->grid_r2; rs.w_max = h->kn.rsplit_max;
+        const int W = h->kn.no_rsplit ? 1 : 0;   // 0: chosen in the kernel from the number of optimal candidates
+        grid_r = (unsigned)std::min<long long>(n * std::max(h->kn.rsplit_max, 1), h->grid_r2);
         const DevProblem *pr = h->pr2_dev.as<DevProblem>();
         const int nt_r = region2_nt(h->fast_r);
         rx.pr = pr; rx.fr = h->frontier.as<int32_t>(); rx.k = k; rx.opt_list = h->opt_ptr; rx.n = (int)n; rx.status = h->status.as<uint8_t>();
         rx.headd = h->headd.as<double>(); rx.headi = h->headi.as<int32_t>(); rx.fd = h->fd; rx.fi = h->fi; rx.epool = h->epool.as<double>(); rx.ctr = ctr;
         rx.kkc = kkc; rx.kkl = kkl; rx.W = W; rx.kept_g = h->kept_g.as<uint8_t>(); rx.ldk = ldk; rx.done_g = h->done_g.as<unsigned int>();
-        rx.tvp_box = h->no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r; rx.rs = rs;
+        rx.tvp_box = h->kn.no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r; rx.rs = rs;
     }
     // (the launch itself comes below: together with the (x,theta) kernel in one grid where an instantiation of the pair exists)
     auto region2_alone = [&]() -> int {
@@ -1547,7 +1091,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     const int32_t *needx_n = dcnt + 7;
     const bool quick_test = !h->storing && dc.parent_slot;
     bool merged_rx = false;
-    if (fused && !quick_test && !h->no_small_rx) {
+    if (fused && !quick_test && !h->kn.no_small_rx) {
         // region kernel + (x,theta) kernel as ONE grid (batch_level.hpp, SmallRX): the two work on disjoint candidates
         DictCache d = dc;
         d.n_list_dev = needx_n;
@@ -1621,7 +1165,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     h->n_smallpath++;
     small_debug_note(cnt_host);
     if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) { h->n_smallpath_doubtful++; g_small_repeats_doubtful++; }
-    if (host_ctr.n_rretry > 0 || cnt_host[17] > 0 || h->test_small_fallback || (fused && (cnt_host[4] > 0 || cnt_host[24] > 0))) {
+    if (host_ctr.n_rretry > 0 || cnt_host[17] > 0 || h->kn.test_small_fallback || (fused && (cnt_host[4] > 0 || cnt_host[24] > 0))) {
         // a candidate k_region2 gave up on (the LDS-engine region kernel is not part of this path), or one that turned out optimal
         // after the region launch: the level is repeated classically
         h->n_smallpath_fallback++; g_small_repeats++;
@@ -1630,7 +1174,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         h->n_prev = 0;
         // A program that produces doubtful candidates keeps doing so (measured: 10-17 % of the small levels of random mpQPs, none on the
         // named configurations): its handle goes back to re-solving them in place, so the repeat is paid once per handle.
-        if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) h->no_small_fuse = true;
+        if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) h->kn.no_small_fuse = true;
         *fallback = true;
         return MPC_OK;
     }
@@ -1674,21 +1218,21 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
     m.k = k; m.kd = k - h->targs.ne; m.fast_t = h->fast_t; m.fast_x = h->fast_x; m.fast_r = h->fast_r; m.mw = h->mw;
     m.gen_children = gen_children ? 1 : 0;
     m.n = n; m.grid_f = h->grid_f; m.grid_r2 = h->grid_r2; m.n_cu = h->n_cu; m.lds_f = h->lds_f; m.lds_v = h->lds_v; m.lds_r2 = h->lds_r2;
-    m.rsplit_max = h->rsplit_max;
+    m.rsplit_max = h->kn.rsplit_max;
     m.pf = h->pf_dev.as<DevProblem>(); m.pr = h->pr2_dev.as<DevProblem>(); m.Pv = h->Pv;
     m.fr = h->frontier.as<int32_t>(); m.status = h->status.as<uint8_t>(); m.ctr = h->ctr.as<LevelCounters>(); m.dcnt = h->dcnt.as<int32_t>();
     m.theta_list = h->theta_list.as<int32_t>(); m.retry_list = h->retry_list.as<int32_t>(); m.part_lists = h->part_lists.as<int32_t>();
     m.targs = h->targs;
     m.zero[m.n_zero++] = {h->ctr.p, sizeof(LevelCounters)};
     m.zero[m.n_zero++] = {h->dcnt.p, 32 * sizeof(int32_t)};
-    m.use_kkt = (h->kkt_mode == 0 && m.kd >= 1 && m.kd <= 8 && h->no_kkt_thread != 1) ? 1 : 0;
-    if (m.use_kkt && h->kkt_spread > 0 && m.kd <= BATCH_KKT_SPREAD_KMAX) m.use_kkt = 2;   // BATCH_KKT_SPREAD lanes per candidate (k_kkt_thread)
+    m.use_kkt = (h->kkt_mode == 0 && m.kd >= 1 && m.kd <= 8 && h->kn.no_kkt_thread != 1) ? 1 : 0;
+    if (m.use_kkt && h->kn.kkt_spread > 0 && m.kd <= BATCH_KKT_SPREAD_KMAX) m.use_kkt = 2;   // BATCH_KKT_SPREAD lanes per candidate (k_kkt_thread)
     m.kkt_listed = 0;
     if (m.use_kkt) {
         HIP_TRY(h, h->kkt_code.ensure(nn, st));
         HIP_TRY(h, h->kkt_L.ensure(nn * (size_t)k * (h->n_t + 1) * sizeof(double), st));
         m.kkt_code = h->kkt_code.as<uint8_t>(); m.kkt_L = h->kkt_L.as<double>();
-        if (!h->no_kkt_lists) {   // the kernel lists what it leaves to the theta stage (as level_run_small)
+        if (!h->kn.no_kkt_lists) {   // the kernel lists what it leaves to the theta stage (as level_run_small)
             HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
             m.targs.kt_list = m.theta_list; m.targs.kt_n = m.dcnt + 0;
             m.targs.kx_list = h->xq_list.as<int32_t>(); m.targs.kx_n = m.dcnt + 10;
@@ -1701,9 +1245,9 @@ static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, Bat
         { int rcb = small_region_slots(h, nn, st, ldk); if (rcb) return rcb; }
         m.zero[m.n_zero++] = {h->done_g.p, nn * 2 * sizeof(unsigned int)};
         m.rs.n_opt_dev = m.dcnt + 18;   // the region launch comes last in the batch form: all optimal candidates, class 2 of the partition at [16..19]
-        m.rs.w_cap = h->grid_r2; m.rs.w_max = h->rsplit_max;
-        m.W = h->no_rsplit ? 1 : 0;
-        m.ldk = ldk; m.fd = h->fd; m.fi = h->fi; m.no_rbox = h->no_rbox ? 1 : 0;
+        m.rs.w_cap = h->grid_r2; m.rs.w_max = h->kn.rsplit_max;
+        m.W = h->kn.no_rsplit ? 1 : 0;
+        m.ldk = ldk; m.fd = h->fd; m.fi = h->fi; m.no_rbox = h->kn.no_rbox ? 1 : 0;
         m.headd = h->headd.as<double>(); m.headi = h->headi.as<int32_t>(); m.epool = h->epool.as<double>();
         m.kept_g = h->kept_g.as<uint8_t>(); m.done_g = h->done_g.as<unsigned int>();
         // retry slots of the LDS-engine region kernel (launch_region_v1's buffers)
@@ -1748,7 +1292,7 @@ static int batch_finish(mpc_handle *h, int32_t gen_children, const BatchMember &
     const int32_t *cnt_host = h->cnt_host();
     h->n_smallpath++;
     small_debug_note(cnt_host);
-    if (cnt_host[28] > m.rcap || h->test_small_fallback) {
+    if (cnt_host[28] > m.rcap || h->kn.test_small_fallback) {
         // more candidates k_region2 gave up on than retry slots were reserved (never observed): the member repeats the level alone
         h->n_smallpath_fallback++;
         *fallback = true;
@@ -1822,19 +1366,19 @@ int mpc_level_batch_start(mpc_handle **hs, int32_t n_handles, const int32_t *gen
     t->gen.assign(gen_children, gen_children + n_handles);
     t->flags = flags & ~(MPC_LEVEL_THEN_BASE | MPC_LEVEL_ONLY_BASE | MPC_LEVEL_STREAM);
     t->members.reserve(n_handles);
-    const double budget_gb = [] { const char *ev = std::getenv("MPC_BATCH_BUDGET_GB"); return ev ? std::atof(ev) : 160.0; }();
+    const double budget_gb = batch_budget_gb();
     double used_gb = 0.0;
     for (int i = 0; i < n_handles; ++i) {
         mpc_handle *h = hs[i];
         stream_release(h);
         { int rcj = x1_join(h); if (rcj) return rcj; }
         // MPC_SMALLPATH_MAX bounds the single-program path only (above it the overlapped classic path is faster for ONE program)
-        const long long keep_max = h->smallpath_max;
+        const long long keep_max = h->kn.smallpath_max;
         // (bounded: the shared launches compact / partition / scan a member with single 1024-thread blocks -- beyond 2^18 candidates a
         // member takes its turn alone, on the multi-block kernels of the classic path)
-        h->smallpath_max = std::max<long long>(keep_max, 1LL << 18);
+        h->kn.smallpath_max = std::max<long long>(keep_max, 1LL << 18);
         const bool ok = small_path_ok(h, h->n, h->k, t->flags, gen_children[i]);
-        h->smallpath_max = keep_max;
+        h->kn.smallpath_max = keep_max;
         bool ok_i = ok;
         if (ok_i) {
             // MPC_BATCH_BUDGET_GB (default 160 of the 288 GB): members beyond it take their turn after the shared launches, one at a time
@@ -1915,7 +1459,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
     HIP_TRY(h, hipSetDevice(h->device));
     stream_release(h);
     // (a deferred k_x1 of the previous level: joined at once unless this is a large level whose first kernel, k_kkt_thread, reads no dictionary)
-    const bool x1_late_join = h->x1_pending && h->fast && !h->force_v1 && h->kkt_mode == 0 && h->no_kkt_thread != 1 &&
+    const bool x1_late_join = h->x1_pending && h->fast && !h->kn.force_v1 && h->kkt_mode == 0 && h->kn.no_kkt_thread != 1 &&
                               (h->skip_small || !small_path_ok(h, h->n, h->k, flags, gen_children)) && h->k - h->targs.ne >= 1 && h->k - h->targs.ne <= KKT_THREAD_MAX;
     if (!x1_late_join) { int rcj = x1_join(h); if (rcj) return rcj; }
     if (!h->skip_small && small_path_ok(h, h->n, h->k, flags, gen_children)) {
@@ -1931,7 +1475,7 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
     LevelRun lv(h, gen_children, flags);
     if (lv.n > 0) {
         if (int rc = lv.begin()) return rc;                            // buffers, counters cleared, pruned buckets
-        if (h->fast && !h->force_v1) {
+        if (h->fast && !h->kn.force_v1) {
             if (int rc = lv.kkt_stage()) return rc;                    // k_kkt_thread
             if (int rc = lv.early_thread_pass()) return rc;            // last level: k_xq_thread on stream2, beside ...
             if (int rc = lv.theta_stage()) return rc;                  // ... k_theta2
@@ -2479,7 +2023,7 @@ static int level_regions_slots_impl(mpc_handle *h, double *head_d, int32_t *head
         }
     }
     HIP_TRY(h, hipStreamSynchronize(s));
-    if (h->debug_cycles && h->used_region2) {
+    if (h->kn.debug_cycles && h->used_region2) {
         long long hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (long long w = 0; w < n_opt; ++w) { const int32_t *oi = head_i + (size_t)w * fi; if (oi[0] == ST_RETRY) hist[oi[7] & 7]++; }
         std::fprintf(stderr, "[mpc] k=%d region retries by reason: chebyshev %lld, r->0 %lld, refactor-after-chebyshev %lld, row lost %lld, >8 refactors %lld, refactor failed %lld\n",
@@ -2609,7 +2153,7 @@ int mpc_level_batch_fetch(mpc_handle **hs, int32_t n_handles, double *const *hea
             continue;
         }
         (void)hipGetLastError();
-        { static const bool dbg = [] { const char *ev = std::getenv("MPC_DEBUG_MANY"); return ev && ev[0] == '1'; }();
+        { const bool dbg = debug_many();
           if (dbg) std::fprintf(stderr, "[many] member %d outside the copy launch: level_done %d streamed %d regions %lld n_opt %lld region2 %d rretry %lld cap_slots %lld erows %lld cap_rows %lld\n", i, (int)h->level_done, (int)h->so.active,
                                 (long long)h->n_regions, (long long)h->n_opt, (int)h->used_region2, (long long)h->n_rretry, (long long)cap_slots[i], (long long)h->n_erows, (long long)cap_rows[i]); }
         const int rc = mpc_level_regions_slots_nowait(h, head_d[i], head_i[i], cap_slots[i], erows[i], cap_rows[i], n_slots + i, n_rows + i);
@@ -2653,7 +2197,7 @@ int mpc_debug_xq_hist(unsigned long long *out) {
 #endif
 int mpc_engine_kind(mpc_handle *h, int32_t out[8]) {
     if (!h || !out) return MPC_ERR_INVALID;
-    const bool fast = h->fast && !h->force_v1;
+    const bool fast = h->fast && !h->kn.force_v1;
     out[0] = fast ? 1 : 0;
     out[1] = fast ? (h->fast_t & 1) + 1 : 0;
     out[2] = fast ? (h->fast_x & 1) + 1 : 0;
@@ -2661,7 +2205,7 @@ int mpc_engine_kind(mpc_handle *h, int32_t out[8]) {
     out[4] = fast ? (h->fast_t <= 1 ? 4 : (h->fast_t <= 3 ? 8 : 10)) : 0;
     out[5] = h->theta_open ? 1 : 0;
     out[6] = h->kkt_mode;
-    out[7] = (fast && h->kkt_mode == 0 && h->no_kkt_thread != 1) ? KKT_THREAD_MAX : 0;
+    out[7] = (fast && h->kkt_mode == 0 && h->kn.no_kkt_thread != 1) ? KKT_THREAD_MAX : 0;
     return MPC_OK;
 }
 int mpc_sync(mpc_handle *h) {
@@ -2844,7 +2388,7 @@ static void many_loop(ManyJob *J) {
     if (B == 0) return finish(MPC_OK);
     mpc_handle *h0 = J->hs[0];
     if (hipSetDevice(h0->device) != hipSuccess) return finish(fail(h0, MPC_ERR_HIP, "mpc_solve_many: hipSetDevice failed"));
-    const double budget_gb = 0.6 * [] { const char *ev = std::getenv("MPC_BATCH_BUDGET_GB"); return ev ? std::atof(ev) : 160.0; }();   // (headroom as in the host layer's loop)
+    const double budget_gb = 0.6 * batch_budget_gb();   // (headroom as in the host layer's loop)
     std::vector<int> depth(B, 0);
     std::vector<int32_t> active;
     for (int i = 0; i < B; ++i) {
@@ -2861,7 +2405,7 @@ static void many_loop(ManyJob *J) {
         return mpc_level_batch_start(hh.data(), (int32_t)hh.size(), gg.data(), J->flags & ~MPC_SOLVE_MANY_BASE, token);
     };
     void *token = nullptr;
-    static const bool dbg = [] { const char *ev = std::getenv("MPC_DEBUG_MANY"); return ev && ev[0] == '1'; }();
+    const bool dbg = debug_many();
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms_since = [&](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(now() - a).count(); };
     { const auto ts = now(); if (!active.empty()) { const int rc = start(active, &token); if (rc != MPC_OK) return finish(rc); } if (dbg) std::fprintf(stderr, "[many] first start %.3f ms\n", ms_since(ts)); }
