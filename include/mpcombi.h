@@ -829,6 +829,42 @@ int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t
 int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const double *start, double tol,
                     int32_t *status, int32_t *wide, uint64_t *kept, double *point, int64_t *stats, float *ms);
 
+/* ---- projections of polytopes (geometry.project_rows_of) -------------------------------------------------------------- */
+/* Polytopes of R^n as unit rows [o | n] in CSR form by row_off, up to MPC_PROJECT_MAX_ROWS rows each.  Stateless; an error text is read
+ * with mpc_last_error(NULL).
+ *
+ * mpc_project_rows: the projection of every polytope onto its first n - n_elim coordinates (k_project_rows), by Fourier-Motzkin
+ *   elimination of the trailing n_elim coordinates, the last one first, every step followed by the sequential rule of mpc_reduce_rows.
+ *   First the radius run of mpc_reduce_rows from start: radius <= tol, MPC_PROJECT_THIN.  A step eliminates coordinate j, the last one
+ *   left, over the live rows in order; c is a row's coefficient of j, Z: |c| <= 1e-12, P: c > 1e-12, N: c < -1e-12.  The new rows: the
+ *   rows of Z in order without column j (scaled to a unit normal again unless c == 0), then for p over P in order and q over N in order
+ *   inside it (-c_q) row_p + c_p row_q without column j, scaled to a unit normal.  A combination whose normal has a norm <= 1e-9 before
+ *   scaling says 0 <= rhs: it is dropped, or with rhs < -tol the polytope is empty, MPC_PROJECT_THIN.  With P or N empty the rows of Z
+ *   alone are kept; no row left: MPC_PROJECT_WHOLE (the whole space).  |Z| + |P||N| > 512: MPC_PROJECT_TOO_LARGE.  Then the interior
+ *   point loses coordinate j, the radius run from it (radius <= tol: MPC_PROJECT_THIN), and the sequential rule over the new rows, every
+ *   run started where that run ended; the kept rows, in order, are the live rows of the next step.  A run that is unbounded or stopped at
+ *   the pivot cap counts as "kept".  n_elim == 0: one pass of mpc_reduce_rows, the kept rows returned.
+ *   status[q]  MPC_PROJECT_OK, _THIN, _WHOLE or _TOO_LARGE (a step above 512 rows, or more than out_cap rows at the end); only
+ *              MPC_PROJECT_OK returns rows: n_out[q] of them in out_rows[q][out_cap][n - n_elim + 1], unit rows [o | n], zeros behind them; the
+ *              others have n_out[q] = 0.
+ *   wide[q]    the number of unbounded or capped runs of polytope q.   peak[q] (may be NULL): the largest |Z| + |P||N| of its steps.
+ *   start      [n_poly][n] where the first run of a polytope starts, or NULL: the origin.
+ *   point      [n_poly][n - n_elim] or NULL: the interior point of the result (MPC_PROJECT_OK; zeros otherwise).
+ *   n_poly == 0: MPC_OK without a launch.
+ *   stats (may be NULL): [0] polytopes, [1] thin, [2] whole, [3] too large, [4] steps, [5] rows made, [6] LPs, [7] pivots, [8] unbounded
+ *   or capped runs.
+ * MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n <= 16, 0 <= n_elim <= n - 1, 1..512 rows per
+ * polytope, finite rows with unit normals, finite start, tol finite and >= 0, 1 <= out_cap <= 512, n_poly in 0..2^31 - 1, row_off
+ * non-decreasing from 0.  Deterministic: atomics only in the counters. */
+#define MPC_PROJECT_MAX_ROWS 512
+#define MPC_PROJECT_OK 0
+#define MPC_PROJECT_THIN 1
+#define MPC_PROJECT_WHOLE 2
+#define MPC_PROJECT_TOO_LARGE 3
+int mpc_project_rows(int32_t device, int32_t n, int32_t n_elim, int64_t n_poly, const int64_t *row_off, const double *ef_rows,
+                     const double *start, double tol, int32_t out_cap, double *out_rows, int32_t *n_out, int32_t *status, int32_t *wide,
+                     int32_t *peak, double *point, int64_t *stats, float *ms);
+
 /* ---- backward exit cells of a closed loop (Solution.invariant_set) --------------------------------------------------- */
 /* Regions and maps as for the transition and exit calls above; xs [n_regions][n_t] is a feasible point of every region (mpc_merge_regions).
  * A CELL is a polytope of 1..256 unit rows that lies in region source[c].  The cells of step 0 are given (the exit pieces of

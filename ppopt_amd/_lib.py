@@ -281,6 +281,8 @@ def load():
                                           _ip, _ip, _ip, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_reduce_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double, _ip, _ip, _u64p, _dp, _lp,
                                            ctypes.POINTER(ctypes.c_float)]),
+        'mpc_project_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double,
+                                            ctypes.c_int32, _dp, _ip, _ip, _ip, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_backward_exits': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _lp, _ip, ctypes.c_int64, _lp, _dp,
                                               _ip, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _lp, _lp, _dp, _ip, _ip, _ip, _ip, _dp,
                                               _ip, _ip, _ip, _lp, ctypes.POINTER(ctypes.c_float), _lp, ctypes.POINTER(ctypes.c_float)]),
@@ -305,7 +307,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
                     'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
-                    'mpc_backward_exits']
+                    'mpc_backward_exits', 'mpc_project_rows']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1435,6 +1437,30 @@ def reduce_rows(row_off, ef_rows, start, tol: float, device: int = 0):
     k = numpy.arange(len(ef)) - numpy.repeat(off[:-1], counts)
     kept = ((mask[poly, k >> 6] >> (k & 63).astype(numpy.uint64)) & numpy.uint64(1)).astype(bool)
     return kept, status, wide, point, stats
+
+
+PROJECT_MAX_ROWS = 512   # rows per polytope and per elimination step of mpc_project_rows (include/mpcombi.h)
+PROJECT_OK, PROJECT_THIN, PROJECT_WHOLE, PROJECT_TOO_LARGE = range(4)
+PROJECT_STATUS = ('OK', 'THIN', 'WHOLE', 'TOO_LARGE')
+
+
+def project_rows(row_off, ef_rows, n_elim: int, start, tol: float, out_cap: int = PROJECT_MAX_ROWS, device: int = 0):
+    """The projections of the polytopes onto their first n - n_elim coordinates (include/mpcombi.h, mpc_project_rows): (out_off
+    [n_poly + 1] int64, out_rows [out_off[-1], n - n_elim + 1] unit rows, status [n_poly] int32 (PROJECT_*), wide, peak int32, point
+    [n_poly, n - n_elim], stats)."""
+    off, ef = _merge_rows('project_rows', row_off, ef_rows)
+    n, count = ef.shape[1] - 1, len(off) - 1
+    k = n - int(n_elim)
+    s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(count, n)
+    cap = int(out_cap)
+    rows = numpy.zeros((count, max(cap, 0), max(k, 0) + 1))
+    n_out, status, wide, peak = (numpy.zeros(count, dtype=numpy.int32) for _ in range(4))
+    point = numpy.zeros((count, max(k, 0)))
+    stats = _geometry_call('mpc_project_rows', ('polytopes', 'thin', 'whole', 'too_large', 'steps', 'rows_made', 'lps', 'pivots', 'wide'), int(device),
+                           n, int(n_elim), count, off, ef, s0, float(tol), cap, rows, n_out, status, wide, peak, point)
+    out_off = numpy.concatenate([[0], numpy.cumsum(n_out, dtype=numpy.int64)]).astype(numpy.int64)
+    taken = numpy.arange(cap)[None, :] < n_out[:, None]
+    return out_off, rows[taken], status, wide, peak, point, stats
 
 
 # status of mpc_backward_exits (include/mpcombi.h)

@@ -1,7 +1,7 @@
 // geometry.hip -- the stateless geometry entry points of the C ABI (include/mpcombi.h): hit-and-run sampling, slices, point
 // location (list scan, adjacency walk, search tree), tree build, closed-loop simulation, vertex enumeration, region volumes and region
 // merging and the overlap removal.  None of them knows mpc_handle; each is a batch in, one or a few launches, the results out.  Their kernels are compiled here
-// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, simplex.hpp); the pools and the scaffold
+// and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, project.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +25,7 @@
 #include "transition.hpp"
 #include "exit_sets.hpp"
 #include "reduce.hpp"
+#include "project.hpp"
 #include "invariant.hpp"
 #include "host_common.hpp"
 
@@ -1174,8 +1175,8 @@ extern "C" int mpc_region_moments(int32_t device, int32_t n_t, int64_t n_poly, c
                      budget, volume, centroid, n_simplices, status, second_moment, stats);
 }
 
-// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets, row reduction, backward exits
-// (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, invariant.hpp)  Every call checks its arguments in one order
+// ---- the family of wavefront-per-item LP calls: region merging, overlap removal, transition graph, exit sets, row reduction, backward exits,
+// projection (merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, invariant.hpp, project.hpp)  Every call checks its arguments in one order
 // (regions, pieces, tol, the item count, the dense arrays, the empty batch, missing arrays, the index arrays, the rest), uploads,
 // launches one wavefront per item over unit rows [o | n] in LDS, and downloads the results and its counters.  What the calls share is
 // here once: the checkers return the refusal, family_launch and family_close are the two ends of the device part.
@@ -1245,7 +1246,7 @@ template <class K, class... A> static void family_launch(OneShot &s, K kernel, i
 
 // the n counters to stats, the device time to ms, and the call's code
 static int family_close(OneShot &s, const DevBuf &d_cnt, int n, int64_t *stats, float *ms) {
-    unsigned long long cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long cnt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     s.download(cnt, d_cnt, (size_t)n * 8);
     if (stats) for (int i = 0; i < n; ++i) stats[i] = (int64_t)cnt[i];
     s.elapsed(ms);
@@ -1564,6 +1565,49 @@ extern "C" int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, cons
     s.download(kept, d_k, words);
     if (point) s.download(point, *d_point, np * n_t * 8);
     return family_close(s, d_cnt, 5, stats, ms);
+}
+
+// ---- projections of polytopes (project.hpp) ------------------------------------------------------------------------------
+extern "C" int mpc_project_rows(int32_t device, int32_t n, int32_t n_elim, int64_t n_poly, const int64_t *row_off, const double *ef_rows,
+                                const double *start, double tol, int32_t out_cap, double *out_rows, int32_t *n_out, int32_t *status, int32_t *wide,
+                                int32_t *peak, double *point, int64_t *stats, float *ms) {
+    const char *who = "mpc_project_rows";
+    family_open(stats, 9, ms);
+    int m_max = 1;
+    if (int rc = merge_check(who, n, n_poly, row_off, ef_rows, &m_max, PJ_MAX_ROWS)) return rc;
+    if (n_elim < 0 || n_elim > n - 1) return bad(who, "n_elim must lie in 0..n - 1");
+    if (int rc = check_tol(who, tol)) return rc;
+    if (out_cap < 1 || out_cap > PJ_MAX_ROWS) return bad(who, "out_cap must lie in 1.." + std::to_string(PJ_MAX_ROWS));
+    if (n_poly == 0) return MPC_OK;
+    if (!out_rows || !n_out || !status || !wide) return bad(who, "missing array");
+    if (start)
+        if (int rc = check_finite(who, "start", start, n_poly * n)) return rc;
+    if (int rc = select_device(nullptr, device)) return rc;
+    // The rows of each LDS area: what a step of an item can make.  One step makes |Z| + |P||N| <= max(m, m^2 / 4) rows of m; the rows
+    // a second step starts from are known on the device alone, so two steps or more take the limit.
+    const int m_lds = n_elim == 0 ? m_max : n_elim == 1 ? std::min(PJ_MAX_ROWS, std::max(m_max, (m_max / 2) * ((m_max + 1) / 2))) : PJ_MAX_ROWS;
+    const size_t lds = pj_lds_bytes(m_lds, n);   // 512 rows at n = 16: 148,472 bytes (the static arrays add 2,112)
+    const int k = n - n_elim;
+    const size_t np = (size_t)n_poly, out_bytes = np * (size_t)out_cap * (k + 1) * 8;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_poly, row_off, ef_rows, n + 1);
+    DevBuf *d_start = start ? &s.upload(start, np * n * 8) : nullptr, *d_point = point ? &s.buf(np * k * 8) : nullptr, *d_peak = &s.buf(np * 4);
+    DevBuf &d_out = s.buf(out_bytes), &d_no = s.buf(np * 4), &d_st = s.buf(np * 4), &d_w = s.buf(np * 4), &d_cnt = family_counters(s, 9);
+    s.fill(d_out, 0, out_bytes);                   // the rows behind n_out[q] are zero
+    if (point) s.fill(*d_point, 0, np * k * 8);   // an item without a result writes no point
+    ProjectArgs a{};
+    a.n = n; a.n_elim = n_elim; a.m_lds = m_lds; a.out_cap = out_cap; a.n_poly = n_poly;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+    a.status = d_st.as<int32_t>(); a.n_out = d_no.as<int32_t>(); a.wide = d_w.as<int32_t>(); a.peak = d_peak->as<int32_t>();
+    a.out_rows = d_out.as<double>(); a.point = d_point ? d_point->as<double>() : nullptr; a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_project_rows, n_poly, lds, a);
+    s.download(status, d_st, np * 4);
+    s.download(n_out, d_no, np * 4);
+    s.download(wide, d_w, np * 4);
+    if (peak) s.download(peak, *d_peak, np * 4);
+    s.download(out_rows, d_out, out_bytes);
+    if (point) s.download(point, *d_point, np * k * 8);
+    return family_close(s, d_cnt, 9, stats, ms);
 }
 
 // ---- backward exit cells of a closed loop (invariant.hpp) ---------------------------------------------------------------

@@ -23,3 +23,11 @@ class Polytope:
         comes back unchanged."""
         from .reduce import reduced_polytope
         return reduced_polytope(self, tol=tol, device=device)
+
+    def project(self, keep, tol: float = 1e-8, device: int = 0) -> 'Polytope':
+        """The projection of this polytope onto the coordinates ``keep``, in their order, without redundant rows (geometry.project,
+        DESIGN §3.24): the rows are scaled to unit normals first (a zero row is a ValueError) and the result has unit rows.  The whole
+        space comes back as a Polytope without rows; a projection that is thin (Chebyshev radius <= tol, or empty) or needs more than
+        512 rows at a step is a ValueError that names the status and the peak row count."""
+        from .project import projected_polytope
+        return projected_polytope(self, keep, tol=tol, device=device)

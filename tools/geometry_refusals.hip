@@ -1,6 +1,6 @@
-// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce and backward-exit calls (mpc_merge_regions,
+// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce, project and backward-exit calls (mpc_merge_regions,
 // mpc_merge_pairs, mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split, mpc_reduce_rows,
-// mpc_backward_exits) as a stand-alone host program for a sanitizer build:
+// mpc_project_rows, mpc_backward_exits) as a stand-alone host program for a sanitizer build:
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/geometry_refusals.hip -o geometry_refusals
 // It includes geometry.hip itself and stands in for the pools of mpcombi_hip.hip, which a refusal never reaches: every call below must
 // come back MPC_ERR_INVALID with a message before a device is selected (an empty batch: MPC_OK), so the program needs no GPU and
@@ -335,6 +335,62 @@ static void reduce_cases() {
     expect("no polytopes, no arrays", mpc_reduce_rows(0, nt, 0, nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), MPC_OK);
 }
 
+// mpc_project_rows
+static void project_cases() {
+    const int n = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    const int cap = 8;
+    VI status(2), wide(2), n_out(2), peak(2);
+    VD out(2 * cap * 2), point(2);
+    int64_t stats[9];
+    float ms = 0.0f;
+    struct Args { int n, n_elim; VL off; VD ef, start; double tol; int out_cap; };
+    const Args good{n, 1, {0, 4, 8}, ef, {0.5, 0.5, 1.0, 0.5}, 1e-8, cap};
+    auto project = [&](const Args &g, int64_t n_poly = -2) {
+        return mpc_project_rows(0, g.n, g.n_elim, n_poly == -2 ? (int64_t)g.off.size() - 1 : n_poly, g.off.data(), g.ef.data(), g.start.data(), g.tol,
+                                g.out_cap, out.data(), n_out.data(), status.data(), wide.data(), peak.data(), point.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;                                                                                            // 513 rows
+    for (int r = 0; r < 128; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    big.insert(big.end(), sq.begin(), sq.begin() + 3);
+    expect("n = 0", project(with([](Args &g) { g.n = 0; })));
+    expect("n = 17", project(with([](Args &g) { g.n = 17; })));
+    expect("n_elim < 0", project(with([](Args &g) { g.n_elim = -1; })));
+    expect("n_elim = n", project(with([](Args &g) { g.n_elim = 2; })));
+    expect("tol < 0", project(with([](Args &g) { g.tol = -1.0; })));
+    expect("tol NaN", project(with([&](Args &g) { g.tol = nan; })));
+    expect("tol inf", project(with([](Args &g) { g.tol = INFINITY; })));
+    expect("out_cap = 0", project(with([](Args &g) { g.out_cap = 0; })));
+    expect("out_cap = 513", project(with([](Args &g) { g.out_cap = 513; })));
+    expect("n_poly < 0", project(good, -1));
+    expect("n_poly = 2^31", project(good, 0x80000000ll));
+    expect("row_off[0] != 0", project(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("row_off decreases", project(with([](Args &g) { g.off = {0, 8, 4}; })));
+    expect("a polytope without rows", project(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("a polytope of 513 rows", project(with([&](Args &g) { g.off = {0, 513}; g.ef = big; g.start.resize(2); })));
+    expect("a non-finite row", project(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("a row that is not unit", project(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("start NaN", project(with([&](Args &g) { g.start[1] = nan; })));
+    expect("start inf", project(with([](Args &g) { g.start[2] = INFINITY; })));
+    const Args &g = good;
+    auto raw = [&](const int64_t *off, const double *rows, double *orows, int32_t *no, int32_t *st, int32_t *wd) {
+        return mpc_project_rows(0, n, 1, 2, off, rows, nullptr, 1e-8, cap, orows, no, st, wd, nullptr, nullptr, nullptr, nullptr);
+    };
+    expect("missing row_off", raw(nullptr, g.ef.data(), out.data(), n_out.data(), status.data(), wide.data()));
+    expect("missing ef_rows", raw(g.off.data(), nullptr, out.data(), n_out.data(), status.data(), wide.data()));
+    expect("missing out_rows", raw(g.off.data(), g.ef.data(), nullptr, n_out.data(), status.data(), wide.data()));
+    expect("missing n_out", raw(g.off.data(), g.ef.data(), out.data(), nullptr, status.data(), wide.data()));
+    expect("missing status", raw(g.off.data(), g.ef.data(), out.data(), n_out.data(), nullptr, wide.data()));
+    expect("missing wide", raw(g.off.data(), g.ef.data(), out.data(), n_out.data(), status.data(), nullptr));
+    expect("no polytopes is MPC_OK without a launch", project(with([](Args &a) { a.off = {0}; a.ef.clear(); a.start.clear(); })), MPC_OK);
+    expect("no polytopes, no arrays", mpc_project_rows(0, n, 1, 0, nullptr, nullptr, nullptr, 1e-8, cap, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                        nullptr, nullptr), MPC_OK);
+}
+
 // mpc_backward_exits
 static void backward_cases() {
     const int nt = 2;
@@ -431,6 +487,7 @@ int main() {
     transition_cases();
     exit_cases();
     reduce_cases();
+    project_cases();
     backward_cases();
     std::printf("%d unexpected\n", n_bad);
     return n_bad ? 1 : 0;
