@@ -904,6 +904,46 @@ int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions, const int
                        int32_t *cell_step, int32_t *cell_parent, int32_t *cell_wide, double *cell_point, int32_t *status, int32_t *steps,
                        int32_t *converged, int64_t *cells_per_step, float *step_ms, int64_t *stats, float *ms);
 
+/* ---- forward cells of a closed loop (Solution.reach_cells) ------------------------------------------------------------ */
+/* Regions and maps as above.  A CELL of step k is a polytope Q of 1..256 unit rows over the INITIAL state theta_0: the initial states whose
+ * state at step k lies in region cell_region[c], where theta_k = G theta_0 + g with [G | g] = cell_map[c] ([n_t][n_t + 1]).  The cells of
+ * step 0 are given, each inside its region, with an interior point each and the map [I | 0].  A cell of step k + 1 is
+ * Q n {theta_0 : P theta_0 + s in R_j} for a cell Q of step k and a region j of succ_idx[succ_off[i] .. succ_off[i + 1]), i = region(Q),
+ * under the NEXT MAP of Q, P = Phi_i G, s = Phi_i g + phi_i: every entry one sum over t ascending from 0.0 of plain IEEE products, so
+ * the maps are the same bits wherever they are computed.  No map is inverted.  Stateless; an error text is read with mpc_last_error(NULL).
+ *
+ * mpc_forward_cells runs every step itself.  The items of a step are ordered by parent cell, then as the successor list is; per item
+ *   (k_fwd_cells, one wavefront): the rows of R_j pulled back through the next map exactly as mpc_transition_pairs forms them (a constant
+ *   row with right-hand side below -tol: no cell and no LP; any other constant row is dropped); the radius of Q's rows and the pulled-back
+ *   ones from Q's point, stopped once it exceeds tol (optimal and not above tol: no cell; unbounded or capped: a cell, flagged wide, as is
+ *   every descendant); for a cell the sequential rule of mpc_reduce_rows over Q's rows, then the pulled-back ones, every run started where
+ *   the radius run ended.  The kept rows become the cell (k_fwd_emit), appended with point and map to the cell table ON THE DEVICE: between
+ *   steps only per-item status words and counts come to the host, which scans the offsets and lists the next items.
+ *   max_steps        so many steps are run (>= 0).  max_cells, max_rows_total: the capacity of the output arrays, step 0 included.
+ *   n_cells, cell_off [n_cells + 1], cell_rows [cell_off[n_cells]][n_t + 1], cell_region, cell_step, cell_parent (-1 at step 0, else the
+ *   index of Q), cell_wide, cell_point [max_cells][n_t] (step 0: as given; later: where the radius run ended), cell_map
+ *   [max_cells][n_t][n_t + 1]: all cells, step by step, a step in item order.
+ *   status           MPC_FORWARD_DONE: max_steps steps were run; MPC_FORWARD_EMPTY: a step yielded no cell, every trajectory has left;
+ *                    MPC_FORWARD_ROWS: a reduced cell keeps more than 256 rows (or an item more than 512); MPC_FORWARD_MAX_CELLS,
+ *                    MPC_FORWARD_MAX_ROWS_TOTAL: a step did not fit.  After the last three the cells of the completed steps are returned.
+ *   steps            the completed steps.  cells_per_step [max_steps + 1]; step_ms [max_steps] (either may be NULL): device ms of step
+ *                    k + 1, a step that found nothing or was refused included.
+ *   stats (may be NULL): [0] items, [1] cells found, [2] items emptied by a constant row, [3] LPs, [4] pivots, [5] unbounded or capped runs.
+ *   n_cells0 == 0 (MPC_FORWARD_EMPTY) or max_steps == 0 (MPC_FORWARD_DONE): MPC_OK without a launch (step 0 is returned).
+ * MPC_ERR_INVALID with a message, before a device is selected: everything mpc_backward_exits refuses, with successor lists for
+ * predecessor lists and without xs; cell_point0 missing or not finite.  Deterministic: atomics only in the counters. */
+#define MPC_FORWARD_DONE 0
+#define MPC_FORWARD_EMPTY 1
+#define MPC_FORWARD_ROWS 2
+#define MPC_FORWARD_MAX_CELLS 3
+#define MPC_FORWARD_MAX_ROWS_TOTAL 4
+int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                      const double *phi, const int64_t *succ_off, const int32_t *succ_idx, int64_t n_cells0, const int64_t *cell_off0,
+                      const double *cell_rows0, const int32_t *cell_region0, const double *cell_point0, double tol, int32_t max_steps,
+                      int64_t max_cells, int64_t max_rows_total, int64_t *n_cells, int64_t *cell_off, double *cell_rows, int32_t *cell_region,
+                      int32_t *cell_step, int32_t *cell_parent, int32_t *cell_wide, double *cell_point, double *cell_map, int32_t *status,
+                      int32_t *steps, int64_t *cells_per_step, float *step_ms, int64_t *stats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

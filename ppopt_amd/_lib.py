@@ -286,6 +286,9 @@ def load():
         'mpc_backward_exits': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _lp, _ip, ctypes.c_int64, _lp, _dp,
                                               _ip, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _lp, _lp, _dp, _ip, _ip, _ip, _ip, _dp,
                                               _ip, _ip, _ip, _lp, ctypes.POINTER(ctypes.c_float), _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_forward_cells': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _lp, _ip, ctypes.c_int64, _lp, _dp,
+                                             _ip, _dp, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _lp, _lp, _dp, _ip, _ip, _ip, _ip,
+                                             _dp, _dp, _ip, _ip, _lp, ctypes.POINTER(ctypes.c_float), _lp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         if os.environ.get('MPC_LIB_ALLOW_MISSING') == '1' and not hasattr(L, name):
@@ -307,7 +310,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
                     'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
-                    'mpc_backward_exits', 'mpc_project_rows']
+                    'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1506,6 +1509,53 @@ def backward_exits(row_off, ef_rows, Phi, phi, xs, pred_off, pred_idx, cell_off,
             'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': pt,
             'status': int(status[0]), 'steps': k, 'converged': bool(conv[0]), 'cells_per_step': per_step[:k + 1].copy(),
             'step_ms': step_ms[:max(max_steps, 0)].astype(numpy.float64), 'stats': stats}
+
+
+# status of mpc_forward_cells (include/mpcombi.h)
+FORWARD_DONE, FORWARD_EMPTY, FORWARD_ROWS, FORWARD_MAX_CELLS, FORWARD_MAX_ROWS_TOTAL = range(5)
+FORWARD_STATUS = ('DONE', 'EMPTY', 'ROWS', 'MAX_CELLS', 'MAX_ROWS_TOTAL')
+
+
+def forward_cells(row_off, ef_rows, Phi, phi, succ_off, succ_idx, cell_off, cell_rows, cell_region, cell_point, tol: float, max_steps: int,
+                  max_cells: int, max_rows_total: int, device: int = 0):
+    """The forward cells of a closed loop, every step in one call (include/mpcombi.h, mpc_forward_cells).  A dict: cell_off, cell_rows,
+    region, step, parent, wide (bool), point, G [cells, n_t, n_t], g [cells, n_t], status (FORWARD_*), steps, cells_per_step [steps + 1],
+    step_ms [max_steps] and stats (items, cells, empty, lps, pivots, wide, ms)."""
+    who = 'forward_cells'
+    off, ef = _merge_rows(who, row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    P = _f64(numpy.asarray(Phi, dtype=numpy.float64))
+    p = _f64(numpy.asarray(phi, dtype=numpy.float64))
+    if P.size != R * n_t * n_t or p.size != R * n_t:
+        raise MpcError(f'{who}: Phi must be [regions, n_t, n_t] and phi [regions, n_t]')
+    soff = numpy.ascontiguousarray(succ_off, dtype=numpy.int64).reshape(-1)
+    sidx = numpy.ascontiguousarray(succ_idx, dtype=numpy.int32).reshape(-1)
+    if len(soff) != R + 1 or (len(soff) and soff[-1] != len(sidx)):
+        raise MpcError(f'{who}: succ_off [regions + 1] must end at the length of succ_idx')
+    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
+    crow = _f64(numpy.asarray(cell_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
+    creg = numpy.ascontiguousarray(cell_region, dtype=numpy.int32).reshape(-1)
+    cpt = _f64(numpy.asarray(cell_point, dtype=numpy.float64)).reshape(-1, n_t)
+    if len(coff) != len(creg) + 1 or coff[0] != 0 or coff[-1] != len(crow) or len(cpt) != len(creg):
+        raise MpcError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one region and one point per cell')
+    max_steps, max_cells, max_rows_total = int(max_steps), int(max_cells), int(max_rows_total)
+    if max_cells < 0 or max_rows_total < 0:
+        raise MpcError(f'{who}: max_cells and max_rows_total must be >= 0')
+    # capacity, not contents: pages the library never writes are never touched
+    out_off, out_rows = numpy.empty(max_cells + 1, dtype=numpy.int64), numpy.empty((max_rows_total, n_t + 1))
+    reg, step, parent, wide = (numpy.empty(max_cells, dtype=numpy.int32) for _ in range(4))
+    point, cmap = numpy.empty((max_cells, n_t)), numpy.empty((max_cells, n_t, n_t + 1))
+    n, status, steps = numpy.zeros(1, dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32)
+    per_step = numpy.zeros(max(max_steps, 0) + 1, dtype=numpy.int64)
+    step_ms = numpy.zeros(max(max_steps, 1), dtype=numpy.float32)
+    stats = _geometry_call('mpc_forward_cells', ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'), int(device), n_t, R, off, ef, P, p, soff, sidx,
+                           len(creg), coff, crow, creg, cpt, float(tol), max_steps, max_cells, max_rows_total, n, out_off, out_rows, reg, step, parent,
+                           wide, point, cmap, status, steps, per_step, step_ms.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+    n, k = int(n[0]), int(steps[0])
+    return {'cell_off': out_off[:n + 1].copy(), 'cell_rows': out_rows[:int(out_off[n])].copy(), 'region': reg[:n].astype(numpy.int64),
+            'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': point[:n].copy(),
+            'G': cmap[:n, :, :n_t].copy(), 'g': cmap[:n, :, n_t].copy(), 'status': int(status[0]), 'steps': k,
+            'cells_per_step': per_step[:k + 1].copy(), 'step_ms': step_ms[:max(max_steps, 0)].astype(numpy.float64), 'stats': stats}
 
 
 class Locator:

@@ -27,6 +27,7 @@
 #include "reduce.hpp"
 #include "project.hpp"
 #include "invariant.hpp"
+#include "forward.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1788,6 +1789,212 @@ extern "C" int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions
     if (cell_point && nc > (size_t)n_cells0 && s.ok())
         s.chk(hipMemcpy(cell_point + (size_t)n_cells0 * n_t, d_cpt.as<double>() + (size_t)n_cells0 * n_t, (nc - (size_t)n_cells0) * n_t * 8,
                         hipMemcpyDeviceToHost));
+    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+    s.download(cnt, d_cnt, sizeof cnt);
+    if (const int rc = s.finish()) return rc;
+    if (stats) for (int i = 0; i < 6; ++i) stats[i] = (int64_t)cnt[i];
+    if (ms) *ms = total_ms;
+    deliver(code, step);
+    return MPC_OK;
+}
+
+// ---- forward cells of a closed loop (forward.hpp) ---------------------------------------------------------------------
+// The forward twin of mpc_backward_exits: the cell table (offsets, rows, points, maps) stays on the device and grows step by step; per
+// step the item list and the regions of the new cells go up, status and n_kept come down, the host scans the offsets.
+extern "C" int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                                 const double *phi, const int64_t *succ_off, const int32_t *succ_idx, int64_t n_cells0, const int64_t *cell_off0,
+                                 const double *cell_rows0, const int32_t *cell_region0, const double *cell_point0, double tol, int32_t max_steps,
+                                 int64_t max_cells, int64_t max_rows_total, int64_t *n_cells, int64_t *cell_off, double *cell_rows,
+                                 int32_t *cell_region, int32_t *cell_step, int32_t *cell_parent, int32_t *cell_wide, double *cell_point,
+                                 double *cell_map, int32_t *status, int32_t *steps, int64_t *cells_per_step, float *step_ms, int64_t *stats,
+                                 float *ms) {
+    const char *who = "mpc_forward_cells";
+    family_open(stats, 6, ms);
+    if (n_cells) *n_cells = 0;
+    if (steps) *steps = 0;
+    if (status) *status = MPC_FORWARD_DONE;
+    int m_reg = 1, m_cell = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
+    if (int rc = merge_check("mpc_forward_cells (cells)", n_t, n_cells0, cell_off0, cell_rows0, &m_cell)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, false, nullptr)) return rc;
+    if (max_steps < 0) return bad(who, "max_steps must be >= 0");
+    if (max_cells < 0 || max_cells > 0x7fffffffll || max_rows_total < 0) return bad(who, "max_cells must lie in 0..2^31 - 1 and max_rows_total be >= 0");
+    if (!n_cells || !status || !steps) return bad(who, "missing output (n_cells, status or steps)");
+    if (n_regions > 0) {
+        if (!succ_off || succ_off[0] != 0) return bad(who, "succ_off must start at 0");
+        for (int64_t i = 0; i < n_regions; ++i)
+            if (succ_off[i + 1] < succ_off[i]) return bad(who, "succ_off must not decrease");
+        if (succ_off[n_regions] > 0 && !succ_idx) return bad(who, "missing succ_idx");
+        for (int64_t k = 0; k < succ_off[n_regions]; ++k)
+            if (succ_idx[k] < 0 || succ_idx[k] >= n_regions) return bad(who, "a successor list names a region out of range");
+    }
+    const int64_t rows0 = n_cells0 > 0 ? cell_off0[n_cells0] : 0;
+    if (n_cells0 > 0) {
+        if (!cell_region0 || !cell_point0) return bad(who, "missing cell_region0 or cell_point0");
+        for (int64_t c = 0; c < n_cells0; ++c)
+            if (cell_region0[c] < 0 || cell_region0[c] >= n_regions) return bad(who, "a cell names a region out of range");
+        if (int rc = check_finite(who, "cell_point0", cell_point0, n_cells0 * n_t)) return rc;
+        if (n_cells0 > max_cells || rows0 > max_rows_total) return bad(who, "the cells of step 0 exceed max_cells or max_rows_total");
+        if (!cell_off || !cell_rows || !cell_region || !cell_step || !cell_parent || !cell_wide || !cell_point || !cell_map)
+            return bad(who, "missing output array");
+    }
+    // the host's side of the cell table: everything but rows, points and maps
+    std::vector<int64_t> off(1, 0);
+    std::vector<int32_t> reg, stp, par, wid;
+    if (n_cells0 > 0) {
+        off.assign(cell_off0, cell_off0 + n_cells0 + 1);
+        reg.assign(cell_region0, cell_region0 + n_cells0);
+        stp.assign((size_t)n_cells0, 0);
+        par.assign((size_t)n_cells0, -1);
+        wid.assign((size_t)n_cells0, 0);
+    }
+    const size_t nr = (size_t)n_regions, w = (size_t)n_t + 1, map_doubles = (size_t)n_t * w;
+    // step 0: theta_0 = I theta_0 + 0
+    std::vector<double> map0((size_t)n_cells0 * map_doubles, 0.0);
+    for (size_t c = 0; c < (size_t)n_cells0; ++c)
+        for (int t = 0; t < n_t; ++t) map0[c * map_doubles + (size_t)t * w + t] = 1.0;
+    auto deliver = [&](int code, int n_steps) {
+        const size_t nc = reg.size();
+        *n_cells = (int64_t)nc;
+        *status = code;
+        *steps = n_steps;
+        if (cell_off) std::memcpy(cell_off, off.data(), (nc + 1) * 8);
+        if (nc) {
+            std::memcpy(cell_region, reg.data(), nc * 4);
+            std::memcpy(cell_step, stp.data(), nc * 4);
+            std::memcpy(cell_parent, par.data(), nc * 4);
+            std::memcpy(cell_wide, wid.data(), nc * 4);
+        }
+    };
+    if (cells_per_step) {
+        for (int k = 0; k <= max_steps; ++k) cells_per_step[k] = 0;
+        cells_per_step[0] = n_cells0;
+    }
+    if (step_ms) for (int k = 0; k < max_steps; ++k) step_ms[k] = 0.0f;
+    if (n_cells0 == 0 || max_steps == 0) {
+        deliver(n_cells0 == 0 ? MPC_FORWARD_EMPTY : MPC_FORWARD_DONE, 0);
+        if (n_cells0 > 0) {
+            std::memcpy(cell_rows, cell_rows0, (size_t)rows0 * w * 8);
+            std::memcpy(cell_point, cell_point0, (size_t)n_cells0 * n_t * 8);
+            std::memcpy(cell_map, map0.data(), map0.size() * 8);
+        }
+        return MPC_OK;
+    }
+    if (int rc = select_device(nullptr, device)) return rc;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8);
+    DevBuf &d_coff = s.upload(off.data(), off.size() * 8), &d_crow = s.upload(cell_rows0, (size_t)rows0 * w * 8);
+    DevBuf &d_cpt = s.upload(cell_point0, (size_t)n_cells0 * n_t * 8), &d_cmap = s.upload(map0.data(), map0.size() * 8);
+    DevBuf &d_creg = s.upload(reg.data(), reg.size() * 4), &d_cnt = family_counters(s, 6);
+    DevBuf &d_next = s.buf(), &d_ir = s.buf(), &d_ic = s.buf(), &d_ci = s.buf(), &d_st = s.buf(), &d_nk = s.buf(), &d_kept = s.buf(), &d_pt = s.buf();
+    auto grow = [&](DevBuf &b, size_t bytes) { if (s.ok()) s.chk(b.ensure(bytes, s.st, true)); };   // keeps what the table holds
+    std::vector<int32_t> item_region, item_cell, st, nk, cell_item;
+    int64_t lo = 0, hi = n_cells0;      // the cells of the last completed step
+    int step = 0, code = MPC_FORWARD_DONE;
+    float total_ms = 0.0f;
+    while (step < max_steps) {
+        // the items of step + 1: by parent cell, then as the successor list is
+        item_region.clear();
+        item_cell.clear();
+        int item_rows = 2;
+        bool too_many = false;
+        for (int64_t c = lo; c < hi && !too_many; ++c) {
+            const int64_t i = reg[(size_t)c], m_q = off[(size_t)c + 1] - off[(size_t)c];
+            for (int64_t k = succ_off[i]; k < succ_off[i + 1]; ++k) {
+                const int32_t j = succ_idx[k];
+                item_region.push_back(j);
+                item_cell.push_back((int32_t)c);
+                item_rows = std::max<int>(item_rows, (int)(row_off[j + 1] - row_off[j] + m_q));
+            }
+            too_many = item_region.size() > 0x7fffffffull;
+        }
+        if (item_region.empty()) { code = MPC_FORWARD_EMPTY; break; }          // no region follows the last cells: every trajectory has left
+        if (too_many) { code = MPC_FORWARD_MAX_CELLS; break; }
+        if (item_rows > RD_MAX_ROWS) { code = MPC_FORWARD_ROWS; break; }
+        const size_t ni = item_region.size(), np = (size_t)(hi - lo);
+        const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static arrays add 2,528)
+        float t_maps = 0.0f, t_cells = 0.0f, t_emit = 0.0f;
+        s.upload(d_ir, item_region.data(), ni * 4);
+        s.upload(d_ic, item_cell.data(), ni * 4);
+        s.ensure(d_next, np * map_doubles * 8);
+        family_launch(s, k_fwd_maps, (int64_t)np, 0, (int)n_t, (long long)np, (long long)lo, d_creg.as<int32_t>(), d_Phi.as<double>(),
+                      d_phi.as<double>(), d_cmap.as<double>(), d_next.as<double>());
+        if (s.ok()) s.chk(hipEventSynchronize(s.e1));
+        s.elapsed(&t_maps);
+        s.ensure(d_st, ni * 4); s.ensure(d_nk, ni * 4); s.ensure(d_kept, ni * RD_WORDS * 8); s.ensure(d_pt, ni * n_t * 8);
+        FwdCellArgs a{};
+        a.nt = n_t; a.m_max = item_rows; a.n_items = (long long)ni; a.first = (long long)lo;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = d_coff.as<long long>(); a.cell_ef = d_crow.as<double>();
+        a.next = d_next.as<double>(); a.cell_point = d_cpt.as<double>();
+        a.item_region = d_ir.as<int32_t>(); a.item_cell = d_ic.as<int32_t>(); a.tol = tol;
+        a.status = d_st.as<int32_t>(); a.n_kept = d_nk.as<int32_t>(); a.kept = d_kept.as<unsigned long long>();
+        a.point = d_pt.as<double>(); a.counters = d_cnt.as<unsigned long long>();
+        family_launch(s, k_fwd_cells, (int64_t)ni, lds, a);
+        st.resize(ni); nk.resize(ni);
+        s.download(st.data(), d_st, ni * 4);        // blocking copies on the null stream: the launch has ended
+        s.download(nk.data(), d_nk, ni * 4);
+        s.elapsed(&t_cells);
+        if (!s.ok()) break;
+        // the scan: the cells of this step in item order
+        cell_item.clear();
+        int64_t new_rows = 0;
+        bool fat = false;
+        for (size_t q = 0; q < ni; ++q) {
+            if (st[q] != PC_CELL && st[q] != PC_CELL_WIDE) continue;
+            fat = fat || nk[q] < 1 || nk[q] > OV_MAX_ROWS;
+            cell_item.push_back((int32_t)q);
+            new_rows += nk[q];
+        }
+        const size_t nn = cell_item.size(), nc = reg.size();
+        bool refused = true;
+        if (nn && fat) code = MPC_FORWARD_ROWS;
+        else if (nn && (int64_t)(nc + nn) > max_cells) code = MPC_FORWARD_MAX_CELLS;
+        else if (nn && off.back() + new_rows > max_rows_total) code = MPC_FORWARD_MAX_ROWS_TOTAL;
+        else refused = false;
+        if (nn && !refused) {
+            for (size_t c = 0; c < nn; ++c) {
+                const size_t q = (size_t)cell_item[c], parent = (size_t)item_cell[q];
+                off.push_back(off.back() + nk[q]);
+                reg.push_back(item_region[q]);
+                stp.push_back(step + 1);
+                par.push_back((int32_t)parent);
+                wid.push_back(st[q] == PC_CELL_WIDE || wid[parent] ? 1 : 0);
+            }
+            grow(d_coff, (nc + nn + 1) * 8);
+            grow(d_crow, (size_t)off.back() * w * 8);
+            grow(d_cpt, (nc + nn) * n_t * 8);
+            grow(d_cmap, (nc + nn) * map_doubles * 8);
+            grow(d_creg, (nc + nn) * 4);
+            if (s.ok()) s.chk(hipMemcpy(d_coff.as<int64_t>() + nc + 1, off.data() + nc + 1, nn * 8, hipMemcpyHostToDevice));
+            if (s.ok()) s.chk(hipMemcpy(d_creg.as<int32_t>() + nc, reg.data() + nc, nn * 4, hipMemcpyHostToDevice));
+            s.upload(d_ci, cell_item.data(), nn * 4);
+            FwdEmitArgs e{};
+            e.nt = n_t; e.m_max = item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc; e.first = (long long)lo;
+            e.row_off = d.off.as<long long>(); e.cell_off = d_coff.as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = d_crow.as<double>();
+            e.next = d_next.as<double>(); e.cell_map = d_cmap.as<double>(); e.item_region = d_ir.as<int32_t>(); e.item_cell = d_ic.as<int32_t>();
+            e.cell_item = d_ci.as<int32_t>(); e.kept = d_kept.as<unsigned long long>(); e.point = d_pt.as<double>();
+            e.cell_point = d_cpt.as<double>(); e.tol = tol;
+            family_launch(s, k_fwd_emit, (int64_t)nn, lds, e);
+            if (s.ok()) s.chk(hipEventSynchronize(s.e1));
+            s.elapsed(&t_emit);
+            if (!s.ok()) break;
+        }
+        if (step_ms) step_ms[step] = t_maps + t_cells + t_emit;
+        total_ms += t_maps + t_cells + t_emit;
+        if (refused) break;
+        if (!nn) { code = MPC_FORWARD_EMPTY; break; }                         // a step without a cell: every trajectory has left
+        ++step;
+        if (cells_per_step) cells_per_step[step] = (int64_t)nn;
+        lo = hi;
+        hi += (int64_t)nn;
+    }
+    if (!s.ok()) return s.finish();
+    const size_t nc = reg.size();
+    s.download(cell_rows, d_crow, (size_t)off.back() * w * 8);
+    s.download(cell_point, d_cpt, nc * n_t * 8);
+    s.download(cell_map, d_cmap, nc * map_doubles * 8);
     unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
     s.download(cnt, d_cnt, sizeof cnt);
     if (const int rc = s.finish()) return rc;

@@ -356,6 +356,19 @@ class Solution:
         return invariant_set(self, A, B, inputs, c=c, tol=tol, graph=graph, exits=exits, max_steps=max_steps, max_cells=max_cells,
                              reduce_rows=reduce_rows, device=device)
 
+    def reach_cells(self, A, B, inputs, c=None, initial=None, steps: int = 8, tol: float = 1e-8, graph=None, max_cells: int = 1 << 20,
+                    max_rows_total=None, device: int = 0):
+        """Where the states of ``initial`` (a Polytope, a list of them, or None: the regions themselves) are after 1 .. ``steps`` steps of
+        the loop under the plant theta+ = A theta + B u + c with this controller's law u = x*(theta)[inputs]: a reach.ForwardCells, cells
+        of INITIAL states of radius above tol, each with the region it is in at its step, the composed map theta_k = G theta_0 + g and
+        its parent (cells_at, itinerary, locate, state_at, volumes, image_vertices, images, entering: the safety and target query).
+        The successors come from ``graph``, the transition_graph of the same arguments (built when None); every step runs on the
+        device inside one library call.  No map is inverted: singular and contracting loops are followed like any other.  Refusals as
+        for transition_graph.  See reach.py and DESIGN §3.25."""
+        from .reach import reach_cells
+        return reach_cells(self, A, B, inputs, c=c, initial=initial, steps=steps, tol=tol, graph=graph, max_cells=max_cells,
+                           max_rows_total=max_rows_total, device=device)
+
     def simulate(self, theta0, steps: int, A, B, inputs, c=None, disturbance=None, seed: int = 0, stop_tol=None, locate: str = 'auto',
                  record: str = 'full', inclusive: bool = False, device: int = 0):
         """This explicit controller in closed loop with the plant theta+ = A theta + B u + c + w, u = x*(theta)[inputs], for many initial

@@ -1,6 +1,7 @@
-// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce, project and backward-exit calls (mpc_merge_regions,
-// mpc_merge_pairs, mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split, mpc_reduce_rows,
-// mpc_project_rows, mpc_backward_exits) as a stand-alone host program for a sanitizer build:
+// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce, project, backward-exit and forward-cell calls
+// (mpc_merge_regions, mpc_merge_pairs, mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split,
+// mpc_reduce_rows, mpc_project_rows, mpc_backward_exits, mpc_forward_cells) as a stand-alone host program for a sanitizer build (DESIGN §3.14,
+// §3.19 to §3.25):
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/geometry_refusals.hip -o geometry_refusals
 // It includes geometry.hip itself and stands in for the pools of mpcombi_hip.hip, which a refusal never reaches: every call below must
 // come back MPC_ERR_INVALID with a message before a device is selected (an empty batch: MPC_OK), so the program needs no GPU and
@@ -481,6 +482,99 @@ static void backward_cases() {
                                                                  nullptr), MPC_OK);
 }
 
+// mpc_forward_cells
+static void forward_cases() {
+    const int nt = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    const int64_t cap_cells = 4, cap_rows = 16;
+    int64_t n_cells = -1, stats[6], per_step[4];
+    VL out_off(cap_cells + 1);
+    VD out_rows(cap_rows * (nt + 1)), out_point(cap_cells * nt), out_map(cap_cells * nt * (nt + 1));
+    VI reg(cap_cells), stp(cap_cells), par(cap_cells), wid(cap_cells);
+    int32_t status = -1, steps = -1;
+    float step_ms[3], ms = 0.0f;
+    struct Args { int n_t; VL off; VD ef, Phi, phi; VL soff; VI sidx; VL coff; VD cef; VI creg; VD cpt; double tol; int max_steps; int64_t max_cells, max_rows; };
+    const Args good{nt, {0, 4, 8}, ef, {1, 0, 0, 1, 0.5, 0, 0, 0.5}, {0, 0, 0.1, 0.1}, {0, 1, 2}, {1, 0}, {0, 4}, sq, {0}, {0.5, 0.5}, 1e-8, 3, cap_cells, cap_rows};
+    auto run = [&](const Args &g, int64_t n_cells0 = -2) {
+        return mpc_forward_cells(0, g.n_t, (int64_t)g.off.size() - 1, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(),
+                                 n_cells0 == -2 ? (int64_t)g.creg.size() : n_cells0, g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), g.tol,
+                                 g.max_steps, g.max_cells, g.max_rows, &n_cells, out_off.data(), out_rows.data(), reg.data(), stp.data(), par.data(),
+                                 wid.data(), out_point.data(), out_map.data(), &status, &steps, per_step, step_ms, stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;
+    for (int r = 0; r < 65; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    expect("n_t = 0", run(with([](Args &g) { g.n_t = 0; })));
+    expect("n_t = 17", run(with([](Args &g) { g.n_t = 17; })));
+    expect("tol < 0", run(with([](Args &g) { g.tol = -1.0; })));
+    expect("tol NaN", run(with([&](Args &g) { g.tol = nan; })));
+    expect("tol inf", run(with([](Args &g) { g.tol = INFINITY; })));
+    expect("max_steps < 0", run(with([](Args &g) { g.max_steps = -1; })));
+    expect("max_cells < 0", run(with([](Args &g) { g.max_cells = -1; })));
+    expect("max_rows_total < 0", run(with([](Args &g) { g.max_rows = -1; })));
+    expect("n_cells0 < 0", run(good, -1));
+    expect("n_cells0 = 2^31", run(good, 0x80000000ll));
+    expect("a region without rows", run(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("row_off[0] != 0", run(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("a region of 260 rows", run(with([&](Args &g) { g.off = {0, 260}; g.ef = big; g.Phi.resize(4); g.phi.resize(2); g.soff = {0, 0}; })));
+    expect("a cell without rows", run(with([](Args &g) { g.coff = {0, 0}; })));
+    expect("a cell of 260 rows", run(with([&](Args &g) { g.coff = {0, 260}; g.cef = big; g.max_rows = 512; })));
+    expect("cell_off[0] != 0", run(with([](Args &g) { g.coff = {1, 4}; })));
+    expect("a non-finite region row", run(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("a region row that is not unit", run(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("a non-finite cell row", run(with([](Args &g) { g.cef[3] = INFINITY; })));
+    expect("a cell row that is not unit", run(with([](Args &g) { g.cef[1] = 0.5; })));
+    expect("Phi NaN", run(with([&](Args &g) { g.Phi[7] = nan; })));
+    expect("phi inf", run(with([](Args &g) { g.phi[0] = -INFINITY; })));
+    expect("cell point NaN", run(with([&](Args &g) { g.cpt[1] = nan; })));
+    expect("succ_off[0] != 0", run(with([](Args &g) { g.soff = {1, 1, 2}; })));
+    expect("succ_off decreases", run(with([](Args &g) { g.soff = {0, 2, 1}; })));
+    expect("successor index out of range", run(with([](Args &g) { g.sidx = {1, 2}; })));
+    expect("negative successor index", run(with([](Args &g) { g.sidx = {-1, 0}; })));
+    expect("cell region out of range", run(with([](Args &g) { g.creg = {2}; })));
+    expect("negative cell region", run(with([](Args &g) { g.creg = {-1}; })));
+    expect("step 0 above max_cells", run(with([](Args &g) { g.max_cells = 0; })));
+    expect("step 0 above max_rows_total", run(with([](Args &g) { g.max_rows = 3; })));
+    const Args &g = good;
+    auto raw = [&](const int64_t *off, const double *rows, const double *Phi, const double *phi, const int64_t *soff, const int32_t *sidx, const int64_t *coff,
+                   const double *cef, const int32_t *creg, const double *cpt, int64_t *n, int64_t *ooff, double *orows, int32_t *oreg, double *opt, double *omap,
+                   int32_t *st) {
+        return mpc_forward_cells(0, nt, 2, off, rows, Phi, phi, soff, sidx, 1, coff, cef, creg, cpt, 1e-8, 3, cap_cells, cap_rows, n, ooff, orows, oreg,
+                                 stp.data(), par.data(), wid.data(), opt, omap, st, &steps, nullptr, nullptr, nullptr, nullptr);
+    };
+    expect("missing row_off", raw(nullptr, g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing ef_rows", raw(g.off.data(), nullptr, g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing Phi", raw(g.off.data(), g.ef.data(), nullptr, g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing phi", raw(g.off.data(), g.ef.data(), g.Phi.data(), nullptr, g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing succ_off", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), nullptr, g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing succ_idx", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), nullptr, g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_off0", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), nullptr, g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_rows0", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), nullptr, g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_region0", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), nullptr, g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_point0", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), nullptr, &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing n_cells", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), nullptr, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing status", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), out_map.data(), nullptr));
+    expect("missing cell_off", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, nullptr, out_rows.data(), reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_rows", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), nullptr, reg.data(), out_point.data(), out_map.data(), &status));
+    expect("missing cell_region", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), nullptr, out_point.data(), out_map.data(), &status));
+    expect("missing cell_point", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), nullptr, out_map.data(), &status));
+    expect("missing cell_map", raw(g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), g.coff.data(), g.cef.data(), g.creg.data(), g.cpt.data(), &n_cells, out_off.data(), out_rows.data(), reg.data(), out_point.data(), nullptr, &status));
+    // the empty calls: MPC_OK without a launch, step 0 returned with the identity maps
+    expect("max_steps = 0 is MPC_OK without a launch", run(with([](Args &a) { a.max_steps = 0; })), MPC_OK);
+    if (n_cells != 1 || status != MPC_FORWARD_DONE || steps != 0 || out_off[1] != 4 || out_rows[11] != sq[11] || reg[0] != 0 || par[0] != -1 ||
+        per_step[0] != 1 || out_point[0] != 0.5 || out_map[0] != 1.0 || out_map[1] != 0.0 || out_map[2] != 0.0 || out_map[4] != 1.0) {
+        std::printf("max_steps = 0: step 0 was not returned\n"); ++n_bad;
+    }
+    expect("no cells is MPC_OK without a launch", run(with([](Args &a) { a.coff = {0}; a.cef.clear(); a.creg.clear(); a.cpt.clear(); })), MPC_OK);
+    if (n_cells != 0 || status != MPC_FORWARD_EMPTY || steps != 0 || out_off[0] != 0) { std::printf("no cells: not EMPTY\n"); ++n_bad; }
+    expect("no cells, no cell arrays, no outputs", mpc_forward_cells(0, nt, 2, g.off.data(), g.ef.data(), g.Phi.data(), g.phi.data(), g.soff.data(), g.sidx.data(), 0,
+                                                                 nullptr, nullptr, nullptr, nullptr, 1e-8, 3, 0, 0, &n_cells, nullptr, nullptr, nullptr, nullptr,
+                                                                 nullptr, nullptr, nullptr, nullptr, &status, &steps, nullptr, nullptr, nullptr, nullptr), MPC_OK);
+}
+
 int main() {
     merge_cases();
     overlap_cases();
@@ -489,6 +583,7 @@ int main() {
     reduce_cases();
     project_cases();
     backward_cases();
+    forward_cases();
     std::printf("%d unexpected\n", n_bad);
     return n_bad ? 1 : 0;
 }
