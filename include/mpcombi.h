@@ -90,7 +90,9 @@ typedef struct {
     int64_t n_x_cached;        /* (x,theta) solves that started from the parent's dictionary cached in HBM */
     /* HIP-event time of single launches of this level (0 when the kernel did not run): k_theta2, the main k_x2 launch
      * (over n_x_items candidates), k_region2 (over n_opt candidates); region_side_stream = 1: that k_region2 launch ran on the
-     * handle's side stream UNDER the (x,theta) stage (its time is not on the level's critical path), 0: in line */
+     * handle's side stream UNDER the (x,theta) stage (its time is not on the level's critical path), 0: in line; mpc_solve_start's
+     * loop also reports 2: the launch of this small level ran beside the level AFTER it (the level was published one level later),
+     * 3: such a launch missed (mpc_set_region_overlap) and these are the figures of the level's repeat in line */
     float ms_theta, ms_x, ms_region2, region_side_stream;
     int64_t n_x_items, n_opt;
     int64_t dict_read_bytes;   /* bytes of one cached dictionary record as k_x2 reads it (0: no cache on this level)   */
@@ -235,7 +237,12 @@ int mpc_level_batch_wait(void *token, mpc_level_stats *stats, int32_t *n_batched
  * An overlapped launch reserves spare record slots for candidates that turn out optimal only after it (re-solved doubtful ones);
  * should a level ever find more of them than it reserved, mpc_level_run / mpc_level_wait return MPC_ERR_CAPACITY -- no
  * candidate is demoted -- and the caller repeats the solve with on = 0, where every optimal candidate is known at launch.
- * (Reference: full_process never loses a region, mp_solvers/mpqp_parrallel_combinatorial.py:52-61.) */
+ * (Reference: full_process never loses a region, mp_solvers/mpqp_parrallel_combinatorial.py:52-61.)
+ * The same switch governs the other overlap of a region stage: inside mpc_solve_start's loop the region stage of a SMALL level runs beside
+ * the kernels of the level after it (its children are generated before its regions exist; a region that turns out lower-dimensional
+ * abandons the pass once and switches this off for the handle).  on = 0: neither overlap; 1 (default): both; 2: large levels as with 1,
+ * small levels build their regions in line (A/B, tests); 3 (tests): as 1, and the first small level closed that way on this handle
+ * reports a miss. */
 int mpc_set_region_overlap(mpc_handle *h, int32_t on);
 /* mpc_set_timing(h, 0): the levels of this handle run WITHOUT the HIP-event records around their stages and heavy kernels -- about
  * fourteen records per large level, four per small one, each a marker the queue stops at (measured, one MI355X: 0.16 ms of a 4.9 ms

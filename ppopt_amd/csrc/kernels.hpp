@@ -984,8 +984,13 @@ MPC_GLOBAL void MPC_LB(1024) k_scan_small(const int32_t *__restrict__ in, int32_
 // keep_lowdim: the serial driver's rule (mp_solvers/mpqp_combinatorial.py:44-61, also mpqp_parallel_combinatorial_exp.py:38-52) --
 // every feasible set is expanded, also one that is optimal with a lower-dimensional region; the parallel driver prunes such
 // a set together with its supersets (mpqp_parrallel_combinatorial.py:57-59)
+// The children-count kernels take both rules in one word: bit 0 = keep_lowdim, bit 1 (EXPAND_PENDING) = an optimal candidate whose region
+// is not built yet (ST_OPT_PENDING) expands like one with a region -- a small level whose region stage runs beside the next level
+// (mpcombi_hip.hip, RegionDefer) generates its children before the regions exist.
+constexpr int EXPAND_LOWDIM = 1, EXPAND_PENDING = 2;
 __device__ __forceinline__ bool expands(int st, int keep_lowdim = 0) {
-    return st == ST_FEASIBLE || st == ST_REGION || st == ST_SINGULAR || st == ST_LP_LIMIT || (keep_lowdim && st == ST_OPT_NO_REGION);
+    return st == ST_FEASIBLE || st == ST_REGION || st == ST_SINGULAR || st == ST_LP_LIMIT || ((keep_lowdim & EXPAND_LOWDIM) && st == ST_OPT_NO_REGION) ||
+           ((keep_lowdim & EXPAND_PENDING) && st == ST_OPT_PENDING);
 }
 
 // Active sets as bit masks of MW 64-bit words (MW = 2: n_c <= 128, MW = 4: n_c <= 256; mpc_mask_words).

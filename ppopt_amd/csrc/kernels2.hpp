@@ -2201,7 +2201,8 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
         if (retry) { st = ST_RETRY; if (lane == 0 && is_last) atomicAdd(&ctr->n_rretry, 1u); }
         if (lane == 0 && is_last) {
             hi[0] = st; hi[1] = c; hi[2] = nE; hi[3] = n_om; hi[4] = n_la; hi[5] = n_re; hi[6] = e_off; hi[7] = reason;
-            status[c] = (uint8_t)(retry ? ST_RRETRY : st);   // distinct from the verdict stages' ST_RETRY, which may be pending on other candidates
+            // (status == nullptr: a launch that runs beside the NEXT level, whose status array this no longer is -- the slot carries the verdict)
+            if (status) status[c] = (uint8_t)(retry ? ST_RRETRY : st);   // distinct from the verdict stages' ST_RETRY, which may be pending on other candidates
         }
         if (rs.count && is_last) {
             // every store of this slot's record is released to system scope before the slot is counted; the wavefront that
@@ -2226,6 +2227,29 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
         atomicAdd(&ctr->r_box, (unsigned long long)rc_box);
         atomicMax(&ctr->r2_t1, (unsigned long long)wall_clock64());
     }
+}
+
+// Behind a k_region2 launch that runs beside the NEXT level (mpcombi_hip.hip, RegionDefer), on that launch's stream: what the host needs to
+// close the level goes to page-locked memory -- the launch's private counters (n_ctr words), then the verdicts of its slots counted by
+// head_i[slot][0] (eight words; [ST_RETRY] = candidates the kernel gave up on), then the number of slots.  One workgroup: a small level.
+MPC_GLOBAL void MPC_LB(256) k_defer_publish(const int32_t *__restrict__ head_i, int fi, const int32_t *__restrict__ n_opt_dev,
+                                            const unsigned int *ctr_words, int n_ctr, unsigned int *dst) {
+    __shared__ unsigned int hist[8];
+    if (threadIdx.x < 8) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const int n_opt = *n_opt_dev;
+    for (int w = threadIdx.x; w < n_opt; w += 256) atomicAdd(&hist[head_i[(size_t)w * fi] & 7], 1u);
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_ctr; i += 256) dst[i] = load_word_agent(ctr_words + i);
+    if (threadIdx.x < 8) dst[n_ctr + threadIdx.x] = hist[threadIdx.x];
+    if (threadIdx.x == 0) dst[n_ctr + 8] = (unsigned int)n_opt;
+}
+// ... and, when no next level followed (the status array is still this level's): the verdicts into status[], as the launch in line leaves them
+MPC_GLOBAL void MPC_LB(256) k_defer_status(const int32_t *__restrict__ head_i, int fi, int n_opt, uint8_t *__restrict__ status) {
+    const int w = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (w >= n_opt) return;
+    const int32_t *hi = head_i + (size_t)w * fi;
+    status[hi[1]] = (uint8_t)(hi[0] == ST_RETRY ? ST_RRETRY : hi[0]);
 }
 
 }  // namespace mpc

@@ -240,6 +240,34 @@ struct mpc_handle {
     DevBuf pruned_b, pruned_head;
     hipEvent_t ev_rjoin = nullptr, ev_rgo = nullptr;
     bool r3_dirty = false;           // a region kernel launched on stream3 has not been joined by a completed level yet
+    // ---- the region stage of a small level beside the NEXT level's kernels (mpc_solve_start's loop only) ----------------------
+    // The region records of a level are output only: the next level needs them for nothing but the verdict "optimal, lower-dimensional"
+    // (pruned with its supersets), which no bounded full-dimensional program produces.  A small level therefore generates its children
+    // before its regions exist (k_children_count, EXPAND_PENDING), k_region2 runs on stream3 from the theta-stage partition on, and the
+    // loop closes the level -- counters, verdicts, record fetch, publication -- behind the NEXT level's closing synchronisation.  A verdict
+    // that would not have expanded is a miss: the solve restarts from the root with the deferral switched off for good on this handle.
+    // Whatever the launch reads or writes and the next level would overwrite lives in the set's own buffers, swapped with the handle's
+    // for the duration of the level (two sets by parity of depth: the next level's launch is queued before this one is closed).
+    struct RegionDefer {
+        DevBuf kkt_code, kkt_L, part_lists, headd, headi, epool, kept_g, done_g;
+        DevBuf dcnt;                 // the level's 32 list lengths (k_region2 reads [6] when each workgroup starts), behind them the launch's own LevelCounters
+        hipEvent_t ev_go = nullptr, ev_done = nullptr;   // recorded behind the theta-stage partition (main stream) / behind the launch's publish (stream3)
+        bool pending = false;        // launched and not closed
+        bool joined = false;         // the next level's children stage (it overwrites the frontier the launch reads) waits for ev_done
+        int depth = -1, k = 0, fd = 0, fi = 0, keep_lowdim = 0;
+        long long n_opt = 0;
+        std::vector<DevBuf *> buffers() { return {&kkt_code, &kkt_L, &part_lists, &headd, &headi, &epool, &kept_g, &done_g, &dcnt}; }
+    } rdefer[2];
+    int defer_mode = 1;              // mpc_set_region_overlap: 0 never, 1 where a level allows it, 2 (tests): ... and the first close on this handle reports a miss
+    bool defer_off = false;          // a deferred region missed on this handle: never again (as no_small_fuse for doubtful candidates)
+    bool defer_miss_forced = false;   // (what a level did is in its statistics: mpc_level_stats::region_side_stream 2 / 3)
+    static constexpr size_t DEFER_DCNT_BYTES = 32 * sizeof(int32_t) + sizeof(LevelCounters);
+    static constexpr int DEFER_PUB_WORDS = (int)(sizeof(LevelCounters) / 4) + 9;   // k_defer_publish: counters, eight verdict counts, the slots
+    // where set i's k_defer_publish writes, in the pinned counter block (cnt_host() below: the level's own words end before byte 1024)
+    static_assert(64 + sizeof(LevelCounters) + 32 * 4 <= 1024 && DEFER_PUB_WORDS * 4 <= 512 && 1024 + 2 * 512 <= 4096, "the pinned block holds both sets' publishes");
+    const unsigned int *defer_pub_host(int i) const { return reinterpret_cast<const unsigned int *>(reinterpret_cast<const char *>(tot_host) + 1024 + 512 * i); }
+    unsigned int *defer_pub_dev(int i) const { return reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(tot_dev) + 1024 + 512 * i); }
+    bool defer_pending() const { return rdefer[0].pending || rdefer[1].pending; }
     bool theta_open = false;         // the parameter set is open in some direction (or the program has equality rows only): the reference's
                                      // optimality LP can be unbounded -> k_recession behind every verdict stage, no overlapped region launch,
                                      // no level without host round trips, no shared launches
@@ -429,18 +457,22 @@ void lu_solve_host(const std::vector<double> &LU, const std::vector<int> &perm, 
 // the buffers a level (re)sizes by its number of candidates: what they outgrow is parked (DevBuf::parked) and given back to the pool by
 // graveyard_flush, which the level paths call behind their closing synchronisation (all streams of the handle have been joined by then)
 static std::vector<DevBuf *> level_buffers(mpc_handle *h) {
-    return {&h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list, &h->childmask, &h->count, &h->offset, &h->recd, &h->reci,
+    std::vector<DevBuf *> v = {&h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list, &h->childmask, &h->count, &h->offset, &h->recd, &h->reci,
             &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list,
             &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
             &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next};
+    for (auto &d : h->rdefer) for (DevBuf *b : d.buffers()) v.push_back(b);
+    return v;
 }
 // the handle's three side streams and its events without timing, in the order sync_objects (create.hpp) takes them from the pools and
 // mpc_destroy returns them
 static std::vector<hipStream_t *> side_streams(mpc_handle *h) { return {&h->stream2, &h->stream3, &h->stream4}; }
 static std::vector<hipEvent_t *> untimed_events(mpc_handle *h) {
-    return {&h->ev_hi, &h->ev_fork, &h->ev_join, &h->ev_xfork, &h->ev_part, &h->ev_xjoin, &h->ev_x1go, &h->ev_x1done, &h->ev_rjoin, &h->ev_rgo};
+    return {&h->ev_hi, &h->ev_fork, &h->ev_join, &h->ev_xfork, &h->ev_part, &h->ev_xjoin, &h->ev_x1go, &h->ev_x1done, &h->ev_rjoin, &h->ev_rgo,
+            &h->rdefer[0].ev_go, &h->rdefer[0].ev_done, &h->rdefer[1].ev_go, &h->rdefer[1].ev_done};
 }
 static void graveyard_flush(mpc_handle *h) {
+    if (h->defer_pending()) return;   // a region launch beside the next level may still read a block its level has outgrown: kept until a flush behind its close
     for (auto &b : h->parked_blocks) dev_pool_give(b.first, b.second);
     h->parked_blocks.clear();
 }
@@ -485,6 +517,7 @@ int mpc_create(const mpc_problem *p, int32_t device, void *stream, mpc_handle **
     // blocks and pinned block to the pools (a caller that creates one handle per binary fixation must not leak on OOM)
     mpc_handle *h = new mpc_handle();
     for (DevBuf *b : level_buffers(h)) b->parked = &h->parked_blocks;
+    h->dcnt.parked = &h->parked_blocks;   // (swapped with a RegionDefer set's for the duration of a deferring level)
     const int rc_fill = create_fill(p, device, stream, h);
     if (rc_fill != MPC_OK) { (void)mpc_destroy(h); return rc_fill; }
     *out = h;
@@ -531,6 +564,7 @@ int mpc_destroy(mpc_handle *h) {
     for (DevBuf *b : {&h->blocks, &h->iblocks, &h->frontier, &h->children, &h->status, &h->pruned, &h->flag, &h->pos, &h->opt_list,
                       &h->childmask, &h->count, &h->offset, &h->recd, &h->reci, &h->ctr, &h->pruned_b, &h->pruned_head, &h->scratch, &h->sums, &h->retry_list, &h->pf_dev, &h->pr2_dev, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->theta_blocks, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list, &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
                       &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next, &h->dcnt}) b->release();
+    for (auto &d : h->rdefer) for (DevBuf *b : d.buffers()) b->release();
     if (h->tot_host) { (void)host_pool_give(h->tot_host); h->tot_host = h->tot_dev = nullptr; }
     for (HostBuf *b : {&h->st_list, &h->st_status, &h->st_hd, &h->st_hi, &h->st_pool, &h->st_fxd, &h->st_fxi, &h->st_rlist, &h->st_flags}) b->release();
     stream_release(h);
@@ -564,6 +598,7 @@ int mpc_trim(mpc_handle *h) {
                       &h->sums, &h->retry_list, &h->headd, &h->headi, &h->epool, &h->facet_flags, &h->kkt_code, &h->kkt_L, &h->xq_groups, &h->xq_list, &h->x1_buf, &h->theta_list, &h->vretry_list,
                       &h->status_tmp, &h->part_counts, &h->part_lists, &h->kept_g, &h->done_g, &h->dict_d[0], &h->dict_d[1], &h->dict_i[0], &h->dict_i[1],
                       &h->dict_stored[0], &h->dict_stored[1], &h->parent_slot, &h->parent_slot_next}) b->release();
+    for (auto &d : h->rdefer) for (DevBuf *b : d.buffers()) b->release();
     for (HostBuf *b : {&h->st_list, &h->st_status, &h->st_hd, &h->st_hi, &h->st_pool, &h->st_fxd, &h->st_fxi, &h->st_rlist, &h->st_flags}) b->release();
     h->n = 0; h->k = 0; h->n_pruned = 0; h->n_pruned_extra = 0; h->level_done = false;
     h->have_prev_dict = false; h->have_parent_slot = false;
@@ -605,7 +640,12 @@ int mpc_program_block(mpc_handle *h, int32_t which, double *out, int64_t cap, in
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return MPC_OK;
 }
-int mpc_set_region_overlap(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->kn.no_roverlap = !on; return MPC_OK; }
+int mpc_set_region_overlap(mpc_handle *h, int32_t on) {
+    if (!h || on < 0 || on > 3) return MPC_ERR_INVALID;
+    h->kn.no_roverlap = on == 0;
+    h->defer_mode = (on == 0 || on == 2) ? 0 : (on == 3 ? 2 : 1);   // (a miss already met stays: defer_off)
+    return MPC_OK;
+}
 int mpc_set_timing(mpc_handle *h, int32_t on) { if (!h) return MPC_ERR_INVALID; h->timing = on; return MPC_OK; }
 int64_t mpc_region_doubles(const mpc_handle *h) { return h ? h->rec_d : 0; }
 int64_t mpc_region_ints(const mpc_handle *h) { return h ? h->rec_i : 0; }
@@ -833,6 +873,26 @@ static int x1_join(mpc_handle *h) {
     h->x1_pending = false;
     return MPC_OK;
 }
+// ---- the region stage of a small level beside the next level (mpc_handle::RegionDefer) ---------------------------------------------
+// the set's buffers <-> the handle's: in at the start of a deferring level (every launch of the level then takes them as it always
+// took the handle's), out before its closing synchronisation (the next level works in the handle's own again)
+static void defer_swap(mpc_handle *h, mpc_handle::RegionDefer &d) {
+    std::swap(h->kkt_code, d.kkt_code); std::swap(h->kkt_L, d.kkt_L); std::swap(h->part_lists, d.part_lists); std::swap(h->headd, d.headd); std::swap(h->headi, d.headi);
+    std::swap(h->epool, d.epool); std::swap(h->kept_g, d.kept_g); std::swap(h->done_g, d.done_g); std::swap(h->dcnt, d.dcnt);
+}
+// Called by a level before its k_children_write: the launch of the level BEFORE reads that level's frontier, which has been this level's
+// children buffer since the hand-over.  A stream wait; the launch ended long ago (it was queued a whole level earlier).
+static int defer_join(mpc_handle *h, hipStream_t st) {
+    for (auto &d : h->rdefer)
+        if (d.pending && !d.joined && d.depth != h->sv_cur) { HIP_TRY(h, hipStreamWaitEvent(st, d.ev_done, 0)); d.joined = true; }
+    return MPC_OK;
+}
+// launches that will not be closed (the level is repeated, the solve abandoned or failed): waited for, their records dropped
+static void defer_drain(mpc_handle *h) {
+    if (!h->defer_pending()) return;
+    (void)hipStreamSynchronize(h->stream3);
+    for (auto &d : h->rdefer) d.pending = false;
+}
 static bool small_path_ok(const mpc_handle *h, long long n, int k, int32_t flags, int32_t gen_children) {
     if (h->kn.no_smallpath || !h->fast || h->kn.force_v1 || h->fast_r < 0 || n < 1 || n > h->kn.smallpath_max) return false;
     if (flags & MPC_LEVEL_GRAPH) return false;
@@ -980,20 +1040,32 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     hipStream_t st = h->stream;
     h->n_opt = h->n_children = h->n_pruned_new = h->n_regions = 0;
     h->n_needx = 0;
+    // (the level's form is known before its first launch: `fused`, and whether it ends with the quick test -- small_dict_cache below decides the same)
+    const bool fused = !h->theta_open && !h->kn.no_small_fuse;
+    const bool will_store = dict_will_store(h, nn, gen_children);
+    // The region stage beside the NEXT level (mpc_handle::RegionDefer): inside mpc_solve_start's loop, on a level with children in the fused
+    // form that does not end with the quick test; not under a profile (per-stage events in line, as for the deferred k_x1), not where the next
+    // level's launches depend on this level's number of regions (MPC_XQ_EARLY_REGIONS).
+    mpc_handle::RegionDefer *df = nullptr;
+    if (h->sv_cur >= 0 && h->defer_mode > 0 && !h->defer_off && !h->kn.no_roverlap && gen_children && fused && !h->timing && h->kn.xq_early_regions == 0 &&
+        (will_store || !(h->have_prev_dict && h->have_parent_slot))) {
+        df = &h->rdefer[h->sv_cur & 1];
+        if (df->pending) return fail(h, MPC_ERR_STATE, "level_run_small: the deferred region launch of two levels ago has not been closed");
+        defer_swap(h, *df);
+    }
     HIP_TRY(h, h->status.ensure(nn, st));
     HIP_TRY(h, h->pruned.ensure((size_t)(h->n_pruned + n) * h->mw * sizeof(uint64_t), st, true));   // the level's newly pruned masks go behind the list
     HIP_TRY(h, h->retry_list.ensure(nn * sizeof(int32_t), st));
     HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
     HIP_TRY(h, h->part_lists.ensure((size_t)PART_CLASSES * nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
+    HIP_TRY(h, h->dcnt.ensure(mpc_handle::DEFER_DCNT_BYTES, st));
     {
         // counters, list lengths, the region kernel's completion flags and the "dictionary stored" flags: cleared by one launch
-        const bool will_store = dict_will_store(h, nn, gen_children);
         HIP_TRY(h, h->done_g.ensure(nn * 2 * sizeof(unsigned int), st));
         if (will_store) HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
         ZeroBufs z{};
         z.p[0] = h->ctr.p; z.bytes[0] = sizeof(LevelCounters);
-        z.p[1] = h->dcnt.p; z.bytes[1] = 32 * sizeof(int32_t);
+        z.p[1] = h->dcnt.p; z.bytes[1] = df ? mpc_handle::DEFER_DCNT_BYTES : 32 * sizeof(int32_t);   // (a deferred launch counts in its own LevelCounters, behind the list lengths)
         z.p[2] = h->done_g.p; z.bytes[2] = nn * 2 * sizeof(unsigned int);
         if (will_store) { z.p[3] = h->dict_stored[h->dict_cur].p; z.bytes[3] = nn; }
         hipLaunchKernelGGL(k_zero_bufs, dim3((unsigned)std::min<size_t>(64, (nn * 8 + 2047) / 2048 + 1)), dim3(256), 0, st, z);
@@ -1041,7 +1113,6 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     // three launches on them at each of its two verdict stages: ONE partition lists them as class 0 beside the classes below, the level
     // goes on without them, and if there was one (counted in [4] / [24]) the host repeats the level on the classic path -- as it does for
     // the other rare cases.  The end of the level is one launch (k_small_end) instead of five, the scan carries the publish.
-    const bool fused = !h->theta_open && !h->kn.no_small_fuse;
     if (!fused) {
         hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 12);
         hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 12);
@@ -1053,6 +1124,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
                        fused ? part_spec({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}})
                              : part_spec({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 4);
     HIP_TRY(h, hipGetLastError());
+    if (df) HIP_TRY(h, hipEventRecord(df->ev_go, st));   // everything the deferred region launch reads has been queued
     // ---- region stage: one slot per optimal candidate, buffers sized by the bound.  It needs the theta stage's verdicts only; a
     // candidate that turns out optimal only later -- a doubtful one of the (x,theta) stage, re-solved -- sends the level to the classic
     // path.  (Measured: on its own stream beside the (x,theta) stage it gains nothing at this size -- the fork / join events cost what
@@ -1060,6 +1132,8 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     // 5.47 / 5.61 ms forked against 5.48 / 5.54 in line -- the region kernel itself is 0.185 instead of 0.158 ms beside k_x2.) -----------------------------------------------
     SmallRX rx{};
     unsigned grid_r = 1;
+    // a deferred launch counts in its own LevelCounters (the next level clears the handle's) and leaves status[] alone (the next level's by then)
+    LevelCounters *ctr_r = df ? reinterpret_cast<LevelCounters *>(h->dcnt.as<char>() + 32 * sizeof(int32_t)) : ctr;
     {
         int ldk = 0;
         { int rcb = small_region_slots(h, nn, st, ldk); if (rcb) return rcb; }
@@ -1070,14 +1144,14 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         grid_r = (unsigned)std::min<long long>(n * std::max(h->kn.rsplit_max, 1), h->grid_r2);
         const DevProblem *pr = h->pr2_dev.as<DevProblem>();
         const int nt_r = region2_nt(h->fast_r);
-        rx.pr = pr; rx.fr = h->frontier.as<int32_t>(); rx.k = k; rx.opt_list = h->opt_ptr; rx.n = (int)n; rx.status = h->status.as<uint8_t>();
-        rx.headd = h->headd.as<double>(); rx.headi = h->headi.as<int32_t>(); rx.fd = h->fd; rx.fi = h->fi; rx.epool = h->epool.as<double>(); rx.ctr = ctr;
+        rx.pr = pr; rx.fr = h->frontier.as<int32_t>(); rx.k = k; rx.opt_list = h->opt_ptr; rx.n = (int)n; rx.status = df ? (uint8_t *)nullptr : h->status.as<uint8_t>();
+        rx.headd = h->headd.as<double>(); rx.headi = h->headi.as<int32_t>(); rx.fd = h->fd; rx.fi = h->fi; rx.epool = h->epool.as<double>(); rx.ctr = ctr_r;
         rx.kkc = kkc; rx.kkl = kkl; rx.W = W; rx.kept_g = h->kept_g.as<uint8_t>(); rx.ldk = ldk; rx.done_g = h->done_g.as<unsigned int>();
         rx.tvp_box = h->kn.no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r; rx.rs = rs;
     }
     // (the launch itself comes below: together with the (x,theta) kernel in one grid where an instantiation of the pair exists)
-    auto region2_alone = [&]() -> int {
-        launch_region2(h->fast_r, dim3(grid_r), h->lds_r2, st, rx.pr, rx.fr, rx.k, rx.opt_list, rx.n, rx.status, rx.headd, rx.headi, rx.fd, rx.fi, rx.epool,
+    auto region2_alone = [&](hipStream_t rst) -> int {
+        launch_region2(h->fast_r, dim3(grid_r), h->lds_r2, rst, rx.pr, rx.fr, rx.k, rx.opt_list, rx.n, rx.status, rx.headd, rx.headi, rx.fd, rx.fi, rx.epool,
                        rx.ctr, rx.kkc, rx.kkl, rx.W, rx.kept_g, rx.ldk, rx.done_g, rx.tvp_box, rx.rs);
         HIP_TRY(h, hipGetLastError());
         return MPC_OK;
@@ -1091,7 +1165,7 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     const int32_t *needx_n = dcnt + 7;
     const bool quick_test = !h->storing && dc.parent_slot;
     bool merged_rx = false;
-    if (fused && !quick_test && !h->kn.no_small_rx) {
+    if (fused && !quick_test && !h->kn.no_small_rx && !df) {
         // region kernel + (x,theta) kernel as ONE grid (batch_level.hpp, SmallRX): the two work on disjoint candidates
         DictCache d = dc;
         d.n_list_dev = needx_n;
@@ -1100,7 +1174,18 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
         merged_rx = small_region2_x2_launch(h->fast_r, h->fast_x, grid_r, (unsigned)std::min<long long>(n, (long long)h->n_cu * 16), h->lds_r2, st, rx, &e_rx);
         if (merged_rx) HIP_TRY(h, e_rx);
     }
-    if (!merged_rx) { int rcr = region2_alone(); if (rcr) return rcr; }
+    if (df) {
+        // stream3, behind the partition's event: the main stream goes on with k_x2 and the end of the level and never waits for this
+        // launch inside the level.  Behind it, on the same stream, what the host needs to close the level goes to the pinned block.
+        HIP_TRY(h, hipStreamWaitEvent(h->stream3, df->ev_go, 0));
+        { int rcr = region2_alone(h->stream3); if (rcr) return rcr; }
+        hipLaunchKernelGGL(k_defer_publish, dim3(1), dim3(256), 0, h->stream3, rx.headi, rx.fi, rx.rs.n_opt_dev, reinterpret_cast<const unsigned int *>(ctr_r),
+                           (int)(sizeof(LevelCounters) / 4), h->defer_pub_dev(h->sv_cur & 1));
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(df->ev_done, h->stream3));
+        df->pending = true; df->joined = false; df->depth = h->sv_cur; df->k = k; df->fd = h->fd; df->fi = h->fi; df->n_opt = 0;
+        df->keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
+    } else if (!merged_rx) { int rcr = region2_alone(st); if (rcr) return rcr; }
     if (quick_test) {   // last level: decisions only -- the quick test on a few vectors of the parent's dictionary first
         DictCache dq = dc;
         dq.n_list_dev = needx_n;
@@ -1143,11 +1228,14 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     }
     if (gen_children) {
         { int rcb = small_children_buffers(h, nn, k, st); if (rcb) return rcb; }
+        // (deferred region launch: the optimal candidates are still "region pending" here and expand as if they had their regions)
         launch_children_count(h->mw, dim3((unsigned)n), st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                              h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(), keep_lowdim);
+                              h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(),
+                              keep_lowdim | (df ? EXPAND_PENDING : 0));
         if (fused) hipLaunchKernelGGL(k_scan_publish, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20,
                                       reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4), reinterpret_cast<const unsigned int *>(dcnt), 32, pub_dst);
         else hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20);
+        { int rcj = defer_join(h, st); if (rcj) return rcj; }   // the children buffer is the frontier the previous level's deferred region launch reads
         hipLaunchKernelGGL(k_children_write, dim3((unsigned)n), dim3(64), 0, st, h->frontier.as<int32_t>(), n, k, h->mw,
                            h->childmask.as<unsigned long long>(), h->offset.as<int32_t>(), h->children.as<int32_t>(),
                            h->storing ? h->dict_stored[h->dict_cur].as<uint8_t>() : (const uint8_t *)nullptr, h->parent_slot_next.as<int32_t>());
@@ -1159,15 +1247,19 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     if (!fused) hipLaunchKernelGGL(k_publish_words2, dim3(1), dim3(128), 0, st, reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4),
                                    reinterpret_cast<const unsigned int *>(dcnt), 32, pub_dst);
     HIP_TRY(h, hipGetLastError());
+    if (df) defer_swap(h, *df);   // every launch is queued: the set keeps what its region launch works in, the handle has its own buffers back
     HIP_TRY(h, hipStreamSynchronize(st));   // the level's only synchronisation
     LevelCounters host_ctr;
     std::memcpy(&host_ctr, h->tot_host + 16, sizeof(LevelCounters));
     h->n_smallpath++;
     small_debug_note(cnt_host);
     if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) { h->n_smallpath_doubtful++; g_small_repeats_doubtful++; }
-    if (host_ctr.n_rretry > 0 || cnt_host[17] > 0 || h->kn.test_small_fallback || (fused && (cnt_host[4] > 0 || cnt_host[24] > 0))) {
+    // (behind a deferred region launch every optimal candidate is still "region pending": exactly the launch's, [6], may be)
+    const int n_late = cnt_host[17] - (df ? cnt_host[6] : 0);
+    if (host_ctr.n_rretry > 0 || n_late != 0 || h->kn.test_small_fallback || (fused && (cnt_host[4] > 0 || cnt_host[24] > 0))) {
         // a candidate k_region2 gave up on (the LDS-engine region kernel is not part of this path), or one that turned out optimal
         // after the region launch: the level is repeated classically
+        if (df) { HIP_TRY(h, hipEventSynchronize(df->ev_done)); df->pending = false; }   // its own deferred launch: waited for, its records dropped
         h->n_smallpath_fallback++; g_small_repeats++;
         // The repeat must not look for other parents' records: this run's k_children_write has overwritten the previous level's frontier
         // (it lives in the children buffer since the hand-over), which that search walks.
@@ -1188,10 +1280,12 @@ static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, m
     h->n_pruned_new = host_ctr.n_pruned_new;
     h->n_erows = host_ctr.e_rows;
     h->n_regions = (long long)host_ctr.status[ST_REGION];
+    if (df) df->n_opt = h->n_opt;   // (regions, rows, the launch's counters: defer_close, behind the next level)
     level_close(h, n);
     if (stats) {
         level_stats_small(h, host_ctr, cnt_host, kkc != nullptr, quick_test, stats);
         stats->ms_verdict = ms[0]; stats->ms_region = ms[1]; stats->ms_children = ms[2]; stats->ms_total = ms[0] + ms[1] + ms[2];
+        if (df) stats->region_side_stream = 2;
     }
     return MPC_OK;
 }
@@ -1550,73 +1644,191 @@ static void solve_release(mpc_handle *h) {
     h->sv_n.store(0, std::memory_order_release);
 }
 
+// One launch writes a level's slot records (every record in slot form on the device) into fresh page-locked blocks of lv and raises the
+// flag behind head_i; nobody waits here (mpc_solve_level does).  counter: a zero word of device memory nothing else uses before the launch.
+static int solve_fetch_slots(mpc_handle *h, mpc_handle::SolveLevel &lv, long long n_opt, int fd, int fi, long long n_erows, size_t b_er,
+                             const void *headd, const void *headi, const void *epool, unsigned int *counter) {
+    const size_t b_hd = (size_t)n_opt * fd * sizeof(double), b_hi = (size_t)n_opt * fi * sizeof(int32_t);
+    if (host_pool_take(b_hd, &lv.hd, nullptr, true) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, true) != hipSuccess ||
+        host_pool_take(b_er, &lv.er, nullptr, true) != hipSuccess) return fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
+    FetchCopy fc{};
+    int32_t *flag = reinterpret_cast<int32_t *>(static_cast<char *>(lv.hi) + ((b_hi + 7) & ~size_t(7)));
+    *flag = 0;
+    void *d_hd = nullptr, *d_hi = nullptr, *d_er = nullptr;
+    if (hipHostGetDevicePointer(&d_hd, lv.hd, 0) != hipSuccess || hipHostGetDevicePointer(&d_hi, lv.hi, 0) != hipSuccess ||
+        hipHostGetDevicePointer(&d_er, lv.er, 0) != hipSuccess) return fail(h, MPC_ERR_HIP, "hipHostGetDevicePointer (level records)");
+    fc.src[0] = headi; fc.dst[0] = d_hi; fc.bytes[0] = b_hi;
+    fc.src[1] = headd; fc.dst[1] = d_hd; fc.bytes[1] = b_hd;
+    fc.src[2] = epool; fc.dst[2] = d_er; fc.bytes[2] = (size_t)n_erows * (h->n_t + 1) * sizeof(double);
+    fc.counter = counter;
+    fc.flag = reinterpret_cast<int32_t *>(static_cast<char *>(d_hi) + ((b_hi + 7) & ~size_t(7)));
+    const unsigned long long words = (b_hi + b_hd + fc.bytes[2]) / 4;
+    hipLaunchKernelGGL(k_fetch_slots, dim3((unsigned)std::min<unsigned long long>(256, words / 2048 + 1)), dim3(256), 0, h->stream, fc);
+    if (hipGetLastError() != hipSuccess) return fail(h, MPC_ERR_HIP, "k_fetch_slots launch");
+    lv.ready_flag = flag;
+    lv.mode = 2; lv.n_slots = n_opt; lv.n_rows = n_erows; lv.chunk = 0; lv.n_chunks = 0;
+    return MPC_OK;
+}
+static void solve_publish(mpc_handle *h, mpc_handle::SolveLevel &lv) {
+    lv.ready.store(1, std::memory_order_release);
+    lv.done.store(1, std::memory_order_release);
+    { std::lock_guard<std::mutex> lk(h->wm); }
+    h->wcv.notify_all();
+}
+
+// Closes a level whose region launch ran beside the level after it (mpc_handle::RegionDefer): behind that level's closing synchronisation
+// (its children stage waited for the launch), or at once (`final`) when the loop ends with the launch pending.  *miss: a slot's verdict
+// would not have expanded as its candidate did -- nothing is published, the caller abandons the pass.  Otherwise the level's statistics
+// get what the launch counted, the records are fetched and the level is published as a level in line is.
+static int defer_close(mpc_handle *h, mpc_handle::RegionDefer &d, int flags, bool final, bool *miss) {
+    *miss = false;
+    const int set = (int)(&d - h->rdefer);
+    auto &lv = h->sv_levels[d.depth];
+    HIP_TRY(h, hipEventSynchronize(d.ev_done));
+    d.pending = false;
+    const unsigned int *pub = h->defer_pub_host(set);
+    LevelCounters rc;
+    std::memcpy(&rc, pub, sizeof(LevelCounters));
+    const unsigned int *verdict = pub + sizeof(LevelCounters) / 4;   // [0..7] slots by head_i[slot][0], [8] slots
+    long long n_slots = 0;
+    for (int i = 0; i < 8; ++i) n_slots += verdict[i];
+    if ((long long)verdict[8] != d.n_opt || n_slots != d.n_opt) return fail(h, MPC_ERR_STATE, "defer_close: the deferred region launch did not write one record per optimal candidate");
+    const bool forced = h->defer_mode == 2 && !h->defer_miss_forced;
+    if (forced) h->defer_miss_forced = true;
+    // what k_small_end would have pruned, what k_region2 gave up on (the LDS-engine region kernel is no part of the small path), and an
+    // mpLP candidate that is expanded as a feasible one after all (its children pass the filter an optimal parent's do not)
+    if (forced || rc.n_rretry > 0 || verdict[ST_RETRY] > 0 || verdict[ST_INFEASIBLE] > 0 || (verdict[ST_OPT_NO_REGION] > 0 && !d.keep_lowdim) ||
+        (verdict[ST_FEASIBLE] > 0 && !h->is_qp)) {
+        *miss = true;
+        return MPC_OK;
+    }
+    mpc_level_stats &st = lv.stats;
+    for (int i = 0; i < 6; ++i) st.n_status[i] += (int64_t)verdict[i];
+    st.n_regions = (int64_t)verdict[ST_REGION];
+    st.n_region_rows = (int64_t)rc.e_rows;
+    st.lp_pivots += (int64_t)rc.pivots;
+    st.wave_cycles[3] += (int64_t)rc.cycles[3];
+    if (d.n_opt > 0 && rc.r2_t1 > ~rc.r2_not_t0 && h->wall_khz > 0) st.ms_region2 = (float)((double)(rc.r2_t1 - ~rc.r2_not_t0) / (double)h->wall_khz);
+    int rcs = MPC_OK;
+    if ((flags & MPC_SOLVE_FETCH) && st.n_regions > 0)
+        rcs = solve_fetch_slots(h, lv, d.n_opt, d.fd, d.fi, (long long)rc.e_rows, std::max<size_t>((size_t)rc.e_rows, 1) * (h->n_t + 1) * sizeof(double),
+                                d.headd.p, d.headi.p, d.epool.p, reinterpret_cast<unsigned int *>(d.dcnt.as<int32_t>() + 30));
+    else lv.mode = 0;
+    if (rcs == MPC_OK && final) {
+        // no level followed: the handle is left as a level in line leaves it (mpc_level_status, mpc_level_regions_* after mpc_solve_wait)
+        defer_swap(h, d);
+        h->n_regions = st.n_regions; h->n_erows = (long long)rc.e_rows;
+        if (d.n_opt > 0) {
+            hipLaunchKernelGGL(k_defer_status, dim3((unsigned)((d.n_opt + 255) / 256)), dim3(256), 0, h->stream, h->headi.as<int32_t>(), d.fi, (int)d.n_opt, h->status.as<uint8_t>());
+            HIP_TRY(h, hipGetLastError());
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (rcs != MPC_OK) return rcs;
+    solve_publish(h, lv);
+    return MPC_OK;
+}
+// A deferred region launch of level `from` missed: every launch is waited for, the handle never defers again, and what the abandoned pass
+// has made known of the levels from `from` on (a streamed level after it may have handed its blocks to sv_levels already; the consumer
+// takes levels in order and is still waiting for `from`) is taken back.
+static void defer_abandon(mpc_handle *h, int from) {
+    (void)hipStreamSynchronize(h->stream);
+    defer_drain(h);
+    h->defer_off = true;
+    const int nl = h->sv_n.load(std::memory_order_acquire);
+    for (int i = from; i < nl; ++i) {
+        auto &lv = h->sv_levels[i];
+        if (!lv.handed) { if (lv.hd) (void)host_pool_give(lv.hd); if (lv.hi) (void)host_pool_give(lv.hi); if (lv.er) (void)host_pool_give(lv.er); }
+        lv.hd = lv.hi = lv.er = nullptr; lv.handed = false; lv.flags = nullptr; lv.ready_flag = nullptr; lv.mode = 0;
+        lv.ready.store(0, std::memory_order_release); lv.done.store(0, std::memory_order_release);
+    }
+}
+
 // The level loop of the reference's driver (mp_solvers/mpqp_parrallel_combinatorial.py:98-139) on the worker thread: root frontier,
 // then level after level -- run, publish the level's records, advance the frontier -- without a hand-over to the caller in between.
+// A small level may leave its region launch running beside the level after it (RegionDefer): that level is published one level later,
+// by defer_close.  After a miss the loop starts again from the root: the levels below the one that missed are final and published (the
+// path is deterministic) -- they are run again for the handle's state alone (`replay_below`).
 static int worker_solve(mpc_handle *h) {
     const int flags = h->sv_flags;
-    int rc = mpc_pruned_clear(h);
-    if (rc == MPC_OK) rc = mpc_frontier_root(h);
     const int level_flags = flags & (MPC_LEVEL_STREAM | MPC_LEVEL_KEEP_LOWDIM);
-    for (int depth = 0; rc == MPC_OK && depth < h->sv_max_levels; ++depth) {
-        const int gen = depth + 1 != h->sv_max_levels;
-        auto &lv = h->sv_levels[depth];
-        lv.k = h->k; lv.n = h->n;
-        const auto t0 = std::chrono::steady_clock::now();
-        h->sv_cur = depth;
-        h->sv_n.store(depth + 1, std::memory_order_release);
-        rc = level_run_impl(h, gen, level_flags, &lv.stats);
-        if (rc == MPC_OK && !lv.ready.load(std::memory_order_relaxed)) {
-            // the level did not stream (no optimal candidate; run without host round trips, its records in device buffers; LDS-engine
-            // region kernel; > 1 GiB of records): fetched here, complete when published
-            if ((flags & MPC_SOLVE_FETCH) && lv.stats.n_regions > 0 && h->n_opt > 0 && !h->so.active) {
-                int64_t rows_cap = 0, ns = 0, nr = 0;
-                mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
-                const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t),
-                             b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
-                const bool all_slots = h->used_region2 && h->n_rretry == 0;   // every record is in slot form on the device
-                if (host_pool_take(b_hd, &lv.hd, nullptr, all_slots) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, all_slots) != hipSuccess ||
-                    host_pool_take(b_er, &lv.er, nullptr, all_slots) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
-                if (rc == MPC_OK && all_slots) {
-                    // one launch writes the three arrays into the host blocks and raises the flag behind head_i; nobody waits here
-                    FetchCopy fc{};
-                    int32_t *flag = reinterpret_cast<int32_t *>(static_cast<char *>(lv.hi) + ((b_hi + 7) & ~size_t(7)));
-                    *flag = 0;
-                    void *d_hd = nullptr, *d_hi = nullptr, *d_er = nullptr;
-                    if (hipHostGetDevicePointer(&d_hd, lv.hd, 0) != hipSuccess || hipHostGetDevicePointer(&d_hi, lv.hi, 0) != hipSuccess ||
-                        hipHostGetDevicePointer(&d_er, lv.er, 0) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "hipHostGetDevicePointer (level records)");
-                    if (rc == MPC_OK) {
-                        fc.src[0] = h->headi.p; fc.dst[0] = d_hi; fc.bytes[0] = b_hi;
-                        fc.src[1] = h->headd.p; fc.dst[1] = d_hd; fc.bytes[1] = b_hd;
-                        fc.src[2] = h->epool.p; fc.dst[2] = d_er; fc.bytes[2] = (size_t)h->n_erows * (h->n_t + 1) * sizeof(double);
-                        fc.counter = reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + 30);   // zero: cleared with the list lengths at the start of every level
-                        fc.flag = reinterpret_cast<int32_t *>(static_cast<char *>(d_hi) + ((b_hi + 7) & ~size_t(7)));
-                        const unsigned long long words = (b_hi + b_hd + fc.bytes[2]) / 4;
-                        hipLaunchKernelGGL(k_fetch_slots, dim3((unsigned)std::min<unsigned long long>(256, words / 2048 + 1)), dim3(256), 0, h->stream, fc);
-                        if (hipGetLastError() != hipSuccess) rc = fail(h, MPC_ERR_HIP, "k_fetch_slots launch");
-                        lv.ready_flag = flag; ns = h->n_opt; nr = h->n_erows;
+    int rc = MPC_OK, replay_below = 0, missed = -1;
+    for (;;) {
+        int miss_at = -1;
+        rc = mpc_pruned_clear(h);
+        if (rc == MPC_OK) rc = mpc_frontier_root(h);
+        for (int depth = 0; rc == MPC_OK && depth < h->sv_max_levels; ++depth) {
+            const int gen = depth + 1 != h->sv_max_levels;
+            if (depth < replay_below) {
+                mpc_level_stats rs{};
+                h->sv_cur = depth;
+                rc = level_run_impl(h, gen, level_flags & ~MPC_LEVEL_STREAM, &rs);
+                h->sv_cur = -1;
+                if (rc != MPC_OK || !gen || rs.n_children == 0) break;
+                rc = mpc_frontier_advance(h);
+                continue;
+            }
+            auto &lv = h->sv_levels[depth];
+            lv.k = h->k; lv.n = h->n;
+            const auto t0 = std::chrono::steady_clock::now();
+            h->sv_cur = depth;
+            if (h->sv_n.load(std::memory_order_relaxed) < depth + 1) h->sv_n.store(depth + 1, std::memory_order_release);
+            rc = level_run_impl(h, gen, level_flags, &lv.stats);
+            auto &mine = h->rdefer[depth & 1], &before = h->rdefer[(depth + 1) & 1];
+            const bool deferred = rc == MPC_OK && mine.pending && mine.depth == depth;
+            if (rc == MPC_OK && depth == missed) lv.stats.region_side_stream = 3;   // its deferred launch missed: this is the repeat, in line
+            if (rc == MPC_OK && before.pending) {
+                // this level's closing synchronisation has passed, its children stage waited for the launch of the level before
+                bool miss = false;
+                rc = defer_close(h, before, flags, false, &miss);
+                if (rc == MPC_OK && miss) { miss_at = before.depth; break; }
+            }
+            if (rc == MPC_OK && !deferred && !lv.ready.load(std::memory_order_relaxed)) {
+                // the level did not stream (no optimal candidate; run without host round trips, its records in device buffers; LDS-engine
+                // region kernel; > 1 GiB of records): fetched here, complete when published
+                if ((flags & MPC_SOLVE_FETCH) && lv.stats.n_regions > 0 && h->n_opt > 0 && !h->so.active) {
+                    int64_t rows_cap = 0, ns = 0, nr = 0;
+                    mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
+                    const size_t b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
+                    if (h->used_region2 && h->n_rretry == 0)   // every record is in slot form on the device
+                        // (the counter: a list length nothing uses, cleared with the others at the start of every level)
+                        rc = solve_fetch_slots(h, lv, h->n_opt, h->fd, h->fi, h->n_erows, b_er, h->headd.p, h->headi.p, h->epool.p, reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + 30));
+                    else {
+                        const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t);
+                        if (host_pool_take(b_hd, &lv.hd, nullptr, false) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, false) != hipSuccess ||
+                            host_pool_take(b_er, &lv.er, nullptr, false) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
+                        if (rc == MPC_OK)
+                            rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), h->n_opt, static_cast<double *>(lv.er),
+                                                          rows_cap, &ns, &nr, false, false);
+                        lv.mode = 2; lv.n_slots = ns; lv.n_rows = nr; lv.chunk = 0; lv.n_chunks = 0;
                     }
-                } else if (rc == MPC_OK)
-                    rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), h->n_opt, static_cast<double *>(lv.er),
-                                                  rows_cap, &ns, &nr, false, false);
-                lv.mode = 2; lv.n_slots = ns; lv.n_rows = nr; lv.chunk = 0; lv.n_chunks = 0;
-            } else lv.mode = 0;
-        } else if (rc == MPC_OK && lv.stats.n_region_retry > 0) {
-            // candidates the LDS-engine kernel re-solved after the stream: their slots are filled in place (the caller lists the level
-            // again after mpc_solve_level_wait)
-            int64_t ns = 0, nr = 0;
-            rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, false, true);
+                } else lv.mode = 0;
+            } else if (rc == MPC_OK && !deferred && lv.stats.n_region_retry > 0) {
+                // candidates the LDS-engine kernel re-solved after the stream: their slots are filled in place (the caller lists the level
+                // again after mpc_solve_level_wait)
+                int64_t ns = 0, nr = 0;
+                rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, false, true);
+            }
+            lv.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            h->sv_cur = -1;
+            if (rc != MPC_OK) break;
+            if (!deferred) solve_publish(h, lv);
+            if (!gen || lv.stats.n_children == 0) {
+                if (deferred) {   // the loop ends with the launch pending: closed at once
+                    bool miss = false;
+                    rc = defer_close(h, mine, flags, true, &miss);
+                    if (rc == MPC_OK && miss) miss_at = depth;
+                }
+                break;
+            }
+            rc = mpc_frontier_advance(h);
         }
-        lv.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         h->sv_cur = -1;
-        if (rc != MPC_OK) break;
-        lv.ready.store(1, std::memory_order_release);
-        lv.done.store(1, std::memory_order_release);
-        { std::lock_guard<std::mutex> lk(h->wm); }
-        h->wcv.notify_all();
-        if (!gen || lv.stats.n_children == 0) break;
-        rc = mpc_frontier_advance(h);
+        if (miss_at < 0 || rc != MPC_OK) break;
+        defer_abandon(h, miss_at);
+        replay_below = missed = miss_at;
     }
-    h->sv_cur = -1;
+    defer_drain(h);   // (an error inside the loop)
     h->base_valid = false;
     if (rc == MPC_OK && (flags & MPC_LEVEL_THEN_BASE)) worker_base_check(h);
     return rc;
