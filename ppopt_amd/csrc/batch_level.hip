@@ -2,7 +2,7 @@
 //
 // MPC_GLOBAL turns every kernel of kernels.hpp / kernels2.hpp into an inlined device function in this translation unit; the
 // kernels below fetch their member's argument block (blockIdx.y) and call those bodies with exactly the arguments
-// level_run_small (mpcombi_hip.hip) passes for a single program.  blockIdx.x / gridDim.x keep their meaning inside the bodies:
+// level_run_small (level_small.hpp) passes for a single program.  blockIdx.x / gridDim.x keep their meaning inside the bodies:
 // the x-extent of a launch is the largest any member of the group needs, a member's surplus blocks leave at once (every body
 // tests its index or its work queue against the member's own counts).
 #define MPC_GLOBAL __device__ __forceinline__
@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(64, (SLOTS >= 2 ? (NT <= 4 ? TH_WAVES_S2 : 2) 
     const uint8_t *kkc = nullptr;
     const double *kkl = nullptr;
     const int32_t *list = nullptr;
-    if (m.use_kkt) { kkc = m.kkt_code; kkl = m.kkt_L; list = m.theta_list; ta.n_dev = m.dcnt + 0; }
+    if (m.use_kkt) { kkc = m.kkt_code; kkl = m.kkt_L; list = m.theta_list; ta.n_dev = m.dcnt + DC_THETA; }
     k_theta2<NT, SLOTS>(m.pf, m.fr, m.n, m.k, m.status, m.ctr, kkc, kkl, ta, list);
 }
 __global__ void __launch_bounds__(1024) m_partition_small(const BatchMember *__restrict__ tab, unsigned long long spec, int slot) {
@@ -97,12 +97,12 @@ __global__ void __launch_bounds__(64, (SLOTS >= 2 ? 2 : R2W)) m_region2(const Ba
                          m.kept_g, m.ldk, m.done_g, m.no_rbox ? (const double *)nullptr : m.targs.tvp + (size_t)NT * NT + NT, rs);
 }
 
-// the candidates k_region2 gave up on (status RRETRY, compacted into retry_list, length at dcnt[28]): the LDS-engine kernel in its
+// the candidates k_region2 gave up on (status RRETRY, compacted into retry_list, length at DC_BATCH_RRETRY): the LDS-engine kernel in its
 // latency form, as launch_region_v1 runs it for a short list -- one wavefront per (candidate, region row), then the assembly pass
 template <int MODE>
 __global__ void __launch_bounds__(64) m_region_v1(const BatchMember *__restrict__ tab) {
     MEMBER;
-    const int n_list = m.dcnt[28];
+    const int n_list = m.dcnt[DC_BATCH_RRETRY];
     if (n_list <= 0 || n_list > m.rcap) return;      // none (the usual case) / more than the reserved slots: the member repeats the level alone
     k_region<MODE>(m.Pr, m.fr, m.k, m.retry_list, n_list, m.status, m.recd, m.reci, m.rec_d, m.rec_i, m.ctr, m.facet_flags);
 }
@@ -112,7 +112,7 @@ template <int SLOTS>
 __global__ void __launch_bounds__(64, XQ_WAVES) m_xq(const BatchMember *__restrict__ tab) {
     MEMBER;
     DictCache dq = m.dc;
-    dq.n_list_dev = m.dcnt + 7;
+    dq.n_list_dev = m.dcnt + DC_OPEN;
     dq.max_blocks = m.xq_blocks;
     k_xq<SLOTS>(m.pf, m.fr, m.k, part_list_of(m, 3), (int)m.n, m.status, m.ctr, dq, m.nxc);
 }
@@ -120,7 +120,7 @@ template <int NXC, int SLOTS>
 __global__ void __launch_bounds__(64, (NXC * SLOTS >= 64 ? 2 : (NXC * SLOTS >= 32 ? X2_WAVES : X2_WAVES_16))) m_x2(const BatchMember *__restrict__ tab) {
     MEMBER;
     DictCache d = m.dc;
-    d.n_list_dev = m.dcnt + (m.quick_test ? 8 : 7);
+    d.n_list_dev = m.dcnt + (m.quick_test ? DC_OPEN_QT : DC_OPEN);
     d.max_blocks = m.x2_blocks;
     k_x2<NXC, SLOTS>(m.pf, m.fr, m.k, m.quick_test ? m.retry_list : part_list_of(m, 3), (int)m.n, m.status, m.ctr, d);
 }
@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(64) m_children_count(const BatchMember *__rest
 }
 __global__ void __launch_bounds__(1024) m_scan_small(const BatchMember *__restrict__ tab) {
     MEMBER;
-    k_scan_small(m.count, m.offset, (int)m.n, m.dcnt + 20);
+    k_scan_small(m.count, m.offset, (int)m.n, m.dcnt + DC_CHILDREN);
 }
 __global__ void __launch_bounds__(64) m_children_write(const BatchMember *__restrict__ tab) {
     MEMBER;
@@ -151,7 +151,7 @@ __global__ void m_histogram(const BatchMember *__restrict__ tab) {
 __global__ void m_publish(const BatchMember *__restrict__ tab) {
     MEMBER;
     k_publish_words(reinterpret_cast<const unsigned int *>(m.ctr), m.pub_ctr, (int)(sizeof(LevelCounters) / 4));
-    k_publish_words(reinterpret_cast<const unsigned int *>(m.dcnt), m.pub_cnt, 32);
+    k_publish_words(reinterpret_cast<const unsigned int *>(m.dcnt), m.pub_cnt, DCNT_WORDS);
 }
 
 }  // namespace
@@ -260,7 +260,7 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
 #undef MPC_LAUNCH_KKT_S
 #undef MPC_LAUNCH_KKT
 #undef MPC_LAUNCH_KKT_
-            if (!r.kkt_listed) hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_TODO, ST_TODO, 0, 0);
+            if (!r.kkt_listed) hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_TODO, ST_TODO, 0, DC_THETA);
         }
         {
             const dim3 g((unsigned)std::min<long long>(n_max, th_max > 0 ? th_max : grid_f), G), b(64);
@@ -276,10 +276,10 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
 #undef MPC_LAUNCH_TH
         }
         TRY(raise_lds(m_verdict, lds_v));
-        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_RETRY, 0}}), 12);
-        hipLaunchKernelGGL(m_verdict, dim3((unsigned)std::min<long long>(n_max, 128), G), dim3(64), lds_v, st, tab, 12);
+        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_RETRY, 0}}), DC_DOUBTFUL_T);
+        hipLaunchKernelGGL(m_verdict, dim3((unsigned)std::min<long long>(n_max, 128), G), dim3(64), lds_v, st, tab, DC_DOUBTFUL_T);
         hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab,
-                           spec_of({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), 4);
+                           spec_of({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), DC_CLASS);
         TRY(hipGetLastError());
         hipLaunchKernelGGL(m_zero_counter, dim3(1, G), dim3(64), 0, st, tab, 0);
         // (x,theta) stage
@@ -287,7 +287,7 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
             const dim3 gg((unsigned)std::min<long long>(n_max, xq_max > 0 ? xq_max : (long long)r.n_cu * 32), G), bb(64);
             if (r.fast_x & 1) hipLaunchKernelGGL((m_xq<2>), gg, bb, 0, st, tab);
             else hipLaunchKernelGGL((m_xq<1>), gg, bb, 0, st, tab);
-            hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_NEEDX, ST_NEEDX_SING, 1, 8);
+            hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_NEEDX, ST_NEEDX_SING, 1, DC_OPEN_QT);
         }
         {
             const dim3 gg((unsigned)std::min<long long>(n_max, x2_max > 0 ? x2_max : (long long)r.n_cu * 16), G), bb(64);
@@ -299,10 +299,10 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
             }
         }
         TRY(hipGetLastError());
-        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_RETRY, 0}}), 24);
-        hipLaunchKernelGGL(m_verdict, dim3((unsigned)std::min<long long>(n_max, 128), G), dim3(64), lds_v, st, tab, 24);
+        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_RETRY, 0}}), DC_DOUBTFUL_X);
+        hipLaunchKernelGGL(m_verdict, dim3((unsigned)std::min<long long>(n_max, 128), G), dim3(64), lds_v, st, tab, DC_DOUBTFUL_X);
         // region stage, behind the (x,theta) stage: every optimal candidate of the level is known -- those of the theta stage and those a
-        // re-solve of a doubtful (x,theta) run has just found -- so one launch covers them all (class 2 of the partition at [16..19];
+        // re-solve of a doubtful (x,theta) run has just found -- so one launch covers them all (class 2 of the partition at DC_BATCH_OPT_CLASS: DC_BATCH_OPT;
         // a single program overlaps its region stage with the (x,theta) stage instead and handles late candidates separately: with
         // other members filling the device there is nothing to gain from that here)
         {
@@ -313,7 +313,7 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
                 hipLaunchKernelGGL(m_recession, dim3((unsigned)std::min<long long>(n_max, 256), G), dim3(64), lds_v, st, tab);
             }
         }
-        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_OPT_PENDING, 2}}), 16);
+        hipLaunchKernelGGL(m_partition_small, dim3(1, G), dim3(1024), 0, st, tab, spec_of({{ST_OPT_PENDING, 2}}), DC_BATCH_OPT_CLASS);
         TRY(hipGetLastError());
         {
             const dim3 g((unsigned)std::min<long long>(n_max * std::max(rsplit, 1), r2_max > 0 ? r2_max : grid_r2), G), b(64);
@@ -333,7 +333,7 @@ hipError_t batch_level_launch(BatchMember *members, int B, hipStream_t st, Batch
             for (int i = g0; i < g1; ++i) { lds_r = std::max(lds_r, members[i].lds_r); rcap = std::max(rcap, members[i].rcap); }
             TRY(raise_lds(m_region_v1<RG_FACET>, lds_r));
             TRY(raise_lds(m_region_v1<RG_ASSEMBLE>, lds_r));
-            hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_RRETRY, ST_RRETRY, 1, 28);
+            hipLaunchKernelGGL(m_compact_small, dim3(1, G), dim3(1024), 0, st, tab, ST_RRETRY, ST_RRETRY, 1, DC_BATCH_RRETRY);
             hipLaunchKernelGGL(m_zero_counter, dim3(1, G), dim3(64), 0, st, tab, 1);
             hipLaunchKernelGGL(m_region_v1<RG_FACET>, dim3((unsigned)std::min(rcap * 8, 512), G), dim3(64), lds_r, st, tab);
             hipLaunchKernelGGL(m_zero_counter, dim3(1, G), dim3(64), 0, st, tab, 1);

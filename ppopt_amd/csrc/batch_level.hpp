@@ -30,7 +30,7 @@
 // together.  Round 3 gave each member the width of a single program's launch -- 64 members x 4,096 blocks, one member's tail after the
 // other: the bench enumeration's shared levels took 143 ms of device time, with shares 83 ms (MPC_BATCH_SHARES=0 A/B), 67 with the split above.
 //
-// The level is the no-round-trip form of mpcombi_hip.hip (level_run_small): list lengths live in device memory, launches are sized
+// The level is the no-round-trip form of level_small.hpp (level_run_small; batch_prepare / batch_finish there fill and read a member): list lengths live in device memory, launches are sized
 // by the members' candidate counts, the host synchronises once per level for ALL members.  Members whose kernels are different
 // template instantiations (n_theta class, rows per lane, mask words, cardinality) form separate groups of the same launch sequence.
 #pragma once
@@ -42,6 +42,43 @@ namespace mpc {
 
 // use_kkt == 2: k_kkt_thread with this many lanes per candidate (levels of a batch are small by construction), up to KMAX inequality rows
 constexpr int BATCH_KKT_SPREAD = 8, BATCH_KKT_SPREAD_KMAX = 6, BATCH_KKT_SPREAD_THREADS = 1 << 19;
+// most inequality rows of a member's one-thread KKT solve (m_kkt_thread is instantiated for 1..8; a single program goes to KKT_THREAD_MAX = 10)
+constexpr int BATCH_KKT_THREAD_MAX = 8;
+
+// ---- the words of a level's device-resident list lengths (mpc_handle::dcnt, BatchMember::dcnt; on the host mpc_handle::cnt_host()) ------
+// One block of DCNT_WORDS int32, cleared at the start of every level and published as a whole at its end.  The three forms of a level
+// -- S: without host round trips (level_small.hpp; "fused" / "round 4" where its two forms differ), B: a member of the shared launches
+// (batch_level.hip), C: classic (level_classic.hpp) -- agree on most words; where they do not, the word has one name per form.  A
+// partition (k_partition_small / k_part_sums) writes PART_CLASSES consecutive words, one per class, from the word it is given: the
+// *_CLASS names are such first words.  Words without a name (1..3, 11, 21..23, 25..27 and the classes nobody asks for) stay zero.
+enum DcntWord : int {
+    DC_THETA = 0,           // S B C: the theta stage's work list (k_kkt_thread's own list, or its compaction)
+    DC_CLASS = 4,           // S B C: classes behind the theta stage, words 4..7 ...
+    DC_DOUBTFUL_FUSED = 4,  // S fused: ... class 0, doubtful candidates; not zero: the level is repeated.  (S round 4, B: not asked for.  C: pinned words, not these)
+    DC_FEASIBLE = 5,        // S B: ... class 1, feasible
+    DC_OPT = 6,             // S B: ... class 2, optimal = S: the region launch's candidates (B: see DC_BATCH_OPT)
+    DC_OPEN = 7,            // S B: ... class 3, feasibility open
+    DC_OPEN_QT = 8,         // S B C: still open after the quick test
+    DC_OPEN_XQT = 9,        // C: what the quick test's thread pass left open
+    DC_KX = 10,             // S B C: the candidates k_kkt_thread's box screen sends to the (x,theta) question (its kx list)
+    DC_DOUBTFUL_T = 12,     // S round 4, B: doubtful after the theta stage, re-solved in place (class 0 of a partition at 12..15)
+    DC_X1 = 12,             // C: one-step plans: the dictionaries k_x1 streams ...
+    DC_X1_REST = 13,        // C: ... and the three lists left to k_x2, words 13..15
+    DC_LATE_CLASS = 16,     // S round 4: partition at 16..19 behind the (x,theta) stage ...
+    DC_LATE = 17,           // S: ... class 1: optimal candidates that missed the region launch (fused: counted by k_small_end)
+    DC_BATCH_OPT_CLASS = 16,   // B: partition at 16..19 behind the (x,theta) stage ...
+    DC_BATCH_OPT = 18,      // B: ... class 2: every optimal candidate of the level = the region launch's (it comes last in this form)
+    DC_CHILDREN = 20,       // S B C: children
+    DC_DOUBTFUL_X = 24,     // S B: doubtful after the (x,theta) stage (class 0 of a partition at 24..27; S fused: counted by k_small_end, not zero: repeated)
+    DC_XFIRST_CLASS = 28,   // C x_first: classes behind the theta stage, words 28..31, published as a range of PART_CLASSES: doubtful ...
+    DC_XFIRST_FEASIBLE = 29,   // C x_first: ... feasible
+    DC_XFIRST_OPT = 30,     // C x_first: ... optimal
+    DC_XFIRST_OPEN = 31,    // C x_first: ... open
+    DC_BATCH_RRETRY = 28,   // B: candidates k_region2 gave up on (the retry list's length)
+    DC_FETCH_COUNTER = 30,  // the level loop (worker_solve, defer_close): k_fetch_slots' workgroup counter, behind the level: must be zero at that launch
+    DCNT_WORDS = 32
+};
+constexpr size_t DCNT_BYTES = DCNT_WORDS * sizeof(int32_t);
 
 struct BatchZero { void *p; unsigned long long bytes; };
 

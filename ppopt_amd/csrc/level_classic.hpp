@@ -24,7 +24,7 @@ struct LevelRun {
     const bool small;               // n <= SMALL_LEVEL_N: compact / partition as single-block launches
     const int blocks256, nb1024;    // blocks of 256 / 1024 candidates
     LevelCounters *ctr = nullptr;   // set by begin: the level's counters on the device; read by every stage
-    int32_t *dcnt = nullptr;        // set by begin: the device-resident list lengths (layout: level_run_small's comment, and [9] [10] [12..15] [28..31] below); read by every stage
+    int32_t *dcnt = nullptr;        // set by begin: the device-resident list lengths (words named by DcntWord, batch_level.hpp); read by every stage
     int32_t *total = nullptr;       // set by begin: device alias of h->tot_host, valid on the host after the next synchronisation; read by compact, partition, queue_tail, region_stage
     // ---- what the statistics report (set by the stages, read by read_back and fill_stats) ------------------------------------------------
     LevelCounters host_ctr;         // set by read_back (zero on an empty level): the counters as published; read by fill_stats
@@ -39,9 +39,9 @@ struct LevelRun {
     bool x1_ran = false;            // set by launch_plans: the one-step plans ran; read by read_back, fill_stats
     // ---- state the helpers share ------------------------------------------------------------------------------------------------------------
     bool pruned_bucketed = false;   // set by begin: the pruned list was bucketed for this level; read by queue_tail
-    bool theta_lean = false;        // set by kkt_stage: the theta list's length stays on the device (dcnt[0]); read by theta_stage, read_back
-    bool xq_lean = false;           // set by quick_test: the length of what it left open stays on the device (dcnt[8]); read by launch_x, x_stage, read_back
-    bool children_lean = false;     // set by queue_tail: children written for the bound, their number in dcnt[20]; read by read_back
+    bool theta_lean = false;        // set by kkt_stage: the theta list's length stays on the device (DC_THETA); read by theta_stage, read_back
+    bool xq_lean = false;           // set by quick_test: the length of what it left open stays on the device (DC_OPEN_QT); read by launch_x, x_stage, read_back
+    bool children_lean = false;     // set by queue_tail: children written for the bound, their number in DC_CHILDREN; read by read_back
     // clears / copies / slot marks that a region launch and the (x,theta) stage need, collected and issued as ONE launch each
     // (k_region_prep): `prep` for the main stream, `rprep` for what only the region kernel reads (issued on ITS stream)
     RegionPrep prep{}, rprep{};     // set by prep_zero_in, overlapped_region_launch, retry_and_late, region2_launch; issued and cleared by prep_flush_on
@@ -262,7 +262,7 @@ struct LevelRun {
             // lean: children and their parent slots are sized by the bound n (n_c - k) and written without waiting for the count
             const double child_bound_bytes = (double)nn * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
             children_lean = child_bound_bytes <= 1.5e9;
-            { int rcs = launch_scan(h, h->count.as<int32_t>(), h->offset.as<int32_t>(), n, children_lean ? dcnt + 20 : total); if (rcs) return rcs; }
+            { int rcs = launch_scan(h, h->count.as<int32_t>(), h->offset.as<int32_t>(), n, children_lean ? dcnt + DC_CHILDREN : total); if (rcs) return rcs; }
             HIP_TRY(h, hipGetLastError());
             int32_t n_children = 0;
             if (children_lean) n_children = (int32_t)std::min<double>((double)nn * std::max(h->n_c - k, 1), 2147483647.0 / (k + 2));   // the bound, for the allocation only
@@ -282,7 +282,7 @@ struct LevelRun {
         HIP_TRY(h, hipGetLastError());
         if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[3], st));
         hipLaunchKernelGGL(k_publish_words2, dim3(1), dim3(128), 0, st, reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4),
-                           reinterpret_cast<const unsigned int *>(dcnt), 32, reinterpret_cast<unsigned int *>(h->tot_dev + 16));
+                           reinterpret_cast<const unsigned int *>(dcnt), DCNT_WORDS, reinterpret_cast<unsigned int *>(h->tot_dev + 16));
         HIP_TRY(h, hipGetLastError());
         return MPC_OK;
     }
@@ -296,7 +296,7 @@ struct LevelRun {
     }
 
     // The (x,theta) stage of a level that keeps dictionaries, in its one-step-plan form, needs no count from the host: its lists
-    // come from the partition below, their lengths stay in device memory (dcnt[28..31]), its launches are sized by the bound n.
+    // come from the partition below, their lengths stay in device memory (DC_XFIRST_CLASS and the three words behind it), its launches are sized by the bound n.
     // Round 5 (`x_first`): it is queued BEHIND THE PARTITION AT ONCE, and only then does the host wait for the counts that size
     // the region stage -- until then the stage waited ~0.1 ms per large level for that read-back and the region launch's host work
     // (tools/timeline.sh: 110 us between the partition and the plan pass on level 4 of config 4).
@@ -309,8 +309,8 @@ struct LevelRun {
         HIP_TRY(h, h->x1_buf.ensure((6 * nn + 16) * sizeof(int32_t), st));
         int32_t *xb = h->x1_buf.as<int32_t>();
         XqPlan pl{};
-        pl.plan_slot = xb; pl.plan_step = xb + nn; pl.x1_list = xb + 2 * nn; pl.x1_n = dcnt + 12;
-        for (int sg = 0; sg < 3; ++sg) { pl.rest[sg] = xb + (3 + sg) * nn; pl.rest_n[sg] = dcnt + 13 + sg; }
+        pl.plan_slot = xb; pl.plan_step = xb + nn; pl.x1_list = xb + 2 * nn; pl.x1_n = dcnt + DC_X1;
+        for (int sg = 0; sg < 3; ++sg) { pl.rest[sg] = xb + (3 + sg) * nn; pl.rest_n[sg] = dcnt + DC_X1_REST + sg; }
         pl.pre1 = dc.pre1; pl.n_pre1 = dc.n_pre1; pl.pre2 = dc.pre2; pl.n_pre2 = dc.n_pre2;
         pl.n_pre1_dev = n_pre1_dev; pl.n_pre2_dev = n_pre2_dev;
         XqAlt alt{};
@@ -361,7 +361,7 @@ struct LevelRun {
         const long long wpc = std::max<long long>(std::min<long long>(4, h->kn.x2_wpc), std::min<long long>(h->kn.x2_wpc, n_all / ((long long)h->kn.x2_div * h->n_cu)));
         const long long grid_x = (long long)h->n_cu * wpc;
         d.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_all / (grid_x * 8)));
-        if (xq_lean) { d.n_list_dev = dcnt + 8; d.chunk = 0; }   // length of `ls` and chunk rule on the device
+        if (xq_lean) { d.n_list_dev = dcnt + DC_OPEN_QT; d.chunk = 0; }   // length of `ls` and chunk rule on the device
         launch_x2(h->fast_x, dim3((unsigned)std::min<long long>(xq_lean ? n_all : (n_all + d.chunk - 1) / d.chunk, grid_x)), st, pf, fr, k, ls, n_items, stp, ctr, d);
         HIP_TRY(h, hipGetLastError());
         return MPC_OK;
@@ -380,13 +380,13 @@ struct LevelRun {
         // Lean form of a large level (round 3): the classic sequence read a list length back after almost every stage -- 22 idle gaps of
         // 15-30 us per solve of config 4 (tools/gpu_idle.sh).  The host needs only the lengths that size the region stage (one
         // read-back after the theta stage) and the final statistics; the theta LP, the (x,theta) stage after the quick test and the
-        // child generation take theirs from device memory (dcnt: [0] theta list, [8] open after the quick test, [20] children) and are
+        // child generation take theirs from device memory (dcnt: DC_THETA, DC_OPEN_QT, DC_CHILDREN) and are
         // launched for the bound the host does know.
-        HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
+        HIP_TRY(h, h->dcnt.ensure(DCNT_BYTES, st));
         {   // counters and list lengths cleared by one launch (a hipMemsetAsync costs the host ~16 us, a launch ~3 us)
             ZeroBufs z{};
             z.p[0] = h->ctr.p; z.bytes[0] = sizeof(LevelCounters);
-            z.p[1] = h->dcnt.p; z.bytes[1] = 32 * sizeof(int32_t);
+            z.p[1] = h->dcnt.p; z.bytes[1] = DCNT_BYTES;
             hipLaunchKernelGGL(k_zero_bufs, dim3(1), dim3(256), 0, st, z);
             HIP_TRY(h, hipGetLastError());
         }
@@ -433,8 +433,8 @@ struct LevelRun {
             if (kkt_lists) {
                 HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
                 HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
-                ta.kt_list = h->theta_list.as<int32_t>(); ta.kt_n = dcnt + 0;
-                ta.kx_list = h->xq_list.as<int32_t>(); ta.kx_n = dcnt + 10;
+                ta.kt_list = h->theta_list.as<int32_t>(); ta.kt_n = dcnt + DC_THETA;
+                ta.kx_list = h->xq_list.as<int32_t>(); ta.kx_n = dcnt + DC_KX;
             }
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[6], st));
             launch_kkt_thread(kd, h->fast_t, spread, g, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, ta, ctr);
@@ -443,7 +443,7 @@ struct LevelRun {
             HIP_TRY(h, hipGetLastError());
             if (kkt_lists) kkt_listed = true;
             else {
-                { int rcs = compact(ST_TODO, ST_TODO, nullptr, dcnt + 0); if (rcs) return rcs; }
+                { int rcs = compact(ST_TODO, ST_TODO, nullptr, dcnt + DC_THETA); if (rcs) return rcs; }
                 HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
                 std::swap(h->theta_list, h->retry_list);   // compact() filled retry_list; keep it as the theta list
             }
@@ -471,8 +471,8 @@ struct LevelRun {
             const int nxc_e = dict_nxc(h);
             const long long sd_e = (long long)nxc_e * h->Pf.n_d0r, si_e = dict_ints(h->Pf.n_d0r, nxc_e, h->n_c);
             if (!dict_will_store(h, nn, gen_children)) {
-                if (!kkt_listed) {      // (else k_kkt_thread has listed them in xq_list, length in dcnt[10])
-                    { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 10); if (rcs) return rcs; }
+                if (!kkt_listed) {      // (else k_kkt_thread has listed them in xq_list, length in DC_KX)
+                    { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + DC_KX); if (rcs) return rcs; }
                     HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
                     std::swap(h->xq_list, h->retry_list);
                 }
@@ -480,7 +480,7 @@ struct LevelRun {
                 dq.stride_d = sd_e; dq.stride_i = si_e;
                 dq.parent_slot = h->parent_slot.as<int32_t>();
                 dq.prev_d = h->dict_d[1 - h->dict_cur].as<double>(); dq.prev_i = h->dict_i[1 - h->dict_cur].as<int32_t>();
-                dq.n_list_dev = dcnt + 10;
+                dq.n_list_dev = dcnt + DC_KX;
                 XqAlt alt{};
                 if (h->kn.xq_thread >= 2 || h->kn.xq_thread < 0) alt = other_parents(h->kn.xq_thread < 0 ? MPC_MAX_NC : h->kn.xq_thread - 1);
                 HIP_TRY(h, hipEventRecord(h->ev_xfork, st));
@@ -503,7 +503,7 @@ struct LevelRun {
         if (n_theta > 0) {   // two-stage theta LP
             ThetaArgs ta = h->targs;
             ta.chunk = (int)std::max<long long>(1, std::min<long long>(16, n_theta / ((long long)h->grid_f * 8)));
-            if (theta_lean) { ta.n_dev = dcnt + 0; ta.chunk = 0; }   // length and chunk rule on the device
+            if (theta_lean) { ta.n_dev = dcnt + DC_THETA; ta.chunk = 0; }   // length and chunk rule on the device
             // wave slots the theta kernel takes (ThetaArgs::wave_div / wave_max): with the length on the device the kernel applies the
             // rule itself, here the host does
             long long grid_th = h->grid_f;
@@ -534,13 +534,13 @@ struct LevelRun {
         const bool x_first = !early_xq && h->storing && dc.parent_slot && h->kn.x1 > 0 && n >= std::max<long long>(h->kn.x1_min, h->kn.x_first_min) && n <= h->kn.x_first_max &&
                              n <= 0x7fffffffLL && !(flags & MPC_LEVEL_GRAPH);
         if (x_first) {
-            { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA, true, dcnt + 28); if (rcs) return rcs; }
-            hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned int *>(dcnt + 28), reinterpret_cast<unsigned int *>(h->tot_dev + 12), PART_CLASSES);
+            { int rcs = partition({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}, cntA, true, dcnt + DC_XFIRST_CLASS); if (rcs) return rcs; }
+            hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, st, reinterpret_cast<const unsigned int *>(dcnt + DC_XFIRST_CLASS), reinterpret_cast<unsigned int *>(h->tot_dev + 12), PART_CLASSES);
             HIP_TRY(h, hipGetLastError());
             HIP_TRY(h, hipEventRecord(h->ev_part, st));
             dc.pre1 = part_list(1); dc.pre2 = part_list(2);
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[2], st));
-            { int rcs = launch_plans(part_list(3), (int)n, n, dcnt + 31, dcnt + 29, dcnt + 30); if (rcs) return rcs; }
+            { int rcs = launch_plans(part_list(3), (int)n, n, dcnt + DC_XFIRST_OPEN, dcnt + DC_XFIRST_FEASIBLE, dcnt + DC_XFIRST_OPT); if (rcs) return rcs; }
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[3], st));
             kernel_timed[1] = true;
             x_done = true;
@@ -670,14 +670,14 @@ struct LevelRun {
                 if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[11], st));
                 HIP_TRY(h, hipGetLastError());
                 xq_thread_timed = true;
-                if (!use_grouped) { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 9); if (rcs) return rcs; xqt_lean = true; }   // (the grouped form sizes its group scan on the host)
+                if (!use_grouped) { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + DC_OPEN_XQT); if (rcs) return rcs; xqt_lean = true; }   // (the grouped form sizes its group scan on the host)
                 else { int32_t n_left = 0; int rcs = compact(ST_NEEDX, ST_NEEDX_SING, &n_left); if (rcs) return rcs; xq_n = n_left; }
                 HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
                 std::swap(h->xq_list, h->retry_list);   // compact() filled retry_list; keep it as the wavefront kernel's list
                 xq_list = h->xq_list.as<int32_t>();
             }
             dq.chunk = (int)std::max<long long>(1, std::min<long long>(16, xq_n / (grid_q * 4)));
-            if (xqt_lean) { dq.n_list_dev = dcnt + 9; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->kn.xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
+            if (xqt_lean) { dq.n_list_dev = dcnt + DC_OPEN_XQT; dq.chunk = 0; dq.skip_below = (h->fast_x & 1) ? 0 : h->kn.xq_skip_below; }   // length and chunk rule on the device; a short list is left to k_x2
             const dim3 gg((unsigned)std::max<long long>(1, std::min<long long>(xqt_lean ? (long long)xq_n : ((long long)xq_n + dq.chunk - 1) / dq.chunk, grid_q)));
             // Grouped by parent when a parent has many open children (config 3: 12.6 per parent, -0.5 ms; config 4: 7.1 per
             // parent, where the per-candidate reads of k_xq are cheaper than one 16 KB copy per parent, +0.45 ms): threshold 10.
@@ -702,7 +702,7 @@ struct LevelRun {
             if (h->timing) HIP_TRY(h, hipEventRecord(h->kev[9], st));
             kernel_timed[4] = true;
             HIP_TRY(h, hipGetLastError());
-            { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + 8); if (rcs) return rcs; }
+            { int rcs = compact(ST_NEEDX, ST_NEEDX_SING, nullptr, dcnt + DC_OPEN_QT); if (rcs) return rcs; }
             xq_lean = true;   // n_needx stays the bound (everything the quick test was given)
             needx_list = h->retry_list.as<int32_t>();
         }
@@ -881,9 +881,9 @@ struct LevelRun {
         h->r3_dirty = false;   // the main stream waited for ev_rjoin before the second partition
         std::memcpy(&host_ctr, h->tot_host + 16, sizeof(LevelCounters));
         const int32_t *cnt_host = h->cnt_host();
-        if (children_lean) h->n_children = cnt_host[20];
-        if (theta_lean) n_theta_items = cnt_host[0];
-        if (xq_lean) n_x_items = (long long)cnt_host[8] + (n_x_items - n_xq_items);   // what the quick test left + the dictionary-only items
+        if (children_lean) h->n_children = cnt_host[DC_CHILDREN];
+        if (theta_lean) n_theta_items = cnt_host[DC_THETA];
+        if (xq_lean) n_x_items = (long long)cnt_host[DC_OPEN_QT] + (n_x_items - n_xq_items);   // what the quick test left + the dictionary-only items
         if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
         if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[1], h->ev[1], h->ev[2]));
         if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]));
@@ -891,8 +891,8 @@ struct LevelRun {
         if ((xq_thread_timed) && h->timing) { HIP_TRY(h, hipEventElapsedTime(&h->ms_xq_thread, h->kev[10], h->kev[11])); h->n_xq_thread = host_ctr.xq_thread; }
         h->ms_x1 = 0;
         if ((x1_ran) && h->timing) HIP_TRY(h, hipEventElapsedTime(&h->ms_x1, h->kev[12], h->kev[13]));
-        h->n_x1 = x1_ran ? (long long)cnt_host[12] : 0;   // dictionaries k_x1 wrote
-        if (h->kn.debug_cycles && x1_ran) { const int32_t *ch = cnt_host; std::fprintf(stderr, "[mpc] k=%d one-step plans: %d streamed by k_x1, %d + %d + %d left to k_x2 (plan pass %.3f ms)\n", k, ch[12], ch[13], ch[14], ch[15], h->ms_xq_thread); }
+        h->n_x1 = x1_ran ? (long long)cnt_host[DC_X1] : 0;   // dictionaries k_x1 wrote
+        if (h->kn.debug_cycles && x1_ran) { const int32_t *ch = cnt_host; std::fprintf(stderr, "[mpc] k=%d one-step plans: %d streamed by k_x1, %d + %d + %d left to k_x2 (plan pass %.3f ms)\n", k, ch[DC_X1], ch[DC_X1_REST], ch[DC_X1_REST + 1], ch[DC_X1_REST + 2], h->ms_xq_thread); }
         if (xq_early_ran) { n_xq_items += host_ctr.xq_thread; h->n_needx += host_ctr.xq_thread; }   // what the pass beside the theta stage decided never reached the partition's count
         if (kernel_timed[2] && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)   // k_region2 times itself (see the kernel)
             kms[2] = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);

@@ -1,5 +1,5 @@
 // mpcombi_hip.hip -- the level engine behind the C ABI (include/mpcombi.h): mpc_handle and everything that needs it, over the
-// gfx950 kernels in kernels.hpp / kernels2.hpp; the stages of a large level's host path are level_classic.hpp, those of handle creation create.hpp, the environment knobs knobs.hpp.  The stateless geometry entry points (hit-and-run, slices, point location, search
+// gfx950 kernels in kernels.hpp / kernels2.hpp; the stages of a large level's host path are level_classic.hpp, those of a level without host round trips (and its batch member) level_small.hpp, those of handle creation create.hpp, the environment knobs knobs.hpp.  The stateless geometry entry points (hit-and-run, slices, point location, search
 // trees, closed loop, vertices, merging) are geometry.hip; the LPs, QPs and MIQPs solved at fixed points are points.hip.
 //
 // Build:  one object per translation unit (this file, geometry.hip, points.hip, batch_level.hip, setup_mfma.hip), linked into
@@ -250,7 +250,7 @@ struct mpc_handle {
     // for the duration of the level (two sets by parity of depth: the next level's launch is queued before this one is closed).
     struct RegionDefer {
         DevBuf kkt_code, kkt_L, part_lists, headd, headi, epool, kept_g, done_g;
-        DevBuf dcnt;                 // the level's 32 list lengths (k_region2 reads [6] when each workgroup starts), behind them the launch's own LevelCounters
+        DevBuf dcnt;                 // the level's DCNT_WORDS list lengths (k_region2 reads DC_OPT when each workgroup starts), behind them the launch's own LevelCounters
         hipEvent_t ev_go = nullptr, ev_done = nullptr;   // recorded behind the theta-stage partition (main stream) / behind the launch's publish (stream3)
         bool pending = false;        // launched and not closed
         bool joined = false;         // the next level's children stage (it overwrites the frontier the launch reads) waits for ev_done
@@ -261,10 +261,10 @@ struct mpc_handle {
     int defer_mode = 1;              // mpc_set_region_overlap: 0 never, 1 where a level allows it, 2 (tests): ... and the first close on this handle reports a miss
     bool defer_off = false;          // a deferred region missed on this handle: never again (as no_small_fuse for doubtful candidates)
     bool defer_miss_forced = false;   // (what a level did is in its statistics: mpc_level_stats::region_side_stream 2 / 3)
-    static constexpr size_t DEFER_DCNT_BYTES = 32 * sizeof(int32_t) + sizeof(LevelCounters);
+    static constexpr size_t DEFER_DCNT_BYTES = DCNT_BYTES + sizeof(LevelCounters);
     static constexpr int DEFER_PUB_WORDS = (int)(sizeof(LevelCounters) / 4) + 9;   // k_defer_publish: counters, eight verdict counts, the slots
     // where set i's k_defer_publish writes, in the pinned counter block (cnt_host() below: the level's own words end before byte 1024)
-    static_assert(64 + sizeof(LevelCounters) + 32 * 4 <= 1024 && DEFER_PUB_WORDS * 4 <= 512 && 1024 + 2 * 512 <= 4096, "the pinned block holds both sets' publishes");
+    static_assert(64 + sizeof(LevelCounters) + DCNT_BYTES <= 1024 && DEFER_PUB_WORDS * 4 <= 512 && 1024 + 2 * 512 <= 4096, "the pinned block holds both sets' publishes");
     const unsigned int *defer_pub_host(int i) const { return reinterpret_cast<const unsigned int *>(reinterpret_cast<const char *>(tot_host) + 1024 + 512 * i); }
     unsigned int *defer_pub_dev(int i) const { return reinterpret_cast<unsigned int *>(reinterpret_cast<char *>(tot_dev) + 1024 + 512 * i); }
     bool defer_pending() const { return rdefer[0].pending || rdefer[1].pending; }
@@ -323,9 +323,9 @@ struct mpc_handle {
     long long rec_d = 0, rec_i = 0;
     // frontier / pruned
     int32_t *tot_host = nullptr, *tot_dev = nullptr;   // 16 counters in pinned host memory that the kernels write directly: list lengths need no copy
-    // behind them the closing publish of a level leaves its LevelCounters, and behind those its 32 list lengths (dcnt): these, on the host
+    // behind them the closing publish of a level leaves its LevelCounters, and behind those its DCNT_WORDS list lengths (dcnt, words named by DcntWord): these, on the host
     int32_t *cnt_host() const {
-        static_assert(sizeof(LevelCounters) % 4 == 0 && sizeof(LevelCounters) + 64 + 32 * 4 <= 4096, "LevelCounters + list lengths must fit the pinned block");
+        static_assert(sizeof(LevelCounters) % 4 == 0 && sizeof(LevelCounters) + 64 + DCNT_BYTES <= 4096, "LevelCounters + list lengths must fit the pinned block");
         return tot_host + 16 + (int)(sizeof(LevelCounters) / 4);
     }
     const int32_t *opt_ptr = nullptr;                  // list of the optimal candidates of the level (a view, not a copy)
@@ -846,20 +846,8 @@ static void stream_release(mpc_handle *h) {   // blocks of a streamed level nobo
     h->so = mpc_handle::StreamOut();
 }
 
-
-// ---- a level without host round trips ---------------------------------------------------------------------------------------
-// The classic path below reads a list length back after almost every stage (to size the next launch): six synchronisations and
-// ~25 dependent launches per level, 0.3-0.45 ms whatever the level computes -- the fixed cost of the first levels of every
-// program, of all of config 2 and of the sub-programs of the mixed-integer enumeration.  Here every list length stays in device
-// memory (h->dcnt; the kernels read it there: ThetaArgs::n_dev, DictCache::n_*_dev, RegionStream::n_opt_dev, k_verdict's n_dev),
-// launches are sized by the one bound the host knows -- the number of candidates of the level --, buffers by the same bound,
-// and the host synchronises ONCE, at the end.  Same kernels, same lists (the single-block compaction / partition kernels keep
-// the candidate order), same decisions.  The rare stages whose buffers cannot be bounded cheaply -- the LDS-engine region kernel
-// for candidates k_region2 gives up on -- are not part of it: if the level turns out to need them, it is repeated on the
-// classic path (deterministic, so the repeat computes the same thing).
-// dcnt layout (int32): [0] theta list | [12] doubtful after the theta stage | [4..7] classes after their re-solve: -, feasible,
-// optimal (= the region launch), open | [8] open after the quick test | [24] doubtful after the (x,theta) stage | [17] optimal
-// candidates that missed the region launch | [20] children
+// ---- what the three forms of a level (no round trips: level_small.hpp, its batch member, classic: level_classic.hpp) share besides their
+// kernels (level_launch.hpp) and the names of their list lengths (DcntWord, batch_level.hpp) ------------------------------------------------
 // Largest number of inequality rows k_kkt_thread solves for (one thread per candidate, everything in registers).  Round 6: 8 -> 10 -- the
 // K = 9, 10 instantiations keep their k x k system and the k x (n_theta + 1) multipliers in 234-256 VGPRs (+ up to 108 AGPRs as spill space,
 // one wavefront per SIMD at n_theta > 4) and still beat the wavefront-wide LDS solve inside k_theta2 several times over; K = 12
@@ -873,53 +861,6 @@ static int x1_join(mpc_handle *h) {
     h->x1_pending = false;
     return MPC_OK;
 }
-// ---- the region stage of a small level beside the next level (mpc_handle::RegionDefer) ---------------------------------------------
-// the set's buffers <-> the handle's: in at the start of a deferring level (every launch of the level then takes them as it always
-// took the handle's), out before its closing synchronisation (the next level works in the handle's own again)
-static void defer_swap(mpc_handle *h, mpc_handle::RegionDefer &d) {
-    std::swap(h->kkt_code, d.kkt_code); std::swap(h->kkt_L, d.kkt_L); std::swap(h->part_lists, d.part_lists); std::swap(h->headd, d.headd); std::swap(h->headi, d.headi);
-    std::swap(h->epool, d.epool); std::swap(h->kept_g, d.kept_g); std::swap(h->done_g, d.done_g); std::swap(h->dcnt, d.dcnt);
-}
-// Called by a level before its k_children_write: the launch of the level BEFORE reads that level's frontier, which has been this level's
-// children buffer since the hand-over.  A stream wait; the launch ended long ago (it was queued a whole level earlier).
-static int defer_join(mpc_handle *h, hipStream_t st) {
-    for (auto &d : h->rdefer)
-        if (d.pending && !d.joined && d.depth != h->sv_cur) { HIP_TRY(h, hipStreamWaitEvent(st, d.ev_done, 0)); d.joined = true; }
-    return MPC_OK;
-}
-// launches that will not be closed (the level is repeated, the solve abandoned or failed): waited for, their records dropped
-static void defer_drain(mpc_handle *h) {
-    if (!h->defer_pending()) return;
-    (void)hipStreamSynchronize(h->stream3);
-    for (auto &d : h->rdefer) d.pending = false;
-}
-static bool small_path_ok(const mpc_handle *h, long long n, int k, int32_t flags, int32_t gen_children) {
-    if (h->kn.no_smallpath || !h->fast || h->kn.force_v1 || h->fast_r < 0 || n < 1 || n > h->kn.smallpath_max) return false;
-    if (flags & MPC_LEVEL_GRAPH) return false;
-    if (h->kn.test_late > 0 || h->kn.debug_cycles) return false;
-    // children and their parent slots are sized by the bound n (n_c - k) candidates of k + 1 indices
-    const double child_bytes = (double)n * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
-    if (gen_children && child_bytes > 512e6) return false;
-    const long long rows_t = h->n_c - h->n_eq + h->n_tc;
-    const double rec_bytes = (double)n * ((double)(h->n_x * h->n_t + h->n_x + k * h->n_t + k) * 8.0 + (double)(8 + 2 * k + h->n_tc + 2 * (h->n_c - k)) * 4.0 +
-                                          (double)rows_t * (h->n_t + 1) * 8.0);
-    return rec_bytes <= 2e9;
-}
-
-// MPC_DEBUG_SMALL=1: at exit, how many no-round-trip levels had doubtful candidates (re-solved in place by the LDS engine) in their two verdict stages
-static std::atomic<long long> g_small_levels{0}, g_small_retry_theta{0}, g_small_retry_x{0}, g_small_retry_cands{0}, g_small_repeats{0}, g_small_repeats_doubtful{0};
-static void small_debug_note(const int32_t *cnt_host) {
-    static const bool on = [] {
-        if (knob_process("MPC_DEBUG_SMALL") == 0.0) return false;
-        std::atexit([] { std::fprintf(stderr, "[mpc] small levels %lld: with doubtful candidates after the theta stage %lld, after the (x,theta) stage %lld (candidates %lld); repeated on the classic path %lld (because of doubtful candidates %lld)\n",
-                                      g_small_levels.load(), g_small_retry_theta.load(), g_small_retry_x.load(), g_small_retry_cands.load(), g_small_repeats.load(), g_small_repeats_doubtful.load()); });
-        return true;
-    }();
-    if (!on) return;
-    g_small_levels++; g_small_retry_theta += (cnt_host[12] + cnt_host[4]) > 0; g_small_retry_x += cnt_host[24] > 0; g_small_retry_cands += cnt_host[12] + cnt_host[4] + cnt_host[24];
-}
-
-// ---- what the three forms of a level (no round trips, batch member, classic) share besides their kernels (level_launch.hpp) ---------
 // shape of the level's region records (doubles / ints per slot) and the region stage's per-level state
 static void level_record_shape(mpc_handle *h, int k) {
     h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
@@ -979,434 +920,8 @@ static void level_stats_common(const mpc_handle *h, const LevelCounters &host_ct
     stats->xq_record_ints = dict_ints_head(h->Pf.n_d0r, dict_nxc(h)) - 1; stats->xq_record_rows = h->Pf.n_d0r; stats->xq_record_cols = h->Pf.n_d0c + 1;
 }
 
-// ... and what the two forms without host round trips add alike: the work-item counts from the published list lengths (dcnt layout below),
-// k_region2's own wall-clock time, the dictionary traffic
-static void level_stats_small(const mpc_handle *h, const LevelCounters &host_ctr, const int32_t *cnt_host, bool kkt, bool quick_test, mpc_level_stats *stats) {
-    level_stats_common(h, host_ctr, stats);
-    stats->n_xtheta_lp = h->n_needx;
-    stats->n_theta_items = kkt ? cnt_host[0] : h->n;
-    if (h->n_opt > 0 && host_ctr.r2_t1 > ~host_ctr.r2_not_t0 && h->wall_khz > 0)   // k_region2 times itself on the wall clock
-        stats->ms_region2 = (float)((double)(host_ctr.r2_t1 - ~host_ctr.r2_not_t0) / (double)h->wall_khz);
-    stats->n_xq_items = quick_test ? cnt_host[7] : 0;
-    stats->n_x_items = (quick_test ? cnt_host[8] : cnt_host[7]) + (h->storing ? (long long)cnt_host[5] + cnt_host[6] : 0);
-    stats->dict_read_bytes = (h->have_prev_dict && h->have_parent_slot) ? dict_record_bytes(h) : 0;
-    stats->dict_write_bytes = h->storing ? dict_record_bytes(h) : 0;
-}
-
-// ---- the buffer set-up the two forms without host round trips share (level_run_small; batch_prepare for a member of the shared launches).
-// Three pieces, not one: level_run_small queues launches between them, and each piece stands where its lines stood, so that no ensure
-// call has moved past a launch on the member's stream.
-// region stage: one slot per optimal candidate (class 2 of the partition behind the theta stage), buffers sized by the bound nn
-static int small_region_slots(mpc_handle *h, size_t nn, hipStream_t st, int &ldk) {
-    h->opt_ptr = h->part_lists.as<int32_t>() + 2 * nn;
-    const int rows_t_ = h->n_c - h->n_eq + h->n_tc;
-    HIP_TRY(h, h->headd.ensure(nn * h->fd * sizeof(double), st));
-    HIP_TRY(h, h->headi.ensure(nn * h->fi * sizeof(int32_t), st));
-    HIP_TRY(h, h->epool.ensure(nn * rows_t_ * (h->n_t + 1) * sizeof(double), st));
-    ldk = (rows_t_ + 1 + 63) & ~63;
-    HIP_TRY(h, h->kept_g.ensure(nn * ldk, st));
-    HIP_TRY(h, h->done_g.ensure(nn * 2 * sizeof(unsigned int), st));
-    h->used_region2 = true;
-    return MPC_OK;
-}
-// (x,theta) stage: the dictionary cache; on a storing level the candidates the theta stage decided (classes 1 and 2, lengths in dcnt[5], [6])
-// ride in front of the open ones
-static int small_dict_cache(mpc_handle *h, size_t nn, int32_t gen_children, hipStream_t st, int32_t *dcnt, DictCache &dc) {
-    { int rcd = dict_cache_begin(h, nn, gen_children, st, dc); if (rcd) return rcd; }
-    if (h->storing) {
-        dc.pre1 = h->part_lists.as<int32_t>() + 1 * nn; dc.n_pre1_dev = dcnt + 5;
-        dc.pre2 = h->part_lists.as<int32_t>() + 2 * nn; dc.n_pre2_dev = dcnt + 6;
-    }
-    dc.chunk = 1;
-    return MPC_OK;
-}
-// children stage: masks, counts, offsets, and children with their parent slots by the bound nn (n_c - k)
-static int small_children_buffers(mpc_handle *h, size_t nn, int k, hipStream_t st) {
-    HIP_TRY(h, h->childmask.ensure(nn * h->mw * sizeof(uint64_t), st));
-    HIP_TRY(h, h->count.ensure(nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->offset.ensure(nn * sizeof(int32_t), st));
-    const size_t child_bound = nn * (size_t)std::max(h->n_c - k, 1);
-    HIP_TRY(h, h->children.ensure(child_bound * (k + 1) * sizeof(int32_t), st));
-    HIP_TRY(h, h->parent_slot_next.ensure(child_bound * sizeof(int32_t), st));
-    return MPC_OK;
-}
-
-static int level_run_small(mpc_handle *h, int32_t gen_children, int32_t flags, mpc_level_stats *stats, bool *fallback) {
-    *fallback = false;
-    { int rcj = x1_join(h); if (rcj) return rcj; }
-    const long long n = h->n;
-    const int k = h->k;
-    const size_t nn = (size_t)n;
-    hipStream_t st = h->stream;
-    h->n_opt = h->n_children = h->n_pruned_new = h->n_regions = 0;
-    h->n_needx = 0;
-    // (the level's form is known before its first launch: `fused`, and whether it ends with the quick test -- small_dict_cache below decides the same)
-    const bool fused = !h->theta_open && !h->kn.no_small_fuse;
-    const bool will_store = dict_will_store(h, nn, gen_children);
-    // The region stage beside the NEXT level (mpc_handle::RegionDefer): inside mpc_solve_start's loop, on a level with children in the fused
-    // form that does not end with the quick test; not under a profile (per-stage events in line, as for the deferred k_x1), not where the next
-    // level's launches depend on this level's number of regions (MPC_XQ_EARLY_REGIONS).
-    mpc_handle::RegionDefer *df = nullptr;
-    if (h->sv_cur >= 0 && h->defer_mode > 0 && !h->defer_off && !h->kn.no_roverlap && gen_children && fused && !h->timing && h->kn.xq_early_regions == 0 &&
-        (will_store || !(h->have_prev_dict && h->have_parent_slot))) {
-        df = &h->rdefer[h->sv_cur & 1];
-        if (df->pending) return fail(h, MPC_ERR_STATE, "level_run_small: the deferred region launch of two levels ago has not been closed");
-        defer_swap(h, *df);
-    }
-    HIP_TRY(h, h->status.ensure(nn, st));
-    HIP_TRY(h, h->pruned.ensure((size_t)(h->n_pruned + n) * h->mw * sizeof(uint64_t), st, true));   // the level's newly pruned masks go behind the list
-    HIP_TRY(h, h->retry_list.ensure(nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->part_lists.ensure((size_t)PART_CLASSES * nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->dcnt.ensure(mpc_handle::DEFER_DCNT_BYTES, st));
-    {
-        // counters, list lengths, the region kernel's completion flags and the "dictionary stored" flags: cleared by one launch
-        HIP_TRY(h, h->done_g.ensure(nn * 2 * sizeof(unsigned int), st));
-        if (will_store) HIP_TRY(h, h->dict_stored[h->dict_cur].ensure(nn, st));
-        ZeroBufs z{};
-        z.p[0] = h->ctr.p; z.bytes[0] = sizeof(LevelCounters);
-        z.p[1] = h->dcnt.p; z.bytes[1] = df ? mpc_handle::DEFER_DCNT_BYTES : 32 * sizeof(int32_t);   // (a deferred launch counts in its own LevelCounters, behind the list lengths)
-        z.p[2] = h->done_g.p; z.bytes[2] = nn * 2 * sizeof(unsigned int);
-        if (will_store) { z.p[3] = h->dict_stored[h->dict_cur].p; z.bytes[3] = nn; }
-        hipLaunchKernelGGL(k_zero_bufs, dim3((unsigned)std::min<size_t>(64, (nn * 8 + 2047) / 2048 + 1)), dim3(256), 0, st, z);
-    }
-    LevelCounters *ctr = h->ctr.as<LevelCounters>();
-    int32_t *dcnt = h->dcnt.as<int32_t>();
-    const int32_t *fr = h->frontier.as<int32_t>();
-    uint8_t *stp = h->status.as<uint8_t>();
-    const DevProblem *pf = h->pf_dev.as<DevProblem>();
-    auto part_list = [&](int c) -> int32_t * { return h->part_lists.as<int32_t>() + (size_t)c * nn; };
-    const int blocks256 = (int)((n + 255) / 256);
-    level_record_shape(h, k);
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[0], st));
-    // ---- KKT solves + box screen, theta stage ----------------------------------------------------------------------------------
-    const uint8_t *kkc = nullptr;
-    const double *kkl = nullptr;
-    const int32_t *theta_list = nullptr;
-    ThetaArgs ta = h->targs;
-    ta.chunk = 1;
-    const int kd = k - h->targs.ne;   // rows the one-thread KKT kernel solves for (the equality rows are eliminated)
-    if (h->kkt_mode == 0 && kd >= 1 && kd <= KKT_THREAD_MAX && !h->kn.no_kkt_thread) {
-        HIP_TRY(h, h->kkt_code.ensure(nn, st));
-        HIP_TRY(h, h->kkt_L.ensure(nn * (size_t)k * (h->n_t + 1) * sizeof(double), st));
-        kkc = h->kkt_code.as<uint8_t>(); kkl = h->kkt_L.as<double>();
-        ThetaArgs tk = h->targs;
-        // the kernel lists the candidates it leaves to the theta stage itself (one atomic per workgroup; a work list: its order changes nothing)
-        const bool kkt_lists = !h->kn.no_kkt_lists;
-        if (kkt_lists) {
-            HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
-            tk.kt_list = h->theta_list.as<int32_t>(); tk.kt_n = dcnt + 0;
-            tk.kx_list = h->xq_list.as<int32_t>(); tk.kx_n = dcnt + 10;
-        }
-        // KKT_SPREAD lanes per candidate while the active set is small (the kernel's comment): the level's 50 us floor becomes ~15
-        const bool spread = h->kn.kkt_spread > 0 && kd <= KKT_SPREAD_KMAX;
-        const dim3 g((unsigned)(spread ? (n * KKT_SPREAD + 255) / 256 : blocks256));
-        launch_kkt_thread(kd, h->fast_t, spread, g, st, pf, fr, n, h->kkt_code.as<uint8_t>(), h->kkt_L.as<double>(), stp, tk, ctr);
-        if (!kkt_lists) hipLaunchKernelGGL(k_compact_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, ST_TODO, ST_TODO, h->theta_list.as<int32_t>(), dcnt + 0);
-        theta_list = h->theta_list.as<int32_t>();
-        ta.n_dev = dcnt + 0;
-    }
-    launch_theta2(h->fast_t, dim3((unsigned)std::min<long long>(n, h->grid_f)), h->lds_f, st, pf, fr, n, k, stp, ctr, kkc, kkl, ta, theta_list);
-    // the doubtful candidates of the theta stage are re-solved in place by the LDS engine first (the classic path does this on a
-    // side stream under the (x,theta) stage), so that the partition below already knows every optimal candidate they yield
-    // Round 5 (`fused`): doubtful candidates are rare (numerically doubtful pivots of the register simplex), so the level does not spend
-    // three launches on them at each of its two verdict stages: ONE partition lists them as class 0 beside the classes below, the level
-    // goes on without them, and if there was one (counted in [4] / [24]) the host repeats the level on the classic path -- as it does for
-    // the other rare cases.  The end of the level is one launch (k_small_end) instead of five, the scan carries the publish.
-    if (!fused) {
-        hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 12);
-        hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 12);
-        // open parameter set: "optimal" only if the reference's max-t LP is bounded (k_recession), decided before the region launch below
-        if (h->theta_open) hipLaunchKernelGGL(k_recession, dim3((unsigned)std::min<long long>(n, 256)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp);
-    }
-    // classes after the theta stage: [1] feasible, [2] optimal, [3] feasibility open ([0] doubtful, fused form only)
-    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n,
-                       fused ? part_spec({{ST_RETRY, 0}, {ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}})
-                             : part_spec({{ST_FEASIBLE, 1}, {ST_OPT_PENDING, 2}, {ST_NEEDX, 3}, {ST_NEEDX_SING, 3}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 4);
-    HIP_TRY(h, hipGetLastError());
-    if (df) HIP_TRY(h, hipEventRecord(df->ev_go, st));   // everything the deferred region launch reads has been queued
-    // ---- region stage: one slot per optimal candidate, buffers sized by the bound.  It needs the theta stage's verdicts only; a
-    // candidate that turns out optimal only later -- a doubtful one of the (x,theta) stage, re-solved -- sends the level to the classic
-    // path.  (Measured: on its own stream beside the (x,theta) stage it gains nothing at this size -- the fork / join events cost what
-    // the overlap of two 50-100 us kernels saves: config 2 1.76 ms against 1.68 in line; round 4, config 4, whose regions take 150 us:
-    // 5.47 / 5.61 ms forked against 5.48 / 5.54 in line -- the region kernel itself is 0.185 instead of 0.158 ms beside k_x2.) -----------------------------------------------
-    SmallRX rx{};
-    unsigned grid_r = 1;
-    // a deferred launch counts in its own LevelCounters (the next level clears the handle's) and leaves status[] alone (the next level's by then)
-    LevelCounters *ctr_r = df ? reinterpret_cast<LevelCounters *>(h->dcnt.as<char>() + 32 * sizeof(int32_t)) : ctr;
-    {
-        int ldk = 0;
-        { int rcb = small_region_slots(h, nn, st, ldk); if (rcb) return rcb; }
-        RegionStream rs{};
-        rs.n_opt_dev = dcnt + 6;
-        rs.w_cap = h->grid_r2; rs.w_max = h->kn.rsplit_max;
-        const int W = h->kn.no_rsplit ? 1 : 0;   // 0: chosen in the kernel from the number of optimal candidates
-        grid_r = (unsigned)std::min<long long>(n * std::max(h->kn.rsplit_max, 1), h->grid_r2);
-        const DevProblem *pr = h->pr2_dev.as<DevProblem>();
-        const int nt_r = region2_nt(h->fast_r);
-        rx.pr = pr; rx.fr = h->frontier.as<int32_t>(); rx.k = k; rx.opt_list = h->opt_ptr; rx.n = (int)n; rx.status = df ? (uint8_t *)nullptr : h->status.as<uint8_t>();
-        rx.headd = h->headd.as<double>(); rx.headi = h->headi.as<int32_t>(); rx.fd = h->fd; rx.fi = h->fi; rx.epool = h->epool.as<double>(); rx.ctr = ctr_r;
-        rx.kkc = kkc; rx.kkl = kkl; rx.W = W; rx.kept_g = h->kept_g.as<uint8_t>(); rx.ldk = ldk; rx.done_g = h->done_g.as<unsigned int>();
-        rx.tvp_box = h->kn.no_rbox ? (const double *)nullptr : h->targs.tvp + (size_t)nt_r * nt_r + nt_r; rx.rs = rs;
-    }
-    // (the launch itself comes below: together with the (x,theta) kernel in one grid where an instantiation of the pair exists)
-    auto region2_alone = [&](hipStream_t rst) -> int {
-        launch_region2(h->fast_r, dim3(grid_r), h->lds_r2, rst, rx.pr, rx.fr, rx.k, rx.opt_list, rx.n, rx.status, rx.headd, rx.headi, rx.fd, rx.fi, rx.epool,
-                       rx.ctr, rx.kkc, rx.kkl, rx.W, rx.kept_g, rx.ldk, rx.done_g, rx.tvp_box, rx.rs);
-        HIP_TRY(h, hipGetLastError());
-        return MPC_OK;
-    };
-    if (!fused) HIP_TRY(h, hipMemsetAsync(&ctr->work_retry, 0, sizeof(unsigned int), st));
-    // ---- (x,theta) stage with the dictionary cache ---------------------------------------------------------------------------------
-    const int nxc = dict_nxc(h);
-    DictCache dc;
-    { int rcb = small_dict_cache(h, nn, gen_children, st, dcnt, dc); if (rcb) return rcb; }
-    const int32_t *needx_list = part_list(3);
-    const int32_t *needx_n = dcnt + 7;
-    const bool quick_test = !h->storing && dc.parent_slot;
-    bool merged_rx = false;
-    if (fused && !quick_test && !h->kn.no_small_rx && !df) {
-        // region kernel + (x,theta) kernel as ONE grid (batch_level.hpp, SmallRX): the two work on disjoint candidates
-        DictCache d = dc;
-        d.n_list_dev = needx_n;
-        rx.pf = pf; rx.list = needx_list; rx.dc = d;
-        hipError_t e_rx = hipSuccess;
-        merged_rx = small_region2_x2_launch(h->fast_r, h->fast_x, grid_r, (unsigned)std::min<long long>(n, (long long)h->n_cu * 16), h->lds_r2, st, rx, &e_rx);
-        if (merged_rx) HIP_TRY(h, e_rx);
-    }
-    if (df) {
-        // stream3, behind the partition's event: the main stream goes on with k_x2 and the end of the level and never waits for this
-        // launch inside the level.  Behind it, on the same stream, what the host needs to close the level goes to the pinned block.
-        HIP_TRY(h, hipStreamWaitEvent(h->stream3, df->ev_go, 0));
-        { int rcr = region2_alone(h->stream3); if (rcr) return rcr; }
-        hipLaunchKernelGGL(k_defer_publish, dim3(1), dim3(256), 0, h->stream3, rx.headi, rx.fi, rx.rs.n_opt_dev, reinterpret_cast<const unsigned int *>(ctr_r),
-                           (int)(sizeof(LevelCounters) / 4), h->defer_pub_dev(h->sv_cur & 1));
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(df->ev_done, h->stream3));
-        df->pending = true; df->joined = false; df->depth = h->sv_cur; df->k = k; df->fd = h->fd; df->fi = h->fi; df->n_opt = 0;
-        df->keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
-    } else if (!merged_rx) { int rcr = region2_alone(st); if (rcr) return rcr; }
-    if (quick_test) {   // last level: decisions only -- the quick test on a few vectors of the parent's dictionary first
-        DictCache dq = dc;
-        dq.n_list_dev = needx_n;
-        const dim3 gg((unsigned)std::min<long long>(n, (long long)h->n_cu * 32));
-        launch_xq(h->fast_x, gg, st, pf, fr, k, needx_list, (int)n, stp, ctr, dq, nxc);
-        hipLaunchKernelGGL(k_compact_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, ST_NEEDX, ST_NEEDX_SING, h->retry_list.as<int32_t>(), dcnt + 8);
-        needx_list = h->retry_list.as<int32_t>();
-        needx_n = dcnt + 8;
-    }
-    if (!merged_rx) {
-        DictCache d = dc;
-        d.n_list_dev = needx_n;
-        // bound of the work items: every candidate once (open, or decided and expanded for its dictionary)
-        launch_x2(h->fast_x, dim3((unsigned)std::min<long long>(n, (long long)h->n_cu * 16)), st, pf, fr, k, needx_list, (int)n, stp, ctr, d);
-    }
-    HIP_TRY(h, hipGetLastError());
-    const int keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
-    unsigned int *pub_dst = reinterpret_cast<unsigned int *>(h->tot_dev + 16);
-    if (fused) {
-        // doubtful candidates of the (x,theta) stage -> [24], optimal ones that missed the region launch -> [17], status histogram,
-        // pruned masks (and, on a level without children, the publish): one launch
-        if (h->timing) { HIP_TRY(h, hipEventRecord(h->ev[1], st)); HIP_TRY(h, hipEventRecord(h->ev[2], st)); }
-        unsigned long long *pout = h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw;
-        launch_small_end(h->mw, st, fr, (int)n, k, stp, pout, ctr, keep_lowdim, dcnt + 24, dcnt + 17, reinterpret_cast<const unsigned int *>(dcnt), 32,
-                         gen_children ? (unsigned int *)nullptr : pub_dst);
-        HIP_TRY(h, hipGetLastError());
-    } else {
-    // doubtful candidates of the (x,theta) stage (rare): re-solved in place as well
-    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_RETRY, 0}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 24);
-    hipLaunchKernelGGL(k_verdict, dim3((unsigned)std::min<long long>(n, 128)), dim3(64), h->lds_v, st, h->Pv, fr, n, k, stp, ctr, part_list(0), dcnt + 24);
-    HIP_TRY(h, hipGetLastError());
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[1], st));
-    // a candidate that is still "optimal, region pending" now was not in the region launch: counted in [17]
-    hipLaunchKernelGGL(k_partition_small, dim3(1), dim3(1024), 0, st, h->status.as<uint8_t>(), (int)n, part_spec({{ST_OPT_PENDING, 1}}), h->part_lists.as<int32_t>(), (long long)n, dcnt + 16);
-    HIP_TRY(h, hipGetLastError());
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[2], st));
-    // ---- pruned masks of this level + children -------------------------------------------------------------------------------------
-    launch_pruned_append(h->mw, dim3(blocks256), st, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                         h->pruned.as<unsigned long long>() + (size_t)h->n_pruned * h->mw, ctr, keep_lowdim);
-    }
-    if (gen_children) {
-        { int rcb = small_children_buffers(h, nn, k, st); if (rcb) return rcb; }
-        // (deferred region launch: the optimal candidates are still "region pending" here and expand as if they had their regions)
-        launch_children_count(h->mw, dim3((unsigned)n), st, h->Pv, h->frontier.as<int32_t>(), n, k, h->status.as<uint8_t>(),
-                              h->pruned.as<unsigned long long>(), (long long)h->n_pruned, h->childmask.as<unsigned long long>(), h->count.as<int32_t>(),
-                              keep_lowdim | (df ? EXPAND_PENDING : 0));
-        if (fused) hipLaunchKernelGGL(k_scan_publish, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20,
-                                      reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4), reinterpret_cast<const unsigned int *>(dcnt), 32, pub_dst);
-        else hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(SCAN_BLOCK), 0, st, h->count.as<int32_t>(), h->offset.as<int32_t>(), (int)n, dcnt + 20);
-        { int rcj = defer_join(h, st); if (rcj) return rcj; }   // the children buffer is the frontier the previous level's deferred region launch reads
-        hipLaunchKernelGGL(k_children_write, dim3((unsigned)n), dim3(64), 0, st, h->frontier.as<int32_t>(), n, k, h->mw,
-                           h->childmask.as<unsigned long long>(), h->offset.as<int32_t>(), h->children.as<int32_t>(),
-                           h->storing ? h->dict_stored[h->dict_cur].as<uint8_t>() : (const uint8_t *)nullptr, h->parent_slot_next.as<int32_t>());
-        HIP_TRY(h, hipGetLastError());
-    }
-    if (!fused) hipLaunchKernelGGL(k_histogram, dim3(std::min(blocks256, 1024)), dim3(256), 0, st, h->status.as<uint8_t>(), n, ctr);
-    if (h->timing) HIP_TRY(h, hipEventRecord(h->ev[3], st));
-    int32_t *cnt_host = h->cnt_host();
-    if (!fused) hipLaunchKernelGGL(k_publish_words2, dim3(1), dim3(128), 0, st, reinterpret_cast<const unsigned int *>(ctr), (int)(sizeof(LevelCounters) / 4),
-                                   reinterpret_cast<const unsigned int *>(dcnt), 32, pub_dst);
-    HIP_TRY(h, hipGetLastError());
-    if (df) defer_swap(h, *df);   // every launch is queued: the set keeps what its region launch works in, the handle has its own buffers back
-    HIP_TRY(h, hipStreamSynchronize(st));   // the level's only synchronisation
-    LevelCounters host_ctr;
-    std::memcpy(&host_ctr, h->tot_host + 16, sizeof(LevelCounters));
-    h->n_smallpath++;
-    small_debug_note(cnt_host);
-    if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) { h->n_smallpath_doubtful++; g_small_repeats_doubtful++; }
-    // (behind a deferred region launch every optimal candidate is still "region pending": exactly the launch's, [6], may be)
-    const int n_late = cnt_host[17] - (df ? cnt_host[6] : 0);
-    if (host_ctr.n_rretry > 0 || n_late != 0 || h->kn.test_small_fallback || (fused && (cnt_host[4] > 0 || cnt_host[24] > 0))) {
-        // a candidate k_region2 gave up on (the LDS-engine region kernel is not part of this path), or one that turned out optimal
-        // after the region launch: the level is repeated classically
-        if (df) { HIP_TRY(h, hipEventSynchronize(df->ev_done)); df->pending = false; }   // its own deferred launch: waited for, its records dropped
-        h->n_smallpath_fallback++; g_small_repeats++;
-        // The repeat must not look for other parents' records: this run's k_children_write has overwritten the previous level's frontier
-        // (it lives in the children buffer since the hand-over), which that search walks.
-        h->n_prev = 0;
-        // A program that produces doubtful candidates keeps doing so (measured: 10-17 % of the small levels of random mpQPs, none on the
-        // named configurations): its handle goes back to re-solving them in place, so the repeat is paid once per handle.
-        if (fused && (cnt_host[4] > 0 || cnt_host[24] > 0)) h->kn.no_small_fuse = true;
-        *fallback = true;
-        return MPC_OK;
-    }
-    float ms[3] = {0, 0, 0};
-    if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
-    if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[1], h->ev[1], h->ev[2]));
-    if (h->timing) HIP_TRY(h, hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]));
-    h->n_opt = cnt_host[6];
-    h->n_children = gen_children ? cnt_host[20] : 0;
-    h->n_needx = cnt_host[7];
-    h->n_pruned_new = host_ctr.n_pruned_new;
-    h->n_erows = host_ctr.e_rows;
-    h->n_regions = (long long)host_ctr.status[ST_REGION];
-    if (df) df->n_opt = h->n_opt;   // (regions, rows, the launch's counters: defer_close, behind the next level)
-    level_close(h, n);
-    if (stats) {
-        level_stats_small(h, host_ctr, cnt_host, kkc != nullptr, quick_test, stats);
-        stats->ms_verdict = ms[0]; stats->ms_region = ms[1]; stats->ms_children = ms[2]; stats->ms_total = ms[0] + ms[1] + ms[2];
-        if (df) stats->region_side_stream = 2;
-    }
-    return MPC_OK;
-}
-
-// ---- the same level for many programs at once (batch_level.hpp) -----------------------------------------------------------------
-// batch_prepare = level_run_small up to its first launch (buffers, arguments; the buffer set-up both share is small_region_slots,
-// small_dict_cache and small_children_buffers above), batch_finish = level_run_small after its one synchronisation; the launches in
-// between are batch_level_launch's, one per stage for all members.
-static int batch_prepare(mpc_handle *h, int32_t gen_children, int32_t flags, BatchMember &m) {
-    const long long n = h->n;
-    const int k = h->k;
-    const size_t nn = (size_t)n;
-    hipStream_t st = h->stream;
-    std::memset(&m, 0, sizeof(m));
-    h->n_opt = h->n_children = h->n_pruned_new = h->n_regions = 0;
-    h->n_needx = 0;
-    HIP_TRY(h, h->status.ensure(nn, st));
-    HIP_TRY(h, h->pruned.ensure((size_t)(h->n_pruned + n) * h->mw * sizeof(uint64_t), st, true));
-    HIP_TRY(h, h->retry_list.ensure(nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->theta_list.ensure(nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->part_lists.ensure((size_t)PART_CLASSES * nn * sizeof(int32_t), st));
-    HIP_TRY(h, h->dcnt.ensure(32 * sizeof(int32_t), st));
-    level_record_shape(h, k);
-    m.k = k; m.kd = k - h->targs.ne; m.fast_t = h->fast_t; m.fast_x = h->fast_x; m.fast_r = h->fast_r; m.mw = h->mw;
-    m.gen_children = gen_children ? 1 : 0;
-    m.n = n; m.grid_f = h->grid_f; m.grid_r2 = h->grid_r2; m.n_cu = h->n_cu; m.lds_f = h->lds_f; m.lds_v = h->lds_v; m.lds_r2 = h->lds_r2;
-    m.rsplit_max = h->kn.rsplit_max;
-    m.pf = h->pf_dev.as<DevProblem>(); m.pr = h->pr2_dev.as<DevProblem>(); m.Pv = h->Pv;
-    m.fr = h->frontier.as<int32_t>(); m.status = h->status.as<uint8_t>(); m.ctr = h->ctr.as<LevelCounters>(); m.dcnt = h->dcnt.as<int32_t>();
-    m.theta_list = h->theta_list.as<int32_t>(); m.retry_list = h->retry_list.as<int32_t>(); m.part_lists = h->part_lists.as<int32_t>();
-    m.targs = h->targs;
-    m.zero[m.n_zero++] = {h->ctr.p, sizeof(LevelCounters)};
-    m.zero[m.n_zero++] = {h->dcnt.p, 32 * sizeof(int32_t)};
-    m.use_kkt = (h->kkt_mode == 0 && m.kd >= 1 && m.kd <= 8 && h->kn.no_kkt_thread != 1) ? 1 : 0;
-    if (m.use_kkt && h->kn.kkt_spread > 0 && m.kd <= BATCH_KKT_SPREAD_KMAX) m.use_kkt = 2;   // BATCH_KKT_SPREAD lanes per candidate (k_kkt_thread)
-    m.kkt_listed = 0;
-    if (m.use_kkt) {
-        HIP_TRY(h, h->kkt_code.ensure(nn, st));
-        HIP_TRY(h, h->kkt_L.ensure(nn * (size_t)k * (h->n_t + 1) * sizeof(double), st));
-        m.kkt_code = h->kkt_code.as<uint8_t>(); m.kkt_L = h->kkt_L.as<double>();
-        if (!h->kn.no_kkt_lists) {   // the kernel lists what it leaves to the theta stage (as level_run_small)
-            HIP_TRY(h, h->xq_list.ensure(nn * sizeof(int32_t), st));
-            m.targs.kt_list = m.theta_list; m.targs.kt_n = m.dcnt + 0;
-            m.targs.kx_list = h->xq_list.as<int32_t>(); m.targs.kx_n = m.dcnt + 10;
-            m.kkt_listed = 1;
-        }
-    }
-    // region stage: one slot per optimal candidate, buffers sized by the bound
-    {
-        int ldk = 0;
-        { int rcb = small_region_slots(h, nn, st, ldk); if (rcb) return rcb; }
-        m.zero[m.n_zero++] = {h->done_g.p, nn * 2 * sizeof(unsigned int)};
-        m.rs.n_opt_dev = m.dcnt + 18;   // the region launch comes last in the batch form: all optimal candidates, class 2 of the partition at [16..19]
-        m.rs.w_cap = h->grid_r2; m.rs.w_max = h->kn.rsplit_max;
-        m.W = h->kn.no_rsplit ? 1 : 0;
-        m.ldk = ldk; m.fd = h->fd; m.fi = h->fi; m.no_rbox = h->kn.no_rbox ? 1 : 0;
-        m.headd = h->headd.as<double>(); m.headi = h->headi.as<int32_t>(); m.epool = h->epool.as<double>();
-        m.kept_g = h->kept_g.as<uint8_t>(); m.done_g = h->done_g.as<unsigned int>();
-        // retry slots of the LDS-engine region kernel (launch_region_v1's buffers)
-        const int rows_t_ = h->n_c - h->n_eq + h->n_tc;
-        m.rcap = (int)std::min<long long>(n, 256);
-        HIP_TRY(h, h->recd.ensure((size_t)m.rcap * h->rec_d * sizeof(double), st));
-        HIP_TRY(h, h->reci.ensure((size_t)m.rcap * h->rec_i * sizeof(int32_t), st));
-        HIP_TRY(h, h->facet_flags.ensure((size_t)m.rcap * rows_t_, st));
-        m.recd = h->recd.as<double>(); m.reci = h->reci.as<int32_t>(); m.facet_flags = h->facet_flags.as<uint8_t>();
-        m.rec_d = h->rec_d; m.rec_i = h->rec_i; m.Pr = h->Pr; m.lds_r = h->lds_r;
-    }
-    // (x,theta) stage with the dictionary cache
-    m.nxc = dict_nxc(h);
-    DictCache dc;
-    { int rcb = small_dict_cache(h, nn, gen_children, st, m.dcnt, dc); if (rcb) return rcb; }
-    if (h->storing) m.zero[m.n_zero++] = {h->dict_stored[h->dict_cur].p, nn};
-    m.dc = dc;
-    m.storing = h->storing ? 1 : 0;
-    m.dict_stored_cur = h->storing ? h->dict_stored[h->dict_cur].as<uint8_t>() : nullptr;
-    m.quick_test = (!h->storing && dc.parent_slot) ? 1 : 0;
-    // pruned masks + children
-    m.keep_lowdim = (flags & MPC_LEVEL_KEEP_LOWDIM) ? 1 : 0;
-    m.theta_open = h->theta_open ? 1 : 0;
-    m.pruned = h->pruned.as<unsigned long long>(); m.n_pruned = h->n_pruned;
-    if (gen_children) {
-        { int rcb = small_children_buffers(h, nn, k, st); if (rcb) return rcb; }
-        m.childmask = h->childmask.as<unsigned long long>(); m.count = h->count.as<int32_t>(); m.offset = h->offset.as<int32_t>();
-        m.children = h->children.as<int32_t>(); m.parent_slot_next = h->parent_slot_next.as<int32_t>();
-    }
-    m.pub_ctr = reinterpret_cast<unsigned int *>(h->tot_dev + 16);
-    m.pub_cnt = reinterpret_cast<unsigned int *>(h->tot_dev + 16 + (int)(sizeof(LevelCounters) / 4));
-    // pruned.ensure(..., keep) may have moved the list: the frontier and everything else above is read after this point only
-    HIP_TRY(h, hipStreamSynchronize(st));   // whatever the member's own stream still had queued (frontier kernels, copies of a grown buffer)
-    return MPC_OK;
-}
-
-static int batch_finish(mpc_handle *h, int32_t gen_children, const BatchMember &m, float ms_total, mpc_level_stats *stats, bool *fallback) {
-    *fallback = false;
-    const long long n = h->n;
-    LevelCounters host_ctr;
-    std::memcpy(&host_ctr, h->tot_host + 16, sizeof(LevelCounters));
-    const int32_t *cnt_host = h->cnt_host();
-    h->n_smallpath++;
-    small_debug_note(cnt_host);
-    if (cnt_host[28] > m.rcap || h->kn.test_small_fallback) {
-        // more candidates k_region2 gave up on than retry slots were reserved (never observed): the member repeats the level alone
-        h->n_smallpath_fallback++;
-        *fallback = true;
-        return MPC_OK;
-    }
-    h->n_opt = cnt_host[18];
-    h->n_rretry = cnt_host[28];      // their records are in the fixed layout (recd / reci), listed in retry_list
-    h->n_children = gen_children ? cnt_host[20] : 0;
-    h->n_needx = cnt_host[7];
-    h->n_pruned_new = host_ctr.n_pruned_new;
-    h->n_erows = host_ctr.e_rows;
-    h->n_regions = (long long)host_ctr.status[ST_REGION];
-    level_close(h, n);
-    if (stats) {
-        level_stats_small(h, host_ctr, cnt_host, m.use_kkt != 0, m.quick_test != 0, stats);
-        stats->n_region_retry = h->n_rretry;
-        stats->ms_total = ms_total;   // the batch's launches, first to last (shared by all members)
-    }
-    return MPC_OK;
-}
+// the level without host round trips and its batch form: level_run_small, batch_prepare / batch_finish, defer_swap / defer_join / defer_drain
+#include "level_small.hpp"
 
 static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mpc_level_stats *stats);
 
@@ -1623,6 +1138,12 @@ static void worker_base_check(mpc_handle *h) {
     if (rb == MPC_OK) { h->base_regions = bs.n_regions; h->base_valid = true; }
 }
 
+// a level of the solve loop back to "not run": blocks nobody took go back to the pool, nothing is known of the level any more
+static void solve_level_reset(mpc_handle::SolveLevel &lv) {
+    if (!lv.handed) { if (lv.hd) (void)host_pool_give(lv.hd); if (lv.hi) (void)host_pool_give(lv.hi); if (lv.er) (void)host_pool_give(lv.er); }
+    lv.hd = lv.hi = lv.er = nullptr; lv.handed = false; lv.flags = nullptr; lv.ready_flag = nullptr; lv.mode = 0;
+    lv.ready.store(0, std::memory_order_release); lv.done.store(0, std::memory_order_release);
+}
 // blocks of levels of the previous solve loop that nobody took
 static void solve_release(mpc_handle *h) {
     if (!h->sv_levels) return;
@@ -1635,12 +1156,7 @@ static void solve_release(mpc_handle *h) {
         if (!lv.handed && lv.ready_flag && !__atomic_load_n(lv.ready_flag, __ATOMIC_ACQUIRE)) pending = true;
     }
     if (pending && h->stream) (void)hipStreamSynchronize(h->stream);
-    for (int i = 0; i < nl; ++i) {
-        auto &lv = h->sv_levels[i];
-        if (!lv.handed) { if (lv.hd) (void)host_pool_give(lv.hd); if (lv.hi) (void)host_pool_give(lv.hi); if (lv.er) (void)host_pool_give(lv.er); }
-        lv.hd = lv.hi = lv.er = nullptr; lv.handed = false; lv.flags = nullptr; lv.ready_flag = nullptr; lv.mode = 0;
-        lv.ready.store(0, std::memory_order_relaxed); lv.done.store(0, std::memory_order_relaxed);
-    }
+    for (int i = 0; i < nl; ++i) solve_level_reset(h->sv_levels[i]);
     h->sv_n.store(0, std::memory_order_release);
 }
 
@@ -1668,6 +1184,33 @@ static int solve_fetch_slots(mpc_handle *h, mpc_handle::SolveLevel &lv, long lon
     lv.ready_flag = flag;
     lv.mode = 2; lv.n_slots = n_opt; lv.n_rows = n_erows; lv.chunk = 0; lv.n_chunks = 0;
     return MPC_OK;
+}
+// The records of the level that has just run in line (not deferred), where the region kernel has not streamed them into lv's blocks already.
+static int solve_fetch_level(mpc_handle *h, mpc_handle::SolveLevel &lv, int flags) {
+    if (lv.ready.load(std::memory_order_relaxed)) {
+        if (lv.stats.n_region_retry == 0) return MPC_OK;
+        // candidates the LDS-engine kernel re-solved after the stream: their slots are filled in place (the caller lists the level
+        // again after mpc_solve_level_wait)
+        int64_t ns = 0, nr = 0;
+        return level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, false, true);
+    }
+    // the level did not stream (no optimal candidate; run without host round trips, its records in device buffers; LDS-engine
+    // region kernel; > 1 GiB of records): fetched here, complete when published
+    if (!((flags & MPC_SOLVE_FETCH) && lv.stats.n_regions > 0 && h->n_opt > 0 && !h->so.active)) { lv.mode = 0; return MPC_OK; }
+    int64_t rows_cap = 0, ns = 0, nr = 0;
+    mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
+    const size_t b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
+    if (h->used_region2 && h->n_rretry == 0)   // every record is in slot form on the device
+        // (the counter: DC_FETCH_COUNTER, a list length the level's own kernels are taken not to use, cleared with the others at its start)
+        return solve_fetch_slots(h, lv, h->n_opt, h->fd, h->fi, h->n_erows, b_er, h->headd.p, h->headi.p, h->epool.p, reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + DC_FETCH_COUNTER));
+    int rc = MPC_OK;
+    const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t);
+    if (host_pool_take(b_hd, &lv.hd, nullptr, false) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, false) != hipSuccess ||
+        host_pool_take(b_er, &lv.er, nullptr, false) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
+    if (rc == MPC_OK)
+        rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), h->n_opt, static_cast<double *>(lv.er), rows_cap, &ns, &nr, false, false);
+    lv.mode = 2; lv.n_slots = ns; lv.n_rows = nr; lv.chunk = 0; lv.n_chunks = 0;
+    return rc;
 }
 static void solve_publish(mpc_handle *h, mpc_handle::SolveLevel &lv) {
     lv.ready.store(1, std::memory_order_release);
@@ -1712,7 +1255,7 @@ static int defer_close(mpc_handle *h, mpc_handle::RegionDefer &d, int flags, boo
     int rcs = MPC_OK;
     if ((flags & MPC_SOLVE_FETCH) && st.n_regions > 0)
         rcs = solve_fetch_slots(h, lv, d.n_opt, d.fd, d.fi, (long long)rc.e_rows, std::max<size_t>((size_t)rc.e_rows, 1) * (h->n_t + 1) * sizeof(double),
-                                d.headd.p, d.headi.p, d.epool.p, reinterpret_cast<unsigned int *>(d.dcnt.as<int32_t>() + 30));
+                                d.headd.p, d.headi.p, d.epool.p, reinterpret_cast<unsigned int *>(d.dcnt.as<int32_t>() + DC_FETCH_COUNTER));
     else lv.mode = 0;
     if (rcs == MPC_OK && final) {
         // no level followed: the handle is left as a level in line leaves it (mpc_level_status, mpc_level_regions_* after mpc_solve_wait)
@@ -1736,12 +1279,7 @@ static void defer_abandon(mpc_handle *h, int from) {
     defer_drain(h);
     h->defer_off = true;
     const int nl = h->sv_n.load(std::memory_order_acquire);
-    for (int i = from; i < nl; ++i) {
-        auto &lv = h->sv_levels[i];
-        if (!lv.handed) { if (lv.hd) (void)host_pool_give(lv.hd); if (lv.hi) (void)host_pool_give(lv.hi); if (lv.er) (void)host_pool_give(lv.er); }
-        lv.hd = lv.hi = lv.er = nullptr; lv.handed = false; lv.flags = nullptr; lv.ready_flag = nullptr; lv.mode = 0;
-        lv.ready.store(0, std::memory_order_release); lv.done.store(0, std::memory_order_release);
-    }
+    for (int i = from; i < nl; ++i) solve_level_reset(h->sv_levels[i]);
 }
 
 // The level loop of the reference's driver (mp_solvers/mpqp_parrallel_combinatorial.py:98-139) on the worker thread: root frontier,
@@ -1783,32 +1321,7 @@ static int worker_solve(mpc_handle *h) {
                 rc = defer_close(h, before, flags, false, &miss);
                 if (rc == MPC_OK && miss) { miss_at = before.depth; break; }
             }
-            if (rc == MPC_OK && !deferred && !lv.ready.load(std::memory_order_relaxed)) {
-                // the level did not stream (no optimal candidate; run without host round trips, its records in device buffers; LDS-engine
-                // region kernel; > 1 GiB of records): fetched here, complete when published
-                if ((flags & MPC_SOLVE_FETCH) && lv.stats.n_regions > 0 && h->n_opt > 0 && !h->so.active) {
-                    int64_t rows_cap = 0, ns = 0, nr = 0;
-                    mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
-                    const size_t b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
-                    if (h->used_region2 && h->n_rretry == 0)   // every record is in slot form on the device
-                        // (the counter: a list length nothing uses, cleared with the others at the start of every level)
-                        rc = solve_fetch_slots(h, lv, h->n_opt, h->fd, h->fi, h->n_erows, b_er, h->headd.p, h->headi.p, h->epool.p, reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + 30));
-                    else {
-                        const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t);
-                        if (host_pool_take(b_hd, &lv.hd, nullptr, false) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, false) != hipSuccess ||
-                            host_pool_take(b_er, &lv.er, nullptr, false) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
-                        if (rc == MPC_OK)
-                            rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), h->n_opt, static_cast<double *>(lv.er),
-                                                          rows_cap, &ns, &nr, false, false);
-                        lv.mode = 2; lv.n_slots = ns; lv.n_rows = nr; lv.chunk = 0; lv.n_chunks = 0;
-                    }
-                } else lv.mode = 0;
-            } else if (rc == MPC_OK && !deferred && lv.stats.n_region_retry > 0) {
-                // candidates the LDS-engine kernel re-solved after the stream: their slots are filled in place (the caller lists the level
-                // again after mpc_solve_level_wait)
-                int64_t ns = 0, nr = 0;
-                rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, false, true);
-            }
+            if (rc == MPC_OK && !deferred) rc = solve_fetch_level(h, lv, flags);
             lv.ms_wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             h->sv_cur = -1;
             if (rc != MPC_OK) break;

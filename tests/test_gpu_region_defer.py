@@ -11,7 +11,7 @@ import warnings
 import numpy
 import pytest
 
-from conftest import load_golden
+from conftest import golden_regions, load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +29,11 @@ def make_program(name, mode):
     return prog, eng
 
 
-def solve_once(prog, eng, max_levels):
-    """-> ({active set: region}, number of regions listed, per level (n, n_regions, n_children, status histogram), per level region_side_stream)"""
+def solve_once(prog, eng, max_levels, profile=None):
+    """-> ({active set: region}, number of regions listed, per level (n, n_regions, n_children, status histogram), per level region_side_stream)
+    ``profile``: a list switches the handle's timing on for this solve (``mpc_set_timing``), as every solve that asks for a profile does."""
     from ppopt_amd.mp_solvers import mpqp_hip_combinatorial as m
-    sol = m.solve(prog, max_levels=max_levels)
+    sol = m.solve(prog, max_levels=max_levels, profile=profile)
     regions = list(sol.critical_regions)
     levels, codes = [], []
     for lv in range(eng.solve_wait()):
@@ -137,3 +138,32 @@ def test_two_solves_back_to_back_on_one_handle():
     second = solve_once(prog, eng, None)
     assert_same(second, want)
     assert second[3] == codes and second[2] == levels and codes.count(2) >= 1
+
+
+# ---- two terms of the deferral's gate (SmallRun::begin, csrc/level_small.hpp): the fused form only, and never under the handle's timing ----
+GATE_GOLDENS = ['c2_dblint_n5', 'rand_6_3_12_s1']
+
+
+def assert_nothing_deferred(name, got):
+    """no level closed late or repeated after a miss; the in-line solve's regions bit for bit; the active sets the reference recorded"""
+    assert 2 not in got[3] and 3 not in got[3]
+    assert_same(got, in_line(name, None))
+    assert sorted(got[0]) == sorted(golden_regions(load_golden(name)))
+
+
+@pytest.mark.parametrize('name', GATE_GOLDENS)
+def test_the_round_4_form_defers_nothing(name, monkeypatch):
+    """MPC_NO_SMALL_FUSE=1 in default mode: a small level that re-solves its doubtful candidates in place builds its regions in line"""
+    monkeypatch.setenv('MPC_NO_SMALL_FUSE', '1')
+    prog, eng = make_program(name, DEFAULT)
+    assert_nothing_deferred(name, solve_once(prog, eng, None))
+
+
+@pytest.mark.parametrize('name', GATE_GOLDENS)
+def test_timing_defers_nothing(name):
+    """the handle's timing switched on (a solve with a profile) in default mode: the per-stage events are recorded in line, no level defers"""
+    prog, eng = make_program(name, DEFAULT)
+    profile = []
+    got = solve_once(prog, eng, None, profile=profile)
+    assert eng._timing is True and len(profile) > 0
+    assert_nothing_deferred(name, got)
