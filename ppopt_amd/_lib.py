@@ -368,6 +368,12 @@ def masks_to_sets(masks: numpy.ndarray, words: int = MASK_WORDS):
     return out
 
 
+def slot_strides(n_x: int, n_t: int, n_c: int, n_tc: int, k: int):
+    """(fd, fi): doubles and ints of one slot of a level of cardinality ``k`` (csrc/records.hpp, RecordShape::fd / fi) -- the one copy of
+    these formulas on the host side (``Engine.slot_strides``; the multi-GPU driver's engines are not ``Engine`` objects)."""
+    return n_x * n_t + n_x + k * n_t + k, 8 + k + n_tc + k + 2 * (n_c - k)
+
+
 class Engine:
     """One device-resident program (mpc_handle).  Mirrors what every reference worker holds: the presolved
     matrices of the program plus the pruned list; see include/mpcombi.h for the call-by-call mapping."""
@@ -565,6 +571,18 @@ class Engine:
             e._last = st
         return out, int(nb.value)
 
+    def slot_strides(self, k: int):
+        return slot_strides(self.n_x, self.n_t, self.n_c, self.n_tc, k)
+
+    def _rows_cap(self, st) -> int:
+        """Upper bound of the rows the level's records own, from its LevelStats (csrc/records.hpp, record_rows_bound): pooled rows + a
+        full row block per candidate the LDS-engine kernel re-solved; a level built by that kernel alone (no register-resident
+        instantiation: one parameter) reports no pooled rows."""
+        nr, rows_t = int(st.n_regions), self.n_c - self.n_eq + self.n_tc
+        if not nr:
+            return 0
+        return int(st.n_region_rows) + int(st.n_region_retry) * rows_t if st.n_region_rows else nr * rows_t
+
     @staticmethod
     def level_batch_fetch(engines):
         """``level_regions_slots_nowait`` for many engines with ONE call into the library and THREE page-locked blocks for all of
@@ -576,15 +594,11 @@ class Engine:
         fds, fis, nss, nrs = [], [], [], []
         for e in engines:
             st = e._last
-            k = int(st.k)
-            nr = int(st.n_regions)
-            fds.append(e.n_x * e.n_t + e.n_x + k * e.n_t + k)
-            fis.append(8 + k + e.n_tc + k + 2 * (e.n_c - k))
-            nss.append(int(st.n_opt) if nr else 0)
-            rows_t = e.n_c - e.n_eq + e.n_tc
-            # mpc_compact_strides' max_rows: pooled rows + a full row block per candidate the LDS-engine kernel re-solved; a level
-            # built by that kernel alone (no register-resident instantiation: one parameter) reports no pooled rows
-            nrs.append(0 if not nr else (int(st.n_region_rows) + int(st.n_region_retry) * rows_t if st.n_region_rows else nr * rows_t))
+            fd, fi = e.slot_strides(int(st.k))
+            fds.append(fd)
+            fis.append(fi)
+            nss.append(int(st.n_opt) if st.n_regions else 0)
+            nrs.append(e._rows_cap(st))
         od = numpy.concatenate([[0], numpy.cumsum([n * f for n, f in zip(nss, fds)])]).astype(numpy.int64)
         oi = numpy.concatenate([[0], numpy.cumsum([n * f for n, f in zip(nss, fis)])]).astype(numpy.int64)
         oe = numpy.concatenate([[0], numpy.cumsum([n * (e.n_t + 1) for n, e in zip(nrs, engines)])]).astype(numpy.int64)
@@ -653,8 +667,7 @@ class Engine:
                 if ns[j] == 0:
                     continue
                 e, k = engines[i], int(stats[j].k)
-                fd = e.n_x * e.n_t + e.n_x + k * e.n_t + k
-                fi = 8 + k + e.n_tc + k + 2 * (e.n_c - k)
+                fd, fi = e.slot_strides(k)
                 records.append((i, big_d[od[j]:od[j] + ns[j] * fd].reshape(ns[j], fd), big_i[oi[j]:oi[j] + ns[j] * fi].reshape(ns[j], fi),
                                 big_e[oe[j]:oe[j] + nr[j] * (e.n_t + 1)].reshape(nr[j], e.n_t + 1), k))
         return 0, (members, stats, int(info.n_shared), float(info.ms_wall), records, bool(info.base))
@@ -726,8 +739,7 @@ class Engine:
         if ns.value == 0:
             return None
         n, k = self.frontier_info()
-        fd = self.n_x * self.n_t + self.n_x + k * self.n_t + k
-        fi = 8 + k + self.n_tc + k + 2 * (self.n_c - k)
+        fd, fi = self.slot_strides(k)
         return (pinned_adopt(hd.value, (ns.value, fd), numpy.float64), pinned_adopt(hi.value, (ns.value, fi), numpy.int32),
                 pinned_adopt(er.value, (max(cr.value, 1), self.n_t + 1), numpy.float64), int(ch.value), int(nch.value))
 
@@ -764,8 +776,7 @@ class Engine:
         if info.mode == 0:
             return 0, int(info.k), int(info.n), None, None, None, 0, 0
         k = int(info.k)
-        fd = self.n_x * self.n_t + self.n_x + k * self.n_t + k
-        fi = 8 + k + self.n_tc + k + 2 * (self.n_c - k)
+        fd, fi = self.slot_strides(k)
         ns = int(info.n_slots)
         return (int(info.mode), k, int(info.n), pinned_adopt(info.head_d, (ns, fd), numpy.float64), pinned_adopt(info.head_i, (ns, fi), numpy.int32),
                 pinned_adopt(info.erows, (max(int(info.n_rows), 1), self.n_t + 1), numpy.float64), int(info.chunk), int(info.n_chunks))

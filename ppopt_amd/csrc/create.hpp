@@ -446,8 +446,8 @@ struct CreateRun {
     }
 
     int records_and_counters() {
-        h->rec_d = (long long)nx * nt + nx + (long long)nc * nt + nc + (long long)(nc + ntc) * nt + (nc + ntc);
-        h->rec_i = 5 + (long long)nc + ntc + nc + nc + nc;
+        h->rec_d = record_shape(h, 0).rec_d();   // (the fixed record does not depend on the cardinality)
+        h->rec_i = record_shape(h, 0).rec_i();
         HIP_TRY(nullptr, h->ctr.ensure(sizeof(LevelCounters), h->stream));
         HIP_TRY(nullptr, h->scratch.ensure(256, h->stream));
         void *hp = nullptr, *dp = nullptr;

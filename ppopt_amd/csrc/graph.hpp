@@ -13,6 +13,7 @@
 // Every array is sorted, so the traversal -- and the order of the regions it returns -- is deterministic.
 #pragma once
 #include <stdint.h>
+#include "records.hpp"
 
 namespace mpc {
 
@@ -77,41 +78,41 @@ __global__ void k_g_frontier(const GMask<MW> *__restrict__ m, long long n, int k
 }
 
 // variant 1 (mpqp_graph.py): the facet constraints of every region of the group -- CriticalRegion.regular_set[1], the inactive
-// constraints whose rows are facets -- as one mask per candidate.  Slot form (k_region2): head_i row = status cand nE n_om n_la
-// n_re e_off 0 | active[k] | omega[n_tc] | lambda[k] | reg_idx[n_c-k] | reg_con[n_c-k].
+// constraints whose rows are facets -- as one mask per candidate, from the slot form of the records (records.hpp; rcon: its s_rcon,
+// spelled from the kernel's own arguments).
 template <int MW>
 __global__ void k_g_facets_slots(const int32_t *__restrict__ head_i, int fi, long long n_slots, int k, int n_c, int n_tc,
                                  GMask<MW> *__restrict__ facet) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slots) return;
     const int32_t *hi = head_i + (size_t)s * fi;
-    if (hi[0] != 3) return;   // MPC_REGION
-    const int32_t *rcon = hi + 8 + k + n_tc + k + (n_c - k);
+    if (hi[SW_STATUS] != SLOT_ST_REGION) return;
+    const int32_t *rcon = hi + SW_LISTS + k + n_tc + k + (n_c - k);
     GMask<MW> f;
 #pragma unroll
     for (int j = 0; j < MW; ++j) f.w[j] = 0;
-    for (int r = 0; r < hi[5]; ++r) {
+    for (int r = 0; r < hi[SW_NRE]; ++r) {
         const int c = rcon[r];
 #pragma unroll
         for (int j = 0; j < MW; ++j) if ((c >> 6) == j) f.w[j] |= 1ull << (c & 63);
     }
-    facet[hi[1]] = f;
+    facet[hi[SW_CAND]] = f;
 }
-// the same for regions that the LDS-engine kernel produced (fixed-stride records: k nE n_om n_la n_re | active[n_c] |
-// omega[n_tc] | lambda[n_c] | reg_idx[n_c] | reg_con[n_c]); list[r] = candidate of record r
+// the same for regions that the LDS-engine kernel produced (fixed-stride records of records.hpp; rcon: its f_rcon); list[r] = candidate
+// of record r
 template <int MW>
 __global__ void k_g_facets_fixed(const int32_t *__restrict__ rec_i, long long stride, const int32_t *__restrict__ list, long long n_list,
                                  const uint8_t *__restrict__ status, int n_c, int n_tc, GMask<MW> *__restrict__ facet) {
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_list) return;
     const int cand = list[r];
-    if (status[cand] != 3) return;
+    if (status[cand] != SLOT_ST_REGION) return;
     const int32_t *ri = rec_i + (size_t)r * stride;
-    const int32_t *rcon = ri + 5 + n_c + n_tc + n_c + n_c;
+    const int32_t *rcon = ri + FW_LISTS + n_c + n_tc + n_c + n_c;
     GMask<MW> f;
 #pragma unroll
     for (int j = 0; j < MW; ++j) f.w[j] = 0;
-    for (int q = 0; q < ri[4]; ++q) {
+    for (int q = 0; q < ri[FW_NRE]; ++q) {
         const int c = rcon[q];
 #pragma unroll
         for (int j = 0; j < MW; ++j) if ((c >> 6) == j) f.w[j] |= 1ull << (c & 63);

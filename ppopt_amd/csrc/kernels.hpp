@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "kkt.hpp"
+#include "records.hpp"
 
 // Every kernel of kernels.hpp / kernels2.hpp is declared MPC_GLOBAL void MPC_LB(bounds) name(...).  In the library's main
 // translation unit these are ordinary kernels.  batch_level.hip defines MPC_GLOBAL as an inlined device function before it
@@ -36,6 +37,10 @@ namespace mpc {
 
 constexpr int ST_INFEASIBLE = 0, ST_FEASIBLE = 1, ST_OPT_NO_REGION = 2, ST_REGION = 3, ST_SINGULAR = 4, ST_LP_LIMIT = 5;
 constexpr int ST_OPT_PENDING = 6;  // internal: optimal, waiting for k_region
+constexpr int ST_RETRY = 7;       // numerically doubtful: re-solve with the LDS engine (k_verdict)
+constexpr int ST_NEEDX = 8;       // theta stage could not show feasibility: (x,theta) LP needed (k_x2)
+constexpr int ST_NEEDX_SING = 9;  // the same, and the KKT matrix was singular (a feasible outcome is ST_SINGULAR)
+static_assert(ST_REGION == SLOT_ST_REGION, "records.hpp: the status of a slot that carries a record");
 constexpr double ZERO_ROW_ATOL = 1e-8;  // numerically_nonzero_rows, constraint_utilities.py:469-470
 constexpr double FULL_DIM_RADIUS = 1e-8;  // is_full_dimensional, mpqp_utils.py:342-344
 
@@ -455,6 +460,8 @@ MPC_GLOBAL void MPC_LB(64) k_region(DevProblem P, const int32_t *__restrict__ ca
     extern __shared__ __attribute__((aligned(16))) double smem[];
     Smem s = carve(P, smem);
     const int lane = lane_id(), nt = P.n_t, nr = nt + 1, nx = P.n_x, nc = P.n_c, ntc = P.n_tc, e = P.n_eq;
+    // The fixed record is written with its offsets spelled out, as sums from FW_LISTS on (f_act .. f_rcon, f_Al .. f_f of records.hpp):
+    // taking them from a RecordShape changes this kernel's compiled code (other scalar registers, other spills).
     unsigned long long pivots = 0;
     for (;;) {
         unsigned int w = 0;
@@ -532,9 +539,9 @@ MPC_GLOBAL void MPC_LB(64) k_region(DevProblem P, const int32_t *__restrict__ ca
                         }
                         const unsigned long long b0 = __ballot(keep && cls == 0), b1 = __ballot(keep && cls == 1), b2 = __ballot(keep && cls == 2);
                         const unsigned long long below = (1ull << lane) - 1ull;
-                        if (keep && cls == 0) ri[5 + nc + ntc + n_la + __popcll(b0 & below)] = val;
-                        if (keep && cls == 1) { const int p = n_re + __popcll(b1 & below); ri[5 + nc + ntc + nc + p] = val; ri[5 + nc + ntc + nc + nc + p] = val2; }
-                        if (keep && cls == 2) ri[5 + nc + n_om + __popcll(b2 & below)] = val;
+                        if (keep && cls == 0) ri[FW_LISTS + nc + ntc + n_la + __popcll(b0 & below)] = val;
+                        if (keep && cls == 1) { const int p = n_re + __popcll(b1 & below); ri[FW_LISTS + nc + ntc + nc + p] = val; ri[FW_LISTS + nc + ntc + nc + nc + p] = val2; }
+                        if (keep && cls == 2) ri[FW_LISTS + nc + n_om + __popcll(b2 & below)] = val;
                         n_la += __popcll(b0); n_re += __popcll(b1); n_om += __popcll(b2);
                     }
                     double *Eo = rd + nx * nt + nx + nc * nt + nc, *fo = Eo + (nc + ntc) * nt;
@@ -604,9 +611,9 @@ MPC_GLOBAL void MPC_LB(64) k_region(DevProblem P, const int32_t *__restrict__ ca
                     if (rr != LP_OPTIMAL) continue;
                     const int o = s.kept[row];
                     if (lane == 0) {
-                        if (o < nlam) ri[5 + nc + ntc + n_la] = s.as[e + o];
-                        else if (o < nlam + nin) { ri[5 + nc + ntc + nc + n_re] = o - nlam; ri[5 + nc + ntc + nc + nc + n_re] = s.inact[o - nlam]; }
-                        else ri[5 + nc + n_om] = o - nlam - nin;
+                        if (o < nlam) ri[FW_LISTS + nc + ntc + n_la] = s.as[e + o];
+                        else if (o < nlam + nin) { ri[FW_LISTS + nc + ntc + nc + n_re] = o - nlam; ri[FW_LISTS + nc + ntc + nc + nc + n_re] = s.inact[o - nlam]; }
+                        else ri[FW_LISTS + nc + n_om] = o - nlam - nin;
                     }
                     if (o < nlam) n_la++; else if (o < nlam + nin) n_re++; else n_om++;
                     // exact duplicates of an earlier kept row are not stored again (remove_duplicate_rows, mpqp_utils.py:191;
@@ -638,8 +645,8 @@ MPC_GLOBAL void MPC_LB(64) k_region(DevProblem P, const int32_t *__restrict__ ca
             double *Al = rd + nx * nt + nx, *bl = Al + nc * nt;
             for (int idx = lane; idx < k * nt; idx += 64) Al[idx] = s.L[(idx / nt) * nr + 1 + idx % nt];
             for (int i = lane; i < k; i += 64) bl[i] = s.L[i * nr];
-            for (int i = lane; i < k; i += 64) ri[5 + i] = s.as[i];
-            if (lane == 0) { ri[0] = k; ri[1] = nE; ri[2] = n_om; ri[3] = n_la; ri[4] = n_re; }
+            for (int i = lane; i < k; i += 64) ri[FW_LISTS + i] = s.as[i];
+            if (lane == 0) { ri[FW_K] = k; ri[FW_NE] = nE; ri[FW_NOM] = n_om; ri[FW_NLA] = n_la; ri[FW_NRE] = n_re; }
         }
         if (lane == 0) status[c] = (uint8_t)st;
     }
@@ -863,7 +870,7 @@ MPC_GLOBAL void MPC_LB(256) k_region_prep(RegionPrep a) {
         }
     }
     for (long long i = blockIdx.x * 256ll + threadIdx.x; i < a.copy_n; i += (long long)gridDim.x * 256ll) a.copy_dst[i] = a.copy_src[i];
-    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.extra; j += gridDim.x * 256) { int32_t *hi = a.head_i + (size_t)(a.first + j) * a.fi; hi[0] = 0; hi[1] = -1; }
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < a.extra; j += gridDim.x * 256) { int32_t *hi = a.head_i + (size_t)(a.first + j) * a.fi; hi[SW_STATUS] = 0; hi[SW_CAND] = -1; }
 }
 
 // The slot arrays of a level that did not stream (head_d, head_i, rows) from their device buffers into page-locked host blocks, by
@@ -1326,26 +1333,29 @@ MPC_GLOBAL void MPC_LB(1024) k_scan_publish(const int32_t *__restrict__ in, int3
 
 // ---- records of the candidates the register region kernel gave up on, into their slots ON THE DEVICE (round 5) -------------------------
 // k_region2 marks such a slot ST_RETRY, the LDS-engine kernel k_region re-solves the candidate into a FIXED-stride record (recd / reci,
-// in the order of retry_list).  Until round 5 the host merged those into the slot arrays after the copy (level_regions_slots_impl:
+// in the order of retry_list).  Until round 5 the host merged those into the slot arrays after the copy (fill_fixed of level_fetch.hpp:
 // eight copy commands and a synchronisation per member -- 2-3 ms per level of 128 programs); this kernel writes them into the slot
 // arrays where they are, the rows [f | E] behind the pooled ones (row0 on), so the member's records leave with the shared copy launch.
-// One block per member; same arithmetic-free moves as the host loop, same slot contents.
+// One block per member; same arithmetic-free moves as the host's fixed_to_slot (records.hpp), same slot contents.
 constexpr int RRETRY_MERGE_MAX = 1024;
 struct RretryMerge {
     const int32_t *opt_list; const int32_t *rlist; const uint8_t *status; const double *recd; const int32_t *reci;
     double *headd; int32_t *headi; double *epool;
-    int n_opt, n_rretry, rec_d, rec_i, fd, fi, row0, nx, nt, nc, ntc, k;
+    RecordShape sh;
+    int n_opt, n_rretry, row0;
 };
 MPC_GLOBAL void MPC_LB(256) k_rretry_merge(RretryMerge a) {
     __shared__ int slots[RRETRY_MERGE_MAX], src[RRETRY_MERGE_MAX], rowoff[RRETRY_MERGE_MAX];
     __shared__ int wc[4];
     __shared__ int m;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const RecordShape &sh = a.sh;
+    const int fd = sh.fd(), fi = sh.fi(), rec_d = (int)sh.rec_d(), rec_i = (int)sh.rec_i(), nt = sh.nt, nr = sh.row_len();
     if (tid == 0) m = 0;
     __syncthreads();
     for (int start = 0; start < a.n_opt; start += 256) {     // the slots marked "given up", in slot order
         const int w = start + tid;
-        const bool f = w < a.n_opt && a.headi[(size_t)w * a.fi] == 7;   // 7 = ST_RETRY (kernels2.hpp)
+        const bool f = w < a.n_opt && a.headi[(size_t)w * fi + SW_STATUS] == ST_RETRY;
         const unsigned long long mk = __ballot(f);
         if (lane == 0) wc[wave] = __popcll(mk);
         __syncthreads();
@@ -1363,34 +1373,33 @@ MPC_GLOBAL void MPC_LB(256) k_rretry_merge(RretryMerge a) {
         int r = -1;
         for (int q = 0; q < a.n_rretry; ++q) if (a.rlist[q] == cand) { r = q; break; }
         src[j] = r;
-        rowoff[j] = (r >= 0 && a.status[cand] == ST_REGION) ? a.reci[(size_t)r * a.rec_i + 1] : 0;
+        rowoff[j] = (r >= 0 && a.status[cand] == ST_REGION) ? a.reci[(size_t)r * rec_i + FW_NE] : 0;
     }
     __syncthreads();
     if (tid == 0) { int run = a.row0; for (int j = 0; j < mm; ++j) { const int ne = rowoff[j]; rowoff[j] = run; run += ne; } }
     __syncthreads();
-    const int nx = a.nx, nt = a.nt, nc = a.nc, ntc = a.ntc, k = a.k, nr = nt + 1;
     for (int j = 0; j < mm; ++j) {
         const int w = slots[j], cand = a.opt_list[w], r = src[j];
         const int st = a.status[cand];
-        int32_t *oi = a.headi + (size_t)w * a.fi;
-        double *od = a.headd + (size_t)w * a.fd;
-        for (int i = tid; i < a.fi; i += 256) oi[i] = i == 0 ? st : (i == 1 ? cand : (i < 8 ? 0 : -1));
+        int32_t *oi = a.headi + (size_t)w * fi;
+        double *od = a.headd + (size_t)w * fd;
+        for (int i = tid; i < fi; i += 256) oi[i] = i == SW_STATUS ? st : (i == SW_CAND ? cand : (i < SW_LISTS ? 0 : -1));
         if (r < 0 || st != ST_REGION) continue;      // (uniform)
-        for (int i = tid; i < a.fd; i += 256) od[i] = 0.0;
+        for (int i = tid; i < fd; i += 256) od[i] = 0.0;
         __syncthreads();
-        const double *rd = a.recd + (size_t)r * a.rec_d;
-        const int32_t *ri = a.reci + (size_t)r * a.rec_i;
-        const int kk = ri[0], nE = ri[1], n_om = ri[2], n_la = ri[3], n_re = ri[4];
-        const double *Al = rd + nx * nt + nx, *bl = Al + (size_t)nc * nt, *E = bl + nc, *f = E + (size_t)(nc + ntc) * nt;
-        for (int i = tid; i < nx * nt + nx; i += 256) od[i] = rd[i];
-        for (int i = tid; i < kk * nt; i += 256) od[nx * nt + nx + i] = Al[i];
-        for (int i = tid; i < kk; i += 256) od[nx * nt + nx + k * nt + i] = bl[i];
-        if (tid == 0) { oi[2] = nE; oi[3] = n_om; oi[4] = n_la; oi[5] = n_re; oi[6] = rowoff[j]; }
-        int32_t *act = oi + 8, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);
-        for (int i = tid; i < kk; i += 256) act[i] = ri[5 + i];
-        for (int i = tid; i < n_om; i += 256) om[i] = ri[5 + nc + i];
-        for (int i = tid; i < n_la; i += 256) la[i] = ri[5 + nc + ntc + i];
-        for (int i = tid; i < n_re; i += 256) { ridx[i] = ri[5 + nc + ntc + nc + i]; rcon[i] = ri[5 + nc + ntc + nc + nc + i]; }
+        const double *rd = a.recd + (size_t)r * rec_d;
+        const int32_t *ri = a.reci + (size_t)r * rec_i;
+        const int kk = ri[FW_K], nE = ri[FW_NE], n_om = ri[FW_NOM], n_la = ri[FW_NLA], n_re = ri[FW_NRE];
+        const double *Al = rd + sh.f_Al(), *bl = rd + sh.f_bl(), *E = rd + sh.f_E(), *f = rd + sh.f_f();
+        for (int i = tid; i < sh.law(); i += 256) od[i] = rd[i];
+        for (int i = tid; i < kk * nt; i += 256) od[sh.s_Al() + i] = Al[i];
+        for (int i = tid; i < kk; i += 256) od[sh.s_bl() + i] = bl[i];
+        if (tid == 0) { oi[SW_NE] = nE; oi[SW_NOM] = n_om; oi[SW_NLA] = n_la; oi[SW_NRE] = n_re; oi[SW_ROW0] = rowoff[j]; }
+        int32_t *act = oi + sh.s_act(), *om = oi + sh.s_om(), *la = oi + sh.s_la(), *ridx = oi + sh.s_ridx(), *rcon = oi + sh.s_rcon();
+        for (int i = tid; i < kk; i += 256) act[i] = ri[sh.f_act() + i];
+        for (int i = tid; i < n_om; i += 256) om[i] = ri[sh.f_om() + i];
+        for (int i = tid; i < n_la; i += 256) la[i] = ri[sh.f_la() + i];
+        for (int i = tid; i < n_re; i += 256) { ridx[i] = ri[sh.f_ridx() + i]; rcon[i] = ri[sh.f_rcon() + i]; }
         for (int i = tid; i < nE * nr; i += 256) {
             const int rr = i / nr, t = i - rr * nr;
             a.epool[(size_t)(rowoff[j] + rr) * nr + t] = t == 0 ? f[rr] : E[(size_t)rr * nt + (t - 1)];
@@ -1412,11 +1421,11 @@ MPC_GLOBAL void k_apply_status(const int32_t *__restrict__ list, int n_list, con
 }
 
 // Spare region slots behind the slots of the overlapped region launch (LevelRun::region2_launch, level_classic.hpp): slot first + j gets status word `st`
-// and candidate list[j] (or -1).  st = 0: unused slot; st = 7 (ST_RETRY): a candidate that turned out optimal after the launch,
+// and candidate list[j] (or -1).  st = 0: unused slot; st = ST_RETRY: a candidate that turned out optimal after the launch,
 // its record comes from the LDS-engine kernel like that of a candidate k_region2 gave up on.
 MPC_GLOBAL void k_init_slots(int32_t *__restrict__ head_i, int fi, int first, int count, int st, const int32_t *__restrict__ list) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < count) { int32_t *hi = head_i + (size_t)(first + j) * fi; hi[0] = st; hi[1] = list ? list[j] : -1; }
+    if (j < count) { int32_t *hi = head_i + (size_t)(first + j) * fi; hi[SW_STATUS] = st; hi[SW_CAND] = list ? list[j] : -1; }
 }
 // keeps rows start, start+stride, ... of a row-major int matrix (frontier sharding, mpc_frontier_shard)
 MPC_GLOBAL void k_take_rows(const int32_t *__restrict__ src, long long n_new, int width, long long start, long long stride,

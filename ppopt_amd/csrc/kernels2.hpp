@@ -29,9 +29,7 @@ __device__ __forceinline__ double theta_row_scale(int ex) {
     if (THETA_SCALE_MODE == 2 && ex > 0) return 1.0;
     return ldexp(1.0, -ex);
 }
-constexpr int ST_RETRY = 7;       // numerically doubtful: re-solve with the LDS engine (k_verdict)
-constexpr int ST_NEEDX = 8;       // theta stage could not show feasibility: (x,theta) LP needed (k_x2)
-constexpr int ST_NEEDX_SING = 9;  // the same, and the KKT matrix was singular (a feasible outcome is ST_SINGULAR)
+// (ST_RETRY, ST_NEEDX, ST_NEEDX_SING: kernels.hpp, beside the other statuses)
 
 
 // hot read-only blocks of k_theta2, passed BY VALUE: the pointers are known to be global memory (global_load / s_load
@@ -1700,7 +1698,7 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
         const int nin = load_active_set(P, cands + (size_t)c * k, k, s);
         double *hd = head_d + (size_t)w * fd;
         int32_t *hi = head_i + (size_t)w * fi;
-        for (int i = lane; i < fi; i += 64) hi[i] = i < 8 ? 0 : -1;
+        for (int i = lane; i < fi; i += 64) hi[i] = i < SW_LISTS ? 0 : -1;
         int st = ST_REGION;
         if (kk < 0) kk = kkt_solve(P, k, s, &ill);
         if (kk != 0) st = kk == 1 ? ST_INFEASIBLE : ST_SINGULAR;
@@ -2115,7 +2113,7 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
             }
             // ---- record ----------------------------------------------------------------------------------------------
             if (is_last && st == ST_REGION && !retry) {
-                int32_t *act = hi + 8, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);
+                int32_t *act = hi + SW_LISTS, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);   // s_act .. s_rcon of records.hpp, as a pointer chain: from a RecordShape the compiled code changes
                 // duplicate rows: row i is dropped from E if an earlier kept row has identical (f, E)
                 bool dup[SLOTS], kp[SLOTS];
 #pragma unroll
@@ -2188,7 +2186,7 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
                 n_la = base_la; n_re = base_re; n_om = base_om;
                 for (int idx = lane; idx < nx * nt; idx += 64) hd[idx] = s.X[(idx / nt) * nr + 1 + idx % nt];
                 for (int i = lane; i < nx; i += 64) hd[nx * nt + i] = s.X[i * nr];
-                double *Al = hd + nx * nt + nx, *bl = Al + k * nt;
+                double *Al = hd + nx * nt + nx, *bl = Al + k * nt;   // s_Al, s_bl of records.hpp
                 for (int idx = lane; idx < k * nt; idx += 64) Al[idx] = s.L[(idx / nt) * nr + 1 + idx % nt];
                 for (int i = lane; i < k; i += 64) bl[i] = s.L[i * nr];
                 for (int i = lane; i < k; i += 64) act[i] = s.as[i];
@@ -2200,7 +2198,7 @@ MPC_GLOBAL void MPC_LB(64, (SLOTS >= 2 ? 2 : R2W)) k_region2(
         if (ill && st == ST_OPT_NO_REGION && !retry) st = ST_FEASIBLE;
         if (retry) { st = ST_RETRY; if (lane == 0 && is_last) atomicAdd(&ctr->n_rretry, 1u); }
         if (lane == 0 && is_last) {
-            hi[0] = st; hi[1] = c; hi[2] = nE; hi[3] = n_om; hi[4] = n_la; hi[5] = n_re; hi[6] = e_off; hi[7] = reason;
+            hi[SW_STATUS] = st; hi[SW_CAND] = c; hi[SW_NE] = nE; hi[SW_NOM] = n_om; hi[SW_NLA] = n_la; hi[SW_NRE] = n_re; hi[SW_ROW0] = e_off; hi[SW_REASON] = reason;
             // (status == nullptr: a launch that runs beside the NEXT level, whose status array this no longer is -- the slot carries the verdict)
             if (status) status[c] = (uint8_t)(retry ? ST_RRETRY : st);   // distinct from the verdict stages' ST_RETRY, which may be pending on other candidates
         }
@@ -2238,7 +2236,7 @@ MPC_GLOBAL void MPC_LB(256) k_defer_publish(const int32_t *__restrict__ head_i, 
     if (threadIdx.x < 8) hist[threadIdx.x] = 0;
     __syncthreads();
     const int n_opt = *n_opt_dev;
-    for (int w = threadIdx.x; w < n_opt; w += 256) atomicAdd(&hist[head_i[(size_t)w * fi] & 7], 1u);
+    for (int w = threadIdx.x; w < n_opt; w += 256) atomicAdd(&hist[head_i[(size_t)w * fi + SW_STATUS] & 7], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < n_ctr; i += 256) dst[i] = load_word_agent(ctr_words + i);
     if (threadIdx.x < 8) dst[n_ctr + threadIdx.x] = hist[threadIdx.x];
@@ -2249,7 +2247,7 @@ MPC_GLOBAL void MPC_LB(256) k_defer_status(const int32_t *__restrict__ head_i, i
     const int w = (int)(blockIdx.x * 256 + threadIdx.x);
     if (w >= n_opt) return;
     const int32_t *hi = head_i + (size_t)w * fi;
-    status[hi[1]] = (uint8_t)(hi[0] == ST_RETRY ? ST_RRETRY : hi[0]);
+    status[hi[SW_CAND]] = (uint8_t)(hi[SW_STATUS] == ST_RETRY ? ST_RRETRY : hi[SW_STATUS]);
 }
 
 }  // namespace mpc

@@ -53,9 +53,8 @@ static bool small_path_ok(const mpc_handle *h, long long n, int k, int32_t flags
     // children and their parent slots are sized by the bound n (n_c - k) candidates of k + 1 indices
     const double child_bytes = (double)n * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
     if (gen_children && child_bytes > 512e6) return false;
-    const long long rows_t = h->n_c - h->n_eq + h->n_tc;
-    const double rec_bytes = (double)n * ((double)(h->n_x * h->n_t + h->n_x + k * h->n_t + k) * 8.0 + (double)(8 + 2 * k + h->n_tc + 2 * (h->n_c - k)) * 4.0 +
-                                          (double)rows_t * (h->n_t + 1) * 8.0);
+    const RecordShape sh = record_shape(h, k);
+    const double rec_bytes = (double)n * ((double)sh.fd() * 8.0 + (double)sh.fi() * 4.0 + (double)sh.rows_t() * sh.row_len() * 8.0);
     return rec_bytes <= 2e9;
 }
 

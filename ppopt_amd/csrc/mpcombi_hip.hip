@@ -295,7 +295,6 @@ struct mpc_handle {
     float ms_x1 = 0;
     long long prev_regions = 0;   // regions the level before found (kn.xq_early_regions compares against it)
     long long n_xq_thread = 0; float ms_xq_thread = 0;   // the last level run: candidates that pass decided, its time
-    bool fetch_nowait = false; // mpc_level_regions_slots_nowait: even the integer heads are only queued
     bool skip_small = false;  // mpc_level_run_batch: this level already went through the no-round-trip launches and has to be repeated classically
     size_t o_elim[6] = {0, 0, 0, 0, 0, 0};   // offsets of Wr, UVr, AATr, Me, Ne, gE in `blocks` (mpc_program_block)
     bool elim_ok = false;     // the blocks with the equality rows eliminated are valid
@@ -401,6 +400,9 @@ int mpc::fail(mpc_handle *h, int code, const std::string &msg) {
     if (h) { std::lock_guard<std::mutex> lk(h->em); h->error = msg; } else g_error = msg;
     return code;
 }
+// the layout of the handle's region records at cardinality k (records.hpp); without k: of the level the handle is at
+static RecordShape record_shape(const mpc_handle *h, int k) { return RecordShape{h->n_x, h->n_t, h->n_c, h->n_tc, h->n_eq, k}; }
+static RecordShape record_shape(const mpc_handle *h) { return record_shape(h, h->k); }
 
 namespace {
 
@@ -864,8 +866,8 @@ static int x1_join(mpc_handle *h) {
 // shape of the level's region records (doubles / ints per slot) and the region stage's per-level state
 static void level_record_shape(mpc_handle *h, int k) {
     h->used_region2 = false; h->n_rretry = 0; h->n_erows = 0; h->rretry_rows = -1;
-    h->fd = h->n_x * h->n_t + h->n_x + k * h->n_t + k;
-    h->fi = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
+    const RecordShape sh = record_shape(h, k);
+    h->fd = sh.fd(); h->fi = sh.fi();
 }
 // partition spec of k_partition_small / k_part_*: status -> class nibble, 15 = none
 static unsigned long long part_spec(std::initializer_list<std::pair<int, int>> classes) {
@@ -930,8 +932,8 @@ static int level_run_impl(mpc_handle *h, int32_t gen_children, int32_t flags, mp
 static double batch_level_gb(const mpc_handle *h, int32_t gen_children) {
     const double n = (double)h->n;
     const int k = h->k;
-    const double rows_t = h->n_c - h->n_eq + h->n_tc;
-    double bytes = n * ((double)(h->n_x * h->n_t + h->n_x + k * h->n_t + k) * 8.0 + (double)(8 + 2 * k + h->n_tc + 2 * (h->n_c - k)) * 4.0 + rows_t * (h->n_t + 1) * 8.0);
+    const RecordShape sh = record_shape(h, k);
+    double bytes = n * ((double)sh.fd() * 8.0 + (double)sh.fi() * 4.0 + (double)sh.rows_t() * sh.row_len() * 8.0);
     if (gen_children) bytes += n * std::max(h->n_c - k, 1) * (k + 2) * 4.0;
     const double nxc = h->fast_x >= 2 ? 32 : 16;
     bytes += 2.0 * n * (nxc * h->Pf.n_d0r * 8.0 + (2.0 * h->Pf.n_d0r + nxc + 4) * 4.0);
@@ -1120,8 +1122,9 @@ int mpc_level_run_ex(mpc_handle *h, int32_t gen_children, int32_t flags, mpc_lev
 }
 
 // ---- the same level, driven by the handle's worker thread ---------------------------------------------------------------
-static int level_regions_slots_impl(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_slots, double *erows, int64_t cap_rows,
-                                    int64_t *n_slots, int64_t *n_rows, bool may_return_early, bool in_place);
+// the level's region records off the device: sizes, SlotFetch and the slot / compact / fixed fetches, the shared copy launches
+#include "level_fetch.hpp"
+
 // The base active set (the equality rows alone; driver :142-146) on the worker thread.  Any failure simply leaves the check to the caller.
 static void worker_base_check(mpc_handle *h) {
     std::vector<int32_t> base((size_t)std::max(h->n_eq, 1));
@@ -1160,31 +1163,6 @@ static void solve_release(mpc_handle *h) {
     h->sv_n.store(0, std::memory_order_release);
 }
 
-// One launch writes a level's slot records (every record in slot form on the device) into fresh page-locked blocks of lv and raises the
-// flag behind head_i; nobody waits here (mpc_solve_level does).  counter: a zero word of device memory nothing else uses before the launch.
-static int solve_fetch_slots(mpc_handle *h, mpc_handle::SolveLevel &lv, long long n_opt, int fd, int fi, long long n_erows, size_t b_er,
-                             const void *headd, const void *headi, const void *epool, unsigned int *counter) {
-    const size_t b_hd = (size_t)n_opt * fd * sizeof(double), b_hi = (size_t)n_opt * fi * sizeof(int32_t);
-    if (host_pool_take(b_hd, &lv.hd, nullptr, true) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, true) != hipSuccess ||
-        host_pool_take(b_er, &lv.er, nullptr, true) != hipSuccess) return fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
-    FetchCopy fc{};
-    int32_t *flag = reinterpret_cast<int32_t *>(static_cast<char *>(lv.hi) + ((b_hi + 7) & ~size_t(7)));
-    *flag = 0;
-    void *d_hd = nullptr, *d_hi = nullptr, *d_er = nullptr;
-    if (hipHostGetDevicePointer(&d_hd, lv.hd, 0) != hipSuccess || hipHostGetDevicePointer(&d_hi, lv.hi, 0) != hipSuccess ||
-        hipHostGetDevicePointer(&d_er, lv.er, 0) != hipSuccess) return fail(h, MPC_ERR_HIP, "hipHostGetDevicePointer (level records)");
-    fc.src[0] = headi; fc.dst[0] = d_hi; fc.bytes[0] = b_hi;
-    fc.src[1] = headd; fc.dst[1] = d_hd; fc.bytes[1] = b_hd;
-    fc.src[2] = epool; fc.dst[2] = d_er; fc.bytes[2] = (size_t)n_erows * (h->n_t + 1) * sizeof(double);
-    fc.counter = counter;
-    fc.flag = reinterpret_cast<int32_t *>(static_cast<char *>(d_hi) + ((b_hi + 7) & ~size_t(7)));
-    const unsigned long long words = (b_hi + b_hd + fc.bytes[2]) / 4;
-    hipLaunchKernelGGL(k_fetch_slots, dim3((unsigned)std::min<unsigned long long>(256, words / 2048 + 1)), dim3(256), 0, h->stream, fc);
-    if (hipGetLastError() != hipSuccess) return fail(h, MPC_ERR_HIP, "k_fetch_slots launch");
-    lv.ready_flag = flag;
-    lv.mode = 2; lv.n_slots = n_opt; lv.n_rows = n_erows; lv.chunk = 0; lv.n_chunks = 0;
-    return MPC_OK;
-}
 // The records of the level that has just run in line (not deferred), where the region kernel has not streamed them into lv's blocks already.
 static int solve_fetch_level(mpc_handle *h, mpc_handle::SolveLevel &lv, int flags) {
     if (lv.ready.load(std::memory_order_relaxed)) {
@@ -1192,23 +1170,23 @@ static int solve_fetch_level(mpc_handle *h, mpc_handle::SolveLevel &lv, int flag
         // candidates the LDS-engine kernel re-solved after the stream: their slots are filled in place (the caller lists the level
         // again after mpc_solve_level_wait)
         int64_t ns = 0, nr = 0;
-        return level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, false, true);
+        return level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), lv.n_slots, static_cast<double *>(lv.er), lv.n_rows, &ns, &nr, FetchMode::in_place);
     }
     // the level did not stream (no optimal candidate; run without host round trips, its records in device buffers; LDS-engine
     // region kernel; > 1 GiB of records): fetched here, complete when published
     if (!((flags & MPC_SOLVE_FETCH) && lv.stats.n_regions > 0 && h->n_opt > 0 && !h->so.active)) { lv.mode = 0; return MPC_OK; }
-    int64_t rows_cap = 0, ns = 0, nr = 0;
-    mpc_compact_strides(h, nullptr, nullptr, &rows_cap);
-    const size_t b_er = (size_t)std::max<int64_t>(rows_cap, 1) * (h->n_t + 1) * sizeof(double);
+    int64_t ns = 0, nr = 0;
+    const RecordSizes z = level_record_sizes(h);
+    const size_t b_er = (size_t)std::max<long long>(z.rows_cap, 1) * (h->n_t + 1) * sizeof(double);
     if (h->used_region2 && h->n_rretry == 0)   // every record is in slot form on the device
         // (the counter: DC_FETCH_COUNTER, a list length the level's own kernels are taken not to use, cleared with the others at its start)
-        return solve_fetch_slots(h, lv, h->n_opt, h->fd, h->fi, h->n_erows, b_er, h->headd.p, h->headi.p, h->epool.p, reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + DC_FETCH_COUNTER));
+        return solve_fetch_slots(h, lv, z.n_slots, z.fd, z.fi, h->n_erows, b_er, h->headd.p, h->headi.p, h->epool.p, reinterpret_cast<unsigned int *>(h->dcnt.as<int32_t>() + DC_FETCH_COUNTER));
     int rc = MPC_OK;
-    const size_t b_hd = (size_t)h->n_opt * h->fd * sizeof(double), b_hi = (size_t)h->n_opt * h->fi * sizeof(int32_t);
+    const size_t b_hd = (size_t)z.n_slots * z.fd * sizeof(double), b_hi = (size_t)z.n_slots * z.fi * sizeof(int32_t);
     if (host_pool_take(b_hd, &lv.hd, nullptr, false) != hipSuccess || host_pool_take(b_hi + 64, &lv.hi, nullptr, false) != hipSuccess ||
         host_pool_take(b_er, &lv.er, nullptr, false) != hipSuccess) rc = fail(h, MPC_ERR_HIP, "mpc_solve: page-locked memory for a level's region records");
     if (rc == MPC_OK)
-        rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), h->n_opt, static_cast<double *>(lv.er), rows_cap, &ns, &nr, false, false);
+        rc = level_regions_slots_impl(h, static_cast<double *>(lv.hd), static_cast<int32_t *>(lv.hi), z.n_slots, static_cast<double *>(lv.er), z.rows_cap, &ns, &nr, FetchMode::complete);
     lv.mode = 2; lv.n_slots = ns; lv.n_rows = nr; lv.chunk = 0; lv.n_chunks = 0;
     return rc;
 }
@@ -1253,10 +1231,13 @@ static int defer_close(mpc_handle *h, mpc_handle::RegionDefer &d, int flags, boo
     st.wave_cycles[3] += (int64_t)rc.cycles[3];
     if (d.n_opt > 0 && rc.r2_t1 > ~rc.r2_not_t0 && h->wall_khz > 0) st.ms_region2 = (float)((double)(rc.r2_t1 - ~rc.r2_not_t0) / (double)h->wall_khz);
     int rcs = MPC_OK;
-    if ((flags & MPC_SOLVE_FETCH) && st.n_regions > 0)
-        rcs = solve_fetch_slots(h, lv, d.n_opt, d.fd, d.fi, (long long)rc.e_rows, std::max<size_t>((size_t)rc.e_rows, 1) * (h->n_t + 1) * sizeof(double),
+    if ((flags & MPC_SOLVE_FETCH) && st.n_regions > 0) {
+        // (st: the level's own k and n_opt, the launch's regions and rows; no candidate re-solved.  Regions without a single row: the block
+        // is sized as for a level that pools nothing, n_regions * rows_t rows, where one row would do)
+        const RecordSizes z = level_record_sizes(h, st);
+        rcs = solve_fetch_slots(h, lv, z.n_slots, z.fd, z.fi, (long long)rc.e_rows, (size_t)std::max<long long>(z.rows_cap, 1) * (h->n_t + 1) * sizeof(double),
                                 d.headd.p, d.headi.p, d.epool.p, reinterpret_cast<unsigned int *>(d.dcnt.as<int32_t>() + DC_FETCH_COUNTER));
-    else lv.mode = 0;
+    } else lv.mode = 0;
     if (rcs == MPC_OK && final) {
         // no level followed: the handle is left as a level in line leaves it (mpc_level_status, mpc_level_regions_* after mpc_solve_wait)
         defer_swap(h, d);
@@ -1579,337 +1560,6 @@ int mpc_level_status(mpc_handle *h, uint8_t *status) {
     return MPC_OK;
 }
 
-int mpc_compact_strides(const mpc_handle *h, int64_t *fd, int64_t *fi, int64_t *max_rows) {
-    if (!h) return MPC_ERR_INVALID;
-    if (fd) *fd = h->n_x * h->n_t + h->n_x + h->k * h->n_t + h->k;
-    if (fi) *fi = 8 + h->k + h->n_tc + h->k + 2 * (h->n_c - h->k);
-    if (max_rows) {
-        const long long rows_t = h->n_c - h->n_eq + h->n_tc;
-        *max_rows = h->used_region2 ? h->n_erows + h->n_rretry * rows_t : h->n_regions * rows_t;
-    }
-    return MPC_OK;
-}
-
-// Regions of the level in compact form, frontier order, written straight into the caller's arrays.
-int mpc_level_regions_compact(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_regions, double *erows, int64_t cap_rows,
-                              int64_t *n_regions, int64_t *n_rows) {
-    if (!h) return MPC_ERR_INVALID;
-    if (!h->level_done) return fail(h, MPC_ERR_STATE, "mpc_level_run has not been called for this frontier");
-    if (n_regions) *n_regions = h->n_regions;
-    if (n_rows) *n_rows = 0;
-    if (h->so.active) return fail(h, MPC_ERR_STATE, "the records of this level were streamed to the host (mpc_level_stream_info)");
-    if (cap_regions < h->n_regions) return fail(h, MPC_ERR_CAPACITY, "region buffers too small");
-    if (h->n_regions == 0 || h->n_opt == 0) return MPC_OK;
-    if (!head_d || !head_i || !erows) return MPC_ERR_INVALID;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int nx = h->n_x, nt = h->n_t, nc = h->n_c, ntc = h->n_tc, k = h->k, nr = nt + 1, fd = h->fd, fi = h->fi;
-    const long long n_opt = h->n_opt, rows_t = nc - h->n_eq + ntc;
-    const long long n_fixed = h->used_region2 ? h->n_rretry : n_opt;
-    hipStream_t s = h->stream;
-    HIP_TRY(h, h->st_list.ensure((size_t)n_opt * sizeof(int32_t)));
-    HIP_TRY(h, h->st_status.ensure((size_t)h->n));
-    HIP_TRY(h, hipMemcpyAsync(h->st_list.p, h->opt_ptr, (size_t)n_opt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(h->st_status.p, h->status.p, (size_t)h->n, hipMemcpyDeviceToHost, s));
-    if (n_fixed > 0) {
-        HIP_TRY(h, h->st_fxd.ensure((size_t)n_fixed * h->rec_d * sizeof(double)));
-        HIP_TRY(h, h->st_fxi.ensure((size_t)n_fixed * h->rec_i * sizeof(int32_t)));
-        HIP_TRY(h, hipMemcpyAsync(h->st_fxd.p, h->recd.p, (size_t)n_fixed * h->rec_d * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(h->st_fxi.p, h->reci.p, (size_t)n_fixed * h->rec_i * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    if (h->used_region2) {
-        HIP_TRY(h, h->st_hd.ensure((size_t)n_opt * fd * sizeof(double)));
-        HIP_TRY(h, h->st_hi.ensure((size_t)n_opt * fi * sizeof(int32_t)));
-        HIP_TRY(h, h->st_pool.ensure((size_t)std::max<long long>(h->n_erows, 1) * nr * sizeof(double)));
-        HIP_TRY(h, hipMemcpyAsync(h->st_hd.p, h->headd.p, (size_t)n_opt * fd * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(h->st_hi.p, h->headi.p, (size_t)n_opt * fi * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (h->n_erows > 0) HIP_TRY(h, hipMemcpyAsync(h->st_pool.p, h->epool.p, (size_t)h->n_erows * nr * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (h->n_rretry > 0) {
-            HIP_TRY(h, h->st_rlist.ensure((size_t)h->n_rretry * sizeof(int32_t)));
-            HIP_TRY(h, hipMemcpyAsync(h->st_rlist.p, h->retry_list.p, (size_t)h->n_rretry * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    const int32_t *list = h->st_list.as<int32_t>(), *rlist = h->st_rlist.as<int32_t>();
-    const uint8_t *st = h->st_status.as<uint8_t>();
-    const double *fxd = h->st_fxd.as<double>(), *hd = h->st_hd.as<double>(), *pool = h->st_pool.as<double>();
-    const int32_t *fxi = h->st_fxi.as<int32_t>(), *hi = h->st_hi.as<int32_t>();
-    long long wreg = 0, wrow = 0;
-    bool overflow = false;
-    // fixed record (mpcombi.h layout) -> compact head + rows
-    auto from_fixed = [&](const double *rd, const int32_t *ri, int cand) {
-        const int kk = ri[0], nE = ri[1], n_om = ri[2], n_la = ri[3], n_re = ri[4];
-        if (wrow + nE > cap_rows) { overflow = true; return; }
-        double *od = head_d + (size_t)wreg * fd;
-        int32_t *oi = head_i + (size_t)wreg * fi;
-        std::fill(od, od + fd, 0.0); std::fill(oi, oi + fi, -1);
-        std::memcpy(od, rd, sizeof(double) * (nx * nt + nx));
-        const double *Al = rd + nx * nt + nx, *bl = Al + (size_t)nc * nt, *E = bl + nc, *f = E + (size_t)(nc + ntc) * nt;
-        std::memcpy(od + nx * nt + nx, Al, sizeof(double) * kk * nt);
-        std::memcpy(od + nx * nt + nx + k * nt, bl, sizeof(double) * kk);
-        oi[0] = ST_REGION; oi[1] = cand; oi[2] = nE; oi[3] = n_om; oi[4] = n_la; oi[5] = n_re; oi[6] = (int32_t)wrow; oi[7] = 0;
-        int32_t *act = oi + 8, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);
-        std::memcpy(act, ri + 5, sizeof(int32_t) * kk);
-        std::memcpy(om, ri + 5 + nc, sizeof(int32_t) * n_om);
-        std::memcpy(la, ri + 5 + nc + ntc, sizeof(int32_t) * n_la);
-        std::memcpy(ridx, ri + 5 + nc + ntc + nc, sizeof(int32_t) * n_re);
-        std::memcpy(rcon, ri + 5 + nc + ntc + nc + nc, sizeof(int32_t) * n_re);
-        for (int r = 0; r < nE; ++r) {
-            double *row = erows + (size_t)(wrow + r) * nr;
-            row[0] = f[r];
-            for (int t = 0; t < nt; ++t) row[1 + t] = E[(size_t)r * nt + t];
-        }
-        wrow += nE; ++wreg;
-    };
-    long long rpos = 0;
-    for (long long w = 0; w < n_opt && !overflow && wreg < cap_regions; ++w) {
-        const int cand = list[w];
-        if (!h->used_region2) {
-            if (st[cand] == ST_REGION) from_fixed(fxd + (size_t)w * h->rec_d, fxi + (size_t)w * h->rec_i, cand);
-            continue;
-        }
-        const int32_t *src_i = hi + (size_t)w * fi;
-        if (src_i[0] == ST_REGION) {
-            const int nE = src_i[2], off = src_i[6];
-            if (wrow + nE > cap_rows) { overflow = true; break; }
-            std::memcpy(head_d + (size_t)wreg * fd, hd + (size_t)w * fd, sizeof(double) * fd);
-            int32_t *oi = head_i + (size_t)wreg * fi;
-            std::memcpy(oi, src_i, sizeof(int32_t) * fi);
-            oi[6] = (int32_t)wrow;
-            std::memcpy(erows + (size_t)wrow * nr, pool + (size_t)off * nr, sizeof(double) * nE * nr);
-            wrow += nE; ++wreg;
-        } else if (src_i[0] == ST_RETRY) {
-            while (rpos < h->n_rretry && rlist[rpos] != cand) ++rpos;
-            if (rpos < h->n_rretry && st[cand] == ST_REGION) from_fixed(fxd + (size_t)rpos * h->rec_d, fxi + (size_t)rpos * h->rec_i, cand);
-        }
-    }
-    (void)rows_t;
-    if (overflow) return fail(h, MPC_ERR_CAPACITY, "row buffer too small (see mpc_compact_strides max_rows)");
-    if (n_regions) *n_regions = wreg;
-    if (n_rows) *n_rows = wrow;
-    return MPC_OK;
-}
-
-int64_t mpc_level_slots(const mpc_handle *h) { return h ? h->n_opt : 0; }
-
-// in_place: the level's records were streamed into head_d / head_i / erows (host memory) by the region kernel itself; only
-// the slots of candidates re-solved by the LDS-engine kernel still have to be filled in
-static int level_regions_slots_impl(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_slots, double *erows, int64_t cap_rows,
-                                    int64_t *n_slots, int64_t *n_rows, bool may_return_early, bool in_place) {
-    if (!h) return MPC_ERR_INVALID;
-    if (!h->level_done) return fail(h, MPC_ERR_STATE, "mpc_level_run has not been called for this frontier");
-    if (h->so.active && !in_place) return fail(h, MPC_ERR_STATE, "the records of this level were streamed to the host (mpc_level_stream_info)");
-    if (n_slots) *n_slots = 0;
-    if (n_rows) *n_rows = 0;
-    if (h->n_regions == 0 || h->n_opt == 0) return MPC_OK;
-    if (cap_slots < h->n_opt) return fail(h, MPC_ERR_CAPACITY, "slot buffers too small (mpc_level_slots)");
-    if (!head_d || !head_i || !erows) return MPC_ERR_INVALID;
-    HIP_TRY(h, hipSetDevice(h->device));
-    const int nx = h->n_x, nt = h->n_t, nc = h->n_c, ntc = h->n_tc, k = h->k, nr = nt + 1, fd = h->fd, fi = h->fi;
-    const long long n_opt = h->n_opt, rows_t = nc - h->n_eq + ntc;
-    const bool merged = h->used_region2 && h->rretry_rows >= 0;   // k_rretry_merge has written the re-solved candidates' records into their slots
-    const long long pool_rows = merged ? h->rretry_rows : h->n_erows;
-    const long long n_fixed = h->used_region2 ? (merged ? 0 : h->n_rretry) : n_opt;
-    const long long rows_need = h->used_region2 ? (merged ? pool_rows : h->n_erows + h->n_rretry * rows_t) : h->n_regions * rows_t;
-    if (cap_rows < rows_need) return fail(h, MPC_ERR_CAPACITY, "row buffer too small (see mpc_compact_strides max_rows)");
-    hipStream_t s = h->stream;
-    if (n_fixed > 0) {
-        HIP_TRY(h, h->st_fxd.ensure((size_t)n_fixed * h->rec_d * sizeof(double)));
-        HIP_TRY(h, h->st_fxi.ensure((size_t)n_fixed * h->rec_i * sizeof(int32_t)));
-        HIP_TRY(h, h->st_list.ensure((size_t)n_opt * sizeof(int32_t)));
-        HIP_TRY(h, h->st_status.ensure((size_t)h->n));
-        HIP_TRY(h, hipMemcpyAsync(h->st_fxd.p, h->recd.p, (size_t)n_fixed * h->rec_d * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(h->st_fxi.p, h->reci.p, (size_t)n_fixed * h->rec_i * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(h->st_list.p, h->opt_ptr, (size_t)n_opt * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipMemcpyAsync(h->st_status.p, h->status.p, (size_t)h->n, hipMemcpyDeviceToHost, s));
-    }
-    long long wrow = 0;
-    if (h->used_region2 && n_fixed == 0 && may_return_early && !in_place) {
-        // every record is in slot form on the device: the small integer heads first, then the two large arrays; the call
-        // returns when the heads have arrived, the rest is in flight on the handle's stream (mpc_sync completes it)
-        HIP_TRY(h, hipMemcpyAsync(head_i, h->headi.p, (size_t)n_opt * fi * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipEventRecord(h->ev_hi, s));
-        HIP_TRY(h, hipMemcpyAsync(head_d, h->headd.p, (size_t)n_opt * fd * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (pool_rows > 0) HIP_TRY(h, hipMemcpyAsync(erows, h->epool.p, (size_t)pool_rows * nr * sizeof(double), hipMemcpyDeviceToHost, s));
-        if (!h->fetch_nowait) HIP_TRY(h, hipEventSynchronize(h->ev_hi));
-        if (n_slots) *n_slots = n_opt;
-        if (n_rows) *n_rows = pool_rows;
-        return MPC_OK;
-    }
-    if (h->used_region2) {
-        if (!in_place) {
-            HIP_TRY(h, hipMemcpyAsync(head_d, h->headd.p, (size_t)n_opt * fd * sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(h, hipMemcpyAsync(head_i, h->headi.p, (size_t)n_opt * fi * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            if (pool_rows > 0) HIP_TRY(h, hipMemcpyAsync(erows, h->epool.p, (size_t)pool_rows * nr * sizeof(double), hipMemcpyDeviceToHost, s));
-        }
-        wrow = pool_rows;
-        if (h->n_rretry > 0 && !merged) {
-            HIP_TRY(h, h->st_rlist.ensure((size_t)h->n_rretry * sizeof(int32_t)));
-            HIP_TRY(h, hipMemcpyAsync(h->st_rlist.p, h->retry_list.p, (size_t)h->n_rretry * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (h->kn.debug_cycles && h->used_region2) {
-        long long hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (long long w = 0; w < n_opt; ++w) { const int32_t *oi = head_i + (size_t)w * fi; if (oi[0] == ST_RETRY) hist[oi[7] & 7]++; }
-        std::fprintf(stderr, "[mpc] k=%d region retries by reason: chebyshev %lld, r->0 %lld, refactor-after-chebyshev %lld, row lost %lld, >8 refactors %lld, refactor failed %lld\n",
-                     k, hist[1], hist[2], hist[3], hist[4], hist[5], hist[6]);
-    }
-    if (n_fixed > 0) {
-        // the candidates solved by the LDS-engine kernel come as fixed-stride records: written into their slots here
-        const int32_t *list = h->st_list.as<int32_t>(), *rlist = h->st_rlist.as<int32_t>();
-        const uint8_t *st = h->st_status.as<uint8_t>();
-        const double *fxd = h->st_fxd.as<double>();
-        const int32_t *fxi = h->st_fxi.as<int32_t>();
-        long long rpos = 0;
-        for (long long w = 0; w < n_opt; ++w) {
-            const int cand = list[w];
-            int32_t *oi = head_i + (size_t)w * fi;
-            long long src = -1;
-            if (!h->used_region2) src = w;
-            else if (oi[0] == ST_RETRY) {
-                while (rpos < h->n_rretry && rlist[rpos] != cand) ++rpos;
-                if (rpos < h->n_rretry) src = rpos;
-            } else continue;
-            std::fill(oi, oi + fi, -1);
-            oi[0] = st[cand]; oi[1] = cand; oi[2] = oi[3] = oi[4] = oi[5] = oi[6] = oi[7] = 0;
-            if (src < 0 || st[cand] != ST_REGION) continue;
-            const double *rd = fxd + (size_t)src * h->rec_d;
-            const int32_t *ri = fxi + (size_t)src * h->rec_i;
-            const int kk = ri[0], nE = ri[1], n_om = ri[2], n_la = ri[3], n_re = ri[4];
-            double *od = head_d + (size_t)w * fd;
-            std::fill(od, od + fd, 0.0);
-            std::memcpy(od, rd, sizeof(double) * (nx * nt + nx));
-            const double *Al = rd + nx * nt + nx, *bl = Al + (size_t)nc * nt, *E = bl + nc, *f = E + (size_t)(nc + ntc) * nt;
-            std::memcpy(od + nx * nt + nx, Al, sizeof(double) * kk * nt);
-            std::memcpy(od + nx * nt + nx + k * nt, bl, sizeof(double) * kk);
-            oi[2] = nE; oi[3] = n_om; oi[4] = n_la; oi[5] = n_re; oi[6] = (int32_t)wrow;
-            int32_t *act = oi + 8, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);
-            std::memcpy(act, ri + 5, sizeof(int32_t) * kk);
-            std::memcpy(om, ri + 5 + nc, sizeof(int32_t) * n_om);
-            std::memcpy(la, ri + 5 + nc + ntc, sizeof(int32_t) * n_la);
-            std::memcpy(ridx, ri + 5 + nc + ntc + nc, sizeof(int32_t) * n_re);
-            std::memcpy(rcon, ri + 5 + nc + ntc + nc + nc, sizeof(int32_t) * n_re);
-            for (int r = 0; r < nE; ++r) {
-                double *row = erows + (size_t)(wrow + r) * nr;
-                row[0] = f[r];
-                for (int t = 0; t < nt; ++t) row[1 + t] = E[(size_t)r * nt + t];
-            }
-            wrow += nE;
-        }
-    }
-    if (n_slots) *n_slots = n_opt;
-    if (n_rows) *n_rows = wrow;
-    return MPC_OK;
-}
-
-int mpc_level_regions_slots(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_slots, double *erows, int64_t cap_rows,
-                            int64_t *n_slots, int64_t *n_rows) {
-    return level_regions_slots_impl(h, head_d, head_i, cap_slots, erows, cap_rows, n_slots, n_rows, false, false);
-}
-int mpc_level_regions_slots_async(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_slots, double *erows, int64_t cap_rows,
-                                  int64_t *n_slots, int64_t *n_rows) {
-    return level_regions_slots_impl(h, head_d, head_i, cap_slots, erows, cap_rows, n_slots, n_rows, true, false);
-}
-int mpc_level_regions_slots_nowait(mpc_handle *h, double *head_d, int32_t *head_i, int64_t cap_slots, double *erows, int64_t cap_rows,
-                                   int64_t *n_slots, int64_t *n_rows) {
-    if (!h) return MPC_ERR_INVALID;
-    h->fetch_nowait = true;
-    const int rc = level_regions_slots_impl(h, head_d, head_i, cap_slots, erows, cap_rows, n_slots, n_rows, true, false);
-    h->fetch_nowait = false;
-    return rc;
-}
-// one event per device: "the last k_fetch_many has finished" (recorded on the stream it ran on)
-static std::mutex g_fetch_mutex;
-static std::map<int, hipEvent_t> g_fetch_event;
-// the launch's table, one pair of buffers PER DEVICE: the wait that frees a table for reuse is the same device's previous launch
-static std::map<int, DevBuf> g_fetch_tab_dev_of;
-static std::map<int, HostBuf> g_fetch_tab_host_of;
-static int fetch_many_wait(int device) {
-    // Every copy launch waits for the one before it (its table is reused), so the LATEST record of the device's event covers all earlier
-    // launches: whoever waits -- from any thread, for any member -- waits for that record (a completed event returns at once).
-    hipEvent_t ev = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_fetch_mutex);
-        auto it = g_fetch_event.find(device);
-        if (it == g_fetch_event.end() || !it->second) return MPC_OK;
-        ev = it->second;
-    }
-    return hipEventSynchronize(ev) == hipSuccess ? MPC_OK : MPC_ERR_HIP;
-}
-int mpc_fetch_wait(int32_t device) { return fetch_many_wait(device); }
-
-int mpc_level_batch_fetch(mpc_handle **hs, int32_t n_handles, double *const *head_d, int32_t *const *head_i, const int64_t *cap_slots,
-                          double *const *erows, const int64_t *cap_rows, int64_t *n_slots, int64_t *n_rows) {
-    if (!hs || n_handles < 0 || !head_d || !head_i || !cap_slots || !erows || !cap_rows || !n_slots || !n_rows) return MPC_ERR_INVALID;
-    std::vector<FetchEntry> tab;
-    mpc_handle *lead = nullptr;
-    for (int i = 0; i < n_handles; ++i) {
-        mpc_handle *h = hs[i];
-        if (!h) return MPC_ERR_INVALID;
-        // every record in slot form on the device, nothing streamed, nothing re-solved by the LDS engine: the copy kernel takes the member
-        // (round 5: also a member with candidates re-solved by the LDS-engine kernel -- k_rretry_merge writes their records into the slots first)
-        const long long rows_t = h->n_c - h->n_eq + h->n_tc;
-        const bool merge = h->n_rretry > 0 && h->rretry_rows < 0;
-        const long long rows_out = h->n_rretry > 0 ? h->n_erows + h->n_rretry * rows_t : h->n_erows;   // (bound: a re-solved region keeps at most rows_t rows)
-        const bool fast = h->level_done && !h->so.active && h->n_regions > 0 && h->n_opt > 0 && h->used_region2 &&
-                          h->n_rretry <= RRETRY_MERGE_MAX && h->n_opt <= 0x7fffffffLL &&
-                          (h->n_rretry == 0 || (h->recd.p && h->reci.p && h->retry_list.p && h->epool.cap >= (size_t)rows_out * (h->n_t + 1) * sizeof(double))) &&
-                          cap_slots[i] >= h->n_opt && cap_rows[i] >= rows_out && head_d[i] && head_i[i] && (erows[i] || rows_out == 0) &&
-                          (!lead || lead->device == h->device);
-        void *d_hd = nullptr, *d_hi = nullptr, *d_er = nullptr;
-        if (fast && hipHostGetDevicePointer(&d_hd, head_d[i], 0) == hipSuccess && hipHostGetDevicePointer(&d_hi, head_i[i], 0) == hipSuccess &&
-            (rows_out == 0 || hipHostGetDevicePointer(&d_er, erows[i], 0) == hipSuccess)) {
-            if (!lead) { lead = h; HIP_TRY(lead, hipSetDevice(lead->device)); }
-            if (merge) {
-                if (h->stream != lead->stream) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (a member that took its level alone: its kernels ran on its own stream)
-                RretryMerge a{};
-                a.opt_list = h->opt_ptr; a.rlist = h->retry_list.as<int32_t>(); a.status = h->status.as<uint8_t>(); a.recd = h->recd.as<double>(); a.reci = h->reci.as<int32_t>();
-                a.headd = h->headd.as<double>(); a.headi = h->headi.as<int32_t>(); a.epool = h->epool.as<double>();
-                a.n_opt = (int)h->n_opt; a.n_rretry = (int)h->n_rretry; a.rec_d = (int)h->rec_d; a.rec_i = (int)h->rec_i; a.fd = h->fd; a.fi = h->fi; a.row0 = (int)h->n_erows;
-                a.nx = h->n_x; a.nt = h->n_t; a.nc = h->n_c; a.ntc = h->n_tc; a.k = h->k;
-                hipLaunchKernelGGL(k_rretry_merge, dim3(1), dim3(256), 0, lead->stream, a);
-                HIP_TRY(h, hipGetLastError());
-                h->rretry_rows = rows_out;
-            }
-            tab.push_back({h->headi.p, d_hi, (unsigned long long)h->n_opt * h->fi * sizeof(int32_t)});
-            tab.push_back({h->headd.p, d_hd, (unsigned long long)h->n_opt * h->fd * sizeof(double)});
-            if (rows_out > 0) tab.push_back({h->epool.p, d_er, (unsigned long long)rows_out * (h->n_t + 1) * sizeof(double)});
-            n_slots[i] = h->n_opt; n_rows[i] = rows_out;
-            continue;
-        }
-        (void)hipGetLastError();
-        { const bool dbg = debug_many();
-          if (dbg) std::fprintf(stderr, "[many] member %d outside the copy launch: level_done %d streamed %d regions %lld n_opt %lld region2 %d rretry %lld cap_slots %lld erows %lld cap_rows %lld\n", i, (int)h->level_done, (int)h->so.active,
-                                (long long)h->n_regions, (long long)h->n_opt, (int)h->used_region2, (long long)h->n_rretry, (long long)cap_slots[i], (long long)h->n_erows, (long long)cap_rows[i]); }
-        const int rc = mpc_level_regions_slots_nowait(h, head_d[i], head_i[i], cap_slots[i], erows[i], cap_rows[i], n_slots + i, n_rows + i);
-        if (rc != MPC_OK) return rc;
-    }
-    if (!tab.empty()) {
-        HIP_TRY(lead, hipSetDevice(lead->device));
-        std::lock_guard<std::mutex> lk(g_fetch_mutex);
-        if (g_fetch_event.count(lead->device) && g_fetch_event[lead->device]) HIP_TRY(lead, hipEventSynchronize(g_fetch_event[lead->device]));   // the table of the previous call is free again
-        const size_t bytes = tab.size() * sizeof(FetchEntry);
-        DevBuf &g_fetch_tab_dev = g_fetch_tab_dev_of[lead->device];
-        HostBuf &g_fetch_tab_host = g_fetch_tab_host_of[lead->device];
-        HIP_TRY(lead, g_fetch_tab_host.ensure(bytes));
-        HIP_TRY(lead, g_fetch_tab_dev.ensure(bytes, lead->stream));
-        std::memcpy(g_fetch_tab_host.p, tab.data(), bytes);
-        HIP_TRY(lead, hipMemcpyAsync(g_fetch_tab_dev.p, g_fetch_tab_host.p, bytes, hipMemcpyHostToDevice, lead->stream));
-        hipLaunchKernelGGL(k_fetch_many, dim3(8, (unsigned)tab.size()), dim3(256), 0, lead->stream, g_fetch_tab_dev.as<FetchEntry>());
-        HIP_TRY(lead, hipGetLastError());
-        auto &ev = g_fetch_event[lead->device];
-        if (!ev) HIP_TRY(lead, pooled_event(&ev, false));
-        HIP_TRY(lead, hipEventRecord(ev, lead->stream));
-    }
-    return MPC_OK;
-}
-int mpc_level_stream_fixup(mpc_handle *h, double *head_d, int32_t *head_i, double *erows, int64_t *n_rows) {
-    if (!h || !head_d || !head_i || !erows) return MPC_ERR_INVALID;
-    if (!h->so.active) return fail(h, MPC_ERR_STATE, "mpc_level_stream_fixup: this level was not streamed");
-    { std::lock_guard<std::mutex> lk(h->wm); if (h->w_busy) return fail(h, MPC_ERR_STATE, "the level is still running"); }
-    int64_t ns = 0;
-    return level_regions_slots_impl(h, head_d, head_i, h->so.n_slots, erows, h->so.cap_rows, &ns, n_rows, false, true);
-}
 #ifdef MPC_XQ_HIST
 // debug build only: histogram of k_xq's decisions, [outcome + 1][ratio tests passed]; reset after reading
 int mpc_debug_xq_hist(unsigned long long *out) {
@@ -1954,49 +1604,6 @@ int mpc_host_free(void *p) {
     return host_pool_give(p) ? MPC_OK : MPC_ERR_INVALID;
 }
 
-int mpc_level_regions(mpc_handle *h, double *rec_d, int32_t *rec_i, int64_t *cand_index, int64_t cap) {
-    if (!h) return MPC_ERR_INVALID;
-    if (!h->level_done) return fail(h, MPC_ERR_STATE, "mpc_level_run has not been called for this frontier");
-    if (cap < h->n_regions) return fail(h, MPC_ERR_CAPACITY, "region buffer too small");
-    if (h->n_regions == 0) return MPC_OK;
-    if (!rec_d || !rec_i) return MPC_ERR_INVALID;
-    // fetch in compact form, then expand into the fixed-stride records of the header
-    const int nx = h->n_x, nt = h->n_t, nc = h->n_c, ntc = h->n_tc, k = h->k, nr = nt + 1, fd = h->fd, fi = h->fi;
-    int64_t max_rows = 0, nreg = 0, nrows = 0;
-    mpc_compact_strides(h, nullptr, nullptr, &max_rows);
-    std::vector<double> c_hd((size_t)h->n_regions * fd), c_er((size_t)std::max<int64_t>(max_rows, 1) * nr);
-    std::vector<int32_t> c_hi((size_t)h->n_regions * fi);
-    int rc = mpc_level_regions_compact(h, c_hd.data(), c_hi.data(), h->n_regions, c_er.data(), max_rows, &nreg, &nrows);
-    if (rc) return rc;
-    for (int64_t w = 0; w < nreg; ++w) {
-        double *rd = rec_d + w * h->rec_d;
-        int32_t *ri = rec_i + w * h->rec_i;
-        std::fill(rd, rd + h->rec_d, 0.0);
-        std::fill(ri, ri + h->rec_i, -1);
-        const double *sd = c_hd.data() + w * fd;
-        const int32_t *si = c_hi.data() + w * fi;
-        const int nE = si[2], n_om = si[3], n_la = si[4], n_re = si[5], off = si[6];
-        std::memcpy(rd, sd, sizeof(double) * (nx * nt + nx));
-        double *Al = rd + nx * nt + nx, *bl = Al + (size_t)nc * nt, *E = bl + nc, *f = E + (size_t)(nc + ntc) * nt;
-        std::memcpy(Al, sd + nx * nt + nx, sizeof(double) * k * nt);
-        std::memcpy(bl, sd + nx * nt + nx + k * nt, sizeof(double) * k);
-        for (int r = 0; r < nE; ++r) {
-            const double *row = c_er.data() + (size_t)(off + r) * nr;
-            f[r] = row[0];
-            for (int t = 0; t < nt; ++t) E[(size_t)r * nt + t] = row[1 + t];
-        }
-        ri[0] = k; ri[1] = nE; ri[2] = n_om; ri[3] = n_la; ri[4] = n_re;
-        const int32_t *act = si + 8, *om = act + k, *la = om + ntc, *ridx = la + k, *rcon = ridx + (nc - k);
-        std::memcpy(ri + 5, act, sizeof(int32_t) * k);
-        std::memcpy(ri + 5 + nc, om, sizeof(int32_t) * n_om);
-        std::memcpy(ri + 5 + nc + ntc, la, sizeof(int32_t) * n_la);
-        std::memcpy(ri + 5 + nc + ntc + nc, ridx, sizeof(int32_t) * n_re);
-        std::memcpy(ri + 5 + nc + ntc + nc + nc, rcon, sizeof(int32_t) * n_re);
-        if (cand_index) cand_index[w] = si[1];
-    }
-    return MPC_OK;
-}
-
 static int copy_out(mpc_handle *h, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
     if (bytes == 0) return MPC_OK;
     HIP_TRY(h, hipSetDevice(h->device));
@@ -2023,29 +1630,6 @@ int mpc_level_pruned_new(mpc_handle *h, uint64_t *out, int64_t cap) {
     if (cap < h->n_pruned_new) return fail(h, MPC_ERR_CAPACITY, "pruned buffer too small");
     return copy_out(h, out, h->pruned.as<uint64_t>() + (size_t)h->n_pruned * h->mw, (size_t)h->n_pruned_new * h->mw * sizeof(uint64_t), hipMemcpyDeviceToHost);
 }
-int mpc_level_regions_device(mpc_handle *h, double *head_d_dev, int32_t *head_i_dev, double *erows_dev, int64_t cap_slots,
-                             int64_t cap_rows, int64_t *n_slots, int64_t *n_rows) {
-    if (!h) return MPC_ERR_INVALID;
-    if (!h->level_done) return fail(h, MPC_ERR_STATE, "mpc_level_run has not been called for this frontier");
-    if (n_slots) *n_slots = 0;
-    if (n_rows) *n_rows = 0;
-    if (h->n_regions == 0 || h->n_opt == 0) return MPC_OK;
-    // only the common case lives entirely on the device: every region came from k_region2; otherwise the caller takes the
-    // host route (mpc_level_regions_slots)
-    if (!h->used_region2 || h->n_rretry > 0 || h->so.active) return fail(h, MPC_ERR_STATE, "records of this level are not all in slot form on the device");
-    if (cap_slots < h->n_opt || cap_rows < h->n_erows) return fail(h, MPC_ERR_CAPACITY, "slot / row buffers too small");
-    if (!head_d_dev || !head_i_dev || (!erows_dev && h->n_erows > 0)) return MPC_ERR_INVALID;
-    HIP_TRY(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(head_d_dev, h->headd.p, (size_t)h->n_opt * h->fd * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(head_i_dev, h->headi.p, (size_t)h->n_opt * h->fi * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (h->n_erows > 0) HIP_TRY(h, hipMemcpyAsync(erows_dev, h->epool.p, (size_t)h->n_erows * (h->n_t + 1) * sizeof(double), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    if (n_slots) *n_slots = h->n_opt;
-    if (n_rows) *n_rows = h->n_erows;
-    return MPC_OK;
-}
-
 int mpc_level_pruned_new_device(mpc_handle *h, uint64_t *out, int64_t cap) {
     if (!h || (!out && cap > 0)) return MPC_ERR_INVALID;
     if (!h->level_done) return fail(h, MPC_ERR_STATE, "mpc_level_run has not been called for this frontier");
@@ -2173,15 +1757,8 @@ static void many_loop(ManyJob *J) {
         std::vector<int64_t> fds(nb), fis(nb);
         for (int j = 0; j < nb; ++j) {
             const mpc_handle *h = J->hs[active[j]];
-            const mpc_level_stats &st = L->stats[j];
-            const int k = st.k;
-            fds[j] = (int64_t)h->n_x * h->n_t + h->n_x + (int64_t)k * h->n_t + k;
-            fis[j] = 8 + k + h->n_tc + k + 2 * (h->n_c - k);
-            const int64_t rows_t = h->n_c - h->n_eq + h->n_tc;
-            if (st.n_regions > 0) {
-                L->ns[j] = st.n_opt;
-                L->nr[j] = st.n_region_rows ? st.n_region_rows + st.n_region_retry * rows_t : st.n_regions * rows_t;
-            }
+            const RecordSizes z = level_record_sizes(h, L->stats[j]);
+            fds[j] = z.fd; fis[j] = z.fi; L->ns[j] = z.n_slots; L->nr[j] = z.rows_cap;
             L->od[j] = L->ld; L->oi[j] = L->li; L->oe[j] = L->le;
             L->ld += L->ns[j] * fds[j]; L->li += L->ns[j] * fis[j]; L->le += L->nr[j] * (h->n_t + 1);
         }

@@ -30,6 +30,7 @@ import numpy
 import torch
 import torch.distributed as dist
 
+from ._lib import slot_strides
 from .region_batch import RegionBatch, gc_paused
 from .solution import Solution
 
@@ -537,8 +538,7 @@ def _solve_distributed(engine, program=None, group=None, profile: Optional[List[
                 # this level's regions start their way to every rank now (device buffers, asynchronous all-gathers) and are
                 # collected after the last level
                 kk = int(k)
-                fd = engine.n_x * engine.n_t + engine.n_x + kk * engine.n_t + kk
-                fi = 8 + kk + engine.n_tc + kk + 2 * (engine.n_c - kk)
+                fd, fi = slot_strides(engine.n_x, engine.n_t, engine.n_c, engine.n_tc, kk)
                 if world == 1 and own_regs is not None:
                     pending = (kk, None, own_regs)
                 else:
