@@ -761,6 +761,34 @@ int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions, const int6
                       const int32_t *item_cutter, const int32_t *has_cut, const double *cut_rows, const double *start, double tol,
                       int32_t *flag, uint64_t *mask, int64_t *stats, float *ms);
 
+/* ---- the largest gap between two affine laws over region pairs (Solution.compare) --------------------------------- */
+/* Regions are polytopes of unit rows [o | n] in CSR form, as for the merge and overlap calls above: ONE table, in which the caller
+ * concatenates the regions of both solutions.  laws is n_regions x n_out x (n_t + 1) row-major, row k of region i = [b_i[k] | A_i[k]]:
+ * the law x_k = A_i[k].theta + b_i[k] on the n_out output rows both sides are compared on.  xs (n_regions x n_t) is a point of every
+ * region, from mpc_merge_regions.  Stateless; an error text is read with mpc_last_error(NULL).
+ *
+ * mpc_law_gap_pairs: for every pair (i, j) = (pair_a[k], pair_b[k]) (k_law_gap, one wavefront per pair):
+ *   radius[k]  the Chebyshev radius of X = R_i n R_j, the run started at xs[i] and taken to its optimum.  radius <= tol: the pair does not
+ *              meet (facet neighbours and disjoint regions): gap[k] NaN, gap_row[k] -1, witness and range NaN, flag 0, no law LP.
+ *   otherwise, with delta_r(theta) = (A_i[r] - A_j[r]).theta + (b_i[r] - b_j[r]) for output row r, lo_r = min and hi_r = max of delta_r
+ *   over X: 2 LPs per row in the fixed order row 0 min, row 0 max, row 1 min, ..., each warm-started where the previous one ended, the
+ *   first from the Chebyshev centre.  A row with A_i[r] == A_j[r] in every entry (compared as doubles, no threshold) is constant:
+ *   lo_r = hi_r = b_i[r] - b_j[r] and no LP runs.
+ *   gap[k]     max_r max(-lo_r, hi_r) >= 0.   gap_row[k]: the lowest r that attains it.   witness[k][n_t]: the theta where that run ended
+ *              (the Chebyshev centre when a constant row gives the gap).   range (may be NULL) [k][n_out][2] = lo_r, hi_r.
+ *   flag[k]    1: a bound, not a value.  A radius run that is unbounded (radius +inf) or stopped at the pivot cap (radius: the value
+ *              reached) gives gap +inf, gap_row -1, range NaN, witness the point reached, and no law LP.  A law LP that is unbounded or
+ *              capped gives lo_r = -inf or hi_r = +inf, hence gap +inf.
+ *   pair_a[k] == pair_b[k] is legal (gap 0).  n_pairs == 0: MPC_OK without a launch.
+ *   stats (may be NULL): [0] pairs, [1] pairs that meet, [2] constant rows (no LP), [3] LPs, [4] pivots, [5] unbounded or capped runs.
+ * MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n_t <= 16, 1 <= n_out <= 256, 1..256 rows per region,
+ * finite rows with unit normals, finite laws and xs, tol finite and >= 0, n_pairs in 0..2^31 - 1, pair indices in range.
+ * Deterministic: atomics only in the counters, no floating-point atomics. */
+int mpc_law_gap_pairs(int32_t device, int32_t n_t, int32_t n_out, int64_t n_regions, const int64_t *row_off, const double *ef_rows,
+                      const double *laws, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol,
+                      double *radius, double *gap, int32_t *gap_row, double *witness, double *range, int32_t *flag, int64_t *stats,
+                      float *ms);
+
 /* ---- transition graph of a closed loop between regions (Solution.transition_graph) --------------------------------- */
 /* Regions are polytopes of unit rows [o | n] in CSR form, as for the merge and overlap calls above; region i has the closed-loop map
  * theta+ = Phi_i theta + phi_i (Phi n_regions x n_t x n_t row-major, phi n_regions x n_t).  xs (n_regions x n_t) is a point of every

@@ -271,6 +271,8 @@ def load():
                                            ctypes.c_double, _u64p, _u64p, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_overlap_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_int64, _ip, _ip, _ip, _dp,
                                              ctypes.c_double, _dp, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_law_gap_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip,
+                                             _ip, ctypes.c_double, _dp, _dp, _ip, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_overlap_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
                                              _ip, _ip, _ip, _dp, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_transition_boxes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _dp, _ip, _lp,
@@ -310,7 +312,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
                     'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
-                    'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells']
+                    'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells', 'mpc_law_gap_pairs']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1360,6 +1362,29 @@ def overlap_pairs(row_off, ef_rows, xs, pair_a, pair_b, has_cut, cut_rows, tol: 
     stats = _geometry_call('mpc_overlap_pairs', ('pairs', 'lps', 'pivots', 'capped'), int(device), n_t, R, off, ef, x, n, pa, pb, hc, cut, float(tol),
                            radius, d_min, d_max, flag)
     return radius, d_min, d_max, flag, stats
+
+
+LAW_GAP_KEYS = ('pairs', 'meets', 'constant_rows', 'lps', 'pivots', 'wide')
+
+
+def law_gap_pairs(row_off, ef_rows, laws, xs, pair_a, pair_b, tol: float, ranges: bool = False, device: int = 0):
+    """The largest law gap of every pair of regions (include/mpcombi.h, mpc_law_gap_pairs): laws [R, n_out, n_t + 1] = [b | A];
+    (radius [n_pairs], gap, gap_row int32, witness [n_pairs, n_t], range [n_pairs, n_out, 2] or None, flag int32, stats)."""
+    off, ef = _merge_rows('law_gap_pairs', row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    lw = _f64(numpy.asarray(laws, dtype=numpy.float64))
+    if lw.ndim != 3 or lw.shape[0] != R or lw.shape[2] != n_t + 1:
+        raise MpcError('law_gap_pairs: laws must be [regions, n_out, n_t + 1]')
+    n_out = lw.shape[1]
+    x = _f64(numpy.asarray(xs, dtype=numpy.float64)).reshape(R, n_t)
+    pa, pb = _index_arrays('law_gap_pairs', 'pair_a and pair_b', pair_a, pair_b)
+    n = len(pa)
+    radius, gap, row, witness = numpy.zeros(n), numpy.zeros(n), numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, n_t))
+    rng = numpy.zeros((n, n_out, 2)) if ranges else None
+    flag = numpy.zeros(n, dtype=numpy.int32)
+    stats = _geometry_call('mpc_law_gap_pairs', LAW_GAP_KEYS, int(device), n_t, n_out, R, off, ef, lw, x, n, pa, pb, float(tol), radius, gap, row,
+                           witness, rng, flag)
+    return radius, gap, row, witness, rng, flag, stats
 
 
 def overlap_split(row_off, ef_rows, piece_off, piece_rows, item_piece, item_cutter, has_cut, cut_rows, start, tol: float, device: int = 0):

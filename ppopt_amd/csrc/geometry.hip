@@ -28,6 +28,7 @@
 #include "project.hpp"
 #include "invariant.hpp"
 #include "forward.hpp"
+#include "compare.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1419,6 +1420,52 @@ extern "C" int mpc_overlap_split(int32_t device, int32_t n_t, int64_t n_regions,
     s.download(flag, d_f, ni * 4);
     s.download(mask, d_m, words);
     return family_close(s, d_cnt, 5, stats, ms);
+}
+
+// ---- the largest law gap of region pairs (compare.hpp) -----------------------------------------------------------------
+extern "C" int mpc_law_gap_pairs(int32_t device, int32_t n_t, int32_t n_out, int64_t n_regions, const int64_t *row_off, const double *ef_rows,
+                                 const double *laws, const double *xs, int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b, double tol,
+                                 double *radius, double *gap, int32_t *gap_row, double *witness, double *range, int32_t *flag, int64_t *stats,
+                                 float *ms) {
+    const char *who = "mpc_law_gap_pairs";
+    family_open(stats, 6, ms);
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (n_out < 1 || n_out > LG_MAX_OUT) return bad(who, "n_out must lie in 1..256");
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+    if (n_regions > 0 && (!laws || !xs)) return bad(who, "missing array (laws or xs)");
+    if (int rc = check_finite(who, "laws", laws, n_regions * n_out * (n_t + 1))) return rc;
+    if (int rc = check_finite(who, "xs", xs, n_regions * n_t)) return rc;
+    if (n_pairs == 0) return MPC_OK;
+    if (!pair_a || !pair_b || !radius || !gap || !gap_row || !witness || !flag) return bad(who, "missing array");
+    int pair_rows = 2;     // i == j is legal: a region against itself, gap 0
+    if (int rc = check_indices(who, "a pair names a region out of range", n_pairs, {{pair_a, n_regions, row_off}, {pair_b, n_regions, row_off}}, false,
+                               0, &pair_rows)) return rc;
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = tr_lds_bytes(pair_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static arrays add 408)
+    const size_t np = (size_t)n_pairs, nr = (size_t)n_regions;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_laws = s.upload(laws, nr * n_out * (n_t + 1) * 8), &d_xs = s.upload(xs, nr * n_t * 8);
+    DevBuf &d_pa = s.upload(pair_a, np * 4), &d_pb = s.upload(pair_b, np * 4);
+    DevBuf &d_r = s.buf(np * 8), &d_g = s.buf(np * 8), &d_row = s.buf(np * 4), &d_w = s.buf(np * n_t * 8), &d_f = s.buf(np * 4);
+    DevBuf *d_range = range ? &s.buf(np * n_out * 2 * 8) : nullptr;
+    DevBuf &d_cnt = family_counters(s, 6);
+    LawGapArgs a{};
+    a.nt = n_t; a.m_max = pair_rows; a.n_out = n_out; a.n_pairs = n_pairs;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.laws = d_laws.as<double>(); a.xs = d_xs.as<double>();
+    a.pair_a = d_pa.as<int32_t>(); a.pair_b = d_pb.as<int32_t>(); a.tol = tol;
+    a.radius = d_r.as<double>(); a.gap = d_g.as<double>(); a.witness = d_w.as<double>(); a.range = d_range ? d_range->as<double>() : nullptr;
+    a.gap_row = d_row.as<int32_t>(); a.flag = d_f.as<int32_t>(); a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_law_gap, n_pairs, lds, a);
+    s.download(radius, d_r, np * 8);
+    s.download(gap, d_g, np * 8);
+    s.download(gap_row, d_row, np * 4);
+    s.download(witness, d_w, np * n_t * 8);
+    if (range) s.download(range, *d_range, np * n_out * 2 * 8);
+    s.download(flag, d_f, np * 4);
+    return family_close(s, d_cnt, 6, stats, ms);
 }
 
 // ---- transition graph of a closed loop (transition.hpp) ---------------------------------------------------------------

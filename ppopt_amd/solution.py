@@ -116,6 +116,18 @@ class Solution:
         from .geometry.reduce import reduce_solution
         return reduce_solution(self, tol=tol, device=device)
 
+    def compare(self, other: 'Solution', outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0):
+        """How far this solution's law is from ``other``'s, exactly: a compare.LawGap.  For every region i of this solution and j of the
+        other whose intersection has a Chebyshev radius above tol: the largest |x_self - x_other| over it in any of the rows ``outputs`` of
+        the program's x (None: all rows), the lowest row that attains it and the theta where it does, by one radius LP and up to two LPs
+        per row on the device; max_gap, worst, gap_of_a / gap_of_b, unmatched_a / unmatched_b and equal(atol) summarise them.  A merged
+        solution is compared on the rows it kept.  ``ranges``: the minimum and maximum of every row's difference per pair; ``coverage``:
+        the share of every region's volume that the other side's meeting regions cover.  ValueError before any launch for an empty
+        solution, different n_theta, n_theta > 16, a region of more than 256 rows, a row the merged solution did not keep and a solution
+        flagged overlapping (use remove_overlaps() first).  See compare.py and DESIGN §3.26."""
+        from .compare import compare_solutions
+        return compare_solutions(self, other, outputs=outputs, tol=tol, ranges=ranges, coverage=coverage, device=device)
+
     def evaluate_objective(self, theta_point) -> Optional[float]:
         self._refuse_merged('evaluate_objective')
         x = self.evaluate(theta_point)
