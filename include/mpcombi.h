@@ -789,6 +789,46 @@ int mpc_law_gap_pairs(int32_t device, int32_t n_t, int32_t n_out, int64_t n_regi
                       double *radius, double *gap, int32_t *gap_row, double *witness, double *range, int32_t *flag, int64_t *stats,
                       float *ms);
 
+/* ---- the candidate sweep over bounding boxes and the row screen behind it (geometry.box_pairs) ---------------------- */
+/* Boxes are n x 2 x n_t row-major (lower bounds, then upper bounds) with one usable byte per box.  A NaN lower bound reads as -inf, a NaN
+ * upper bound as +inf.  Stateless; an error text is read with mpc_last_error(NULL).
+ *
+ * mpc_box_pairs: the pairs (i, j), i a box of family a in the row range [i0, i1), j a box of family b, both usable, with
+ *     min(hi_a[i][k], hi_b[j][k]) - max(lo_a[i][k], lo_b[j][k]) > margin      for every coordinate k,
+ *   evaluated in fp64 exactly as written (one subtraction, a strict compare; infinities are ordinary values, an inf - inf that gives
+ *   NaN fails).  mode MPC_BOX_CROSS: every (i, j), i == j included.  MPC_BOX_UPPER: family a against itself, i < j only; family b is left
+ *   out (n_b = 0, NULL) or names family a again.
+ *   total      the number of pairs of the range; always written.
+ *   pair_a, pair_b [cap]  the pairs, ascending by (i, j), written iff 0 < total <= cap: a list that does not fit is not written at all
+ *              and the caller repeats the call with cap >= total.  cap == 0 with NULL pointers is the count-only call.
+ *   row_count  (may be NULL) [i1 - i0] the pairs of every row of the range.
+ *   The order comes from the construction (k_box_pairs counts per (row, segment of family b), an exclusive scan gives every cell its
+ *   offset, a second pass writes in place): no sort, no atomic, two calls give the same bytes.
+ *   stats (may be NULL): [0] box tests (usable a in the range x usable b; UPPER: the usable j > i behind every usable i of the range),
+ *   [1] pairs, [2] segments of family b.  A family (or range) without a usable box: total 0 without a launch.
+ * MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n_t <= 16, an unknown mode, a family with no box,
+ * UPPER with two different families, a row range outside 0 <= i0 <= i1 <= n_a, cap < 0, a margin that is not finite.
+ *
+ * mpc_pair_screen: regions are polytopes of unit rows [o | n] in CSR form, as for the merge and overlap calls above.  For every candidate
+ *   (i, j) = (pair_a[k], pair_b[k]) and every screened side (sides: MPC_SCREEN_ROWS_A, MPC_SCREEN_ROWS_B or both): side A tests the rows of
+ *   region i against box_for_a_rows[j], side B the rows of region j against box_for_b_rows[i]; both tables are n_regions x 2 x n_t, and
+ *   the one of a side that is not screened may be NULL.  With s = sum over ascending k of n_k (lo[k] if n_k > 0 else hi[k]), terms with
+ *   n_k == 0 skipped, the least value of n.theta on the box, a row separates when s - o > 1e-12 (1 + |o|); keep[k] = 0 iff some row
+ *   separates (k_pair_screen, one lane per candidate).  A separated pair has an empty intersection whenever the box contains the set
+ *   it stands for.  stats (may be NULL): [0] pairs, [1] dropped, [2] rows read.
+ * MPC_ERR_INVALID as for mpc_merge_pairs, plus sides outside 1..3 and candidate indices out of range.  n_pairs == 0: MPC_OK without a
+ * launch.  Deterministic: atomics only in the counters. */
+#define MPC_BOX_CROSS 0
+#define MPC_BOX_UPPER 1
+#define MPC_SCREEN_ROWS_A 1
+#define MPC_SCREEN_ROWS_B 2
+int mpc_box_pairs(int32_t device, int32_t n_t, int32_t mode, int64_t n_a, const double *box_a, const uint8_t *usable_a, int64_t n_b,
+                  const double *box_b, const uint8_t *usable_b, double margin, int64_t i0, int64_t i1, int64_t cap, int64_t *pair_a,
+                  int64_t *pair_b, int64_t *row_count, int64_t *total, int64_t *stats, float *ms);
+int mpc_pair_screen(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int64_t n_pairs,
+                    const int64_t *pair_a, const int64_t *pair_b, const double *box_for_a_rows, const double *box_for_b_rows, int32_t sides,
+                    uint8_t *keep, int64_t *stats, float *ms);
+
 /* ---- transition graph of a closed loop between regions (Solution.transition_graph) --------------------------------- */
 /* Regions are polytopes of unit rows [o | n] in CSR form, as for the merge and overlap calls above; region i has the closed-loop map
  * theta+ = Phi_i theta + phi_i (Phi n_regions x n_t x n_t row-major, phi n_regions x n_t).  xs (n_regions x n_t) is a point of every

@@ -273,6 +273,11 @@ def load():
                                              ctypes.c_double, _dp, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_law_gap_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, ctypes.c_int64, _ip,
                                              _ip, ctypes.c_double, _dp, _dp, _ip, _dp, _dp, _ip, _lp, ctypes.POINTER(ctypes.c_float)]),
+        'mpc_box_pairs': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _dp, _u8p, ctypes.c_int64, _dp, _u8p,
+                                         ctypes.c_double, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _lp, _lp, _lp, _lp, _lp,
+                                         ctypes.POINTER(ctypes.c_float)]),
+        'mpc_pair_screen': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_int64, _lp, _lp, _dp, _dp,
+                                           ctypes.c_int32, _u8p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_overlap_split': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, ctypes.c_int64, _lp, _dp, ctypes.c_int64,
                                              _ip, _ip, _ip, _dp, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_transition_boxes': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _dp, _ip, _lp,
@@ -312,7 +317,8 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_tree_build', 'mpc_locator_tree_size', 'mpc_locator_get_tree', 'mpc_locator_set_tree', 'mpc_merge_regions',
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
                     'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
-                    'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells', 'mpc_law_gap_pairs']
+                    'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells', 'mpc_law_gap_pairs', 'mpc_box_pairs',
+                    'mpc_pair_screen']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1270,7 +1276,8 @@ def _merge_rows(who, row_off, ef_rows):
     return off, ef
 
 
-_PTR = {numpy.dtype(numpy.float64): _dp, numpy.dtype(numpy.int64): _lp, numpy.dtype(numpy.int32): _ip, numpy.dtype(numpy.uint64): _u64p}
+_PTR = {numpy.dtype(numpy.float64): _dp, numpy.dtype(numpy.int64): _lp, numpy.dtype(numpy.int32): _ip, numpy.dtype(numpy.uint64): _u64p,
+        numpy.dtype(numpy.uint8): _u8p}
 
 
 def _ptr(a):
@@ -1385,6 +1392,71 @@ def law_gap_pairs(row_off, ef_rows, laws, xs, pair_a, pair_b, tol: float, ranges
     stats = _geometry_call('mpc_law_gap_pairs', LAW_GAP_KEYS, int(device), n_t, n_out, R, off, ef, lw, x, n, pa, pb, float(tol), radius, gap, row,
                            witness, rng, flag)
     return radius, gap, row, witness, rng, flag, stats
+
+
+BOX_CROSS, BOX_UPPER = 0, 1               # mode of mpc_box_pairs (include/mpcombi.h)
+SCREEN_ROWS_A, SCREEN_ROWS_B = 1, 2       # sides of mpc_pair_screen
+BOX_PAIR_KEYS = ('tests', 'pairs', 'segments')
+PAIR_SCREEN_KEYS = ('pairs', 'dropped', 'rows_read')
+
+
+def _boxes(who, box, usable):
+    """a family of mpc_box_pairs: (box [R, 2, n_t] float64, usable [R] uint8), or (None, None) for a family left out"""
+    if box is None:
+        return None, None
+    b = _f64(numpy.asarray(box, dtype=numpy.float64))
+    u = numpy.ascontiguousarray(numpy.asarray(usable).reshape(-1) != 0, dtype=numpy.uint8)
+    if b.ndim != 3 or b.shape[1] != 2 or len(u) != len(b):
+        raise MpcError(f'{who}: boxes must be [R, 2, n_t] with one usable entry per box')
+    return b, u
+
+
+def box_pairs(box_a, usable_a, box_b, usable_b, margin: float, i0: int, i1: int, cap: int, pair_a=None, pair_b=None, row_counts: bool = False,
+              device: int = 0):
+    """The candidate sweep (include/mpcombi.h, mpc_box_pairs): family b None is BOX_UPPER.  ``pair_a``, ``pair_b``: int64 arrays of at
+    least ``cap`` entries to write into (made here when None and cap > 0).  (total, pair_a, pair_b, row_count or None, stats): the
+    arrays as given, filled with the ``total`` pairs iff 0 < total <= cap and untouched otherwise."""
+    who = 'box_pairs'
+    ba, ua = _boxes(who, box_a, usable_a)
+    bb, ub = _boxes(who, box_b, usable_b)
+    if ba is None:
+        raise MpcError(f'{who}: family a is missing')
+    if bb is not None and bb.shape[2] != ba.shape[2]:
+        raise MpcError(f'{who}: the two families must have the same n_t')
+    cap = int(cap)
+    if cap > 0:
+        pair_a = numpy.zeros(cap, dtype=numpy.int64) if pair_a is None else pair_a
+        pair_b = numpy.zeros(cap, dtype=numpy.int64) if pair_b is None else pair_b
+        for p in (pair_a, pair_b):
+            if not (isinstance(p, numpy.ndarray) and p.dtype == numpy.int64 and p.ndim == 1 and len(p) >= cap and p.flags.c_contiguous):
+                raise MpcError(f'{who}: pair_a and pair_b must be contiguous int64 arrays of at least cap entries')
+    rc = numpy.zeros(max(int(i1) - int(i0), 0), dtype=numpy.int64) if row_counts else None
+    total = numpy.zeros(1, dtype=numpy.int64)
+    stats = _geometry_call('mpc_box_pairs', BOX_PAIR_KEYS, int(device), ba.shape[2], BOX_UPPER if bb is None else BOX_CROSS, len(ba), ba, ua,
+                           0 if bb is None else len(bb), bb, ub, float(margin), int(i0), int(i1), cap, pair_a if cap > 0 else None,
+                           pair_b if cap > 0 else None, rc, total)
+    return int(total[0]), pair_a, pair_b, rc, stats
+
+
+def pair_screen(row_off, ef_rows, pair_a, pair_b, box_for_a_rows, box_for_b_rows, sides: int, device: int = 0):
+    """The row screen of a candidate list (include/mpcombi.h, mpc_pair_screen): (keep [n_pairs] uint8, stats)."""
+    who = 'pair_screen'
+    off, ef = _merge_rows(who, row_off, ef_rows)
+    n_t, R = ef.shape[1] - 1, len(off) - 1
+    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int64).reshape(-1)
+    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int64).reshape(-1)
+    if pa.shape != pb.shape:
+        raise MpcError(f'{who}: pair_a and pair_b must have the same length')
+    boxes = []
+    for b in (box_for_a_rows, box_for_b_rows):
+        if b is not None:
+            b = _f64(numpy.asarray(b, dtype=numpy.float64))
+            if b.shape != (R, 2, n_t):
+                raise MpcError(f'{who}: a box table must be [regions, 2, n_t]')
+        boxes.append(b)
+    keep = numpy.ones(len(pa), dtype=numpy.uint8)
+    stats = _geometry_call('mpc_pair_screen', PAIR_SCREEN_KEYS, int(device), n_t, R, off, ef, len(pa), pa, pb, boxes[0], boxes[1], int(sides), keep)
+    return keep, stats
 
 
 def overlap_split(row_off, ef_rows, piece_off, piece_rows, item_piece, item_cutter, has_cut, cut_rows, start, tol: float, device: int = 0):

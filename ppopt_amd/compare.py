@@ -14,8 +14,10 @@ same K output rows.  For a region i of A and a region j of B:
            unbounded or capped law LP gives lo = -inf or hi = +inf, hence gap +inf.
 
 Stages: unit rows of both solutions in ONE region table (A's regions, then B's); feasible points and boxes (_lib.merge_regions);
-candidate pairs whose boxes overlap by more than tol in every coordinate (cross_box_pairs, a host sweep); per candidate the radius LP
-and up to 2 K law LPs on the device (csrc/compare.hpp, k_law_gap, one wavefront per pair).
+candidate pairs whose boxes overlap by more than tol in every coordinate (cross_box_pairs, a host sweep, or with sweep='device'
+geometry.box_pairs); with screen='rows' the candidates that one row of either region separates from the other's box are dropped
+(geometry.screen_pairs); per remaining candidate the radius LP and up to 2 K law LPs on the device (csrc/compare.hpp,
+k_law_gap, one wavefront per pair).
 
 Out of scope: gaps of value functions (a difference of quadratics is no LP), jumps across shared facets (radius 0), solutions flagged
 overlapping (reduce them with remove_overlaps first).
@@ -305,13 +307,20 @@ def _coverage(off, rows, n_t, n_a, res, tol, device):
     return covered[:n_a], covered[n_a:]
 
 
-def compare_solutions(a, b, outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0) -> LawGap:
+def compare_solutions(a, b, outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0,
+                      sweep: str = 'host', screen: str = 'none') -> LawGap:
     """Solution.compare (the module docstring): a LawGap between the laws of ``a`` and ``b`` on the rows ``outputs`` of the program's x
     (None: all rows, which then must be equal in number on both sides).  For a merged solution, whose regions keep only
     merge_info['outputs'], the rows are mapped onto the ones it kept.  ``coverage``: covered_a[i] = sum_j vol(X_ij) / vol(R_i) and
     covered_b likewise, by geometry.reduce_rows_of on the stacked rows of the meeting pairs and geometry.polytope_volumes; exact when the
-    other side does not overlap itself, and within their limits (ValueError naming the one that was hit).  Neither solution is modified."""
+    other side does not overlap itself, and within their limits (ValueError naming the one that was hit).  Neither solution is modified.
+    ``sweep`` = 'device': the candidates come from geometry.box_pairs instead of cross_box_pairs, the same list, so every result is the
+    same bit for bit.  ``screen`` = 'rows': candidates that a single row separates from the partner's box never reach the LPs; the
+    per-pair arrays then hold the kept candidates only (every meeting pair is among them), and stats gains box_candidates, screened
+    and screen_ms.  ValueError for any other value."""
     from . import _lib
+    from .geometry.box_pairs import box_pairs, screen_pairs, sweep_options
+    on_device, rows_screen = sweep_options('compare', sweep, screen)
     t0 = time.perf_counter()
     n_t, rows_a, rows_b = check_sources(a, b, outputs, tol)
     off_a, ef_a, void_a = solution_rows(a.critical_regions, n_t, 'compare')
@@ -328,13 +337,25 @@ def compare_solutions(a, b, outputs=None, tol: float = 1e-8, ranges: bool = Fals
     usable[[n_a + i for i in void_b]] = False
     xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
     t1 = time.perf_counter()
-    pa, pb = cross_box_pairs(box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], tol)
+    sweep_stats = {}
+    if on_device:
+        pa, pb, sw = box_pairs(box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], margin=tol, device=device)
+        sweep_stats = {'sweep_kernel_ms': sw['ms']}
+    else:
+        pa, pb = cross_box_pairs(box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], tol)
     sweep_ms = (time.perf_counter() - t1) * 1e3
+    if rows_screen:
+        t1 = time.perf_counter()
+        keep, sc = screen_pairs(off, ef, pa, pb + n_a, box, box, sides='both', device=device)
+        sweep_stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
+        pa, pb = pa[keep], pb[keep]
+        sweep_stats['screen_ms'] = (time.perf_counter() - t1) * 1e3
     res = law_gap_pairs(off, ef, laws, pa, pb + n_a, tol=tol, xs=xs, ranges=ranges, device=device)
     res['i'], res['j'] = pa, pb
     stats = dict(res['stats'])
     stats['device_ms'] += s['ms']
     stats.update(candidates=len(pa), box_pairs=int(usable[:n_a].sum()) * int(usable[n_a:].sum()), sweep_ms=sweep_ms)
+    stats.update(sweep_stats)
     covered_a = covered_b = None
     if coverage:
         covered_a, covered_b = _coverage(off, ef, n_t, n_a, res, tol, device)

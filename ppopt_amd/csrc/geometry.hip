@@ -4,6 +4,7 @@
 // and nowhere else (locate.hpp, tree.hpp, closed_loop.hpp, vertices.hpp, volume.hpp, merge.hpp, overlap.hpp, transition.hpp, exit_sets.hpp, reduce.hpp, project.hpp, simplex.hpp); the pools and the scaffold
 // of a one-shot call (OneShot, select_device) are host_common.hpp.
 #include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -29,6 +30,7 @@
 #include "invariant.hpp"
 #include "forward.hpp"
 #include "compare.hpp"
+#include "box_pairs.hpp"
 #include "host_common.hpp"
 
 using namespace mpc;
@@ -1466,6 +1468,136 @@ extern "C" int mpc_law_gap_pairs(int32_t device, int32_t n_t, int32_t n_out, int
     if (range) s.download(range, *d_range, np * n_out * 2 * 8);
     s.download(flag, d_f, np * 4);
     return family_close(s, d_cnt, 6, stats, ms);
+}
+
+// ---- the candidate sweep and the row screen (box_pairs.hpp) -----------------------------------------------------------
+template <bool EMIT> static void box_pairs_launch(dim3 grid, const BoxPairArgs &a) {
+    if (a.nt <= 4) hipLaunchKernelGGL((k_box_pairs<4, EMIT>), grid, dim3(BP_BLOCK), 0, nullptr, a);
+    else if (a.nt <= 8) hipLaunchKernelGGL((k_box_pairs<8, EMIT>), grid, dim3(BP_BLOCK), 0, nullptr, a);
+    else hipLaunchKernelGGL((k_box_pairs<16, EMIT>), grid, dim3(BP_BLOCK), 0, nullptr, a);
+}
+
+extern "C" int mpc_box_pairs(int32_t device, int32_t n_t, int32_t mode, int64_t n_a, const double *box_a, const uint8_t *usable_a, int64_t n_b,
+                             const double *box_b, const uint8_t *usable_b, double margin, int64_t i0, int64_t i1, int64_t cap, int64_t *pair_a,
+                             int64_t *pair_b, int64_t *row_count, int64_t *total, int64_t *stats, float *ms) {
+    const char *who = "mpc_box_pairs";
+    family_open(stats, 3, ms);
+    if (total) *total = 0;
+    if (n_t < 1 || n_t > BP_MAX_NT) return bad(who, "n_t must lie in 1..16");
+    if (mode != BP_CROSS && mode != BP_UPPER) return bad(who, "mode must be 0 (CROSS) or 1 (UPPER)");
+    if (n_a < 1 || (mode == BP_CROSS && n_b < 1)) return bad(who, "a family has no box");
+    if (!box_a || !usable_a || !total || (mode == BP_CROSS && (!box_b || !usable_b))) return bad(who, "missing array");
+    if (mode == BP_UPPER) {
+        if ((box_b && box_b != box_a) || (usable_b && usable_b != usable_a) || (n_b != n_a && n_b != 0))
+            return bad(who, "UPPER takes one family against itself: leave family b out or pass family a again");
+        n_b = n_a; box_b = box_a; usable_b = usable_a;
+    }
+    if (n_a > 0x7fffffffll || n_b > 0x7fffffffll) return bad(who, "too many boxes for one launch");
+    if (i0 < 0 || i1 < i0 || i1 > n_a) return bad(who, "the row range must lie in 0 <= i0 <= i1 <= n_a");
+    if (cap < 0) return bad(who, "cap must be >= 0");
+    if (cap > 0 && (!pair_a || !pair_b)) return bad(who, "missing array (pair_a or pair_b with cap > 0)");
+    if (!std::isfinite(margin)) return bad(who, "margin must be finite");
+    const int64_t rows = i1 - i0;
+    if (row_count) std::fill(row_count, row_count + rows, (int64_t)0);
+    // the box tests of the range: usable a x usable b, for UPPER the usable j > i behind every usable i
+    int64_t tests = 0, ua = 0, ub = 0;
+    for (int64_t j = 0; j < n_b; ++j) ub += usable_b[j] != 0;
+    if (mode == BP_CROSS) {
+        for (int64_t i = i0; i < i1; ++i) ua += usable_a[i] != 0;
+        tests = ua * ub;
+    } else {
+        int64_t behind = 0;
+        for (int64_t i = n_a - 1; i >= i0; --i) {
+            if (usable_a[i] && i < i1) tests += behind;
+            behind += usable_a[i] != 0;
+        }
+    }
+    if (stats) stats[0] = tests;
+    if (tests == 0) return MPC_OK;      // a family (or the range) without a usable box: no pair, no launch
+    if (int rc = select_device(nullptr, device)) return rc;
+    const long long row_blocks = (rows + BP_BLOCK - 1) / BP_BLOCK, n_tiles = (n_b + BP_TILE - 1) / BP_TILE;
+    // segments: about four workgroups per CU, at most BP_MAX_SEG, every one a whole number of tiles
+    long long n_seg = std::min<long long>({n_tiles, (long long)BP_MAX_SEG, (4ll * std::max(1, cu_count(device)) + row_blocks - 1) / row_blocks});
+    const long long seg_tiles = (n_tiles + n_seg - 1) / n_seg;
+    n_seg = (n_tiles + seg_tiles - 1) / seg_tiles;
+    const size_t n_cells = (size_t)rows * (size_t)n_seg, box_bytes_a = (size_t)n_a * 2 * n_t * 8, box_bytes_b = (size_t)n_b * 2 * n_t * 8;
+    OneShot s(who, nullptr, true);
+    DevBuf &d_ba = s.upload(box_a, box_bytes_a), &d_ua = s.upload(usable_a, (size_t)n_a);
+    DevBuf &d_bb = mode == BP_UPPER ? d_ba : s.upload(box_b, box_bytes_b), &d_ub = mode == BP_UPPER ? d_ua : s.upload(usable_b, (size_t)n_b);
+    DevBuf &d_cnt = s.buf((n_cells + 1) * 8), &d_off = s.buf((n_cells + 1) * 8);
+    s.fill(d_cnt, 0, (n_cells + 1) * 8);    // the entry behind the last cell stays 0: the scan leaves the total there
+    size_t tmp_bytes = 0;
+    s.chk(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt.as<unsigned long long>(), d_off.as<unsigned long long>(), 0ull, n_cells + 1,
+                                  rocprim::plus<unsigned long long>(), nullptr));
+    DevBuf &d_tmp = s.buf(std::max<size_t>(8, tmp_bytes));
+    BoxPairArgs a{};
+    a.nt = n_t; a.mode = mode; a.n_seg = (int)n_seg; a.seg_tiles = (int)seg_tiles; a.n_b = n_b; a.n_tiles = n_tiles; a.i0 = i0; a.rows = rows;
+    a.box_a = d_ba.as<double>(); a.box_b = d_bb.as<double>(); a.usable_a = d_ua.as<uint8_t>(); a.usable_b = d_ub.as<uint8_t>();
+    a.margin = margin; a.counts = d_cnt.as<unsigned long long>(); a.offsets = d_off.as<unsigned long long>();
+    const dim3 grid((unsigned)row_blocks, (unsigned)n_seg);
+    DevBuf *d_rc = row_count ? &s.buf((size_t)rows * 8) : nullptr;
+    s.launch_timed([&] {
+        box_pairs_launch<false>(grid, a);
+        s.chk(rocprim::exclusive_scan(d_tmp.p, tmp_bytes, d_cnt.as<unsigned long long>(), d_off.as<unsigned long long>(), 0ull, n_cells + 1,
+                                      rocprim::plus<unsigned long long>(), nullptr));
+        if (d_rc && s.ok())
+            hipLaunchKernelGGL(k_box_row_counts, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, nullptr, (long long)rows, (int)n_seg,
+                               d_off.as<unsigned long long>(), d_rc->as<long long>());
+    });
+    unsigned long long n_pairs = 0;
+    s.download(&n_pairs, DevBuf{d_off.as<unsigned long long>() + n_cells, 8}, 8);    // a blocking copy: the count pass has ended
+    if (d_rc) s.download(row_count, *d_rc, (size_t)rows * 8);
+    float ms_count = 0.0f, ms_emit = 0.0f;
+    s.elapsed(&ms_count);
+    if (!s.ok()) return s.finish();
+    *total = (int64_t)n_pairs;
+    if (stats) { stats[1] = (int64_t)n_pairs; stats[2] = n_seg; }
+    if (cap > 0 && n_pairs > 0 && n_pairs <= (unsigned long long)cap) {      // a list that does not fit is not written at all
+        DevBuf &d_pa = s.buf((size_t)n_pairs * 8), &d_pb = s.buf((size_t)n_pairs * 8);
+        a.pair_a = d_pa.as<long long>(); a.pair_b = d_pb.as<long long>();
+        s.launch_timed([&] { box_pairs_launch<true>(grid, a); });
+        s.download(pair_a, d_pa, (size_t)n_pairs * 8);
+        s.download(pair_b, d_pb, (size_t)n_pairs * 8);
+        s.elapsed(&ms_emit);
+    }
+    if (ms) *ms = ms_count + ms_emit;
+    return s.finish();
+}
+
+extern "C" int mpc_pair_screen(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, int64_t n_pairs,
+                               const int64_t *pair_a, const int64_t *pair_b, const double *box_for_a_rows, const double *box_for_b_rows,
+                               int32_t sides, uint8_t *keep, int64_t *stats, float *ms) {
+    const char *who = "mpc_pair_screen";
+    family_open(stats, 3, ms);
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_max)) return rc;
+    if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+    if (sides < 1 || sides > (PS_SIDE_A | PS_SIDE_B)) return bad(who, "sides must be 1 (rows of a), 2 (rows of b) or 3 (both)");
+    if (n_pairs == 0) return MPC_OK;
+    if (!pair_a || !pair_b || !keep || ((sides & PS_SIDE_A) && !box_for_a_rows) || ((sides & PS_SIDE_B) && !box_for_b_rows)) return bad(who, "missing array");
+    for (int64_t k = 0; k < n_pairs; ++k)
+        if (pair_a[k] < 0 || pair_a[k] >= n_regions || pair_b[k] < 0 || pair_b[k] >= n_regions) return bad(who, "a pair names a region out of range");
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t np = (size_t)n_pairs, box_bytes = (size_t)n_regions * 2 * n_t * 8;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
+    DevBuf &d_pa = s.upload(pair_a, np * 8), &d_pb = s.upload(pair_b, np * 8);
+    DevBuf *d_xa = (sides & PS_SIDE_A) ? &s.upload(box_for_a_rows, box_bytes) : nullptr;
+    DevBuf *d_xb = !(sides & PS_SIDE_B) ? nullptr : (box_for_b_rows == box_for_a_rows && d_xa) ? d_xa : &s.upload(box_for_b_rows, box_bytes);
+    DevBuf &d_keep = s.buf(np), &d_cnt = family_counters(s, 3);
+    PairScreenArgs a{};
+    a.nt = n_t; a.sides = sides; a.n_pairs = n_pairs; a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>();
+    a.pair_a = d_pa.as<long long>(); a.pair_b = d_pb.as<long long>();
+    a.box_for_a = d_xa ? d_xa->as<double>() : nullptr; a.box_for_b = d_xb ? d_xb->as<double>() : nullptr;
+    a.keep = d_keep.as<uint8_t>(); a.counters = d_cnt.as<unsigned long long>();
+    const dim3 grid((unsigned)((n_pairs + 255) / 256));
+    s.launch_timed([&] {
+        if (n_t <= 4) hipLaunchKernelGGL(k_pair_screen<4>, grid, dim3(256), 0, nullptr, a);
+        else if (n_t <= 8) hipLaunchKernelGGL(k_pair_screen<8>, grid, dim3(256), 0, nullptr, a);
+        else hipLaunchKernelGGL(k_pair_screen<16>, grid, dim3(256), 0, nullptr, a);
+    });
+    s.download(keep, d_keep, np);
+    return family_close(s, d_cnt, 3, stats, ms);
 }
 
 // ---- transition graph of a closed loop (transition.hpp) ---------------------------------------------------------------

@@ -6,4 +6,5 @@ from .reduce import ReducedRows, reduce_polytopes, reduce_rows_of
 from .project import ProjectedRows, affine_image, controllable_pre, minkowski_sum, project_polytopes, project_rows_of
 from .slice import LineSlice, SolutionSlice, slice_polytopes
 from .moments import ExpectedValues, RegionMoments, integrate_quadratic, moments_of_rows, polytope_moments
+from .box_pairs import box_pairs, screen_pairs
 from .volume import CoverageVolume, RegionVolumes, polytope_volumes, volumes_of_rows

@@ -11,7 +11,8 @@ tie rule of Solution.get_region).  The procedure is deterministic:
      with |g| that small and |h| not, the cheaper region is cheaper everywhere (d_min = d_max = +-inf by the sign of h, no LP);
      otherwise the cut row of the pair is the unit row of {J_j <= J_i}, [h / |g| | -g / |g|], and d(theta) = (J_i - J_j) / |g| the depth
      behind it;
-  3. candidate pairs i < j: boxes overlapping by more than tol in every coordinate.  On the device (csrc/overlap.hpp,
+  3. candidate pairs i < j: boxes overlapping by more than tol in every coordinate (box_pairs, a host sweep, or with sweep='device'
+     geometry.box_pairs; screen='rows' drops the candidates that a row of one region separates from the other's box).  On the device (csrc/overlap.hpp,
      k_overlap_pairs): r = the Chebyshev radius of R_i n R_j, and d_min, d_max over it.  Verdicts, first match:
        a radius run unbounded or capped  EQUAL when value-equal, else CROSSING      r <= tol          DISJOINT
        value-equal                       EQUAL    (i is cut by R_j)                  d_max <= tol      I_WINS  (j is cut by R_i)
@@ -181,13 +182,25 @@ def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, m
     return live, round_ms
 
 
+def _device_box_pairs(box, usable, tol: float, device: int):
+    """box_pairs by geometry.box_pairs.  box_pairs does not open a NaN bound: a box that holds one meets nothing there, so it is masked
+    here.  (Boxes of usable regions carry no NaN unless a simplex run overflowed: DESIGN §3.27.)"""
+    from .geometry.box_pairs import box_pairs as device_pairs
+    return device_pairs(box, usable & ~numpy.isnan(box).any(axis=(1, 2)), margin=tol, device=device)
+
+
 def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20,
-                       device: int = 0, void=(), reduce_rows: bool = False) -> OverlapPartition:
+                       device: int = 0, void=(), reduce_rows: bool = False, sweep: str = 'host', screen: str = 'none') -> OverlapPartition:
     """The partition of the polytopes {n.theta <= o} (unit rows ef_rows = [o | n] in CSR form by row_off) by the lowest affine value
     g_i.theta + h_i: an OverlapPartition.  Steps 2 to 4 of the module docstring; every LP runs on the device.  ``void``: polytopes
     known to be empty (they vanish and cut nothing), like the ones the device finds empty.  ``reduce_rows``: the children of every
-    round lose their redundant rows (difference_rounds, ``reduce``)."""
+    round lose their redundant rows (difference_rounds, ``reduce``).  ``sweep`` = 'device': the candidates of step 3 come from
+    geometry.box_pairs, the same list as box_pairs gives; ``screen`` = 'rows': the candidates that a single row separates from the partner's
+    box never reach the pair stage (they could only be DISJOINT), ``pairs`` holds the kept ones and stats gains box_candidates, screened,
+    screen_ms.  With either, stats also holds sweep_ms, the wall time of the sweep."""
     from . import _lib
+    from .geometry.box_pairs import screen_pairs, sweep_options
+    on_device, rows_screen = sweep_options('partition_by_value', sweep, screen)
     t0 = time.perf_counter()
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
     ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
@@ -214,7 +227,22 @@ def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, valu
     usable[list(void)] = False
     xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
     # 2. values
-    pa, pb = box_pairs(box, usable, tol)
+    if on_device or rows_screen:
+        t1 = time.perf_counter()
+        if on_device:
+            pa, pb, sw = _device_box_pairs(box, usable, tol, device)
+            stats['sweep_kernel_ms'] = sw['ms']
+        else:
+            pa, pb = box_pairs(box, usable, tol)
+        stats['sweep_ms'] = (time.perf_counter() - t1) * 1e3
+    else:
+        pa, pb = box_pairs(box, usable, tol)
+    if rows_screen:
+        t1 = time.perf_counter()
+        keep, sc = screen_pairs(off, ef, pa, pb, box, box, sides='both', device=device)
+        stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
+        pa, pb = pa[keep], pb[keep]
+        stats['screen_ms'] = (time.perf_counter() - t1) * 1e3
     n_pairs = len(pa)
     stats['candidate_pairs'] = n_pairs
     g_thr = value_tol * (1.0 + float(numpy.max(numpy.linalg.norm(g, axis=1))))
@@ -335,13 +363,17 @@ def check_source(source, tol: float, value_tol: float, max_pieces: int):
     return n_t, qv, rv
 
 
-def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0, reduce_rows: bool = False):
+def remove_overlaps(source, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0, reduce_rows: bool = False,
+                    sweep: str = 'host', screen: str = 'none'):
     """Solution.remove_overlaps (the module docstring).  Returns a new Solution of ReducedRegion; the source is not modified.
-    ``reduce_rows``: the pieces lose their redundant rows round by round (partition_by_value)."""
+    ``reduce_rows``: the pieces lose their redundant rows round by round (partition_by_value).  ``sweep``, ``screen``: where the candidate
+    pairs come from and whether rows screen them (partition_by_value); the reduced solution is the same either way."""
+    from .geometry.box_pairs import sweep_options
+    sweep_options('remove_overlaps', sweep, screen)
     t0 = time.perf_counter()
     n_t, qv, rv = check_source(source, tol, value_tol, max_pieces)
     off, rows, void = solution_rows(source.critical_regions, n_t, 'remove_overlaps')
     part = partition_by_value(off, rows, qv, rv, n_t, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device,
-                              void=void, reduce_rows=reduce_rows)
+                              void=void, reduce_rows=reduce_rows, sweep=sweep, screen=screen)
     part.stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
     return build_reduced_solution(source, part.sources, part.pieces, part.verdict_counts, part.vanished, part.stats)

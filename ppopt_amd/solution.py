@@ -95,7 +95,7 @@ class Solution:
         return merge_regions(self, outputs=outputs, tol=tol, law_tol=law_tol, device=device)
 
     def remove_overlaps(self, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20, device: int = 0,
-                        reduce_rows: bool = False) -> 'Solution':
+                        reduce_rows: bool = False, sweep: str = 'host', screen: str = 'none') -> 'Solution':
         """A new, non-overlapping solution: every region keeps only the part of the parameter space where its value function is the
         lowest among the regions that contain the point (ties to the higher index, as get_region resolves them), as convex pieces
         (overlap.ReducedRegion with ``source``), ordered by source; the pair comparisons and the region differences are LPs on the device
@@ -103,9 +103,11 @@ class Solution:
         ValueError before any launch for an empty or merged solution, n_theta > 16, a region of more than 256 rows, non-finite
         tolerances and value functions with different quadratic parts (mpQP / mpMIQP); after a round for a piece of more than 256
         rows or more than max_pieces pieces.  ``reduce_rows``: the pieces lose their redundant rows round by round on the device, before
-        the row limit is checked (off by default)."""
+        the row limit is checked (off by default).  ``sweep`` = 'device' lists the candidate pairs on the device (the same
+        list), ``screen`` = 'rows' drops the candidates one row already separates; the result is the same either way."""
         from .overlap import remove_overlaps
-        return remove_overlaps(self, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows)
+        return remove_overlaps(self, tol=tol, value_tol=value_tol, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows, sweep=sweep,
+                               screen=screen)
 
     def reduce_rows(self, tol: float = 1e-8, device: int = 0) -> 'Solution':
         """A new solution whose regions have lost their redundant rows by the sequential rule of geometry.reduce, for
@@ -116,7 +118,8 @@ class Solution:
         from .geometry.reduce import reduce_solution
         return reduce_solution(self, tol=tol, device=device)
 
-    def compare(self, other: 'Solution', outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0):
+    def compare(self, other: 'Solution', outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0,
+                sweep: str = 'host', screen: str = 'none'):
         """How far this solution's law is from ``other``'s, exactly: a compare.LawGap.  For every region i of this solution and j of the
         other whose intersection has a Chebyshev radius above tol: the largest |x_self - x_other| over it in any of the rows ``outputs`` of
         the program's x (None: all rows), the lowest row that attains it and the theta where it does, by one radius LP and up to two LPs
@@ -124,9 +127,12 @@ class Solution:
         solution is compared on the rows it kept.  ``ranges``: the minimum and maximum of every row's difference per pair; ``coverage``:
         the share of every region's volume that the other side's meeting regions cover.  ValueError before any launch for an empty
         solution, different n_theta, n_theta > 16, a region of more than 256 rows, a row the merged solution did not keep and a solution
-        flagged overlapping (use remove_overlaps() first).  See compare.py and DESIGN §3.26."""
+        flagged overlapping (use remove_overlaps() first).  ``sweep`` = 'device' lists the candidate pairs on the device (the same list,
+        the same result bit for bit); ``screen`` = 'rows' drops the candidates one row already separates, and the per-pair arrays then hold
+        the kept candidates only.  See compare.py and DESIGN §3.26."""
         from .compare import compare_solutions
-        return compare_solutions(self, other, outputs=outputs, tol=tol, ranges=ranges, coverage=coverage, device=device)
+        return compare_solutions(self, other, outputs=outputs, tol=tol, ranges=ranges, coverage=coverage, device=device, sweep=sweep,
+                                 screen=screen)
 
     def evaluate_objective(self, theta_point) -> Optional[float]:
         self._refuse_merged('evaluate_objective')
@@ -331,16 +337,19 @@ class Solution:
         from .invariance import certify_recursive_feasibility
         return certify_recursive_feasibility(self, A, B, inputs, c=c, disturbance=disturbance, tol=tol, device=device)
 
-    def transition_graph(self, A, B, inputs, c=None, tol: float = 1e-8, full_radius: bool = False, device: int = 0):
+    def transition_graph(self, A, B, inputs, c=None, tol: float = 1e-8, full_radius: bool = False, device: int = 0, sweep: str = 'host',
+                         screen: str = 'none'):
         """Which region can follow which under the plant theta+ = A theta + B u + c with this controller's law u = x*(theta)[inputs]: a
         transition.TransitionGraph (successors in CSR form, per edge radius, status and witness; reachable, steps_to, cycles_outside).
         i -> j is an edge iff {theta in R_i : its image lies in R_j} has a Chebyshev radius above tol, one LP per candidate pair on the
         device; ``full_radius`` runs every LP to its optimum.  Transitions through a facet or a vertex are not edges, so statements about
         trajectories hold for almost every initial state.  ValueError before any launch for mixed-integer solutions, solutions flagged
         overlapping that have not been through remove_overlaps, and the arguments certify_recursive_feasibility refuses; merged
-        solutions and reduced continuous ones are accepted.  See transition.py and DESIGN §3.20."""
+        solutions and reduced continuous ones are accepted.  ``sweep`` = 'device' lists the candidate pairs on the device (the same list),
+        ``screen`` = 'rows' drops the candidates that a row of the target separates from the image box; the graph is the same
+        either way.  See transition.py and DESIGN §3.20."""
         from .transition import transition_graph
-        return transition_graph(self, A, B, inputs, c=c, tol=tol, full_radius=full_radius, device=device)
+        return transition_graph(self, A, B, inputs, c=c, tol=tol, full_radius=full_radius, device=device, sweep=sweep, screen=screen)
 
     def exit_sets(self, A, B, inputs, c=None, tol: float = 1e-8, graph=None, max_pieces: int = 1 << 20, device: int = 0,
                   reduce_rows: bool = False):
@@ -351,7 +360,9 @@ class Solution:
         of the region difference.  A run that is unbounded or capped keeps its piece and flags it wide: the pieces never lose a state
         that exits.  Refusals as for transition_graph, and ValueError after a round that leaves a piece above 256 rows or more than
         max_pieces pieces.  ``reduce_rows``: the pieces lose their redundant rows round by round on the device, before the row limit is
-        checked (off by default); ExitSets.reduced() does the same to a finished result.  See exit_sets.py and DESIGN §3.21."""
+        checked (off by default); ExitSets.reduced() does the same to a finished result.  A graph built with
+        transition_graph(sweep='device', screen='rows') is passed as ``graph``; no argument of its own is needed.  See exit_sets.py and
+        DESIGN §3.21."""
         from .exit_sets import exit_sets
         return exit_sets(self, A, B, inputs, c=c, tol=tol, graph=graph, max_pieces=max_pieces, device=device, reduce_rows=reduce_rows)
 
@@ -363,7 +374,8 @@ class Solution:
         ``exits``, the exit_sets of the same arguments, the predecessors come from ``graph``, the transition_graph (each built when None);
         every later step runs on the device inside one library call, until a step yields no cell (converged) or max_steps, max_cells or
         the 256-row limit of a cell stops it (status).  Wide cells over-approximate what leaves; parts thinner than tol are not reported.
-        Refusals as for transition_graph.  See invariant_set.py and DESIGN §3.23."""
+        Refusals as for transition_graph.  A graph built with transition_graph(sweep='device', screen='rows') is passed as ``graph``.
+        See invariant_set.py and DESIGN §3.23."""
         from .invariant_set import invariant_set
         return invariant_set(self, A, B, inputs, c=c, tol=tol, graph=graph, exits=exits, max_steps=max_steps, max_cells=max_cells,
                              reduce_rows=reduce_rows, device=device)
@@ -376,7 +388,8 @@ class Solution:
         its parent (cells_at, itinerary, locate, state_at, volumes, image_vertices, images, entering: the safety and target query).
         The successors come from ``graph``, the transition_graph of the same arguments (built when None); every step runs on the
         device inside one library call.  No map is inverted: singular and contracting loops are followed like any other.  Refusals as
-        for transition_graph.  See reach.py and DESIGN §3.25."""
+        for transition_graph.  A graph built with transition_graph(sweep='device', screen='rows') is passed as ``graph``.  See reach.py
+        and DESIGN §3.25."""
         from .reach import reach_cells
         return reach_cells(self, A, B, inputs, c=c, initial=initial, steps=steps, tol=tol, graph=graph, max_cells=max_cells,
                            max_rows_total=max_rows_total, device=device)

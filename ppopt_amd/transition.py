@@ -16,7 +16,9 @@ Lower-dimensional transitions -- through a facet or a vertex, T_ij of radius <= 
 trajectories (reachable, steps_to, cycles_outside) holds for almost every initial state, not for every one.
 
 Stages: feasible points and boxes of the regions (_lib.merge_regions), the exact boxes of the images (k_transition_boxes), candidate
-pairs whose image box and region box meet (image_box_pairs, a host sweep), one LP per candidate (k_transition_pairs).
+pairs whose image box and region box meet (image_box_pairs, a host sweep, or with sweep='device' geometry.box_pairs), with
+screen='rows' without the candidates that one row of the target separates from the image box (geometry.screen_pairs), one
+LP per candidate (k_transition_pairs).
 """
 import time
 from dataclasses import dataclass, field
@@ -26,7 +28,7 @@ import numpy
 
 from .region_merge import MAX_DIM, MAX_ROWS, solution_rows
 
-__all__ = ['TransitionGraph', 'transition_graph', 'transition_pairs', 'image_box_pairs', 'STATUS', 'NO_EDGE', 'EDGE', 'UNBOUNDED', 'UNDECIDED']
+__all__ = ['TransitionGraph', 'transition_graph', 'transition_pairs', 'image_box_pairs', 'screen_box', 'STATUS', 'NO_EDGE', 'EDGE', 'UNBOUNDED', 'UNDECIDED']
 
 STATUS = ('NO_EDGE', 'EDGE', 'UNBOUNDED', 'UNDECIDED')
 NO_EDGE, EDGE, UNBOUNDED, UNDECIDED = range(4)      # the status codes of mpc_transition_pairs
@@ -71,17 +73,55 @@ def image_box_pairs(image_box: numpy.ndarray, region_box: numpy.ndarray, usable:
     return pa[o].astype(numpy.int64), pb[o].astype(numpy.int64)
 
 
+SCREEN_BOX_SLACK = 1e-9      # the least relative widening of an image box before rows screen it (screen_box)
+
+
+def screen_box(image_box, tol: float) -> numpy.ndarray:
+    """The box the row screen tests the rows of a target against: every bound of the image box moved outwards by
+    max(tol, SCREEN_BOX_SLACK) (1 + |bound|); infinite bounds stay, NaN bounds stay (they separate nothing).  The screen is safe only
+    against a box that CONTAINS the image.  k_transition_boxes computes the bounds by LPs to about 1e-12 relative, and the image of a
+    region under a singular map is flat: where it lies in a facet of its target (a saturated state bound), an upper bound of
+    5 + 6e-12 is past the target's row theta_k <= 5 by more than the screen's threshold and a real edge would be dropped (29 of 64,205 on
+    the complete config 3).  The sweep before it takes the same boxes as good to tol (its margin is -tol)."""
+    box = numpy.asarray(image_box, dtype=numpy.float64)
+    with numpy.errstate(invalid='ignore'):
+        w = max(float(tol), SCREEN_BOX_SLACK) * (1.0 + numpy.abs(box))
+        return numpy.stack([box[:, 0] - w[:, 0], box[:, 1] + w[:, 1]], axis=1)
+
+
+def _device_image_box_pairs(image_box, region_box, usable, tol: float, device: int):
+    """image_box_pairs by geometry.box_pairs.  image_box_pairs opens BOTH bounds of a coordinate in which either bound of a box is NaN;
+    the device rule opens the NaN bound alone, so such coordinates are opened here first.  (Boxes of usable regions carry no NaN and no
+    two equal infinities in a coordinate unless a simplex run overflowed: DESIGN §3.27.)"""
+    from .geometry.box_pairs import box_pairs
+
+    def opened(box):
+        unknown = numpy.isnan(box).any(axis=1)
+        if not unknown.any():
+            return box
+        box = box.copy()
+        box[:, 0][unknown], box[:, 1][unknown] = -numpy.inf, numpy.inf
+        return box
+
+    return box_pairs(opened(image_box), usable, opened(region_box), usable, margin=-tol, device=device)
+
+
 def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, full_radius: bool = False, pairs=None, device: int = 0,
-                     void=()) -> dict:
+                     void=(), sweep: str = 'host', screen: str = 'none') -> dict:
     """The pair stage on arrays: polytopes of unit rows ef_rows = [o | n] in CSR form by row_off with the maps Phi [R, n_t, n_t], phi
     [R, n_t].  ``pairs`` = None: image boxes, candidates by image_box_pairs, then one LP per candidate; ``pairs`` = (i, j) arrays: those
     pairs, without the screen.  ``full_radius``: every radius run goes to its optimum (the radius is r_ij and the witness the Chebyshev
     centre) instead of stopping once the radius exceeds tol (the radius is then a lower bound above tol).  ``void``: polytopes known to
-    be empty, like the ones the device finds empty: they are no candidates.
+    be empty, like the ones the device finds empty: they are no candidates.  ``sweep`` = 'device': the candidates come from
+    geometry.box_pairs, the same list as image_box_pairs gives.  ``screen`` = 'rows' (with ``pairs`` None): the candidates that a row of the
+    target region separates from the source's image box, widened by screen_box, are dropped before the LPs; stats gains box_candidates,
+    screened, screen_ms and the result ``screen_box``, the boxes that were screened.
 
     Returns a dict: i, j (sorted by (i, j)), radius, status (NO_EDGE, EDGE, UNBOUNDED, UNDECIDED), witness [pairs, n_t], region_status
     [R] (UNDECIDED where the box stage was capped, else 0), image_box, region_box, usable and stats."""
     from . import _lib
+    from .geometry.box_pairs import screen_pairs, sweep_options
+    on_device, rows_screen = sweep_options('transition_pairs', sweep, screen)
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
     ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
     R = len(off) - 1
@@ -120,8 +160,19 @@ def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, fu
         stats['box_lps'], stats['box_pivots'] = s['lps'], s['pivots']
         region_status[capped != 0] = UNDECIDED
         t0 = time.perf_counter()
-        pa, pb = image_box_pairs(image_box, region_box, usable, tol)
+        if on_device:
+            pa, pb, sw = _device_image_box_pairs(image_box, region_box, usable, tol, device)
+            stats['sweep_kernel_ms'] = sw['ms']
+        else:
+            pa, pb = image_box_pairs(image_box, region_box, usable, tol)
         stats['sweep_ms'] = (time.perf_counter() - t0) * 1e3
+        if rows_screen:
+            t0 = time.perf_counter()
+            outer = screen_box(image_box, tol)
+            keep, sc = screen_pairs(off, ef, pa, pb, None, outer, sides='b', device=device)
+            stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
+            pa, pb = pa[keep], pb[keep]
+            stats['screen_ms'] = (time.perf_counter() - t0) * 1e3
     stats['candidates'] = len(pa)
     if len(pa):
         radius, st, witness, s = _lib.transition_pairs(off, ef, Phi, phi, xs, pa, pb, full_radius, tol, device)
@@ -131,8 +182,11 @@ def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, fu
     else:
         radius, st, witness = numpy.zeros(0), numpy.zeros(0, dtype=numpy.int32), numpy.zeros((0, n_t))
     stats['edges'] = int(numpy.sum(st != NO_EDGE))
-    return {'i': pa, 'j': pb, 'radius': radius, 'status': st, 'witness': witness, 'region_status': region_status, 'image_box': image_box,
-            'region_box': region_box, 'usable': usable, 'stats': stats}
+    res = {'i': pa, 'j': pb, 'radius': radius, 'status': st, 'witness': witness, 'region_status': region_status, 'image_box': image_box,
+           'region_box': region_box, 'usable': usable, 'stats': stats}
+    if rows_screen and pairs is None:
+        res['screen_box'] = outer
+    return res
 
 
 def _csr(n: int, src: numpy.ndarray, dst: numpy.ndarray):
@@ -280,16 +334,20 @@ def check_source(source, A, B, inputs, c, tol: float):
     return A, B, inp, c, n_t
 
 
-def transition_graph(source, A, B, inputs, c=None, tol: float = 1e-8, full_radius: bool = False, device: int = 0) -> TransitionGraph:
+def transition_graph(source, A, B, inputs, c=None, tol: float = 1e-8, full_radius: bool = False, device: int = 0, sweep: str = 'host',
+                     screen: str = 'none') -> TransitionGraph:
     """Solution.transition_graph (the module docstring): which region can follow which under the plant theta+ = A theta + B u + c,
-    u = x*(theta)[inputs].  The source is not modified."""
+    u = x*(theta)[inputs].  The source is not modified.  ``sweep``, ``screen``: as for transition_pairs; the graph is the same either way."""
     from .invariance import closed_loop_maps
+    from .geometry.box_pairs import sweep_options
+    sweep_options('transition_graph', sweep, screen)
     t0 = time.perf_counter()
     A, B, inp, c, n_t = check_source(source, A, B, inputs, c, tol)
     off, rows, void = solution_rows(source.critical_regions, n_t, 'transition_graph')
     _, _, xlaw = source._stacked()
     Phi, phi = closed_loop_maps(xlaw, A, B, inp, c)
-    res = transition_pairs(off, rows, Phi, phi, n_t, tol=tol, full_radius=full_radius, device=device, void=void)
+    res = transition_pairs(off, rows, Phi, phi, n_t, tol=tol, full_radius=full_radius, device=device, void=void, sweep=sweep,
+                           screen=screen)
     keep = res['status'] != NO_EDGE
     stats = dict(res['stats'])
     stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
