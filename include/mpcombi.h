@@ -904,6 +904,44 @@ int mpc_exit_split(int32_t device, int32_t n_t, int64_t n_regions, const int64_t
 int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const double *start, double tol,
                     int32_t *status, int32_t *wide, uint64_t *kept, double *point, int64_t *stats, float *ms);
 
+/* ---- support functions of polytopes (geometry.support_of) ------------------------------------------------------------ */
+/* Polytopes as unit rows [o | n] in CSR form by row_off, 1..MPC_SUPPORT_MAX_ROWS rows each, as for mpc_reduce_rows.  Directions in a second
+ * CSR table: polytope q owns the rows dir_off[q] .. dir_off[q + 1] of dirs [n_dir][n_t]; a polytope without directions is legal.  Stateless;
+ * an error text is read with mpc_last_error(NULL).
+ *
+ * mpc_support_rows: h_P(d) = max {d.x : x in P} for every polytope P and each of its directions d (k_support_rows; one wavefront per block
+ *   of 64 consecutive directions of one polytope, the blocks listed by the call itself).
+ *   Interior point: the radius run of mpc_reduce_rows from start, stopped once t > tol.  Optimal with t <= tol: P is thin, poly_status
+ *   MPC_SUPPORT_THIN, and every direction of P gets value = arg = NaN and dir_status MPC_SUPPORT_THIN without an LP.  Otherwise the point p
+ *   where the run ended.  An unbounded or capped radius run is not thin and sets wide[q] = 1: an unbounded run (it ends while t <= tol,
+ *   where the point need not lie in P) moves p along the ray it found to t = tol + 1, a point of P of that radius; a capped run with
+ *   t >= 0 goes on from the point reached; a capped run with t < 0 knows no point of P, and every direction of P gets value +inf, arg NaN
+ *   and MPC_SUPPORT_CAPPED without an LP.
+ *   One direction: d == 0 in every entry: value 0, arg p, MPC_SUPPORT_OK, no LP.  Otherwise max c.x, c = d / |d| (d scaled by a power of
+ *   two first, so that no finite direction overflows or underflows), by the vertex simplex
+ *   from p with a fresh basis.  Optimal: arg is the point reached and value = d.arg (fma over ascending t), MPC_SUPPORT_OK.  Unbounded:
+ *   value +inf, arg the last point reached, MPC_SUPPORT_UNBOUNDED.  Pivot cap: value +inf, a bound and not a value, MPC_SUPPORT_CAPPED.
+ *   Every run starts from p alone, so the result of a direction depends on (rows, start, tol, d) only: permuting a polytope's directions
+ *   or repeating one changes no bit of any result.
+ *   value [n_dir], dir_status [n_dir], arg [n_dir][n_t] or NULL.
+ *   poly_status[q]  MPC_SUPPORT_OK or MPC_SUPPORT_THIN.   wide[q]: 1 when the radius run of q was unbounded or capped.
+ *   start      [n_poly][n_t] where the radius run of a polytope starts, or NULL: the origin.
+ *   point      [n_poly][n_t] or NULL: where the radius run ended, the p above.
+ *   n_poly == 0: MPC_OK without a launch.  No direction at all: one launch for poly_status, wide and point.
+ *   stats (may be NULL): [0] polytopes, [1] thin ones, [2] directions, [3] zero directions, [4] LPs (one radius run per polytope and one
+ *   run per direction that is not zero), [5] pivots, [6] unbounded or capped runs.
+ * MPC_ERR_INVALID with a message, before a device is selected: a missing array, 1 <= n_t <= 16, 1..512 rows per polytope, finite rows with
+ * unit normals, dir_off non-decreasing from 0, at most 2^31 - 1 polytopes, directions and blocks, finite directions, finite start, tol
+ * finite and >= 0.  Deterministic: atomics only in the counters. */
+#define MPC_SUPPORT_MAX_ROWS 512
+#define MPC_SUPPORT_OK 0
+#define MPC_SUPPORT_UNBOUNDED 1
+#define MPC_SUPPORT_CAPPED 2
+#define MPC_SUPPORT_THIN 3
+int mpc_support_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *dir_off,
+                     const double *dirs, const double *start, double tol, double *value, double *arg, int32_t *dir_status,
+                     int32_t *poly_status, int32_t *wide, double *point, int64_t *stats, float *ms);
+
 /* ---- projections of polytopes (geometry.project_rows_of) -------------------------------------------------------------- */
 /* Polytopes of R^n as unit rows [o | n] in CSR form by row_off, up to MPC_PROJECT_MAX_ROWS rows each.  Stateless; an error text is read
  * with mpc_last_error(NULL).

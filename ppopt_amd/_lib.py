@@ -288,6 +288,8 @@ def load():
                                           _ip, _ip, _ip, _dp, ctypes.c_double, _ip, _u64p, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_reduce_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double, _ip, _ip, _u64p, _dp, _lp,
                                            ctypes.POINTER(ctypes.c_float)]),
+        'mpc_support_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _lp, _dp, _dp, ctypes.c_double, _dp, _dp, _ip,
+                                            _ip, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_project_rows': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, ctypes.c_double,
                                             ctypes.c_int32, _dp, _ip, _ip, _ip, _ip, _dp, _lp, ctypes.POINTER(ctypes.c_float)]),
         'mpc_backward_exits': (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _lp, _dp, _dp, _dp, _dp, _lp, _ip, ctypes.c_int64, _lp, _dp,
@@ -318,7 +320,7 @@ EXPORTED_SYMBOLS = ['mpc_device_count', 'mpc_version', 'mpc_last_global_error', 
                     'mpc_merge_pairs', 'mpc_locator_simulate', 'mpc_region_vertices', 'mpc_region_volumes', 'mpc_region_moments',
                     'mpc_overlap_pairs', 'mpc_overlap_split', 'mpc_transition_boxes', 'mpc_transition_pairs', 'mpc_exit_split', 'mpc_reduce_rows',
                     'mpc_backward_exits', 'mpc_project_rows', 'mpc_forward_cells', 'mpc_law_gap_pairs', 'mpc_box_pairs',
-                    'mpc_pair_screen']
+                    'mpc_pair_screen', 'mpc_support_rows']
 
 
 def pinned_empty(shape, dtype) -> numpy.ndarray:
@@ -1548,6 +1550,29 @@ def reduce_rows(row_off, ef_rows, start, tol: float, device: int = 0):
     k = numpy.arange(len(ef)) - numpy.repeat(off[:-1], counts)
     kept = ((mask[poly, k >> 6] >> (k & 63).astype(numpy.uint64)) & numpy.uint64(1)).astype(bool)
     return kept, status, wide, point, stats
+
+
+SUPPORT_MAX_ROWS = 512   # rows per polytope of mpc_support_rows (include/mpcombi.h)
+SUPPORT_OK, SUPPORT_UNBOUNDED, SUPPORT_CAPPED, SUPPORT_THIN = range(4)
+SUPPORT_STATUS = ('OK', 'UNBOUNDED', 'CAPPED', 'THIN')
+
+
+def support_rows(row_off, ef_rows, dir_off, dirs, start, tol: float, args: bool = True, device: int = 0):
+    """h_P(d) for every polytope and each of its directions (include/mpcombi.h, mpc_support_rows): (value [n_dir], arg [n_dir, n_t] or None
+    without ``args``, dir_status [n_dir] int32 (SUPPORT_*), poly_status [n_poly] int32 (SUPPORT_OK, SUPPORT_THIN), wide [n_poly] int32,
+    point [n_poly, n_t], stats).  Polytope q owns the rows dir_off[q] .. dir_off[q + 1] of dirs."""
+    off, ef = _merge_rows('support_rows', row_off, ef_rows)
+    n_t, n = ef.shape[1] - 1, len(off) - 1
+    doff = numpy.ascontiguousarray(dir_off, dtype=numpy.int64).reshape(-1)
+    d = _f64(numpy.asarray(dirs, dtype=numpy.float64)).reshape(-1, n_t)
+    if len(doff) != n + 1 or doff[-1] != len(d):
+        raise MpcError('support_rows: dir_off [n_poly + 1] must end at the number of rows of dirs [n_dir, n_t]')
+    s0 = None if start is None else _f64(numpy.asarray(start, dtype=numpy.float64)).reshape(n, n_t)
+    value, arg, ds = numpy.zeros(len(d)), (numpy.zeros((len(d), n_t)) if args else None), numpy.zeros(len(d), dtype=numpy.int32)
+    ps, wide, point = numpy.zeros(n, dtype=numpy.int32), numpy.zeros(n, dtype=numpy.int32), numpy.zeros((n, n_t))
+    stats = _geometry_call('mpc_support_rows', ('polytopes', 'thin', 'directions', 'zero', 'lps', 'pivots', 'wide'), int(device), n_t, n, off, ef,
+                           doff, d, s0, float(tol), value, arg, ds, ps, wide, point)
+    return value, arg, ds, ps, wide, point, stats
 
 
 PROJECT_MAX_ROWS = 512   # rows per polytope and per elimination step of mpc_project_rows (include/mpcombi.h)

@@ -26,6 +26,7 @@
 #include "transition.hpp"
 #include "exit_sets.hpp"
 #include "reduce.hpp"
+#include "support.hpp"
 #include "project.hpp"
 #include "invariant.hpp"
 #include "forward.hpp"
@@ -1745,6 +1746,66 @@ extern "C" int mpc_reduce_rows(int32_t device, int32_t n_t, int64_t n_poly, cons
     s.download(kept, d_k, words);
     if (point) s.download(point, *d_point, np * n_t * 8);
     return family_close(s, d_cnt, 5, stats, ms);
+}
+
+// ---- support functions of polytopes (support.hpp) -------------------------------------------------------------------------
+extern "C" int mpc_support_rows(int32_t device, int32_t n_t, int64_t n_poly, const int64_t *row_off, const double *ef_rows, const int64_t *dir_off,
+                                const double *dirs, const double *start, double tol, double *value, double *arg, int32_t *dir_status,
+                                int32_t *poly_status, int32_t *wide, double *point, int64_t *stats, float *ms) {
+    const char *who = "mpc_support_rows";
+    family_open(stats, 7, ms);
+    int m_max = 1;
+    if (int rc = merge_check(who, n_t, n_poly, row_off, ef_rows, &m_max, RD_MAX_ROWS)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (n_poly == 0) return MPC_OK;
+    if (!dir_off) return bad(who, "missing dir_off");
+    if (dir_off[0] != 0) return bad(who, "dir_off[0] must be 0");
+    // the items: polytope q's directions in blocks of SF_BLOCK, one item for a polytope without any
+    std::vector<int32_t> item_poly, item_count;
+    std::vector<long long> item_first;
+    for (int64_t q = 0; q < n_poly; ++q) {
+        const int64_t k = dir_off[q + 1] - dir_off[q];
+        if (k < 0) return bad(who, "dir_off decreases");
+        if (dir_off[q + 1] > 0x7fffffffll) return bad(who, "more than 2^31 - 1 directions");
+        for (int64_t j = 0; j == 0 || j < k; j += SF_BLOCK) {
+            item_poly.push_back((int32_t)q);
+            item_first.push_back(dir_off[q] + j);
+            item_count.push_back((int32_t)std::min<int64_t>(SF_BLOCK, k - j));
+        }
+    }
+    const int64_t n_dir = dir_off[n_poly], n_items = (int64_t)item_poly.size();
+    if (int rc = check_count(who, "n_items", n_items)) return rc;
+    if (!value || !dir_status || !poly_status || !wide || (n_dir > 0 && !dirs)) return bad(who, "missing array");
+    if (int rc = check_finite(who, "dirs", dirs, n_dir * n_t)) return rc;
+    if (start)
+        if (int rc = check_finite(who, "start", start, n_poly * n_t)) return rc;
+    if (int rc = select_device(nullptr, device)) return rc;
+    const size_t lds = sf_lds_bytes(m_max, n_t);   // 512 rows at n_t = 16: 79,112 bytes
+    const size_t np = (size_t)n_poly, nd = (size_t)n_dir, ni = (size_t)n_items;
+    OneShot s(who, nullptr, true);
+    const RegionsOnDevice d = upload_regions(s, n_poly, row_off, ef_rows, n_t + 1);
+    DevBuf &d_doff = s.upload(dir_off, (np + 1) * 8), &d_dirs = s.upload(dirs, nd * n_t * 8);
+    DevBuf &d_ip = s.upload(item_poly.data(), ni * 4), &d_ic = s.upload(item_count.data(), ni * 4), &d_if = s.upload(item_first.data(), ni * 8);
+    DevBuf *d_start = start ? &s.upload(start, np * n_t * 8) : nullptr, *d_point = point ? &s.buf(np * n_t * 8) : nullptr;
+    DevBuf *d_arg = arg ? &s.buf(std::max<size_t>(8, nd * n_t * 8)) : nullptr;
+    DevBuf &d_val = s.buf(std::max<size_t>(8, nd * 8)), &d_ds = s.buf(std::max<size_t>(8, nd * 4)), &d_ps = s.buf(np * 4), &d_w = s.buf(np * 4);
+    DevBuf &d_cnt = family_counters(s, 7);
+    SupportArgs a{};
+    a.nt = n_t; a.m_max = m_max; a.n_items = n_items;
+    a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.dir_off = d_doff.as<long long>(); a.dirs = d_dirs.as<double>();
+    a.item_poly = d_ip.as<int32_t>(); a.item_count = d_ic.as<int32_t>(); a.item_first = d_if.as<long long>();
+    a.start = d_start ? d_start->as<double>() : nullptr; a.tol = tol;
+    a.value = d_val.as<double>(); a.arg = d_arg ? d_arg->as<double>() : nullptr; a.dir_status = d_ds.as<int32_t>();
+    a.poly_status = d_ps.as<int32_t>(); a.wide = d_w.as<int32_t>(); a.point = d_point ? d_point->as<double>() : nullptr;
+    a.counters = d_cnt.as<unsigned long long>();
+    family_launch(s, k_support_rows, n_items, lds, a);
+    s.download(value, d_val, nd * 8);
+    if (arg) s.download(arg, *d_arg, nd * n_t * 8);
+    s.download(dir_status, d_ds, nd * 4);
+    s.download(poly_status, d_ps, np * 4);
+    s.download(wide, d_w, np * 4);
+    if (point) s.download(point, *d_point, np * n_t * 8);
+    return family_close(s, d_cnt, 7, stats, ms);
 }
 
 // ---- projections of polytopes (project.hpp) ------------------------------------------------------------------------------

@@ -31,3 +31,25 @@ class Polytope:
         512 rows at a step is a ValueError that names the status and the peak row count."""
         from .project import projected_polytope
         return projected_polytope(self, keep, tol=tol, device=device)
+
+    def support(self, directions, tol: float = 1e-8, device: int = 0):
+        """(values, args): h(d) = max {d.x : x in this polytope} for every row d of ``directions`` [k, n] and a point that attains it
+        (geometry.support); one direction [n] gives one value and one point.  The rows are scaled to unit normals first (a
+        zero row is a ValueError); the values are those of the directions as given.  +inf: the polytope is unbounded along d (or the
+        run met the pivot cap); NaN: the polytope is thin (Chebyshev radius <= tol)."""
+        from .support import polytope_support
+        return polytope_support(self, directions, tol=tol, device=device)
+
+    def erode(self, Q: 'Polytope', E=None, tol: float = 1e-8, reduce_rows: bool = True, device: int = 0) -> 'Polytope':
+        """The Pontryagin difference {x : x + E q in this polytope for every q in Q} (geometry.support.pontryagin_difference, DESIGN
+        §3.28): unit rows [o_k - h_Q(E' n_k) | n_k], without the redundant ones unless ``reduce_rows`` is off.  ``E``: [n, n_q], None
+        for Q in this polytope's space.  ValueError that names the status for a difference that is EMPTY (Q unbounded where this
+        polytope is bounded) or THIN (Chebyshev radius <= tol, or empty), and for a thin Q."""
+        from .support import eroded_polytope
+        return eroded_polytope(self, Q, E=E, tol=tol, reduce_rows=reduce_rows, device=device)
+
+    def contains_polytope(self, other: 'Polytope', tol: float = 1e-8, device: int = 0) -> bool:
+        """Whether ``other`` lies in this polytope: h_other(n_k) <= o_k + tol for every unit row [o_k | n_k] of this one
+        (geometry.support.containment).  False for an ``other`` that is thin or unbounded where this polytope is bounded."""
+        from .support import polytope_contains
+        return polytope_contains(self, other, tol=tol, device=device)

@@ -118,6 +118,17 @@ class Solution:
         from .geometry.reduce import reduce_solution
         return reduce_solution(self, tol=tol, device=device)
 
+    def output_range(self, outputs=None, tol: float = 1e-8, device: int = 0):
+        """The bounds the explicit controller can command: a geometry.support.OutputRange with lo[i, k] and hi[i, k], the smallest and
+        largest value of row outputs[k] of the law A_i theta + b_i over region i (None: every row the regions keep), arg_lo and arg_hi
+        where they are attained, and flag for an entry that is a bound and not a value (an unbounded region, or the pivot cap); two LPs
+        per region and row on the device, in the order row 0 max, row 0 min, row 1 max, ...; a constant row costs none and gives lo = hi
+        = b_i[k] exactly.  ``overall()`` gives the extremes over all regions.  The regions are the rows the locator holds, scaled to unit
+        normals.  ValueError before any launch for an empty solution, n_theta > 16, a region of more than 512 rows, a row a merged
+        solution did not keep and a tol that is not finite and >= 0.  See DESIGN §3.28."""
+        from .geometry.support import output_range
+        return output_range(self, outputs=outputs, tol=tol, device=device)
+
     def compare(self, other: 'Solution', outputs=None, tol: float = 1e-8, ranges: bool = False, coverage: bool = False, device: int = 0,
                 sweep: str = 'host', screen: str = 'none'):
         """How far this solution's law is from ``other``'s, exactly: a compare.LawGap.  For every region i of this solution and j of the

@@ -1,7 +1,7 @@
-// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce, project, backward-exit and forward-cell calls
+// geometry_refusals.hip -- the argument checking of the merge, overlap, transition, exit, reduce, support, project, backward-exit and forward-cell calls
 // (mpc_merge_regions, mpc_merge_pairs, mpc_overlap_pairs, mpc_overlap_split, mpc_transition_boxes, mpc_transition_pairs, mpc_exit_split,
-// mpc_reduce_rows, mpc_project_rows, mpc_backward_exits, mpc_forward_cells) as a stand-alone host program for a sanitizer build (DESIGN §3.14,
-// §3.19 to §3.25):
+// mpc_reduce_rows, mpc_support_rows, mpc_project_rows, mpc_backward_exits, mpc_forward_cells) as a stand-alone host program for a sanitizer build (DESIGN §3.14,
+// §3.19 to §3.25, §3.28):
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined tools/geometry_refusals.hip -o geometry_refusals
 // It includes geometry.hip itself and stands in for the pools of mpcombi_hip.hip, which a refusal never reaches: every call below must
 // come back MPC_ERR_INVALID with a message before a device is selected (an empty batch: MPC_OK), so the program needs no GPU and
@@ -336,6 +336,65 @@ static void reduce_cases() {
     expect("no polytopes, no arrays", mpc_reduce_rows(0, nt, 0, nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), MPC_OK);
 }
 
+// mpc_support_rows
+static void support_cases() {
+    const int nt = 2;
+    const VD sq{1, 1, 0, 1, 0, 1, 0, -1, 0, 0, 0, -1};                                                 // [0, 1]^2
+    VD ef = sq;
+    ef.insert(ef.end(), {1.5, 1, 0, 1, 0, 1, -0.5, -1, 0, 0, 0, -1});                                  // [1/2, 3/2] x [0, 1]
+    VD value(3), arg(6), point(4);
+    VI dstat(3), pstat(2), wide(2);
+    int64_t stats[7];
+    float ms = 0.0f;
+    struct Args { int n_t; VL off; VD ef; VL doff; VD dirs, start; double tol; };
+    const Args good{nt, {0, 4, 8}, ef, {0, 2, 3}, {1, 0, 0, 0, -1, 2}, {0.5, 0.5, 1.0, 0.5}, 1e-8};
+    auto support = [&](const Args &g, int64_t n_poly = -2) {
+        return mpc_support_rows(0, g.n_t, n_poly == -2 ? (int64_t)g.off.size() - 1 : n_poly, g.off.data(), g.ef.data(), g.doff.data(), g.dirs.data(),
+                                g.start.data(), g.tol, value.data(), arg.data(), dstat.data(), pstat.data(), wide.data(), point.data(), stats, &ms);
+    };
+    auto with = [&](auto change) { Args g = good; change(g); return g; };
+    const double nan = std::nan("");
+    VD big;                                                                                            // 513 rows
+    for (int r = 0; r < 128; ++r) big.insert(big.end(), sq.begin(), sq.end());
+    big.insert(big.end(), sq.begin(), sq.begin() + 3);
+    expect("n_t = 0", support(with([](Args &g) { g.n_t = 0; })));
+    expect("n_t = 17", support(with([](Args &g) { g.n_t = 17; })));
+    expect("tol < 0", support(with([](Args &g) { g.tol = -1.0; })));
+    expect("tol NaN", support(with([&](Args &g) { g.tol = nan; })));
+    expect("tol inf", support(with([](Args &g) { g.tol = INFINITY; })));
+    expect("n_poly < 0", support(good, -1));
+    expect("n_poly = 2^31", support(good, 0x80000000ll));
+    expect("row_off[0] != 0", support(with([](Args &g) { g.off = {1, 4, 8}; })));
+    expect("row_off decreases", support(with([](Args &g) { g.off = {0, 8, 4}; })));
+    expect("a polytope without rows", support(with([](Args &g) { g.off = {0, 0, 8}; })));
+    expect("a polytope of 513 rows", support(with([&](Args &g) { g.off = {0, 513}; g.ef = big; g.doff = {0, 3}; g.start.resize(2); })));
+    expect("a non-finite row", support(with([&](Args &g) { g.ef[4] = nan; })));
+    expect("a row that is not unit", support(with([](Args &g) { g.ef[1] = 2.0; })));
+    expect("dir_off[0] != 0", support(with([](Args &g) { g.doff = {1, 2, 3}; })));
+    expect("dir_off decreases", support(with([](Args &g) { g.doff = {0, 3, 2}; })));
+    expect("2^31 directions", support(with([](Args &g) { g.doff = {0, 2, 0x80000000ll}; })));
+    expect("a direction NaN", support(with([&](Args &g) { g.dirs[3] = nan; })));
+    expect("a direction inf", support(with([](Args &g) { g.dirs[0] = INFINITY; })));
+    expect("start NaN", support(with([&](Args &g) { g.start[1] = nan; })));
+    expect("start inf", support(with([](Args &g) { g.start[2] = INFINITY; })));
+    const Args &g = good;
+    auto raw = [&](const int64_t *off, const double *rows, const int64_t *doff, const double *dirs, double *val, int32_t *ds, int32_t *ps, int32_t *wd) {
+        return mpc_support_rows(0, nt, 2, off, rows, doff, dirs, nullptr, 1e-8, val, nullptr, ds, ps, wd, nullptr, nullptr, nullptr);
+    };
+    expect("missing row_off", raw(nullptr, g.ef.data(), g.doff.data(), g.dirs.data(), value.data(), dstat.data(), pstat.data(), wide.data()));
+    expect("missing ef_rows", raw(g.off.data(), nullptr, g.doff.data(), g.dirs.data(), value.data(), dstat.data(), pstat.data(), wide.data()));
+    expect("missing dir_off", raw(g.off.data(), g.ef.data(), nullptr, g.dirs.data(), value.data(), dstat.data(), pstat.data(), wide.data()));
+    expect("missing dirs", raw(g.off.data(), g.ef.data(), g.doff.data(), nullptr, value.data(), dstat.data(), pstat.data(), wide.data()));
+    expect("missing value", raw(g.off.data(), g.ef.data(), g.doff.data(), g.dirs.data(), nullptr, dstat.data(), pstat.data(), wide.data()));
+    expect("missing dir_status", raw(g.off.data(), g.ef.data(), g.doff.data(), g.dirs.data(), value.data(), nullptr, pstat.data(), wide.data()));
+    expect("missing poly_status", raw(g.off.data(), g.ef.data(), g.doff.data(), g.dirs.data(), value.data(), dstat.data(), nullptr, wide.data()));
+    expect("missing wide", raw(g.off.data(), g.ef.data(), g.doff.data(), g.dirs.data(), value.data(), dstat.data(), pstat.data(), nullptr));
+    expect("no polytopes is MPC_OK without a launch",
+           support(with([](Args &a) { a.off = {0}; a.ef.clear(); a.doff = {0}; a.dirs.clear(); a.start.clear(); })), MPC_OK);
+    expect("no polytopes, no arrays", mpc_support_rows(0, nt, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 1e-8, nullptr, nullptr, nullptr, nullptr,
+                                                       nullptr, nullptr, nullptr, nullptr), MPC_OK);
+}
+
 // mpc_project_rows
 static void project_cases() {
     const int n = 2;
@@ -581,6 +640,7 @@ int main() {
     transition_cases();
     exit_cases();
     reduce_cases();
+    support_cases();
     project_cases();
     backward_cases();
     forward_cases();
