@@ -1599,6 +1599,43 @@ def project_rows(row_off, ef_rows, n_elim: int, start, tol: float, out_cap: int 
     return out_off, rows[taken], status, wide, peak, point, stats
 
 
+class _CellCall:
+    """What backward_exits and forward_cells share around their library call.  The cells of step 0 converted and checked (``per_cell``:
+    what the refusal says every cell has one of; n_points: the rows of the caller's point array, None without one) and the limits, then
+    capacity-sized outputs, grouped as the C argument lists have them: cells0 (count, cell_off, cell_rows, region), limits (max_steps,
+    max_cells, max_rows_total), table (n_cells, cell_off, cell_rows, region, step, parent, wide, point), status, steps, per_step
+    (cells_per_step, step_ms)."""
+
+    def __init__(self, who, n_t, cell_off, cell_rows, cell_reg, per_cell, n_points, max_steps, max_cells, max_rows_total):
+        coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
+        crow = _f64(numpy.asarray(cell_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
+        creg = numpy.ascontiguousarray(cell_reg, dtype=numpy.int32).reshape(-1)
+        if len(coff) != len(creg) + 1 or coff[0] != 0 or coff[-1] != len(crow) or (n_points is not None and n_points != len(creg)):
+            raise MpcError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with {per_cell} per cell')
+        max_steps, max_cells, max_rows_total = int(max_steps), int(max_cells), int(max_rows_total)
+        if max_cells < 0 or max_rows_total < 0:
+            raise MpcError(f'{who}: max_cells and max_rows_total must be >= 0')
+        self.cells0, self.limits = (len(creg), coff, crow, creg), (max_steps, max_cells, max_rows_total)
+        # capacity, not contents: pages the library never writes are never touched
+        reg, step, parent, wide = (numpy.empty(max_cells, dtype=numpy.int32) for _ in range(4))
+        self.table = (numpy.zeros(1, dtype=numpy.int64), numpy.empty(max_cells + 1, dtype=numpy.int64), numpy.empty((max_rows_total, n_t + 1)),
+                      reg, step, parent, wide, numpy.empty((max_cells, n_t)))
+        self.status, self.steps = numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32)
+        self.step_ms = numpy.zeros(max(max_steps, 1), dtype=numpy.float32)
+        self.per_step = (numpy.zeros(max(max_steps, 0) + 1, dtype=numpy.int64), self.step_ms.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+
+    def result(self, reg_key, stats):
+        """The keys both results have (the region of a cell under ``reg_key``), cut to the cells the call delivered."""
+        n, out_off, out_rows, reg, step, parent, wide, point = self.table
+        n, k = int(n[0]), int(self.steps[0])
+        return {'cell_off': out_off[:n + 1].copy(), 'cell_rows': out_rows[:int(out_off[n])].copy(), reg_key: reg[:n].astype(numpy.int64),
+                'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': point[:n].copy(),
+                'status': int(self.status[0]), 'steps': k, 'cells_per_step': self.per_step[0][:k + 1].copy(),
+                'step_ms': self.step_ms[:max(self.limits[0], 0)].astype(numpy.float64), 'stats': stats}
+
+
+_CELL_STATS = ('items', 'cells', 'empty', 'lps', 'pivots', 'wide')
+
 # status of mpc_backward_exits (include/mpcombi.h)
 BACKWARD_CONVERGED, BACKWARD_MAX_STEPS, BACKWARD_ROWS, BACKWARD_MAX_CELLS, BACKWARD_MAX_ROWS_TOTAL = range(5)
 BACKWARD_STATUS = ('CONVERGED', 'MAX_STEPS', 'ROWS', 'MAX_CELLS', 'MAX_ROWS_TOTAL')
@@ -1617,31 +1654,14 @@ def backward_exits(row_off, ef_rows, Phi, phi, xs, pred_off, pred_idx, cell_off,
     pidx = numpy.ascontiguousarray(pred_idx, dtype=numpy.int32).reshape(-1)
     if len(poff) != R + 1 or (len(poff) and poff[-1] != len(pidx)):
         raise MpcError(f'{who}: pred_off [regions + 1] must end at the length of pred_idx')
-    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
-    crow = _f64(numpy.asarray(cell_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
-    csrc = numpy.ascontiguousarray(cell_source, dtype=numpy.int32).reshape(-1)
-    if len(coff) != len(csrc) + 1 or coff[0] != 0 or coff[-1] != len(crow):
-        raise MpcError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one source per cell')
-    max_steps, max_cells, max_rows_total = int(max_steps), int(max_cells), int(max_rows_total)
-    if max_cells < 0 or max_rows_total < 0:
-        raise MpcError(f'{who}: max_cells and max_rows_total must be >= 0')
-    # capacity, not contents: pages the library never writes are never touched
-    out_off, out_rows = numpy.empty(max_cells + 1, dtype=numpy.int64), numpy.empty((max_rows_total, n_t + 1))
-    src, step, parent, wide = (numpy.empty(max_cells, dtype=numpy.int32) for _ in range(4))
-    point = numpy.empty((max_cells, n_t))
-    n, status, steps, conv = numpy.zeros(1, dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32)
-    per_step = numpy.zeros(max(max_steps, 0) + 1, dtype=numpy.int64)
-    step_ms = numpy.zeros(max(max_steps, 1), dtype=numpy.float32)
-    stats = _geometry_call('mpc_backward_exits', ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'), int(device), n_t, R, off, ef, P, p, x, poff, pidx,
-                           len(csrc), coff, crow, csrc, float(tol), max_steps, max_cells, max_rows_total, n, out_off, out_rows, src, step, parent, wide,
-                           point, status, steps, conv, per_step, step_ms.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-    n, n0, k = int(n[0]), len(csrc), int(steps[0])
-    pt = point[:n].copy()
-    pt[:min(n0, n)] = numpy.nan
-    return {'cell_off': out_off[:n + 1].copy(), 'cell_rows': out_rows[:int(out_off[n])].copy(), 'source': src[:n].astype(numpy.int64),
-            'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': pt,
-            'status': int(status[0]), 'steps': k, 'converged': bool(conv[0]), 'cells_per_step': per_step[:k + 1].copy(),
-            'step_ms': step_ms[:max(max_steps, 0)].astype(numpy.float64), 'stats': stats}
+    t = _CellCall(who, n_t, cell_off, cell_rows, cell_source, 'one source', None, max_steps, max_cells, max_rows_total)
+    conv = numpy.zeros(1, dtype=numpy.int32)
+    stats = _geometry_call('mpc_backward_exits', _CELL_STATS, int(device), n_t, R, off, ef, P, p, x, poff, pidx, *t.cells0, float(tol), *t.limits,
+                           *t.table, t.status, t.steps, conv, *t.per_step)
+    r = t.result('source', stats)
+    r['point'][:t.cells0[0]] = numpy.nan
+    r['converged'] = bool(conv[0])
+    return r
 
 
 # status of mpc_forward_cells (include/mpcombi.h)
@@ -1665,30 +1685,15 @@ def forward_cells(row_off, ef_rows, Phi, phi, succ_off, succ_idx, cell_off, cell
     sidx = numpy.ascontiguousarray(succ_idx, dtype=numpy.int32).reshape(-1)
     if len(soff) != R + 1 or (len(soff) and soff[-1] != len(sidx)):
         raise MpcError(f'{who}: succ_off [regions + 1] must end at the length of succ_idx')
-    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
-    crow = _f64(numpy.asarray(cell_rows, dtype=numpy.float64)).reshape(-1, n_t + 1)
-    creg = numpy.ascontiguousarray(cell_region, dtype=numpy.int32).reshape(-1)
     cpt = _f64(numpy.asarray(cell_point, dtype=numpy.float64)).reshape(-1, n_t)
-    if len(coff) != len(creg) + 1 or coff[0] != 0 or coff[-1] != len(crow) or len(cpt) != len(creg):
-        raise MpcError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one region and one point per cell')
-    max_steps, max_cells, max_rows_total = int(max_steps), int(max_cells), int(max_rows_total)
-    if max_cells < 0 or max_rows_total < 0:
-        raise MpcError(f'{who}: max_cells and max_rows_total must be >= 0')
-    # capacity, not contents: pages the library never writes are never touched
-    out_off, out_rows = numpy.empty(max_cells + 1, dtype=numpy.int64), numpy.empty((max_rows_total, n_t + 1))
-    reg, step, parent, wide = (numpy.empty(max_cells, dtype=numpy.int32) for _ in range(4))
-    point, cmap = numpy.empty((max_cells, n_t)), numpy.empty((max_cells, n_t, n_t + 1))
-    n, status, steps = numpy.zeros(1, dtype=numpy.int64), numpy.zeros(1, dtype=numpy.int32), numpy.zeros(1, dtype=numpy.int32)
-    per_step = numpy.zeros(max(max_steps, 0) + 1, dtype=numpy.int64)
-    step_ms = numpy.zeros(max(max_steps, 1), dtype=numpy.float32)
-    stats = _geometry_call('mpc_forward_cells', ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'), int(device), n_t, R, off, ef, P, p, soff, sidx,
-                           len(creg), coff, crow, creg, cpt, float(tol), max_steps, max_cells, max_rows_total, n, out_off, out_rows, reg, step, parent,
-                           wide, point, cmap, status, steps, per_step, step_ms.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-    n, k = int(n[0]), int(steps[0])
-    return {'cell_off': out_off[:n + 1].copy(), 'cell_rows': out_rows[:int(out_off[n])].copy(), 'region': reg[:n].astype(numpy.int64),
-            'step': step[:n].astype(numpy.int64), 'parent': parent[:n].astype(numpy.int64), 'wide': wide[:n] != 0, 'point': point[:n].copy(),
-            'G': cmap[:n, :, :n_t].copy(), 'g': cmap[:n, :, n_t].copy(), 'status': int(status[0]), 'steps': k,
-            'cells_per_step': per_step[:k + 1].copy(), 'step_ms': step_ms[:max(max_steps, 0)].astype(numpy.float64), 'stats': stats}
+    t = _CellCall(who, n_t, cell_off, cell_rows, cell_region, 'one region and one point', len(cpt), max_steps, max_cells, max_rows_total)
+    cmap = numpy.empty((t.limits[1], n_t, n_t + 1))
+    stats = _geometry_call('mpc_forward_cells', _CELL_STATS, int(device), n_t, R, off, ef, P, p, soff, sidx, *t.cells0, cpt, float(tol), *t.limits,
+                           *t.table, cmap, t.status, t.steps, *t.per_step)
+    r = t.result('region', stats)
+    n = len(r['region'])
+    r['G'], r['g'] = cmap[:n, :, :n_t].copy(), cmap[:n, :, n_t].copy()
+    return r
 
 
 class Locator:

@@ -14,14 +14,11 @@
 //                of Q by ts_pull_back (transition.hpp), a constant one as flag 2 with right-hand side +inf.  The map is staged in LDS as
 //                [n_t][n_t] and [n_t], the layout ts_pull_back reads.
 //     empty        a constant row with beta < -tol: no state of Q lands in R_j (PC_EMPTY), no LP.
-//     radius run   over the m_Q + m_j rows from Q's point, the run stops once t > tol.  Optimal with t <= tol: PC_NONE.  Otherwise the
-//                  item is a cell: PC_CELL, or PC_CELL_WIDE behind an unbounded or capped run.
-//     row loop     rd_row_loop<true> (reduce.hpp) in place over all slots in order: Q's rows, then the pulled-back ones; every run starts
-//                  where the radius run ended.  An unbounded or capped run keeps its row and counts in counters[5].
-//     output       status[item], kept[item][RD_WORDS], n_kept[item], point[item][n_t]: those of k_pre_cells (invariant.hpp).
+//     the rest     pc_judge of invariant.hpp, the tail k_pre_cells runs: the radius run over the m_Q + m_j rows from Q's point, the row
+//                  loop over all slots in order (Q's rows, then the pulled-back ones), status, kept, n_kept, point and the counters.
 //   k_fwd_emit   one wavefront per new cell: the same ov_load and ts_pull_back, so the slots hold bit for bit the rows that were judged;
-//                the kept slots go to the rows [cell_off[c], cell_off[c] + n_kept) of the cell table in slot order; the parent's next
-//                map becomes the child's [G | g], the item's point the child's point.  No LP.
+//                the kept slots go to the rows [cell_off[c], cell_off[c] + n_kept) of the cell table in slot order (pc_scatter of
+//                invariant.hpp); the parent's next map becomes the child's [G | g], the item's point the child's point.  No LP.
 //   The only atomics are the counters; no floating-point atomics: a rerun gives the same bits.
 #pragma once
 #include <stdint.h>
@@ -86,43 +83,13 @@ __global__ void __launch_bounds__(64) k_fwd_cells(FwdCellArgs a) {
     const long long reg = a.item_region[q], cell = a.item_cell[q], r0 = a.row_off[reg], c0 = a.cell_off[cell];
     const int m_q = (int)(a.cell_off[cell + 1] - c0), m_j = (int)(a.row_off[reg + 1] - r0), m = m_q + m_j;
     const double tol = a.tol;
-    unsigned long long pivots = 0, wide = 0, lps = 0;
     fw_stage_map(a.next + (cell - a.first) * (long long)nt * (nt + 1), nt, s_P, s_sh);
     ov_load(S, a.cell_ef, c0, m_q, nt, 0);
     if (lane < TR_D) S.x[lane] = lane < nt ? a.cell_point[cell * nt + lane] : 0.0;
     if (lane < RD_WORDS) s_kept[lane] = 0ull;
     __syncthreads();
     const int empty = __any(ts_pull_back(S, a.ef, r0, m_j, nt, m_q, s_P, s_sh, tol));
-    bool is_cell = false, open = false;
-    double px = 0.0;
-    if (!empty) {
-        const int st = ov_radius(S, m, nt, tol, pivots);
-        lps = 1;
-        open = st == TR_UNBOUNDED || st == TR_CAPPED;
-        wide += open;
-        is_cell = !(st == TR_OPTIMAL && !(S.x[nt] > tol));
-        px = lane < nt ? S.x[lane] : 0.0;
-    }
-    if (is_cell) rd_row_loop<true>(S, m, nt, tol, px, pivots, lps, wide, s_kept);
-    __syncthreads();
-    int count = 0;
-    if (lane < RD_WORDS) {
-        a.kept[q * RD_WORDS + lane] = s_kept[lane];
-        count = __popcll(s_kept[lane]);
-    }
-#pragma unroll
-    for (int off = 4; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    if (lane < nt) a.point[q * nt + lane] = px;
-    if (lane == 0) {
-        a.status[q] = empty ? PC_EMPTY : !is_cell ? PC_NONE : open ? PC_CELL_WIDE : PC_CELL;
-        a.n_kept[q] = count;
-        atomicAdd(a.counters + 0, 1ull);
-        atomicAdd(a.counters + 1, is_cell ? 1ull : 0ull);
-        atomicAdd(a.counters + 2, empty ? 1ull : 0ull);
-        atomicAdd(a.counters + 3, lps);
-        atomicAdd(a.counters + 4, pivots);
-        atomicAdd(a.counters + 5, wide);
-    }
+    pc_judge(S, m, nt, tol, empty, s_kept, q, a.status, a.n_kept, a.kept, a.point, a.counters);
 }
 
 struct FwdEmitArgs {
@@ -162,18 +129,7 @@ __global__ void __launch_bounds__(64) k_fwd_emit(FwdEmitArgs a) {
     __syncthreads();
     if (lane < nt) a.cell_point[(a.first_cell + c) * nt + lane] = a.point[q * nt + lane];
     for (int e = lane; e < nt * nr; e += 64) a.cell_map[(a.first_cell + c) * (long long)nt * nr + e] = map[e];
-    const unsigned long long *mask = a.kept + q * RD_WORDS;
-    for (int k = lane; k < m; k += 64) {
-        const int w = k >> 6;
-        const unsigned long long word = mask[w];
-        if (!((word >> (k & 63)) & 1ull)) continue;
-        long long at = out0 + __popcll(word & ((1ull << (k & 63)) - 1ull));
-        for (int u = 0; u < w; ++u) at += __popcll(mask[u]);
-        if (at >= out1) continue;         // the scan and the mask agree by construction: never taken, and never a store past the cell
-        double *out = a.cell_ef + at * (long long)nr;
-        out[0] = S.b[k];
-        for (int t = 0; t < nt; ++t) out[1 + t] = S.A[k * nr + t];
-    }
+    pc_scatter(S, m, nt, a.kept + q * RD_WORDS, out0, out1, a.cell_ef);
 }
 
 }  // namespace mpc

@@ -1851,9 +1851,216 @@ extern "C" int mpc_project_rows(int32_t device, int32_t n, int32_t n_elim, int64
     return family_close(s, d_cnt, 9, stats, ms);
 }
 
+// ---- the cell table of the two calls that loop: backward exit cells and forward cells ---------------------------
+// Both keep the cells of all steps in one CSR table that stays on the device and grows step by step; per step the item list goes up,
+// status and n_kept come down, the host scans the offsets and lists the next items.  What the two do alike is here once: the argument
+// checks, the table with its host and device side, the item list, the scan, the append, and the two ways out.  Each call keeps its own
+// loop, launches and stop rules.
+
+// What differs in the argument checks of a call: the names in its refusals, its own null checks, the start points it takes.
+struct CellCall {
+    const char *who, *who_cells;          // "mpc_x", "mpc_x (cells)"
+    const char *adj, *adj_noun;           // "pred", "predecessor": <adj>_off, <adj>_idx, "a <adj_noun> list ..."
+    const char *no_outputs;               // the refusal of a missing scalar output
+    const char *cell0, *cell_noun;        // "missing <cell0>", "a cell names a <cell_noun> out of range"
+    bool has_outputs, has_cell0, has_arrays;      // the scalar outputs, the per-cell inputs of step 0, the output arrays: all there
+    bool want_xs;
+    const double *xs, *cell_point0;       // [n_regions][n_t] with want_xs; [n_cells0][n_t] or nullptr: the call takes none
+};
+
+static int cells_check(const CellCall &c, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
+                       const double *phi, const int64_t *adj_off, const int32_t *adj_idx, int64_t n_cells0, const int64_t *cell_off0,
+                       const double *cell_rows0, const int32_t *cell_reg0, double tol, int32_t max_steps, int64_t max_cells, int64_t max_rows_total) {
+    const char *who = c.who;
+    int m_reg = 1, m_cell = 1;
+    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
+    if (int rc = merge_check(c.who_cells, n_t, n_cells0, cell_off0, cell_rows0, &m_cell)) return rc;
+    if (int rc = check_tol(who, tol)) return rc;
+    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, c.want_xs, c.xs)) return rc;
+    if (max_steps < 0) return bad(who, "max_steps must be >= 0");
+    if (max_cells < 0 || max_cells > 0x7fffffffll || max_rows_total < 0) return bad(who, "max_cells must lie in 0..2^31 - 1 and max_rows_total be >= 0");
+    if (!c.has_outputs) return bad(who, c.no_outputs);
+    if (n_regions > 0) {
+        if (!adj_off || adj_off[0] != 0) return bad(who, std::string(c.adj) + "_off must start at 0");
+        for (int64_t i = 0; i < n_regions; ++i)
+            if (adj_off[i + 1] < adj_off[i]) return bad(who, std::string(c.adj) + "_off must not decrease");
+        if (adj_off[n_regions] > 0 && !adj_idx) return bad(who, std::string("missing ") + c.adj + "_idx");
+        for (int64_t k = 0; k < adj_off[n_regions]; ++k)
+            if (adj_idx[k] < 0 || adj_idx[k] >= n_regions) return bad(who, std::string("a ") + c.adj_noun + " list names a region out of range");
+    }
+    if (n_cells0 > 0) {
+        if (!c.has_cell0) return bad(who, std::string("missing ") + c.cell0);
+        for (int64_t k = 0; k < n_cells0; ++k)
+            if (cell_reg0[k] < 0 || cell_reg0[k] >= n_regions) return bad(who, std::string("a cell names a ") + c.cell_noun + " out of range");
+        if (c.cell_point0)
+            if (int rc = check_finite(who, "cell_point0", c.cell_point0, n_cells0 * n_t)) return rc;
+        if (n_cells0 > max_cells || cell_off0[n_cells0] > max_rows_total) return bad(who, "the cells of step 0 exceed max_cells or max_rows_total");
+        if (!c.has_arrays) return bad(who, "missing output array");
+    }
+    return MPC_OK;
+}
+
+// b grown to ``bytes`` with what it holds kept: for a table of all steps
+static void grow_kept(OneShot &s, DevBuf &b, size_t bytes) { if (s.ok()) s.chk(b.ensure(bytes, s.st, true)); }
+
+// where a call wants the host's side of the table
+struct CellOut { int64_t *n_cells; int32_t *status, *steps; int64_t *cell_off; int32_t *cell_reg, *cell_step, *cell_parent, *cell_wide; };
+
+struct CellTable {
+    const int n_t;
+    const int64_t n_cells0;
+    // the host's side: everything but the rows, the points and what else a call keeps per cell
+    std::vector<int64_t> off;
+    std::vector<int32_t> reg, stp, par, wid;      // reg: the source region (backward) or the region (forward) of a cell
+    int64_t lo = 0, hi;                           // the cells of the last completed step
+    // the device's side (to_device): offsets, rows [.][n_t + 1] and points [cells][n_t] of all steps; the items, the new cells' items, and
+    // per item what the cell kernel writes: status, n_kept, kept [RD_WORDS], point [n_t]
+    DevBuf *d_off = nullptr, *d_rows = nullptr, *d_pt = nullptr;
+    DevBuf *d_ir = nullptr, *d_ic = nullptr, *d_ci = nullptr, *d_st = nullptr, *d_nk = nullptr, *d_kept = nullptr, *d_ipt = nullptr;
+    // the items of the next step (list_items); what came down for them, and the new cells in item order (scan)
+    std::vector<int32_t> item_region, item_cell, st, nk, cell_item;
+    int item_rows = 2;                            // the LDS rows of the largest item
+    bool too_many = false, fat = false;           // more than 2^31 - 1 items; a new cell with no row or more than OV_MAX_ROWS
+    int64_t new_rows = 0;
+
+    CellTable(int n_t_, int64_t n0, const int64_t *cell_off0, const int32_t *cell_reg0) : n_t(n_t_), n_cells0(n0), off(1, 0), hi(n0) {
+        if (n0 > 0) {
+            off.assign(cell_off0, cell_off0 + n0 + 1);
+            reg.assign(cell_reg0, cell_reg0 + n0);
+            stp.assign((size_t)n0, 0);
+            par.assign((size_t)n0, -1);
+            wid.assign((size_t)n0, 0);
+        }
+    }
+    size_t row_bytes() const { return (size_t)off.back() * ((size_t)n_t + 1) * 8; }
+
+    // cells_per_step [max_steps + 1] and step_ms [max_steps] before the first step
+    void open_steps(int64_t *cells_per_step, float *step_ms, int max_steps) const {
+        if (cells_per_step) {
+            for (int k = 0; k <= max_steps; ++k) cells_per_step[k] = 0;
+            cells_per_step[0] = n_cells0;
+        }
+        if (step_ms) for (int k = 0; k < max_steps; ++k) step_ms[k] = 0.0f;
+    }
+
+    // cell_point0 == nullptr: the cells of step 0 have no point
+    void to_device(OneShot &s, const double *cell_rows0, const double *cell_point0) {
+        const size_t pt_bytes = (size_t)n_cells0 * n_t * 8;
+        d_off = &s.upload(off.data(), off.size() * 8);
+        d_rows = &s.upload(cell_rows0, row_bytes());
+        d_pt = cell_point0 ? &s.upload(cell_point0, pt_bytes) : &s.buf(pt_bytes);
+        d_ir = &s.buf(); d_ic = &s.buf(); d_ci = &s.buf(); d_st = &s.buf(); d_nk = &s.buf(); d_kept = &s.buf(); d_ipt = &s.buf();
+    }
+
+    // The items of the next step: by parent cell of the last step, then as the adjacency list of its region is.  Both operands of an item
+    // passed merge_check at MG_MAX_ROWS, so item_rows fits the row loop.
+    static_assert(2 * MG_MAX_ROWS <= RD_MAX_ROWS, "an item's rows must fit rd_row_loop");
+    void list_items(const int64_t *adj_off, const int32_t *adj_idx, const int64_t *row_off) {
+        item_region.clear();
+        item_cell.clear();
+        item_rows = 2;
+        too_many = false;
+        for (int64_t c = lo; c < hi && !too_many; ++c) {
+            const int64_t i = reg[(size_t)c], m_q = off[(size_t)c + 1] - off[(size_t)c];
+            for (int64_t k = adj_off[i]; k < adj_off[i + 1]; ++k) {
+                const int32_t j = adj_idx[k];
+                item_region.push_back(j);
+                item_cell.push_back((int32_t)c);
+                item_rows = std::max<int>(item_rows, (int)(row_off[j + 1] - row_off[j] + m_q));
+            }
+            too_many = item_region.size() > 0x7fffffffull;
+        }
+    }
+
+    // the item list up, room for what the cell kernel writes
+    void upload_items(OneShot &s) {
+        const size_t ni = item_region.size();
+        s.upload(*d_ir, item_region.data(), ni * 4);
+        s.upload(*d_ic, item_cell.data(), ni * 4);
+        s.ensure(*d_st, ni * 4); s.ensure(*d_nk, ni * 4); s.ensure(*d_kept, ni * RD_WORDS * 8); s.ensure(*d_ipt, ni * n_t * 8);
+    }
+
+    // status and n_kept down, then the scan: the cells of this step in item order
+    void scan(OneShot &s) {
+        const size_t ni = item_region.size();
+        st.resize(ni); nk.resize(ni);
+        s.download(st.data(), *d_st, ni * 4);       // blocking copies on the null stream: the launch has ended
+        s.download(nk.data(), *d_nk, ni * 4);
+        cell_item.clear();
+        new_rows = 0;
+        fat = false;
+        if (!s.ok()) return;
+        for (size_t q = 0; q < ni; ++q) {
+            if (st[q] != PC_CELL && st[q] != PC_CELL_WIDE) continue;
+            fat = fat || nk[q] < 1 || nk[q] > OV_MAX_ROWS;
+            cell_item.push_back((int32_t)q);
+            new_rows += nk[q];
+        }
+    }
+
+    // The caps on the scanned cells, in their one order; true and the call's own *code (for a fat cell, max_cells, max_rows_total) when
+    // one refuses them.
+    bool refused(int64_t max_cells, int64_t max_rows_total, int rows, int cells, int rows_total, int *code) const {
+        if (cell_item.empty()) return false;
+        if (fat) *code = rows;
+        else if ((int64_t)(reg.size() + cell_item.size()) > max_cells) *code = cells;
+        else if (off.back() + new_rows > max_rows_total) *code = rows_total;
+        else return false;
+        return true;
+    }
+
+    // The scanned cells join the table as step ``step``: the host's vectors, the device's tables grown with their contents kept, the
+    // tail of the offsets and cell_item up.  Returns the first new cell; lo and hi stay until advance().
+    size_t append(OneShot &s, int step) {
+        const size_t nn = cell_item.size(), nc = reg.size();
+        for (size_t c = 0; c < nn; ++c) {
+            const size_t q = (size_t)cell_item[c], parent = (size_t)item_cell[q];
+            off.push_back(off.back() + nk[q]);
+            reg.push_back(item_region[q]);
+            stp.push_back(step);
+            par.push_back((int32_t)parent);
+            wid.push_back(st[q] == PC_CELL_WIDE || wid[parent] ? 1 : 0);
+        }
+        grow_kept(s, *d_off, (nc + nn + 1) * 8);
+        grow_kept(s, *d_rows, row_bytes());
+        grow_kept(s, *d_pt, (nc + nn) * n_t * 8);
+        if (s.ok()) s.chk(hipMemcpy(d_off->as<int64_t>() + nc + 1, off.data() + nc + 1, nn * 8, hipMemcpyHostToDevice));
+        s.upload(*d_ci, cell_item.data(), nn * 4);
+        return nc;
+    }
+    void advance() { lo = hi; hi = (int64_t)reg.size(); }
+
+    void deliver(const CellOut &o, int code, int n_steps) const {
+        const size_t nc = reg.size();
+        *o.n_cells = (int64_t)nc;
+        *o.status = code;
+        *o.steps = n_steps;
+        if (o.cell_off) std::memcpy(o.cell_off, off.data(), (nc + 1) * 8);
+        if (nc) {
+            std::memcpy(o.cell_reg, reg.data(), nc * 4);
+            std::memcpy(o.cell_step, stp.data(), nc * 4);
+            std::memcpy(o.cell_parent, par.data(), nc * 4);
+            std::memcpy(o.cell_wide, wid.data(), nc * 4);
+        }
+    }
+
+    // The closing download: the rows, the points of the cells from ``first_point`` on (cell_point == nullptr: none), the six counters to
+    // stats; the call's code.
+    int close(OneShot &s, const DevBuf &d_cnt, double *cell_rows, double *cell_point, size_t first_point, int64_t *stats) const {
+        if (!s.ok()) return s.finish();
+        const size_t nc = reg.size();
+        s.download(cell_rows, *d_rows, row_bytes());
+        if (cell_point && nc > first_point && s.ok())
+            s.chk(hipMemcpy(cell_point + first_point * n_t, d_pt->as<double>() + first_point * n_t, (nc - first_point) * n_t * 8, hipMemcpyDeviceToHost));
+        unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
+        s.download(cnt, d_cnt, sizeof cnt);
+        if (const int rc = s.finish()) return rc;
+        if (stats) for (int i = 0; i < 6; ++i) stats[i] = (int64_t)cnt[i];
+        return MPC_OK;
+    }
+};
+
 // ---- backward exit cells of a closed loop (invariant.hpp) ---------------------------------------------------------------
-// The one call of the family that loops: the cell table (offsets, rows, points) stays on the device and grows step by step; per step the
-// item list goes up, status and n_kept come down, the host scans the offsets and lists the next items.
 extern "C" int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
                                   const double *phi, const double *xs, const int64_t *pred_off, const int32_t *pred_idx, int64_t n_cells0,
                                   const int64_t *cell_off0, const double *cell_rows0, const int32_t *cell_source0, double tol, int32_t max_steps,
@@ -1867,149 +2074,60 @@ extern "C" int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions
     if (steps) *steps = 0;
     if (converged) *converged = 0;
     if (status) *status = MPC_BACKWARD_MAX_STEPS;
-    int m_reg = 1, m_cell = 1;
-    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
-    if (int rc = merge_check("mpc_backward_exits (cells)", n_t, n_cells0, cell_off0, cell_rows0, &m_cell)) return rc;
-    if (int rc = check_tol(who, tol)) return rc;
-    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, true, xs)) return rc;
-    if (max_steps < 0) return bad(who, "max_steps must be >= 0");
-    if (max_cells < 0 || max_cells > 0x7fffffffll || max_rows_total < 0) return bad(who, "max_cells must lie in 0..2^31 - 1 and max_rows_total be >= 0");
-    if (!n_cells || !status || !steps || !converged) return bad(who, "missing output (n_cells, status, steps or converged)");
-    if (n_regions > 0) {
-        if (!pred_off || pred_off[0] != 0) return bad(who, "pred_off must start at 0");
-        for (int64_t i = 0; i < n_regions; ++i)
-            if (pred_off[i + 1] < pred_off[i]) return bad(who, "pred_off must not decrease");
-        if (pred_off[n_regions] > 0 && !pred_idx) return bad(who, "missing pred_idx");
-        for (int64_t k = 0; k < pred_off[n_regions]; ++k)
-            if (pred_idx[k] < 0 || pred_idx[k] >= n_regions) return bad(who, "a predecessor list names a region out of range");
-    }
-    const int64_t rows0 = n_cells0 > 0 ? cell_off0[n_cells0] : 0;
-    if (n_cells0 > 0) {
-        if (!cell_source0) return bad(who, "missing cell_source0");
-        for (int64_t c = 0; c < n_cells0; ++c)
-            if (cell_source0[c] < 0 || cell_source0[c] >= n_regions) return bad(who, "a cell names a source region out of range");
-        if (n_cells0 > max_cells || rows0 > max_rows_total) return bad(who, "the cells of step 0 exceed max_cells or max_rows_total");
-        if (!cell_off || !cell_rows || !cell_source || !cell_step || !cell_parent || !cell_wide) return bad(who, "missing output array");
-    }
-    // the host's side of the cell table: everything but the rows
-    std::vector<int64_t> off(1, 0);
-    std::vector<int32_t> src, stp, par, wid;
-    if (n_cells0 > 0) {
-        off.assign(cell_off0, cell_off0 + n_cells0 + 1);
-        src.assign(cell_source0, cell_source0 + n_cells0);
-        stp.assign((size_t)n_cells0, 0);
-        par.assign((size_t)n_cells0, -1);
-        wid.assign((size_t)n_cells0, 0);
-    }
-    const size_t nr = (size_t)n_regions, w = (size_t)n_t + 1;
-    auto deliver = [&](int code, int n_steps) {
-        const size_t nc = src.size();
-        *n_cells = (int64_t)nc;
-        *status = code;
-        *steps = n_steps;
-        *converged = code == MPC_BACKWARD_CONVERGED;
-        if (cell_off) std::memcpy(cell_off, off.data(), (nc + 1) * 8);
-        if (nc) {
-            std::memcpy(cell_source, src.data(), nc * 4);
-            std::memcpy(cell_step, stp.data(), nc * 4);
-            std::memcpy(cell_parent, par.data(), nc * 4);
-            std::memcpy(cell_wide, wid.data(), nc * 4);
-        }
-    };
-    if (cells_per_step) {
-        for (int k = 0; k <= max_steps; ++k) cells_per_step[k] = 0;
-        cells_per_step[0] = n_cells0;
-    }
-    if (step_ms) for (int k = 0; k < max_steps; ++k) step_ms[k] = 0.0f;
+    const CellCall call{who, "mpc_backward_exits (cells)", "pred", "predecessor", "missing output (n_cells, status, steps or converged)",
+                        "cell_source0", "source region", n_cells && status && steps && converged, cell_source0 != nullptr,
+                        cell_off && cell_rows && cell_source && cell_step && cell_parent && cell_wide, true, xs, nullptr};
+    if (int rc = cells_check(call, n_t, n_regions, row_off, ef_rows, Phi, phi, pred_off, pred_idx, n_cells0, cell_off0, cell_rows0, cell_source0, tol,
+                             max_steps, max_cells, max_rows_total))
+        return rc;
+    CellTable t(n_t, n_cells0, cell_off0, cell_source0);
+    const CellOut out{n_cells, status, steps, cell_off, cell_source, cell_step, cell_parent, cell_wide};
+    t.open_steps(cells_per_step, step_ms, max_steps);
     if (n_cells0 == 0 || max_steps == 0) {
-        deliver(n_cells0 == 0 ? MPC_BACKWARD_CONVERGED : MPC_BACKWARD_MAX_STEPS, 0);
-        if (n_cells0 > 0) std::memcpy(cell_rows, cell_rows0, (size_t)rows0 * w * 8);
+        t.deliver(out, n_cells0 == 0 ? MPC_BACKWARD_CONVERGED : MPC_BACKWARD_MAX_STEPS, 0);
+        *converged = n_cells0 == 0;
+        if (n_cells0 > 0) std::memcpy(cell_rows, cell_rows0, t.row_bytes());
         return MPC_OK;
     }
     if (int rc = select_device(nullptr, device)) return rc;
     OneShot s(who, nullptr, true);
+    const size_t nr = (size_t)n_regions;
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8), &d_xs = s.upload(xs, nr * n_t * 8);
-    DevBuf &d_coff = s.upload(off.data(), off.size() * 8), &d_crow = s.upload(cell_rows0, (size_t)rows0 * w * 8);
-    DevBuf &d_cpt = s.buf((size_t)n_cells0 * n_t * 8), &d_cnt = family_counters(s, 6);
-    DevBuf &d_ir = s.buf(), &d_ic = s.buf(), &d_ci = s.buf(), &d_st = s.buf(), &d_nk = s.buf(), &d_kept = s.buf(), &d_pt = s.buf();
-    auto grow = [&](DevBuf &b, size_t bytes) { if (s.ok()) s.chk(b.ensure(bytes, s.st, true)); };   // keeps what the table holds
-    std::vector<int32_t> item_region, item_cell, st, nk, cell_item;
-    int64_t lo = 0, hi = n_cells0;      // the cells of the last completed step
+    t.to_device(s, cell_rows0, nullptr);
+    DevBuf &d_cnt = family_counters(s, 6);
     int step = 0, code = MPC_BACKWARD_CONVERGED;
     float total_ms = 0.0f;
     for (;;) {
-        // the items of step + 1: by parent cell, then as the predecessor list is
-        item_region.clear();
-        item_cell.clear();
-        int item_rows = 2;
-        bool too_many = false;
-        for (int64_t c = lo; c < hi && !too_many; ++c) {
-            const int64_t j = src[(size_t)c], m_q = off[(size_t)c + 1] - off[(size_t)c];
-            for (int64_t k = pred_off[j]; k < pred_off[j + 1]; ++k) {
-                const int32_t i = pred_idx[k];
-                item_region.push_back(i);
-                item_cell.push_back((int32_t)c);
-                item_rows = std::max<int>(item_rows, (int)(row_off[i + 1] - row_off[i] + m_q));
-            }
-            too_many = item_region.size() > 0x7fffffffull;
-        }
-        if (item_region.empty()) break;                                       // nothing can precede the last cells: converged
+        t.list_items(pred_off, pred_idx, row_off);
+        if (t.item_region.empty()) break;                                     // nothing can precede the last cells: converged
         if (step == max_steps) { code = MPC_BACKWARD_MAX_STEPS; break; }
-        if (too_many) { code = MPC_BACKWARD_MAX_CELLS; break; }
-        const size_t ni = item_region.size();
-        const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_kept adds 64)
-        s.upload(d_ir, item_region.data(), ni * 4);
-        s.upload(d_ic, item_cell.data(), ni * 4);
-        s.ensure(d_st, ni * 4); s.ensure(d_nk, ni * 4); s.ensure(d_kept, ni * RD_WORDS * 8); s.ensure(d_pt, ni * n_t * 8);
+        if (t.too_many) { code = MPC_BACKWARD_MAX_CELLS; break; }
+        const size_t ni = t.item_region.size();
+        const size_t lds = tr_lds_bytes(t.item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static s_kept adds 64)
+        t.upload_items(s);
         PreCellArgs a{};
-        a.nt = n_t; a.m_max = item_rows; a.n_items = (long long)ni;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = d_coff.as<long long>(); a.cell_ef = d_crow.as<double>();
+        a.nt = n_t; a.m_max = t.item_rows; a.n_items = (long long)ni;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = t.d_off->as<long long>(); a.cell_ef = t.d_rows->as<double>();
         a.Phi = d_Phi.as<double>(); a.phi = d_phi.as<double>(); a.xs = d_xs.as<double>();
-        a.item_region = d_ir.as<int32_t>(); a.item_cell = d_ic.as<int32_t>(); a.tol = tol;
-        a.status = d_st.as<int32_t>(); a.n_kept = d_nk.as<int32_t>(); a.kept = d_kept.as<unsigned long long>();
-        a.point = d_pt.as<double>(); a.counters = d_cnt.as<unsigned long long>();
+        a.item_region = t.d_ir->as<int32_t>(); a.item_cell = t.d_ic->as<int32_t>(); a.tol = tol;
+        a.status = t.d_st->as<int32_t>(); a.n_kept = t.d_nk->as<int32_t>(); a.kept = t.d_kept->as<unsigned long long>();
+        a.point = t.d_ipt->as<double>(); a.counters = d_cnt.as<unsigned long long>();
         family_launch(s, k_pre_cells, (int64_t)ni, lds, a);
-        st.resize(ni); nk.resize(ni);
-        s.download(st.data(), d_st, ni * 4);        // blocking copies on the null stream: the launch has ended
-        s.download(nk.data(), d_nk, ni * 4);
+        t.scan(s);
         float t_cells = 0.0f, t_emit = 0.0f;
         s.elapsed(&t_cells);
         if (!s.ok()) break;
-        // the scan: the cells of this step in item order
-        cell_item.clear();
-        int64_t new_rows = 0;
-        bool fat = false;
-        for (size_t q = 0; q < ni; ++q) {
-            if (st[q] != PC_CELL && st[q] != PC_CELL_WIDE) continue;
-            fat = fat || nk[q] < 1 || nk[q] > OV_MAX_ROWS;
-            cell_item.push_back((int32_t)q);
-            new_rows += nk[q];
-        }
-        const size_t nn = cell_item.size(), nc = src.size();
-        if (nn && fat) code = MPC_BACKWARD_ROWS;
-        else if (nn && (int64_t)(nc + nn) > max_cells) code = MPC_BACKWARD_MAX_CELLS;
-        else if (nn && off.back() + new_rows > max_rows_total) code = MPC_BACKWARD_MAX_ROWS_TOTAL;
-        if (nn && code == MPC_BACKWARD_CONVERGED) {
-            for (size_t c = 0; c < nn; ++c) {
-                const size_t q = (size_t)cell_item[c], parent = (size_t)item_cell[q];
-                off.push_back(off.back() + nk[q]);
-                src.push_back(item_region[q]);
-                stp.push_back(step + 1);
-                par.push_back((int32_t)parent);
-                wid.push_back(st[q] == PC_CELL_WIDE || wid[parent] ? 1 : 0);
-            }
-            grow(d_coff, (nc + nn + 1) * 8);
-            grow(d_crow, (size_t)off.back() * w * 8);
-            grow(d_cpt, (nc + nn) * n_t * 8);
-            if (s.ok()) s.chk(hipMemcpy(d_coff.as<int64_t>() + nc + 1, off.data() + nc + 1, nn * 8, hipMemcpyHostToDevice));
-            s.upload(d_ci, cell_item.data(), nn * 4);
+        const size_t nn = t.cell_item.size();
+        const bool refused = t.refused(max_cells, max_rows_total, MPC_BACKWARD_ROWS, MPC_BACKWARD_MAX_CELLS, MPC_BACKWARD_MAX_ROWS_TOTAL, &code);
+        if (nn && !refused) {
+            const size_t nc = t.append(s, step + 1);
             PreEmitArgs e{};
-            e.nt = n_t; e.m_max = item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc;
-            e.row_off = d.off.as<long long>(); e.cell_off = d_coff.as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = d_crow.as<double>();
-            e.Phi = d_Phi.as<double>(); e.phi = d_phi.as<double>(); e.item_region = d_ir.as<int32_t>(); e.item_cell = d_ic.as<int32_t>();
-            e.cell_item = d_ci.as<int32_t>(); e.kept = d_kept.as<unsigned long long>(); e.point = d_pt.as<double>();
-            e.cell_point = d_cpt.as<double>(); e.tol = tol;
+            e.nt = n_t; e.m_max = t.item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc;
+            e.row_off = d.off.as<long long>(); e.cell_off = t.d_off->as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = t.d_rows->as<double>();
+            e.Phi = d_Phi.as<double>(); e.phi = d_phi.as<double>(); e.item_region = t.d_ir->as<int32_t>(); e.item_cell = t.d_ic->as<int32_t>();
+            e.cell_item = t.d_ci->as<int32_t>(); e.kept = t.d_kept->as<unsigned long long>(); e.point = t.d_ipt->as<double>();
+            e.cell_point = t.d_pt->as<double>(); e.tol = tol;
             family_launch(s, k_pre_emit, (int64_t)nn, lds, e);
             if (s.ok()) s.chk(hipEventSynchronize(s.e1));
             s.elapsed(&t_emit);
@@ -2017,30 +2135,20 @@ extern "C" int mpc_backward_exits(int32_t device, int32_t n_t, int64_t n_regions
         }
         if (step_ms && step < max_steps) step_ms[step] = t_cells + t_emit;
         total_ms += t_cells + t_emit;
-        if (!nn || code != MPC_BACKWARD_CONVERGED) break;                     // a step without a cell: converged
+        if (!nn || refused) break;                                            // a step without a cell: converged
         ++step;
         if (cells_per_step) cells_per_step[step] = (int64_t)nn;
-        lo = hi;
-        hi += (int64_t)nn;
+        t.advance();
     }
-    if (!s.ok()) return s.finish();
-    const size_t nc = src.size();
-    s.download(cell_rows, d_crow, (size_t)off.back() * w * 8);
-    if (cell_point && nc > (size_t)n_cells0 && s.ok())
-        s.chk(hipMemcpy(cell_point + (size_t)n_cells0 * n_t, d_cpt.as<double>() + (size_t)n_cells0 * n_t, (nc - (size_t)n_cells0) * n_t * 8,
-                        hipMemcpyDeviceToHost));
-    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (const int rc = s.finish()) return rc;
-    if (stats) for (int i = 0; i < 6; ++i) stats[i] = (int64_t)cnt[i];
+    if (int rc = t.close(s, d_cnt, cell_rows, cell_point, (size_t)n_cells0, stats)) return rc;
     if (ms) *ms = total_ms;
-    deliver(code, step);
+    t.deliver(out, code, step);
+    *converged = code == MPC_BACKWARD_CONVERGED;
     return MPC_OK;
 }
 
 // ---- forward cells of a closed loop (forward.hpp) ---------------------------------------------------------------------
-// The forward twin of mpc_backward_exits: the cell table (offsets, rows, points, maps) stays on the device and grows step by step; per
-// step the item list and the regions of the new cells go up, status and n_kept come down, the host scans the offsets.
+// Beside the cell table: the maps [G | g] and the regions of the cells on the device, and the points of step 0.
 extern "C" int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions, const int64_t *row_off, const double *ef_rows, const double *Phi,
                                  const double *phi, const int64_t *succ_off, const int32_t *succ_idx, int64_t n_cells0, const int64_t *cell_off0,
                                  const double *cell_rows0, const int32_t *cell_region0, const double *cell_point0, double tol, int32_t max_steps,
@@ -2053,69 +2161,25 @@ extern "C" int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions,
     if (n_cells) *n_cells = 0;
     if (steps) *steps = 0;
     if (status) *status = MPC_FORWARD_DONE;
-    int m_reg = 1, m_cell = 1;
-    if (int rc = merge_check(who, n_t, n_regions, row_off, ef_rows, &m_reg)) return rc;
-    if (int rc = merge_check("mpc_forward_cells (cells)", n_t, n_cells0, cell_off0, cell_rows0, &m_cell)) return rc;
-    if (int rc = check_tol(who, tol)) return rc;
-    if (int rc = transition_check_maps(who, n_t, n_regions, Phi, phi, false, nullptr)) return rc;
-    if (max_steps < 0) return bad(who, "max_steps must be >= 0");
-    if (max_cells < 0 || max_cells > 0x7fffffffll || max_rows_total < 0) return bad(who, "max_cells must lie in 0..2^31 - 1 and max_rows_total be >= 0");
-    if (!n_cells || !status || !steps) return bad(who, "missing output (n_cells, status or steps)");
-    if (n_regions > 0) {
-        if (!succ_off || succ_off[0] != 0) return bad(who, "succ_off must start at 0");
-        for (int64_t i = 0; i < n_regions; ++i)
-            if (succ_off[i + 1] < succ_off[i]) return bad(who, "succ_off must not decrease");
-        if (succ_off[n_regions] > 0 && !succ_idx) return bad(who, "missing succ_idx");
-        for (int64_t k = 0; k < succ_off[n_regions]; ++k)
-            if (succ_idx[k] < 0 || succ_idx[k] >= n_regions) return bad(who, "a successor list names a region out of range");
-    }
-    const int64_t rows0 = n_cells0 > 0 ? cell_off0[n_cells0] : 0;
-    if (n_cells0 > 0) {
-        if (!cell_region0 || !cell_point0) return bad(who, "missing cell_region0 or cell_point0");
-        for (int64_t c = 0; c < n_cells0; ++c)
-            if (cell_region0[c] < 0 || cell_region0[c] >= n_regions) return bad(who, "a cell names a region out of range");
-        if (int rc = check_finite(who, "cell_point0", cell_point0, n_cells0 * n_t)) return rc;
-        if (n_cells0 > max_cells || rows0 > max_rows_total) return bad(who, "the cells of step 0 exceed max_cells or max_rows_total");
-        if (!cell_off || !cell_rows || !cell_region || !cell_step || !cell_parent || !cell_wide || !cell_point || !cell_map)
-            return bad(who, "missing output array");
-    }
-    // the host's side of the cell table: everything but rows, points and maps
-    std::vector<int64_t> off(1, 0);
-    std::vector<int32_t> reg, stp, par, wid;
-    if (n_cells0 > 0) {
-        off.assign(cell_off0, cell_off0 + n_cells0 + 1);
-        reg.assign(cell_region0, cell_region0 + n_cells0);
-        stp.assign((size_t)n_cells0, 0);
-        par.assign((size_t)n_cells0, -1);
-        wid.assign((size_t)n_cells0, 0);
-    }
+    const CellCall call{who, "mpc_forward_cells (cells)", "succ", "successor", "missing output (n_cells, status or steps)",
+                        "cell_region0 or cell_point0", "region", n_cells && status && steps, cell_region0 && cell_point0,
+                        cell_off && cell_rows && cell_region && cell_step && cell_parent && cell_wide && cell_point && cell_map, false, nullptr,
+                        cell_point0};
+    if (int rc = cells_check(call, n_t, n_regions, row_off, ef_rows, Phi, phi, succ_off, succ_idx, n_cells0, cell_off0, cell_rows0, cell_region0, tol,
+                             max_steps, max_cells, max_rows_total))
+        return rc;
+    CellTable t(n_t, n_cells0, cell_off0, cell_region0);
+    const CellOut out{n_cells, status, steps, cell_off, cell_region, cell_step, cell_parent, cell_wide};
     const size_t nr = (size_t)n_regions, w = (size_t)n_t + 1, map_doubles = (size_t)n_t * w;
     // step 0: theta_0 = I theta_0 + 0
     std::vector<double> map0((size_t)n_cells0 * map_doubles, 0.0);
     for (size_t c = 0; c < (size_t)n_cells0; ++c)
-        for (int t = 0; t < n_t; ++t) map0[c * map_doubles + (size_t)t * w + t] = 1.0;
-    auto deliver = [&](int code, int n_steps) {
-        const size_t nc = reg.size();
-        *n_cells = (int64_t)nc;
-        *status = code;
-        *steps = n_steps;
-        if (cell_off) std::memcpy(cell_off, off.data(), (nc + 1) * 8);
-        if (nc) {
-            std::memcpy(cell_region, reg.data(), nc * 4);
-            std::memcpy(cell_step, stp.data(), nc * 4);
-            std::memcpy(cell_parent, par.data(), nc * 4);
-            std::memcpy(cell_wide, wid.data(), nc * 4);
-        }
-    };
-    if (cells_per_step) {
-        for (int k = 0; k <= max_steps; ++k) cells_per_step[k] = 0;
-        cells_per_step[0] = n_cells0;
-    }
-    if (step_ms) for (int k = 0; k < max_steps; ++k) step_ms[k] = 0.0f;
+        for (int k = 0; k < n_t; ++k) map0[c * map_doubles + (size_t)k * w + k] = 1.0;
+    t.open_steps(cells_per_step, step_ms, max_steps);
     if (n_cells0 == 0 || max_steps == 0) {
-        deliver(n_cells0 == 0 ? MPC_FORWARD_EMPTY : MPC_FORWARD_DONE, 0);
+        t.deliver(out, n_cells0 == 0 ? MPC_FORWARD_EMPTY : MPC_FORWARD_DONE, 0);
         if (n_cells0 > 0) {
-            std::memcpy(cell_rows, cell_rows0, (size_t)rows0 * w * 8);
+            std::memcpy(cell_rows, cell_rows0, t.row_bytes());
             std::memcpy(cell_point, cell_point0, (size_t)n_cells0 * n_t * 8);
             std::memcpy(cell_map, map0.data(), map0.size() * 8);
         }
@@ -2125,97 +2189,48 @@ extern "C" int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions,
     OneShot s(who, nullptr, true);
     const RegionsOnDevice d = upload_regions(s, n_regions, row_off, ef_rows, n_t + 1);
     DevBuf &d_Phi = s.upload(Phi, nr * n_t * n_t * 8), &d_phi = s.upload(phi, nr * n_t * 8);
-    DevBuf &d_coff = s.upload(off.data(), off.size() * 8), &d_crow = s.upload(cell_rows0, (size_t)rows0 * w * 8);
-    DevBuf &d_cpt = s.upload(cell_point0, (size_t)n_cells0 * n_t * 8), &d_cmap = s.upload(map0.data(), map0.size() * 8);
-    DevBuf &d_creg = s.upload(reg.data(), reg.size() * 4), &d_cnt = family_counters(s, 6);
-    DevBuf &d_next = s.buf(), &d_ir = s.buf(), &d_ic = s.buf(), &d_ci = s.buf(), &d_st = s.buf(), &d_nk = s.buf(), &d_kept = s.buf(), &d_pt = s.buf();
-    auto grow = [&](DevBuf &b, size_t bytes) { if (s.ok()) s.chk(b.ensure(bytes, s.st, true)); };   // keeps what the table holds
-    std::vector<int32_t> item_region, item_cell, st, nk, cell_item;
-    int64_t lo = 0, hi = n_cells0;      // the cells of the last completed step
+    t.to_device(s, cell_rows0, cell_point0);
+    DevBuf &d_cmap = s.upload(map0.data(), map0.size() * 8), &d_creg = s.upload(t.reg.data(), t.reg.size() * 4), &d_cnt = family_counters(s, 6);
+    DevBuf &d_next = s.buf();
     int step = 0, code = MPC_FORWARD_DONE;
     float total_ms = 0.0f;
     while (step < max_steps) {
-        // the items of step + 1: by parent cell, then as the successor list is
-        item_region.clear();
-        item_cell.clear();
-        int item_rows = 2;
-        bool too_many = false;
-        for (int64_t c = lo; c < hi && !too_many; ++c) {
-            const int64_t i = reg[(size_t)c], m_q = off[(size_t)c + 1] - off[(size_t)c];
-            for (int64_t k = succ_off[i]; k < succ_off[i + 1]; ++k) {
-                const int32_t j = succ_idx[k];
-                item_region.push_back(j);
-                item_cell.push_back((int32_t)c);
-                item_rows = std::max<int>(item_rows, (int)(row_off[j + 1] - row_off[j] + m_q));
-            }
-            too_many = item_region.size() > 0x7fffffffull;
-        }
-        if (item_region.empty()) { code = MPC_FORWARD_EMPTY; break; }          // no region follows the last cells: every trajectory has left
-        if (too_many) { code = MPC_FORWARD_MAX_CELLS; break; }
-        if (item_rows > RD_MAX_ROWS) { code = MPC_FORWARD_ROWS; break; }
-        const size_t ni = item_region.size(), np = (size_t)(hi - lo);
-        const size_t lds = tr_lds_bytes(item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static arrays add 2,528)
+        t.list_items(succ_off, succ_idx, row_off);
+        if (t.item_region.empty()) { code = MPC_FORWARD_EMPTY; break; }        // no region follows the last cells: every trajectory has left
+        if (t.too_many) { code = MPC_FORWARD_MAX_CELLS; break; }
+        const size_t ni = t.item_region.size(), np = (size_t)(t.hi - t.lo);
+        const size_t lds = tr_lds_bytes(t.item_rows, n_t);   // 512 rows at n_t = 16: 78,840 bytes (the static arrays add 2,528)
         float t_maps = 0.0f, t_cells = 0.0f, t_emit = 0.0f;
-        s.upload(d_ir, item_region.data(), ni * 4);
-        s.upload(d_ic, item_cell.data(), ni * 4);
+        t.upload_items(s);
         s.ensure(d_next, np * map_doubles * 8);
-        family_launch(s, k_fwd_maps, (int64_t)np, 0, (int)n_t, (long long)np, (long long)lo, d_creg.as<int32_t>(), d_Phi.as<double>(),
+        family_launch(s, k_fwd_maps, (int64_t)np, 0, (int)n_t, (long long)np, (long long)t.lo, d_creg.as<int32_t>(), d_Phi.as<double>(),
                       d_phi.as<double>(), d_cmap.as<double>(), d_next.as<double>());
         if (s.ok()) s.chk(hipEventSynchronize(s.e1));
         s.elapsed(&t_maps);
-        s.ensure(d_st, ni * 4); s.ensure(d_nk, ni * 4); s.ensure(d_kept, ni * RD_WORDS * 8); s.ensure(d_pt, ni * n_t * 8);
         FwdCellArgs a{};
-        a.nt = n_t; a.m_max = item_rows; a.n_items = (long long)ni; a.first = (long long)lo;
-        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = d_coff.as<long long>(); a.cell_ef = d_crow.as<double>();
-        a.next = d_next.as<double>(); a.cell_point = d_cpt.as<double>();
-        a.item_region = d_ir.as<int32_t>(); a.item_cell = d_ic.as<int32_t>(); a.tol = tol;
-        a.status = d_st.as<int32_t>(); a.n_kept = d_nk.as<int32_t>(); a.kept = d_kept.as<unsigned long long>();
-        a.point = d_pt.as<double>(); a.counters = d_cnt.as<unsigned long long>();
+        a.nt = n_t; a.m_max = t.item_rows; a.n_items = (long long)ni; a.first = (long long)t.lo;
+        a.row_off = d.off.as<long long>(); a.ef = d.ef.as<double>(); a.cell_off = t.d_off->as<long long>(); a.cell_ef = t.d_rows->as<double>();
+        a.next = d_next.as<double>(); a.cell_point = t.d_pt->as<double>();
+        a.item_region = t.d_ir->as<int32_t>(); a.item_cell = t.d_ic->as<int32_t>(); a.tol = tol;
+        a.status = t.d_st->as<int32_t>(); a.n_kept = t.d_nk->as<int32_t>(); a.kept = t.d_kept->as<unsigned long long>();
+        a.point = t.d_ipt->as<double>(); a.counters = d_cnt.as<unsigned long long>();
         family_launch(s, k_fwd_cells, (int64_t)ni, lds, a);
-        st.resize(ni); nk.resize(ni);
-        s.download(st.data(), d_st, ni * 4);        // blocking copies on the null stream: the launch has ended
-        s.download(nk.data(), d_nk, ni * 4);
+        t.scan(s);
         s.elapsed(&t_cells);
         if (!s.ok()) break;
-        // the scan: the cells of this step in item order
-        cell_item.clear();
-        int64_t new_rows = 0;
-        bool fat = false;
-        for (size_t q = 0; q < ni; ++q) {
-            if (st[q] != PC_CELL && st[q] != PC_CELL_WIDE) continue;
-            fat = fat || nk[q] < 1 || nk[q] > OV_MAX_ROWS;
-            cell_item.push_back((int32_t)q);
-            new_rows += nk[q];
-        }
-        const size_t nn = cell_item.size(), nc = reg.size();
-        bool refused = true;
-        if (nn && fat) code = MPC_FORWARD_ROWS;
-        else if (nn && (int64_t)(nc + nn) > max_cells) code = MPC_FORWARD_MAX_CELLS;
-        else if (nn && off.back() + new_rows > max_rows_total) code = MPC_FORWARD_MAX_ROWS_TOTAL;
-        else refused = false;
+        const size_t nn = t.cell_item.size();
+        const bool refused = t.refused(max_cells, max_rows_total, MPC_FORWARD_ROWS, MPC_FORWARD_MAX_CELLS, MPC_FORWARD_MAX_ROWS_TOTAL, &code);
         if (nn && !refused) {
-            for (size_t c = 0; c < nn; ++c) {
-                const size_t q = (size_t)cell_item[c], parent = (size_t)item_cell[q];
-                off.push_back(off.back() + nk[q]);
-                reg.push_back(item_region[q]);
-                stp.push_back(step + 1);
-                par.push_back((int32_t)parent);
-                wid.push_back(st[q] == PC_CELL_WIDE || wid[parent] ? 1 : 0);
-            }
-            grow(d_coff, (nc + nn + 1) * 8);
-            grow(d_crow, (size_t)off.back() * w * 8);
-            grow(d_cpt, (nc + nn) * n_t * 8);
-            grow(d_cmap, (nc + nn) * map_doubles * 8);
-            grow(d_creg, (nc + nn) * 4);
-            if (s.ok()) s.chk(hipMemcpy(d_coff.as<int64_t>() + nc + 1, off.data() + nc + 1, nn * 8, hipMemcpyHostToDevice));
-            if (s.ok()) s.chk(hipMemcpy(d_creg.as<int32_t>() + nc, reg.data() + nc, nn * 4, hipMemcpyHostToDevice));
-            s.upload(d_ci, cell_item.data(), nn * 4);
+            const size_t nc = t.append(s, step + 1);
+            grow_kept(s, d_cmap, (nc + nn) * map_doubles * 8);
+            grow_kept(s, d_creg, (nc + nn) * 4);
+            if (s.ok()) s.chk(hipMemcpy(d_creg.as<int32_t>() + nc, t.reg.data() + nc, nn * 4, hipMemcpyHostToDevice));
             FwdEmitArgs e{};
-            e.nt = n_t; e.m_max = item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc; e.first = (long long)lo;
-            e.row_off = d.off.as<long long>(); e.cell_off = d_coff.as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = d_crow.as<double>();
-            e.next = d_next.as<double>(); e.cell_map = d_cmap.as<double>(); e.item_region = d_ir.as<int32_t>(); e.item_cell = d_ic.as<int32_t>();
-            e.cell_item = d_ci.as<int32_t>(); e.kept = d_kept.as<unsigned long long>(); e.point = d_pt.as<double>();
-            e.cell_point = d_cpt.as<double>(); e.tol = tol;
+            e.nt = n_t; e.m_max = t.item_rows; e.n_cells = (long long)nn; e.first_cell = (long long)nc; e.first = (long long)t.lo;
+            e.row_off = d.off.as<long long>(); e.cell_off = t.d_off->as<long long>(); e.ef = d.ef.as<double>(); e.cell_ef = t.d_rows->as<double>();
+            e.next = d_next.as<double>(); e.cell_map = d_cmap.as<double>(); e.item_region = t.d_ir->as<int32_t>(); e.item_cell = t.d_ic->as<int32_t>();
+            e.cell_item = t.d_ci->as<int32_t>(); e.kept = t.d_kept->as<unsigned long long>(); e.point = t.d_ipt->as<double>();
+            e.cell_point = t.d_pt->as<double>(); e.tol = tol;
             family_launch(s, k_fwd_emit, (int64_t)nn, lds, e);
             if (s.ok()) s.chk(hipEventSynchronize(s.e1));
             s.elapsed(&t_emit);
@@ -2227,19 +2242,11 @@ extern "C" int mpc_forward_cells(int32_t device, int32_t n_t, int64_t n_regions,
         if (!nn) { code = MPC_FORWARD_EMPTY; break; }                         // a step without a cell: every trajectory has left
         ++step;
         if (cells_per_step) cells_per_step[step] = (int64_t)nn;
-        lo = hi;
-        hi += (int64_t)nn;
+        t.advance();
     }
-    if (!s.ok()) return s.finish();
-    const size_t nc = reg.size();
-    s.download(cell_rows, d_crow, (size_t)off.back() * w * 8);
-    s.download(cell_point, d_cpt, nc * n_t * 8);
-    s.download(cell_map, d_cmap, nc * map_doubles * 8);
-    unsigned long long cnt[6] = {0, 0, 0, 0, 0, 0};
-    s.download(cnt, d_cnt, sizeof cnt);
-    if (const int rc = s.finish()) return rc;
-    if (stats) for (int i = 0; i < 6; ++i) stats[i] = (int64_t)cnt[i];
+    s.download(cell_map, d_cmap, t.reg.size() * map_doubles * 8);
+    if (int rc = t.close(s, d_cnt, cell_rows, cell_point, 0, stats)) return rc;
     if (ms) *ms = total_ms;
-    deliver(code, step);
+    t.deliver(out, code, step);
     return MPC_OK;
 }

@@ -33,11 +33,10 @@ from typing import Optional
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, solution_rows
+from ._cells import check_cell_call, fill_stats, new_stats
+from .region_merge import mask_rows, solution_rows
 
 __all__ = ['InvariantSet', 'InvariantVolumes', 'invariant_set', 'backward_exit_cells']
-
-MAX_TABLE_DOUBLES = 1 << 26     # the default capacity of the cell table, in doubles (max_rows_total = this // (n_t + 1))
 
 
 @dataclass
@@ -212,65 +211,11 @@ def backward_exit_cells(row_off, ef_rows, Phi, phi, n_t: int, predecessors, cell
     0 included; ``void``: polytopes known to be empty: they precede nothing.  Every ValueError is raised before the library is touched."""
     from . import _lib
     t0 = time.perf_counter()
-    who = 'backward_exit_cells'
-    if not (1 <= n_t <= MAX_DIM):
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f'{who}: tol must be finite and >= 0')
-    if int(max_steps) < 0:
-        raise ValueError(f'{who}: max_steps must be >= 0')
-    if int(max_cells) < 1:
-        raise ValueError(f'{who}: max_cells must be >= 1')
-    if max_rows_total is None:
-        max_rows_total = MAX_TABLE_DOUBLES // (n_t + 1)
-    if int(max_rows_total) < 1:
-        raise ValueError(f'{who}: max_rows_total must be >= 1')
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
+    off, ef, Phi, phi, pred_off, pred_idx, coff, crow, csrc, max_rows_total = check_cell_call(
+        'backward_exit_cells', row_off, ef_rows, Phi, phi, n_t, 'predecessors', predecessors, cell_off, cell_rows, 'cell_source', 'one source',
+        cell_source, tol, max_steps, max_cells, max_rows_total, void)
     R = len(off) - 1
-    Phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64)
-    phi = numpy.ascontiguousarray(phi, dtype=numpy.float64)
-    if R < 1 or off[0] != 0 or off[-1] != len(ef) or Phi.shape != (R, n_t, n_t) or phi.shape != (R, n_t):
-        raise ValueError(f'{who}: row_off [R + 1], Phi [R, n_t, n_t] and phi [R, n_t] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'{who}: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(Phi)) and numpy.all(numpy.isfinite(phi))):
-        raise ValueError(f'{who}: rows and maps must be finite')
-    if len(predecessors) != R:
-        raise ValueError(f'{who}: predecessors needs one index list per polytope')
-    # the lists in one sweep (a solution has thousands of regions): ascending, once each, without the void polytopes
-    lens = numpy.asarray([len(p) for p in predecessors], dtype=numpy.int64)
-    flat = numpy.concatenate([numpy.asarray(p, dtype=numpy.int64).reshape(-1) for p in predecessors]) if lens.sum() else numpy.zeros(0, dtype=numpy.int64)
-    if len(flat) and (flat.min() < 0 or flat.max() >= R):
-        raise ValueError(f'{who}: predecessors must name polytopes 0..{R - 1}')
-    owner = numpy.repeat(numpy.arange(R), lens)
-    order = numpy.lexsort((flat, owner))
-    flat, owner = flat[order], owner[order]
-    keep = numpy.ones(len(flat), dtype=bool)
-    keep[1:] = (flat[1:] != flat[:-1]) | (owner[1:] != owner[:-1])
-    if len(void):
-        dead = numpy.zeros(R, dtype=bool)
-        dead[numpy.asarray(list(void), dtype=numpy.int64)] = True
-        keep &= ~dead[flat]
-    pred_idx = flat[keep].astype(numpy.int32)
-    pred_off = numpy.concatenate([[0], numpy.cumsum(numpy.bincount(owner[keep], minlength=R))]).astype(numpy.int64)
-    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
-    crow = numpy.ascontiguousarray(cell_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    csrc = numpy.ascontiguousarray(cell_source, dtype=numpy.int64).reshape(-1)
-    if len(coff) != len(csrc) + 1 or coff[0] != 0 or coff[-1] != len(crow):
-        raise ValueError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one source per cell')
-    if len(csrc):
-        c_counts = numpy.diff(coff)
-        if c_counts.min() < 1 or c_counts.max() > MAX_ROWS:
-            raise ValueError(f'{who}: every cell needs 1..{MAX_ROWS} rows')
-        if csrc.min() < 0 or csrc.max() >= R:
-            raise ValueError(f'{who}: cell_source must name polytopes 0..{R - 1}')
-        if not numpy.all(numpy.isfinite(crow)):
-            raise ValueError(f'{who}: cell rows must be finite')
-        if len(csrc) > int(max_cells) or len(crow) > int(max_rows_total):
-            raise ValueError(f'{who}: the cells of step 0 exceed max_cells = {int(max_cells)} or max_rows_total = {int(max_rows_total)}')
-    stats = {'items': 0, 'cells': 0, 'empty': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0, 'step_ms': [], 'cells_per_step': [len(csrc)]}
+    stats = new_stats(len(csrc))
     if len(csrc) == 0 or int(max_steps) == 0:
         stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
         done = len(csrc) == 0
@@ -284,13 +229,7 @@ def backward_exit_cells(row_off, ef_rows, Phi, phi, n_t: int, predecessors, cell
     t1 = time.perf_counter()
     r = _lib.backward_exits(off, ef, Phi, phi, xs, pred_off, pred_idx, coff, crow, csrc, tol, int(max_steps), int(max_cells), int(max_rows_total),
                             device)
-    for k in ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'):
-        stats[k] = r['stats'][k]
-    stats['device_ms'] += r['stats']['ms']
-    stats['call_ms'] = (time.perf_counter() - t1) * 1e3
-    stats['step_ms'] = [float(v) for v in r['step_ms'][:min(r['steps'] + 1, int(max_steps))]]
-    stats['cells_per_step'] = [int(v) for v in r['cells_per_step']]
-    stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
+    fill_stats(stats, r, max_steps, t1, t0)
     return InvariantSet(n_regions=R, cell_off=r['cell_off'], cell_rows=r['cell_rows'], source=r['source'], step=r['step'], parent=r['parent'],
                         wide=r['wide'], converged=r['converged'], steps=r['steps'], stats=stats, region_off=off, region_rows=ef, tol=float(tol),
                         status=_lib.BACKWARD_STATUS[r['status']], point=r['point'])

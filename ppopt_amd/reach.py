@@ -42,8 +42,9 @@ from typing import Optional
 
 import numpy
 
-from .invariant_set import MAX_TABLE_DOUBLES, _inside
-from .region_merge import MAX_DIM, MAX_ROWS, solution_rows
+from ._cells import check_cell_call, fill_stats, new_stats
+from .invariant_set import _inside
+from .region_merge import MAX_ROWS, solution_rows
 
 __all__ = ['ForwardCells', 'ForwardVolumes', 'forward_cells', 'reach_cells']
 
@@ -261,59 +262,16 @@ def forward_cells(row_off, ef_rows, Phi, phi, n_t: int, successors, cell_off, ce
     is touched."""
     t0 = time.perf_counter()
     who = 'forward_cells'
-    if not (isinstance(n_t, (int, numpy.integer)) and 1 <= n_t <= MAX_DIM):
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f'{who}: tol must be finite and >= 0')
-    if int(max_steps) < 0:
-        raise ValueError(f'{who}: max_steps must be >= 0')
-    if int(max_cells) < 1:
-        raise ValueError(f'{who}: max_cells must be >= 1')
-    if max_rows_total is None:
-        max_rows_total = MAX_TABLE_DOUBLES // (n_t + 1)
-    if int(max_rows_total) < 1:
-        raise ValueError(f'{who}: max_rows_total must be >= 1')
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    R = len(off) - 1
-    Phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64)
-    phi = numpy.ascontiguousarray(phi, dtype=numpy.float64)
-    if R < 1 or off[0] != 0 or off[-1] != len(ef) or Phi.shape != (R, n_t, n_t) or phi.shape != (R, n_t):
-        raise ValueError(f'{who}: row_off [R + 1], Phi [R, n_t, n_t] and phi [R, n_t] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'{who}: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(Phi)) and numpy.all(numpy.isfinite(phi))):
-        raise ValueError(f'{who}: rows and maps must be finite')
-    if len(successors) != R:
-        raise ValueError(f'{who}: successors needs one index list per polytope')
-    lists = [numpy.unique(numpy.asarray(s, dtype=numpy.int64).reshape(-1)) for s in successors]       # ascending, once each
-    succ_idx = numpy.concatenate(lists) if R else numpy.zeros(0, dtype=numpy.int64)
-    if len(succ_idx) and (succ_idx.min() < 0 or succ_idx.max() >= R):
-        raise ValueError(f'{who}: successors must name polytopes 0..{R - 1}')
-    succ_off = numpy.concatenate([[0], numpy.cumsum([len(s) for s in lists])]).astype(numpy.int64)
-    coff = numpy.ascontiguousarray(cell_off, dtype=numpy.int64).reshape(-1)
-    crow = numpy.ascontiguousarray(cell_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    creg = numpy.ascontiguousarray(cell_region, dtype=numpy.int64).reshape(-1)
-    if len(coff) != len(creg) + 1 or coff[0] != 0 or coff[-1] != len(crow):
-        raise ValueError(f'{who}: cell_off [cells + 1] must run from 0 to the number of rows of cell_rows, with one region per cell')
-    n0 = len(creg)
+    off, ef, Phi, phi, succ_off, succ_idx, coff, crow, creg, max_rows_total = check_cell_call(
+        who, row_off, ef_rows, Phi, phi, n_t, 'successors', successors, cell_off, cell_rows, 'cell_region', 'one region', cell_region, tol, max_steps,
+        max_cells, max_rows_total)
+    R, n0 = len(off) - 1, len(creg)
     cpt = None
-    if n0:
-        c_counts = numpy.diff(coff)
-        if c_counts.min() < 1 or c_counts.max() > MAX_ROWS:
-            raise ValueError(f'{who}: every cell needs 1..{MAX_ROWS} rows')
-        if creg.min() < 0 or creg.max() >= R:
-            raise ValueError(f'{who}: cell_region must name polytopes 0..{R - 1}')
-        if not numpy.all(numpy.isfinite(crow)):
-            raise ValueError(f'{who}: cell rows must be finite')
-        if n0 > int(max_cells) or len(crow) > int(max_rows_total):
-            raise ValueError(f'{who}: the cells of step 0 exceed max_cells = {int(max_cells)} or max_rows_total = {int(max_rows_total)}')
     if cell_point is not None:
         cpt = numpy.ascontiguousarray(cell_point, dtype=numpy.float64)
         if cpt.shape != (n0, n_t) or not numpy.all(numpy.isfinite(cpt)):
             raise ValueError(f'{who}: cell_point must be a finite [{n0}, {n_t}] array')
-    stats = {'items': 0, 'cells': 0, 'empty': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0, 'step_ms': [], 'cells_per_step': [n0]}
+    stats = new_stats(n0)
     if n0 == 0 or int(max_steps) == 0:
         stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
         return ForwardCells(n_regions=R, cell_off=coff, cell_rows=crow, region=creg, step=numpy.zeros(n0, dtype=numpy.int64),
@@ -328,13 +286,7 @@ def forward_cells(row_off, ef_rows, Phi, phi, n_t: int, successors, cell_off, ce
     t1 = time.perf_counter()
     r = _lib.forward_cells(off, ef, Phi, phi, succ_off, succ_idx, coff, crow, creg, cpt, tol, int(max_steps), int(max_cells), int(max_rows_total),
                            device)
-    for k in ('items', 'cells', 'empty', 'lps', 'pivots', 'wide'):
-        stats[k] = r['stats'][k]
-    stats['device_ms'] += r['stats']['ms']
-    stats['call_ms'] = (time.perf_counter() - t1) * 1e3
-    stats['step_ms'] = [float(v) for v in r['step_ms'][:min(r['steps'] + 1, int(max_steps))]]
-    stats['cells_per_step'] = [int(v) for v in r['cells_per_step']]
-    stats['wall_ms'] = (time.perf_counter() - t0) * 1e3
+    fill_stats(stats, r, max_steps, t1, t0)
     return ForwardCells(n_regions=R, cell_off=r['cell_off'], cell_rows=r['cell_rows'], region=r['region'], step=r['step'], parent=r['parent'],
                         G=r['G'], g=r['g'], wide=r['wide'], point=r['point'], status=_lib.FORWARD_STATUS[r['status']], steps=r['steps'],
                         stats=stats, region_off=off, region_rows=ef, tol=float(tol))

@@ -361,6 +361,15 @@ def test_limits_of_steps_and_cells():
     assert len(none) == 0 and none.converged and none.steps == 0 and none.status == 'CONVERGED'
     with pytest.raises(ValueError, match='step 0'):
         _run(polys, Phi, phi, pred, cells0, max_cells=3)
+    # a chain that ends exactly at max_steps has converged: the items are listed before max_steps is tested.  R0 + (2, 0) lies inside R1, the
+    # only cell of step 0, so step 1 is R0 whole (1 radius run + 8 rows = 9 LPs), and nothing precedes R0
+    R0, R1 = xc.box_rows([0.0, 0.0], [1.0, 1.0]), xc.box_rows([1.5, -0.5], [3.5, 1.5])
+    chain = ([R0, R1], numpy.tile(numpy.eye(2), (2, 1, 1)), numpy.array([[2.0, 0.0], [10.0, 0.0]]), [[], [0]], [(1, R1)])
+    got = _run(*chain, max_steps=1)
+    assert got.status == 'CONVERGED' and got.converged and got.steps == 1 and got.source.tolist() == [1, 0]
+    assert got.rows_of(1).tobytes() == R0.tobytes() and got.stats['lps'] == 9
+    got = _run(*chain, max_steps=0)
+    assert got.status == 'MAX_STEPS' and not got.converged and len(got) == 1
 
 
 def test_two_runs_give_identical_bits():
