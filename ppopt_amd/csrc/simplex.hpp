@@ -5,6 +5,10 @@
 // way), with the columns of the inverse basis d_k in LDS (B d_k = e_k).  Slot k's rate mu_k = c.d_k; a pseudo slot enters when
 // |mu_k| / |d_k| > 1e-11, a real slot when mu_k / |d_k| > 1e-11 (the largest normalised rate first, pseudo slots before real ones).
 // Ratio test over the rows outside the set (lanes over rows, slacks clamped at 0), ties to the lowest row; no blocking row: unbounded.
+// A row blocks when its rate along the direction p = -+d_k exceeds 1e-12 max(1, |p|), not 1e-12 alone: next to a nearly parallel row in
+// the set |d_k| reaches 1e5, and the rate of an exact copy of a working row (the rows of a merged region and of its member stacked, as
+// Solution.compare does) is then rounding noise of 1e-11 instead of 0; taken as a blocking row at step 0 it was a pivot of 1e-12 that
+// left the inverse basis without meaning (a radius of -1.7e-12 for 0.034, and one of 0.045 at an infeasible point for -0.37).
 // A run that reaches TR_PIVOT_CAP pivots reports "unbounded" as well: a wider bound than the true one never costs exactness.
 // Column n_t of a row is the coefficient of the extra coordinate of a (theta, t) run (d = n_t + 1): tr_load sets it to -1 for phase 1,
 // other loaders set their own.  ``stop_t`` ends a run of dimension n_t + 1 as soon as x_{n_t} exceeds it (TR_REACHED).
@@ -87,10 +91,10 @@ __device__ inline int tr_simplex(const TrLds &S, int m, int nt, int d, bool phas
     for (int it = 0; it < TR_PIVOT_CAP; ++it) {
         if (d > nt && S.x[nt] > stop_t) return TR_REACHED;   // S.x is settled: every iteration ends with a barrier
         // 1. entering slot
-        double key = -1.0, sgn = 1.0;
+        double key = -1.0, sgn = 1.0, dd = 0.0;
         int slot = -1;
         if (lane < d) {
-            double mu = 0.0, dd = 0.0;
+            double mu = 0.0;
             for (int i = 0; i < d; ++i) { const double v = S.D[lane * TR_D + i]; mu = fma(S.c[i], v, mu); dd = fma(v, v, dd); }
             const double rate = dd > 0.0 ? mu / sqrt(dd) : 0.0;
             if (S.W[lane] < 0) { if (fabs(rate) > TR_RATE_EPS) { key = 4.0 + fabs(rate); slot = lane; sgn = rate > 0.0 ? 1.0 : -1.0; } }
@@ -104,6 +108,7 @@ __device__ inline int tr_simplex(const TrLds &S, int m, int nt, int d, bool phas
         }
         if (slot < 0) return TR_OPTIMAL;
         sgn = __shfl(sgn, slot);
+        const double g_min = TR_RATE_G * fmax(1.0, sqrt(__shfl(dd, slot)));   // relative to |p| = |d_slot| (the header comment)
         // 2. direction p = -sgn d_slot
         if (lane < d) S.p[lane] = -sgn * S.D[slot * TR_D + lane];
         __syncthreads();
@@ -114,7 +119,7 @@ __device__ inline int tr_simplex(const TrLds &S, int m, int nt, int d, bool phas
             if (S.flag[r]) continue;
             double g = 0.0, ax = 0.0;
             for (int i = 0; i < d; ++i) { const double a = S.A[r * stride + i]; g = fma(a, S.p[i], g); ax = fma(a, S.x[i], ax); }
-            if (g > TR_RATE_G) {
+            if (g > g_min) {
                 const double t = fmax(S.b[r] - ax, 0.0) / g;
                 if (t < tbest || (t == tbest && r < rbest)) { tbest = t; rbest = r; }
             }

@@ -5,6 +5,7 @@ order, and no package code except build_merged_solution, which only assembles th
 
 info['knife'] counts the pairs tested whose outcome hangs on an LP value within KNIFE of its threshold (a row's max minus its offset
 against tol max(1, |o|), or t* against tol): there a device result may differ by rounding, and the tests exempt such cases.
+info['tested'] lists every candidate pair in the order tested: (rows of P, rows of Q, valid rows of P, valid rows of Q, convex).
 """
 import numpy
 from scipy.optimize import linprog
@@ -119,7 +120,7 @@ def merge_reference(solution, outputs=None, tol=1e-8, law_tol=1e-8):
     key = list(range(R))
     alive = set(range(R))
     knife = [0]
-    info = {'rounds': 0, 'pairs': 0, 'too_many_rows': 0}
+    info = {'rounds': 0, 'pairs': 0, 'too_many_rows': 0, 'tested': []}
     while fresh:
         for i in fresh:
             boxes[i] = _box(rows[i], n_t)
@@ -137,6 +138,7 @@ def merge_reference(solution, outputs=None, tol=1e-8, law_tol=1e-8):
         taken, fresh = set(), []
         for p, q in sorted(cand, key=lambda pq: (key[pq[0]], key[pq[1]])):
             ok, va, vb = _pair_test(rows[p], rows[q], n_t, tol, knife)   # every candidate is tested, as on the device
+            info['tested'].append((rows[p], rows[q], va, vb, ok))
             if not ok or p in taken or q in taken:
                 continue
             u = _dedupe(numpy.vstack([rows[p][va], rows[q][vb]]), tol)

@@ -9,6 +9,7 @@ import numpy
 import pytest
 from scipy.optimize import linprog
 
+import merge_exact_reference as exact
 import region_merge_reference as ref
 from ppopt_amd import _lib
 from ppopt_amd.critical_region import CriticalRegion
@@ -241,7 +242,7 @@ def _member_rows(src, i):
     return numpy.asarray(r.E, float), numpy.asarray(r.f, float).reshape(-1)
 
 
-@pytest.mark.parametrize('name', ['c3_l4'])
+@pytest.mark.parametrize('name', ['c3_l4', 'c3_graph'])
 def test_members_and_merged_regions_contain_each_other(name):
     src = _solve(name)
     merged = _merged(name)
@@ -264,6 +265,38 @@ def test_members_and_merged_regions_contain_each_other(name):
             Q = hit_and_run_batch(Polytope(E, f), chains=8, samples=2, seed=5).reshape(-1, E.shape[1])
             Q = numpy.vstack([Q, centres[i]])
             assert numpy.all(Q @ r.E.T - r.f.reshape(-1) <= TOL * numpy.maximum(1.0, numpy.abs(r.f.reshape(-1)))), (name, i)
+
+
+def test_merged_regions_of_the_complete_c3_are_exact_unions():
+    """Every merged region of the complete c3 with more than one member against the union of its members by the difference recursion
+    (tests/merge_exact_reference.py): no piece fatter than 10 tol outside the members, none of a member outside the region; and
+    Solution.compare(merged, source) finds every such member inside its region, with HiGHS's radius.
+    The bound is the 10 tol of the generated cases.  By the rule one merge leaves at most a sliver of radius tol max(1, |o|) / 2 (a
+    valid row lets the partner stick out that far) plus t* <= tol, 4.75e-8 with |o| <= 7.51 on c3; measured: nothing outside, and at
+    most 1.82e-8 of a member missing (regions of up to 4 members), a factor 5 under the bound."""
+    src = _solve('c3_graph')
+    merged = _merged('c3_graph')
+    multi = [k for k, r in enumerate(merged.critical_regions) if len(r.members) > 1]
+    assert len(multi) > 200
+    worst = (0.0, 0.0)
+    for k in multi:
+        r = merged.critical_regions[k]
+        out, miss = exact.union_defect((r.E, r.f), [_member_rows(src, i) for i in r.members], TOL)
+        worst = (max(worst[0], out), max(worst[1], miss))
+        assert out <= 10 * TOL and miss <= 10 * TOL, (k, r.members, out, miss)
+    print('largest outside, missing:', worst)
+    g = merged.compare(src, outputs=OUTPUTS['c3_graph'])
+    assert g.wide == 0
+    own = numpy.flatnonzero(numpy.isin(g.i, multi))
+    found = {(int(g.i[n]), int(g.j[n])): int(n) for n in own}
+    for k in multi:
+        r = merged.critical_regions[k]
+        for i in r.members:
+            E, f = _member_rows(src, i)
+            want = exact.chebyshev_radius(numpy.vstack([r.E, E]), numpy.concatenate([r.f.reshape(-1), f]))
+            if want > 2 * TOL:
+                n = found[(k, i)]
+                assert g.meets[n] and abs(g.radius[n] - want) <= 1e-9 * (1.0 + want), (k, i, g.radius[n], want)
 
 
 def test_areas_maximality_and_rows():
