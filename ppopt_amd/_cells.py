@@ -1,11 +1,11 @@
 """The host side that invariant_set.backward_exit_cells and reach.forward_cells share: both hand polytopes with
 maps, an adjacency and the cells of step 0 to one library call that runs every step.  Here: the argument checks, the adjacency as a
-CSR, and the stats.  Host only; nothing here touches the library."""
+CSR, and the stats; the checks of the polytopes and their maps come from _pairs.py.  Host only; nothing here touches the library."""
 import time
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS
+from ._pairs import MAX_ROWS, check_polytopes, check_scalars, map_entries
 
 MAX_TABLE_DOUBLES = 1 << 26     # the default capacity of the cell table, in doubles (max_rows_total = this // (n_t + 1))
 
@@ -34,10 +34,7 @@ def check_cell_call(who, row_off, ef_rows, Phi, phi, n_t, adj_name, adjacency, c
     """Every ValueError of the two calls but the forward one's cell_point, in their one order.  ``adj_name`` ('predecessors'), ``reg_name``
     ('cell_source') and ``per_cell`` ('one source') are the caller's words in the refusals.  The arrays the library call takes:
     (off, ef, Phi, phi, adj_off, adj_idx, cell_off, cell_rows, cell_reg, max_rows_total), max_rows_total with its default filled in."""
-    if not (isinstance(n_t, (int, numpy.integer)) and 1 <= n_t <= MAX_DIM):
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f'{who}: tol must be finite and >= 0')
+    check_scalars(who, n_t, tol)
     if int(max_steps) < 0:
         raise ValueError(f'{who}: max_steps must be >= 0')
     if int(max_cells) < 1:
@@ -46,18 +43,8 @@ def check_cell_call(who, row_off, ef_rows, Phi, phi, n_t, adj_name, adjacency, c
         max_rows_total = MAX_TABLE_DOUBLES // (n_t + 1)
     if int(max_rows_total) < 1:
         raise ValueError(f'{who}: max_rows_total must be >= 1')
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    R = len(off) - 1
-    Phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64)
-    phi = numpy.ascontiguousarray(phi, dtype=numpy.float64)
-    if R < 1 or off[0] != 0 or off[-1] != len(ef) or Phi.shape != (R, n_t, n_t) or phi.shape != (R, n_t):
-        raise ValueError(f'{who}: row_off [R + 1], Phi [R, n_t, n_t] and phi [R, n_t] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'{who}: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(Phi)) and numpy.all(numpy.isfinite(phi))):
-        raise ValueError(f'{who}: rows and maps must be finite')
+    Phi, phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64), numpy.ascontiguousarray(phi, dtype=numpy.float64)
+    off, ef, _, R = check_polytopes(who, row_off, ef_rows, n_t, extra=map_entries(Phi, phi, n_t), word='maps')
     if len(adjacency) != R:
         raise ValueError(f'{who}: {adj_name} needs one index list per polytope')
     adj_off, adj_idx = adjacency_csr(who, adj_name, adjacency, R, void)

@@ -14,8 +14,8 @@ same K output rows.  For a region i of A and a region j of B:
            unbounded or capped law LP gives lo = -inf or hi = +inf, hence gap +inf.
 
 Stages: unit rows of both solutions in ONE region table (A's regions, then B's); feasible points and boxes (_lib.merge_regions);
-candidate pairs whose boxes overlap by more than tol in every coordinate (cross_box_pairs, a host sweep, or with sweep='device'
-geometry.box_pairs); with screen='rows' the candidates that one row of either region separates from the other's box are dropped
+candidate pairs by _pairs.candidate_pairs: boxes that overlap by more than tol in every coordinate (cross_box_pairs, a host sweep, or with
+sweep='device' geometry.box_pairs); with screen='rows' the candidates that one row of either region separates from the other's box are dropped
 (geometry.screen_pairs); per remaining candidate the radius LP and up to 2 K law LPs on the device (csrc/compare.hpp,
 k_law_gap, one wavefront per pair).
 
@@ -28,7 +28,9 @@ from typing import Optional
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS, solution_rows
+from ._pairs import (MAX_ROWS, candidate_pairs, check_pair_indices, check_polytopes, check_region_limits, check_rows_finite, check_scalars,
+                     feasible_points, host_pairs)
+from .region_merge import solution_rows
 
 __all__ = ['LawGap', 'compare_solutions', 'law_gap_pairs', 'cross_box_pairs', 'output_rows', 'MAX_OUTPUTS']
 
@@ -39,37 +41,7 @@ def cross_box_pairs(box_a: numpy.ndarray, usable_a: numpy.ndarray, box_b: numpy.
     """(i, j), ascending by (i, j), with i a usable box of box_a [Ra, 2, n_t] (lower, upper) and j a usable box of box_b [Rb, 2, n_t] that
     overlap by more than tol in every coordinate.  One sweep along the first coordinate over both kinds of boxes together; infinite
     bounds are fine, and a NaN bound leaves its coordinate open."""
-    ia, ib = numpy.flatnonzero(usable_a), numpy.flatnonzero(usable_b)
-    none = numpy.zeros(0, dtype=numpy.int64)
-    if not len(ia) or not len(ib):
-        return none, none
-    lo = numpy.concatenate([box_a[ia, 0], box_b[ib, 0]])
-    hi = numpy.concatenate([box_a[ia, 1], box_b[ib, 1]])
-    lo, hi = numpy.where(numpy.isnan(lo), -numpy.inf, lo), numpy.where(numpy.isnan(hi), numpy.inf, hi)
-    who = numpy.concatenate([ia, ib])
-    is_a = numpy.arange(len(who)) < len(ia)
-    order = numpy.argsort(lo[:, 0], kind='stable')
-    lo, hi, who, is_a = lo[order], hi[order], who[order], is_a[order]
-    end = numpy.searchsorted(lo[:, 0], hi[:, 0] - tol, side='left')    # lo_l < hi_k - tol for l in (k, end[k])
-    pa, pb = [], []
-    with numpy.errstate(invalid='ignore'):
-        for k in range(len(who) - 1):
-            e = int(end[k])
-            if e <= k + 1:
-                continue
-            other = numpy.flatnonzero(is_a[k + 1:e] != is_a[k]) + k + 1
-            if not len(other):
-                continue
-            hit = numpy.all(numpy.minimum(hi[k], hi[other]) - numpy.maximum(lo[k], lo[other]) > tol, axis=1)
-            other = who[other[hit]]
-            mine = numpy.full(len(other), who[k])
-            pa.append(mine if is_a[k] else other)
-            pb.append(other if is_a[k] else mine)
-    if not pa:
-        return none, none
-    pa, pb = numpy.concatenate(pa), numpy.concatenate(pb)
-    o = numpy.lexsort((pb, pa))
-    return pa[o].astype(numpy.int64), pb[o].astype(numpy.int64)
+    return host_pairs('bound', box_a, usable_a, box_b, usable_b, tol)
 
 
 def law_gap_pairs(row_off, ef_rows, laws, pair_a, pair_b, tol: float = 1e-8, xs=None, ranges: bool = False, device: int = 0) -> dict:
@@ -83,29 +55,15 @@ def law_gap_pairs(row_off, ef_rows, laws, pair_a, pair_b, tol: float = 1e-8, xs=
     not finite or below 0 and pair indices out of range."""
     from . import _lib
     who = 'law_gap_pairs'
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.asarray(ef_rows, dtype=numpy.float64)
+    off, ef, n_t, R = check_polytopes(who, row_off, ef_rows, max_rows=None)
     laws = numpy.asarray(laws, dtype=numpy.float64)
-    if ef.ndim != 2 or ef.shape[1] < 2 or len(off) < 2 or off[0] != 0 or off[-1] != len(ef):
-        raise ValueError(f'{who}: row_off [R + 1] must run from 0 to the number of rows of ef_rows [rows, n_t + 1] and describe R >= 1 polytopes')
-    n_t, R = ef.shape[1] - 1, len(off) - 1
-    if n_t > MAX_DIM:
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
     if laws.ndim != 3 or laws.shape[0] != R or laws.shape[2] != n_t + 1:
         raise ValueError(f'{who}: laws must be [{R}, K, {n_t + 1}] = [b | A], not {list(laws.shape)}')
     if not 1 <= laws.shape[1] <= MAX_OUTPUTS:
         raise ValueError(f'{who}: the number of output rows K = {laws.shape[1]} is outside 1..{MAX_OUTPUTS}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f'{who}: tol must be finite and >= 0')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'{who}: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(laws))):
-        raise ValueError(f'{who}: rows and laws must be finite')
-    pa = numpy.asarray(pair_a, dtype=numpy.int64).reshape(-1)
-    pb = numpy.asarray(pair_b, dtype=numpy.int64).reshape(-1)
-    if pa.shape != pb.shape or (len(pa) and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= R)):
-        raise ValueError(f'{who}: pair_a and pair_b must be two index arrays of one length into the polytopes')
+    check_scalars(who, n_t, tol)
+    check_rows_finite(who, off, [ef, laws], word='laws')
+    pa, pb = check_pair_indices(who, 'pair_a and pair_b', pair_a, pair_b, R)
     if xs is not None:
         xs = numpy.ascontiguousarray(xs, dtype=numpy.float64)
         if xs.shape != (R, n_t) or not numpy.all(numpy.isfinite(xs)):
@@ -265,14 +223,11 @@ def check_sources(a, b, outputs, tol: float):
     n_t, n_tb = _n_theta(a), _n_theta(b)
     if n_t != n_tb:
         raise ValueError(f'{who}: the solutions have different n_theta ({n_t} and {n_tb})')
-    if n_t > MAX_DIM:
-        raise ValueError(f'{who}: n_theta = {n_t} > {MAX_DIM}')
+    check_region_limits(who, (), n_t)
     if not (numpy.isfinite(tol) and tol >= 0.0):
         raise ValueError(f'{who}: tol must be finite and >= 0')
-    for name, s in (('this', a), ('the other', b)):
-        for i, r in enumerate(s.critical_regions):
-            if numpy.asarray(r.E).reshape(-1, n_t).shape[0] > MAX_ROWS:
-                raise ValueError(f'{who}: region {i} of {name} solution has more than {MAX_ROWS} rows')
+    check_region_limits(who, a.critical_regions, n_t, 'of this solution')
+    check_region_limits(who, b.critical_regions, n_t, 'of the other solution')
     rows_a, rows_b = output_rows(a, outputs, who), output_rows(b, outputs, who)
     if len(rows_a) != len(rows_b):
         raise ValueError(f'{who}: the solutions keep {len(rows_a)} and {len(rows_b)} rows of x: name the rows to compare with outputs')
@@ -318,9 +273,8 @@ def compare_solutions(a, b, outputs=None, tol: float = 1e-8, ranges: bool = Fals
     same bit for bit.  ``screen`` = 'rows': candidates that a single row separates from the partner's box never reach the LPs; the
     per-pair arrays then hold the kept candidates only (every meeting pair is among them), and stats gains box_candidates, screened
     and screen_ms.  ValueError for any other value."""
-    from . import _lib
-    from .geometry.box_pairs import box_pairs, screen_pairs, sweep_options
-    on_device, rows_screen = sweep_options('compare', sweep, screen)
+    from .geometry.box_pairs import sweep_options
+    sweep_options('compare', sweep, screen)
     t0 = time.perf_counter()
     n_t, rows_a, rows_b = check_sources(a, b, outputs, tol)
     off_a, ef_a, void_a = solution_rows(a.critical_regions, n_t, 'compare')
@@ -331,31 +285,14 @@ def compare_solutions(a, b, outputs=None, tol: float = 1e-8, ranges: bool = Fals
     laws = numpy.concatenate([_laws(a, rows_a, n_t), _laws(b, rows_b, n_t)])
     if not numpy.all(numpy.isfinite(laws)):
         raise ValueError('compare: the laws must be finite')
-    xs, box, status, s = _lib.merge_regions(off, ef, device)
-    usable = status == 0
-    usable[list(void_a)] = False
-    usable[[n_a + i for i in void_b]] = False
-    xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
-    t1 = time.perf_counter()
-    sweep_stats = {}
-    if on_device:
-        pa, pb, sw = box_pairs(box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], margin=tol, device=device)
-        sweep_stats = {'sweep_kernel_ms': sw['ms']}
-    else:
-        pa, pb = cross_box_pairs(box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], tol)
-    sweep_ms = (time.perf_counter() - t1) * 1e3
-    if rows_screen:
-        t1 = time.perf_counter()
-        keep, sc = screen_pairs(off, ef, pa, pb + n_a, box, box, sides='both', device=device)
-        sweep_stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
-        pa, pb = pa[keep], pb[keep]
-        sweep_stats['screen_ms'] = (time.perf_counter() - t1) * 1e3
+    xs, box, usable, s = feasible_points(off, ef, list(void_a) + [n_a + i for i in void_b], device)
+    pa, pb, swept = candidate_pairs('compare', 'bound', box[:n_a], usable[:n_a], box[n_a:], usable[n_a:], tol, off, ef, lambda: (box, box), 'both',
+                                    sweep, screen, device, shift=n_a)
     res = law_gap_pairs(off, ef, laws, pa, pb + n_a, tol=tol, xs=xs, ranges=ranges, device=device)
     res['i'], res['j'] = pa, pb
     stats = dict(res['stats'])
     stats['device_ms'] += s['ms']
-    stats.update(candidates=len(pa), box_pairs=int(usable[:n_a].sum()) * int(usable[n_a:].sum()), sweep_ms=sweep_ms)
-    stats.update(sweep_stats)
+    stats.update(candidates=len(pa), box_pairs=int(usable[:n_a].sum()) * int(usable[n_a:].sum()), **swept)
     covered_a = covered_b = None
     if coverage:
         covered_a, covered_b = _coverage(off, ef, n_t, n_a, res, tol, device)

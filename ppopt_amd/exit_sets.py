@@ -32,7 +32,8 @@ from typing import List, Optional
 import numpy
 
 from .overlap import difference_rounds
-from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, solution_rows
+from ._pairs import check_polytopes, check_scalars, feasible_points, map_entries
+from .region_merge import mask_rows, solution_rows
 
 __all__ = ['ExitSets', 'ExitVolumes', 'exit_sets', 'exit_pieces', 'pulled_back_rows', 'ROW_EPS']
 
@@ -162,24 +163,11 @@ def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1
     ``reduce``)."""
     from . import _lib
     t0 = time.perf_counter()
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    R = len(off) - 1
-    if not (1 <= n_t <= MAX_DIM):
-        raise ValueError(f'exit_pieces: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError('exit_pieces: tol must be finite and >= 0')
+    check_scalars('exit_pieces', n_t, tol)
     if int(max_pieces) < 1:
         raise ValueError('exit_pieces: max_pieces must be >= 1')
-    Phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64)
-    phi = numpy.ascontiguousarray(phi, dtype=numpy.float64)
-    if R < 1 or off[0] != 0 or off[-1] != len(ef) or Phi.shape != (R, n_t, n_t) or phi.shape != (R, n_t):
-        raise ValueError('exit_pieces: row_off [R + 1], Phi [R, n_t, n_t] and phi [R, n_t] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'exit_pieces: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(Phi)) and numpy.all(numpy.isfinite(phi))):
-        raise ValueError('exit_pieces: rows and maps must be finite')
+    Phi, phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64), numpy.ascontiguousarray(phi, dtype=numpy.float64)
+    off, ef, _, R = check_polytopes('exit_pieces', row_off, ef_rows, n_t, extra=map_entries(Phi, phi, n_t), word='maps')
     if len(successors) != R:
         raise ValueError('exit_pieces: successors needs one index list per polytope')
     cutters = []
@@ -189,11 +177,8 @@ def exit_pieces(row_off, ef_rows, Phi, phi, n_t: int, successors, tol: float = 1
             raise ValueError(f'exit_pieces: successors must name polytopes 0..{R - 1}')
         cutters.append(s.tolist())
     stats = {'rounds': 0, 'items': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0, 'round_ms': [], 'max_item_rows': 0}
-    xs, _, status, s = _lib.merge_regions(off, ef, device)
+    xs, _, usable, s = feasible_points(off, ef, void, device)
     stats['device_ms'] += s['ms']
-    usable = status == 0
-    usable[list(void)] = False
-    xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
 
     # 2. the rounds of the difference (overlap.difference_rounds) against pulled-back cutters
     def launch(poff, prows, item_source, entries, start):

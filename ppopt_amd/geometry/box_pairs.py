@@ -20,9 +20,10 @@ from typing import Optional
 
 import numpy
 
+from .._pairs import MAX_DIM, check_pair_indices, check_polytopes
+
 __all__ = ['box_pairs', 'screen_pairs', 'sweep_options', 'SIDES', 'MAX_DIM']
 
-MAX_DIM = 16
 SIDES = {'a': 1, 'b': 2, 'both': 3}     # whose rows are screened (MPC_SCREEN_ROWS_A, MPC_SCREEN_ROWS_B)
 
 
@@ -105,17 +106,8 @@ def screen_pairs(row_off, ef_rows, pair_a, pair_b, box_for_a_rows=None, box_for_
     who = 'screen_pairs'
     if sides not in SIDES:
         raise ValueError(f"{who}: sides must be 'a', 'b' or 'both', not {sides!r}")
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64)
-    if ef.ndim != 2 or ef.shape[1] < 2 or len(off) < 2 or off[0] != 0 or off[-1] != len(ef):
-        raise ValueError(f'{who}: row_off [R + 1] must run from 0 to the number of rows of ef_rows [rows, n_t + 1] and describe R >= 1 polytopes')
-    n_t, R = ef.shape[1] - 1, len(off) - 1
-    if n_t > MAX_DIM:
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    pa = numpy.ascontiguousarray(pair_a, dtype=numpy.int64).reshape(-1)
-    pb = numpy.ascontiguousarray(pair_b, dtype=numpy.int64).reshape(-1)
-    if pa.shape != pb.shape or (len(pa) and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= R)):
-        raise ValueError(f'{who}: pair_a and pair_b must be two index arrays of one length into the polytopes')
+    off, ef, n_t, R = check_polytopes(who, row_off, ef_rows, max_rows=None)
+    pa, pb = check_pair_indices(who, 'pair_a and pair_b', pair_a, pair_b, R)
     boxes = []
     for name, box, bit in (('box_for_a_rows', box_for_a_rows, 1), ('box_for_b_rows', box_for_b_rows, 2)):
         if not SIDES[sides] & bit:

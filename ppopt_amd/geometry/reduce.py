@@ -21,12 +21,12 @@ from typing import Sequence, Union
 
 import numpy
 
+from .._pairs import MAX_DIM, check_region_limits, check_rows_finite, check_scalars
 from .polytope import Polytope
 
 __all__ = ['ReducedRows', 'reduce_rows_of', 'reduce_polytopes', 'MAX_ROWS', 'MAX_DIM', 'OK', 'THIN']
 
 MAX_ROWS = 512    # RD_MAX_ROWS of csrc/reduce.hpp
-MAX_DIM = 16
 OK, THIN = 0, 1   # status of a polytope (MPC_REDUCE_OK, MPC_REDUCE_THIN)
 
 
@@ -56,10 +56,7 @@ class ReducedRows:
 
 def check_rows(who: str, row_off, ef_rows, n_t: int, tol: float, start=None):
     """(off int64, ef float64 [rows, n_t + 1], start or None) of a call the device accepts; ValueError in the name of ``who`` otherwise."""
-    if not (isinstance(n_t, (int, numpy.integer)) and 1 <= n_t <= MAX_DIM):
-        raise ValueError(f'{who}: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError(f'{who}: tol must be finite and >= 0')
+    check_scalars(who, n_t, tol)
     off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
     ef = numpy.asarray(ef_rows, dtype=numpy.float64)
     if ef.ndim != 2 or ef.shape[1] != n_t + 1:
@@ -67,11 +64,7 @@ def check_rows(who: str, row_off, ef_rows, n_t: int, tol: float, start=None):
     ef = numpy.ascontiguousarray(ef)
     if len(off) < 2 or off[0] != 0 or off[-1] != len(ef):
         raise ValueError(f'{who}: row_off [n + 1] must run from 0 to the number of rows and describe n >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'{who}: every polytope needs 1..{MAX_ROWS} rows')
-    if not numpy.all(numpy.isfinite(ef)):
-        raise ValueError(f'{who}: rows must be finite')
+    check_rows_finite(who, off, [ef], MAX_ROWS)
     if numpy.any(numpy.abs(numpy.sqrt(numpy.sum(ef[:, 1:] * ef[:, 1:], axis=1)) - 1.0) > 1e-6):
         raise ValueError(f'{who}: rows must have unit normals')
     if start is not None:
@@ -143,8 +136,7 @@ def reduce_solution(source, tol: float = 1e-8, device: int = 0):
     if source.merge_info is None and source.overlap_info is None:
         raise ValueError(f'{who}: only the results of merge_regions and remove_overlaps are reduced (their regions own their E, f)')
     n_t = source.theta_dim() if source.program is not None else numpy.asarray(regs[0].E).shape[1]
-    if n_t > MAX_DIM:
-        raise ValueError(f'{who}: n_theta = {n_t} > {MAX_DIM}')
+    check_region_limits(who, (), n_t)
     if not (numpy.isfinite(tol) and tol >= 0.0):
         raise ValueError(f'{who}: tol must be finite and >= 0')
     parts, index, void = [], [], []

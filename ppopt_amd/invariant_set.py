@@ -34,6 +34,7 @@ from typing import Optional
 import numpy
 
 from ._cells import check_cell_call, fill_stats, new_stats
+from ._pairs import feasible_points
 from .region_merge import mask_rows, solution_rows
 
 __all__ = ['InvariantSet', 'InvariantVolumes', 'invariant_set', 'backward_exit_cells']
@@ -161,10 +162,10 @@ class InvariantSet:
         off = numpy.concatenate([self.region_off, self.region_off[-1] + self.cell_off[1:]]).astype(numpy.int64)
         ef = numpy.vstack([self.region_rows, self.cell_rows])
         stats = {'rounds': 0, 'items': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0, 'round_ms': [], 'max_item_rows': 0}
-        xs, _, status, s = _lib.merge_regions(self.region_off, self.region_rows, device)
+        xs, _, usable, s = feasible_points(self.region_off, self.region_rows, (), device)
         stats['device_ms'] += s['ms']
-        xs = numpy.vstack([numpy.where(numpy.isfinite(xs), xs, 0.0), numpy.zeros((len(self), n_t))])
-        usable = numpy.concatenate([status == 0, numpy.zeros(len(self), dtype=bool)])
+        xs = numpy.vstack([xs, numpy.zeros((len(self), n_t))])
+        usable = numpy.concatenate([usable, numpy.zeros(len(self), dtype=bool)])
         cutters = [[(R + int(c), None) for c in self.cells_of(i)] for i in range(R)] + [[] for _ in range(len(self))]
 
         def launch(poff, prows, item_source, entries, start):

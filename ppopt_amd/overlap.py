@@ -11,8 +11,9 @@ tie rule of Solution.get_region).  The procedure is deterministic:
      with |g| that small and |h| not, the cheaper region is cheaper everywhere (d_min = d_max = +-inf by the sign of h, no LP);
      otherwise the cut row of the pair is the unit row of {J_j <= J_i}, [h / |g| | -g / |g|], and d(theta) = (J_i - J_j) / |g| the depth
      behind it;
-  3. candidate pairs i < j: boxes overlapping by more than tol in every coordinate (box_pairs, a host sweep, or with sweep='device'
-     geometry.box_pairs; screen='rows' drops the candidates that a row of one region separates from the other's box).  On the device (csrc/overlap.hpp,
+  3. candidate pairs i < j by _pairs.candidate_pairs: boxes overlapping by more than tol in every coordinate (box_pairs, a host sweep, or
+     with sweep='device' geometry.box_pairs; screen='rows' drops the candidates that a row of one region separates from the other's box,
+     DESIGN §3.27).  On the device (csrc/overlap.hpp,
      k_overlap_pairs): r = the Chebyshev radius of R_i n R_j, and d_min, d_max over it.  Verdicts, first match:
        a radius run unbounded or capped  EQUAL when value-equal, else CROSSING      r <= tol          DISJOINT
        value-equal                       EQUAL    (i is cut by R_j)                  d_max <= tol      I_WINS  (j is cut by R_i)
@@ -33,7 +34,8 @@ from typing import List, Optional
 import numpy
 
 from .critical_region import CriticalRegion
-from .region_merge import MAX_DIM, MAX_ROWS, mask_rows, solution_rows
+from ._pairs import MAX_ROWS, candidate_pairs, check_polytopes, check_region_limits, check_scalars, feasible_points, host_pairs
+from .region_merge import mask_rows, solution_rows
 
 __all__ = ['ReducedRegion', 'OverlapPartition', 'remove_overlaps', 'partition_by_value', 'difference_rounds', 'build_reduced_solution', 'VERDICTS']
 
@@ -63,28 +65,7 @@ class OverlapPartition:
 def box_pairs(box: numpy.ndarray, usable: numpy.ndarray, tol: float):
     """(i, j) with i < j, ascending, of the usable regions whose boxes [R, 2, n_t] overlap by more than tol in every coordinate: a sweep
     along the first coordinate."""
-    idx = numpy.flatnonzero(usable)
-    if len(idx) < 2:
-        return numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int64)
-    lo, hi = box[idx, 0], box[idx, 1]
-    order = numpy.argsort(lo[:, 0], kind='stable')
-    lo, hi, idx = lo[order], hi[order], idx[order]
-    end = numpy.searchsorted(lo[:, 0], hi[:, 0] - tol, side='left')    # lo_j < hi_i - tol for j in (k, end[k])
-    pa, pb = [], []
-    with numpy.errstate(invalid='ignore'):
-        for k in range(len(idx) - 1):
-            e = int(end[k])
-            if e <= k + 1:
-                continue
-            hit = numpy.all(numpy.minimum(hi[k], hi[k + 1:e]) - numpy.maximum(lo[k], lo[k + 1:e]) > tol, axis=1)
-            other = idx[k + 1:e][hit]
-            pa.append(numpy.minimum(idx[k], other))
-            pb.append(numpy.maximum(idx[k], other))
-    if not pa:
-        return numpy.zeros(0, dtype=numpy.int64), numpy.zeros(0, dtype=numpy.int64)
-    pa, pb = numpy.concatenate(pa), numpy.concatenate(pb)
-    o = numpy.lexsort((pb, pa))
-    return pa[o].astype(numpy.int64), pb[o].astype(numpy.int64)
+    return host_pairs('mask', box, usable, None, None, tol)
 
 
 def classify_pairs(radius, d_min, d_max, flag, equal, tol: float) -> numpy.ndarray:
@@ -182,13 +163,6 @@ def difference_rounds(who, off, ef, xs, usable, cutters, launch, cutting_rows, m
     return live, round_ms
 
 
-def _device_box_pairs(box, usable, tol: float, device: int):
-    """box_pairs by geometry.box_pairs.  box_pairs does not open a NaN bound: a box that holds one meets nothing there, so it is masked
-    here.  (Boxes of usable regions carry no NaN unless a simplex run overflowed: DESIGN §3.27.)"""
-    from .geometry.box_pairs import box_pairs as device_pairs
-    return device_pairs(box, usable & ~numpy.isnan(box).any(axis=(1, 2)), margin=tol, device=device)
-
-
 def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, value_tol: float = 1e-9, max_pieces: int = 1 << 20,
                        device: int = 0, void=(), reduce_rows: bool = False, sweep: str = 'host', screen: str = 'none') -> OverlapPartition:
     """The partition of the polytopes {n.theta <= o} (unit rows ef_rows = [o | n] in CSR form by row_off) by the lowest affine value
@@ -199,50 +173,25 @@ def partition_by_value(row_off, ef_rows, g, h, n_t: int, tol: float = 1e-8, valu
     box never reach the pair stage (they could only be DISJOINT), ``pairs`` holds the kept ones and stats gains box_candidates, screened,
     screen_ms.  With either, stats also holds sweep_ms, the wall time of the sweep."""
     from . import _lib
-    from .geometry.box_pairs import screen_pairs, sweep_options
-    on_device, rows_screen = sweep_options('partition_by_value', sweep, screen)
+    from .geometry.box_pairs import sweep_options
+    sweep_options('partition_by_value', sweep, screen)
     t0 = time.perf_counter()
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    g = numpy.ascontiguousarray(g, dtype=numpy.float64).reshape(-1, n_t)
-    h = numpy.ascontiguousarray(h, dtype=numpy.float64).reshape(-1)
-    R = len(off) - 1
-    if not (1 <= n_t <= MAX_DIM):
-        raise ValueError(f'partition_by_value: n_theta = {n_t} is outside 1..{MAX_DIM}')
+    check_scalars('partition_by_value', n_t)
     if not (numpy.isfinite(tol) and tol >= 0.0 and numpy.isfinite(value_tol) and value_tol >= 0.0):
         raise ValueError('partition_by_value: tol and value_tol must be finite and >= 0')
-    if R < 1 or len(g) != R or len(h) != R or off[0] != 0 or off[-1] != len(ef):
-        raise ValueError('partition_by_value: row_off [R + 1], g [R, n_t] and h [R] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'partition_by_value: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(g)) and numpy.all(numpy.isfinite(h))):
-        raise ValueError('partition_by_value: rows and values must be finite')
+    g = numpy.ascontiguousarray(g, dtype=numpy.float64).reshape(-1, n_t)
+    h = numpy.ascontiguousarray(h, dtype=numpy.float64).reshape(-1)
+    off, ef, _, R = check_polytopes('partition_by_value', row_off, ef_rows, n_t, extra=[('g [R, n_t]', g, (n_t,)), ('h [R]', h, ())], word='values')
     stats = {'regions_before': R, 'candidate_pairs': 0, 'rounds': 0, 'work_items': 0, 'max_item_rows': 0, 'lps': 0, 'pivots': 0, 'wide': 0, 'device_ms': 0.0}
-    xs, box, status, s = _lib.merge_regions(off, ef, device)
+    xs, box, usable, s = feasible_points(off, ef, void, device)
     stats['lps'] += s['lps']
     stats['pivots'] += s['pivots']
     stats['device_ms'] += s['ms']
-    usable = status == 0
-    usable[list(void)] = False
-    xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
     # 2. values
-    if on_device or rows_screen:
-        t1 = time.perf_counter()
-        if on_device:
-            pa, pb, sw = _device_box_pairs(box, usable, tol, device)
-            stats['sweep_kernel_ms'] = sw['ms']
-        else:
-            pa, pb = box_pairs(box, usable, tol)
-        stats['sweep_ms'] = (time.perf_counter() - t1) * 1e3
-    else:
-        pa, pb = box_pairs(box, usable, tol)
-    if rows_screen:
-        t1 = time.perf_counter()
-        keep, sc = screen_pairs(off, ef, pa, pb, box, box, sides='both', device=device)
-        stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
-        pa, pb = pa[keep], pb[keep]
-        stats['screen_ms'] = (time.perf_counter() - t1) * 1e3
+    pa, pb, swept = candidate_pairs('partition_by_value', 'mask', box, usable, None, None, tol, off, ef, lambda: (box, box), 'both', sweep, screen, device)
+    if (sweep, screen) == ('host', 'none'):
+        del swept['sweep_ms']      # reported with the device sweep or the screen only
+    stats.update(swept)
     n_pairs = len(pa)
     stats['candidate_pairs'] = n_pairs
     g_thr = value_tol * (1.0 + float(numpy.max(numpy.linalg.norm(g, axis=1))))
@@ -347,11 +296,7 @@ def check_source(source, tol: float, value_tol: float, max_pieces: int):
         raise ValueError('remove_overlaps: a merged solution keeps no full law to compare values with: reduce the source '
                          '(merge_info["source"]) instead')
     n_t = source.theta_dim() if source.program is not None else numpy.asarray(source.critical_regions[0].E).shape[1]
-    if n_t > MAX_DIM:
-        raise ValueError(f'remove_overlaps: n_theta = {n_t} > {MAX_DIM}')
-    for i, r in enumerate(source.critical_regions):
-        if numpy.asarray(r.E).reshape(-1, n_t).shape[0] > MAX_ROWS:
-            raise ValueError(f'remove_overlaps: region {i} has more than {MAX_ROWS} rows')
+    check_region_limits('remove_overlaps', source.critical_regions, n_t)
     if not (numpy.isfinite(tol) and tol >= 0.0 and numpy.isfinite(value_tol) and value_tol >= 0.0):
         raise ValueError('remove_overlaps: tol and value_tol must be finite and >= 0')
     if int(max_pieces) < 1:

@@ -21,10 +21,8 @@ from typing import List, Optional
 
 import numpy
 
+from ._pairs import MAX_DIM, MAX_ROWS, check_region_limits      # the limits are defined there; importers of this module find them here
 from .critical_region import CriticalRegion
-
-MAX_DIM = 16      # n_theta of the device kernels
-MAX_ROWS = 256    # rows of a region (source regions and merged ones)
 
 __all__ = ['MergedRegion', 'merge_regions', 'build_merged_solution', 'unit_rows', 'solution_rows','law_groups', 'dedupe_rows', 'check_source']
 
@@ -44,15 +42,11 @@ def check_source(source, outputs, tol: float, law_tol: float):
     if source.is_mixed_integer_sol() or any(r.y_fixation is not None for r in source.critical_regions):
         raise ValueError('merge_regions: mixed-integer solutions are not merged')
     n_t = source.theta_dim() if source.program is not None else numpy.asarray(source.critical_regions[0].E).shape[1]
-    if n_t > MAX_DIM:
-        raise ValueError(f'merge_regions: n_theta = {n_t} > {MAX_DIM}')
+    check_region_limits('merge_regions', (), n_t)
     if not (numpy.isfinite(tol) and tol >= 0.0 and numpy.isfinite(law_tol) and law_tol >= 0.0):
         raise ValueError('merge_regions: tol and law_tol must be finite and >= 0')
-    n_x = None
-    for i, r in enumerate(source.critical_regions):
-        if numpy.asarray(r.E).reshape(-1, n_t).shape[0] > MAX_ROWS:
-            raise ValueError(f'merge_regions: region {i} has more than {MAX_ROWS} rows')
-        n_x = numpy.asarray(r.A).reshape(-1, n_t).shape[0] if n_x is None else n_x
+    check_region_limits('merge_regions', source.critical_regions, n_t)
+    n_x = numpy.asarray(source.critical_regions[0].A).reshape(-1, n_t).shape[0] if source.critical_regions else None
     if outputs is None:
         outputs = list(range(n_x or 0))
     else:

@@ -16,7 +16,7 @@ Lower-dimensional transitions -- through a facet or a vertex, T_ij of radius <= 
 trajectories (reachable, steps_to, cycles_outside) holds for almost every initial state, not for every one.
 
 Stages: feasible points and boxes of the regions (_lib.merge_regions), the exact boxes of the images (k_transition_boxes), candidate
-pairs whose image box and region box meet (image_box_pairs, a host sweep, or with sweep='device' geometry.box_pairs), with
+pairs by _pairs.candidate_pairs: image box and region box meet (image_box_pairs, a host sweep, or with sweep='device' geometry.box_pairs), with
 screen='rows' without the candidates that one row of the target separates from the image box (geometry.screen_pairs), one
 LP per candidate (k_transition_pairs).
 """
@@ -26,7 +26,8 @@ from typing import Optional
 
 import numpy
 
-from .region_merge import MAX_DIM, MAX_ROWS, solution_rows
+from ._pairs import candidate_pairs, check_pair_indices, check_polytopes, check_region_limits, feasible_points, host_pairs, map_entries
+from .region_merge import solution_rows
 
 __all__ = ['TransitionGraph', 'transition_graph', 'transition_pairs', 'image_box_pairs', 'screen_box', 'STATUS', 'NO_EDGE', 'EDGE', 'UNBOUNDED', 'UNDECIDED']
 
@@ -38,39 +39,7 @@ def image_box_pairs(image_box: numpy.ndarray, region_box: numpy.ndarray, usable:
     """The directed candidates (i, j), sorted by (i, j), among the usable regions: the image box of i (image_box [R, 2, n_t], lower /
     upper) and the region box of j (region_box [R, 2, n_t]) overlap by more than -tol in every coordinate.  One sweep along the first
     coordinate over both kinds of boxes together; infinite bounds are fine, and a box with a NaN bound in a coordinate is open there."""
-    idx = numpy.flatnonzero(usable)
-    none = numpy.zeros(0, dtype=numpy.int64)
-    if not len(idx):
-        return none, none
-    n = len(idx)
-    lo = numpy.concatenate([image_box[idx, 0], region_box[idx, 0]])
-    hi = numpy.concatenate([image_box[idx, 1], region_box[idx, 1]])
-    unknown = numpy.isnan(lo) | numpy.isnan(hi)            # a coordinate with a NaN bound separates nothing
-    lo, hi = numpy.where(unknown, -numpy.inf, lo), numpy.where(unknown, numpy.inf, hi)
-    who = numpy.concatenate([idx, idx])
-    is_image = numpy.arange(2 * n) < n
-    order = numpy.argsort(lo[:, 0], kind='stable')
-    lo, hi, who, is_image = lo[order], hi[order], who[order], is_image[order]
-    end = numpy.searchsorted(lo[:, 0], hi[:, 0] + tol, side='left')    # lo_l < hi_k + tol for l in (k, end[k])
-    pa, pb = [], []
-    with numpy.errstate(invalid='ignore'):
-        for k in range(2 * n - 1):
-            e = int(end[k])
-            if e <= k + 1:
-                continue
-            other = numpy.flatnonzero(is_image[k + 1:e] != is_image[k]) + k + 1
-            if not len(other):
-                continue
-            miss = numpy.any(numpy.minimum(hi[k], hi[other]) - numpy.maximum(lo[k], lo[other]) <= -tol, axis=1)
-            other = who[other[~miss]]
-            mine = numpy.full(len(other), who[k])
-            pa.append(mine if is_image[k] else other)
-            pb.append(other if is_image[k] else mine)
-    if not pa:
-        return none, none
-    pa, pb = numpy.concatenate(pa), numpy.concatenate(pb)
-    o = numpy.lexsort((pb, pa))
-    return pa[o].astype(numpy.int64), pb[o].astype(numpy.int64)
+    return host_pairs('coordinate', image_box, usable, region_box, usable, -tol)
 
 
 SCREEN_BOX_SLACK = 1e-9      # the least relative widening of an image box before rows screen it (screen_box)
@@ -89,23 +58,6 @@ def screen_box(image_box, tol: float) -> numpy.ndarray:
         return numpy.stack([box[:, 0] - w[:, 0], box[:, 1] + w[:, 1]], axis=1)
 
 
-def _device_image_box_pairs(image_box, region_box, usable, tol: float, device: int):
-    """image_box_pairs by geometry.box_pairs.  image_box_pairs opens BOTH bounds of a coordinate in which either bound of a box is NaN;
-    the device rule opens the NaN bound alone, so such coordinates are opened here first.  (Boxes of usable regions carry no NaN and no
-    two equal infinities in a coordinate unless a simplex run overflowed: DESIGN §3.27.)"""
-    from .geometry.box_pairs import box_pairs
-
-    def opened(box):
-        unknown = numpy.isnan(box).any(axis=1)
-        if not unknown.any():
-            return box
-        box = box.copy()
-        box[:, 0][unknown], box[:, 1][unknown] = -numpy.inf, numpy.inf
-        return box
-
-    return box_pairs(opened(image_box), usable, opened(region_box), usable, margin=-tol, device=device)
-
-
 def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, full_radius: bool = False, pairs=None, device: int = 0,
                      void=(), sweep: str = 'host', screen: str = 'none') -> dict:
     """The pair stage on arrays: polytopes of unit rows ef_rows = [o | n] in CSR form by row_off with the maps Phi [R, n_t, n_t], phi
@@ -120,59 +72,34 @@ def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, fu
     Returns a dict: i, j (sorted by (i, j)), radius, status (NO_EDGE, EDGE, UNBOUNDED, UNDECIDED), witness [pairs, n_t], region_status
     [R] (UNDECIDED where the box stage was capped, else 0), image_box, region_box, usable and stats."""
     from . import _lib
-    from .geometry.box_pairs import screen_pairs, sweep_options
-    on_device, rows_screen = sweep_options('transition_pairs', sweep, screen)
-    off = numpy.ascontiguousarray(row_off, dtype=numpy.int64).reshape(-1)
-    ef = numpy.ascontiguousarray(ef_rows, dtype=numpy.float64).reshape(-1, n_t + 1)
-    R = len(off) - 1
-    if not (1 <= n_t <= MAX_DIM):
-        raise ValueError(f'transition_pairs: n_theta = {n_t} is outside 1..{MAX_DIM}')
-    if not (numpy.isfinite(tol) and tol >= 0.0):
-        raise ValueError('transition_pairs: tol must be finite and >= 0')
-    Phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64)
-    phi = numpy.ascontiguousarray(phi, dtype=numpy.float64)
-    if R < 1 or off[0] != 0 or off[-1] != len(ef) or Phi.shape != (R, n_t, n_t) or phi.shape != (R, n_t):
-        raise ValueError('transition_pairs: row_off [R + 1], Phi [R, n_t, n_t] and phi [R, n_t] must describe R >= 1 polytopes')
-    counts = numpy.diff(off)
-    if counts.min() < 1 or counts.max() > MAX_ROWS:
-        raise ValueError(f'transition_pairs: every polytope needs 1..{MAX_ROWS} rows')
-    if not (numpy.all(numpy.isfinite(ef)) and numpy.all(numpy.isfinite(Phi)) and numpy.all(numpy.isfinite(phi))):
-        raise ValueError('transition_pairs: rows and maps must be finite')
+    from .geometry.box_pairs import sweep_options
+    sweep_options('transition_pairs', sweep, screen)
+    Phi, phi = numpy.ascontiguousarray(Phi, dtype=numpy.float64), numpy.ascontiguousarray(phi, dtype=numpy.float64)
+    off, ef, _, R = check_polytopes('transition_pairs', row_off, ef_rows, n_t, tol, extra=map_entries(Phi, phi, n_t), word='maps')
     if pairs is not None:
-        pa = numpy.asarray(pairs[0], dtype=numpy.int64).reshape(-1)
-        pb = numpy.asarray(pairs[1], dtype=numpy.int64).reshape(-1)
-        if pa.shape != pb.shape or (len(pa) and (min(pa.min(), pb.min()) < 0 or max(pa.max(), pb.max()) >= R)):
-            raise ValueError('transition_pairs: pairs must be two index arrays of one length into the polytopes')
+        pa, pb = check_pair_indices('transition_pairs', 'pairs', pairs[0], pairs[1], R)
         o = numpy.lexsort((pb, pa))
         pa, pb = pa[o], pb[o]
     stats = {'box_ms': 0.0, 'pair_ms': 0.0, 'sweep_ms': 0.0, 'candidates': 0, 'lps': 0, 'pivots': 0, 'capped': 0, 'edges': 0, 'box_lps': 0,
              'box_pivots': 0}
-    xs, region_box, status, s = _lib.merge_regions(off, ef, device)
+    xs, region_box, usable, s = feasible_points(off, ef, void, device)
     stats['box_ms'] += s['ms']
-    usable = status == 0
-    usable[list(void)] = False
-    xs = numpy.where(numpy.isfinite(xs), xs, 0.0)
     region_status = numpy.zeros(R, dtype=numpy.int32)
     image_box = None
+    screened = []      # the widened image boxes, once the screen has asked for them
     if pairs is None:
         image_box, capped, s = _lib.transition_boxes(off, ef, Phi, phi, xs, device)
         stats['box_ms'] += s['ms']
         stats['box_lps'], stats['box_pivots'] = s['lps'], s['pivots']
         region_status[capped != 0] = UNDECIDED
-        t0 = time.perf_counter()
-        if on_device:
-            pa, pb, sw = _device_image_box_pairs(image_box, region_box, usable, tol, device)
-            stats['sweep_kernel_ms'] = sw['ms']
-        else:
-            pa, pb = image_box_pairs(image_box, region_box, usable, tol)
-        stats['sweep_ms'] = (time.perf_counter() - t0) * 1e3
-        if rows_screen:
-            t0 = time.perf_counter()
-            outer = screen_box(image_box, tol)
-            keep, sc = screen_pairs(off, ef, pa, pb, None, outer, sides='b', device=device)
-            stats.update(box_candidates=len(pa), screened=int(sc['dropped']), screen_kernel_ms=sc['ms'])
-            pa, pb = pa[keep], pb[keep]
-            stats['screen_ms'] = (time.perf_counter() - t0) * 1e3
+
+        def screen_boxes():
+            screened.append(screen_box(image_box, tol))
+            return None, screened[0]
+
+        pa, pb, swept = candidate_pairs('transition_pairs', 'coordinate', image_box, usable, region_box, usable, -tol, off, ef, screen_boxes, 'b',
+                                        sweep, screen, device)
+        stats.update(swept)
     stats['candidates'] = len(pa)
     if len(pa):
         radius, st, witness, s = _lib.transition_pairs(off, ef, Phi, phi, xs, pa, pb, full_radius, tol, device)
@@ -184,8 +111,8 @@ def transition_pairs(row_off, ef_rows, Phi, phi, n_t: int, tol: float = 1e-8, fu
     stats['edges'] = int(numpy.sum(st != NO_EDGE))
     res = {'i': pa, 'j': pb, 'radius': radius, 'status': st, 'witness': witness, 'region_status': region_status, 'image_box': image_box,
            'region_box': region_box, 'usable': usable, 'stats': stats}
-    if rows_screen and pairs is None:
-        res['screen_box'] = outer
+    if screened:
+        res['screen_box'] = screened[0]
     return res
 
 
@@ -326,11 +253,7 @@ def check_source(source, A, B, inputs, c, tol: float):
         raise ValueError(f'{who}: the solution is flagged overlapping: a point may lie in several regions, and which law acts there is '
                          f'chosen by objective; reduce it with remove_overlaps first')
     A, B, inp, c, _, n_t = _check(source, A, B, inputs, c, None, tol, who=who)
-    if n_t > MAX_DIM:
-        raise ValueError(f'{who}: n_theta = {n_t} > {MAX_DIM}')
-    for i, r in enumerate(source.critical_regions):
-        if numpy.asarray(r.E).reshape(-1, n_t).shape[0] > MAX_ROWS:
-            raise ValueError(f'{who}: region {i} has more than {MAX_ROWS} rows')
+    check_region_limits(who, source.critical_regions, n_t)
     return A, B, inp, c, n_t
 
 

@@ -405,3 +405,56 @@ def test_remove_overlaps_with_the_device_sweep_and_the_screen():
     assert numpy.array_equal(host.sources, dev.sources) and numpy.array_equal(host.sources, kept.sources)
     for p, q, r in zip(host.pieces, dev.pieces, kept.pieces):
         assert (p is None) == (q is None) == (r is None) and (p is None or (p.tobytes() == q.tobytes() == r.tobytes()))
+
+
+# ---- 8. the keys of stats, per call and per setting -----------------------------------------------------------------------------------------
+def _settings():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location('sweep_bench', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools', 'sweep_bench.py'))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module.SETTINGS
+
+
+SWEEP_KEYS = {('host', 'none'): set(), ('device', 'none'): {'sweep_kernel_ms'},
+              ('device', 'rows'): {'sweep_kernel_ms', 'box_candidates', 'screened', 'screen_kernel_ms', 'screen_ms'},
+              ('host', 'rows'): {'box_candidates', 'screened', 'screen_kernel_ms', 'screen_ms'}}
+OVERLAP_KEYS = {'regions_before', 'candidate_pairs', 'rounds', 'work_items', 'max_item_rows', 'lps', 'pivots', 'wide', 'device_ms', 'regions_after', 'wall_ms'}
+GRAPH_KEYS = {'box_ms', 'pair_ms', 'sweep_ms', 'candidates', 'lps', 'pivots', 'capped', 'edges', 'box_lps', 'box_pivots', 'wall_ms'}
+COMPARE_KEYS = {'pairs', 'meets', 'constant_rows', 'lps', 'pivots', 'wide', 'pair_ms', 'device_ms', 'candidates', 'box_pairs', 'sweep_ms', 'wall_ms'}
+
+
+def test_the_keys_of_stats_in_the_four_settings():
+    """The twelve key sets as they were when every call had its own candidate stage: remove_overlaps reports sweep_ms only with the device
+    sweep or the screen, the other two always.  And the results of the four settings are the same bytes (compare: on the meeting pairs,
+    the only ones every setting lists; all pairs between the two settings with and the two without the screen)."""
+    settings = _settings()
+    assert set(settings) == set(SWEEP_KEYS) and len(settings) == 4
+    from test_gpu_overlap import _solved
+    _, overlapping, _ = _solved('mplp')
+    sol, plant = _double_integrator(2), pg.double_integrator_plant(2)
+    reduced, graphs, gaps = {}, {}, {}
+    for sweep, screen in settings:
+        kw = dict(sweep=sweep, screen=screen)
+        reduced[sweep, screen] = overlapping.remove_overlaps(**kw)
+        graphs[sweep, screen] = sol.transition_graph(plant['A'], plant['B'], plant['inputs'], **kw)
+        gaps[sweep, screen] = sol.compare(sol, **kw)
+        extra = SWEEP_KEYS[sweep, screen]
+        assert set(reduced[sweep, screen].overlap_info['stats']) == OVERLAP_KEYS | extra | ({'sweep_ms'} if extra else set()), kw
+        assert set(graphs[sweep, screen].stats) == GRAPH_KEYS | extra, kw
+        assert set(gaps[sweep, screen].stats) == COMPARE_KEYS | extra, kw
+    first = settings[0]
+    for s in settings[1:]:
+        for key in ('indptr', 'indices', 'radius', 'status', 'witness', 'region_status'):
+            assert getattr(graphs[first], key).tobytes() == getattr(graphs[s], key).tobytes(), (s, key)
+        assert reduced[first].overlap_info['sources'].tobytes() == reduced[s].overlap_info['sources'].tobytes(), s
+        assert len(reduced[first]) == len(reduced[s])
+        for p, q in zip(reduced[first].critical_regions, reduced[s].critical_regions):
+            assert p.E.tobytes() == q.E.tobytes() and p.f.tobytes() == q.f.tobytes(), s
+        a, b = gaps[first], gaps[s]
+        for key in ('i', 'j', 'radius', 'gap', 'row', 'witness', 'flag'):
+            assert getattr(a, key)[a.meets].tobytes() == getattr(b, key)[b.meets].tobytes(), (s, key)
+    for a, b in ((gaps['host', 'none'], gaps['device', 'none']), (gaps['host', 'rows'], gaps['device', 'rows'])):
+        for key in LAW_GAP_ARRAYS:
+            assert getattr(a, key).tobytes() == getattr(b, key).tobytes(), key
