@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the combinatorial mpQP hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2]
+    python bench.py --gpus N --steps K --warmup W [--workload c4|c3|c2] [--full]
+
+A plain run does what the headline figure needs and nothing more: it sets up, warms up, times the K steps, writes the last timed
+solution if --dump-outputs is given, and prints the result line (one further solve, untimed and with a profile, counts the step's
+candidates and regions).  --full adds everything else the benchmark measures: the two further timed regions (per-kernel HIP events,
+collector off), the roofline accounting, the time to materialise every region, point location, the mixed-integer and many-programs
+extras, the complete solution by the graph traversal and the CPU baseline; --sweep and --deep are parts of it.
 
 A "step" is one complete pass of the parallel combinatorial algorithm over the workload program: every BFS level
 (verdict -> region -> child generation on the device, region records copied back and turned into CriticalRegion
@@ -12,7 +18,7 @@ N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-
 process per GPU, the frontier of every level sharded over the ranks, one RCCL exchange per level
 (ppopt_amd/distributed.py).  The problem is one program, so total work is fixed: scaling is "strong".
 
-rank 0 prints ONE JSON line.  Besides the contract keys it carries
+rank 0 prints ONE JSON line.  With --full it carries, besides the contract keys,
   roofline      algorithmic HBM bytes of the dominant kernel over its HIP-event time (SURVEY.md §8(d) formula)
   cpu_baseline  the CPU oracle (C port of the reference algorithm, OpenMP) timed on a bounded sample of the same
                 candidates on this box's host cores -- a reported baseline, not the target.
@@ -206,24 +212,57 @@ def cpu_baseline(prog, frontiers, gpu_status, target_candidates):
                     'the parity tests bound their number'}
 
 
+def headline(workload, prog, world, distributed, n_steps, n_warmup, elapsed, step_ms, prof, regions):
+    """The result line of a plain run: the contract keys and what describes the step.  ``elapsed``: seconds of the timed region of
+    ``n_steps`` steps, ``step_ms`` their single times; ``prof``: the profile of one solve (its levels and the base-set check),
+    ``regions``: the regions that solve returned.  --full adds its own keys to this record."""
+    candidates = sum(p['candidates'] for p in prof)
+    return {
+        'metric': 'candidate active-sets checked/sec (combinatorial mpQP)',
+        'value': candidates * n_steps / elapsed,
+        'unit': 'candidates/s',
+        'n_gpus': world,
+        'steps': n_steps,
+        'warmup': n_warmup,
+        'ms_per_step': 1e3 * elapsed / n_steps,
+        'higher_is_better': True,
+        'scaling': 'strong',
+        'vs_baseline': None,
+        'dtype': 'f64',
+        'data': 'synthetic',
+        'config': {'workload': workload, 'n_x': prog.num_x(), 'n_theta': prog.num_t(),
+                   'n_c': prog.num_constraints(), 'n_eq': len(prog.equality_indices), 'n_tc': int(prog.A_t.shape[0]),
+                   'candidates_per_step': candidates, 'regions_per_step': regions,
+                   'parallelism': (f'{world} GPU(s): small levels replicated, one split, then subtree-local levels that exchange '
+                                   f'only pruned masks') if distributed else 'single GPU'},
+        'regions_per_s': regions * n_steps / elapsed,
+        'levels': [{'k': p['k'], 'candidates': p['candidates'], 'status': p['status'], 'regions': p['regions']} for p in prof if p['depth'] > 0],
+        'step_ms': [round(v, 2) for v in step_ms],
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='c4', choices=sorted(WORKLOADS))
-    ap.add_argument('--cpu-sample', type=int, default=300000, help='candidates in the CPU baseline sample (0 = skip)')
-    ap.add_argument('--locate', type=int, default=100000, help='points of the point-location extra (0 = skip)')
-    ap.add_argument('--mi', type=int, default=1, help='mixed-integer enumeration extra on a synthetic mpMIQP (0 = skip)')
-    ap.add_argument('--complete', type=int, default=1, help='complete solution of the workload by the connected-graph traversal, as an extra (0 = skip)')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, everything else the benchmark measures: per-kernel and collector-off timed regions, roofline, '
+                    'materialisation, point location, mixed-integer and many-programs extras, complete solution, CPU baseline (off: the headline figure alone)')
+    ap.add_argument('--cpu-sample', type=int, default=300000, help='with --full: candidates in the CPU baseline sample (0 = skip)')
+    ap.add_argument('--locate', type=int, default=100000, help='with --full: points of the point-location extra (0 = skip)')
+    ap.add_argument('--mi', type=int, default=1, help='with --full: mixed-integer enumeration extra on a synthetic mpMIQP (0 = skip)')
+    ap.add_argument('--complete', type=int, default=1, help='with --full: complete solution of the workload by the connected-graph traversal, as an extra (0 = skip)')
     ap.add_argument('--events-in-value', action='store_true', help='one timed region only, with the HIP-event records of the per-kernel accounting inside it (the protocol of rounds 1-4)')
     ap.add_argument('--dist-single', action='store_true', help='run the multi-GPU driver with a process group of one rank (self-test)')
-    ap.add_argument('--sweep', action='store_true', help='shape sweep over the target class (n_x <= 20, n_theta <= 10): one JSON line with a row per shape (tools/shape_sweep.py); not the headline')
-    ap.add_argument('--deep', type=int, default=0, help='also time the six-level variant of c4 on one GPU (the scaling workload the multi-GPU runs report under extra)')
+    ap.add_argument('--sweep', action='store_true', help='with --full: shape sweep over the target class (n_x <= 20, n_theta <= 10): one JSON line with a row per shape (tools/shape_sweep.py); not the headline')
+    ap.add_argument('--deep', type=int, default=0, help='with --full: also time the six-level variant of c4 on one GPU (the scaling workload the multi-GPU runs report under extra)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write the solution of the last timed step as DIR/<name>.npy (float64, under 64 MB in all; see dump_outputs)')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if (args.sweep or args.deep) and not args.full:
+        ap.error('--sweep and --deep are parts of the full benchmark: add --full')
     if args.sweep:
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
         import shape_sweep
@@ -340,13 +379,18 @@ def main():
         if args.dump_outputs and rank == 0:
             dumped = dump_outputs(sol, args.dump_outputs)     # the last step of the region `value` comes from, written after its timing
         del sol
-        step(None)      # (hand-over: the region objects of the last untimed-events step are released outside the next region)
-        elapsed_events, profiles, _, sol = timed_region(True)
-        del sol
-        step(None)
-        elapsed_nogc, _, _, sol_c = timed_region(False, collector=False)
-        del sol_c
-        sol = step(None)
+        if args.full:
+            step(None)      # (hand-over: the region objects of the last untimed-events step are released outside the next region)
+            elapsed_events, profiles, _, sol = timed_region(True)
+            del sol
+            step(None)
+            elapsed_nogc, _, _, sol_c = timed_region(False, collector=False)
+            del sol_c
+            sol = step(None)
+        else:
+            # the headline counts candidates, and only a profile holds their number: one more solve, untimed, after the region
+            profiles = [[]]
+            sol = step(profiles[0])
 
     # ---- accounting (identical on every rank; rank 0 reports) ----------------------------------------------
     prof = profiles[-1]
@@ -354,13 +398,37 @@ def main():
     candidates = sum(p['candidates'] for p in prof)
     regions = len(sol.critical_regions)
     steps = max(args.steps, 1)
+    nx, nt, nc = prog.num_x(), prog.num_t(), prog.num_constraints()
+    out = headline(f'{args.workload}: {descr}', prog, world, distributed, args.steps, args.warmup, elapsed, step_ms, prof, regions)
+    out['full'] = bool(args.full)
+
+    def finish():
+        if distributed:
+            dist.destroy_process_group()
+        sys.stdout.flush()
+        try:
+            import ctypes
+            ctypes.CDLL(None).fflush(None)     # C stdio buffers (the RCCL banner) leave before fd 1 is restored
+        except OSError:
+            pass
+        if real_stdout is not None:
+            os.dup2(real_stdout, 1)
+            os.close(real_stdout)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+
+    if not args.full:
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
+        finish()
+        return
+    # ---- everything below is the full benchmark: none of it enters `value` ---------------------------------
     all_levels = [p for pr in profiles for p in pr if p['depth'] > 0]
     # per-stage HIP-event times of this rank, summed over all timed steps
     ms = {kname: sum(p.get(kname, 0.0) for p in all_levels) for kname in ('ms_verdict', 'ms_region', 'ms_children')}
     local_cands = sum(p.get('local_candidates', p['candidates']) for p in all_levels)
     n_e = float(numpy.mean([r.E.shape[0] for r in sol.critical_regions])) if regions else 0.0
     rho = regions / max(candidates, 1)
-    nx, nt, nc = prog.num_x(), prog.num_t(), prog.num_constraints()
     # SURVEY.md 8(d) figure for the whole path (every kernel of a level together)
     bytes_path = sum(algorithmic_bytes(prog, p['k'], rho, n_e) * p.get('local_candidates', p['candidates']) for p in all_levels)
     ms_path = ms['ms_verdict'] + ms['ms_region'] + ms['ms_children']
@@ -472,14 +540,11 @@ def main():
         except (OSError, ValueError, KeyError, TypeError):
             traffic = dom_traffic = None
     b_alg = bytes_path / max(local_cands, 1)
-    out = {
-        'metric': 'candidate active-sets checked/sec (combinatorial mpQP)',
-        'value': candidates * steps / elapsed,
-        'unit': 'candidates/s',
-        'n_gpus': world,
-        'steps': args.steps,
-        'warmup': args.warmup,
-        'ms_per_step': 1e3 * elapsed / steps,
+    # (protocol figures where the driver's parser keeps them: VERDICT r5 item 8a)
+    out['config'].update({'ms_per_step_with_kernel_events': 1e3 * elapsed_events / steps,
+                          'ms_per_step_collector_off': (1e3 * elapsed_nogc / steps) if elapsed_nogc is not None else None,
+                          'value_protocol': 'collector on, no HIP-event records inside the levels'})
+    out.update({
         'ms_per_step_with_kernel_events': 1e3 * elapsed_events / steps,
         'ms_per_step_collector_off': (1e3 * elapsed_nogc / steps) if elapsed_nogc is not None else None,
         'collector': ('value / ms_per_step: the cyclic collector ON in the process, as a user\'s solve() runs -- solve() itself holds it while it creates its region objects (region_batch.gc_paused; MPC_KEEP_GC=1 leaves it running) -- (round 5 timed them with gc.disable()); '
@@ -489,24 +554,7 @@ def main():
                           'its levels); per-kernel durations (roofline.dominant_kernel, roofline.kernels, kernel_ms_per_step): a second timed region '
                           'of the same K steps with a profile per step = HIP events around every stage and heavy kernel on the stream it is '
                           'launched on; that region runs at ms_per_step_with_kernel_events'),
-        'higher_is_better': True,
-        'scaling': 'strong',
-        'vs_baseline': None,
-        'dtype': 'f64',
-        'data': 'synthetic',
-        'config': {'workload': f'{args.workload}: {descr}', 'n_x': nx, 'n_theta': nt,
-                   'n_c': nc, 'n_eq': len(prog.equality_indices), 'n_tc': int(prog.A_t.shape[0]),
-                   'candidates_per_step': candidates, 'regions_per_step': regions,
-                   # (protocol figures where the driver's parser keeps them: VERDICT r5 item 8a)
-                   'ms_per_step_with_kernel_events': 1e3 * elapsed_events / steps,
-                   'ms_per_step_collector_off': (1e3 * elapsed_nogc / steps) if elapsed_nogc is not None else None,
-                   'value_protocol': 'collector on, no HIP-event records inside the levels',
-                   'parallelism': (f'{world} GPU(s): small levels replicated, one split, then subtree-local levels that exchange '
-                                   f'only pruned masks') if distributed else 'single GPU'},
-        'regions_per_s': regions * steps / elapsed,
-        'levels': [{'k': p['k'], 'candidates': p['candidates'], 'status': p['status'], 'regions': p['regions']} for p in levels],
         'kernel_ms_per_step': {k: v / steps for k, v in ms.items()},
-        'step_ms': [round(v, 2) for v in step_ms],
         'roofline': {'bound': 'hbm', 'kernel': 'path: every kernel of a level (SURVEY.md 8(d): achieved = B_alg x candidates/s)',
                      'achieved': b_alg * (candidates * steps / elapsed) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                      'frac': b_alg * (candidates * steps / elapsed) / 1e9 / HBM_PEAK_GBS, 'traffic': traffic,
@@ -544,7 +592,7 @@ def main():
                              'runs on.  k_region2 and k_theta2 are fp64 simplex pivots in registers (VALU issue / dependent latency, '
                              'almost no HBM traffic); k_x2 streams one cached dictionary per candidate and k_xq reads the vectors of the '
                              'parent\'s dictionary its product-form iterations touch: the two kernels the HBM roof applies to.'},
-    }
+    })
     # CriticalRegion objects returned by the solve are views into per-level arrays that are cut out on first access;
     # the time to touch every field of every region is reported separately (not part of `value`)
     t_mat = time.perf_counter()
@@ -766,19 +814,7 @@ def main():
             'candidates_per_s': deep_cands * n_deep / deep_elapsed, 'n_gpus': world,
             'levels': [{'k': p['k'], 'candidates': p['candidates'], 'regions': p['regions']} for p in dprof if p['depth'] > 0]}}
         del dsol
-    if distributed:
-        dist.destroy_process_group()
-    sys.stdout.flush()
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)     # C stdio buffers (the RCCL banner) leave before fd 1 is restored
-    except OSError:
-        pass
-    if real_stdout is not None:
-        os.dup2(real_stdout, 1)
-        os.close(real_stdout)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
+    finish()
 
 
 if __name__ == '__main__':

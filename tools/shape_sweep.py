@@ -2,7 +2,7 @@
 random mpQPs generate_mpqp_data(n_x, n_theta, m, seed) with n_x in {6, 10, 14, 20}, n_theta in {2, 6, 10}, m in {n_x, 2 n_x, 3 n_x},
 two mpLPs, BASELINE config 5 (control allocation) and config 1 (transport mpLP).
 
-    python bench.py --sweep                 (one JSON line)        or        python tools/shape_sweep.py [out.json]
+    python bench.py --full --sweep          (one JSON line)        or        python tools/shape_sweep.py [out.json]
 
 Every program is solved to full depth (the reference's loop: max(n_x, n_theta) - n_eq levels) unless its tree passes 10^7 candidates:
 then to the deepest level that keeps the total below that (the row says so: `full_depth`).  Per cell: shape after the presolve, levels,
