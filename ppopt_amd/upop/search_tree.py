@@ -136,6 +136,8 @@ class SearchTree:
                 if not overlapping and 0 <= found <= r:
                     break
                 rows = ef[row_off[r]:row_off[r + 1]]
+                if len(rows) == 0:   # the scan walks rows: a region without rows is never met, here neither
+                    continue
                 if inclusive:
                     inside = bool(numpy.all(rows[:, 1:] @ th <= rows[:, 0] + tol))
                 else:

@@ -1,13 +1,16 @@
-"""Search trees on the device: mpc_tree_build against the independent CPU reference, determinism, and tree location
-identical to the scan (and the walk where it applies) on solved programs."""
+"""Search trees on the device: mpc_tree_build against the independent CPU reference and its exact checker (check_tree:
+no region leaves a subtree that its points reach) on the cases and builder arguments of search_tree_cases.py, determinism, and tree
+location identical to the scan (and the walk where it applies) on witness points and on solved programs."""
 import warnings
 
 import numpy
 import pytest
 
+import search_tree_cases as stc
 import search_tree_reference as ref
 from ppopt_amd import _lib
 from ppopt_amd.upop import SearchTree
+from search_tree_cases import _random_polytopes
 from test_search_tree_cpu import CASES, _Prog, _region, reference_tree
 from ppopt_amd.solution import Solution
 
@@ -28,28 +31,12 @@ def test_device_tree_equals_the_reference(name):
     dev = sol.search_tree()
     assert dev.stats['pairs'] == len(sol.critical_regions) * len(dev.planes)
     assert numpy.array_equal(dev.planes, t['planes'])
-    if _knife_pairs(t, 16 * sol.point_location_tolerance) == 0:
-        for k in ('node_plane', 'node_child', 'node_off', 'items'):
-            assert numpy.array_equal(getattr(dev, k), t[k]), k
-        assert numpy.all(dev.node_tau >= t['tau_raw'] - 1e-12)
-        # the allowance grows with |o| and |theta*|_1: bounded by twice the reference's widened tau
-        assert numpy.all(dev.node_tau <= 2.0 * t['node_tau'] + 1e-12)
-
-
-def _random_polytopes(rng, n, m, R):
-    """R random polytopes with m rows in n dimensions around random centres, some with scaled and duplicate rows"""
-    regs = []
-    for r in range(R):
-        E = rng.normal(size=(m, n))
-        c = rng.normal(size=n) * (10.0 if r % 3 == 0 else 1.0)
-        f = E @ c + rng.uniform(0.1, 1.0, size=m)
-        if r % 4 == 1:
-            E[::2] *= 1e3
-            f[::2] *= 1e3
-        if r % 5 == 2:
-            E[1], f[1] = E[0], f[0]
-        regs.append(_region(E, f, rng))
-    return regs
+    assert _knife_pairs(t, 16 * sol.point_location_tolerance) == 0
+    for k in ('node_plane', 'node_child', 'node_off', 'items'):
+        assert numpy.array_equal(getattr(dev, k), t[k]), k
+    assert numpy.all(dev.node_tau >= t['tau_raw'] - 1e-12)
+    # the allowance grows with |o| and |theta*|_1: bounded by twice the reference's widened tau
+    assert numpy.all(dev.node_tau <= 2.0 * t['node_tau'] + 1e-12)
 
 
 @pytest.mark.parametrize('n,m,R', [(3, 8, 12), (6, 24, 10), (16, 40, 6), (4, 256, 3)])
@@ -58,10 +45,10 @@ def test_random_polytopes_against_the_reference(n, m, R):
     sol = Solution(_Prog(2, n, rng), _random_polytopes(rng, n, m, R), point_location_tolerance=1e-5)
     t = reference_tree(sol)
     dev = sol.search_tree()
-    if _knife_pairs(t, 16e-5) == 0:
-        for k in ('node_plane', 'node_child', 'node_off', 'items'):
-            assert numpy.array_equal(getattr(dev, k), t[k]), k
-        assert numpy.all(dev.node_tau >= t['tau_raw'] - 1e-12)
+    assert _knife_pairs(t, 16e-5) == 0
+    for k in ('node_plane', 'node_child', 'node_off', 'items'):
+        assert numpy.array_equal(getattr(dev, k), t[k]), k
+    assert numpy.all(dev.node_tau >= t['tau_raw'] - 1e-12)
     pts = numpy.vstack([rng.normal(size=(20000, n)) * 5.0] + [numpy.linalg.lstsq(cr.E, cr.f.ravel() - 0.05, rcond=None)[0] + rng.normal(size=(200, n)) * 1e-3
                                                                for cr in sol.critical_regions])
     for inclusive in (False, True):
@@ -74,6 +61,90 @@ def test_two_builds_are_identical():
     b = SearchTree.build(sol)
     for k in ('planes', 'node_plane', 'node_child', 'node_tau', 'node_off', 'items'):
         assert numpy.array_equal(getattr(a, k), getattr(b, k))
+
+
+# ---- soundness of device-built trees by the exact checker (search_tree_reference.check_tree, search_tree_cases.py) -----------------------
+_ARRAYS = ('planes', 'node_plane', 'node_child', 'node_tau', 'node_off', 'items')
+
+
+def _device_tree(name, leaf_size=1, max_depth=48, band=None, own=True):
+    """(SearchTree, arrays, stats) of a case built through Locator.build_tree with the case's plane list"""
+    c = stc.case(name)
+    band = c.band if band is None else band
+    cand = c.cand if own and c.cand is not None else (None, None)
+    loc = c.sol.locator()
+    stats = loc.build_tree(c.planes, cand[0], cand[1], c.tol, band, leaf_size, max_depth)
+    arrays = loc.get_tree()
+    tree = SearchTree(c.sol, arrays, c.tol, band, stats)
+    loc.tree_owner = tree
+    return tree, arrays, stats
+
+
+def _check_device_tree(name, leaf_size=1, max_depth=48, band=None, own=True):
+    c = stc.case(name)
+    t = stc.reference(name, leaf_size, max_depth, band, own)
+    tree, arrays, stats = _device_tree(name, leaf_size, max_depth, band, own)
+    rec = stc.check(name, arrays, leaf_size, max_depth, band, own)
+    print(name, leaf_size, max_depth, band, own, 'nodes', len(arrays['node_plane']), 'dropped', rec['dropped'], 'margin', rec['margin'],
+          {k: v for k, v in rec.items() if isinstance(v, list) and v})
+    assert rec['structure'] == []
+    assert rec['unsound'] == [] and rec['missing'] == [], 'the tree loses points of a region'
+    assert rec['not_one_sided'] == [] and rec['loose'] == [] and rec['stopped_early'] == []
+    assert numpy.array_equal(arrays['planes'], t['planes'])
+    for k in ('node_plane', 'node_child', 'node_off', 'items'):
+        assert numpy.array_equal(arrays[k], t[k]), k
+    assert stats['capped'] == 0
+    assert stats['pairs'] == c.n_regions * len(c.planes)
+    assert stats['tau_lps'] == rec['dropped']
+    return tree, arrays, rec
+
+
+@pytest.mark.parametrize('name', stc.NAMES)
+def test_device_tree_is_sound(name):
+    _, arrays, rec = _check_device_tree(name)
+    assert rec['dropped'] > 0 and rec['margin'] > 0.0
+    if name == 'planes_257':
+        assert arrays['node_plane'].max() >= 256, 'a winner of the second chunk of k_tree_split'
+    if name == 'edges':
+        leaves = numpy.flatnonzero(arrays['node_plane'] < 0)
+        for j in stc.EDGE_EMPTY + (stc.EDGE_NO_ROWS,):
+            assert all(j in arrays['items'][arrays['node_off'][k]:arrays['node_off'][k + 1]] for k in leaves)
+
+
+@pytest.mark.parametrize('leaf_size,max_depth,band,own', stc.ARGS)
+@pytest.mark.parametrize('name', stc.ARG_CASES)
+def test_device_tree_is_sound_for_every_builder_argument(name, leaf_size, max_depth, band, own):
+    _check_device_tree(name, leaf_size, max_depth, band, own)
+
+
+@pytest.mark.parametrize('name', stc.NAMES)
+def test_witness_points_are_located_as_the_scan_locates_them(name):
+    """the point of every dropped region farthest over its node's plane, pulled 1e-3 of the way to the region's centre: the first point a
+    short tau would lose"""
+    c = stc.case(name)
+    dev, arrays, _ = _device_tree(name)
+    pts, nodes, regions, with_dropped = stc.witnesses(name, arrays)
+    assert with_dropped and set(nodes.tolist()) == set(with_dropped)
+    sol, loc = c.sol, c.sol.locator()
+    for inclusive in (False, True):
+        want = sol.get_region_batch(pts, inclusive=inclusive)
+        assert (want >= 0).any()
+        assert numpy.array_equal(dev.locate_batch(pts, inclusive=inclusive), want), (name, inclusive)
+        assert numpy.array_equal([dev.locate(th, inclusive=inclusive) for th in pts], want), (name, inclusive)
+        half = 0.5 * c.tol
+        want = loc.query(pts, half, sol.is_overlapping, want_x=False, inclusive=inclusive)[0]
+        assert numpy.array_equal(loc.query(pts, half, sol.is_overlapping, want_x=False, inclusive=inclusive, tree=True)[0], want), (name, inclusive)
+        assert numpy.array_equal([dev.locate(th, inclusive=inclusive, tol=half) for th in pts], want), (name, inclusive)
+    if name == 'edges':   # empty regions are never located; the scan never meets the region without rows
+        assert not set(sol.get_region_batch(pts).tolist()) & set(stc.EDGE_EMPTY + (stc.EDGE_NO_ROWS,))
+
+
+def test_two_builds_of_a_deep_partition_are_identical_bytes():
+    a = _device_tree('part_2_6')[1]
+    b = _device_tree('part_2_6')[1]
+    assert len(a['node_plane']) == 127
+    for k in _ARRAYS:
+        assert a[k].tobytes() == b[k].tobytes(), k
 
 
 def _solve(name):

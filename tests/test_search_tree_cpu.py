@@ -1,6 +1,8 @@
 """Search trees without a device: trees built by the independent CPU reference (tests/search_tree_reference.py) on
 hand-built solutions, checked for their structure, for host descent equal to a numpy re-statement of the scan, and through the
-C++ / JavaScript export."""
+C++ / JavaScript export.  Then the exact checker of any builder's tree (search_tree_reference.check_tree) on the cases of
+search_tree_cases.py: reference trees pass it, every list of its record names the node of a planted defect, every case is knife-free,
+and the witness points of every dropped region are located as the scan locates them."""
 import hashlib
 import os
 import shutil
@@ -9,58 +11,14 @@ import subprocess
 import numpy
 import pytest
 
+import search_tree_cases as stc
 import search_tree_reference as ref
-from ppopt_amd.critical_region import CriticalRegion
 from ppopt_amd.solution import Solution
 from ppopt_amd.upop import SearchTree
 from ppopt_amd.upop.linear_code_gen import generate_code_cpp, generate_code_js, plane_table
+from search_tree_cases import _Prog, _region, _triangles
 
 TOL = 1e-5
-
-
-class _Prog:
-    def __init__(self, n_x, n_t, rng, quadratic=True):
-        self.c = rng.normal(size=(n_x, 1))
-        self.H = rng.normal(size=(n_x, n_t))
-        if quadratic:
-            M = rng.normal(size=(n_x, n_x))
-            self.Q = M @ M.T + numpy.eye(n_x)
-        self.c_c = numpy.zeros((1, 1))
-        self.c_t = numpy.zeros((n_t, 1))
-        self.Q_t = numpy.zeros((n_t, n_t))
-        self._nt = n_t
-
-    def num_t(self):
-        return self._nt
-
-    def evaluate_objective(self, x, th):
-        v = th.T @ self.H.T @ x + self.c.T @ x
-        if hasattr(self, 'Q'):
-            v = v + 0.5 * x.T @ self.Q @ x
-        return float(v[0, 0])
-
-
-def _region(E, f, rng, n_x=2):
-    E = numpy.asarray(E, float)
-    n_t = E.shape[1]
-    return CriticalRegion(rng.normal(size=(n_x, n_t)), rng.normal(size=(n_x, 1)), numpy.zeros((0, n_t)), numpy.zeros((0, 1)), E,
-                          numpy.asarray(f, float).reshape(-1, 1), [])
-
-
-def _triangles(rng, scale=1.0, centre=(0.0, 0.0), row_scales=None):
-    """the box [-1, 1]^2 (scaled, shifted) cut by its diagonals into four triangles"""
-    cx, cy = centre
-    tri = [([[0, 1], [1, -1], [-1, -1]], [1, 0, 0]), ([[1, 0], [-1, 1], [-1, -1]], [1, 0, 0]),
-           ([[0, -1], [-1, 1], [1, 1]], [1, 0, 0]), ([[-1, 0], [1, -1], [1, 1]], [1, 0, 0])]
-    regs = []
-    for k, (E, f) in enumerate(tri):
-        E = numpy.array(E, float)
-        f = numpy.array(f, float) * scale + E @ numpy.array([cx, cy])
-        if row_scales is not None:
-            s = numpy.array(row_scales[k % len(row_scales)], float)
-            E, f = E * s[:, None], f * s
-        regs.append(_region(E, f, rng))
-    return regs
 
 
 def cases():
@@ -252,3 +210,194 @@ def test_to_arrays_round_trip():
     for k in ('planes', 'node_plane', 'node_child', 'node_tau', 'node_off', 'items'):
         assert numpy.array_equal(getattr(tree, k), getattr(again, k))
     assert again.tol == tree.tol
+
+
+# ---- the exact checker (search_tree_reference.check_tree) and the cases of search_tree_cases.py ------------------------------------------
+_LISTS = ('structure', 'unsound', 'missing', 'not_one_sided', 'loose', 'stopped_early')
+
+
+def _clean(rec):
+    return {k: rec[k] for k in _LISTS if rec[k]}
+
+
+def _edited(t):
+    return {k: (v.copy() if isinstance(v, numpy.ndarray) else v) for k, v in t.items()}
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_hand_reference_trees_pass_the_checker(name):
+    sol = CASES[name]
+    ef, row_off, _ = sol._stacked()
+    _, start, plane_of, _ = plane_table(sol.critical_regions, sol.theta_dim())
+    for band in (None, 0.0, 0.1):
+        t = tree_of(name, band)
+        rec = ref.check_tree(t, ef, row_off, TOL, t['band'], t['classification'], 48, 1, (start, plane_of))
+        assert _clean(rec) == {}, (name, band)
+
+
+@pytest.mark.parametrize('name', stc.NAMES)
+def test_reference_trees_pass_the_checker(name):
+    t = stc.reference(name)
+    rec = stc.check(name, t)
+    assert _clean(rec) == {} and rec['dropped'] > 0
+    assert rec['margin'] >= ref.ALLOW   # the reference widens every bound by at least 1e-9
+    c = stc.case(name)
+    inner = t['node_plane'][t['node_plane'] >= 0]
+    assert inner.min() >= c.n_dummy, 'a dummy plane makes no progress'
+    if name == 'planes_257':
+        assert inner.max() >= 256, 'a winner of the second chunk'
+    if name == 'edges':   # an empty expanded polytope straddles every plane; so does the region without rows
+        leaves = numpy.flatnonzero(t['node_plane'] < 0)
+        for j in stc.EDGE_EMPTY + (stc.EDGE_NO_ROWS,):
+            assert all(j in t['items'][t['node_off'][k]:t['node_off'][k + 1]] for k in leaves)
+    if name == 'over_3_8':
+        assert numpy.isinf(t['classification'][2]).sum() + numpy.isinf(t['classification'][3]).sum() == 156
+
+
+@pytest.mark.parametrize('name', stc.ARG_CASES)
+def test_reference_trees_of_every_argument_pass_the_checker(name):
+    shapes = set()
+    for leaf, depth, band, own in stc.ARGS:
+        t = stc.reference(name, leaf, depth, band, own)
+        assert _clean(stc.check(name, t, leaf, depth, band, own)) == {}, (leaf, depth, band, own)
+        shapes.add((leaf, depth, len(t['node_plane'])))
+    assert len(set(s[2] for s in shapes)) > 2, 'the arguments change the tree'
+
+
+def test_a_flipped_classification_does_not_pass():
+    c = stc.case('part_3_5')
+    cls = stc.classification('part_3_5')
+    t = stc.reference('part_3_5')
+    h = t['node_plane'][0]
+    j = int(numpy.flatnonzero(cls[0][:, h] & ~cls[1][:, h])[0])   # "+" only at the root's plane
+    plus, minus = cls[0].copy(), cls[1].copy()
+    plus[j, h], minus[j, h] = False, True
+    flipped = ref.Classification((plus, minus) + tuple(cls[2:]))
+    bad = ref.build(c.ef, c.row_off, c.planes, c.cand[0], c.cand[1], c.tol, c.band, cls=flipped)
+    rec = stc.check('part_3_5', bad)
+    assert [e[:3] for e in rec['not_one_sided']] == [(0, 1, j)]
+    assert rec['unsound'] == []   # build() takes tau from the exact hi, so the tree is poor, not wrong
+
+
+def _planted():
+    """the (3, 5) reference tree, an inner node of it with leaves for children and a raw tau+ above zero"""
+    t = stc.reference('part_3_5')
+    plane, child = t['node_plane'], t['node_child']
+    k = next(int(k) for k in numpy.flatnonzero(plane >= 0) if numpy.all(plane[child[k]] < 0) and t['tau_raw'][k, 1] > 1e-8)
+    return t, k
+
+
+def test_the_checker_catches_a_short_tau():
+    t, k = _planted()
+    e = _edited(t)
+    e['node_tau'][k, 1] = t['tau_raw'][k, 1] - 2e-9
+    rec = stc.check('part_3_5', e)
+    assert rec['unsound'] and all(u[:2] == (k, 1) for u in rec['unsound'])
+    assert all(u[3] - u[4] == pytest.approx(2e-9, abs=1e-12) for u in rec['unsound'])
+    leaf = int(t['node_child'][k, 0])
+    assert rec['missing'] == [(leaf, u[2]) for u in rec['unsound']]
+    assert {x: rec[x] for x in _LISTS if x not in ('unsound', 'missing')} == {x: [] for x in _LISTS if x not in ('unsound', 'missing')}
+    e['node_tau'][k, 1] = t['tau_raw'][k, 1]   # the exact bound itself passes: the comparison has no margin either way
+    assert stc.check('part_3_5', e)['unsound'] == []
+
+
+def test_the_checker_catches_a_loose_tau():
+    t, k = _planted()
+    e = _edited(t)
+    e['node_tau'][k, 0] = 1.0
+    rec = stc.check('part_3_5', e)
+    assert [x[:3] for x in rec['loose']] == [(k, 0, 1.0)]
+    e['node_tau'][k, 0] = numpy.inf   # every bound of the partition is finite
+    assert [x[:2] for x in stc.check('part_3_5', e)['loose']] == [(k, 0)]
+    assert _clean(rec).keys() == {'loose'}
+
+
+def test_the_checker_catches_a_region_removed_from_a_leaf():
+    t, k = _planted()
+    leaf = int(t['node_child'][k, 1])
+    e = _edited(t)
+    at = int(t['node_off'][leaf])
+    j = int(t['items'][at])
+    e['items'] = numpy.delete(t['items'], at)
+    e['node_off'][leaf + 1:] -= 1
+    rec = stc.check('part_3_5', e)
+    assert rec['missing'] == [(leaf, j)]
+    assert len(rec['structure']) == 1 and 'not every region' in rec['structure'][0]
+
+
+def test_the_checker_catches_swapped_children():
+    t, k = _planted()
+    e = _edited(t)
+    e['node_child'][k] = t['node_child'][k][::-1]
+    rec = stc.check('part_3_5', e)
+    assert rec['unsound'] and {u[0] for u in rec['unsound']} == {k}
+    assert {u[0] for u in rec['not_one_sided']} == {k}
+    assert {m[0] for m in rec['missing']} == set(int(c) for c in t['node_child'][k])
+
+
+def test_the_checker_catches_a_build_cut_short():
+    t = stc.reference('part_3_5', 1, 2, stc.BAND, True)
+    assert _clean(stc.check('part_3_5', t, 1, 2)) == {}
+    rec = stc.check('part_3_5', t, 1, 48)
+    leaves = numpy.flatnonzero(t['node_plane'] < 0)
+    assert [s[0] for s in rec['stopped_early']] == [int(k) for k in leaves if t['node_off'][k + 1] - t['node_off'][k] > 1]
+    assert len(rec['stopped_early']) == 4
+    assert [s[0] for s in stc.check('part_3_5', t, 8, 48)['stopped_early']] == []
+
+
+def test_the_checker_catches_broken_arrays():
+    t, k = _planted()
+    e = _edited(t)
+    e['node_child'][k, 0] = k
+    assert any('after their parent' in m for m in stc.check('part_3_5', e)['structure'])
+    e = _edited(t)
+    e['node_off'][-1] += 1
+    assert any('node_off' in m for m in stc.check('part_3_5', e)['structure'])
+    t2 = stc.reference('over_3_8')
+    e = _edited(t2)
+    leaf = next(int(q) for q in numpy.flatnonzero(t2['node_plane'] < 0) if t2['node_off'][q + 1] - t2['node_off'][q] > 1)
+    a = int(t2['node_off'][leaf])
+    e['items'][[a, a + 1]] = t2['items'][[a + 1, a]]
+    assert stc.check('over_3_8', e)['structure'] == [f'leaf {leaf}: the list does not ascend']
+
+
+def _bands(name):
+    return stc.BANDS if name in stc.ARG_CASES else (stc.case(name).band,)
+
+
+@pytest.mark.parametrize('name', stc.NAMES)
+def test_cases_are_knife_free(name):
+    """the reference alone reports no pair within 1e-9 of -band / +band: the device tests compare structures without an if"""
+    for band in _bands(name):
+        count, nearest = ref.knife_pairs(stc.classification(name, band), band)
+        assert count == 0 and nearest > 1e-6, (name, band, nearest)
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_hand_cases_are_knife_free(name):
+    for band in (None, 0.0, 0.1):
+        t = tree_of(name, band)
+        assert ref.knife_pairs(t['classification'], t['band'])[0] == 0
+
+
+@pytest.mark.parametrize('name', stc.NAMES)
+def test_witness_points_are_located_as_the_scan_locates_them(name):
+    c = stc.case(name)
+    t = stc.reference(name)
+    pts, nodes, regions, with_dropped = stc.witnesses(name, t)
+    assert with_dropped and set(nodes.tolist()) == set(with_dropped), 'a point for every inner node that drops a region'
+    tree = SearchTree.from_arrays(c.sol, t)
+    P = c.sol.program
+    met = 0
+    for inclusive in (False, True):
+        for tol in (c.tol, 0.5 * c.tol):
+            for th, j in zip(pts, regions):
+                want = ref.scan(c.ef, c.row_off, c.xlaw, th, tol, c.sol.is_overlapping, inclusive, getattr(P, 'Q', None), P.c, P.H)
+                assert tree.locate(th, inclusive=inclusive, tol=tol) == want, (name, th, inclusive, tol)
+                met += want >= 0
+    assert met > 0
+    # at the build tolerance every witness lies in its own region, strictly: the scan finds that region or one listed before it
+    inside = [numpy.all(c.ef[c.row_off[j]:c.row_off[j + 1], 1:] @ th - c.ef[c.row_off[j]:c.row_off[j + 1], 0] < c.tol) for th, j in zip(pts, regions)]
+    unit = numpy.all(numpy.linalg.norm(c.ef[:, 1:], axis=1) <= 1.0 + 1e-12)
+    assert all(inside) or not unit
+    assert any(inside)
